@@ -44,6 +44,24 @@ def spmv_bytes(nnz, nrows, ncols):
     return 12 * nnz + 4 * (nrows + 1) + 8 * ncols + 8 * nrows
 
 
+DUMP_MAX_ENTRIES = 1 << 21  # --dump-outputs: at most 16.8 MB of y, plus as much again for the sampled row numbers
+
+
+def dump_outputs(out_dir, y):
+    """y (a host float64 array) as out_dir/y.npy: whole when it is small, else a sorted sample of
+    DUMP_MAX_ENTRIES rows drawn with a fixed seed, whose row numbers go to out_dir/y_rows.npy (float64, exact)"""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    rows_path = os.path.join(out_dir, "y_rows.npy")
+    if os.path.exists(rows_path):
+        os.remove(rows_path)
+    if y.size > DUMP_MAX_ENTRIES:
+        rows = np.sort(np.random.default_rng(0x5EED).choice(y.size, DUMP_MAX_ENTRIES, replace=False))
+        np.save(rows_path, rows.astype(np.float64))
+        y = y[rows]
+    np.save(os.path.join(out_dir, "y.npy"), np.ascontiguousarray(y, dtype=np.float64))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -66,7 +84,13 @@ def main():
                          "separated: banded, c4[:<scale>], c5:<m>[:cpu<ms>], zi:<m>, feast:<m>, spmv:poisson3d:<m>, spmv:rmat:<scale>); the "
                          "200^3 factorisation comes first: it asks the driver for 255 GB, and memory other configurations have "
                          "just released is still being wiped in the background (DESIGN.md, Device memory)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default="",
+                    help="after the timed region, write the y of the last timed step (rank 0) as DIR/y.npy, float64; "
+                         "when y has more than %d entries, a fixed seeded sample of them, with their row numbers in "
+                         "DIR/y_rows.npy" % DUMP_MAX_ENTRIES)
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # plain `python bench.py --gpus N`: start one rank per GPU ourselves.  A fresh child process runs the
@@ -332,6 +356,13 @@ def main():
             info = H0.info()
             elapsed = timed_region()
             exchange_failed = 0.0
+    if args.dump_outputs:
+        # the y of the last timed step, before anything below launches the kernels again (timed_region ended with a
+        # synchronise and, at N > 1, a barrier: every rank's rows are in).  No peer may store into rank 0's y until
+        # it has been copied out.
+        if rank == 0:
+            dump_outputs(args.dump_outputs, op.y_full.cpu().numpy())
+        barrier()
     ms_per_step = 1e3 * elapsed / args.steps
     value = B_total / (elapsed / args.steps) / 1e9
 

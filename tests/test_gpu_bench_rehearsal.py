@@ -223,3 +223,31 @@ def test_three_ranks_all_schedules(gpu):
     three = _run(3, args)
     assert three["n_gpus"] == 3 and three["y_sha1"] == one["y_sha1"]
     assert set(three["config"]["exchange_ms_per_step_by_chunks"]) == {"rccl1", "rccl2", "rccl4", "peer1", "peer2", "peer4"}
+
+
+def test_dump_outputs(gpu, tmp_path):
+    """--dump-outputs DIR: the y of the last timed step as DIR/y.npy (float64), from rank 0.  Under the reference
+    order it is the y the line fingerprints, the same for one rank and for two (over either exchange), and the same
+    from run to run; past 2^21 rows a fixed, seeded sample of it, with its row numbers in DIR/y_rows.npy"""
+    import hashlib
+
+    import numpy as np
+    args = ["--rows", "400000"]
+    one = _run(1, args + ["--dump-outputs", str(tmp_path / "one")])
+    y = np.load(tmp_path / "one" / "y.npy")
+    assert y.dtype == np.float64 and y.shape == (400000,) and not (tmp_path / "one" / "y_rows.npy").exists()
+    assert hashlib.sha1(y.tobytes()).hexdigest() == one["y_sha1"]
+    for exchange in ("rccl", "peer"):
+        d = tmp_path / ("two_" + exchange)
+        _run(2, args + ["--dump-outputs", str(d)], chunks=1, exchange=exchange)
+        assert np.array_equal(np.load(d / "y.npy"), y), exchange
+    # a larger y: a sample of 2^21 rows, drawn the same way every run
+    args = ["--rows", "2400000"]
+    runs = []
+    for name in ("a", "b"):
+        _run(1, args + ["--dump-outputs", str(tmp_path / name)])
+        runs.append((np.load(tmp_path / name / "y.npy"), np.load(tmp_path / name / "y_rows.npy")))
+    (ya, ra), (yb, rb) = runs
+    assert ya.dtype == ra.dtype == np.float64 and ya.shape == ra.shape == (1 << 21,)
+    assert ra[0] >= 0 and ra[-1] < 2400000 and np.all(np.diff(ra) > 0) and np.all(ra == np.floor(ra))
+    assert np.array_equal(ra, rb) and np.array_equal(ya, yb)
