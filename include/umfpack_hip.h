@@ -70,6 +70,8 @@ extern "C" {
 
 #define UMFPACK_OK 0
 #define UMFPACK_WARNING_singular_matrix 1
+#define UMFPACK_WARNING_determinant_underflow 2
+#define UMFPACK_WARNING_determinant_overflow 3
 #define UMFPACK_ERROR_out_of_memory (-1)
 #define UMFPACK_ERROR_invalid_Numeric_object (-3)
 #define UMFPACK_ERROR_invalid_Symbolic_object (-4)
@@ -170,6 +172,40 @@ int spl_umfpack_stats(void *Numeric, double out[8]);
  * matrix-vector product): bytes of device memory, milliseconds their construction took, pivots per block (0: none).
  * Returns 0, or -1 if the object is invalid. */
 int spl_umfpack_solve_report(void *Numeric, double out[8]);
+
+/* ---- determinant -----------------------------------------------------------------------------
+ * Read from the factors a Numeric object holds, without the matrix (UMFPACK's umfpack_di_get_determinant).  Every
+ * path's own bookkeeping enters: the sign of the row interchanges of the band with partial pivoting and of the threshold
+ * pivoting inside the diagonal blocks of the fronts, and for static pivoting (factors of B = Dr P A Dc) the sign of P and
+ * the products of the scalings; the symmetric orderings contribute nothing.  The pivots are reduced on the device in one
+ * pass as a mantissa and a binary exponent (no overflow), in a fixed order: two calls on the same factors give the same
+ * bits.  Factors that are still an unchecked speculation (paths 2, 4, 5 before a solve has accepted them) first go
+ * through the check a solve makes, with a fixed right-hand side, under the same turns a solve takes; that check may
+ * replace them through the usual fallbacks, and the determinant is then that of the replacement.  The check is made
+ * once per set of factors and leaves spl_umfpack_solve_report describing the caller's last solve.  Accepting the
+ * factors this way does NOT end their speculation for the solves: those keep checking every right-hand side (and
+ * keep their longer refinement), exactly as without a determinant call, so a later solve whose right-hand side the
+ * factors fail can still replace them — a determinant returned before then is that of the factors it was read from,
+ * and the next call reads (and first checks) the replacement.  A factorisation with an inf or NaN pivot cannot be
+ * read: UMFPACK_ERROR_invalid_Numeric_object.
+ * umfpack_di_get_determinant: with Ex, det = Mx 10^Ex, 1 <= |Mx| < 10, Ex integral (0 and 0 when det = 0); without
+ * Ex, *Mx = det, +-inf with UMFPACK_WARNING_determinant_overflow or 0 with UMFPACK_WARNING_determinant_underflow
+ * when it is out of range.  A zero pivot: det = 0, UMFPACK_WARNING_singular_matrix.  Rectangular objects:
+ * UMFPACK_ERROR_invalid_system; Mx NULL: UMFPACK_ERROR_argument_missing; Info[0] gets the status when Info is given.
+ * umfpack_zi_get_determinant does not exist: where the native complex fronts are not used, a `zi` object factors the
+ * real 2n x 2n embedding, whose determinant is |det A|^2 — the phase of det A is not in those factors.  `zi` objects
+ * passed here return UMFPACK_ERROR_invalid_Numeric_object. */
+int umfpack_di_get_determinant(double *Mx, double *Ex, void *Numeric, double Info[]);
+
+/* sign in {-1, 0, +1} and log_abs = ln |det A| (-inf when singular): never overflows (numpy's slogdet).  Status as
+ * umfpack_di_get_determinant. */
+int spl_umfpack_di_log_determinant(void *Numeric, double *sign, double *log_abs);
+
+/* inertia of a SYMMETRIC matrix: out = (positive, negative, zero) eigenvalue counts, by Sylvester's law, from the
+ * pivots — only when the factors held are a congruence of A: A == A^T, no interchanges, no scaling (paths 1 - 4 with
+ * spl_umfpack_stats flag bit 1 clear).  Otherwise (paths 0 and 5, block pivoting, unsymmetric A, a zero pivot) it
+ * returns UMFPACK_ERROR_invalid_system and out = (-1, -1, -1): it never guesses.  Errors as above. */
+int spl_umfpack_inertia(void *Numeric, double out[3]);
 
 #ifdef __cplusplus
 }

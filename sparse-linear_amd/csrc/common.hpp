@@ -272,6 +272,17 @@ int mf_singular(const mf::Factors *F);
 void mf_chain_info(const mf::Factors *F, double out[3]);
 void mf_solve(const mf::Factors *F, int sys, double *d_c, int k, size_t stride, hipStream_t s);
 void mf_free(mf::Factors *F);
+// where the pivots of multifrontal factors lie (determinant.hip reads them): pivot g (new ordering) of real fronts is
+// arena[poff[f] + j (ldp[f] + 1)], f = front_of[g], j = g - p0[f]; the inverse of diagonal block b of front f (threshold
+// pivoting: inv(L11) P_b) is at invs + ioff[f] + b 2 64 64.  Device pointers except the host tree.
+struct MfPivots {
+  const mf::Tree *tree;
+  int zm;  // 2: complex fronts (not served)
+  const double *arena, *invs;
+  const int *front_of, *p0, *ldp;
+  const int64_t *poff;
+};
+MfPivots mf_pivots(const mf::Factors *F);
 
 // ---- SpGEMM (spgemm.hip) ------------------------------------------------------------------
 void spgemm_device(int64_t nrowsA, int64_t ncolsA, const int *Ap, const int *Ai, const double *Ax,
@@ -332,5 +343,20 @@ void choose_panels(const Matrix *m, int *rows_per_panel, int *w, int *nslices);
 int spmv_kernel_in_use(const Matrix *m);
 bool panels_pay(const Matrix *m);
 bool panels_beat_stream(const Matrix *m);  // order-free mode: the panel image instead of the CSR-stream kernel
+
+// ---- pivot products (determinant.hip) ---------------------------------------------------------
+// product of |pivot| over the non-zero finite pivots = m 2^e (m in [0.5, 1)); neg / zero / bad: pivots < 0 / == 0 /
+// inf or NaN
+struct DetResult {
+  double m;
+  int64_t e;
+  int64_t neg, zero, bad;
+};
+DetResult det_pivots_strided(int64_t n, const double *d_diag, int64_t stride, hipStream_t s);
+DetResult det_pivots_tree(int64_t n, const double *d_arena, const int *d_front_of, const int *d_p0, const int *d_ldp,
+                          const int64_t *d_poff, hipStream_t s);
+// parity (0 / 1) of all row interchanges of the threshold pivoting inside diagonal blocks: slot[b] = offset of the stored
+// inv(L11) P_b of block b in d_invs, jb[b] its pivots
+int block_pivot_parity(const double *d_invs, const std::vector<int64_t> &slot, const std::vector<int> &jb, hipStream_t s);
 
 }  // namespace spl

@@ -1145,6 +1145,11 @@ void mf_free(mf::Factors *F) { delete F; }
 
 int mf_singular(const mf::Factors *F) { return F->singular; }
 
+MfPivots mf_pivots(const mf::Factors *F) {
+  const TreeView &v = F->view;
+  return MfPivots{F->tree.get(), F->zm, F->arena.get(), F->invs.get(), v.front_of, v.p0, v.ldp, v.poff};
+}
+
 void mf_chain_info(const mf::Factors *F, double out[3]) {
   out[0] = out[1] = out[2] = 0.0;
   for (const mf::Factors::Chain *c : {&F->chain, &F->chain_t})  // (both sets, where both systems have been solved)

@@ -26,6 +26,7 @@
 #include <algorithm>
 #include <atomic>
 #include <chrono>
+#include <cmath>
 #include <future>
 #include <mutex>
 #include <vector>
@@ -98,6 +99,13 @@ struct Numeric {
   // speculation; solve checks the backward error it computes anyway and, if it is not at
   // rounding level, refactors with partial pivoting (under `mu`) and solves again
   std::atomic<int> speculative{0};
+  // 1: the factors held passed the acceptance check a solve runs, made by a determinant call (umfpack_di_get_determinant
+  // and the like) on a speculative object: later determinant calls need only the pivot reduction.  Cleared whenever the
+  // factors are rebuilt.  Solves keep checking as before (speculative is left as it is: ending it would cut their
+  // refinement from 10 steps to 2 and their fallbacks off), so a later solve may still replace factors accepted here.
+  std::atomic<int> det_checked{0};
+  // 1: the real embedding of a complex matrix (umfpack_zi.hip): its determinant is |det|^2 of the complex matrix
+  int embedding = 0;
   std::mutex mu;
   DBuf<double> AB;
   DBuf<double> blkinv;  // no-pivot path: inv(L11), inv(U11) of every diagonal block
@@ -672,9 +680,11 @@ __global__ __launch_bounds__(256) void same_csr_kernel(int64_t n, int64_t nnz, c
   if (bad) *differ = 1;
 }
 
-static bool matrix_is_symmetric(const Numeric *N, hipStream_t s) {
+// honour_env = false: the fact itself, whatever SPL_LU_SYMMETRIC says (the inertia needs the fact, not the choice of
+// factorisation)
+static bool matrix_is_symmetric(const Numeric *N, hipStream_t s, bool honour_env = true) {
   const char *e = getenv("SPL_LU_SYMMETRIC");
-  if (e && e[0] == '0') return false;
+  if (honour_env && e && e[0] == '0') return false;
   const Matrix *A = N->A, *At = N->At;
   if (!A || !At || A->nnz != At->nnz || !A->rowptr.get() || !At->rowptr.get()) return false;
   DBuf<int> differ(1);
@@ -711,6 +721,7 @@ static size_t tree_factor_bytes(const Numeric *N) {
 
 // multifrontal factors without interchanges on the nested-dissection tree (multifrontal.hip)
 void factor_multifrontal(Numeric *N, hipStream_t s) {
+  N->det_checked = 0;
   N->AB.release();
   N->blkinv.release();
   if (N->mfact) { mf_free(N->mfact); N->mfact = nullptr; }
@@ -760,6 +771,7 @@ bool factor_static_pivot(Numeric *N, const int *Ap, const int *Ai, const double 
   const char *off = getenv("SPL_LU_STATIC_PIVOT");
   if (off && off[0] == '0') return false;
   N->sp_stage = 2;  // whatever happens below, it is not tried twice
+  N->det_checked = 0;
   const bool timing = getenv("SPL_MF_TIMING") != nullptr;
   const auto t_begin = std::chrono::steady_clock::now();
   auto since = [&] { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_begin).count(); };
@@ -872,6 +884,7 @@ static void ensure_band_ordering(Numeric *N, hipStream_t s) {
 
 void factor_band(Numeric *N, bool nopiv, hipStream_t s) {
   const int n = N->n;
+  N->det_checked = 0;
   ensure_band_ordering(N, s);
   // Will the band fit?  Decided BEFORE anything of the current factors is released: a band that does not
   // fit (a large 3-D matrix whose speculation failed) must leave the object as it was — its speculative
@@ -1337,6 +1350,7 @@ int umfpack_di_numeric(const int Ap[], const int Ai[], const double Ax[], void *
       return UMFPACK_ERROR_internal_error;
     }
     N = new Numeric();
+    N->embedding = t_pattern_vouched ? 1 : 0;
     SPL_HIP(hipGetDevice(&N->device));
     // the calling thread's default stream: ordered after and before work on the legacy default stream (the caller's
     // torch kernels, this library's other entry points) like the legacy stream itself, but factorisations and solves
@@ -1542,7 +1556,8 @@ static void gmres_polish(Numeric *N, int sys, const Matrix *op, const double *b,
 
 // device_io: X and B are device pointers (spl_umfpack_*_solve_many_dev), else host
 static int solve_columns(Numeric *N, int sys, int k, double *X, const double *B, const int *Ap, const int *Ai,
-                         const double *Ax, bool device_io = false, double *Info = nullptr) {
+                         const double *Ax, bool device_io = false, double *Info = nullptr,
+                         bool caller_holds_turn = false) {
   const int n = N->n;
   if (N->broken) return UMFPACK_ERROR_invalid_Numeric_object;  // a failed refactorisation left no factors
   try {
@@ -1580,7 +1595,7 @@ static int solve_columns(Numeric *N, int sys, int k, double *X, const double *B,
                            device_io ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, s));
     // speculative factors may be replaced below: solves on such an object take turns
     std::unique_lock<std::mutex> turn(N->mu, std::defer_lock);
-    if (N->speculative) turn.lock();
+    if (N->speculative && !caller_holds_turn) turn.lock();
     std::vector<double> omega((size_t)k, 0.0), on((size_t)k, 0.0);
     bool polished = false;
     int walks = 0, ir_taken = 0, ir_attempted = 0;
@@ -1705,7 +1720,7 @@ static int solve_columns(Numeric *N, int sys, int k, double *X, const double *B,
       double worst = 0.0;
       for (int c = 0; c < k; ++c) worst = (omega[(size_t)c] <= worst) ? worst : omega[(size_t)c];  // NaN -> worst
       delivered = worst;
-      if (turn.owns_lock() && N->speculative && !(worst <= 1e-13)) {
+      if ((turn.owns_lock() || caller_holds_turn) && N->speculative && !(worst <= 1e-13)) {
         // first the static-pivoting stage (stays on the tree, still checked by this very loop), then, if that
         // fails too, the band factorisation with partial pivoting
         // a symmetric matrix whose L D L^T speculation failed: the same tree once more as LU with threshold pivoting
@@ -1928,6 +1943,253 @@ int spl_umfpack_solve_report(void *NumericIn, double out[8]) {
   return 0;
 }
 
+}  // extern "C"
+
+// ---- determinant, log-determinant, inertia ---------------------------------------------------------------------
+// det A = sigma * prod(pivots) / prod(scales): the pivots come from the device in one pass (determinant.hip), sigma
+// and the scales from what each path keeps on the host side:
+//   orderings (RCM band_perm, nested dissection perm / inv) are symmetric: Q A Q^T has the determinant of A;
+//   band with partial pivoting: one sign per row interchange recorded in ipiv;
+//   fronts with threshold pivoting inside the diagonal blocks: the parity of the blocks' interchanges (folded into the
+//   stored inverses); rscale only ranks the candidates, it does not scale the stored factors;
+//   static pivoting: the factors are those of B = Dr P A Dc, so det A = sign(P) det B / (prod dr prod dc).
+namespace {
+
+struct DetValue {
+  int sign = 1;      // -1, 0, +1
+  double m = 0.5;    // |det| = m 2^e, m in [0.5, 1) (undefined when sign == 0)
+  int64_t e = 1;
+  int64_t neg = 0, zero = 0;  // negative / zero pivots
+  int64_t bad = 0;            // inf / NaN pivots: the factors cannot be read
+};
+
+// parity (0 / 1) of a permutation of 0 .. n-1, by its cycles
+int perm_parity(const std::vector<int> &p) {
+  std::vector<char> seen(p.size(), 0);
+  int odd = 0;
+  for (size_t i = 0; i < p.size(); ++i) {
+    if (seen[i]) continue;
+    size_t len = 0;
+    for (size_t j = i; !seen[j]; j = (size_t)p[j]) { seen[j] = 1; ++len; }
+    odd ^= (int)((len - 1) & 1);
+  }
+  return odd;
+}
+
+// product of non-zero x[i] as m 2^e, pairwise (the rounding grows with log2 n)
+void host_product(const std::vector<double> &x, double &m, int64_t &e) {
+  std::vector<double> pm(x.size());
+  std::vector<int64_t> pe(x.size());
+  for (size_t i = 0; i < x.size(); ++i) {
+    int ex = 0;
+    pm[i] = std::frexp(std::fabs(x[i]), &ex);
+    pe[i] = ex;
+  }
+  for (size_t w = 1; w < pm.size(); w *= 2)
+    for (size_t i = 0; i + w < pm.size(); i += 2 * w) {
+      int ex = 0;
+      pm[i] = std::frexp(pm[i] * pm[i + w], &ex);
+      pe[i] += pe[i + w] + ex;
+    }
+  m = pm.empty() ? 0.5 : pm[0];
+  e = pm.empty() ? 1 : pe[0];
+}
+
+template <typename T>
+std::vector<T> download(const T *d, size_t n, hipStream_t s) {
+  std::vector<T> h(n);
+  if (n) SPL_HIP(hipMemcpyAsync(h.data(), d, n * sizeof(T), hipMemcpyDeviceToHost, s));
+  SPL_HIP(hipStreamSynchronize(s));
+  return h;
+}
+
+// a fixed right-hand side for the acceptance check of speculative factors: values in [-1, 1) from a hash of the index
+std::vector<double> check_rhs(int n) {
+  std::vector<double> b((size_t)n);
+  for (int i = 0; i < n; ++i) {
+    uint64_t h = (uint64_t)i * 0x9E3779B97F4A7C15ull + 0x632BE59BD9B4E019ull;
+    h ^= h >> 29;
+    h *= 0xBF58476D1CE4E5B9ull;
+    h ^= h >> 32;
+    b[(size_t)i] = (double)(h >> 11) * (2.0 / 9007199254740992.0) - 1.0;
+  }
+  return b;
+}
+
+// The reduction over the factors N holds now.  The caller holds the object's turn when it is speculative.
+DetValue factor_determinant(Numeric *N, hipStream_t s) {
+  DetValue v;
+  const int n = N->n;
+  if (n == 0) return v;
+  int odd = 0;              // parity of the permutations
+  double sm = 0.5;          // prod of the scales = sm 2^se
+  int64_t se = 1;
+  DetResult r{};
+  if (N->mfact) {
+    const MfPivots P = mf_pivots(N->mfact);
+    r = det_pivots_tree(n, P.arena, P.front_of, P.p0, P.ldp, P.poff, s);
+    if (N->mf_piv && N->sp_stage != 1) {  // (the factors of static pivoting are built without interchanges)
+      std::vector<int64_t> slot;
+      std::vector<int> jb;
+      const mf::Tree &T = *P.tree;
+      for (int f = 0; f < T.nfronts; ++f)
+        for (int j0 = 0; j0 < T.np[(size_t)f]; j0 += mf::kBlock) {
+          slot.push_back(T.ioff[(size_t)f] + (int64_t)(j0 / mf::kBlock) * 2 * mf::kBlock * mf::kBlock);
+          jb.push_back(std::min(mf::kBlock, T.np[(size_t)f] - j0));
+        }
+      odd ^= block_pivot_parity(P.invs, slot, jb, s);
+    }
+    if (N->sp_stage == 1) {
+      // sp_idx[0][k] = row of A that became row pnd[k] of B, sp_idx[1] = B's inverse ordering (pnd^-1): the row
+      // permutation of B = Dr P A Dc is their composition, so its parity is the sum of theirs
+      odd ^= perm_parity(download(N->sp_idx[0].get(), (size_t)n, s));
+      odd ^= perm_parity(download(N->sp_idx[1].get(), (size_t)n, s));
+      // sp_scale[1][j] = dc_j and sp_scale[3][i] = dr_i, every index once
+      std::vector<double> scales = download(N->sp_scale[1].get(), (size_t)n, s);
+      const std::vector<double> dr = download(N->sp_scale[3].get(), (size_t)n, s);
+      scales.insert(scales.end(), dr.begin(), dr.end());
+      host_product(scales, sm, se);
+    }
+  } else if (N->nopiv) {
+    r = det_pivots_strided(n, N->AB.get() + N->ku, N->ldab, s);  // Band: A(j, j) = AB[ku + j ldab]
+  } else {
+    r = det_pivots_strided(n, N->AB.get() + N->kl + N->ku, N->ldab, s);  // LAPACK band LU: U(j, j) = AB[kl + ku + j ldab]
+    const std::vector<int> ipiv = download(N->ipiv.get(), (size_t)n, s);
+    for (int j = 0; j < n; ++j) odd ^= ipiv[(size_t)j] != j ? 1 : 0;
+  }
+  v.neg = r.neg;
+  v.zero = r.zero;
+  v.bad = r.bad;
+  if (r.bad > 0) return v;
+  if (r.zero > 0) { v.sign = 0; return v; }
+  v.sign = ((odd ^ (int)(r.neg & 1)) & 1) ? -1 : 1;
+  int ex = 0;
+  v.m = std::frexp(r.m / sm, &ex);
+  v.e = r.e - se + ex;
+  return v;
+}
+
+// Common front of the three calls: validation, the acceptance check of speculative factors, the reduction.
+// Returns a status (UMFPACK_OK or UMFPACK_WARNING_singular_matrix, or an error) and fills v; inertia also learns
+// whether the factors held are a congruence of A.
+int determinant_of(void *NumericIn, DetValue &v, bool *congruence) {
+  Numeric *N = as_numeric(NumericIn);
+  if (!N || N->broken || N->embedding) return UMFPACK_ERROR_invalid_Numeric_object;
+  if (N->rectangular) return UMFPACK_ERROR_invalid_system;
+  try {
+    DeviceGuard g(N->device);
+    hipStream_t s = hipStreamPerThread;
+    // the same turns as the solves: a speculative object may have its factors replaced by the check below, or by a
+    // solve on another thread while the pivots are read
+    std::unique_lock<std::mutex> turn(N->mu, std::defer_lock);
+    if (N->speculative) turn.lock();
+    if (N->speculative && !N->det_checked && !N->singular && N->n > 0) {
+      // factors nobody has accepted yet: the check of a solve, with a fixed right-hand side; it may replace them through
+      // the fallbacks (block pivoting retry, static pivoting, band with partial pivoting)
+      // (what spl_umfpack_solve_report describes stays the caller's last solve: the check is not one)
+      const int walks = N->last_walks, ir_taken = N->last_ir_taken, ir_attempted = N->last_ir_attempted;
+      const double omega = N->last_omega;
+      const std::vector<double> b = check_rhs(N->n);
+      std::vector<double> x((size_t)N->n);
+      const int st = solve_columns(N, UMFPACK_A, 1, x.data(), b.data(), nullptr, nullptr, nullptr, false, nullptr, true);
+      N->last_walks = walks;
+      N->last_ir_taken = ir_taken;
+      N->last_ir_attempted = ir_attempted;
+      N->last_omega = omega;
+      if (st < 0) return st;
+      N->det_checked = 1;
+    }
+    if (N->broken) return UMFPACK_ERROR_invalid_Numeric_object;
+    if (congruence) {
+      // a congruence of A: A symmetric, no interchanges, no scaling (paths 1 - 4 without block pivoting)
+      const bool no_interchanges = N->nopiv && N->sp_stage != 1 && !(N->mfact && N->mf_piv);
+      *congruence = no_interchanges && !N->singular && matrix_is_symmetric(N, s, false);
+    }
+    if (N->singular) {
+      v = DetValue{};
+      v.sign = 0;
+      return UMFPACK_WARNING_singular_matrix;
+    }
+    v = factor_determinant(N, s);
+    if (v.bad > 0) return UMFPACK_ERROR_invalid_Numeric_object;  // an inf or NaN pivot: nothing to report
+    return v.sign == 0 ? UMFPACK_WARNING_singular_matrix : UMFPACK_OK;
+  } catch (const DeviceError &e) {
+    return e.status == SPL_ERROR_out_of_memory ? UMFPACK_ERROR_out_of_memory : UMFPACK_ERROR_internal_error;
+  } catch (const std::bad_alloc &) {
+    return UMFPACK_ERROR_out_of_memory;
+  } catch (...) {
+    return UMFPACK_ERROR_internal_error;
+  }
+}
+
+}  // namespace
+
+extern "C" {
+
+int umfpack_di_get_determinant(double *Mx, double *Ex, void *NumericIn, double Info[]) {
+  int st;
+  DetValue v;
+  if (!Mx) st = UMFPACK_ERROR_argument_missing;
+  else st = determinant_of(NumericIn, v, nullptr);
+  if (st >= 0) {
+    if (v.sign == 0) {
+      *Mx = 0.0;
+      if (Ex) *Ex = 0.0;
+    } else if (Ex) {
+      // |det| = m 2^e = Mx 10^Ex with 1 <= |Mx| < 10; the exact double where det is one (exact powers of ten up to 1e22)
+      const double d = std::ldexp(v.m, (int)std::max<int64_t>(std::min<int64_t>(v.e, 4096), -4096));
+      double mx, ex;
+      if (std::isnormal(d) && d < 1e300 && d > 1e-300) {
+        ex = std::floor(std::log10(d));
+        const double p = std::pow(10.0, std::fabs(ex));
+        mx = ex >= 0 ? d / p : d * p;
+      } else {
+        const long double l = std::log10((long double)v.m) + (long double)v.e * 0.301029995663981195213738894724493027L;
+        const long double fl = std::floor(l);
+        ex = (double)fl;
+        mx = (double)std::pow(10.0L, l - fl);
+      }
+      if (mx >= 10.0) { mx /= 10.0; ex += 1.0; }
+      if (mx < 1.0) { mx *= 10.0; ex -= 1.0; }
+      *Mx = v.sign * mx;
+      *Ex = ex;
+    } else {
+      const double d = std::ldexp(v.m, (int)std::max<int64_t>(std::min<int64_t>(v.e, 4096), -4096));
+      *Mx = v.sign * d;
+      if (std::isinf(d)) st = UMFPACK_WARNING_determinant_overflow;
+      else if (d == 0.0) st = UMFPACK_WARNING_determinant_underflow;
+    }
+  }
+  if (Info) Info[0] = st;
+  return st;
+}
+
+int spl_umfpack_di_log_determinant(void *NumericIn, double *sign, double *log_abs) {
+  if (!sign || !log_abs) return UMFPACK_ERROR_argument_missing;
+  DetValue v;
+  const int st = determinant_of(NumericIn, v, nullptr);
+  if (st < 0) return st;
+  *sign = v.sign;
+  *log_abs = v.sign == 0 ? -HUGE_VAL
+                         : (double)(std::log((long double)v.m) + (long double)v.e * 0.693147180559945309417232121458176568L);
+  return st;
+}
+
+int spl_umfpack_inertia(void *NumericIn, double out[3]) {
+  if (!out) return UMFPACK_ERROR_argument_missing;
+  out[0] = out[1] = out[2] = -1.0;
+  DetValue v;
+  bool congruence = false;
+  const int st = determinant_of(NumericIn, v, &congruence);
+  if (st < 0) return st;
+  if (!congruence) return UMFPACK_ERROR_invalid_system;
+  const int n = spl_umfpack_dimension(NumericIn);
+  out[0] = (double)(n - v.neg - v.zero);
+  out[1] = (double)v.neg;
+  out[2] = (double)v.zero;
+  return st;
+}
+
 void umfpack_di_free_symbolic(void **SymbolicIO) {
   if (!SymbolicIO || !*SymbolicIO) return;
   Symbolic *S = as_symbolic(*SymbolicIO);
@@ -1962,6 +2224,8 @@ void umfpack_di_report_status(const double Control[], int status) {
   const char *msg = "unknown status";
   switch (status) {
     case UMFPACK_WARNING_singular_matrix: msg = "WARNING: matrix is singular"; break;
+    case UMFPACK_WARNING_determinant_underflow: msg = "WARNING: determinant underflow"; break;
+    case UMFPACK_WARNING_determinant_overflow: msg = "WARNING: determinant overflow"; break;
     case UMFPACK_ERROR_out_of_memory: msg = "ERROR: out of memory (band profile too wide for HBM)"; break;
     case UMFPACK_ERROR_invalid_Numeric_object: msg = "ERROR: Numeric object is invalid"; break;
     case UMFPACK_ERROR_invalid_Symbolic_object: msg = "ERROR: Symbolic object is invalid"; break;

@@ -19,6 +19,7 @@
 #include <stdexcept>
 #include <string>
 #include <tuple>
+#include <utility>
 #include <vector>
 
 #include "../../include/sparse_linear_hip.h"
@@ -378,5 +379,43 @@ inline std::vector<std::vector<double>> linearSolve(const Matrix &mat, const std
 
 // (<\>) (Umfpack.hs:48-50)
 inline std::vector<double> solve(const Matrix &mat, const std::vector<double> &b) { return linearSolve(mat, {b})[0]; }
+
+// det A = mantissa 10^exponent10, 1 <= |mantissa| < 10 (0, 0 when singular), from the factors
+// (umfpack_di_get_determinant; speculative factors are checked first, as a solve checks them)
+struct Determinant {
+  double mantissa = 0.0;
+  long exponent10 = 0;
+};
+inline Determinant determinant(const Factors &fact) {
+  double mx = 0.0, ex = 0.0;
+  const int st = umfpack_di_get_determinant(&mx, &ex, *fact.fnum, nullptr);
+  umfpack_di_report_status(nullptr, st);
+  if (st < 0) detail::oops("determinant", "umfpack_di_get_determinant failed");
+  return Determinant{mx, (long)ex};
+}
+// (sign, ln |det A|): numpy's slogdet (spl_umfpack_di_log_determinant)
+inline std::pair<int, double> logDeterminant(const Factors &fact) {
+  double sign = 0.0, logabs = 0.0;
+  const int st = spl_umfpack_di_log_determinant(*fact.fnum, &sign, &logabs);
+  umfpack_di_report_status(nullptr, st);
+  if (st < 0) detail::oops("logDeterminant", "spl_umfpack_di_log_determinant failed");
+  return {(int)sign, logabs};
+}
+// (positive, negative, zero) eigenvalue counts of a symmetric A whose factors are a congruence of it
+// (spl_umfpack_inertia); throws when they are not (interchanges, scalings, an unsymmetric matrix)
+struct Inertia {
+  long positive = 0, negative = 0, zero = 0;
+};
+inline Inertia inertia(const Factors &fact) {
+  double out[3];
+  const int st = spl_umfpack_inertia(*fact.fnum, out);
+  if (st == UMFPACK_ERROR_invalid_system)
+    detail::oops("inertia", "the factors held are not a congruence of A (see Factors::stats().path)");
+  umfpack_di_report_status(nullptr, st);
+  if (st < 0) detail::oops("inertia", "spl_umfpack_inertia failed");
+  return Inertia{(long)out[0], (long)out[1], (long)out[2]};
+}
+inline Determinant det(const Matrix &mat) { return determinant(factor(mat, analyze(mat))); }
+inline std::pair<int, double> slogdet(const Matrix &mat) { return logDeterminant(factor(mat, analyze(mat))); }
 
 }}}  // namespace Numeric::LinearAlgebra::Umfpack

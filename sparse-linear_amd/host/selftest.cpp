@@ -147,6 +147,23 @@ int main() {
     const U::Factors::Stats st = f.stats();
     EXPECT(st.n == 5 && st.path == 1 && st.kl == 0 && st.ku == 0 && st.fronts == 0 && st.device_bytes > 0);
   }
+  // det of the 1-D Laplacian tridiag(-1, 2, -1) of order n is n + 1; it is positive definite
+  {
+    const Int n = 999;
+    std::vector<std::tuple<Int, Int, double>> t;
+    for (Int i = 0; i < n; ++i) {
+      t.emplace_back(i, i, 2.0);
+      if (i > 0) { t.emplace_back(i, i - 1, -1.0); t.emplace_back(i - 1, i, -1.0); }
+    }
+    const Matrix L = fromTriples(n, n, t);
+    U::Factors f = U::factor(L, U::analyze(L));
+    const U::Determinant d = U::determinant(f);
+    EXPECT(d.mantissa >= 1.0 && d.mantissa < 10.0 && std::fabs(d.mantissa * std::pow(10.0, (double)d.exponent10) - 1000.0) < 1e-9);
+    const std::pair<int, double> sl = U::logDeterminant(f);
+    EXPECT(sl.first == 1 && std::fabs(sl.second - std::log(1000.0)) < 1e-12);
+    const U::Inertia in = U::inertia(f);
+    EXPECT(in.positive == n && in.negative == 0 && in.zero == 0);
+  }
   // work arrays of 256 KiB and more are kept for reuse (at most 2 GiB of them); releasing gives them back once
   EXPECT(U::releaseCachedMemory() <= (size_t)2 << 30);
   EXPECT(U::releaseCachedMemory() == 0);

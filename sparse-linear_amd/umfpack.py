@@ -70,6 +70,12 @@ def _declare():
     L.spl_umfpack_stats.argtypes = [vp, C.POINTER(C.c_double)]
     L.spl_umfpack_solve_report.restype = C.c_int
     L.spl_umfpack_solve_report.argtypes = [vp, C.POINTER(C.c_double)]
+    L.umfpack_di_get_determinant.restype = i
+    L.umfpack_di_get_determinant.argtypes = [dp, dp, vp, dp]
+    L.spl_umfpack_di_log_determinant.restype = i
+    L.spl_umfpack_di_log_determinant.argtypes = [vp, dp, dp]
+    L.spl_umfpack_inertia.restype = i
+    L.spl_umfpack_inertia.argtypes = [vp, dp]
     L._umf_declared = True
     return L
 
@@ -129,6 +135,21 @@ class Factors(_Handle):
         st["complex_fronts"] = flags & 1          # native complex fronts (zi objects)
         st["block_pivoting"] = (flags >> 1) & 1   # threshold pivoting inside the diagonal blocks of the fronts
         return st
+
+    @property
+    def determinant(self):
+        """(mantissa, exponent10) of det A (module function `determinant`)"""
+        return determinant(self)
+
+    @property
+    def logDeterminant(self):
+        """(sign, ln |det A|) (module function `logDeterminant`)"""
+        return logDeterminant(self)
+
+    @property
+    def inertia(self):
+        """(positive, negative, zero) eigenvalue counts (module function `inertia`)"""
+        return inertia(self)
 
     @property
     def solve_report(self):
@@ -270,3 +291,62 @@ def linearSolveManyDevice_(fact, mode, mat, B):
     _report("linearSolveManyDevice_: umfpack_solve", st)
     return X
 
+
+
+_PATH_NAMES = {0: "band LU with partial pivoting", 1: "band without interchanges", 2: "band without interchanges (speculation)",
+               3: "multifrontal without interchanges", 4: "multifrontal without interchanges (speculation)",
+               5: "multifrontal with static pivoting"}
+
+
+def _real_factors(fact, what):
+    if fact.complex:
+        raise UmfpackError("%s: complex factors are not served — where the native complex fronts are not used they are "
+                           "the factors of the real 2n embedding, whose determinant is |det A|^2 and has lost the phase"
+                           % what)
+
+
+def determinant(fact):
+    """det A = mantissa * 10**exponent10 with 1 <= |mantissa| < 10 (0, 0 when singular), from the factors
+    (umfpack_di_get_determinant); factors that are still a speculation are checked first, as a solve checks them"""
+    _real_factors(fact, "determinant")
+    mx, ex = C.c_double(), C.c_double()
+    _report("determinant: umfpack_di_get_determinant",
+            _declare().umfpack_di_get_determinant(C.byref(mx), C.byref(ex), fact.value, None))
+    return mx.value, int(ex.value)
+
+
+def logDeterminant(fact):
+    """(sign, ln |det A|) with sign in {-1, 0, 1} (ln|det| = -inf when singular): numpy's slogdet, never overflows
+    (spl_umfpack_di_log_determinant)"""
+    _real_factors(fact, "logDeterminant")
+    sg, la = C.c_double(), C.c_double()
+    _report("logDeterminant: spl_umfpack_di_log_determinant",
+            _declare().spl_umfpack_di_log_determinant(fact.value, C.byref(sg), C.byref(la)))
+    return int(sg.value), la.value
+
+
+def inertia(fact):
+    """(positive, negative, zero) eigenvalue counts of a symmetric A (spl_umfpack_inertia) — only when the factors held
+    are a congruence of A (no interchanges, no scaling); raises UmfpackError naming what prevents it otherwise"""
+    _real_factors(fact, "inertia")
+    out = (C.c_double * 3)()
+    st = _declare().spl_umfpack_inertia(fact.value, out)
+    if st == -13:  # UMFPACK_ERROR_invalid_system: not a congruence of A
+        path = fact.path
+        why = _PATH_NAMES.get(path, "path %d" % path)
+        if path in (1, 2, 3, 4):
+            why += ", with threshold pivoting inside the diagonal blocks" if fact.stats["block_pivoting"] else \
+                ", of a matrix that is not symmetric (or singular)"
+        raise UmfpackError("inertia: the factors held (path %d: %s) are not a congruence of A" % (path, why), st)
+    _report("inertia: spl_umfpack_inertia", st)
+    return int(out[0]), int(out[1]), int(out[2])
+
+
+def det(mat):
+    """determinant of a real square matrix: analyse, factor, read the pivots; returns (mantissa, exponent10)"""
+    return determinant(factor(mat, analyze(mat)))
+
+
+def slogdet(mat):
+    """(sign, ln |det A|) of a real square matrix: analyse, factor, read the pivots"""
+    return logDeterminant(factor(mat, analyze(mat)))
