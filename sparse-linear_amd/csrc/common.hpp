@@ -207,26 +207,6 @@ void segmented_sort_pairs64(const int64_t *d_ptr64, int64_t nseg, int64_t *d_key
 void segmented_sort_pairs_u32(const int64_t *d_ptr64, int64_t nseg, unsigned *d_key, double *d_val,
                               hipStream_t s);
 // finish a Matrix whose rowptr64/colidx/val are filled: int32 pointers, stats
-// the `zi` wrapper's note on a `di` Numeric object: which row pairs of the embedding it swapped
-void numeric_set_pair_swap(void *Numeric, std::vector<char> &&flags);
-const std::vector<char> *numeric_pair_swap(void *Numeric);  // nullptr: none
-// ... and, for a complex symmetric matrix, the unit-modulus diagonal D = diag(u_r) of the congruence D A D it embedded
-// symmetrically (umfpack_zi.hip): n pairs (re, im)
-void numeric_set_pair_unit(void *Numeric, std::vector<double> &&u);
-const std::vector<double> *numeric_pair_unit(void *Numeric);  // nullptr: none
-// symbolic analysis of the real embedding of a complex matrix, ordered on the complex pattern (umfpack.hip)
-int symbolic_of_embedding(int n, const int *Ap, const int *Ai, const int *Ep, const int *Ei, void **Symbolic);
-double symbolic_tree_flops(void *Symbolic);  // LU flops of the multifrontal tree of a `di` analysis; 0: band path
-int numeric_of_embedding(const int *Ep, const int *Ei, const double *Ex, void *Symbolic, void **Numeric, int native = 0);
-bool symbolic_has_complex_tree(void *Symbolic);  // the analysis kept the tree of the complex pattern (native complex fronts possible)
-uint64_t pattern_hash(const int *Ai, int64_t nnz);
-// rectangular matrices (umfpack.hip, Symbolic::rectangular): analysed and "factored" as far as the reference's binding
-// can observe — statuses; solves return UMFPACK_ERROR_invalid_system as UMFPACK's do
-int symbolic_rectangular(int n_row, int n_col, const int *Ap, const int *Ai, void **Symbolic);
-bool symbolic_is_rectangular(void *Symbolic);
-int numeric_rectangular_of(void *Symbolic, const int *Ap, const int *Ai, const std::vector<char> &nonzero, void **Numeric,
-                           const double *re = nullptr, const double *im = nullptr, int vstride = 1);  // values: small matrices get their numerical rank
-bool numeric_is_rectangular(void *Numeric);
 void finalize_matrix(Matrix *m, hipStream_t s);
 int spmv_cus(const Matrix *m);  // CUs the persistent SpMV images are laid out for: the device's minus the reserved ones
 void measure_locality(Matrix *m, hipStream_t s);  // fills new_line_fraction on first call

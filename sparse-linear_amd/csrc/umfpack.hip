@@ -32,118 +32,10 @@
 #include <vector>
 
 #include <complex>
-#include "common.hpp"
-#include "mf_symbolic.hpp"
 #include "static_pivot.hpp"
-#include "../../include/umfpack_hip.h"
+#include "umfpack_impl.hpp"
 
 namespace spl {
-
-namespace {
-
-constexpr uint32_t kSymMagic = 0x53594D42u;  // "SYMB"
-constexpr uint32_t kNumMagic = 0x4E554D52u;  // "NUMR"
-
-struct Symbolic {
-  uint32_t magic = kSymMagic;
-  int n = 0;
-  int nnz = 0;
-  int kl = 0, ku = 0;
-  std::vector<int> perm;  // new -> old (reverse Cuthill-McKee: the band paths)
-  std::vector<int> inv;   // old -> new
-  std::vector<int> Ap;    // pattern check in numeric (UMFPACK_ERROR_different_pattern)
-  uint64_t ai_hash = 0;   // ... together with a hash of the row indices
-  // nested-dissection tree of the multifrontal path, present when that path is the cheaper one
-  std::shared_ptr<const mf::Tree> tree;
-  // embeddings of complex matrices (umfpack_zi.hip): the tree of the COMPLEX pattern itself, from the same dissection
-  // (tree is its expansion): what the native complex fronts are built on
-  std::shared_ptr<const mf::Tree> ztree;
-  bool have_band = false;  // perm / inv / kl / ku are set (large matrices whose tree wins by a lower bound skip them)
-  // Rectangular matrices (round 4).  UMFPACK analyses and factors them and refuses to SOLVE with them
-  // (UMFPACK_ERROR_invalid_system: "the matrix is not square"); through the reference's binding nothing of such a
-  // factorisation is observable but the statuses (Umfpack.hs:60-102 binds symbolic, numeric, solve and the frees).
-  // Here: the analysis records the shape and the pattern, the numeric call checks the pattern and reports whether a
-  // full set of min(n_row, n_col) non-zero pivots exists at all — the structural rank over the non-zero entries, where
-  // UMFPACK counts the non-zero pivots it found (UMFPACK_WARNING_singular_matrix otherwise) — and holds no factors;
-  // the solve returns UMFPACK_ERROR_invalid_system as UMFPACK's does.
-  int n_row = 0, n_col = 0;
-  bool rectangular = false;
-};
-
-struct Numeric {
-  uint32_t magic = kNumMagic;
-  int device = 0;
-  int n = 0, kl = 0, ku = 0, ldab = 1;
-  int singular = 0;
-  int rectangular = 0;  // 1: of a rectangular matrix (Symbolic::rectangular): no factors, solves return invalid_system
-  int nopiv = 0;  // 1: blocked factorisation without interchanges
-  int mf_sym = 0;  // 1: the multifrontal factors held are those of a symmetric matrix (L D L^T: half the update flops)
-  // Native complex fronts (round 3).  This object holds the real embedding E of a complex matrix (umfpack_zi.hip) for
-  // residuals, refinement and every fallback; with zfront = 1 the multifrontal factors are those of the COMPLEX matrix
-  // on the tree of its own pattern (ztree: half the unknowns, complex fronts in two planes, multifrontal.hip) — a
-  // solve with them is a solve with E (packed complex vectors ARE the real vectors of the embedding), at half the
-  // flops and bytes.  zsym: the complex matrix is symmetric (A == A^T): L D L^T.
-  std::shared_ptr<const mf::Tree> ztree;
-  int zfront = 0, zsym = 0;
-  // Threshold pivoting inside the diagonal blocks of the fronts (Band::piv): on for every matrix that is not
-  // diagonally dominant by columns — its factors without interchanges are a speculation, and the rows of a pivot block
-  // are free to change places.  A symmetric matrix is first tried as L D L^T (no interchanges: half the flops); if the
-  // check of a solve rejects those factors, the same tree is factored once more as LU with block pivoting
-  // (block_pivot_retry) before static pivoting takes over.  SPL_LU_BLOCK_PIVOT=0: never.
-  int dominant = 0, mf_piv = 0, block_pivot_retry = 0;
-  DBuf<double> rscale;  // row scales of the block pivoting (new ordering of the tree in use)
-  // set when a refactorisation failed after the previous factors were released: the object holds no
-  // usable factors any more and every later solve returns an error instead of launching kernels
-  std::atomic<int> broken{0};
-  // 1: the matrix is NOT diagonally dominant by columns and the no-interchange factors are a
-  // speculation; solve checks the backward error it computes anyway and, if it is not at
-  // rounding level, refactors with partial pivoting (under `mu`) and solves again
-  std::atomic<int> speculative{0};
-  // 1: the factors held passed the acceptance check a solve runs, made by a determinant call (umfpack_di_get_determinant
-  // and the like) on a speculative object: later determinant calls need only the pivot reduction.  Cleared whenever the
-  // factors are rebuilt.  Solves keep checking as before (speculative is left as it is: ending it would cut their
-  // refinement from 10 steps to 2 and their fallbacks off), so a later solve may still replace factors accepted here.
-  std::atomic<int> det_checked{0};
-  // 1: the real embedding of a complex matrix (umfpack_zi.hip): its determinant is |det|^2 of the complex matrix
-  int embedding = 0;
-  std::mutex mu;
-  DBuf<double> AB;
-  DBuf<double> blkinv;  // no-pivot path: inv(L11), inv(U11) of every diagonal block
-  DBuf<int> ipiv, perm, inv;
-  // multifrontal factors (then AB is empty and perm/inv hold the nested-dissection ordering); the
-  // band ordering is kept for the pivoting fallback
-  mf::Factors *mfact = nullptr;
-  std::shared_ptr<const mf::Tree> tree;
-  std::vector<int> band_perm, band_inv;
-  Matrix *A = nullptr;   // rows of A   (residual b - A x)
-  Matrix *At = nullptr;  // rows of A^T (residual b - A^T x)
-  // set by the `zi` wrapper (umfpack_zi.hip): rows 2r, 2r+1 of the real embedding were swapped
-  std::vector<char> pair_swap;
-  std::vector<double> pair_unit;  // zi wrapper, complex symmetric matrices: unit-modulus u_r (re, im) of the congruence D A D
-  // Static pivoting (static_pivot.hpp): 0 not tried, 1 the factors held are those of B = Dr P A Dc on B's own
-  // tree (still a checked speculation), 2 tried and given up.  spA / spAt: rows of B / of B^T on the device
-  // (what mf_factor scatters); sp_idx / sp_scale: the permutations and scalings around a solve with B's factors,
-  // composed with B's nested-dissection ordering — [0] before, [1] after A x = b; [2] before, [3] after A^T x = b.
-  int sp_stage = 0;
-  // the most recent solve call that finished on this object (spl_umfpack_solve_report; UMFPACK reports the like in
-  // Info[UMFPACK_IR_TAKEN .. UMFPACK_OMEGA1]): walks over the factors (first solve + refinement steps, whatever path),
-  // refinement steps kept / attempted, largest componentwise backward error among the delivered columns
-  std::atomic<int> last_walks{0}, last_ir_taken{0}, last_ir_attempted{0};
-  std::atomic<double> last_omega{0.0};
-  Matrix *spA = nullptr, *spAt = nullptr;
-  DBuf<int> sp_idx[4];
-  DBuf<double> sp_scale[4];
-  ~Numeric() {
-    delete A;
-    delete At;
-    delete spA;
-    delete spAt;
-    if (mfact) mf_free(mfact);
-  }
-};
-
-thread_local bool t_pattern_vouched = false;  // set around umfpack_di_numeric by spl::numeric_of_embedding
-thread_local int t_native_complex = 0;  // ... 1: the embedding is plain (no swapped pairs): native complex fronts may serve it; 2: and A == A^T
 
 // 64-bit hash of the row indices: the second half of the pattern check in numeric (the pointers are
 // compared exactly; a pattern with the same column counts but other rows would be scattered with a
@@ -160,6 +52,20 @@ uint64_t hash_indices(const int *Ai, int64_t nnz) {
   for (; p < nnz; ++p) { h[0] ^= (uint64_t)(uint32_t)Ai[p]; h[0] *= 0x100000001B3ull; h[0] ^= h[0] >> 29; }
   return (h[0] * 31 + h[1]) * 31 + (h[2] * 31 + h[3]) + (uint64_t)nnz;
 }
+
+int validate_host_csc(int n_row, int n_col, const int *Ap, const int *Ai) {
+  if (Ap[0] != 0) return UMFPACK_ERROR_invalid_matrix;
+  for (int j = 0; j < n_col; ++j) {
+    if (Ap[j] > Ap[j + 1]) return UMFPACK_ERROR_invalid_matrix;
+    for (int p = Ap[j]; p < Ap[j + 1]; ++p) {
+      if (Ai[p] < 0 || Ai[p] >= n_row) return UMFPACK_ERROR_invalid_matrix;
+      if (p > Ap[j] && Ai[p] <= Ai[p - 1]) return UMFPACK_ERROR_invalid_matrix;  // unsorted / duplicate
+    }
+  }
+  return UMFPACK_OK;
+}
+
+namespace {
 
 // ---- reverse Cuthill-McKee on the pattern of A + A^T (host) --------------------------------
 void rcm_order(int n, const int *Ap, const int *Ai, std::vector<int> &perm) {
@@ -592,27 +498,6 @@ __global__ __launch_bounds__(256) void axpby_kernel(size_t n, double alpha, cons
   if (i < n) y[i] = alpha * x[i] + (beta == 0.0 ? 0.0 : beta * y[i]);
 }
 
-inline Symbolic *as_symbolic(void *p) {
-  Symbolic *s = static_cast<Symbolic *>(p);
-  return (s && s->magic == kSymMagic) ? s : nullptr;
-}
-inline Numeric *as_numeric(void *p) {
-  Numeric *s = static_cast<Numeric *>(p);
-  return (s && s->magic == kNumMagic) ? s : nullptr;
-}
-
-int validate_host_csc(int n_row, int n_col, const int *Ap, const int *Ai) {
-  if (Ap[0] != 0) return UMFPACK_ERROR_invalid_matrix;
-  for (int j = 0; j < n_col; ++j) {
-    if (Ap[j] > Ap[j + 1]) return UMFPACK_ERROR_invalid_matrix;
-    for (int p = Ap[j]; p < Ap[j + 1]; ++p) {
-      if (Ai[p] < 0 || Ai[p] >= n_row) return UMFPACK_ERROR_invalid_matrix;
-      if (p > Ap[j] && Ai[p] <= Ai[p - 1]) return UMFPACK_ERROR_invalid_matrix;  // unsorted / duplicate
-    }
-  }
-  return UMFPACK_OK;
-}
-
 // columns of c (device, permuted order, column r at d_c + r * stride) <- solutions of B z = c or
 // B^T z = c; kalloc >= k columns are allocated (a multiple of kSolveGroup when k > 1)
 void band_solve(const Numeric *N, int sys, double *d_c, int k, size_t stride, hipStream_t s) {
@@ -954,18 +839,9 @@ void factor_band(Numeric *N, bool nopiv, hipStream_t s) {
 }
 
 }  // namespace
-}  // namespace spl
 
-using namespace spl;
-
-extern "C" {
-
-// The analysis behind umfpack_di_symbolic and, with mult = 2, umfpack_zi_symbolic: (Ap, Ai) is the n x n pattern
-// that is ORDERED; the object describes the (n mult) x (n mult) matrix of dense mult x mult blocks whose CSC
-// pattern is (Ep, Ei) — what numeric will be handed and checks against.  mult = 1: Ep = Ap, Ei = Ai.
-static int symbolic_common(int n, const int *Ap, const int *Ai, int mult, const int *Ep, const int *Ei,
-                           void **SymbolicOut) {
-  try {
+int symbolic_common(int n, const int *Ap, const int *Ai, int mult, const int *Ep, const int *Ei, Symbolic **SymbolicOut) {
+  return umf_guarded([&] {
     std::unique_ptr<Symbolic> S(new Symbolic());
     S->n = n * mult;
     S->nnz = Ep[S->n];
@@ -1100,19 +976,12 @@ static int symbolic_common(int n, const int *Ap, const int *Ai, int mult, const 
     }
     *SymbolicOut = S.release();
     return UMFPACK_OK;
-  } catch (const std::bad_alloc &) {
-    return UMFPACK_ERROR_out_of_memory;
-  } catch (...) {  // e.g. std::system_error from a thread that could not be started: never across the C ABI
-    return UMFPACK_ERROR_internal_error;
-  }
+  });
 }
 
-}  // extern "C"
-
-namespace spl {
 // analysis of a rectangular matrix: shape and pattern only (Symbolic::rectangular)
-int symbolic_rectangular(int n_row, int n_col, const int *Ap, const int *Ai, void **SymbolicOut) {
-  try {
+int symbolic_rectangular(int n_row, int n_col, const int *Ap, const int *Ai, Symbolic **SymbolicOut) {
+  return umf_guarded([&] {
     std::unique_ptr<Symbolic> S(new Symbolic());
     S->rectangular = true;
     S->n_row = n_row;
@@ -1123,11 +992,7 @@ int symbolic_rectangular(int n_row, int n_col, const int *Ap, const int *Ai, voi
     S->ai_hash = hash_indices(Ai, S->nnz);
     *SymbolicOut = S.release();
     return UMFPACK_OK;
-  } catch (const std::bad_alloc &) {
-    return UMFPACK_ERROR_out_of_memory;
-  } catch (...) {
-    return UMFPACK_ERROR_internal_error;
-  }
+  });
 }
 // size of a maximum matching of the columns to the rows over the entries keep[p] != 0: augmenting paths by depth-first
 // search with a look-ahead for free rows (Duff's MC21), iterative; O(n_col nnz) at worst, near-linear on what occurs
@@ -1224,11 +1089,11 @@ int dense_numeric_rank(int n_row, int n_col, const int *Ap, const int *Ai, const
 }
 
 // "factorisation" of a rectangular matrix: the pattern check and the status (Symbolic::rectangular)
-int numeric_rectangular(Symbolic *S, const int *Ap, const int *Ai, const std::vector<char> &nonzero, void **NumericOut,
-                        const double *re = nullptr, const double *im = nullptr, int vstride = 1) {
+int numeric_rectangular(Symbolic *S, const int *Ap, const int *Ai, const std::vector<char> &nonzero, Numeric **NumericOut,
+                        const double *re, const double *im, int vstride) {
   if (Ap[S->n_col] != S->nnz || !std::equal(S->Ap.begin(), S->Ap.end(), Ap) || hash_indices(Ai, S->nnz) != S->ai_hash)
     return UMFPACK_ERROR_different_pattern;
-  try {
+  return umf_guarded([&] {
     std::unique_ptr<Numeric> N(new Numeric());
     N->rectangular = 1;
     N->n = 0;
@@ -1245,27 +1110,11 @@ int numeric_rectangular(Symbolic *S, const int *Ap, const int *Ai, const std::ve
     const int st = N->singular ? UMFPACK_WARNING_singular_matrix : UMFPACK_OK;
     *NumericOut = N.release();
     return st;
-  } catch (const std::bad_alloc &) {
-    return UMFPACK_ERROR_out_of_memory;
-  } catch (...) {
-    return UMFPACK_ERROR_internal_error;
-  }
-}
-bool symbolic_is_rectangular(void *SymbolicIn) {
-  Symbolic *S = as_symbolic(SymbolicIn);
-  return S && S->rectangular;
-}
-int numeric_rectangular_of(void *SymbolicIn, const int *Ap, const int *Ai, const std::vector<char> &nonzero, void **NumericOut,
-                           const double *re, const double *im, int vstride) {
-  Symbolic *S = as_symbolic(SymbolicIn);
-  if (!S || !S->rectangular) return UMFPACK_ERROR_invalid_Symbolic_object;
-  return numeric_rectangular(S, Ap, Ai, nonzero, NumericOut, re, im, vstride);
-}
-bool numeric_is_rectangular(void *NumericIn) {
-  Numeric *N = as_numeric(NumericIn);
-  return N && N->rectangular;
+  });
 }
 }  // namespace spl
+
+using namespace spl;
 
 extern "C" {
 
@@ -1279,78 +1128,29 @@ int umfpack_di_symbolic(int n_row, int n_col, const int Ap[], const int Ai[], co
   if (Ap[n_col] < 0) return UMFPACK_ERROR_invalid_matrix;
   int st = validate_host_csc(n_row, n_col, Ap, Ai);
   if (st != UMFPACK_OK) return st;
-  if (n_row != n_col) return symbolic_rectangular(n_row, n_col, Ap, Ai, SymbolicOut);
-  return symbolic_common(n_col, Ap, Ai, 1, Ap, Ai, SymbolicOut);
+  Symbolic *S = nullptr;
+  st = n_row != n_col ? symbolic_rectangular(n_row, n_col, Ap, Ai, &S) : symbolic_common(n_col, Ap, Ai, 1, Ap, Ai, &S);
+  *SymbolicOut = S;
+  return st;
 }
 
 }  // extern "C"
 
 namespace spl {
-uint64_t pattern_hash(const int *Ai, int64_t nnz) { return hash_indices(Ai, nnz); }
 
-// numeric factorisation of an embedding whose pattern the caller has already checked against its own record
-// native: 0 the embedding has swapped pairs or scaled blocks (real fronts only); 1 it is the plain embedding of a complex
-// matrix (native complex fronts may serve it); 2 and that matrix is symmetric
-int numeric_of_embedding(const int *Ep, const int *Ei, const double *Ex, void *Symbolic, void **Numeric, int native) {
-  struct Vouch {
-    explicit Vouch(int native) { t_pattern_vouched = true; t_native_complex = native; }
-    ~Vouch() { t_pattern_vouched = false; t_native_complex = 0; }
-  } vouch(native);
-  return umfpack_di_numeric(Ep, Ei, Ex, Symbolic, Numeric, nullptr, nullptr);
-}
-// Native complex fronts serve this analysis?  They need the tree (of the complex pattern), and pay where the tree has
-// flops to halve: below ~1e12 flops of the embedding's tree (2-D meshes up to 10^6 unknowns) a factorisation is
-// launch-bound either way and a batch of right-hand sides takes twice the passes over the tree (four complex columns
-// per pass against eight real ones).  SPL_ZI_NATIVE=1 / 0: always / never.
-bool symbolic_has_complex_tree(void *SymbolicIn) {
-  Symbolic *S = as_symbolic(SymbolicIn);
-  if (!S || !S->tree || !S->ztree) return false;
-  const char *zn = getenv("SPL_ZI_NATIVE");
-  if (zn && zn[0] == '0') return false;
-  if (zn && zn[0] == '1') return true;
-  return S->tree->flops >= 1e12;
-}
-// analysis of the real embedding of an n x n complex matrix from the complex pattern itself (umfpack_zi.hip);
-// (Ep, Ei): the pattern of the embedding, 2n x 2n, interleaved unknowns
-int symbolic_of_embedding(int n, const int *Ap, const int *Ai, const int *Ep, const int *Ei, void **SymbolicOut) {
-  return symbolic_common(n, Ap, Ai, 2, Ep, Ei, SymbolicOut);
-}
-double symbolic_tree_flops(void *SymbolicIn) {
-  Symbolic *S = as_symbolic(SymbolicIn);
-  return S && S->tree ? S->tree->flops : 0.0;
-}
-}  // namespace spl
-
-extern "C" {
-
-int umfpack_di_numeric(const int Ap[], const int Ai[], const double Ax[], void *SymbolicIn,
-                       void **NumericOut, const double Control[], double Info[]) {
-  (void)Control; (void)Info;
-  if (!NumericOut) return UMFPACK_ERROR_argument_missing;
-  *NumericOut = nullptr;
-  Symbolic *S = as_symbolic(SymbolicIn);
-  if (!S) return UMFPACK_ERROR_invalid_Symbolic_object;
-  if (!Ap || !Ai || !Ax) return UMFPACK_ERROR_argument_missing;
-  if (S->rectangular) {
-    if (Ap[S->n_col] != S->nnz) return UMFPACK_ERROR_different_pattern;
-    std::vector<char> nonzero((size_t)S->nnz);
-    for (int p = 0; p < S->nnz; ++p) nonzero[(size_t)p] = (Ax[p] != 0.0 && Ax[p] == Ax[p]) ? 1 : 0;  // (NaN: no pivot)
-    return numeric_rectangular(S, Ap, Ai, nonzero, NumericOut, Ax, nullptr, 1);
-  }
+int numeric_factor(Symbolic *S, const int *Ap, const int *Ai, const double *Ax, EmbeddingOpts opts, Numeric **NumericOut) {
   const int n = S->n;
-  // (the `zi` wrapper has compared the complex pattern — a quarter of the embedding's — and vouches for the rest)
-  if (!t_pattern_vouched &&
-      (Ap[n] != S->nnz || !std::equal(S->Ap.begin(), S->Ap.end(), Ap) || hash_indices(Ai, S->nnz) != S->ai_hash))
-    return UMFPACK_ERROR_different_pattern;
-  Numeric *N = nullptr;
-  try {
+  return umf_guarded([&] {
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) {
       set_last_error_text("no HIP device visible");
       return UMFPACK_ERROR_internal_error;
     }
-    N = new Numeric();
-    N->embedding = t_pattern_vouched ? 1 : 0;
+    std::unique_ptr<Numeric> owned(new Numeric());
+    Numeric *N = owned.get();
+    N->embedding = opts.embedding ? 1 : 0;
+    N->pair_swap = std::move(opts.pair_swap);
+    N->pair_unit = std::move(opts.pair_unit);
     SPL_HIP(hipGetDevice(&N->device));
     // the calling thread's default stream: ordered after and before work on the legacy default stream (the caller's
     // torch kernels, this library's other entry points) like the legacy stream itself, but factorisations and solves
@@ -1372,14 +1172,10 @@ int umfpack_di_numeric(const int Ap[], const int Ai[], const double Ax[], void *
     void *hAt = nullptr;
     {
       int stc = spl_matrix_create_csr(n, n, 0, n, Ap, Ai, Ax, &hAt);
-      if (stc != SPL_OK) {
-        delete N;
-        return stc == SPL_ERROR_out_of_memory ? UMFPACK_ERROR_out_of_memory
-               : stc == SPL_ERROR_invalid_matrix ? UMFPACK_ERROR_invalid_matrix : UMFPACK_ERROR_internal_error;
-      }
+      if (stc != SPL_OK) return umf_status(stc);
     }
     N->At = static_cast<Matrix *>(hAt);
-    if (!N->At->rowptr.get()) { delete N; return UMFPACK_ERROR_out_of_memory; }
+    if (!N->At->rowptr.get()) return UMFPACK_ERROR_out_of_memory;
     lap("rows of A^T (upload)");
     N->ipiv.alloc((size_t)n);
     N->perm.alloc((size_t)n);
@@ -1387,12 +1183,9 @@ int umfpack_di_numeric(const int Ap[], const int Ai[], const double Ax[], void *
     N->band_perm = S->perm;  // (empty when the analysis skipped the band ordering: ensure_band_ordering)
     N->band_inv = S->inv;
     N->tree = S->tree;
-    {
-      const char *zn = getenv("SPL_ZI_NATIVE");  // 0: the real fronts of the embedding also for complex matrices
-      if (t_native_complex && S->tree && S->ztree && !(zn && zn[0] == '0')) {
-        N->ztree = S->ztree;
-        N->zsym = t_native_complex == 2 ? 1 : 0;
-      }
+    if (opts.native) {
+      N->ztree = S->ztree;
+      N->zsym = opts.zsym ? 1 : 0;
     }
     set_ordering(N, N->tree ? N->tree->perm : N->band_perm, N->tree ? N->tree->inv : N->band_inv, s);
     // device copies of A for the residuals of the refinement: rows of A (transposed on the
@@ -1404,9 +1197,7 @@ int umfpack_di_numeric(const int Ap[], const int Ai[], const double Ax[], void *
     int st = spl_matrix_transpose(hAt, &hA);
     if (st != SPL_OK) {
       spl_matrix_free(&hA);
-      delete N;
-      return st == SPL_ERROR_out_of_memory ? UMFPACK_ERROR_out_of_memory
-             : st == SPL_ERROR_invalid_matrix ? UMFPACK_ERROR_invalid_matrix : UMFPACK_ERROR_internal_error;
+      return umf_status(st);
     }
     N->A = static_cast<Matrix *>(hA);
     lap("ordering, rows of A");
@@ -1420,20 +1211,21 @@ int umfpack_di_numeric(const int Ap[], const int Ai[], const double Ax[], void *
       dominant = band_is_column_dominant(n, N->At->rowptr.get(), N->At->colidx.get(), N->At->val.get(), s);
     N->dominant = dominant ? 1 : 0;
     if (!force_pivot && (dominant || !no_speculation)) {
-      bool fits = true;
-      try {
-        if (!dominant && getenv("SPL_LU_TEST_SPECULATION_OOM")) throw DeviceError{SPL_ERROR_out_of_memory};  // tests: as if it did not fit
-        // the analysis left a region without separators as one giant leaf (Tree::gave_up): that front is not for
-        // factoring — straight to static pivoting, whose transversal gives the matrix its mesh pattern back
-        if (!dominant && N->tree && N->tree->gave_up) throw DeviceError{SPL_ERROR_out_of_memory};
-        if (N->tree) factor_multifrontal(N, s); else factor_band(N, true, s);
-      } catch (const DeviceError &e) {
-        // The speculation's own ordering does not fit the device: the pattern of A + A^T has no separators — e.g. a
-        // mesh matrix whose rows arrive in random order (tools/fuzz_lu_scale.py, family perm2d: 195 364 unknowns
-        // returned UMFPACK_ERROR_out_of_memory where SuperLU solved).  The transversal of static pivoting puts the
-        // large entries back on the diagonal and B = Dr P A Dc is ordered on its own pattern.
-        if (dominant || e.status != SPL_ERROR_out_of_memory) throw;
-        fits = false;
+      // SPL_LU_TEST_SPECULATION_OOM (tests): as if the speculation did not fit.  The analysis left a region without
+      // separators as one giant leaf (Tree::gave_up): that front is not for factoring — straight to static pivoting,
+      // whose transversal gives the matrix its mesh pattern back.
+      bool fits = dominant || !(getenv("SPL_LU_TEST_SPECULATION_OOM") || (N->tree && N->tree->gave_up));
+      if (fits) {
+        try {
+          if (N->tree) factor_multifrontal(N, s); else factor_band(N, true, s);
+        } catch (const DeviceError &e) {
+          // The speculation's own ordering does not fit the device: the pattern of A + A^T has no separators — e.g. a
+          // mesh matrix whose rows arrive in random order (tools/fuzz_lu_scale.py, family perm2d: 195 364 unknowns
+          // returned UMFPACK_ERROR_out_of_memory where SuperLU solved).  The transversal of static pivoting puts the
+          // large entries back on the diagonal and B = Dr P A Dc is ordered on its own pattern.
+          if (dominant || e.status != SPL_ERROR_out_of_memory) throw;
+          fits = false;
+        }
       }
       N->speculative = dominant ? 0 : 1;
       if (!fits || (N->speculative && N->singular)) {  // a zero pivot without interchanges proves nothing
@@ -1446,19 +1238,44 @@ int umfpack_di_numeric(const int Ap[], const int Ai[], const double Ax[], void *
       factor_band(N, false, s);
     }
     lap("factorisation");
-    *NumericOut = N;
+    *NumericOut = owned.release();
     return N->singular ? UMFPACK_WARNING_singular_matrix : UMFPACK_OK;
-  } catch (const DeviceError &e) {
-    delete N;
-    return e.status == SPL_ERROR_out_of_memory ? UMFPACK_ERROR_out_of_memory : UMFPACK_ERROR_internal_error;
-  } catch (const std::bad_alloc &) {
-    delete N;
-    return UMFPACK_ERROR_out_of_memory;
-  } catch (...) {
-    delete N;
-    return UMFPACK_ERROR_internal_error;
-  }
+  });
 }
+}  // namespace spl
+
+extern "C" {
+
+int umfpack_di_numeric(const int Ap[], const int Ai[], const double Ax[], void *SymbolicIn,
+                       void **NumericOut, const double Control[], double Info[]) {
+  (void)Control; (void)Info;
+  if (!NumericOut) return UMFPACK_ERROR_argument_missing;
+  *NumericOut = nullptr;
+  Symbolic *S = as_symbolic(SymbolicIn);
+  if (!S) return UMFPACK_ERROR_invalid_Symbolic_object;
+  if (!Ap || !Ai || !Ax) return UMFPACK_ERROR_argument_missing;
+  Numeric *N = nullptr;
+  int st;
+  if (S->rectangular) {
+    if (Ap[S->n_col] != S->nnz) return UMFPACK_ERROR_different_pattern;
+    st = umf_guarded([&] {
+      std::vector<char> nonzero((size_t)S->nnz);
+      for (int p = 0; p < S->nnz; ++p) nonzero[(size_t)p] = (Ax[p] != 0.0 && Ax[p] == Ax[p]) ? 1 : 0;  // (NaN: no pivot)
+      return numeric_rectangular(S, Ap, Ai, nonzero, &N, Ax, nullptr, 1);
+    });
+  } else {
+    const int n = S->n;
+    if (Ap[n] != S->nnz || !std::equal(S->Ap.begin(), S->Ap.end(), Ap) || hash_indices(Ai, S->nnz) != S->ai_hash)
+      return UMFPACK_ERROR_different_pattern;
+    st = numeric_factor(S, Ap, Ai, Ax, EmbeddingOpts{}, &N);
+  }
+  *NumericOut = N;
+  return st;
+}
+
+}  // extern "C"
+
+namespace spl {
 
 // k systems op(A) X(:,c) = B(:,c) with the factors of N; X, B are n x k column-major on the host.
 // Iterative refinement with UMFPACK's defaults and stopping rules, column by column (irstep = 2;
@@ -1555,12 +1372,11 @@ static void gmres_polish(Numeric *N, int sys, const Matrix *op, const double *b,
 }
 
 // device_io: X and B are device pointers (spl_umfpack_*_solve_many_dev), else host
-static int solve_columns(Numeric *N, int sys, int k, double *X, const double *B, const int *Ap, const int *Ai,
-                         const double *Ax, bool device_io = false, double *Info = nullptr,
-                         bool caller_holds_turn = false) {
+int solve_columns(Numeric *N, int sys, int k, double *X, const double *B, const int *Ap, const int *Ai,
+                  const double *Ax, bool device_io, double *Info, bool caller_holds_turn) {
   const int n = N->n;
   if (N->broken) return UMFPACK_ERROR_invalid_Numeric_object;  // a failed refactorisation left no factors
-  try {
+  return umf_guarded([&] {
     DeviceGuard g(N->device);
     // the calling thread's default stream: ordered after and before work on the legacy default stream (the caller's
     // torch kernels, this library's other entry points) like the legacy stream itself, but factorisations and solves
@@ -1801,14 +1617,11 @@ static int solve_columns(Numeric *N, int sys, int k, double *X, const double *B,
       Info[83] = 0.0;        // the denominator of a row with entries never vanishes unless its whole numerator does)
     }
     return N->singular ? UMFPACK_WARNING_singular_matrix : UMFPACK_OK;
-  } catch (const DeviceError &e) {
-    return e.status == SPL_ERROR_out_of_memory ? UMFPACK_ERROR_out_of_memory : UMFPACK_ERROR_internal_error;
-  } catch (const std::bad_alloc &) {
-    return UMFPACK_ERROR_out_of_memory;
-  } catch (...) {
-    return UMFPACK_ERROR_internal_error;
-  }
+  });
 }
+}  // namespace spl
+
+extern "C" {
 
 int umfpack_di_solve(int sys, const int Ap[], const int Ai[], const double Ax[], double X[],
                      const double B[], void *NumericIn, const double Control[], double Info[]) {
@@ -1851,27 +1664,6 @@ int spl_umfpack_di_solve_many_dev(int sys, const int Ap[], const int Ai[], const
   if (sys != UMFPACK_A && sys != UMFPACK_At) return UMFPACK_ERROR_invalid_system;
   return solve_columns(N, sys, nrhs, d_X, d_B, Ap, Ai, Ax, true);
 }
-
-}  // extern "C"
-
-namespace spl {
-void numeric_set_pair_swap(void *NumericIn, std::vector<char> &&flags) {
-  if (Numeric *N = as_numeric(NumericIn)) N->pair_swap = std::move(flags);
-}
-const std::vector<char> *numeric_pair_swap(void *NumericIn) {
-  Numeric *N = as_numeric(NumericIn);
-  return N && !N->pair_swap.empty() ? &N->pair_swap : nullptr;
-}
-void numeric_set_pair_unit(void *NumericIn, std::vector<double> &&u) {
-  if (Numeric *N = as_numeric(NumericIn)) N->pair_unit = std::move(u);
-}
-const std::vector<double> *numeric_pair_unit(void *NumericIn) {
-  Numeric *N = as_numeric(NumericIn);
-  return N && !N->pair_unit.empty() ? &N->pair_unit : nullptr;
-}
-}  // namespace spl
-
-extern "C" {
 
 // dimension of the factored system (used by the `zi` wrappers in split-array mode); 0 if invalid
 int spl_umfpack_dimension(void *NumericIn) {
@@ -2076,7 +1868,7 @@ int determinant_of(void *NumericIn, DetValue &v, bool *congruence) {
   Numeric *N = as_numeric(NumericIn);
   if (!N || N->broken || N->embedding) return UMFPACK_ERROR_invalid_Numeric_object;
   if (N->rectangular) return UMFPACK_ERROR_invalid_system;
-  try {
+  return umf_guarded([&] {
     DeviceGuard g(N->device);
     hipStream_t s = hipStreamPerThread;
     // the same turns as the solves: a speculative object may have its factors replaced by the check below, or by a
@@ -2113,13 +1905,7 @@ int determinant_of(void *NumericIn, DetValue &v, bool *congruence) {
     v = factor_determinant(N, s);
     if (v.bad > 0) return UMFPACK_ERROR_invalid_Numeric_object;  // an inf or NaN pivot: nothing to report
     return v.sign == 0 ? UMFPACK_WARNING_singular_matrix : UMFPACK_OK;
-  } catch (const DeviceError &e) {
-    return e.status == SPL_ERROR_out_of_memory ? UMFPACK_ERROR_out_of_memory : UMFPACK_ERROR_internal_error;
-  } catch (const std::bad_alloc &) {
-    return UMFPACK_ERROR_out_of_memory;
-  } catch (...) {
-    return UMFPACK_ERROR_internal_error;
-  }
+  });
 }
 
 }  // namespace

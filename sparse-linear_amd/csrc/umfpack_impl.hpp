@@ -1,0 +1,181 @@
+// umfpack_impl.hpp — the objects behind the UMFPACK handles and the internal calls between the real (`di`,
+// umfpack.hip) and the complex (`zi`, umfpack_zi.hip) halves of the ABI.  Included by those two files only.
+#pragma once
+#include <atomic>
+#include <memory>
+#include <mutex>
+#include <new>
+#include <vector>
+
+#include "common.hpp"
+#include "mf_symbolic.hpp"
+#include "../../include/umfpack_hip.h"
+
+namespace spl {
+
+constexpr uint32_t kSymMagic = 0x53594D42u;  // "SYMB"
+constexpr uint32_t kNumMagic = 0x4E554D52u;  // "NUMR"
+
+struct Symbolic {
+  uint32_t magic = kSymMagic;
+  int n = 0;
+  int nnz = 0;
+  int kl = 0, ku = 0;
+  std::vector<int> perm;  // new -> old (reverse Cuthill-McKee: the band paths)
+  std::vector<int> inv;   // old -> new
+  std::vector<int> Ap;    // pattern check in numeric (UMFPACK_ERROR_different_pattern)
+  uint64_t ai_hash = 0;   // ... together with a hash of the row indices
+  // nested-dissection tree of the multifrontal path, present when that path is the cheaper one
+  std::shared_ptr<const mf::Tree> tree;
+  // embeddings of complex matrices (umfpack_zi.hip): the tree of the COMPLEX pattern itself, from the same dissection
+  // (tree is its expansion): what the native complex fronts are built on
+  std::shared_ptr<const mf::Tree> ztree;
+  bool have_band = false;  // perm / inv / kl / ku are set (large matrices whose tree wins by a lower bound skip them)
+  // Rectangular matrices (round 4).  UMFPACK analyses and factors them and refuses to SOLVE with them
+  // (UMFPACK_ERROR_invalid_system: "the matrix is not square"); through the reference's binding nothing of such a
+  // factorisation is observable but the statuses (Umfpack.hs:60-102 binds symbolic, numeric, solve and the frees).
+  // Here: the analysis records the shape and the pattern, the numeric call checks the pattern and reports whether a
+  // full set of min(n_row, n_col) non-zero pivots exists at all — the structural rank over the non-zero entries, where
+  // UMFPACK counts the non-zero pivots it found (UMFPACK_WARNING_singular_matrix otherwise) — and holds no factors;
+  // the solve returns UMFPACK_ERROR_invalid_system as UMFPACK's does.
+  int n_row = 0, n_col = 0;
+  bool rectangular = false;
+};
+
+struct Numeric {
+  uint32_t magic = kNumMagic;
+  int device = 0;
+  int n = 0, kl = 0, ku = 0, ldab = 1;
+  int singular = 0;
+  int rectangular = 0;  // 1: of a rectangular matrix (Symbolic::rectangular): no factors, solves return invalid_system
+  int nopiv = 0;  // 1: blocked factorisation without interchanges
+  int mf_sym = 0;  // 1: the multifrontal factors held are those of a symmetric matrix (L D L^T: half the update flops)
+  // Native complex fronts (round 3).  This object holds the real embedding E of a complex matrix (umfpack_zi.hip) for
+  // residuals, refinement and every fallback; with zfront = 1 the multifrontal factors are those of the COMPLEX matrix
+  // on the tree of its own pattern (ztree: half the unknowns, complex fronts in two planes, multifrontal.hip) — a
+  // solve with them is a solve with E (packed complex vectors ARE the real vectors of the embedding), at half the
+  // flops and bytes.  zsym: the complex matrix is symmetric (A == A^T): L D L^T.
+  std::shared_ptr<const mf::Tree> ztree;
+  int zfront = 0, zsym = 0;
+  // Threshold pivoting inside the diagonal blocks of the fronts (Band::piv): on for every matrix that is not
+  // diagonally dominant by columns — its factors without interchanges are a speculation, and the rows of a pivot block
+  // are free to change places.  A symmetric matrix is first tried as L D L^T (no interchanges: half the flops); if the
+  // check of a solve rejects those factors, the same tree is factored once more as LU with block pivoting
+  // (block_pivot_retry) before static pivoting takes over.  SPL_LU_BLOCK_PIVOT=0: never.
+  int dominant = 0, mf_piv = 0, block_pivot_retry = 0;
+  DBuf<double> rscale;  // row scales of the block pivoting (new ordering of the tree in use)
+  // set when a refactorisation failed after the previous factors were released: the object holds no
+  // usable factors any more and every later solve returns an error instead of launching kernels
+  std::atomic<int> broken{0};
+  // 1: the matrix is NOT diagonally dominant by columns and the no-interchange factors are a
+  // speculation; solve checks the backward error it computes anyway and, if it is not at
+  // rounding level, refactors with partial pivoting (under `mu`) and solves again
+  std::atomic<int> speculative{0};
+  // 1: the factors held passed the acceptance check a solve runs, made by a determinant call (umfpack_di_get_determinant
+  // and the like) on a speculative object: later determinant calls need only the pivot reduction.  Cleared whenever the
+  // factors are rebuilt.  Solves keep checking as before (speculative is left as it is: ending it would cut their
+  // refinement from 10 steps to 2 and their fallbacks off), so a later solve may still replace factors accepted here.
+  std::atomic<int> det_checked{0};
+  // 1: the real embedding of a complex matrix (umfpack_zi.hip): its determinant is |det|^2 of the complex matrix
+  int embedding = 0;
+  std::mutex mu;
+  DBuf<double> AB;
+  DBuf<double> blkinv;  // no-pivot path: inv(L11), inv(U11) of every diagonal block
+  DBuf<int> ipiv, perm, inv;
+  // multifrontal factors (then AB is empty and perm/inv hold the nested-dissection ordering); the
+  // band ordering is kept for the pivoting fallback
+  mf::Factors *mfact = nullptr;
+  std::shared_ptr<const mf::Tree> tree;
+  std::vector<int> band_perm, band_inv;
+  Matrix *A = nullptr;   // rows of A   (residual b - A x)
+  Matrix *At = nullptr;  // rows of A^T (residual b - A^T x)
+  // set by the `zi` wrapper (umfpack_zi.hip): rows 2r, 2r+1 of the real embedding were swapped
+  std::vector<char> pair_swap;
+  std::vector<double> pair_unit;  // zi wrapper, complex symmetric matrices: unit-modulus u_r (re, im) of the congruence D A D
+  // Static pivoting (static_pivot.hpp): 0 not tried, 1 the factors held are those of B = Dr P A Dc on B's own
+  // tree (still a checked speculation), 2 tried and given up.  spA / spAt: rows of B / of B^T on the device
+  // (what mf_factor scatters); sp_idx / sp_scale: the permutations and scalings around a solve with B's factors,
+  // composed with B's nested-dissection ordering — [0] before, [1] after A x = b; [2] before, [3] after A^T x = b.
+  int sp_stage = 0;
+  // the most recent solve call that finished on this object (spl_umfpack_solve_report; UMFPACK reports the like in
+  // Info[UMFPACK_IR_TAKEN .. UMFPACK_OMEGA1]): walks over the factors (first solve + refinement steps, whatever path),
+  // refinement steps kept / attempted, largest componentwise backward error among the delivered columns
+  std::atomic<int> last_walks{0}, last_ir_taken{0}, last_ir_attempted{0};
+  std::atomic<double> last_omega{0.0};
+  Matrix *spA = nullptr, *spAt = nullptr;
+  DBuf<int> sp_idx[4];
+  DBuf<double> sp_scale[4];
+  ~Numeric() {
+    delete A;
+    delete At;
+    delete spA;
+    delete spAt;
+    if (mfact) mf_free(mfact);
+  }
+};
+
+inline Symbolic *as_symbolic(void *p) {
+  Symbolic *s = static_cast<Symbolic *>(p);
+  return (s && s->magic == kSymMagic) ? s : nullptr;
+}
+inline Numeric *as_numeric(void *p) {
+  Numeric *s = static_cast<Numeric *>(p);
+  return (s && s->magic == kNumMagic) ? s : nullptr;
+}
+
+// The error boundary of the UMFPACK calls: f's status, or the status of the exception it throws (nothing may cross
+// the C ABI).
+template <typename F>
+int umf_guarded(F &&f) {
+  try {
+    return f();
+  } catch (const DeviceError &e) {
+    return e.status == SPL_ERROR_out_of_memory ? UMFPACK_ERROR_out_of_memory : UMFPACK_ERROR_internal_error;
+  } catch (const std::bad_alloc &) {
+    return UMFPACK_ERROR_out_of_memory;
+  } catch (...) {  // e.g. std::system_error from a thread that could not be started
+    return UMFPACK_ERROR_internal_error;
+  }
+}
+// the UMFPACK status of an SPL status (sparse_linear_hip.h) returned by the matrix calls behind numeric
+inline int umf_status(int spl_status) {
+  return spl_status == SPL_ERROR_out_of_memory    ? UMFPACK_ERROR_out_of_memory
+         : spl_status == SPL_ERROR_invalid_matrix ? UMFPACK_ERROR_invalid_matrix
+                                                  : UMFPACK_ERROR_internal_error;
+}
+
+// 64-bit hash of the row indices: the second half of the pattern check in numeric
+uint64_t hash_indices(const int *Ai, int64_t nnz);
+// Ap[0] == 0, Ap monotone, 0 <= Ai < n_row and ascending in every column: UMFPACK_OK or UMFPACK_ERROR_invalid_matrix
+int validate_host_csc(int n_row, int n_col, const int *Ap, const int *Ai);
+
+// The analysis behind umfpack_di_symbolic and, with mult = 2, umfpack_zi_symbolic: (Ap, Ai) is the n x n pattern
+// that is ORDERED; the object describes the (n mult) x (n mult) matrix of dense mult x mult blocks whose CSC
+// pattern is (Ep, Ei) — what numeric will be handed and checks against.  mult = 1: Ep = Ap, Ei = Ai.
+int symbolic_common(int n, const int *Ap, const int *Ai, int mult, const int *Ep, const int *Ei, Symbolic **SymbolicOut);
+
+// Rectangular matrices (Symbolic::rectangular): the analysis records shape and pattern; the "factorisation" checks the
+// pattern and counts pivots over the entries nonzero[p] != 0 — with values (re; im null, or packed complex: im = re + 1
+// and vstride 2) small matrices get their numerical rank.
+int symbolic_rectangular(int n_row, int n_col, const int *Ap, const int *Ai, Symbolic **SymbolicOut);
+int numeric_rectangular(Symbolic *S, const int *Ap, const int *Ai, const std::vector<char> &nonzero, Numeric **NumericOut,
+                        const double *re = nullptr, const double *im = nullptr, int vstride = 1);
+
+// What the `zi` half tells numeric_factor about the real embedding of a complex matrix; the defaults: a real matrix.
+struct EmbeddingOpts {
+  bool embedding = false;  // the real embedding of a complex matrix (Numeric::embedding)
+  bool native = false;     // the plain embedding, and native complex fronts serve it (Numeric::ztree)
+  bool zsym = false;       // ... and the complex matrix is symmetric (Numeric::zsym)
+  std::vector<char> pair_swap;    // Numeric::pair_swap
+  std::vector<double> pair_unit;  // Numeric::pair_unit
+};
+// The numeric factorisation of a square matrix whose arguments and pattern the caller has checked; *NumericOut is
+// set only when it succeeds (status >= 0).
+int numeric_factor(Symbolic *S, const int *Ap, const int *Ai, const double *Ax, EmbeddingOpts opts, Numeric **NumericOut);
+
+// k systems op(A) X(:,c) = B(:,c) with the factors of N (sys: UMFPACK_A or UMFPACK_At); X and B are n x k
+// column-major, in device memory when device_io is set, else on the host.  Info: what umfpack_*_solve reports there.
+int solve_columns(Numeric *N, int sys, int k, double *X, const double *B, const int *Ap, const int *Ai,
+                  const double *Ax, bool device_io = false, double *Info = nullptr, bool caller_holds_turn = false);
+
+}  // namespace spl

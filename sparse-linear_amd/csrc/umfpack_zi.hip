@@ -36,8 +36,7 @@
 #include <utility>
 #include <vector>
 
-#include "common.hpp"
-#include "../../include/umfpack_hip.h"
+#include "umfpack_impl.hpp"
 
 namespace {
 
@@ -210,69 +209,102 @@ __global__ __launch_bounds__(256) void unit_pairs_kernel(const double *__restric
 struct ZiSymbolic {  // remembers n so that numeric can rebuild the embedding, and the complex pattern it analysed
   unsigned magic = 0x5A53594Du;
   int n = 0;
-  void *di = nullptr;
+  spl::Symbolic *di = nullptr;
   std::vector<int> Ap;
   uint64_t ai_hash = 0;
 };
+
+// Native complex fronts serve this analysis?  They need the tree (of the complex pattern), and pay where the tree has
+// flops to halve: below ~1e12 flops of the embedding's tree (2-D meshes up to 10^6 unknowns) a factorisation is
+// launch-bound either way and a batch of right-hand sides takes twice the passes over the tree (four complex columns
+// per pass against eight real ones).  SPL_ZI_NATIVE=1 / 0: always / never.
+bool native_fronts(const spl::Symbolic &S) {
+  if (!S.tree || !S.ztree) return false;
+  const char *zn = getenv("SPL_ZI_NATIVE");
+  if (zn && zn[0] == '0') return false;
+  if (zn && zn[0] == '1') return true;
+  return S.tree->flops >= 1e12;
+}
+
+// nrhs complex systems on the host through the real embedding N holds: right-hand sides packed (re, im) pairs when
+// the imaginary pointers are NULL, else split arrays of n x nrhs (column-major); interleave, apply the swapped pairs
+// and the congruence, solve, undo both, de-interleave
+int solve_host(spl::Numeric *N, int sys, const int *Ap, const int *Ai, const double *Ax, int nrhs, double *Xx,
+               double *Xz, const double *Bx, const double *Bz, double *Info) {
+  return spl::umf_guarded([&] {
+    const std::vector<char> &swap = N->pair_swap;
+    const std::vector<double> &unit = N->pair_unit;
+    const size_t n2 = (size_t)N->n, n = n2 / 2, tot = n2 * (size_t)nrhs;
+    const bool packed = !Xz && !Bz;
+    std::vector<double> b(tot), x(tot);
+    for (size_t c = 0; c < (size_t)nrhs; ++c) {
+      for (size_t k = 0; k < n; ++k) {
+        b[c * n2 + 2 * k] = packed ? Bx[c * n2 + 2 * k] : Bx[c * n + k];
+        b[c * n2 + 2 * k + 1] = packed ? Bx[c * n2 + 2 * k + 1] : (Bz ? Bz[c * n + k] : 0.0);
+      }
+      if (!swap.empty() && sys == UMFPACK_A) swap_pairs(swap, b.data() + c * n2);     // (Q E) x = Q b
+      if (!unit.empty()) unit_pairs(unit, sys == UMFPACK_A ? 0 : 2, b.data() + c * n2);  // E' x' = T b  /  E' y' = W^T c
+    }
+    const int st = sys != UMFPACK_A && sys != UMFPACK_At
+                       ? UMFPACK_ERROR_invalid_system
+                       : spl::solve_columns(N, sys, nrhs, x.data(), b.data(), Ap, Ai, Ax, false, Info);
+    for (size_t c = 0; c < (size_t)nrhs; ++c) {
+      if (!swap.empty() && sys != UMFPACK_A) swap_pairs(swap, x.data() + c * n2);       // y = Q w
+      if (!unit.empty()) unit_pairs(unit, sys == UMFPACK_A ? 1 : 3, x.data() + c * n2);  // x = W x'  /  y = T^T y'
+      for (size_t k = 0; k < n; ++k) {
+        if (packed) { Xx[c * n2 + 2 * k] = x[c * n2 + 2 * k]; Xx[c * n2 + 2 * k + 1] = x[c * n2 + 2 * k + 1]; }
+        else { Xx[c * n + k] = x[c * n2 + 2 * k]; if (Xz) Xz[c * n + k] = x[c * n2 + 2 * k + 1]; }
+      }
+    }
+    return st;
+  });
+}
 
 }  // namespace
 
 extern "C" {
 
 int umfpack_zi_symbolic(int n_row, int n_col, const int Ap[], const int Ai[], const double Ax[],
-                        const double Az[], void **Symbolic, const double Control[], double Info[]) {
-  (void)Ax; (void)Az;
-  if (!Symbolic) return UMFPACK_ERROR_argument_missing;
-  *Symbolic = nullptr;
+                        const double Az[], void **SymbolicOut, const double Control[], double Info[]) {
+  (void)Ax; (void)Az; (void)Control; (void)Info;
+  if (!SymbolicOut) return UMFPACK_ERROR_argument_missing;
+  *SymbolicOut = nullptr;
   if (!Ap) return UMFPACK_ERROR_argument_missing;
   if (n_row <= 0 || n_col <= 0) return UMFPACK_ERROR_n_nonpositive;
+  // (a missing Ai is an invalid matrix here, a missing argument for umfpack_di_symbolic)
   if (Ap[0] != 0 || Ap[n_col] < 0 || (Ap[n_col] > 0 && !Ai)) return UMFPACK_ERROR_invalid_matrix;
-  for (int j = 0; j < n_col; ++j) {
-    if (Ap[j] > Ap[j + 1]) return UMFPACK_ERROR_invalid_matrix;
-    for (int p = Ap[j]; p < Ap[j + 1]; ++p)
-      if (Ai[p] < 0 || Ai[p] >= n_row || (p > Ap[j] && Ai[p] <= Ai[p - 1])) return UMFPACK_ERROR_invalid_matrix;
-  }
-  if (n_row != n_col) {  // rectangular: shape and pattern only (umfpack.hip, Symbolic::rectangular)
-    try {
-      ZiSymbolic *S = new ZiSymbolic();
-      S->n = n_col;
-      const int st = spl::symbolic_rectangular(n_row, n_col, Ap, Ai, &S->di);
-      if (st < 0) { delete S; return st; }
-      *Symbolic = S;
-      return st;
-    } catch (...) {
-      return UMFPACK_ERROR_out_of_memory;
-    }
-  }
-  try {
-    Embedded E;
-    if (!embed(n_col, Ap, Ai, nullptr, nullptr, false, E)) return UMFPACK_ERROR_out_of_memory;
-    ZiSymbolic *S = new ZiSymbolic();
+  const int valid = spl::validate_host_csc(n_row, n_col, Ap, Ai);
+  if (valid != UMFPACK_OK) return valid;
+  return spl::umf_guarded([&] {
+    std::unique_ptr<ZiSymbolic> S(new ZiSymbolic());
     S->n = n_col;
-    S->Ap.assign(Ap, Ap + n_col + 1);
-    S->ai_hash = spl::pattern_hash(Ai, Ap[n_col]);
-    (void)Control; (void)Info;
-    // ordered on the complex pattern (half the vertices, a quarter of the edges of the embedding), then expanded
-    const int st = spl::symbolic_of_embedding(n_col, Ap, Ai, E.p.data(), E.i.data(), &S->di);
-    if (st < 0) { delete S; return st; }
-    *Symbolic = S;
+    int st;
+    if (n_row != n_col) {  // rectangular: shape and pattern only (umfpack.hip, Symbolic::rectangular)
+      st = spl::symbolic_rectangular(n_row, n_col, Ap, Ai, &S->di);
+    } else {
+      Embedded E;
+      if (!embed(n_col, Ap, Ai, nullptr, nullptr, false, E)) return UMFPACK_ERROR_out_of_memory;
+      S->Ap.assign(Ap, Ap + n_col + 1);
+      S->ai_hash = spl::hash_indices(Ai, Ap[n_col]);
+      // ordered on the complex pattern (half the vertices, a quarter of the edges of the embedding), then expanded
+      st = spl::symbolic_common(n_col, Ap, Ai, 2, E.p.data(), E.i.data(), &S->di);
+    }
+    if (st >= 0) *SymbolicOut = S.release();
     return st;
-  } catch (const std::bad_alloc &) {
-    return UMFPACK_ERROR_out_of_memory;
-  } catch (...) {  // nothing may cross the C ABI
-    return UMFPACK_ERROR_internal_error;
-  }
+  });
 }
 
 int umfpack_zi_numeric(const int Ap[], const int Ai[], const double Ax[], const double Az[],
-                       void *Symbolic, void **Numeric, const double Control[], double Info[]) {
-  if (!Numeric) return UMFPACK_ERROR_argument_missing;
-  *Numeric = nullptr;
-  ZiSymbolic *S = static_cast<ZiSymbolic *>(Symbolic);
+                       void *SymbolicIn, void **NumericOut, const double Control[], double Info[]) {
+  (void)Control; (void)Info;
+  if (!NumericOut) return UMFPACK_ERROR_argument_missing;
+  *NumericOut = nullptr;
+  ZiSymbolic *S = static_cast<ZiSymbolic *>(SymbolicIn);
   if (!S || S->magic != 0x5A53594Du) return UMFPACK_ERROR_invalid_Symbolic_object;
   if (!Ap || !Ai || !Ax) return UMFPACK_ERROR_argument_missing;
-  if (spl::symbolic_is_rectangular(S->di)) {
-    try {
+  spl::Numeric *N = nullptr;
+  const int st = spl::umf_guarded([&] {
+    if (S->di->rectangular) {
       const int nnz = Ap[S->n];
       if (nnz < 0) return UMFPACK_ERROR_different_pattern;
       std::vector<char> nonzero((size_t)nnz);
@@ -280,12 +312,8 @@ int umfpack_zi_numeric(const int Ap[], const int Ai[], const double Ax[], const 
         const double re = Az ? Ax[p] : Ax[2 * (size_t)p], im = Az ? Az[p] : Ax[2 * (size_t)p + 1];
         nonzero[(size_t)p] = ((re != 0.0 || im != 0.0) && re == re && im == im) ? 1 : 0;
       }
-      return spl::numeric_rectangular_of(S->di, Ap, Ai, nonzero, Numeric, Ax, Az ? Az : Ax + 1, Az ? 1 : 2);
-    } catch (...) {
-      return UMFPACK_ERROR_out_of_memory;
+      return spl::numeric_rectangular(S->di, Ap, Ai, nonzero, &N, Ax, Az ? Az : Ax + 1, Az ? 1 : 2);
     }
-  }
-  try {
     // Static pivoting inside the 2 x 2 blocks of the diagonal.  The scalar factorisation of the
     // embedding pivots on the REAL part of a complex diagonal entry first; where the imaginary part
     // is the larger one (a shift z I - A close to the real axis of A's diagonal: pivot ~ 0), the two
@@ -294,7 +322,7 @@ int umfpack_zi_numeric(const int Ap[], const int Ai[], const double Ax[], const 
     // pattern of the embedding does not change (every block is a full 2 x 2).
     const int n = S->n;
     // UMFPACK_ERROR_different_pattern, decided on the complex pattern (the embedding's is four times as long)
-    if (!std::equal(S->Ap.begin(), S->Ap.end(), Ap) || spl::pattern_hash(Ai, Ap[n]) != S->ai_hash)
+    if (!std::equal(S->Ap.begin(), S->Ap.end(), Ap) || spl::hash_indices(Ai, Ap[n]) != S->ai_hash)
       return UMFPACK_ERROR_different_pattern;
     const bool timing = getenv("SPL_MF_TIMING") != nullptr;
     const auto t0 = std::chrono::steady_clock::now();
@@ -306,9 +334,9 @@ int umfpack_zi_numeric(const int Ap[], const int Ai[], const double Ax[], const 
     // congruence: a complex pivot is as good as its modulus — whenever the analysis chose the tree; a complex symmetric
     // matrix is then factored as L D L^T in complex arithmetic.  The embeddings below serve the band path, and
     // SPL_ZI_NATIVE=0.
-    const bool native = spl::symbolic_has_complex_tree(S->di);
+    const bool native = native_fronts(*S->di);
     const char *zs = getenv("SPL_ZI_SYMMETRIC");
-    const bool wanted = native || (zs ? zs[0] != '0' : spl::symbolic_tree_flops(S->di) >= 1e12);
+    const bool wanted = native || (zs ? zs[0] != '0' : (S->di->tree ? S->di->tree->flops : 0.0) >= 1e12);
     const bool is_sym = wanted && n > 1 && complex_symmetric(n, Ap, Ai, Ax, Az);
     const bool symmetric = is_sym && !native;
     std::vector<char> swap;
@@ -355,127 +383,67 @@ int umfpack_zi_numeric(const int Ap[], const int Ai[], const double Ax[], const 
               native ? (is_sym ? "plain (native complex fronts, symmetric)" : "plain (native complex fronts)")
                      : symmetric ? "symmetric" : "general",
               std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count());
-    (void)Control; (void)Info;
-    const int st = spl::numeric_of_embedding(E.p.data(), E.i.data(), E.x.data(), S->di, Numeric,
-                                             native ? (is_sym ? 2 : 1) : 0);
-    if (st >= 0 && any) spl::numeric_set_pair_swap(*Numeric, std::move(swap));
-    if (st >= 0 && symmetric) spl::numeric_set_pair_unit(*Numeric, std::move(unit));
-    return st;
-  } catch (const std::bad_alloc &) {
-    return UMFPACK_ERROR_out_of_memory;
-  } catch (...) {  // nothing may cross the C ABI
-    return UMFPACK_ERROR_internal_error;
-  }
-}
-
-static int zi_solve(int sys, const int Ap[], const int Ai[], const double Ax[], const double Az[],
-                    double Xx[], double Xz[], const double Bx[], const double Bz[], void *Numeric,
-                    const double Control[], double Info[]);
-
-int umfpack_zi_solve(int sys, const int Ap[], const int Ai[], const double Ax[], const double Az[],
-                     double Xx[], double Xz[], const double Bx[], const double Bz[], void *Numeric,
-                     const double Control[], double Info[]) {
-  const int st = zi_solve(sys, Ap, Ai, Ax, Az, Xx, Xz, Bx, Bz, Numeric, Control, Info);
-  if (Info && st < 0) Info[0] = st;  // Info[UMFPACK_STATUS] on the error returns as well
+    spl::EmbeddingOpts opts;
+    opts.embedding = true;
+    opts.native = native;
+    opts.zsym = native && is_sym;
+    if (any) opts.pair_swap = std::move(swap);
+    if (symmetric) opts.pair_unit = std::move(unit);
+    return spl::numeric_factor(S->di, E.p.data(), E.i.data(), E.x.data(), std::move(opts), &N);
+  });
+  *NumericOut = N;
   return st;
 }
 
-static int zi_solve(int sys, const int Ap[], const int Ai[], const double Ax[], const double Az[],
-                    double Xx[], double Xz[], const double Bx[], const double Bz[], void *Numeric,
-                    const double Control[], double Info[]) {
+int umfpack_zi_solve(int sys, const int Ap[], const int Ai[], const double Ax[], const double Az[],
+                     double Xx[], double Xz[], const double Bx[], const double Bz[], void *NumericIn,
+                     const double Control[], double Info[]) {
   (void)Az;
-  if (spl::numeric_is_rectangular(Numeric)) return UMFPACK_ERROR_invalid_system;
-  if (!Xx || !Bx) return UMFPACK_ERROR_argument_missing;
-  if (!Ap || !Ai || !Ax) return UMFPACK_ERROR_argument_missing;
-  // the Numeric object holds device copies of E and E^T (residuals use those, like the `di` path)
-  const std::vector<char> *swap = spl::numeric_pair_swap(Numeric);
-  const std::vector<double> *unit = spl::numeric_pair_unit(Numeric);
-  if (!Xz && !Bz && !swap && !unit) return umfpack_di_solve(sys, Ap, Ai, Ax, Xx, Bx, Numeric, Control, Info);
-  // split real / imaginary arrays and / or swapped row pairs: interleave, solve, de-interleave
-  try {
-    // UMFPACK's solve takes no dimension argument: it lives in the Numeric object
-    const int n2 = spl_umfpack_dimension(Numeric);
-    if (n2 <= 0) return UMFPACK_ERROR_invalid_Numeric_object;
-    const int n = n2 / 2;
-    const bool packed = !Xz && !Bz;
-    std::vector<double> b((size_t)n2), x((size_t)n2);
-    for (int k = 0; k < n; ++k) {
-      b[(size_t)2 * k] = packed ? Bx[(size_t)2 * k] : Bx[k];
-      b[(size_t)2 * k + 1] = packed ? Bx[(size_t)2 * k + 1] : (Bz ? Bz[k] : 0.0);
-    }
-    if (swap && sys == UMFPACK_A) swap_pairs(*swap, b.data());          // (Q E) x = Q b
-    if (unit) unit_pairs(*unit, sys == UMFPACK_A ? 0 : 2, b.data());    // E' x' = T b  /  E' y' = W^T c
-    const int st = umfpack_di_solve(sys, Ap, Ai, Ax, x.data(), b.data(), Numeric, Control, Info);
-    if (swap && sys != UMFPACK_A) swap_pairs(*swap, x.data());          // y = Q w
-    if (unit) unit_pairs(*unit, sys == UMFPACK_A ? 1 : 3, x.data());    // x = W x'  /  y = T^T y'
-    for (int k = 0; k < n; ++k) {
-      if (packed) { Xx[(size_t)2 * k] = x[(size_t)2 * k]; Xx[(size_t)2 * k + 1] = x[(size_t)2 * k + 1]; }
-      else { Xx[k] = x[(size_t)2 * k]; if (Xz) Xz[k] = x[(size_t)2 * k + 1]; }
-    }
-    return st;
-  } catch (const std::bad_alloc &) {
-    return UMFPACK_ERROR_out_of_memory;
-  } catch (...) {  // nothing may cross the C ABI
-    return UMFPACK_ERROR_internal_error;
-  }
+  spl::Numeric *N = spl::as_numeric(NumericIn);
+  const int st = [&] {
+    if (N && N->rectangular) return UMFPACK_ERROR_invalid_system;
+    if (!Xx || !Bx) return UMFPACK_ERROR_argument_missing;
+    if (!Ap || !Ai || !Ax) return UMFPACK_ERROR_argument_missing;
+    if (!N) return UMFPACK_ERROR_invalid_Numeric_object;
+    // the Numeric object holds device copies of E and E^T (residuals use those, like the `di` path)
+    if (!Xz && !Bz && N->pair_swap.empty() && N->pair_unit.empty())
+      return umfpack_di_solve(sys, Ap, Ai, Ax, Xx, Bx, NumericIn, Control, Info);
+    return solve_host(N, sys, Ap, Ai, Ax, 1, Xx, Xz, Bx, Bz, Info);
+  }();
+  if (Info && st < 0) Info[0] = st;  // Info[UMFPACK_STATUS] on the error returns as well
+  return st;
 }
 
 // batched complex linearSolve: nrhs right-hand sides, each packed (re, im) pairs when the
 // imaginary pointers are NULL, else split arrays of n x nrhs (column-major)
 int spl_umfpack_zi_solve_many(int sys, const int Ap[], const int Ai[], const double Ax[], const double Az[],
                               int nrhs, double Xx[], double Xz[], const double Bx[], const double Bz[],
-                              void *Numeric) {
+                              void *NumericIn) {
   (void)Az;
-  if (spl::numeric_is_rectangular(Numeric)) return UMFPACK_ERROR_invalid_system;
+  spl::Numeric *N = spl::as_numeric(NumericIn);
+  if (N && N->rectangular) return UMFPACK_ERROR_invalid_system;
   if (nrhs < 0) return UMFPACK_ERROR_argument_missing;
   if (!Ap || !Ai || !Ax) return UMFPACK_ERROR_argument_missing;
-  const int n2 = spl_umfpack_dimension(Numeric);
-  if (n2 < 0 || (n2 == 0 && !Numeric)) return UMFPACK_ERROR_invalid_Numeric_object;
-  if (nrhs > 0 && n2 > 0 && (!Xx || !Bx)) return UMFPACK_ERROR_argument_missing;
-  const std::vector<char> *swap = spl::numeric_pair_swap(Numeric);
-  const std::vector<double> *unit = spl::numeric_pair_unit(Numeric);
-  if (!Xz && !Bz && !swap && !unit) return spl_umfpack_di_solve_many(sys, Ap, Ai, Ax, nrhs, Xx, Bx, Numeric);
-  try {
-    const size_t n = (size_t)n2 / 2, tot = (size_t)n2 * (size_t)nrhs;
-    const bool packed = !Xz && !Bz;
-    std::vector<double> b(tot), x(tot);
-    for (size_t c = 0; c < (size_t)nrhs; ++c) {
-      for (size_t k = 0; k < n; ++k) {
-        b[c * n2 + 2 * k] = packed ? Bx[c * n2 + 2 * k] : Bx[c * n + k];
-        b[c * n2 + 2 * k + 1] = packed ? Bx[c * n2 + 2 * k + 1] : (Bz ? Bz[c * n + k] : 0.0);
-      }
-      if (swap && sys == UMFPACK_A) swap_pairs(*swap, b.data() + c * n2);
-      if (unit) unit_pairs(*unit, sys == UMFPACK_A ? 0 : 2, b.data() + c * n2);
-    }
-    const int st = spl_umfpack_di_solve_many(sys, Ap, Ai, Ax, nrhs, x.data(), b.data(), Numeric);
-    for (size_t c = 0; c < (size_t)nrhs; ++c) {
-      if (swap && sys != UMFPACK_A) swap_pairs(*swap, x.data() + c * n2);
-      if (unit) unit_pairs(*unit, sys == UMFPACK_A ? 1 : 3, x.data() + c * n2);
-      for (size_t k = 0; k < n; ++k) {
-        if (packed) { Xx[c * n2 + 2 * k] = x[c * n2 + 2 * k]; Xx[c * n2 + 2 * k + 1] = x[c * n2 + 2 * k + 1]; }
-        else { Xx[c * n + k] = x[c * n2 + 2 * k]; if (Xz) Xz[c * n + k] = x[c * n2 + 2 * k + 1]; }
-      }
-    }
-    return st;
-  } catch (const std::bad_alloc &) {
-    return UMFPACK_ERROR_out_of_memory;
-  } catch (...) {  // nothing may cross the C ABI
-    return UMFPACK_ERROR_internal_error;
-  }
+  if (!N) return UMFPACK_ERROR_invalid_Numeric_object;
+  if (nrhs > 0 && N->n > 0 && (!Xx || !Bx)) return UMFPACK_ERROR_argument_missing;
+  if (!Xz && !Bz && N->pair_swap.empty() && N->pair_unit.empty())
+    return spl_umfpack_di_solve_many(sys, Ap, Ai, Ax, nrhs, Xx, Bx, NumericIn);
+  return solve_host(N, sys, Ap, Ai, Ax, nrhs, Xx, Xz, Bx, Bz, nullptr);
 }
 
 // packed complex right-hand sides and solutions in device memory (see umfpack_hip.h)
 int spl_umfpack_zi_solve_many_dev(int sys, const int Ap[], const int Ai[], const double Ax[], int nrhs, double *d_X,
-                                  const double *d_B, void *Numeric) {
-  if (spl::numeric_is_rectangular(Numeric)) return UMFPACK_ERROR_invalid_system;
+                                  const double *d_B, void *NumericIn) {
+  spl::Numeric *N = spl::as_numeric(NumericIn);
+  if (N && N->rectangular) return UMFPACK_ERROR_invalid_system;
   if (nrhs < 0) return UMFPACK_ERROR_argument_missing;
-  const int n2 = spl_umfpack_dimension(Numeric);
-  if (n2 < 0 || (n2 == 0 && !Numeric)) return UMFPACK_ERROR_invalid_Numeric_object;
+  const int n2 = N ? N->n : 0;
+  if (n2 == 0 && !NumericIn) return UMFPACK_ERROR_invalid_Numeric_object;
   if (nrhs > 0 && n2 > 0 && (!d_X || !d_B)) return UMFPACK_ERROR_argument_missing;
-  const std::vector<char> *swap = spl::numeric_pair_swap(Numeric);
-  const std::vector<double> *unit = spl::numeric_pair_unit(Numeric);
-  if ((!swap && !unit) || nrhs == 0 || n2 == 0) return spl_umfpack_di_solve_many_dev(sys, Ap, Ai, Ax, nrhs, d_X, d_B, Numeric);
-  try {
+  const std::vector<char> *swap = N && !N->pair_swap.empty() ? &N->pair_swap : nullptr;
+  const std::vector<double> *unit = N && !N->pair_unit.empty() ? &N->pair_unit : nullptr;
+  if ((!swap && !unit) || nrhs == 0 || n2 == 0) return spl_umfpack_di_solve_many_dev(sys, Ap, Ai, Ax, nrhs, d_X, d_B, NumericIn);
+  return spl::umf_guarded([&] {
     const size_t n = (size_t)n2 / 2, total = n * (size_t)nrhs;
     if (unit) {  // symmetric embedding: E' x' = T b, x = W x'  /  E' y' = W^T c, y = T^T y'
       spl::DBuf<double> u(2 * n), b(2 * total);
@@ -484,7 +452,7 @@ int spl_umfpack_zi_solve_many_dev(int sys, const int Ap[], const int Ai[], const
       const dim3 grid((unsigned)((total + 255) / 256));
       hipLaunchKernelGGL(unit_pairs_kernel, grid, dim3(256), 0, nullptr, u.get(), sys == UMFPACK_A ? 0 : 2, b.get(), n, total);
       SPL_HIP(hipDeviceSynchronize());
-      const int st = spl_umfpack_di_solve_many_dev(sys, Ap, Ai, Ax, nrhs, d_X, b.get(), Numeric);
+      const int st = spl_umfpack_di_solve_many_dev(sys, Ap, Ai, Ax, nrhs, d_X, b.get(), NumericIn);
       if (st < 0) return st;
       hipLaunchKernelGGL(unit_pairs_kernel, grid, dim3(256), 0, nullptr, u.get(), sys == UMFPACK_A ? 1 : 3, d_X, n, total);
       SPL_HIP(hipDeviceSynchronize());
@@ -498,20 +466,14 @@ int spl_umfpack_zi_solve_many_dev(int sys, const int Ap[], const int Ai[], const
       SPL_HIP(hipMemcpy(b.get(), d_B, 2 * total * sizeof(double), hipMemcpyDeviceToDevice));
       hipLaunchKernelGGL(swap_pairs_kernel, grid, dim3(256), 0, nullptr, flags.get(), b.get(), n, total);
       SPL_HIP(hipDeviceSynchronize());
-      return spl_umfpack_di_solve_many_dev(sys, Ap, Ai, Ax, nrhs, d_X, b.get(), Numeric);
+      return spl_umfpack_di_solve_many_dev(sys, Ap, Ai, Ax, nrhs, d_X, b.get(), NumericIn);
     }
-    const int st = spl_umfpack_di_solve_many_dev(sys, Ap, Ai, Ax, nrhs, d_X, d_B, Numeric);
+    const int st = spl_umfpack_di_solve_many_dev(sys, Ap, Ai, Ax, nrhs, d_X, d_B, NumericIn);
     if (st < 0) return st;
     hipLaunchKernelGGL(swap_pairs_kernel, grid, dim3(256), 0, nullptr, flags.get(), d_X, n, total);  // y = Q w
     SPL_HIP(hipDeviceSynchronize());
     return st;
-  } catch (const spl::DeviceError &e) {
-    return e.status == SPL_ERROR_out_of_memory ? UMFPACK_ERROR_out_of_memory : UMFPACK_ERROR_internal_error;
-  } catch (const std::bad_alloc &) {
-    return UMFPACK_ERROR_out_of_memory;
-  } catch (...) {  // nothing may cross the C ABI
-    return UMFPACK_ERROR_internal_error;
-  }
+  });
 }
 
 void umfpack_zi_free_symbolic(void **Symbolic) {
@@ -520,7 +482,8 @@ void umfpack_zi_free_symbolic(void **Symbolic) {
   *Symbolic = nullptr;
   if (S->magic != 0x5A53594Du) return;
   S->magic = 0;
-  umfpack_di_free_symbolic(&S->di);
+  void *di = S->di;
+  umfpack_di_free_symbolic(&di);
   delete S;
 }
 
