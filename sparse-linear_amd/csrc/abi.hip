@@ -47,6 +47,17 @@ void upload(DBuf<T> &dst, const T *src, size_t n, hipStream_t s) {
   if (n) SPL_HIP(hipMemcpyAsync(dst.get(), src, n * sizeof(T), hipMemcpyHostToDevice, s));
 }
 
+// malloc()'d host arrays, freed unless released to a caller who frees them with spl_free
+struct FreeDeleter {
+  void operator()(void *p) const { free(p); }
+};
+template <typename T>
+using HostArray = std::unique_ptr<T[], FreeDeleter>;
+template <typename T>
+HostArray<T> host_alloc(size_t n) {
+  return HostArray<T>(static_cast<T *>(malloc(n * sizeof(T))));
+}
+
 int check_tuple(int nrows, int ncols, const int *Ap, const int *Ai, const double *Ax) {
   if (nrows < 0 || ncols < 0) return SPL_ERROR_n_nonpositive;
   if (!Ap) return SPL_ERROR_argument_missing;
@@ -56,93 +67,212 @@ int check_tuple(int nrows, int ncols, const int *Ap, const int *Ai, const double
   return SPL_OK;
 }
 
-// Build the row-major image of a CSC 5-tuple on the current device.
-// out receives rows [row0,row1) chosen as the part-th of nparts nnz-balanced blocks.
-int build_from_csc(int nrows, int ncols, const int *Ap, const int *Ai, const double *Ax, int part,
-                   int nparts, Matrix **out) {
+// a CSC 5-tuple on the device; x holds vw doubles per entry (2: packed complex)
+struct DeviceCsc {
+  DBuf<int> p, i;
+  DBuf<double> x;
+  int64_t nnz = 0;
+};
+
+// upload a CSC 5-tuple that passed check_tuple and validate its pointers and indices
+int upload_validated(int nrows, int ncols, const int *Ap, const int *Ai, const double *Ax, int vw, DeviceCsc &d,
+                     hipStream_t s) {
+  d.nnz = Ap[ncols];
+  upload(d.p, Ap, (size_t)ncols + 1, s);
+  upload(d.i, Ai, (size_t)d.nnz, s);
+  upload(d.x, Ax, (size_t)d.nnz * (size_t)vw, s);
+  return validate_compressed(d.p.get(), d.i.get(), ncols, nrows, d.nnz, s);
+}
+
+// check, upload and validate a CSC 5-tuple; sort its columns if a caller violated the ascending-row invariant
+// (the reference's SPA does not care about input order)
+int upload_csc(int nrows, int ncols, const int *Ap, const int *Ai, const double *Ax, int vw, DeviceCsc &d,
+               hipStream_t s) {
+  int st = check_tuple(nrows, ncols, Ap, Ai, Ax);
+  if (st != SPL_OK) return st;
+  st = upload_validated(nrows, ncols, Ap, Ai, Ax, vw, d, s);
+  if (st != SPL_OK) return st;
+  if (!columns_sorted(d.p.get(), d.i.get(), ncols, s)) {
+    DBuf<int64_t> p64((size_t)ncols + 1);
+    widen_i32_to_i64(d.p.get(), p64.get(), (int64_t)ncols + 1, s);
+    if (vw == 1) {
+      segmented_sort_pairs(p64.get(), ncols, d.i.get(), d.x.get(), s);
+      SPL_HIP(hipStreamSynchronize(s));
+    } else {
+      // packed complex: sort the entry positions with the rows, then gather the 16-byte values along them
+      DBuf<double> pos((size_t)d.nnz), sorted((size_t)d.nnz * 2);
+      fill_positions(d.nnz, pos.get(), s);
+      segmented_sort_pairs(p64.get(), ncols, d.i.get(), pos.get(), s);
+      gather_complex_values(d.nnz, pos.get(), d.x.get(), sorted.get(), s);
+      SPL_HIP(hipStreamSynchronize(s));
+      d.x = std::move(sorted);
+    }
+  }
+  return SPL_OK;
+}
+
+// copy a device CSC result into malloc()'d host arrays the caller adopts (`fromForeign False`, freed with spl_free);
+// vw doubles per value
+int download_result(int64_t ncols, int64_t nnz, int vw, const int64_t *dCp64, const int *dCi, const double *dCx,
+                    int **Cp, int **Ci, double **Cx, hipStream_t s) {
+  if (nnz >= 0x7fffffffLL) return SPL_ERROR_index_overflow;
+  const size_t n = (size_t)(nnz ? nnz : 1);
+  HostArray<int> hp = host_alloc<int>((size_t)ncols + 1), hi = host_alloc<int>(n);
+  HostArray<double> hx = host_alloc<double>(n * (size_t)vw);
+  if (!hp || !hi || !hx) return SPL_ERROR_out_of_memory;
+  DBuf<int> dCp32((size_t)ncols + 1);
+  narrow_i64_to_i32(dCp64, dCp32.get(), ncols + 1, s);
+  SPL_HIP(hipMemcpyAsync(hp.get(), dCp32.get(), ((size_t)ncols + 1) * sizeof(int), hipMemcpyDeviceToHost, s));
+  if (nnz) {
+    SPL_HIP(hipMemcpyAsync(hi.get(), dCi, (size_t)nnz * sizeof(int), hipMemcpyDeviceToHost, s));
+    SPL_HIP(hipMemcpyAsync(hx.get(), dCx, (size_t)nnz * (size_t)vw * sizeof(double), hipMemcpyDeviceToHost, s));
+  }
+  SPL_HIP(hipStreamSynchronize(s));
+  *Cp = hp.release();
+  *Ci = hi.release();
+  *Cx = hx.release();
+  return SPL_OK;
+}
+
+// a handle under construction: rows [row0, row0 + nrows_local) of an nrows_global x ncols matrix, vw doubles per value
+std::unique_ptr<Matrix> make_matrix(int device, int64_t nrows_global, int64_t ncols, int64_t row0, int64_t nrows_local,
+                                    int vw = 1) {
+  std::unique_ptr<Matrix> m(new Matrix());
+  m->device = device;
+  m->nrows_global = nrows_global;
+  m->ncols = ncols;
+  m->row0 = row0;
+  m->nrows_local = nrows_local;
+  m->vw = vw;
+  return m;
+}
+
+// finish a handle whose rowptr64 / colidx / val are filled and hand it to the caller
+int publish(std::unique_ptr<Matrix> m, hipStream_t s, void **H) {
+  finalize_matrix(m.get(), s);
+  *H = m.release();
+  return SPL_OK;
+}
+
+// Build the row-major image of a CSC 5-tuple with vw doubles per value on the current device (not yet finalized).
+// out receives rows [row0,row1) chosen as the part-th of nparts nnz-balanced blocks; packed complex tuples come
+// whole (nparts == 1).
+int build_from_csc(int vw, int nrows, int ncols, const int *Ap, const int *Ai, const double *Ax, int part, int nparts,
+                   std::unique_ptr<Matrix> &out) {
   int st = check_tuple(nrows, ncols, Ap, Ai, Ax);
   if (st != SPL_OK) return st;
   if (nparts < 1 || part < 0 || part >= nparts) return SPL_ERROR_argument_missing;
-  const int64_t nnz = Ap[ncols];
   const int dev = current_device();
   hipStream_t s = nullptr;
-
-  DBuf<int> dAp, dAi;
-  DBuf<double> dAx;
-  upload(dAp, Ap, (size_t)ncols + 1, s);
-  upload(dAi, Ai, (size_t)nnz, s);
-  upload(dAx, Ax, (size_t)nnz, s);
-  st = validate_compressed(dAp.get(), dAi.get(), ncols, nrows, nnz, s);
+  DeviceCsc A;
+  st = upload_validated(nrows, ncols, Ap, Ai, Ax, vw, A, s);
   if (st != SPL_OK) return st;
+  const int64_t nnz = A.nnz;
 
-  Matrix *full = new Matrix();
-  full->device = dev;
-  full->nrows_global = nrows;
-  full->ncols = ncols;
-  full->row0 = 0;
-  full->nrows_local = nrows;
+  std::unique_ptr<Matrix> full = make_matrix(dev, nrows, ncols, 0, nrows, vw);
   full->nnz = nnz;
-  try {
+  if (vw == 1) {
     full->rowptr64.alloc((size_t)nrows + 1);
     full->colidx.alloc((size_t)nnz);
     full->val.alloc((size_t)nnz);
-    transpose_compressed(dAp.get(), dAi.get(), dAx.get(), ncols, nrows, nnz, full->rowptr64.get(),
-                         full->colidx.get(), full->val.get(), s);
-    if (nparts == 1) {
-      finalize_matrix(full, s);
-      *out = full;
-      return SPL_OK;
-    }
-    // nnz-balanced contiguous row blocks: block p starts at the first row whose
-    // pointer is >= nnz*p/nparts (identical on every rank: same input, same rule)
-    std::vector<int64_t> hptr((size_t)nrows + 1);
-    SPL_HIP(hipMemcpy(hptr.data(), full->rowptr64.get(), ((size_t)nrows + 1) * sizeof(int64_t),
-                      hipMemcpyDeviceToHost));
-    auto boundary = [&](int p) -> int64_t {
-      if (p <= 0) return 0;
-      if (p >= nparts) return nrows;
-      const int64_t target = (int64_t)(((__int128)nnz * p) / nparts);
-      int64_t lo = 0, hi = nrows;
-      while (lo < hi) {
-        const int64_t mid = (lo + hi) / 2;
-        if (hptr[(size_t)mid] < target) lo = mid + 1; else hi = mid;
-      }
-      return lo;
-    };
-    const int64_t r0 = boundary(part), r1 = boundary(part + 1);
-    Matrix *blk = new Matrix();
-    blk->device = dev;
-    blk->nrows_global = nrows;
-    blk->ncols = ncols;
-    blk->row0 = r0;
-    blk->nrows_local = r1 - r0;
-    const int64_t k0 = hptr[(size_t)r0], k1 = hptr[(size_t)r1];
-    blk->nnz = k1 - k0;
-    try {
-      std::vector<int64_t> rel((size_t)(r1 - r0) + 1);
-      for (int64_t i = 0; i <= r1 - r0; ++i) rel[(size_t)i] = hptr[(size_t)(r0 + i)] - k0;
-      upload(blk->rowptr64, rel.data(), rel.size(), s);
-      blk->colidx.alloc((size_t)blk->nnz);
-      blk->val.alloc((size_t)blk->nnz);
-      if (blk->nnz) {
-        SPL_HIP(hipMemcpyAsync(blk->colidx.get(), full->colidx.get() + k0, (size_t)blk->nnz * sizeof(int),
-                               hipMemcpyDeviceToDevice, s));
-        SPL_HIP(hipMemcpyAsync(blk->val.get(), full->val.get() + k0, (size_t)blk->nnz * sizeof(double),
-                               hipMemcpyDeviceToDevice, s));
-      }
-      SPL_HIP(hipStreamSynchronize(s));
-      finalize_matrix(blk, s);
-    } catch (...) {
-      delete blk;
-      throw;
-    }
-    delete full;
-    *out = blk;
-    return SPL_OK;
-  } catch (...) {
-    delete full;
-    throw;
+    transpose_compressed(A.p.get(), A.i.get(), A.x.get(), ncols, nrows, nnz, full->rowptr64.get(), full->colidx.get(),
+                         full->val.get(), s);
+  } else {
+    // packed complex (Umfpack/Internal.hs:124-132): transpose the PATTERN with the entry positions as payload and
+    // gather the 16-byte values along the permutation
+    DBuf<double> pos((size_t)nnz), perm((size_t)nnz);
+    fill_positions(nnz, pos.get(), s);
+    full->rowptr64.alloc((size_t)nrows + 1);
+    full->colidx.alloc((size_t)nnz);
+    full->val.alloc((size_t)nnz * 2);
+    transpose_compressed(A.p.get(), A.i.get(), pos.get(), ncols, nrows, nnz, full->rowptr64.get(), full->colidx.get(),
+                         perm.get(), s);
+    gather_complex_values(nnz, perm.get(), A.x.get(), full->val.get(), s);
+    SPL_HIP(hipStreamSynchronize(s));
   }
+  if (nparts == 1) {
+    out = std::move(full);
+    return SPL_OK;
+  }
+  // nnz-balanced contiguous row blocks: block p starts at the first row whose
+  // pointer is >= nnz*p/nparts (identical on every rank: same input, same rule)
+  std::vector<int64_t> hptr((size_t)nrows + 1);
+  SPL_HIP(hipMemcpy(hptr.data(), full->rowptr64.get(), ((size_t)nrows + 1) * sizeof(int64_t), hipMemcpyDeviceToHost));
+  auto boundary = [&](int p) -> int64_t {
+    if (p <= 0) return 0;
+    if (p >= nparts) return nrows;
+    const int64_t target = (int64_t)(((__int128)nnz * p) / nparts);
+    int64_t lo = 0, hi = nrows;
+    while (lo < hi) {
+      const int64_t mid = (lo + hi) / 2;
+      if (hptr[(size_t)mid] < target) lo = mid + 1; else hi = mid;
+    }
+    return lo;
+  };
+  const int64_t r0 = boundary(part), r1 = boundary(part + 1);
+  std::unique_ptr<Matrix> blk = make_matrix(dev, nrows, ncols, r0, r1 - r0);
+  const int64_t k0 = hptr[(size_t)r0], k1 = hptr[(size_t)r1];
+  blk->nnz = k1 - k0;
+  std::vector<int64_t> rel((size_t)(r1 - r0) + 1);
+  for (int64_t i = 0; i <= r1 - r0; ++i) rel[(size_t)i] = hptr[(size_t)(r0 + i)] - k0;
+  upload(blk->rowptr64, rel.data(), rel.size(), s);
+  blk->colidx.alloc((size_t)blk->nnz);
+  blk->val.alloc((size_t)blk->nnz);
+  if (blk->nnz) {
+    SPL_HIP(hipMemcpyAsync(blk->colidx.get(), full->colidx.get() + k0, (size_t)blk->nnz * sizeof(int),
+                           hipMemcpyDeviceToDevice, s));
+    SPL_HIP(hipMemcpyAsync(blk->val.get(), full->val.get() + k0, (size_t)blk->nnz * sizeof(double),
+                           hipMemcpyDeviceToDevice, s));
+  }
+  SPL_HIP(hipStreamSynchronize(s));
+  out = std::move(blk);
+  return SPL_OK;
+}
+
+// the finalized image of a real CSC 5-tuple, for the one-shot SpMV / SpMM calls
+int one_shot_image(int nrows, int ncols, const int *Ap, const int *Ai, const double *Ax, std::unique_ptr<Matrix> &m) {
+  int st = build_from_csc(1, nrows, ncols, Ap, Ai, Ax, 0, 1, m);
+  if (st == SPL_OK) finalize_matrix(m.get(), nullptr);
+  return st;
+}
+
+// a CSC 5-tuple as the caller passed it
+struct HostCsc {
+  int nrows, ncols;
+  const int *p, *i;
+  const double *x;
+};
+
+// a device result with 64-bit column pointers, as the SpGEMM / lin / kron kernels produce it
+struct DeviceResult {
+  DBuf<int64_t> p;
+  DBuf<int> i;
+  DBuf<double> x;
+  int64_t nnz = 0;
+};
+
+// the body of the one-shot binary operations (spl_spgemm, spl_lin, spl_kronecker and their complex forms), after the
+// caller's argument checks: upload A and B with vw doubles per value, op(A, B, C, s) on the device, download the
+// nrowsC x ncolsC result into the caller's *Cp / *Ci / *Cx; the shape is written on success only
+template <typename Op>
+int binary_one_shot(int vw, const HostCsc &a, const HostCsc &b, int64_t nrowsC, int64_t ncolsC, int *nrowsC_out,
+                    int *ncolsC_out, int **Cp, int **Ci, double **Cx, Op &&op) {
+  return guarded([&]() -> int {
+    (void)current_device();
+    hipStream_t s = nullptr;
+    DeviceCsc A, B;
+    int st = upload_csc(a.nrows, a.ncols, a.p, a.i, a.x, vw, A, s);
+    if (st != SPL_OK) return st;
+    st = upload_csc(b.nrows, b.ncols, b.p, b.i, b.x, vw, B, s);
+    if (st != SPL_OK) return st;
+    DeviceResult C;
+    op(A, B, C, s);
+    st = download_result(ncolsC, C.nnz, vw, C.p.get(), C.i.get(), C.x.get(), Cp, Ci, Cx, s);
+    if (st != SPL_OK) return st;
+    *nrowsC_out = (int)nrowsC;
+    *ncolsC_out = (int)ncolsC;
+    return SPL_OK;
+  });
 }
 
 // y (host) = A x (host) [+ y]
@@ -211,53 +341,21 @@ int spl_matrix_create_rowblock(int nrows, int ncols, const int *Ap, const int *A
   if (!H) return SPL_ERROR_argument_missing;
   *H = nullptr;
   return guarded([&]() -> int {
-    Matrix *m = nullptr;
-    int st = build_from_csc(nrows, ncols, Ap, Ai, Ax, part, nparts, &m);
-    if (st == SPL_OK) *H = m;
-    return st;
+    std::unique_ptr<Matrix> m;
+    int st = build_from_csc(1, nrows, ncols, Ap, Ai, Ax, part, nparts, m);
+    return st != SPL_OK ? st : publish(std::move(m), nullptr, H);
   });
 }
 
 // Complex Double: the CSC 5-tuple with packed (re, im) values (what the reference passes for its complex
-// instance, Umfpack/Internal.hs:124-132).  The row-major image is built by transposing the PATTERN with the
-// entry positions as payload and gathering the 16-byte values along the permutation.
+// instance, Umfpack/Internal.hs:124-132)
 int spl_matrix_create_z(int nrows, int ncols, const int *Ap, const int *Ai, const double *Az, void **H) {
   if (!H) return SPL_ERROR_argument_missing;
   *H = nullptr;
   return guarded([&]() -> int {
-    int st = check_tuple(nrows, ncols, Ap, Ai, Az);
-    if (st != SPL_OK) return st;
-    const int64_t nnz = Ap[ncols];
-    const int dev = current_device();
-    hipStream_t s = nullptr;
-    DBuf<int> dAp, dAi;
-    DBuf<double> dAz, dpos, dperm;
-    upload(dAp, Ap, (size_t)ncols + 1, s);
-    upload(dAi, Ai, (size_t)nnz, s);
-    upload(dAz, Az, (size_t)nnz * 2, s);
-    st = validate_compressed(dAp.get(), dAi.get(), ncols, nrows, nnz, s);
-    if (st != SPL_OK) return st;
-    dpos.alloc((size_t)nnz);
-    dperm.alloc((size_t)nnz);
-    fill_positions(nnz, dpos.get(), s);
-    std::unique_ptr<Matrix> m(new Matrix());
-    m->device = dev;
-    m->nrows_global = nrows;
-    m->ncols = ncols;
-    m->row0 = 0;
-    m->nrows_local = nrows;
-    m->nnz = nnz;
-    m->vw = 2;
-    m->rowptr64.alloc((size_t)nrows + 1);
-    m->colidx.alloc((size_t)nnz);
-    m->val.alloc((size_t)nnz * 2);
-    transpose_compressed(dAp.get(), dAi.get(), dpos.get(), ncols, nrows, nnz, m->rowptr64.get(), m->colidx.get(),
-                         dperm.get(), s);
-    gather_complex_values(nnz, dperm.get(), dAz.get(), m->val.get(), s);
-    SPL_HIP(hipStreamSynchronize(s));
-    finalize_matrix(m.get(), s);
-    *H = m.release();
-    return SPL_OK;
+    std::unique_ptr<Matrix> m;
+    int st = build_from_csc(2, nrows, ncols, Ap, Ai, Az, 0, 1, m);
+    return st != SPL_OK ? st : publish(std::move(m), nullptr, H);
   });
 }
 
@@ -280,29 +378,17 @@ int spl_matrix_create_csr(int64_t nrows_global, int64_t ncols, int64_t row0, int
   return guarded([&]() -> int {
     const int dev = current_device();
     hipStream_t s = nullptr;
-    Matrix *m = new Matrix();
-    try {
-      m->device = dev;
-      m->nrows_global = nrows_global;
-      m->ncols = ncols;
-      m->row0 = row0;
-      m->nrows_local = nrows_local;
-      m->nnz = nnz;
-      DBuf<int> dptr;
-      upload(dptr, rowptr, (size_t)nrows_local + 1, s);
-      upload(m->colidx, colidx, (size_t)nnz, s);
-      upload(m->val, val, (size_t)nnz, s);
-      int st = validate_compressed(dptr.get(), m->colidx.get(), nrows_local, ncols, nnz, s);
-      if (st != SPL_OK) { delete m; return st; }
-      m->rowptr64.alloc((size_t)nrows_local + 1);
-      widen_i32_to_i64(dptr.get(), m->rowptr64.get(), nrows_local + 1, s);
-      finalize_matrix(m, s);
-    } catch (...) {
-      delete m;
-      throw;
-    }
-    *H = m;
-    return SPL_OK;
+    std::unique_ptr<Matrix> m = make_matrix(dev, nrows_global, ncols, row0, nrows_local);
+    m->nnz = nnz;
+    DBuf<int> dptr;
+    upload(dptr, rowptr, (size_t)nrows_local + 1, s);
+    upload(m->colidx, colidx, (size_t)nnz, s);
+    upload(m->val, val, (size_t)nnz, s);
+    int st = validate_compressed(dptr.get(), m->colidx.get(), nrows_local, ncols, nnz, s);
+    if (st != SPL_OK) return st;
+    m->rowptr64.alloc((size_t)nrows_local + 1);
+    widen_i32_to_i64(dptr.get(), m->rowptr64.get(), nrows_local + 1, s);
+    return publish(std::move(m), s, H);
   });
 }
 
@@ -318,22 +404,9 @@ int spl_matrix_create_synthetic(int kind, int64_t n_or_m, int K, uint64_t seed, 
   if (n > 0x7fffffffLL) return SPL_ERROR_index_overflow;
   if (row0 < 0 || row1 < row0 || row1 > n) return SPL_ERROR_argument_missing;
   return guarded([&]() -> int {
-    const int dev = current_device();
-    Matrix *m = new Matrix();
-    try {
-      m->device = dev;
-      m->nrows_global = n;
-      m->ncols = n;
-      m->row0 = row0;
-      m->nrows_local = row1 - row0;
-      generate_synthetic(m, kind, n_or_m, K, seed, nullptr);
-      finalize_matrix(m, nullptr);
-    } catch (...) {
-      delete m;
-      throw;
-    }
-    *H = m;
-    return SPL_OK;
+    std::unique_ptr<Matrix> m = make_matrix(current_device(), n, n, row0, row1 - row0);
+    generate_synthetic(m.get(), kind, n_or_m, K, seed, nullptr);
+    return publish(std::move(m), nullptr, H);
   });
 }
 
@@ -361,25 +434,13 @@ int spl_matrix_create_rmat(int scale, int edge_factor, double a, double b, doubl
     int st = compress_device((int)n, (int)n, nedges, dc.get(), dr.get(), dv.get(), dptr.get(), oidx, oval, &nz,
                              &bad, s);
     if (st != SPL_OK) return st;
-    Matrix *m = new Matrix();
-    try {
-      m->device = dev;
-      m->nrows_global = n;
-      m->ncols = n;
-      m->row0 = 0;
-      m->nrows_local = n;
-      m->nnz = nz;
-      m->rowptr64.alloc((size_t)n + 1);
-      widen_i32_to_i64(dptr.get(), m->rowptr64.get(), n + 1, s);
-      m->colidx = std::move(oidx);
-      m->val = std::move(oval);
-      finalize_matrix(m, s);
-    } catch (...) {
-      delete m;
-      throw;
-    }
-    *H = m;
-    return SPL_OK;
+    std::unique_ptr<Matrix> m = make_matrix(dev, n, n, 0, n);
+    m->nnz = nz;
+    m->rowptr64.alloc((size_t)n + 1);
+    widen_i32_to_i64(dptr.get(), m->rowptr64.get(), n + 1, s);
+    m->colidx = std::move(oidx);
+    m->val = std::move(oval);
+    return publish(std::move(m), s, H);
   });
 }
 
@@ -395,28 +456,15 @@ int spl_matrix_spgemm(void *HA, void *HB, void **HC, int64_t *products) {
   return guarded([&]() -> int {
     DeviceGuard g(A->device);
     hipStream_t s = nullptr;
-    Matrix *C = new Matrix();
-    try {
-      C->device = A->device;
-      C->nrows_global = A->nrows_global;
-      C->ncols = B->ncols;
-      C->row0 = A->row0;
-      C->nrows_local = A->nrows_local;
-      // rows of A*B = columns of (A*B)^T = B^T * A^T: the CSR arrays of B and A are the CSC
-      // arrays of B^T and A^T, so the column-wise kernel runs on them unchanged
-      spgemm_device(B->ncols, B->nrows_global, B->rowptr.get(), B->colidx.get(), B->val.get(), A->nrows_local,
-                    A->rowptr.get(), A->colidx.get(), A->val.get(), C->rowptr64, C->colidx, C->val, &C->nnz,
-                    products, s);
-      finalize_matrix(C, s);
-    } catch (...) {
-      delete C;
-      throw;
-    }
-    *HC = C;
-    return SPL_OK;
+    std::unique_ptr<Matrix> C = make_matrix(A->device, A->nrows_global, B->ncols, A->row0, A->nrows_local);
+    // rows of A*B = columns of (A*B)^T = B^T * A^T: the CSR arrays of B and A are the CSC
+    // arrays of B^T and A^T, so the column-wise kernel runs on them unchanged
+    spgemm_device(B->ncols, B->nrows_global, B->rowptr.get(), B->colidx.get(), B->val.get(), A->nrows_local,
+                  A->rowptr.get(), A->colidx.get(), A->val.get(), C->rowptr64, C->colidx, C->val, &C->nnz,
+                  products, s);
+    return publish(std::move(C), s, HC);
   });
 }
-
 
 // ---- device-resident forms of lin / transpose / compress (round 3) -----------------------------------------
 // The host 5-tuple entry points (spl_lin, spl_transpose, spl_compress) pay PCIe and marshalling for kernels that
@@ -435,22 +483,14 @@ int spl_matrix_lin(void *HA, const double alpha[2], void *HB, const double beta[
   return guarded([&]() -> int {
     DeviceGuard g(A->device);
     hipStream_t s = nullptr;
-    std::unique_ptr<Matrix> C(new Matrix());
-    C->device = A->device;
-    C->nrows_global = A->nrows_global;
-    C->ncols = A->ncols;
-    C->row0 = A->row0;
-    C->nrows_local = A->nrows_local;
-    C->vw = A->vw;
+    std::unique_ptr<Matrix> C = make_matrix(A->device, A->nrows_global, A->ncols, A->row0, A->nrows_local, A->vw);
     if (A->vw == 1)
       lin_device(alpha[0], A->rowptr.get(), A->colidx.get(), A->val.get(), beta[0], B->rowptr.get(), B->colidx.get(),
                  B->val.get(), A->nrows_local, C->rowptr64, C->colidx, C->val, &C->nnz, s);
     else
       lin_device_z(alpha, A->rowptr.get(), A->colidx.get(), A->val.get(), beta, B->rowptr.get(), B->colidx.get(),
                    B->val.get(), A->nrows_local, C->rowptr64, C->colidx, C->val, &C->nnz, s);
-    finalize_matrix(C.get(), s);
-    *HC = C.release();
-    return SPL_OK;
+    return publish(std::move(C), s, HC);
   });
 }
 
@@ -472,14 +512,8 @@ int spl_matrix_to_complex(void *H, void **HZ) {
   return guarded([&]() -> int {
     DeviceGuard g(A->device);
     hipStream_t s = nullptr;
-    std::unique_ptr<Matrix> C(new Matrix());
-    C->device = A->device;
-    C->nrows_global = A->nrows_global;
-    C->ncols = A->ncols;
-    C->row0 = A->row0;
-    C->nrows_local = A->nrows_local;
+    std::unique_ptr<Matrix> C = make_matrix(A->device, A->nrows_global, A->ncols, A->row0, A->nrows_local, 2);
     C->nnz = A->nnz;
-    C->vw = 2;
     C->rowptr64.alloc((size_t)A->nrows_local + 1);
     SPL_HIP(hipMemcpyAsync(C->rowptr64.get(), A->rowptr64.get(), ((size_t)A->nrows_local + 1) * sizeof(int64_t),
                            hipMemcpyDeviceToDevice, s));
@@ -491,9 +525,7 @@ int spl_matrix_to_complex(void *H, void **HZ) {
       if (blocks > 65536) blocks = 65536;
       hipLaunchKernelGGL(promote_complex_kernel, dim3((unsigned)blocks), dim3(256), 0, s, A->val.get(), A->nnz, C->val.get());
     }
-    finalize_matrix(C.get(), s);
-    *HZ = C.release();
-    return SPL_OK;
+    return publish(std::move(C), s, HZ);
   });
 }
 
@@ -508,19 +540,14 @@ int spl_matrix_transpose(void *H, void **HT) {
   return guarded([&]() -> int {
     DeviceGuard g(A->device);
     hipStream_t s = nullptr;
-    std::unique_ptr<Matrix> C(new Matrix());
-    C->device = A->device;
-    C->nrows_global = C->nrows_local = A->ncols;
-    C->ncols = A->nrows_global;
+    std::unique_ptr<Matrix> C = make_matrix(A->device, A->ncols, A->nrows_global, 0, A->ncols);
     C->nnz = A->nnz;
     C->rowptr64.alloc((size_t)A->ncols + 1);
     C->colidx.alloc((size_t)A->nnz);
     C->val.alloc((size_t)A->nnz);
     transpose_compressed(A->rowptr.get(), A->colidx.get(), A->val.get(), A->nrows_local, A->ncols, A->nnz,
                          C->rowptr64.get(), C->colidx.get(), C->val.get(), s);
-    finalize_matrix(C.get(), s);
-    *HT = C.release();
-    return SPL_OK;
+    return publish(std::move(C), s, HT);
   });
 }
 
@@ -547,19 +574,14 @@ int spl_matrix_compress_dev(int nrows, int ncols, int64_t ntriples, const int *d
                                /*check_only=*/true);
       if (st != SPL_OK) { if (bad) *bad = where; return st; }
     }
-    std::unique_ptr<Matrix> C(new Matrix());
-    C->device = dev;
-    C->nrows_global = C->nrows_local = nrows;
-    C->ncols = ncols;
+    std::unique_ptr<Matrix> C = make_matrix(dev, nrows, ncols, 0, nrows);
     DBuf<int> ptr32((size_t)nrows + 1);
     int64_t where = -1;
     int st = compress_device(ncols, nrows, ntriples, d_cols, d_rows, d_vals, ptr32.get(), C->colidx, C->val, &C->nnz, &where, s, false);
     if (st != SPL_OK) { if (bad) *bad = where; return st; }
     C->rowptr64.alloc((size_t)nrows + 1);
     widen_i32_to_i64(ptr32.get(), C->rowptr64.get(), (int64_t)nrows + 1, s);
-    finalize_matrix(C.get(), s);
-    *H = C.release();
-    return SPL_OK;
+    return publish(std::move(C), s, H);
   });
 }
 
@@ -939,17 +961,9 @@ int spl_gaxpy(int nrows, int ncols, const int *Ap, const int *Ai, const double *
   // the reference checks dimensions before touching anything (Sparse.hs:438-445)
   if (nrows >= 0 && ncols >= 0 && (xlen != ncols || ylen != nrows)) return SPL_ERROR_dimension_mismatch;
   return guarded([&]() -> int {
-    Matrix *m = nullptr;
-    int st = build_from_csc(nrows, ncols, Ap, Ai, Ax, 0, 1, &m);
-    if (st != SPL_OK) return st;
-    try {
-      st = host_spmv(m, xlen, x, ylen, y, 1);
-    } catch (...) {
-      delete m;
-      throw;
-    }
-    delete m;
-    return st;
+    std::unique_ptr<Matrix> m;
+    int st = one_shot_image(nrows, ncols, Ap, Ai, Ax, m);
+    return st != SPL_OK ? st : host_spmv(m.get(), xlen, x, ylen, y, 1);
   });
 }
 
@@ -957,17 +971,9 @@ int spl_mulv(int nrows, int ncols, const int *Ap, const int *Ai, const double *A
              const double *x, double *y) {
   if (nrows >= 0 && ncols >= 0 && xlen != ncols) return SPL_ERROR_dimension_mismatch;
   return guarded([&]() -> int {
-    Matrix *m = nullptr;
-    int st = build_from_csc(nrows, ncols, Ap, Ai, Ax, 0, 1, &m);
-    if (st != SPL_OK) return st;
-    try {
-      st = host_spmv(m, xlen, x, nrows, y, 0);
-    } catch (...) {
-      delete m;
-      throw;
-    }
-    delete m;
-    return st;
+    std::unique_ptr<Matrix> m;
+    int st = one_shot_image(nrows, ncols, Ap, Ai, Ax, m);
+    return st != SPL_OK ? st : host_spmv(m.get(), xlen, x, nrows, y, 0);
   });
 }
 
@@ -992,24 +998,18 @@ int spl_mulm(int nrows, int ncols, const int *Ap, const int *Ai, const double *A
   if ((int64_t)brows * bcols > 0 && !B) return SPL_ERROR_argument_missing;
   if ((int64_t)nrows * bcols > 0 && !C) return SPL_ERROR_argument_missing;
   return guarded([&]() -> int {
-    Matrix *m = nullptr;
-    int st = build_from_csc(nrows, ncols, Ap, Ai, Ax, 0, 1, &m);
+    std::unique_ptr<Matrix> m;
+    int st = one_shot_image(nrows, ncols, Ap, Ai, Ax, m);
     if (st != SPL_OK) return st;
-    try {
-      hipStream_t s = nullptr;
-      const size_t nb = (size_t)brows * bcols, nc = (size_t)nrows * bcols;
-      DBuf<double> dB, dC(nc);
-      upload(dB, B, nb, s);
-      // the reference runs one axpy_ per column of B (Sparse.hs:482-488); the fused kernel reads A
-      // once for all columns and keeps each column's evaluation order
-      st = launch_spmm(m, dB.get(), dC.get(), bcols, 0, s);
-      if (st == SPL_OK && nc) SPL_HIP(hipMemcpyAsync(C, dC.get(), nc * sizeof(double), hipMemcpyDeviceToHost, s));
-      SPL_HIP(hipStreamSynchronize(s));
-    } catch (...) {
-      delete m;
-      throw;
-    }
-    delete m;
+    hipStream_t s = nullptr;
+    const size_t nb = (size_t)brows * bcols, nc = (size_t)nrows * bcols;
+    DBuf<double> dB, dC(nc);
+    upload(dB, B, nb, s);
+    // the reference runs one axpy_ per column of B (Sparse.hs:482-488); the fused kernel reads A
+    // once for all columns and keeps each column's evaluation order
+    st = launch_spmm(m.get(), dB.get(), dC.get(), bcols, 0, s);
+    if (st == SPL_OK && nc) SPL_HIP(hipMemcpyAsync(C, dC.get(), nc * sizeof(double), hipMemcpyDeviceToHost, s));
+    SPL_HIP(hipStreamSynchronize(s));
     return st;
   });
 }
@@ -1036,16 +1036,13 @@ int spl_transpose(int nrows, int ncols, const int *Ap, const int *Ai, const doub
   return guarded([&]() -> int {
     (void)current_device();
     hipStream_t s = nullptr;
-    DBuf<int> dAp, dAi, dTi((size_t)nnz), dTp((size_t)nrows + 1);
-    DBuf<double> dAx, dTx((size_t)nnz);
+    DeviceCsc A;
+    DBuf<int> dTi((size_t)nnz), dTp((size_t)nrows + 1);
+    DBuf<double> dTx((size_t)nnz);
     DBuf<int64_t> dTp64((size_t)nrows + 1);
-    upload(dAp, Ap, (size_t)ncols + 1, s);
-    upload(dAi, Ai, (size_t)nnz, s);
-    upload(dAx, Ax, (size_t)nnz, s);
-    int v = validate_compressed(dAp.get(), dAi.get(), ncols, nrows, nnz, s);
+    int v = upload_validated(nrows, ncols, Ap, Ai, Ax, 1, A, s);
     if (v != SPL_OK) return v;
-    transpose_compressed(dAp.get(), dAi.get(), dAx.get(), ncols, nrows, nnz, dTp64.get(), dTi.get(),
-                         dTx.get(), s);
+    transpose_compressed(A.p.get(), A.i.get(), A.x.get(), ncols, nrows, nnz, dTp64.get(), dTi.get(), dTx.get(), s);
     narrow_i64_to_i32(dTp64.get(), dTp.get(), (int64_t)nrows + 1, s);
     SPL_HIP(hipMemcpyAsync(Tp, dTp.get(), ((size_t)nrows + 1) * sizeof(int), hipMemcpyDeviceToHost, s));
     if (nnz) {
@@ -1057,67 +1054,7 @@ int spl_transpose(int nrows, int ncols, const int *Ap, const int *Ai, const doub
   });
 }
 
-}  // extern "C"
-
 // ---- assembly / SpGEMM one-shots ------------------------------------------------------------
-
-namespace {
-
-struct DeviceCsc {
-  DBuf<int> p, i;
-  DBuf<double> x;
-  int64_t nnz = 0;
-};
-
-// upload + validate a CSC 5-tuple; sort its columns if a caller violated the
-// ascending-row invariant (the reference's SPA does not care about input order)
-int upload_csc(int nrows, int ncols, const int *Ap, const int *Ai, const double *Ax, DeviceCsc &d,
-               hipStream_t s) {
-  int st = check_tuple(nrows, ncols, Ap, Ai, Ax);
-  if (st != SPL_OK) return st;
-  d.nnz = Ap[ncols];
-  upload(d.p, Ap, (size_t)ncols + 1, s);
-  upload(d.i, Ai, (size_t)d.nnz, s);
-  upload(d.x, Ax, (size_t)d.nnz, s);
-  st = validate_compressed(d.p.get(), d.i.get(), ncols, nrows, d.nnz, s);
-  if (st != SPL_OK) return st;
-  if (!columns_sorted(d.p.get(), d.i.get(), ncols, s)) {
-    DBuf<int64_t> p64((size_t)ncols + 1);
-    widen_i32_to_i64(d.p.get(), p64.get(), (int64_t)ncols + 1, s);
-    segmented_sort_pairs(p64.get(), ncols, d.i.get(), d.x.get(), s);
-    SPL_HIP(hipStreamSynchronize(s));
-  }
-  return SPL_OK;
-}
-
-// copy a device result into malloc()'d host arrays (adoptable by `fromForeign False`)
-int download_result(int64_t ncols, int64_t nnz, const int64_t *dCp64, const int *dCi, const double *dCx,
-                    int **Cp, int **Ci, double **Cx, hipStream_t s) {
-  if (nnz >= 0x7fffffffLL) return SPL_ERROR_index_overflow;
-  int *hp = (int *)malloc(((size_t)ncols + 1) * sizeof(int));
-  int *hi = (int *)malloc((size_t)(nnz ? nnz : 1) * sizeof(int));
-  double *hx = (double *)malloc((size_t)(nnz ? nnz : 1) * sizeof(double));
-  if (!hp || !hi || !hx) { free(hp); free(hi); free(hx); return SPL_ERROR_out_of_memory; }
-  try {
-    DBuf<int> dCp32((size_t)ncols + 1);
-    narrow_i64_to_i32(dCp64, dCp32.get(), ncols + 1, s);
-    SPL_HIP(hipMemcpyAsync(hp, dCp32.get(), ((size_t)ncols + 1) * sizeof(int), hipMemcpyDeviceToHost, s));
-    if (nnz) {
-      SPL_HIP(hipMemcpyAsync(hi, dCi, (size_t)nnz * sizeof(int), hipMemcpyDeviceToHost, s));
-      SPL_HIP(hipMemcpyAsync(hx, dCx, (size_t)nnz * sizeof(double), hipMemcpyDeviceToHost, s));
-    }
-    SPL_HIP(hipStreamSynchronize(s));
-  } catch (...) {
-    free(hp); free(hi); free(hx);
-    throw;
-  }
-  *Cp = hp; *Ci = hi; *Cx = hx;
-  return SPL_OK;
-}
-
-}  // namespace
-
-extern "C" {
 
 int spl_spgemm(int nrowsA, int ncolsA, const int *Ap, const int *Ai, const double *Ax, int nrowsB,
                int ncolsB, const int *Bp, const int *Bi, const double *Bx, int *nrowsC, int *ncolsC,
@@ -1126,26 +1063,11 @@ int spl_spgemm(int nrowsA, int ncolsA, const int *Ap, const int *Ai, const doubl
   *Cp = nullptr; *Ci = nullptr; *Cx = nullptr;
   if (nrowsA >= 0 && ncolsA >= 0 && nrowsB >= 0 && ncolsB >= 0 && ncolsA != nrowsB)
     return SPL_ERROR_dimension_mismatch;  // Sparse.hs:694
-  return guarded([&]() -> int {
-    (void)current_device();
-    hipStream_t s = nullptr;
-    DeviceCsc A, B;
-    int st = upload_csc(nrowsA, ncolsA, Ap, Ai, Ax, A, s);
-    if (st != SPL_OK) return st;
-    st = upload_csc(nrowsB, ncolsB, Bp, Bi, Bx, B, s);
-    if (st != SPL_OK) return st;
-    DBuf<int64_t> dCp;
-    DBuf<int> dCi;
-    DBuf<double> dCx;
-    int64_t nnzC = 0;
-    spgemm_device(nrowsA, ncolsA, A.p.get(), A.i.get(), A.x.get(), ncolsB, B.p.get(), B.i.get(), B.x.get(),
-                  dCp, dCi, dCx, &nnzC, nullptr, s);
-    st = download_result(ncolsB, nnzC, dCp.get(), dCi.get(), dCx.get(), Cp, Ci, Cx, s);
-    if (st != SPL_OK) return st;
-    *nrowsC = nrowsA;
-    *ncolsC = ncolsB;
-    return SPL_OK;
-  });
+  return binary_one_shot(1, {nrowsA, ncolsA, Ap, Ai, Ax}, {nrowsB, ncolsB, Bp, Bi, Bx}, nrowsA, ncolsB, nrowsC, ncolsC,
+                         Cp, Ci, Cx, [&](DeviceCsc &A, DeviceCsc &B, DeviceResult &C, hipStream_t s) {
+                           spgemm_device(nrowsA, ncolsA, A.p.get(), A.i.get(), A.x.get(), ncolsB, B.p.get(), B.i.get(),
+                                         B.x.get(), C.p, C.i, C.x, &C.nnz, nullptr, s);
+                         });
 }
 
 // hcat / vcat / fromBlocks / fromBlocksDiag (Sparse.hs:500-595): nblocks CSC blocks placed at (row_off, col_off)
@@ -1182,33 +1104,10 @@ int spl_assemble_blocks(int nblocks, const int *nrows, const int *ncols, const i
       pi[(size_t)b] = di[(size_t)b].get();
       px[(size_t)b] = dx[(size_t)b].get();
     }
-    DBuf<int64_t> dCp;
-    DBuf<int> dCi;
-    DBuf<double> dCx;
-    int64_t nnzC = 0;
-    blocks_assemble_device(nblocks, ncols, pp.data(), pi.data(), px.data(), value_width, row_off, col_off, ncolsC, dCp, dCi,
-                           dCx, &nnzC, s);
-    if (nnzC >= 0x7fffffffLL) return SPL_ERROR_index_overflow;
-    // download (values are value_width doubles per entry)
-    int *hp = (int *)malloc(((size_t)ncolsC + 1) * sizeof(int));
-    int *hi = (int *)malloc((size_t)(nnzC ? nnzC : 1) * sizeof(int));
-    double *hx = (double *)malloc((size_t)(nnzC ? nnzC : 1) * (size_t)value_width * sizeof(double));
-    if (!hp || !hi || !hx) { free(hp); free(hi); free(hx); return SPL_ERROR_out_of_memory; }
-    try {
-      DBuf<int> dCp32((size_t)ncolsC + 1);
-      narrow_i64_to_i32(dCp.get(), dCp32.get(), (int64_t)ncolsC + 1, s);
-      SPL_HIP(hipMemcpyAsync(hp, dCp32.get(), ((size_t)ncolsC + 1) * sizeof(int), hipMemcpyDeviceToHost, s));
-      if (nnzC) {
-        SPL_HIP(hipMemcpyAsync(hi, dCi.get(), (size_t)nnzC * sizeof(int), hipMemcpyDeviceToHost, s));
-        SPL_HIP(hipMemcpyAsync(hx, dCx.get(), (size_t)nnzC * (size_t)value_width * sizeof(double), hipMemcpyDeviceToHost, s));
-      }
-      SPL_HIP(hipStreamSynchronize(s));
-    } catch (...) {
-      free(hp); free(hi); free(hx);
-      throw;
-    }
-    *Cp = hp; *Ci = hi; *Cx = hx;
-    return SPL_OK;
+    DeviceResult C;
+    blocks_assemble_device(nblocks, ncols, pp.data(), pi.data(), px.data(), value_width, row_off, col_off, ncolsC, C.p,
+                           C.i, C.x, &C.nnz, s);
+    return download_result(ncolsC, C.nnz, value_width, C.p.get(), C.i.get(), C.x.get(), Cp, Ci, Cx, s);
   });
 }
 
@@ -1219,76 +1118,11 @@ int spl_lin(double alpha, int nrowsA, int ncolsA, const int *Ap, const int *Ai, 
   *Cp = nullptr; *Ci = nullptr; *Cx = nullptr;
   if (nrowsA >= 0 && ncolsA >= 0 && nrowsB >= 0 && ncolsB >= 0 && (nrowsA != nrowsB || ncolsA != ncolsB))
     return SPL_ERROR_dimension_mismatch;  // Sparse.hs:408-409
-  return guarded([&]() -> int {
-    (void)current_device();
-    hipStream_t s = nullptr;
-    DeviceCsc A, B;
-    int st = upload_csc(nrowsA, ncolsA, Ap, Ai, Ax, A, s);
-    if (st != SPL_OK) return st;
-    st = upload_csc(nrowsB, ncolsB, Bp, Bi, Bx, B, s);
-    if (st != SPL_OK) return st;
-    DBuf<int64_t> dCp;
-    DBuf<int> dCi;
-    DBuf<double> dCx;
-    int64_t nnzC = 0;
-    lin_device(alpha, A.p.get(), A.i.get(), A.x.get(), beta, B.p.get(), B.i.get(), B.x.get(), ncolsA, dCp,
-               dCi, dCx, &nnzC, s);
-    st = download_result(ncolsA, nnzC, dCp.get(), dCi.get(), dCx.get(), Cp, Ci, Cx, s);
-    if (st != SPL_OK) return st;
-    *nrowsC = nrowsA;
-    *ncolsC = ncolsA;
-    return SPL_OK;
-  });
-}
-
-// upload + validate a packed-complex CSC 5-tuple; unsorted columns are sorted by row with the values following
-// their positions
-static int upload_csc_z(int nrows, int ncols, const int *Ap, const int *Ai, const double *Az, DeviceCsc &d,
-                        hipStream_t s) {
-  int st = check_tuple(nrows, ncols, Ap, Ai, Az);
-  if (st != SPL_OK) return st;
-  d.nnz = Ap[ncols];
-  upload(d.p, Ap, (size_t)ncols + 1, s);
-  upload(d.i, Ai, (size_t)d.nnz, s);
-  upload(d.x, Az, (size_t)d.nnz * 2, s);
-  st = validate_compressed(d.p.get(), d.i.get(), ncols, nrows, d.nnz, s);
-  if (st != SPL_OK) return st;
-  if (!columns_sorted(d.p.get(), d.i.get(), ncols, s)) {
-    DBuf<int64_t> p64((size_t)ncols + 1);
-    DBuf<double> pos((size_t)d.nnz), sorted((size_t)d.nnz * 2);
-    widen_i32_to_i64(d.p.get(), p64.get(), (int64_t)ncols + 1, s);
-    fill_positions(d.nnz, pos.get(), s);
-    segmented_sort_pairs(p64.get(), ncols, d.i.get(), pos.get(), s);
-    gather_complex_values(d.nnz, pos.get(), d.x.get(), sorted.get(), s);
-    SPL_HIP(hipStreamSynchronize(s));
-    d.x = std::move(sorted);
-  }
-  return SPL_OK;
-}
-
-// copy a packed-complex device result into malloc()'d host arrays
-static int download_result_z(int64_t ncols, int64_t nnz, const int64_t *dCp64, const int *dCi, const double *dCz,
-                             int **Cp, int **Ci, double **Cz, hipStream_t s) {
-  if (nnz >= 0x7fffffffLL) return SPL_ERROR_index_overflow;
-  int *hp = (int *)malloc(((size_t)ncols + 1) * sizeof(int));
-  int *hi = (int *)malloc((size_t)(nnz ? nnz : 1) * sizeof(int));
-  double *hz = (double *)malloc((size_t)(nnz ? nnz : 1) * 2 * sizeof(double));
-  if (!hp || !hi || !hz) { free(hp); free(hi); free(hz); return SPL_ERROR_out_of_memory; }
-  try {
-    DBuf<int> dCp32((size_t)ncols + 1);
-    narrow_i64_to_i32(dCp64, dCp32.get(), ncols + 1, s);
-    SPL_HIP(hipMemcpyAsync(hp, dCp32.get(), ((size_t)ncols + 1) * sizeof(int), hipMemcpyDeviceToHost, s));
-    if (nnz) {
-      SPL_HIP(hipMemcpyAsync(hi, dCi, (size_t)nnz * sizeof(int), hipMemcpyDeviceToHost, s));
-      SPL_HIP(hipMemcpyAsync(hz, dCz, (size_t)nnz * 2 * sizeof(double), hipMemcpyDeviceToHost, s));
-    }
-    SPL_HIP(hipStreamSynchronize(s));
-  } catch (...) {
-    free(hp); free(hi); free(hz);
-    throw;
-  }
-  *Cp = hp; *Ci = hi; *Cz = hz;
-  return SPL_OK;
+  return binary_one_shot(1, {nrowsA, ncolsA, Ap, Ai, Ax}, {nrowsB, ncolsB, Bp, Bi, Bx}, nrowsA, ncolsA, nrowsC, ncolsC,
+                         Cp, Ci, Cx, [&](DeviceCsc &A, DeviceCsc &B, DeviceResult &C, hipStream_t s) {
+                           lin_device(alpha, A.p.get(), A.i.get(), A.x.get(), beta, B.p.get(), B.i.get(), B.x.get(),
+                                      ncolsA, C.p, C.i, C.x, &C.nnz, s);
+                         });
 }
 
 int spl_spgemm_z(int nrowsA, int ncolsA, const int *Ap, const int *Ai, const double *Az, int nrowsB, int ncolsB,
@@ -1298,26 +1132,11 @@ int spl_spgemm_z(int nrowsA, int ncolsA, const int *Ap, const int *Ai, const dou
   *Cp = nullptr; *Ci = nullptr; *Cz = nullptr;
   if (nrowsA >= 0 && ncolsA >= 0 && nrowsB >= 0 && ncolsB >= 0 && ncolsA != nrowsB)
     return SPL_ERROR_dimension_mismatch;  // Sparse.hs:694
-  return guarded([&]() -> int {
-    (void)current_device();
-    hipStream_t s = nullptr;
-    DeviceCsc A, B;
-    int st = upload_csc_z(nrowsA, ncolsA, Ap, Ai, Az, A, s);
-    if (st != SPL_OK) return st;
-    st = upload_csc_z(nrowsB, ncolsB, Bp, Bi, Bz, B, s);
-    if (st != SPL_OK) return st;
-    DBuf<int64_t> dCp;
-    DBuf<int> dCi;
-    DBuf<double> dCz;
-    int64_t nnzC = 0;
-    spgemm_device_z(nrowsA, ncolsA, A.p.get(), A.i.get(), A.x.get(), ncolsB, B.p.get(), B.i.get(), B.x.get(), dCp, dCi,
-                    dCz, &nnzC, s);
-    st = download_result_z(ncolsB, nnzC, dCp.get(), dCi.get(), dCz.get(), Cp, Ci, Cz, s);
-    if (st != SPL_OK) return st;
-    *nrowsC = nrowsA;
-    *ncolsC = ncolsB;
-    return SPL_OK;
-  });
+  return binary_one_shot(2, {nrowsA, ncolsA, Ap, Ai, Az}, {nrowsB, ncolsB, Bp, Bi, Bz}, nrowsA, ncolsB, nrowsC, ncolsC,
+                         Cp, Ci, Cz, [&](DeviceCsc &A, DeviceCsc &B, DeviceResult &C, hipStream_t s) {
+                           spgemm_device_z(nrowsA, ncolsA, A.p.get(), A.i.get(), A.x.get(), ncolsB, B.p.get(),
+                                           B.i.get(), B.x.get(), C.p, C.i, C.x, &C.nnz, s);
+                         });
 }
 
 int spl_lin_z(const double alpha[2], int nrowsA, int ncolsA, const int *Ap, const int *Ai, const double *Az,
@@ -1327,26 +1146,11 @@ int spl_lin_z(const double alpha[2], int nrowsA, int ncolsA, const int *Ap, cons
   *Cp = nullptr; *Ci = nullptr; *Cz = nullptr;
   if (nrowsA >= 0 && ncolsA >= 0 && nrowsB >= 0 && ncolsB >= 0 && (nrowsA != nrowsB || ncolsA != ncolsB))
     return SPL_ERROR_dimension_mismatch;  // Sparse.hs:408-409
-  return guarded([&]() -> int {
-    (void)current_device();
-    hipStream_t s = nullptr;
-    DeviceCsc A, B;
-    int st = upload_csc_z(nrowsA, ncolsA, Ap, Ai, Az, A, s);
-    if (st != SPL_OK) return st;
-    st = upload_csc_z(nrowsB, ncolsB, Bp, Bi, Bz, B, s);
-    if (st != SPL_OK) return st;
-    DBuf<int64_t> dCp;
-    DBuf<int> dCi;
-    DBuf<double> dCz;
-    int64_t nnzC = 0;
-    lin_device_z(alpha, A.p.get(), A.i.get(), A.x.get(), beta, B.p.get(), B.i.get(), B.x.get(), ncolsA, dCp, dCi,
-                 dCz, &nnzC, s);
-    st = download_result_z(ncolsA, nnzC, dCp.get(), dCi.get(), dCz.get(), Cp, Ci, Cz, s);
-    if (st != SPL_OK) return st;
-    *nrowsC = nrowsA;
-    *ncolsC = ncolsA;
-    return SPL_OK;
-  });
+  return binary_one_shot(2, {nrowsA, ncolsA, Ap, Ai, Az}, {nrowsB, ncolsB, Bp, Bi, Bz}, nrowsA, ncolsA, nrowsC, ncolsC,
+                         Cp, Ci, Cz, [&](DeviceCsc &A, DeviceCsc &B, DeviceResult &C, hipStream_t s) {
+                           lin_device_z(alpha, A.p.get(), A.i.get(), A.x.get(), beta, B.p.get(), B.i.get(), B.x.get(),
+                                        ncolsA, C.p, C.i, C.x, &C.nnz, s);
+                         });
 }
 
 int spl_kronecker(int nrowsA, int ncolsA, const int *Ap, const int *Ai, const double *Ax, int nrowsB,
@@ -1357,26 +1161,12 @@ int spl_kronecker(int nrowsA, int ncolsA, const int *Ap, const int *Ai, const do
   if (nrowsA < 0 || ncolsA < 0 || nrowsB < 0 || ncolsB < 0) return SPL_ERROR_n_nonpositive;
   if ((int64_t)nrowsA * nrowsB >= 0x7fffffffLL || (int64_t)ncolsA * ncolsB >= 0x7fffffffLL)
     return SPL_ERROR_index_overflow;  // the seam is int32 (Foreign.hs:24-28)
-  return guarded([&]() -> int {
-    (void)current_device();
-    hipStream_t s = nullptr;
-    DeviceCsc A, B;
-    int st = upload_csc(nrowsA, ncolsA, Ap, Ai, Ax, A, s);
-    if (st != SPL_OK) return st;
-    st = upload_csc(nrowsB, ncolsB, Bp, Bi, Bx, B, s);
-    if (st != SPL_OK) return st;
-    DBuf<int64_t> dCp;
-    DBuf<int> dCi;
-    DBuf<double> dCx;
-    int64_t nnzC = 0;
-    kronecker_device(nrowsB, A.p.get(), A.i.get(), A.x.get(), ncolsA, B.p.get(), B.i.get(), B.x.get(), ncolsB,
-                     dCp, dCi, dCx, &nnzC, s);
-    st = download_result((int64_t)ncolsA * ncolsB, nnzC, dCp.get(), dCi.get(), dCx.get(), Cp, Ci, Cx, s);
-    if (st != SPL_OK) return st;
-    *nrowsC = nrowsA * nrowsB;
-    *ncolsC = ncolsA * ncolsB;
-    return SPL_OK;
-  });
+  return binary_one_shot(1, {nrowsA, ncolsA, Ap, Ai, Ax}, {nrowsB, ncolsB, Bp, Bi, Bx}, (int64_t)nrowsA * nrowsB,
+                         (int64_t)ncolsA * ncolsB, nrowsC, ncolsC, Cp, Ci, Cx,
+                         [&](DeviceCsc &A, DeviceCsc &B, DeviceResult &C, hipStream_t s) {
+                           kronecker_device(nrowsB, A.p.get(), A.i.get(), A.x.get(), ncolsA, B.p.get(), B.i.get(),
+                                            B.x.get(), ncolsB, C.p, C.i, C.x, &C.nnz, s);
+                         });
 }
 
 int spl_take_diag(int nrows, int ncols, const int *Ap, const int *Ai, const double *Ax, double *d) {
@@ -1387,7 +1177,7 @@ int spl_take_diag(int nrows, int ncols, const int *Ap, const int *Ai, const doub
     (void)current_device();
     hipStream_t s = nullptr;
     DeviceCsc A;
-    int st = upload_csc(nrows, ncols, Ap, Ai, Ax, A, s);
+    int st = upload_csc(nrows, ncols, Ap, Ai, Ax, 1, A, s);
     if (st != SPL_OK) return st;
     if (n == 0) return SPL_OK;
     DBuf<double> dd((size_t)n);
@@ -1418,22 +1208,18 @@ int spl_compress(int nrows, int ncols, int64_t nnz, const int *rows, const int *
     int st = compress_device(nrows, ncols, nnz, dr.get(), dc.get(), dv.get(), dptr.get(), oidx, oval, &nz,
                              bad, s);
     if (st != SPL_OK) return st;
-    int *hi = (int *)malloc((size_t)(nz ? nz : 1) * sizeof(int));
-    double *hx = (double *)malloc((size_t)(nz ? nz : 1) * sizeof(double));
-    if (!hi || !hx) { free(hi); free(hx); return SPL_ERROR_out_of_memory; }
-    try {
-      SPL_HIP(hipMemcpyAsync(Ap, dptr.get(), ((size_t)ncols + 1) * sizeof(int), hipMemcpyDeviceToHost, s));
-      if (nz) {
-        SPL_HIP(hipMemcpyAsync(hi, oidx.get(), (size_t)nz * sizeof(int), hipMemcpyDeviceToHost, s));
-        SPL_HIP(hipMemcpyAsync(hx, oval.get(), (size_t)nz * sizeof(double), hipMemcpyDeviceToHost, s));
-      }
-      SPL_HIP(hipStreamSynchronize(s));
-    } catch (...) {
-      free(hi); free(hx);
-      throw;
+    // Ap is the caller's (32-bit pointers straight from the kernel); the entries are malloc()'d like download_result's
+    HostArray<int> hi = host_alloc<int>((size_t)(nz ? nz : 1));
+    HostArray<double> hx = host_alloc<double>((size_t)(nz ? nz : 1));
+    if (!hi || !hx) return SPL_ERROR_out_of_memory;
+    SPL_HIP(hipMemcpyAsync(Ap, dptr.get(), ((size_t)ncols + 1) * sizeof(int), hipMemcpyDeviceToHost, s));
+    if (nz) {
+      SPL_HIP(hipMemcpyAsync(hi.get(), oidx.get(), (size_t)nz * sizeof(int), hipMemcpyDeviceToHost, s));
+      SPL_HIP(hipMemcpyAsync(hx.get(), oval.get(), (size_t)nz * sizeof(double), hipMemcpyDeviceToHost, s));
     }
-    *Ai = hi;
-    *Ax = hx;
+    SPL_HIP(hipStreamSynchronize(s));
+    *Ai = hi.release();
+    *Ax = hx.release();
     return SPL_OK;
   });
 }
