@@ -9,6 +9,9 @@ be the next x.  A "step" is one SpMV over the whole matrix (plus the all-gather
 at N > 1).  Inputs are generated in HBM by counter-based generators
 (include/spl_synth.h) and are resident before the timed region starts.
 
+A plain run sets up, warms up, times the K steps, writes --dump-outputs and prints the result line with the
+headline figure and its configuration, and nothing else.  Everything below `value` is measured only with --full.
+
   value     = algorithmic bytes of ONE whole-matrix SpMV / (time per step)   [GB/s]
               B = 12*nnz + 4*(nrows+1) + 8*ncols + 8*nrows   
   roofline  = the SpMV kernel alone on this rank: its own algorithmic bytes per
@@ -17,13 +20,15 @@ at N > 1).  Inputs are generated in HBM by counter-based generators
               reference's mulV (serial CSC scatter, 64-bit indices,
               Sparse.hs:433-471) on the same matrix, 1 core; its result is also
               compared element-wise with the GPU's y (1e-10 relative).
+  y_sha1, y_sum, y_norm2 = fingerprint of the whole y after one more step
+              (equal for every N and exchange under --order reference).
 
   secondary (N = 1 only, after the timed region; --no-secondary skips it) = the other configurations of
               BASELINE.json the driver's one line can carry: the banded variant of C2, C4 (SpGEMM A*A, R-MAT
               scale 20) and the C5 ladder (sparse LU + solves, 100^3 and, memory permitting, 200^3), each with
               its own roofline and parity fields (tools/bench_secondary.py).
 
-Launch: python bench.py [--gpus N --steps K --warmup W]; for N > 1 either under
+Launch: python bench.py [--gpus N --steps K --warmup W] [--full]; for N > 1 either under
 python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ... (one rank per GPU), or plainly as
 python bench.py --gpus N: without WORLD_SIZE in the environment the script starts that launcher itself, as a
 child process and before anything touches a GPU, and exits with its status.
@@ -76,11 +81,14 @@ def main():
                     help="order of the floating-point sums: free = any order (1e-10 contract, column-sorted panel "
                          "kernel where it pays), reference = the reference's order, bit-identical (spl_matrix_set_spmv_order)")
     ap.add_argument("--panel", default="", help="force the column-sorted panel image: rows_per_panel,cols_log2[,unroll[,form]]")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed region, also measure the kernel's roofline, fingerprint y, run the CPU baseline "
+                         "with its parity check and the secondary configurations (N = 1); a plain run prints the headline only")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline and parity check")
     ap.add_argument("--cpu-reps", type=int, default=3)
-    ap.add_argument("--no-secondary", action="store_true", help="skip the banded / C4 / C5 block after the timed region")
+    ap.add_argument("--no-secondary", action="store_true", help="--full without the banded / C4 / C5 block after the timed region")
     ap.add_argument("--secondary", default="c5:200:cpu32,banded,spmv:poisson3d:200,spmv:rmat:20,c4,c5:100,zi:100,feast:80",
-                    help="which secondary configurations to run, in this order, each in a child process of its own (comma "
+                    help="under --full: which secondary configurations to run, in this order, each in a child process of its own (comma "
                          "separated: banded, c4[:<scale>], c5:<m>[:cpu<ms>], zi:<m>, feast:<m>, spmv:poisson3d:<m>, spmv:rmat:<scale>); the "
                          "200^3 factorisation comes first: it asks the driver for 255 GB, and memory other configurations have "
                          "just released is still being wiped in the background (DESIGN.md, Device memory)")
@@ -366,55 +374,6 @@ def main():
     ms_per_step = 1e3 * elapsed / args.steps
     value = B_total / (elapsed / args.steps) / 1e9
 
-    # ---- roofline of the dominant kernel: HIP events on the launch stream, kernel only
-    ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    torch.cuda.synchronize()
-    ev0.record(stream)
-    for _ in range(args.steps):
-        spmv()
-    ev1.record(stream)
-    torch.cuda.synchronize()
-    kern_ms = ev0.elapsed_time(ev1) / args.steps
-    achieved = B_local / (kern_ms * 1e-3) / 1e9
-    kcode = handles[0].spmv_kernel()
-    kernel = {8: "spmv_blocked_lockstep", 15: "spmv_sell", 16: "spmv_panel"}.get(kcode, "spmv_stream")
-    # HBM/fabric bytes per launch from the committed rocprofv3 PMC passes (N = 1, default sizes only).  The
-    # figure belongs to the kernel SOURCE it was measured on: profiles/traffic.json carries the SHA-1 of that
-    # file (tools/update_traffic.py writes both), and a figure whose source has changed since is not reported.
-    traffic, traffic_note = None, None
-    tfile = os.path.join(ROOT, "profiles", "traffic.json")
-    if N == 1 and n == 10_000_000 and args.draws == 20 and os.path.exists(tfile):
-        import hashlib
-        ent = json.load(open(tfile)).get("%s:%s" % (args.matrix, kernel))
-        if ent:
-            src = os.path.join(ROOT, ent["source"])
-            now = hashlib.sha1(open(src, "rb").read()).hexdigest() if os.path.exists(src) else None
-            if now == ent["source_sha1"]:
-                traffic = ent["traffic_bytes"]
-            else:
-                traffic_note = "stale: %s changed since %s was collected" % (ent["source"], ent["from"])
-    # What the memory pipeline allows for this mix.  The L2 takes one request per channel and
-    # clock: 263 G requests/s chip-wide whatever their size (tools/probe/gather_probe2, row A) — request_bound_ms
-    # is the kernel's L2 requests (x gathers that do not share a line + the lines of the matrix stream) at that
-    # rate, i.e. the floor if the stream overlapped the gathers perfectly.  It does not: a CU's HBM stream and
-    # its L2 gathers share the vector L1's miss slots and their times add up (tools/probe/tcp_mix_probe, every
-    # cache policy: tcp_policy_probe) — slot_model_ms = gather requests / 263e9 + stream bytes / 6.5e12.
-    request_bound_ms = slot_model_ms = None
-    if kernel in ("spmv_panel", "spmv_blocked_lockstep") and N == 1:
-        per_entry = 0.75 if kernel == "spmv_panel" else 1.0  # gather requests per stored entry (PMC: TCP_TCC_READ_REQ)
-        request_bound_ms = round(1e3 * (per_entry * nnz_local + 12.0 * nnz_local / 128.0) / 263e9, 4)
-        slot_model_ms = round(1e3 * (per_entry * nnz_local / 263e9 + 12.0 * nnz_local / 6.5e12), 4)
-    roofline = {"bound": "hbm", "achieved": round(achieved, 1), "peak": HBM_PEAK_GBPS, "unit": "GB/s",
-                "frac": round(achieved / HBM_PEAK_GBPS, 4), "traffic": traffic,
-                "kernel": kernel, "kernel_ms": round(kern_ms, 4), "bytes_per_launch": B_local,
-                "request_bound_ms": request_bound_ms, "slot_model_ms": slot_model_ms}
-    if traffic_note:
-        roofline["traffic_note"] = traffic_note
-    if kcode == 8:
-        roofline["image"] = "blocked %d rows x 2^%d cols" % (info["blocked_rows"], info["blocked_cols_log2"])
-    elif kcode == 16:
-        roofline["image"] = "panels %d rows x 2^%d cols" % (info["blocked_rows"], info["blocked_cols_log2"])
-
     out = {
         "metric": "fp64 CSR SpMV effective GB/s", "value": round(value, 1), "unit": "GB/s",
         "n_gpus": N, "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(ms_per_step, 4),
@@ -425,27 +384,80 @@ def main():
                                   "" if N == 1 else ", %d row blocks, exchange of y: %s" % (N, exchange)),
                    "algorithmic_bytes": B_total, "hbm_frac_of_%dx8TBps" % N: round(value / (N * HBM_PEAK_GBPS), 4),
                    "sum_order": args.order},
-        "roofline": roofline,
     }
     if args.variant or args.blocked or args.panel:  # forced kernel / image (ablations): said only when not the default choice
         out["config"]["forced"] = {"variant": args.variant, "blocked": args.blocked, "panel": args.panel}
-    # fingerprint of the whole y every rank holds after the last step: equal for every N and exchange
-    import hashlib
-    step()
-    torch.cuda.synchronize()
-    barrier()  # one-sided exchange: no rank may release its receive buffers while a peer is still storing
-    yh = op.y_full.cpu().numpy()
-    out["y_sha1"] = hashlib.sha1(yh.tobytes()).hexdigest()  # equal for every N under --order reference
-    out["y_sum"], out["y_norm2"] = float("%.13g" % yh.sum()), float("%.13g" % np.sqrt((yh * yh).sum()))  # equal to ~1e-15 under either order
     if tuning:
         out["config"]["exchange_ms_per_step_by_chunks"] = tuning  # measured before the timed region
     if fell_back:
         out["config"]["exchange_fallback"] = "the one-sided exchange gave up during the timed region; the region was timed again over RCCL"
-    if len(handles) > 1:
-        roofline["launches_per_step"] = len(handles)
 
-    # ---- CPU baseline beside it (rank 0, N = 1): the reference's own algorithm, 1 core
-    if N == 1 and rank == 0 and not args.no_cpu_baseline:
+    # ---- --full only: whatever else is measured or checked after the timed region
+    roofline = None
+    if args.full:
+        # roofline of the dominant kernel: HIP events on the launch stream, kernel only
+        ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        torch.cuda.synchronize()
+        ev0.record(stream)
+        for _ in range(args.steps):
+            spmv()
+        ev1.record(stream)
+        torch.cuda.synchronize()
+        kern_ms = ev0.elapsed_time(ev1) / args.steps
+        achieved = B_local / (kern_ms * 1e-3) / 1e9
+        kcode = handles[0].spmv_kernel()
+        kernel = {8: "spmv_blocked_lockstep", 15: "spmv_sell", 16: "spmv_panel"}.get(kcode, "spmv_stream")
+        # HBM/fabric bytes per launch from the committed rocprofv3 PMC passes (N = 1, default sizes only).  The
+        # figure belongs to the kernel SOURCE it was measured on: profiles/traffic.json carries the SHA-1 of that
+        # file (tools/update_traffic.py writes both), and a figure whose source has changed since is not reported.
+        traffic, traffic_note = None, None
+        tfile = os.path.join(ROOT, "profiles", "traffic.json")
+        if N == 1 and n == 10_000_000 and args.draws == 20 and os.path.exists(tfile):
+            import hashlib
+            ent = json.load(open(tfile)).get("%s:%s" % (args.matrix, kernel))
+            if ent:
+                src = os.path.join(ROOT, ent["source"])
+                now = hashlib.sha1(open(src, "rb").read()).hexdigest() if os.path.exists(src) else None
+                if now == ent["source_sha1"]:
+                    traffic = ent["traffic_bytes"]
+                else:
+                    traffic_note = "stale: %s changed since %s was collected" % (ent["source"], ent["from"])
+        # What the memory pipeline allows for this mix.  The L2 takes one request per channel and
+        # clock: 263 G requests/s chip-wide whatever their size (tools/probe/gather_probe2, row A) — request_bound_ms
+        # is the kernel's L2 requests (x gathers that do not share a line + the lines of the matrix stream) at that
+        # rate, i.e. the floor if the stream overlapped the gathers perfectly.  It does not: a CU's HBM stream and
+        # its L2 gathers share the vector L1's miss slots and their times add up (tools/probe/tcp_mix_probe, every
+        # cache policy: tcp_policy_probe) — slot_model_ms = gather requests / 263e9 + stream bytes / 6.5e12.
+        request_bound_ms = slot_model_ms = None
+        if kernel in ("spmv_panel", "spmv_blocked_lockstep") and N == 1:
+            per_entry = 0.75 if kernel == "spmv_panel" else 1.0  # gather requests per stored entry (PMC: TCP_TCC_READ_REQ)
+            request_bound_ms = round(1e3 * (per_entry * nnz_local + 12.0 * nnz_local / 128.0) / 263e9, 4)
+            slot_model_ms = round(1e3 * (per_entry * nnz_local / 263e9 + 12.0 * nnz_local / 6.5e12), 4)
+        roofline = {"bound": "hbm", "achieved": round(achieved, 1), "peak": HBM_PEAK_GBPS, "unit": "GB/s",
+                    "frac": round(achieved / HBM_PEAK_GBPS, 4), "traffic": traffic,
+                    "kernel": kernel, "kernel_ms": round(kern_ms, 4), "bytes_per_launch": B_local,
+                    "request_bound_ms": request_bound_ms, "slot_model_ms": slot_model_ms}
+        if traffic_note:
+            roofline["traffic_note"] = traffic_note
+        if kcode == 8:
+            roofline["image"] = "blocked %d rows x 2^%d cols" % (info["blocked_rows"], info["blocked_cols_log2"])
+        elif kcode == 16:
+            roofline["image"] = "panels %d rows x 2^%d cols" % (info["blocked_rows"], info["blocked_cols_log2"])
+        if len(handles) > 1:
+            roofline["launches_per_step"] = len(handles)
+        out["roofline"] = roofline
+
+        # fingerprint of the whole y every rank holds after the last step: equal for every N and exchange
+        import hashlib
+        step()
+        torch.cuda.synchronize()
+        barrier()  # one-sided exchange: no rank may release its receive buffers while a peer is still storing
+        yh = op.y_full.cpu().numpy()
+        out["y_sha1"] = hashlib.sha1(yh.tobytes()).hexdigest()  # equal for every N under --order reference
+        out["y_sum"], out["y_norm2"] = float("%.13g" % yh.sum()), float("%.13g" % np.sqrt((yh * yh).sum()))  # equal to ~1e-15 under either order
+
+    # ---- --full: CPU baseline beside it (rank 0, N = 1): the reference's own algorithm, 1 core
+    if args.full and N == 1 and rank == 0 and not args.no_cpu_baseline:
         from oracle import oracle as O
         y_gpu = y_local.cpu().numpy()
         cp, ri, v = H.export_csc()  # CSC(A): the reference's Matrix fields
@@ -478,12 +490,12 @@ def main():
     if exchange_failed:
         out["invalid"] = "the one-sided exchange of y timed out on at least one rank: y is incomplete, the figures mean nothing"
 
-    # ---- the other configurations of BASELINE.json (N = 1): C5 LU ladder, banded C2, C4 SpGEMM, SpMV on their matrices.
+    # ---- --full: the other configurations of BASELINE.json (N = 1): C5 LU ladder, banded C2, C4 SpGEMM, SpMV on their matrices.
     # Each runs in a child process of its own (tools/bench_secondary.py --item ...) with a time limit: whatever
     # happens there — a device fault, an out-of-memory kill, a hang — costs that item, never the headline line
     # measured above; and a factorisation measured in a fresh process IS the one-shot case.  This parent
     # releases its device memory first and only waits; it is never replaced by another program.
-    if N == 1 and rank == 0 and not args.no_secondary and args.secondary:
+    if args.full and N == 1 and rank == 0 and not args.no_secondary and args.secondary:
         import gc
         import subprocess
         for h in handles:
@@ -522,7 +534,8 @@ def main():
 
     if rank == 0 and N > 1:
         # the last line on stderr, <= 500 bytes: what a failed or odd-looking scaling run is diagnosed from
-        brief = {"n_gpus": N, "value": out["value"], "ms_per_step": out["ms_per_step"], "kernel_ms": roofline["kernel_ms"],
+        brief = {"n_gpus": N, "value": out["value"], "ms_per_step": out["ms_per_step"],
+                 "kernel_ms": roofline["kernel_ms"] if roofline else None,
                  "exchange": exchange[:120], "tournament": tuning, "fell_back": fell_back}
         line = json.dumps(brief, separators=(",", ":"))
         sys.stderr.write("\n" + (line if len(line) <= 500 else json.dumps({k: brief[k] for k in ("n_gpus", "value", "ms_per_step", "kernel_ms", "fell_back")})) + "\n")

@@ -22,7 +22,7 @@ def _free_port():
     return p
 
 
-def _run(nproc, extra, chunks=None, exchange=None, plain=False, env_extra=None, want_stderr=False, drop_env=()):
+def _run(nproc, extra, chunks=None, exchange=None, plain=False, env_extra=None, want_stderr=False, drop_env=(), full=True):
     env = dict(os.environ, SPL_BENCH_REHEARSAL="1", HSA_ENABLE_IPC_MODE_LEGACY="0")
     env.update(env_extra or {})
     for k in drop_env:
@@ -38,7 +38,9 @@ def _run(nproc, extra, chunks=None, exchange=None, plain=False, env_extra=None, 
     else:
         cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(nproc),
                "--master-addr", "127.0.0.1", "--master-port", str(_free_port()), os.path.join(ROOT, "bench.py")]
-    cmd += ["--gpus", str(nproc), "--steps", "3", "--warmup", "1", "--no-cpu-baseline", "--no-secondary"]
+    cmd += ["--gpus", str(nproc), "--steps", "3", "--warmup", "1"]
+    if full:  # roofline and the fingerprint of y; the CPU baseline and the secondary block are not wanted here
+        cmd += ["--full", "--no-cpu-baseline", "--no-secondary"]
     if "--order" not in extra:
         cmd += ["--order", "reference"]  # bit-identical sums: the SHA-1 of y must not depend on the rank count
     cmd += extra
@@ -155,7 +157,7 @@ def test_secondary_block_rides_on_the_headline_line(gpu):
     env = dict(os.environ)
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT"):
         env.pop(k, None)
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--rows", "400000", "--steps", "3", "--warmup", "1",
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--rows", "400000", "--steps", "3", "--warmup", "1",
            "--cpu-reps", "1", "--secondary", "c5:16:cpu8,banded,no-such-item,c4:12,zi:14,spmv:poisson3d:16,spmv:rmat:12,feast:10"]
     r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
@@ -223,6 +225,30 @@ def test_three_ranks_all_schedules(gpu):
     three = _run(3, args)
     assert three["n_gpus"] == 3 and three["y_sha1"] == one["y_sha1"]
     assert set(three["config"]["exchange_ms_per_step_by_chunks"]) == {"rccl1", "rccl2", "rccl4", "peer1", "peer2", "peer4"}
+
+
+def test_plain_run_prints_the_headline_only(gpu, tmp_path):
+    """without --full a run sets up, warms up, times its steps, dumps y and prints the line: the headline and its
+    configuration, no roofline, fingerprint, CPU baseline, parity or secondary block (none of them is run).  The dumped
+    y is the y a --full run fingerprints, for one rank and for two"""
+    import hashlib
+
+    import numpy as np
+    args = ["--rows", "400000"]
+    full = _run(1, args)
+    for nproc in (1, 2):
+        d = tmp_path / ("plain%d" % nproc)
+        out, err = _run(nproc, args + ["--dump-outputs", str(d)], full=False, want_stderr=True)
+        assert out["metric"] == "fp64 CSR SpMV effective GB/s" and out["unit"] == "GB/s" and out["dtype"] == "f64"
+        assert out["higher_is_better"] is True and out["value"] > 0 and out["ms_per_step"] > 0
+        assert out["n_gpus"] == nproc and out["steps"] == 3 and out["warmup"] == 1
+        assert out["config"]["algorithmic_bytes"] == full["config"]["algorithmic_bytes"]
+        for k in ("roofline", "y_sha1", "y_sum", "y_norm2", "cpu_baseline", "cpu_fair_openmp", "parity", "secondary"):
+            assert k not in out, k
+        assert hashlib.sha1(np.load(d / "y.npy").tobytes()).hexdigest() == full["y_sha1"]
+        if nproc > 1:
+            brief = json.loads([l for l in err.strip().splitlines() if l.startswith("{")][-1])
+            assert brief["value"] == out["value"] and brief["kernel_ms"] is None
 
 
 def test_dump_outputs(gpu, tmp_path):

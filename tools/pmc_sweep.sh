@@ -7,7 +7,7 @@ mkdir -p gpurun_out/$tag
 i=0
 for cfg in "$@"; do
   i=$((i+1))
-  t=$(timeout -k 10 300 python bench.py --steps 20 --warmup 3 --no-cpu-baseline $cfg 2>&1 | tail -1 | python -c "import sys,json; d=json.loads(sys.stdin.read()); print(d['roofline']['kernel_ms'])")
+  t=$(timeout -k 10 300 python bench.py --full --steps 20 --warmup 3 --no-cpu-baseline $cfg 2>&1 | tail -1 | python -c "import sys,json; d=json.loads(sys.stdin.read()); print(d['roofline']['kernel_ms'])")
   timeout -k 10 300 rocprofv3 --pmc TCC_EA0_RDREQ_sum TCC_HIT_sum TCC_MISS_sum TCC_REQ_sum --output-format csv -d gpurun_out/$tag/c$i -- python3 bench.py --no-cpu-baseline --steps 2 --warmup 1 $cfg > gpurun_out/$tag/c$i.log 2>&1
   python3 - "$cfg" "$t" gpurun_out/$tag/c$i <<'PY' | tee -a gpurun_out/$tag/summary.txt
 import csv,glob,collections,sys

@@ -7,6 +7,7 @@
 repo=${GRAFT_REPO_ROOT:-/root/repo}
 cd "$repo" || exit 1
 mkdir -p gpurun_out/r05
+res=$_  # the folder just made
 steps=${*:-spmv spgemm solve100 factor100 solve200 bench feast}
 for st in $steps; do
   echo "[r05_collect] $st $(date +%T)"
@@ -27,8 +28,8 @@ for st in $steps; do
                cp gpurun_out/pmc_factor/summary.txt gpurun_out/r05/pmc_factor_z100.txt; rm -rf gpurun_out/pmc_factor ;;
     factor200) FFP_REPS=1 bash tools/pmc_factor.sh 200 > gpurun_out/r05/pmc_factor_200.log 2>&1 || { echo "pmc_factor 200 failed"; exit 1; }
                cp gpurun_out/pmc_factor/summary.txt gpurun_out/r05/pmc_factor_200.txt; rm -rf gpurun_out/pmc_factor ;;
-    bench)     timeout -k 10 600 python3 bench.py --steps 20 --warmup 5 > gpurun_out/r05/bench.json 2> gpurun_out/r05/bench.err || { echo "bench failed"; exit 1; }
-               wc -c gpurun_out/r05/bench.json ;;
+    bench)     timeout -k 10 600 python3 bench.py --full --steps 20 --warmup 5 > "$res/bench.json" 2> "$res/bench.err" || { echo "bench failed"; exit 1; }
+               wc -c "$res/bench.json" ;;
     feast)     for i in 1 2 3; do timeout -k 10 200 python3 tools/bench_secondary.py --item feast:80 2>/dev/null | grep '^{' | tail -1 >> gpurun_out/r05/feast3.jsonl || { echo "feast failed"; exit 1; }; done ;;
   esac
 done
