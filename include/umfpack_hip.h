@@ -207,6 +207,37 @@ int spl_umfpack_di_log_determinant(void *Numeric, double *sign, double *log_abs)
  * returns UMFPACK_ERROR_invalid_system and out = (-1, -1, -1): it never guesses.  Errors as above. */
 int spl_umfpack_inertia(void *Numeric, double out[3]);
 
+/* ---- condition number --------------------------------------------------------------------------------------------
+ * sys = UMFPACK_A: kappa_1(A); sys = UMFPACK_At: kappa_1(A^T) = kappa_inf(A)  (zi: A^H, the same figure).
+ * out[0] kappa estimate = out[1] * out[2], out[1] ||A|| (exact), out[2] estimate of ||A^-1|| (a lower bound reached
+ * by the witness), out[3] iterations, out[4] batched solve calls, out[5] t used.  x (may be NULL): the witness,
+ * n doubles (zi: xx / xz split, or packed in xx when xz is NULL, as the zi solves take vectors).
+ * ||A^-1|| is estimated by Higham & Tisseur's block 1-norm method (MATLAB's condest, LAPACK's xGECON does the like with
+ * t = 1) with t columns (1 .. 16; 2 is the usual choice) and at most 5 iterations: at most 6 batched solves of t columns
+ * with op(A) and 5 with its (conjugate) transpose, usually 4 to 6 in all; in practice the exact norm or within a factor
+ * of 3 of it, never above it.  ||A|| is the largest column (sys = A) or row (sys = At) sum of |a_ij| (the modulus for
+ * complex entries), exact, from the copy of A the object keeps on the device.  Ap / Ai / Ax are the caller's host arrays,
+ * as for umfpack_*_solve.  The witness proves the estimate: ||A^-1 x||_p >= out[2] ||x||_p — for p = 1 (sys = A) x is a
+ * unit vector or a column of the starting block and the two sides are equal; for p = inf (sys = At) x is the conjugate
+ * sign vector of the winning row of A^-1, and entry i of A^-1 x is that row's 1-norm.
+ * Contract:
+ *  - The estimate is of A, not of the factors: every solve of the estimator is refined and checked as a caller's solve
+ *    is; if that check replaces speculative factors during the call, the estimate is unaffected.
+ *  - spl_umfpack_solve_report is left describing the caller's own last solve, as the determinant calls leave it.
+ *  - Calls are deterministic: two calls on the same factors give the same bits.
+ *  - Thread safety is that of the solves (the call takes the turns a solve takes on speculative factors).
+ *  - The first transposed solve on unsymmetric multifrontal factors builds the transposed chain set
+ *    (spl_umfpack_solve_report out[5 .. 7]), exactly as a caller's first A^T solve would; real L D L^T factors (A = A^T)
+ *    use solves with A for both directions.
+ * Statuses: UMFPACK_OK; UMFPACK_WARNING_singular_matrix for factors with a zero pivot (out[0] = out[2] = +inf, no solves,
+ * x not written); UMFPACK_ERROR_invalid_system for a rectangular object or sys other than 0 / 1;
+ * UMFPACK_ERROR_argument_missing for t outside 1 .. 16, out NULL or Ap / Ai / Ax NULL; UMFPACK_ERROR_invalid_Numeric_object
+ * for an invalid or broken object, or one of the other value kind (a `zi` object passed to the `di` call or the reverse). */
+int spl_umfpack_di_condest(int sys, int t, const int Ap[], const int Ai[], const double Ax[], void *Numeric,
+                           double out[6], double x[]);
+int spl_umfpack_zi_condest(int sys, int t, const int Ap[], const int Ai[], const double Ax[], const double Az[],
+                           void *Numeric, double out[6], double xx[], double xz[]);
+
 #ifdef __cplusplus
 }
 #endif

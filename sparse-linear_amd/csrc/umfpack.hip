@@ -1976,6 +1976,89 @@ int spl_umfpack_inertia(void *NumericIn, double out[3]) {
   return st;
 }
 
+}  // extern "C"
+
+// ---- condition estimate ----------------------------------------------------------------------------------------------
+// kappa_1(op(A)) = ||op(A)||_1 ||op(A)^-1||_1: the norm exact from the device copy of A the object keeps for its residuals
+// (rows of A^T: the column sums of A; rows of A: its row sums), the inverse's norm estimated (condest.hip) with the solves
+// of the caller's path.
+namespace spl {
+
+int condest_numeric(Numeric *N, int sys, int t, int width, const DeviceSolve &solve, double out[6], double *witness) {
+  return umf_guarded([&] {
+    DeviceGuard g(N->device);
+    hipStream_t s = hipStreamPerThread;
+    // the turns of the solves, held for the whole estimate: its solves check speculative factors and may replace them
+    std::unique_lock<std::mutex> turn(N->mu, std::defer_lock);
+    if (N->speculative) turn.lock();
+    if (N->broken) return UMFPACK_ERROR_invalid_Numeric_object;
+    const int n = N->n / width;
+    out[1] = matrix_abs_norm(sys == UMFPACK_A ? N->At : N->A, width, s);
+    out[5] = (double)std::min(t, n);
+    if (N->singular || n == 0) {
+      out[0] = out[2] = HUGE_VAL;
+      return UMFPACK_WARNING_singular_matrix;
+    }
+    // what spl_umfpack_solve_report describes stays the caller's last solve: the estimator's solves are not the caller's
+    struct KeepReport {
+      Numeric *N;
+      int walks = N->last_walks, ir_taken = N->last_ir_taken, ir_attempted = N->last_ir_attempted;
+      double omega = N->last_omega;
+      ~KeepReport() {
+        N->last_walks = walks;
+        N->last_ir_taken = ir_taken;
+        N->last_ir_attempted = ir_attempted;
+        N->last_omega = omega;
+      }
+    } keep{N};
+    // real L D L^T factors: A = A^T, so the transposed solves are solves with A (no transposed chain set is built)
+    const bool sym = width == 1 && !N->embedding && N->mf_sym;
+    const int sys_y = sym ? UMFPACK_A : sys, sys_z = sym ? UMFPACK_A : UMFPACK_At - sys;
+    DBuf<double> dw(witness ? (size_t)N->n : 0);
+    CondestResult r;
+    const int st = condest_inverse_norm(n, width, sys_y, sys_z, sys == UMFPACK_At, t, solve, s, r,
+                                        witness ? dw.get() : nullptr);
+    if (st < 0) return st;
+    out[2] = r.norm_inv;
+    out[0] = out[1] * out[2];
+    out[3] = r.iterations;
+    out[4] = r.solves;
+    out[5] = r.t;
+    if (witness) {
+      SPL_HIP(hipMemcpyAsync(witness, dw.get(), (size_t)N->n * sizeof(double), hipMemcpyDeviceToHost, s));
+      SPL_HIP(hipStreamSynchronize(s));
+    }
+    return UMFPACK_OK;
+  });
+}
+
+// the checks of spl_umfpack_{di,zi}_condest, in the order of the solves'; UMFPACK_OK when the estimate may run
+int condest_arguments(Numeric *N, bool complex_kind, int sys, int t, const double *out, const void *Ap, const void *Ai,
+                      const void *Ax) {
+  if (!N || N->broken || (N->embedding != 0) != complex_kind) return UMFPACK_ERROR_invalid_Numeric_object;
+  if (N->rectangular) return UMFPACK_ERROR_invalid_system;
+  if (!out || !Ap || !Ai || !Ax || t < 1 || t > kCondestMaxT) return UMFPACK_ERROR_argument_missing;
+  if (sys != UMFPACK_A && sys != UMFPACK_At) return UMFPACK_ERROR_invalid_system;
+  return UMFPACK_OK;
+}
+
+}  // namespace spl
+
+extern "C" {
+
+int spl_umfpack_di_condest(int sys, int t, const int Ap[], const int Ai[], const double Ax[], void *NumericIn,
+                           double out[6], double x[]) {
+  if (out)
+    for (int i = 0; i < 6; ++i) out[i] = 0.0;
+  Numeric *N = as_numeric(NumericIn);
+  const int st = condest_arguments(N, false, sys, t, out, Ap, Ai, Ax);
+  if (st != UMFPACK_OK) return st;
+  const DeviceSolve solve = [N](int sys_c, int k, double *d_X, const double *d_B) {
+    return solve_columns(N, sys_c, k, d_X, d_B, nullptr, nullptr, nullptr, true, nullptr, true);
+  };
+  return condest_numeric(N, sys, t, 1, solve, out, x);
+}
+
 void umfpack_di_free_symbolic(void **SymbolicIO) {
   if (!SymbolicIO || !*SymbolicIO) return;
   Symbolic *S = as_symbolic(*SymbolicIO);

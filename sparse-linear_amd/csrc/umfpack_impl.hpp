@@ -2,6 +2,7 @@
 // umfpack.hip) and the complex (`zi`, umfpack_zi.hip) halves of the ABI.  Included by those two files only.
 #pragma once
 #include <atomic>
+#include <functional>
 #include <memory>
 #include <mutex>
 #include <new>
@@ -177,5 +178,29 @@ int numeric_factor(Symbolic *S, const int *Ap, const int *Ai, const double *Ax, 
 // column-major, in device memory when device_io is set, else on the host.  Info: what umfpack_*_solve reports there.
 int solve_columns(Numeric *N, int sys, int k, double *X, const double *B, const int *Ap, const int *Ai,
                   const double *Ax, bool device_io = false, double *Info = nullptr, bool caller_holds_turn = false);
+
+// ---- condition estimate (condest.hip; entry points spl_umfpack_{di,zi}_condest) ----------------------------------------
+constexpr int kCondestMaxT = 16;  // columns of the estimator's blocks: 1 .. 16
+// k columns op(A) X(:,c) = B(:,c) in device memory, n x k of the value width; returns a UMFPACK status
+using DeviceSolve = std::function<int(int sys, int k, double *d_X, const double *d_B)>;
+struct CondestResult {
+  double norm_inv = 0.0;  // the estimate of ||op(A)^-1||_1: a lower bound the witness reaches
+  int iterations = 0, solves = 0, t = 0;
+};
+// Higham & Tisseur's block estimate of ||op(A)^-1||_1 for an n x n matrix of value width w (1 real, 2 packed complex):
+// Y = op(A)^-1 X solves with sys_y, Z = op(A)^-H S with sys_z.  d_witness (n w doubles, may be null): p_inf false: a
+// vector x with ||op(A)^-1 x||_1 = est ||x||_1; p_inf true (op(A) = A^T or A^H): x with ||A^-1 x||_inf >= est ||x||_inf.
+int condest_inverse_norm(int n, int w, int sys_y, int sys_z, bool p_inf, int t, const DeviceSolve &solve, hipStream_t s,
+                         CondestResult &res, double *d_witness);
+// the largest sum of |a_ij| over the rows a device matrix holds; width 2: the rows 2g of the real embedding of a complex
+// matrix, whose entries pair up into the complex a_gj (umfpack_zi.hip)
+double matrix_abs_norm(const Matrix *rows, int width, hipStream_t s);
+// The body of spl_umfpack_{di,zi}_condest on a valid square object of the right value kind (umfpack.hip): out[6] as the
+// header says, witness (host, N->n doubles: packed for complex objects) when not null.  `solve` runs with the object's
+// turn held when it is speculative (solve_columns(..., caller_holds_turn = true)).
+int condest_numeric(Numeric *N, int sys, int t, int width, const DeviceSolve &solve, double out[6], double *witness);
+// the argument checks of spl_umfpack_{di,zi}_condest (complex_kind: a `zi` object is expected); UMFPACK_OK or the status
+int condest_arguments(Numeric *N, bool complex_kind, int sys, int t, const double *out, const void *Ap, const void *Ai,
+                      const void *Ax);
 
 }  // namespace spl

@@ -260,6 +260,47 @@ int solve_host(spl::Numeric *N, int sys, const int *Ap, const int *Ai, const dou
   });
 }
 
+// nrhs packed complex systems in device memory through the real embedding N holds: apply the swapped pairs or the unit
+// congruence to the right-hand sides, solve_embedded(b) the embedded systems into d_X, undo them on the solutions
+template <typename Solve>
+int solve_dev(spl::Numeric *N, int sys, int nrhs, double *d_X, const double *d_B, Solve &&solve_embedded) {
+  const std::vector<char> *swap = !N->pair_swap.empty() ? &N->pair_swap : nullptr;
+  const std::vector<double> *unit = !N->pair_unit.empty() ? &N->pair_unit : nullptr;
+  if ((!swap && !unit) || nrhs == 0 || N->n == 0) return solve_embedded(d_B);
+  if (sys != UMFPACK_A && sys != UMFPACK_At) return UMFPACK_ERROR_invalid_system;
+  return spl::umf_guarded([&] {
+    const size_t n = (size_t)N->n / 2, total = n * (size_t)nrhs;
+    if (unit) {  // symmetric embedding: E' x' = T b, x = W x'  /  E' y' = W^T c, y = T^T y'
+      spl::DBuf<double> u(2 * n), b(2 * total);
+      SPL_HIP(hipMemcpy(u.get(), unit->data(), 2 * n * sizeof(double), hipMemcpyHostToDevice));
+      SPL_HIP(hipMemcpy(b.get(), d_B, 2 * total * sizeof(double), hipMemcpyDeviceToDevice));
+      const dim3 grid((unsigned)((total + 255) / 256));
+      hipLaunchKernelGGL(unit_pairs_kernel, grid, dim3(256), 0, nullptr, u.get(), sys == UMFPACK_A ? 0 : 2, b.get(), n, total);
+      SPL_HIP(hipDeviceSynchronize());
+      const int st = solve_embedded(b.get());
+      if (st < 0) return st;
+      hipLaunchKernelGGL(unit_pairs_kernel, grid, dim3(256), 0, nullptr, u.get(), sys == UMFPACK_A ? 1 : 3, d_X, n, total);
+      SPL_HIP(hipDeviceSynchronize());
+      return st;
+    }
+    spl::DBuf<char> flags(n);
+    SPL_HIP(hipMemcpy(flags.get(), swap->data(), n, hipMemcpyHostToDevice));
+    const dim3 grid((unsigned)((total + 255) / 256));
+    if (sys == UMFPACK_A) {  // (Q E) x = Q b
+      spl::DBuf<double> b(2 * total);
+      SPL_HIP(hipMemcpy(b.get(), d_B, 2 * total * sizeof(double), hipMemcpyDeviceToDevice));
+      hipLaunchKernelGGL(swap_pairs_kernel, grid, dim3(256), 0, nullptr, flags.get(), b.get(), n, total);
+      SPL_HIP(hipDeviceSynchronize());
+      return solve_embedded(b.get());
+    }
+    const int st = solve_embedded(d_B);
+    if (st < 0) return st;
+    hipLaunchKernelGGL(swap_pairs_kernel, grid, dim3(256), 0, nullptr, flags.get(), d_X, n, total);  // y = Q w
+    SPL_HIP(hipDeviceSynchronize());
+    return st;
+  });
+}
+
 }  // namespace
 
 extern "C" {
@@ -440,40 +481,38 @@ int spl_umfpack_zi_solve_many_dev(int sys, const int Ap[], const int Ai[], const
   const int n2 = N ? N->n : 0;
   if (n2 == 0 && !NumericIn) return UMFPACK_ERROR_invalid_Numeric_object;
   if (nrhs > 0 && n2 > 0 && (!d_X || !d_B)) return UMFPACK_ERROR_argument_missing;
-  const std::vector<char> *swap = N && !N->pair_swap.empty() ? &N->pair_swap : nullptr;
-  const std::vector<double> *unit = N && !N->pair_unit.empty() ? &N->pair_unit : nullptr;
-  if ((!swap && !unit) || nrhs == 0 || n2 == 0) return spl_umfpack_di_solve_many_dev(sys, Ap, Ai, Ax, nrhs, d_X, d_B, NumericIn);
-  return spl::umf_guarded([&] {
-    const size_t n = (size_t)n2 / 2, total = n * (size_t)nrhs;
-    if (unit) {  // symmetric embedding: E' x' = T b, x = W x'  /  E' y' = W^T c, y = T^T y'
-      spl::DBuf<double> u(2 * n), b(2 * total);
-      SPL_HIP(hipMemcpy(u.get(), unit->data(), 2 * n * sizeof(double), hipMemcpyHostToDevice));
-      SPL_HIP(hipMemcpy(b.get(), d_B, 2 * total * sizeof(double), hipMemcpyDeviceToDevice));
-      const dim3 grid((unsigned)((total + 255) / 256));
-      hipLaunchKernelGGL(unit_pairs_kernel, grid, dim3(256), 0, nullptr, u.get(), sys == UMFPACK_A ? 0 : 2, b.get(), n, total);
-      SPL_HIP(hipDeviceSynchronize());
-      const int st = spl_umfpack_di_solve_many_dev(sys, Ap, Ai, Ax, nrhs, d_X, b.get(), NumericIn);
-      if (st < 0) return st;
-      hipLaunchKernelGGL(unit_pairs_kernel, grid, dim3(256), 0, nullptr, u.get(), sys == UMFPACK_A ? 1 : 3, d_X, n, total);
-      SPL_HIP(hipDeviceSynchronize());
-      return st;
-    }
-    spl::DBuf<char> flags(n);
-    SPL_HIP(hipMemcpy(flags.get(), swap->data(), n, hipMemcpyHostToDevice));
-    const dim3 grid((unsigned)((total + 255) / 256));
-    if (sys == UMFPACK_A) {  // (Q E) x = Q b
-      spl::DBuf<double> b(2 * total);
-      SPL_HIP(hipMemcpy(b.get(), d_B, 2 * total * sizeof(double), hipMemcpyDeviceToDevice));
-      hipLaunchKernelGGL(swap_pairs_kernel, grid, dim3(256), 0, nullptr, flags.get(), b.get(), n, total);
-      SPL_HIP(hipDeviceSynchronize());
-      return spl_umfpack_di_solve_many_dev(sys, Ap, Ai, Ax, nrhs, d_X, b.get(), NumericIn);
-    }
-    const int st = spl_umfpack_di_solve_many_dev(sys, Ap, Ai, Ax, nrhs, d_X, d_B, NumericIn);
-    if (st < 0) return st;
-    hipLaunchKernelGGL(swap_pairs_kernel, grid, dim3(256), 0, nullptr, flags.get(), d_X, n, total);  // y = Q w
-    SPL_HIP(hipDeviceSynchronize());
-    return st;
+  const bool plain = !N || (N->pair_swap.empty() && N->pair_unit.empty());
+  if (plain || nrhs == 0 || n2 == 0) return spl_umfpack_di_solve_many_dev(sys, Ap, Ai, Ax, nrhs, d_X, d_B, NumericIn);
+  return solve_dev(N, sys, nrhs, d_X, d_B, [&](const double *b) {
+    return spl_umfpack_di_solve_many_dev(sys, Ap, Ai, Ax, nrhs, d_X, b, NumericIn);
   });
+}
+
+// kappa_1(A) / kappa_1(A^H) = kappa_inf(A) of a complex matrix: the estimator's solves are those of
+// spl_umfpack_zi_solve_many_dev, with the object's turn held (umfpack.hip: condest_numeric)
+int spl_umfpack_zi_condest(int sys, int t, const int Ap[], const int Ai[], const double Ax[], const double Az[],
+                           void *NumericIn, double out[6], double xx[], double xz[]) {
+  (void)Az;
+  if (out)
+    for (int i = 0; i < 6; ++i) out[i] = 0.0;
+  spl::Numeric *N = spl::as_numeric(NumericIn);
+  const int st = spl::condest_arguments(N, true, sys, t, out, Ap, Ai, Ax);
+  if (st != UMFPACK_OK) return st;
+  const spl::DeviceSolve solve = [N](int sys_c, int k, double *d_X, const double *d_B) {
+    return solve_dev(N, sys_c, k, d_X, d_B, [&](const double *b) {
+      return spl::solve_columns(N, sys_c, k, d_X, b, nullptr, nullptr, nullptr, true, nullptr, true);
+    });
+  };
+  std::vector<double> w(xx ? (size_t)N->n : 0);
+  const int cst = spl::condest_numeric(N, sys, t, 2, solve, out, xx ? w.data() : nullptr);
+  if (cst == UMFPACK_OK && xx) {
+    const size_t n = (size_t)N->n / 2;
+    for (size_t k = 0; k < n; ++k) {
+      if (xz) { xx[k] = w[2 * k]; xz[k] = w[2 * k + 1]; }
+      else { xx[2 * k] = w[2 * k]; xx[2 * k + 1] = w[2 * k + 1]; }
+    }
+  }
+  return cst;
 }
 
 void umfpack_zi_free_symbolic(void **Symbolic) {

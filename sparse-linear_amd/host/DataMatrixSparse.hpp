@@ -415,6 +415,29 @@ inline Inertia inertia(const Factors &fact) {
   if (st < 0) detail::oops("inertia", "spl_umfpack_inertia failed");
   return Inertia{(long)out[0], (long)out[1], (long)out[2]};
 }
+// kappa_1(A) (norm = 1) or kappa_inf(A) (norm = 0, for infinity) from the factors, on the device
+// (spl_umfpack_di_condest): ||A|| exact, ||A^-1|| a lower bound by Higham & Tisseur's block estimator with t columns,
+// which the witness x reaches: ||A^-1 x|| >= norm_inv ||x|| in that norm
+struct ConditionEstimate {
+  double cond = 0.0, norm_A = 0.0, norm_inv = 0.0;
+  int iterations = 0, solves = 0;
+  std::vector<double> witness;
+};
+inline ConditionEstimate conditionEstimate(const Factors &fact, const Matrix &mat, int norm = 1, int t = 2) {
+  if (norm != 1 && norm != 0) detail::oops("conditionEstimate", "norm must be 1, or 0 for the infinity norm");
+  detail::Const c(mat);
+  ConditionEstimate r;
+  r.witness.assign((size_t)mat.ncols, 0.0);
+  double out[6];
+  const int st = spl_umfpack_di_condest(norm == 1 ? UMFPACK_A : UMFPACK_At, t, c.p.data(), c.i.data(), c.x, *fact.fnum,
+                                        out, r.witness.data());
+  umfpack_di_report_status(nullptr, st);
+  if (st < 0) detail::oops("conditionEstimate", "spl_umfpack_di_condest failed");
+  r.cond = out[0]; r.norm_A = out[1]; r.norm_inv = out[2];
+  r.iterations = (int)out[3]; r.solves = (int)out[4];
+  return r;
+}
+inline double condest(const Matrix &mat, int norm = 1) { return conditionEstimate(factor(mat, analyze(mat)), mat, norm).cond; }
 inline Determinant det(const Matrix &mat) { return determinant(factor(mat, analyze(mat))); }
 inline std::pair<int, double> slogdet(const Matrix &mat) { return logDeterminant(factor(mat, analyze(mat))); }
 

@@ -163,6 +163,13 @@ int main() {
     EXPECT(sl.first == 1 && std::fabs(sl.second - std::log(1000.0)) < 1e-12);
     const U::Inertia in = U::inertia(f);
     EXPECT(in.positive == n && in.negative == 0 && in.zero == 0);
+    // kappa_1 = ||A||_1 ||A^-1||_1 = 4 (n + 1)^2 / 8; the witness reaches the estimate
+    const U::ConditionEstimate ce = U::conditionEstimate(f, L);
+    EXPECT(ce.norm_A == 4.0 && std::fabs(ce.cond - 500000.0) < 1e-12 * 500000.0 && ce.solves <= 11);
+    const std::vector<double> y = U::linearSolve_(f, U::UmfpackNormal, L, ce.witness);
+    double ny = 0.0, nx = 0.0;
+    for (Int i = 0; i < n; ++i) { ny += std::fabs(y[(size_t)i]); nx += std::fabs(ce.witness[(size_t)i]); }
+    EXPECT(std::fabs(ny / nx - ce.norm_inv) < 1e-8 * ce.norm_inv);
   }
   // work arrays of 256 KiB and more are kept for reuse (at most 2 GiB of them); releasing gives them back once
   EXPECT(U::releaseCachedMemory() <= (size_t)2 << 30);
