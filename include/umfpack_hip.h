@@ -139,6 +139,41 @@ int spl_umfpack_di_solve_many_dev(int sys, const int Ap[], const int Ai[], const
 int spl_umfpack_zi_solve_many_dev(int sys, const int Ap[], const int Ai[], const double Ax[], int nrhs, double *d_X,
                                   const double *d_B, void *Numeric);
 
+/* ---- analysis and factorisation of a DEVICE-RESIDENT matrix ---------------------------------------------------------
+ * H is a whole-matrix handle of sparse_linear_hip.h — real for `di`; complex for `zi` (spl_matrix_create_z,
+ * spl_matrix_to_complex, spl_matrix_lin on complex handles) — as the spl_matrix_* family assembles them in device memory
+ * (compress_dev, lin, transpose, spgemm): the matrix is factored where it lies, for callers that run one analysis and
+ * many factorisations of same-pattern matrices z B - A built on the device (Feast.hs:210-218).
+ *  - The objects written are those of umfpack_*_symbolic / umfpack_*_numeric: freed by umfpack_*_free_*, accepted by
+ *    every entry point of this header; a Symbolic of either origin serves numeric calls of either origin.
+ *  - The factorisation is the one umfpack_*_numeric makes of the same matrix — same paths, same environment switches,
+ *    same bits: both routes put the same two images (rows of A, rows of A^T) on the device.  Static pivoting from a
+ *    numeric call reads the matrix back from the object's own device copy, as the solves do.
+ *  - numeric_dev moves O(n) bytes between host and device (swap flags or units of a complex matrix, statuses, the
+ *    tables of the factorisation), never the matrix: the symmetry test, the diagonal pass and the real embedding of a
+ *    complex matrix (csrc/umfpack_zi.hip) are kernels over H's image (csrc/lu_from_handle.hip).  symbolic_dev exports
+ *    the pattern once (the analysis is host code).
+ *  - UMFPACK_ERROR_different_pattern is decided exactly, on the device, against a copy of the analysed pattern the
+ *    Symbolic keeps in H's layout; symbolic_dev makes it from H, for a Symbolic of umfpack_*_symbolic the first
+ *    numeric_dev call does (one download of H's pattern, checked against the analysis' own record; under a lock: other
+ *    threads factoring with that Symbolic wait for it; a handle that fails this first check leaves no copy behind, so
+ *    the download is repeated by every call until a handle with the analysed pattern arrives).
+ *  - H is borrowed: not modified, free to be released when the call returns, usable by other threads for read-only
+ *    operations meanwhile.  The Numeric object holds its own device copies.
+ *  - Streams and threads: as umfpack_*_numeric (above: hipStreamPerThread, ordered with the legacy default stream the
+ *    handle operations run on; calls from several host threads overlap).
+ *  - Solves on such an object may pass Ap = Ai = Ax = NULL to spl_umfpack_*_solve_many_dev (above); the entry points
+ *    that require host arrays (umfpack_*_solve, spl_umfpack_*_solve_many, _condest) still do: export the handle.
+ * Statuses: H NULL or not a matrix handle, or an output pointer NULL: UMFPACK_ERROR_argument_missing; a row-block
+ * handle, one of the other value kind or one without 32-bit row pointers: UMFPACK_ERROR_invalid_matrix; a complex handle
+ * whose embedding would reach 2^31 entries: UMFPACK_ERROR_out_of_memory (from both calls, decided on the handle alone, before its pattern is looked at); a Symbolic of the other kind:
+ * UMFPACK_ERROR_invalid_Symbolic_object; a zero pivot: UMFPACK_WARNING_singular_matrix.  Rectangular handles take the
+ * host route (exported, then umfpack_*_symbolic / _numeric) and return its statuses. */
+int spl_umfpack_di_symbolic_dev(void *H, void **Symbolic);
+int spl_umfpack_zi_symbolic_dev(void *H, void **Symbolic);
+int spl_umfpack_di_numeric_dev(void *H, void *Symbolic, void **Numeric);
+int spl_umfpack_zi_numeric_dev(void *H, void *Symbolic, void **Numeric);
+
 /* dimension of the system a Numeric object factors (0 if invalid); helper of the zi wrappers */
 int spl_umfpack_dimension(void *Numeric);
 

@@ -1138,7 +1138,38 @@ int umfpack_di_symbolic(int n_row, int n_col, const int Ap[], const int Ai[], co
 
 namespace spl {
 
+static bool factor_static_pivot_of_copy(Numeric *N, hipStream_t s);
+
 int numeric_factor(Symbolic *S, const int *Ap, const int *Ai, const double *Ax, EmbeddingOpts opts, Numeric **NumericOut) {
+  const int n = S->n;
+  // rows of A^T == the CSC arrays as they are; rows of A by transposing that copy on the device (spl_matrix_create
+  // would send the same arrays over PCIe a second time and transpose them with the same kernel — 0.7 GB at config C5,
+  // a fifth of a FEAST refactorisation of 10^6 complex unknowns)
+  const StageImages from_host = [&](Numeric *N, hipStream_t, const std::function<void(const char *)> &lap) {
+    void *hAt = nullptr;
+    const int st = spl_matrix_create_csr(n, n, 0, n, Ap, Ai, Ax, &hAt);
+    if (st != SPL_OK) return umf_status(st);
+    N->At = static_cast<Matrix *>(hAt);
+    if (!N->At->rowptr.get()) return UMFPACK_ERROR_out_of_memory;
+    lap("rows of A^T (upload)");
+    return stage_transposed_image(N, false);
+  };
+  return numeric_factor_staged(S, std::move(opts), from_host, Ap, Ai, Ax, NumericOut);
+}
+
+int stage_transposed_image(Numeric *N, bool from_rows) {
+  void *h = nullptr;
+  const int st = spl_matrix_transpose(from_rows ? N->A : N->At, &h);
+  if (st != SPL_OK) {
+    spl_matrix_free(&h);
+    return umf_status(st);
+  }
+  (from_rows ? N->At : N->A) = static_cast<Matrix *>(h);
+  return static_cast<Matrix *>(h)->rowptr.get() ? UMFPACK_OK : UMFPACK_ERROR_out_of_memory;
+}
+
+int numeric_factor_staged(Symbolic *S, EmbeddingOpts opts, const StageImages &stage, const int *Ap, const int *Ai,
+                          const double *Ax, Numeric **NumericOut) {
   const int n = S->n;
   return umf_guarded([&] {
     int ndev = 0;
@@ -1158,7 +1189,7 @@ int numeric_factor(Symbolic *S, const int *Ap, const int *Ai, const double *Ax, 
     hipStream_t s = hipStreamPerThread;
     const bool timing = getenv("SPL_MF_TIMING") != nullptr;  // phase times on stderr (diagnostic)
     auto t_last = std::chrono::steady_clock::now();
-    auto lap = [&](const char *what) {
+    const std::function<void(const char *)> lap = [&](const char *what) {
       if (!timing) return;
       (void)hipStreamSynchronize(s);
       const auto now = std::chrono::steady_clock::now();
@@ -1168,15 +1199,12 @@ int numeric_factor(Symbolic *S, const int *Ap, const int *Ai, const double *Ax, 
     N->n = n;
     N->kl = S->kl;
     N->ku = S->ku;
-    // rows of A^T == the CSC arrays as they are: needed first, for the dominance test
-    void *hAt = nullptr;
+    // device copies of A: rows of A^T (the dominance test, the scatters of the factorisations) and rows of A (the
+    // residuals of the refinement)
     {
-      int stc = spl_matrix_create_csr(n, n, 0, n, Ap, Ai, Ax, &hAt);
-      if (stc != SPL_OK) return umf_status(stc);
+      const int sts = stage(N, s, lap);
+      if (sts != UMFPACK_OK) return sts;
     }
-    N->At = static_cast<Matrix *>(hAt);
-    if (!N->At->rowptr.get()) return UMFPACK_ERROR_out_of_memory;
-    lap("rows of A^T (upload)");
     N->ipiv.alloc((size_t)n);
     N->perm.alloc((size_t)n);
     N->inv.alloc((size_t)n);
@@ -1188,18 +1216,6 @@ int numeric_factor(Symbolic *S, const int *Ap, const int *Ai, const double *Ax, 
       N->zsym = opts.zsym ? 1 : 0;
     }
     set_ordering(N, N->tree ? N->tree->perm : N->band_perm, N->tree ? N->tree->inv : N->band_inv, s);
-    // device copies of A for the residuals of the refinement: rows of A (transposed on the
-    // device) and rows of A^T (the CSC arrays as they are)
-    // (by transposing the copy just uploaded, on the device: spl_matrix_create would send the same arrays over PCIe
-    // a second time and transpose them with the same kernel — 0.7 GB at config C5, a fifth of a FEAST refactorisation
-    // of 10^6 complex unknowns)
-    void *hA = nullptr;
-    int st = spl_matrix_transpose(hAt, &hA);
-    if (st != SPL_OK) {
-      spl_matrix_free(&hA);
-      return umf_status(st);
-    }
-    N->A = static_cast<Matrix *>(hA);
     lap("ordering, rows of A");
     // Path: SPL_LU_FORCE_PIVOT=1 -> partial pivoting; =0 -> only provably safe no-interchange
     // factors (column diagonal dominance); default -> no-interchange factors for every matrix,
@@ -1229,7 +1245,7 @@ int numeric_factor(Symbolic *S, const int *Ap, const int *Ai, const double *Ax, 
       }
       N->speculative = dominant ? 0 : 1;
       if (!fits || (N->speculative && N->singular)) {  // a zero pivot without interchanges proves nothing
-        if (!factor_static_pivot(N, Ap, Ai, Ax, s)) {
+        if (!(Ap ? factor_static_pivot(N, Ap, Ai, Ax, s) : factor_static_pivot_of_copy(N, s))) {
           N->speculative = 0;
           factor_band(N, false, s);
         }
@@ -1269,6 +1285,73 @@ int umfpack_di_numeric(const int Ap[], const int Ai[], const double Ax[], void *
       return UMFPACK_ERROR_different_pattern;
     st = numeric_factor(S, Ap, Ai, Ax, EmbeddingOpts{}, &N);
   }
+  *NumericOut = N;
+  return st;
+}
+
+// ---- the same two calls on a device-resident matrix handle (umfpack_hip.h; kernels in lu_from_handle.hip) ----------
+
+int spl_umfpack_di_symbolic_dev(void *H, void **SymbolicOut) {
+  if (!SymbolicOut) return UMFPACK_ERROR_argument_missing;
+  *SymbolicOut = nullptr;
+  Matrix *M = as_matrix(H);
+  if (!M) return UMFPACK_ERROR_argument_missing;
+  const int hs = handle_status(M, 1);
+  if (hs != UMFPACK_OK) return hs;
+  return umf_guarded([&] {
+    DeviceGuard g(M->device);
+    // the analysis is host code: the pattern crosses once, here
+    std::vector<int> Ap, Ai;
+    handle_to_host_csc(M, Ap, Ai, nullptr);
+    void *S = nullptr;
+    const int st = umfpack_di_symbolic((int)M->nrows_global, (int)M->ncols, Ap.data(), Ai.data(), nullptr, &S, nullptr, nullptr);
+    if (st < 0) return st;
+    try {
+      pattern_from_handle(M, static_cast<Symbolic *>(S)->dpat, hipStreamPerThread);
+    } catch (...) {
+      umfpack_di_free_symbolic(&S);
+      throw;
+    }
+    *SymbolicOut = S;
+    return st;
+  });
+}
+
+int spl_umfpack_di_numeric_dev(void *H, void *SymbolicIn, void **NumericOut) {
+  if (!NumericOut) return UMFPACK_ERROR_argument_missing;
+  *NumericOut = nullptr;
+  Symbolic *S = as_symbolic(SymbolicIn);
+  if (!S) return UMFPACK_ERROR_invalid_Symbolic_object;
+  Matrix *M = as_matrix(H);
+  if (!M) return UMFPACK_ERROR_argument_missing;
+  const int hs = handle_status(M, 1);
+  if (hs != UMFPACK_OK) return hs;
+  Numeric *N = nullptr;
+  const int st = umf_guarded([&] {
+    DeviceGuard g(M->device);
+    if (S->rectangular) {  // no factors are kept: the host route, with its statuses
+      if (M->nrows_global != S->n_row || M->ncols != S->n_col) return UMFPACK_ERROR_different_pattern;
+      std::vector<int> Ap, Ai;
+      std::vector<double> Ax;
+      handle_to_host_csc(M, Ap, Ai, &Ax);
+      void *out = nullptr;
+      const int sr = umfpack_di_numeric(Ap.data(), Ai.data(), Ax.data(), S, &out, nullptr, nullptr);
+      N = static_cast<Numeric *>(out);
+      return sr;
+    }
+    if (M->nrows_global != S->n || M->ncols != S->n || M->nnz != S->nnz ||
+        !handle_has_pattern(M, S->dpat, S->Ap, S->ai_hash, hipStreamPerThread))
+      return UMFPACK_ERROR_different_pattern;
+    // rows of A: a copy of the handle's image; rows of A^T: its transpose, on the device (exact and order-preserving:
+    // the two images are those the host route makes from the CSC arrays)
+    const StageImages from_handle = [&](Numeric *Nn, hipStream_t s, const std::function<void(const char *)> &lap) {
+      Nn->A = clone_handle(M, s);
+      SPL_HIP(hipStreamSynchronize(s));
+      lap("rows of A (device copy)");
+      return stage_transposed_image(Nn, true);
+    };
+    return numeric_factor_staged(S, EmbeddingOpts{}, from_handle, nullptr, nullptr, nullptr, &N);
+  });
   *NumericOut = N;
   return st;
 }

@@ -1,7 +1,9 @@
 // umfpack_impl.hpp — the objects behind the UMFPACK handles and the internal calls between the real (`di`,
-// umfpack.hip) and the complex (`zi`, umfpack_zi.hip) halves of the ABI.  Included by those two files only.
+// umfpack.hip) and the complex (`zi`, umfpack_zi.hip) halves of the ABI.  Included by those two files and by
+// lu_from_handle.hip (what their calls on device-resident handles run on the device) only.
 #pragma once
 #include <atomic>
+#include <cmath>
 #include <functional>
 #include <memory>
 #include <mutex>
@@ -17,8 +19,20 @@ namespace spl {
 constexpr uint32_t kSymMagic = 0x53594D42u;  // "SYMB"
 constexpr uint32_t kNumMagic = 0x4E554D52u;  // "NUMR"
 
+// The analysed pattern on the device, in the layout of a matrix handle (row pointers and column indices of the rows
+// image): what the numeric calls on handles compare against (lu_from_handle.hip).  Made by the analysis of a handle, or
+// by the first numeric call on a handle with a host-born analysis (under `mu`: several threads factor with one
+// Symbolic).
+struct DevicePattern {
+  std::mutex mu;
+  std::atomic<bool> ready{false};
+  int64_t nrows = 0, nnz = 0;
+  DBuf<int> rowptr, colidx;
+};
+
 struct Symbolic {
   uint32_t magic = kSymMagic;
+  DevicePattern dpat;
   int n = 0;
   int nnz = 0;
   int kl = 0, ku = 0;
@@ -173,6 +187,60 @@ struct EmbeddingOpts {
 // The numeric factorisation of a square matrix whose arguments and pattern the caller has checked; *NumericOut is
 // set only when it succeeds (status >= 0).
 int numeric_factor(Symbolic *S, const int *Ap, const int *Ai, const double *Ax, EmbeddingOpts opts, Numeric **NumericOut);
+// The same with the two device images staged by the caller: stage(N, s, lap) puts the rows of A into N->A and the rows
+// of A^T into N->At (on stream s or synchronised; lap names a finished phase for SPL_MF_TIMING) and returns a UMFPACK
+// status.  numeric_factor stages them from host arrays; the numeric calls on handles from a handle.  Ap / Ai / Ax: the
+// host CSC arrays for static pivoting, or all null — it then reads them back from N->At, as the solves do.
+using StageImages = std::function<int(Numeric *N, hipStream_t s, const std::function<void(const char *)> &lap)>;
+int numeric_factor_staged(Symbolic *S, EmbeddingOpts opts, const StageImages &stage, const int *Ap, const int *Ai,
+                          const double *Ax, Numeric **NumericOut);
+// the second image of a stager: N->At from N->A (from_rows) or N->A from N->At, by the device transpose; a UMFPACK status
+int stage_transposed_image(Numeric *N, bool from_rows);
+
+// ---- LU from device-resident matrix handles (lu_from_handle.hip; entry points spl_umfpack_{di,zi}_{symbolic,numeric}_dev)
+// UMFPACK_OK for a whole-matrix handle with `vw` doubles per value and 32-bit row pointers, else
+// UMFPACK_ERROR_invalid_matrix
+int handle_status(const Matrix *H, int vw);
+// the handle as host CSC arrays (the pattern once for an analysis, the whole matrix on the rectangular route): Ax, when
+// not null, receives H->vw doubles per entry
+void handle_to_host_csc(const Matrix *H, std::vector<int> &Ap, std::vector<int> &Ai, std::vector<double> *Ax);
+void pattern_from_handle(const Matrix *H, DevicePattern &P, hipStream_t s);  // device copy; sets P.ready
+// H has exactly the analysed pattern?  P is compared on the device; a host-born analysis (P not ready) first checks H's
+// pattern against its own record (column pointers Ap and hash of the row indices) and keeps it as P.
+bool handle_has_pattern(const Matrix *H, DevicePattern &P, const std::vector<int> &Ap, uint64_t ai_hash, hipStream_t s);
+Matrix *clone_handle(const Matrix *H, hipStream_t s);  // device-to-device copy of the rows image (no SpMV images)
+bool complex_handle_symmetric(const Matrix *H, hipStream_t s);  // A == A^T, pattern and bits of the values
+// u = sqrt(conj(a) / |a|) of a diagonal entry a = re + i im of a complex symmetric matrix (the congruence D A D of
+// umfpack_zi.hip): the root with the non-negative real part, without cancellation; (1, 0) when a is zero or not finite.
+// One function for the host route and the handle route: their units have to be the same bits.
+inline void congruence_unit(double re, double im, double u[2]) {
+  u[0] = 1.0;
+  u[1] = 0.0;
+  const double mod = std::hypot(re, im);
+  if (!std::isfinite(mod) || mod == 0.0) return;
+  const double c = re / mod, sn = -im / mod;
+  if (c >= 0.0) {
+    u[0] = std::sqrt(0.5 * (1.0 + c));
+    u[1] = sn / (2.0 * u[0]);
+  } else {
+    u[1] = std::copysign(std::sqrt(0.5 * (1.0 - c)), sn);
+    u[0] = sn / (2.0 * u[1]);
+  }
+}
+// the diagonal of a complex handle: swap flags (|im a_rr| > |re a_rr|; units false) or the unit-modulus u_r of the
+// symmetric congruence (units true; computed on the host from the n diagonal entries, see complex_handle_diagonal), on
+// the device for the embedding kernel and on the host for the solves
+struct ComplexDiagonal {
+  DBuf<char> d_swap;
+  DBuf<double> d_unit;
+  std::vector<char> swap;
+  std::vector<double> unit;
+  bool any_swap = false;
+};
+void complex_handle_diagonal(const Matrix *H, bool units, ComplexDiagonal &D, hipStream_t s);
+// rows image of the real 2n x 2n embedding of a complex handle (umfpack_zi.hip): plain, swapped pairs (d_swap), or the
+// symmetric congruence (d_unit); finalized, synchronised
+Matrix *embed_handle(const Matrix *H, const char *d_swap, const double *d_unit, hipStream_t s);
 
 // k systems op(A) X(:,c) = B(:,c) with the factors of N (sys: UMFPACK_A or UMFPACK_At); X and B are n x k
 // column-major, in device memory when device_io is set, else on the host.  Info: what umfpack_*_solve reports there.

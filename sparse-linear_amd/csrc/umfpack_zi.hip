@@ -212,6 +212,15 @@ struct ZiSymbolic {  // remembers n so that numeric can rebuild the embedding, a
   spl::Symbolic *di = nullptr;
   std::vector<int> Ap;
   uint64_t ai_hash = 0;
+  spl::DevicePattern dpat;  // the complex pattern in a handle's layout (the numeric calls on handles)
+};
+
+// What umfpack_zi_numeric decides before it embeds — the same decisions for host arrays and for a handle; only where
+// the symmetry test runs differs (`symmetric_matrix` is asked at most once).
+struct ZiChoice {
+  bool native = false;     // native complex fronts take the plain embedding
+  bool is_sym = false;     // A == A^T was wanted and holds
+  bool symmetric = false;  // the symmetric congruence embedding
 };
 
 // Native complex fronts serve this analysis?  They need the tree (of the complex pattern), and pay where the tree has
@@ -224,6 +233,36 @@ bool native_fronts(const spl::Symbolic &S) {
   if (zn && zn[0] == '0') return false;
   if (zn && zn[0] == '1') return true;
   return S.tree->flops >= 1e12;
+}
+
+template <typename SymmetryTest>
+ZiChoice zi_choice(const spl::Symbolic &S, int n, SymmetryTest &&symmetric_matrix) {
+  ZiChoice c;
+  c.native = native_fronts(S);
+  const char *zs = getenv("SPL_ZI_SYMMETRIC");
+  const bool wanted = c.native || (zs ? zs[0] != '0' : (S.tree ? S.tree->flops : 0.0) >= 1e12);
+  c.is_sym = wanted && n > 1 && symmetric_matrix();
+  c.symmetric = c.is_sym && !c.native;
+  return c;
+}
+
+// What the `zi` calls on handles ask of H before anything else: a whole complex matrix with 32-bit row pointers
+// (UMFPACK_ERROR_invalid_matrix) whose real embedding, four entries per stored entry, stays below 2^31 entries when it
+// is square (UMFPACK_ERROR_out_of_memory, as embed() reports; a rectangular matrix is never embedded).  The size is a
+// property of the handle alone, so it is refused here, before the pattern is exported or compared.
+int zi_handle_status(const spl::Matrix *M) {
+  const int hs = spl::handle_status(M, 2);
+  if (hs != UMFPACK_OK) return hs;
+  if (M->nrows_global == M->ncols && 4 * M->nnz >= 0x7fffffffLL) return UMFPACK_ERROR_out_of_memory;
+  return UMFPACK_OK;
+}
+
+// the line SPL_MF_TIMING prints about the embedding
+void report_embedding(const ZiChoice &c, const char *where, std::chrono::steady_clock::time_point t0) {
+  fprintf(stderr, "[zi numeric] %s embedding built on the %s %8.2f ms\n",
+          c.native ? (c.is_sym ? "plain (native complex fronts, symmetric)" : "plain (native complex fronts)")
+                   : c.symmetric ? "symmetric" : "general",
+          where, std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count());
 }
 
 // nrhs complex systems on the host through the real embedding N holds: right-hand sides packed (re, im) pairs when
@@ -375,11 +414,8 @@ int umfpack_zi_numeric(const int Ap[], const int Ai[], const double Ax[], const 
     // congruence: a complex pivot is as good as its modulus — whenever the analysis chose the tree; a complex symmetric
     // matrix is then factored as L D L^T in complex arithmetic.  The embeddings below serve the band path, and
     // SPL_ZI_NATIVE=0.
-    const bool native = native_fronts(*S->di);
-    const char *zs = getenv("SPL_ZI_SYMMETRIC");
-    const bool wanted = native || (zs ? zs[0] != '0' : (S->di->tree ? S->di->tree->flops : 0.0) >= 1e12);
-    const bool is_sym = wanted && n > 1 && complex_symmetric(n, Ap, Ai, Ax, Az);
-    const bool symmetric = is_sym && !native;
+    const ZiChoice choice = zi_choice(*S->di, n, [&] { return complex_symmetric(n, Ap, Ai, Ax, Az); });
+    const bool native = choice.native, is_sym = choice.is_sym, symmetric = choice.symmetric;
     std::vector<char> swap;
     std::vector<double> unit;
     bool any = false;
@@ -392,20 +428,7 @@ int umfpack_zi_numeric(const int Ap[], const int Ai[], const double Ax[], const 
         if (it == last || *it != j) continue;
         const size_t p = (size_t)(it - Ai);
         const double re = Az ? Ax[p] : Ax[2 * p], im = Az ? Az[p] : Ax[2 * p + 1];
-        const double mod = std::hypot(re, im);
-        if (!std::isfinite(mod) || mod == 0.0) continue;
-        // u = sqrt(conj(a) / |a|), the root with the non-negative real part, without cancellation
-        const double c = re / mod, sn = -im / mod;
-        double ur, ui;
-        if (c >= 0.0) {
-          ur = std::sqrt(0.5 * (1.0 + c));
-          ui = sn / (2.0 * ur);
-        } else {
-          ui = std::copysign(std::sqrt(0.5 * (1.0 - c)), sn);
-          ur = sn / (2.0 * ui);
-        }
-        unit[(size_t)2 * j] = ur;
-        unit[(size_t)2 * j + 1] = ui;
+        spl::congruence_unit(re, im, &unit[(size_t)2 * j]);
       }
     } else if (!native) {
       swap.assign((size_t)n, 0);
@@ -419,11 +442,7 @@ int umfpack_zi_numeric(const int Ap[], const int Ai[], const double Ax[], const 
     Embedded E;
     if (!embed(n, Ap, Ai, Ax, Az, true, E, any ? swap.data() : nullptr, symmetric ? unit.data() : nullptr))
       return UMFPACK_ERROR_out_of_memory;
-    if (timing)
-      fprintf(stderr, "[zi numeric] %s embedding built on the host %8.2f ms\n",
-              native ? (is_sym ? "plain (native complex fronts, symmetric)" : "plain (native complex fronts)")
-                     : symmetric ? "symmetric" : "general",
-              std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count());
+    if (timing) report_embedding(choice, "host", t0);
     spl::EmbeddingOpts opts;
     opts.embedding = true;
     opts.native = native;
@@ -431,6 +450,91 @@ int umfpack_zi_numeric(const int Ap[], const int Ai[], const double Ax[], const 
     if (any) opts.pair_swap = std::move(swap);
     if (symmetric) opts.pair_unit = std::move(unit);
     return spl::numeric_factor(S->di, E.p.data(), E.i.data(), E.x.data(), std::move(opts), &N);
+  });
+  *NumericOut = N;
+  return st;
+}
+
+// ---- the same two calls on a device-resident complex matrix handle (umfpack_hip.h; kernels in lu_from_handle.hip) ---
+
+int spl_umfpack_zi_symbolic_dev(void *H, void **SymbolicOut) {
+  if (!SymbolicOut) return UMFPACK_ERROR_argument_missing;
+  *SymbolicOut = nullptr;
+  spl::Matrix *M = spl::as_matrix(H);
+  if (!M) return UMFPACK_ERROR_argument_missing;
+  const int hs = zi_handle_status(M);
+  if (hs != UMFPACK_OK) return hs;
+  return spl::umf_guarded([&] {
+    spl::DeviceGuard g(M->device);
+    // the analysis is host code: the pattern crosses once, here
+    std::vector<int> Ap, Ai;
+    spl::handle_to_host_csc(M, Ap, Ai, nullptr);
+    void *S = nullptr;
+    const int st = umfpack_zi_symbolic((int)M->nrows_global, (int)M->ncols, Ap.data(), Ai.data(), nullptr, nullptr, &S,
+                                       nullptr, nullptr);
+    if (st < 0) return st;
+    try {
+      spl::pattern_from_handle(M, static_cast<ZiSymbolic *>(S)->dpat, hipStreamPerThread);
+    } catch (...) {
+      umfpack_zi_free_symbolic(&S);
+      throw;
+    }
+    *SymbolicOut = S;
+    return st;
+  });
+}
+
+int spl_umfpack_zi_numeric_dev(void *H, void *SymbolicIn, void **NumericOut) {
+  if (!NumericOut) return UMFPACK_ERROR_argument_missing;
+  *NumericOut = nullptr;
+  ZiSymbolic *S = static_cast<ZiSymbolic *>(SymbolicIn);
+  if (!S || S->magic != 0x5A53594Du) return UMFPACK_ERROR_invalid_Symbolic_object;
+  spl::Matrix *M = spl::as_matrix(H);
+  if (!M) return UMFPACK_ERROR_argument_missing;
+  const int hs = zi_handle_status(M);
+  if (hs != UMFPACK_OK) return hs;
+  spl::Numeric *N = nullptr;
+  const int st = spl::umf_guarded([&] {
+    spl::DeviceGuard g(M->device);
+    if (S->di->rectangular) {  // no factors are kept: the host route, with its statuses
+      if (M->nrows_global != S->di->n_row || M->ncols != S->di->n_col) return UMFPACK_ERROR_different_pattern;
+      std::vector<int> Ap, Ai;
+      std::vector<double> Ax;
+      spl::handle_to_host_csc(M, Ap, Ai, &Ax);
+      void *out = nullptr;
+      const int sr = umfpack_zi_numeric(Ap.data(), Ai.data(), Ax.data(), nullptr, S, &out, nullptr, nullptr);
+      N = static_cast<spl::Numeric *>(out);
+      return sr;
+    }
+    const int n = S->n;
+    hipStream_t s = hipStreamPerThread;
+    if (M->nrows_global != n || M->ncols != n || M->nnz != (int64_t)S->Ap[(size_t)n] ||
+        !spl::handle_has_pattern(M, S->dpat, S->Ap, S->ai_hash, s))
+      return UMFPACK_ERROR_different_pattern;
+    const bool timing = getenv("SPL_MF_TIMING") != nullptr;
+    const auto t0 = std::chrono::steady_clock::now();
+    // the decisions of umfpack_zi_numeric, their inputs computed where the matrix is: symmetry, swap flags and units
+    // by kernels over the handle's image; n bytes of flags or 16 n of units come down for the solves
+    const ZiChoice choice = zi_choice(*S->di, n, [&] { return spl::complex_handle_symmetric(M, s); });
+    spl::ComplexDiagonal D;
+    if (choice.symmetric) spl::complex_handle_diagonal(M, true, D, s);
+    else if (!choice.native) spl::complex_handle_diagonal(M, false, D, s);
+    spl::EmbeddingOpts opts;
+    opts.embedding = true;
+    opts.native = choice.native;
+    opts.zsym = choice.native && choice.is_sym;
+    if (D.any_swap) opts.pair_swap = std::move(D.swap);
+    if (choice.symmetric) opts.pair_unit = std::move(D.unit);
+    // rows of E: the embedding kernel; rows of E^T: its transpose on the device (exact and order-preserving: the two
+    // images are those the host route makes from embed()'s CSC arrays)
+    const spl::StageImages from_handle = [&](spl::Numeric *Nn, hipStream_t ss, const std::function<void(const char *)> &lap) {
+      Nn->A = spl::embed_handle(M, D.any_swap ? D.d_swap.get() : nullptr, choice.symmetric ? D.d_unit.get() : nullptr, ss);
+      if (!Nn->A->rowptr.get()) return UMFPACK_ERROR_out_of_memory;
+      if (timing) report_embedding(choice, "device", t0);
+      lap("rows of E (embedding)");
+      return spl::stage_transposed_image(Nn, true);
+    };
+    return spl::numeric_factor_staged(S->di, std::move(opts), from_handle, nullptr, nullptr, nullptr, &N);
   });
   *NumericOut = N;
   return st;

@@ -64,6 +64,14 @@ def _declare():
     L.spl_umfpack_di_solve_many_dev.argtypes = [i, ip, ip, dp, i, vp, vp, vp]
     L.spl_umfpack_zi_solve_many_dev.restype = i
     L.spl_umfpack_zi_solve_many_dev.argtypes = [i, ip, ip, dp, i, vp, vp, vp]
+    for name in ("spl_umfpack_di_symbolic_dev", "spl_umfpack_zi_symbolic_dev"):
+        getattr(L, name).restype = i
+        getattr(L, name).argtypes = [vp, C.POINTER(vp)]
+    for name in ("spl_umfpack_di_numeric_dev", "spl_umfpack_zi_numeric_dev"):
+        getattr(L, name).restype = i
+        getattr(L, name).argtypes = [vp, vp, C.POINTER(vp)]
+    L.spl_umfpack_dimension.restype = i
+    L.spl_umfpack_dimension.argtypes = [vp]
     L.spl_umfpack_path.restype = i
     L.spl_umfpack_path.argtypes = [vp]
     L.spl_umfpack_stats.restype = C.c_int
@@ -202,6 +210,41 @@ def factor(mat, analysis):
     return f
 
 
+def analyzeDevice(dm):
+    """`analyze` of a device-resident matrix (a `DeviceMatrix`, real or complex): spl_umfpack_{di,zi}_symbolic_dev.
+    The pattern crosses to the host once (the analysis is host code); the result serves `factor` and `factorDevice`."""
+    L = _declare()
+    _ffi.require_gpu()
+    sym = C.c_void_p()
+    if dm.is_complex:
+        st = L.spl_umfpack_zi_symbolic_dev(dm.handle, C.byref(sym))
+        a = Analysis(sym.value, "umfpack_zi_free_symbolic")
+        a.complex = True
+    else:
+        st = L.spl_umfpack_di_symbolic_dev(dm.handle, C.byref(sym))
+        a = Analysis(sym.value, "umfpack_di_free_symbolic")
+    _report("analyzeDevice: umfpack_symbolic", st)
+    return a
+
+
+def factorDevice(dm, analysis):
+    """`factor` of a device-resident matrix (spl_umfpack_{di,zi}_numeric_dev): the matrix is factored where it lies —
+    nothing of it crosses PCIe, the embedding of a complex matrix is built by a kernel — and the handle is only
+    borrowed: the factors keep their own device copies.  `analysis` may come from `analyze` or `analyzeDevice`."""
+    L = _declare()
+    _ffi.require_gpu()
+    num = C.c_void_p()
+    if dm.is_complex:
+        st = L.spl_umfpack_zi_numeric_dev(dm.handle, analysis.value, C.byref(num))
+        f = Factors(num.value, "umfpack_zi_free_numeric")
+        f.complex = True
+    else:
+        st = L.spl_umfpack_di_numeric_dev(dm.handle, analysis.value, C.byref(num))
+        f = Factors(num.value, "umfpack_di_free_numeric")
+    f.status = _report("factorDevice: umfpack_numeric", st)
+    return f
+
+
 def linearSolve_(fact, mode, mat, b):
     """solve with existing factors (Umfpack.hs:87-102); returns the solution vector"""
     L = _declare()
@@ -273,9 +316,16 @@ def solve(mat, b):
 def linearSolveManyDevice_(fact, mode, mat, B):
     """`linearSolveMany_` with the right-hand sides and the solutions in device memory: B is a torch tensor on
     the GPU of shape (k, nrows) — row c = right-hand side c, float64 for real factors, complex128 for complex
-    ones — and the result is a new tensor of the same shape and device (spl_umfpack_{di,zi}_solve_many_dev)."""
+    ones — and the result is a new tensor of the same shape and device (spl_umfpack_{di,zi}_solve_many_dev).
+    `mat` is the host `Matrix`, or a `DeviceMatrix` or None for factors of a device-resident matrix (`factorDevice`):
+    the C side then gets NULL arrays, as umfpack_hip.h allows — the factors hold their own copy of the matrix."""
     import torch
     L = _declare()
+    from .sparse import DeviceMatrix, Matrix
+    if mat is None or isinstance(mat, DeviceMatrix):
+        return _solve_many_device_null(L, fact, mode, mat, B)
+    if not isinstance(mat, Matrix):
+        raise UmfpackError("linearSolveManyDevice_: mat must be a Matrix, a DeviceMatrix or None, not %s" % type(mat).__name__)
     want = torch.complex128 if mat.is_complex else torch.float64
     if bool(fact.complex) != bool(mat.is_complex):
         raise UmfpackError("linearSolveManyDevice_: %s factors used with a %s matrix"
@@ -295,6 +345,32 @@ def linearSolveManyDevice_(fact, mode, mat, B):
     _report("linearSolveManyDevice_: umfpack_solve", st)
     return X
 
+def _solve_many_device_null(L, fact, mode, dm, B):
+    """linearSolveManyDevice_ without host arrays: dm is a DeviceMatrix (checked against the factors) or None"""
+    import torch
+    n = int(L.spl_umfpack_dimension(fact.value)) // (2 if fact.complex else 1)
+    if dm is not None:
+        inf = dm.info()
+        if bool(fact.complex) != bool(dm.is_complex):
+            raise UmfpackError("linearSolveManyDevice_: %s factors used with a %s matrix"
+                               % ("complex" if fact.complex else "real", "complex" if dm.is_complex else "real"))
+        if inf["nrows_global"] != n or inf["ncols"] != n:
+            raise UmfpackError("linearSolveManyDevice_: factors of %d unknowns used with a %d x %d matrix"
+                               % (n, inf["nrows_global"], inf["ncols"]))
+    want = torch.complex128 if fact.complex else torch.float64
+    if not (isinstance(B, torch.Tensor) and B.is_cuda and B.dtype == want and B.dim() == 2 and B.shape[1] == n
+            and B.is_contiguous()):
+        raise UmfpackError("linearSolveManyDevice_: B must be a contiguous %s GPU tensor of shape (k, %d)" % (want, n))
+    k = int(B.shape[0])
+    X = torch.zeros((k, n), dtype=want, device=B.device)
+    if k == 0:
+        return X
+    torch.cuda.current_stream(B.device).synchronize()  # the library works on the null stream of the device
+    fn = L.spl_umfpack_zi_solve_many_dev if fact.complex else L.spl_umfpack_di_solve_many_dev
+    with torch.cuda.device(B.device):
+        st = fn(int(mode), None, None, None, k, C.c_void_p(X.data_ptr()), C.c_void_p(B.data_ptr()), fact.value)
+    _report("linearSolveManyDevice_: umfpack_solve", st)
+    return X
 
 
 _PATH_NAMES = {0: "band LU with partial pivoting", 1: "band without interchanges", 2: "band without interchanges (speculation)",
