@@ -12,14 +12,20 @@
 //   numeric  (GPU):  LU of B = P A P^T without row interchanges — blocked in band storage
 //                    (band_nopiv.hip) or multifrontal on the tree (multifrontal.hip), both on the
 //                    fp64 matrix cores — when A is diagonally dominant by columns, and as a checked
-//                    speculation otherwise; fallback: LAPACK band storage AB[2kl+ku+1][n] with
+//                    speculation otherwise.  What replaces a speculation that fails, and in which
+//                    order, is the ladder (next_factors): block-pivot retry of an L D L^T
+//                    speculation, static pivoting, and last LAPACK band storage AB[2kl+ku+1][n] with
 //                    partial pivoting inside the band (this file), numerically the same as dense
-//                    partial pivoting; a zero pivot sets the singular-matrix warning;
+//                    partial pivoting; a zero pivot sets the singular-matrix warning.  Which factors
+//                    an object holds is Numeric::held (umfpack_impl.hpp); they change hands through
+//                    factors_fit / rebuild_factors only;
 //   solve    (GPU):  permute, forward/back substitution (or U^T, L^T for sys = 1) through the band
 //                    or the tree, un-permute, then up to 2 steps of iterative refinement with the
 //                    residual computed by the SpMV kernels (UMFPACK's default irstep = 2) and
 //                    UMFPACK's stopping rules on the componentwise backward error; all right-hand
-//                    sides of a batched call share the passes.
+//                    sides of a batched call share the passes.  Speculative factors whose refined
+//                    solution is not backward stable are rejected: the solve asks the ladder for the
+//                    next factors and runs again (solve_columns).
 // The pivoting band LU here updates one column at a time (rank-1 updates, HBM-bound): it is the
 // safety net, not the fast path.
 #include <stdio.h>
@@ -498,21 +504,30 @@ __global__ __launch_bounds__(256) void axpby_kernel(size_t n, double alpha, cons
   if (i < n) y[i] = alpha * x[i] + (beta == 0.0 ? 0.0 : beta * y[i]);
 }
 
+// the tree the fronts of the factors held stand on; null for the band kinds
+static const mf::Tree *held_tree(const Numeric *N) {
+  if (N->held != Held::tree && N->held != Held::tree_static) return nullptr;
+  return N->kind.complex_fronts ? N->ztree.get() : N->tree.get();
+}
+
 // columns of c (device, permuted order, column r at d_c + r * stride) <- solutions of B z = c or
 // B^T z = c; kalloc >= k columns are allocated (a multiple of kSolveGroup when k > 1)
 void band_solve(const Numeric *N, int sys, double *d_c, int k, size_t stride, hipStream_t s) {
   if (N->n == 0 || k == 0) return;
-  if (N->mfact) {
-    mf_solve(N->mfact, sys, d_c, k, stride, s);
-    return;
+  switch (N->held) {
+    case Held::tree:
+    case Held::tree_static:
+      return mf_solve(N->mfact, sys, d_c, k, stride, s);
+    case Held::band_blocked:
+      return band_nopiv_solve(sys, N->n, N->kl, N->ku, N->ldab, N->AB.get(), N->blkinv.get(), d_c, k, stride, s);
+    case Held::band_pivoted:
+      for (int c = 0; c < k; ++c)
+        hipLaunchKernelGGL(band_solve_kernel, dim3(1), dim3(1024), 0, s, sys, N->n, N->kl, N->ku, N->ldab,
+                           N->AB.get(), N->ipiv.get(), d_c + (size_t)c * stride);
+      return;
+    case Held::none:  // (a broken object: solve_columns has returned before it gets here)
+      return;
   }
-  if (N->nopiv) {
-    band_nopiv_solve(sys, N->n, N->kl, N->ku, N->ldab, N->AB.get(), N->blkinv.get(), d_c, k, stride, s);
-    return;
-  }
-  for (int c = 0; c < k; ++c)
-    hipLaunchKernelGGL(band_solve_kernel, dim3(1), dim3(1024), 0, s, sys, N->n, N->kl, N->ku, N->ldab,
-                       N->AB.get(), N->ipiv.get(), d_c + (size_t)c * stride);
 }
 
 // d_x (device, original order) <- op(A)^-1 d_b using the factors only, k columns
@@ -521,7 +536,7 @@ void factor_solve(const Numeric *N, int sys, const double *d_b, double *d_x, dou
   const int n = N->n;
   if (n == 0 || k == 0) return;
   const dim3 g((unsigned)((n + 255) / 256), (unsigned)k);
-  if (N->sp_stage == 1) {
+  if (N->held == Held::tree_static) {
     // factors of B = Dr P A Dc:  A x = b  <=>  B (Dc^-1 x) = Dr P b;  A^T x = b  <=>  B^T (Dr^-1 P x) = Dc b
     // (the row permutation, the scalings and B's ordering are composed into one gather on either side)
     const int a = sys == UMFPACK_A ? 0 : 2;
@@ -536,11 +551,20 @@ void factor_solve(const Numeric *N, int sys, const double *d_b, double *d_x, dou
   // Factors of a SYMMETRIC matrix (L D L^T on the tree): the transposed system is the same system, so it takes the
   // untransposed kernels (the faster ones: their panels run down the contiguous direction).  On native complex fronts
   // sys = At asks for the CONJUGATE transpose: A^H = conj(A) for A == A^T, and conj(A) x = b <=> A conj(x) = conj(b).
-  const bool same = sys != UMFPACK_A && N->mfact && N->mf_sym && !N->mf_piv;
-  const bool conj = same && N->zfront;
+  const bool same = sys != UMFPACK_A && N->held == Held::tree && N->kind.ldlt;
+  const bool conj = same && N->kind.complex_fronts;
   hipLaunchKernelGGL(gather_perm_kernel, g, dim3(256), 0, s, n, N->perm.get(), d_b, d_work, stride, conj ? 1 : 0);
   band_solve(N, same ? UMFPACK_A : sys, d_work, k, stride, s);
   hipLaunchKernelGGL(gather_perm_kernel, g, dim3(256), 0, s, n, N->inv.get(), d_work, d_x, stride, conj ? 2 : 0);  // x[i] = z[inv[i]]
+}
+
+// a device array on the host (synchronises)
+template <typename T>
+std::vector<T> download(const T *d, size_t n, hipStream_t s) {
+  std::vector<T> h(n);
+  if (n) SPL_HIP(hipMemcpyAsync(h.data(), d, n * sizeof(T), hipMemcpyDeviceToHost, s));
+  SPL_HIP(hipStreamSynchronize(s));
+  return h;
 }
 
 // install an ordering (new -> old, old -> new) on the device
@@ -565,11 +589,16 @@ __global__ __launch_bounds__(256) void same_csr_kernel(int64_t n, int64_t nnz, c
   if (bad) *differ = 1;
 }
 
+// the environment switch `name` is set and begins with `c`
+static bool env_is(const char *name, char c) {
+  const char *e = getenv(name);
+  return e && e[0] == c;
+}
+
 // honour_env = false: the fact itself, whatever SPL_LU_SYMMETRIC says (the inertia needs the fact, not the choice of
 // factorisation)
 static bool matrix_is_symmetric(const Numeric *N, hipStream_t s, bool honour_env = true) {
-  const char *e = getenv("SPL_LU_SYMMETRIC");
-  if (honour_env && e && e[0] == '0') return false;
+  if (honour_env && env_is("SPL_LU_SYMMETRIC", '0')) return false;
   const Matrix *A = N->A, *At = N->At;
   if (!A || !At || A->nnz != At->nnz || !A->rowptr.get() || !At->rowptr.get()) return false;
   DBuf<int> differ(1);
@@ -598,85 +627,130 @@ __global__ __launch_bounds__(256) void row_scale_kernel(int64_t m, int step, con
   rs[g] = sum > 0.0 && sum < 1e300 ? 1.0 / sum : 1.0;
 }
 
-// resident bytes of the tree factors held (or about to be built)
-static size_t tree_factor_bytes(const Numeric *N) {
-  if (N->zfront && N->ztree) return mf_device_bytes(*N->ztree, 2);
-  return N->tree ? mf_device_bytes(*N->tree, 1) : 0;
+// SPL_LU_BLOCK_PIVOT=0: no threshold pivoting inside the diagonal blocks of the fronts, as a choice of the
+// speculation or as the retry of a rejected L D L^T speculation
+static bool block_pivot_enabled() { return !env_is("SPL_LU_BLOCK_PIVOT", '0'); }
+
+// Phase times on stderr under SPL_MF_TIMING (diagnostic): lap() waits for the stream and prints the time since the
+// last lap; since(): milliseconds since the timer was made.
+struct PhaseTimer {
+  using Clock = std::chrono::steady_clock;
+  const char *fmt;  // of a lap: "[tag] %-26s %8.2f ms\n"
+  hipStream_t s;
+  const bool on = getenv("SPL_MF_TIMING") != nullptr;
+  const Clock::time_point t_begin = Clock::now();
+  Clock::time_point t_last = t_begin;
+  double since() const { return std::chrono::duration<double, std::milli>(Clock::now() - t_begin).count(); }
+  void lap(const char *what) {
+    if (!on) return;
+    (void)hipStreamSynchronize(s);
+    const auto now = Clock::now();
+    fprintf(stderr, fmt, what, std::chrono::duration<double, std::milli>(now - t_last).count());
+    t_last = now;
+  }
+};
+
+// ---- replacing the factors of an object --------------------------------------------------------------------------------
+// The protocol of the three factorisations below: decide whether the new factors fit (factors_fit) BEFORE anything is
+// released — a miss is a return value and leaves the object as it was —, then rebuild_factors: release what is held,
+// build; a build that throws leaves the object without factors (broken).
+
+// resident bytes of the factors held
+static size_t held_factor_bytes(const Numeric *N) {
+  if (const mf::Tree *T = held_tree(N)) return mf_device_bytes(*T, N->kind.complex_fronts ? 2 : 1);
+  return (N->AB.n + N->blkinv.n) * sizeof(double);  // the band kinds (none: both empty)
 }
 
-// multifrontal factors without interchanges on the nested-dissection tree (multifrontal.hip)
-void factor_multifrontal(Numeric *N, hipStream_t s) {
+// Will factors of `bytes` fit once those held are gone?  Free memory plus what is held, less an eighth.
+static bool factors_fit(const Numeric *N, size_t bytes) {
+  const size_t avail = device_free_bytes() + held_factor_bytes(N);
+  return bytes <= avail - avail / 8;
+}
+
+static void release_factors(Numeric *N) {
   N->det_checked = 0;
   N->AB.release();
   N->blkinv.release();
   if (N->mfact) { mf_free(N->mfact); N->mfact = nullptr; }
-  const size_t free_b = device_free_bytes();
-  N->zfront = N->ztree ? 1 : 0;
-  if (tree_factor_bytes(N) > free_b - free_b / 8) throw DeviceError{SPL_ERROR_out_of_memory};
-  N->nopiv = 1;
-  if (!N->A->rowptr.get()) throw DeviceError{SPL_ERROR_index_overflow};  // int32 row pointers at this seam
-  const char *bp = getenv("SPL_LU_BLOCK_PIVOT");
-  const bool pivot = !N->dominant && !(bp && bp[0] == '0');
-  if (pivot && N->A->rowptr64.get()) {
-    const int step = N->zfront ? 2 : 1;
-    const int64_t m = (int64_t)N->n / step;
-    if ((int64_t)N->rscale.n != m) N->rscale.alloc((size_t)m);
-    hipLaunchKernelGGL(row_scale_kernel, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, s, m, step, N->perm.get(),
-                       N->A->rowptr64.get(), N->A->val.get(), N->rscale.get());
+  // tree_static: B and the gathers around its solves go with its factors
+  N->spA.reset();
+  N->spAt.reset();
+  for (int a = 0; a < 4; ++a) { N->sp_idx[a].release(); N->sp_scale[a].release(); }
+  N->held = Held::none;
+  N->kind = TreeKind{};
+}
+
+template <typename Build>
+static void rebuild_factors(Numeric *N, Build &&build) {
+  release_factors(N);
+  try {
+    build();
+  } catch (...) {
+    N->broken = 1;  // the old factors are gone and the new ones could not be built
+    throw;
   }
-  const double *rscale = pivot && N->rscale.get() && N->A->rowptr64.get() ? N->rscale.get() : nullptr;
-  if (N->zfront) {
-    // the embedding of a complex matrix: complex fronts on the tree of the complex pattern, assembled from E's own
-    // arrays (column 2j / row 2j of E hold column / row j of the complex matrix); perm / inv are the expanded ordering
-    N->mf_sym = N->zsym && !N->block_pivot_retry;
-    N->mf_piv = pivot && !N->mf_sym;
-    N->mfact = mf_factor(N->ztree, N->At->rowptr.get(), N->At->colidx.get(), N->At->val.get(), N->A->rowptr.get(),
-                         N->A->colidx.get(), N->A->val.get(), N->perm.get(), N->inv.get(), s, N->mf_sym != 0, true,
-                         N->mf_piv != 0, rscale);
+}
+
+// Multifrontal factors on the nested-dissection tree (multifrontal.hip), no interchanges between the fronts.
+// false: they do not fit; nothing was touched.  As the block-pivot retry of a rejected L D L^T speculation (`retry`:
+// the same tree once more as LU) the order is the OTHER one: the factors held — of the same fronts — are released
+// first and the fit is measured afterwards; a miss there is an error and leaves the object without factors (broken).
+bool factor_multifrontal(Numeric *N, bool retry, hipStream_t s) {
+  TreeKind kind{N->ztree != nullptr, false, false};
+  const std::shared_ptr<const mf::Tree> &tree = kind.complex_fronts ? N->ztree : N->tree;
+  const size_t bytes = mf_device_bytes(*tree, kind.complex_fronts ? 2 : 1);
+  if (!retry && !factors_fit(N, bytes)) return false;
+  rebuild_factors(N, [&] {
+    if (retry && !factors_fit(N, bytes)) throw DeviceError{SPL_ERROR_out_of_memory};
+    if (!N->A->rowptr.get()) throw DeviceError{SPL_ERROR_index_overflow};  // int32 row pointers at this seam
+    const bool pivot = !N->dominant && block_pivot_enabled();
+    if (pivot && N->A->rowptr64.get()) {
+      const int step = kind.complex_fronts ? 2 : 1;
+      const int64_t m = (int64_t)N->n / step;
+      if ((int64_t)N->rscale.n != m) N->rscale.alloc((size_t)m);
+      hipLaunchKernelGGL(row_scale_kernel, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, s, m, step, N->perm.get(),
+                         N->A->rowptr64.get(), N->A->val.get(), N->rscale.get());
+    }
+    const double *rscale = pivot && N->rscale.get() && N->A->rowptr64.get() ? N->rscale.get() : nullptr;
+    // A symmetric matrix (exactly: A == A^T) is factored as L D L^T on the same fronts: the trailing updates only
+    // compute the tiles on and below the diagonal (Band::sym, csrc/dense_lu_kernels.hpp); SPL_LU_SYMMETRIC=0: plain LU.
+    // The embedding of a complex matrix: complex fronts on the tree of the complex pattern, assembled from E's own
+    // arrays (column 2j / row 2j of E hold column / row j of the complex matrix); perm / inv are the expanded ordering.
+    kind.ldlt = !retry && (kind.complex_fronts ? N->zsym != 0 : matrix_is_symmetric(N, s));
+    kind.block_pivoting = pivot && !kind.ldlt;
+    N->mfact = mf_factor(tree, N->At->rowptr.get(), N->At->colidx.get(), N->At->val.get(), N->A->rowptr.get(),
+                         N->A->colidx.get(), N->A->val.get(), N->perm.get(), N->inv.get(), s, kind.ldlt,
+                         kind.complex_fronts, kind.block_pivoting, rscale);
     N->singular = mf_singular(N->mfact);
-    return;
-  }
-  // a symmetric matrix (exactly: A == A^T) is factored as L D L^T on the same fronts: the trailing updates only
-  // compute the tiles on and below the diagonal (Band::sym, csrc/dense_lu_kernels.hpp); SPL_LU_SYMMETRIC=0: plain LU
-  N->mf_sym = !N->block_pivot_retry && matrix_is_symmetric(N, s) ? 1 : 0;
-  N->mf_piv = pivot && !N->mf_sym;
-  N->mfact = mf_factor(N->tree, N->At->rowptr.get(), N->At->colidx.get(), N->At->val.get(), N->A->rowptr.get(),
-                       N->A->colidx.get(), N->A->val.get(), N->perm.get(), N->inv.get(), s, N->mf_sym != 0, false,
-                       N->mf_piv != 0, rscale);
-  N->singular = mf_singular(N->mfact);
+    N->kind = kind;
+    N->held = Held::tree;
+  });
+  return true;
 }
 
 // Static pivoting (static_pivot.hpp): factor B = Dr P A Dc — the maximum-product transversal on the diagonal,
 // |b_jj| = 1 >= |b_ij| — without interchanges on B's own nested-dissection tree.  Returns false when it
-// cannot be done (structurally singular, scalings out of range, does not fit, zero pivot): the caller then
-// falls back to the band factorisation with partial pivoting.  The object is left consistent either way.
+// cannot be done (structurally singular, scalings out of range, does not fit, zero pivot): the ladder then
+// goes on to the band factorisation with partial pivoting.  The object is left consistent either way: untouched, or —
+// after a zero pivot — without factors.
 bool factor_static_pivot(Numeric *N, const int *Ap, const int *Ai, const double *Ax, hipStream_t s) {
   const int n = N->n;
-  if (N->sp_stage != 0 || n < 2) return false;
-  const char *off = getenv("SPL_LU_STATIC_PIVOT");
-  if (off && off[0] == '0') return false;
-  N->sp_stage = 2;  // whatever happens below, it is not tried twice
-  N->det_checked = 0;
-  const bool timing = getenv("SPL_MF_TIMING") != nullptr;
-  const auto t_begin = std::chrono::steady_clock::now();
-  auto since = [&] { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_begin).count(); };
+  if (N->static_pivot_tried || n < 2) return false;
+  if (env_is("SPL_LU_STATIC_PIVOT", '0')) return false;
+  N->static_pivot_tried = true;  // whatever happens below, it is not tried twice
+  PhaseTimer timer{"[static pivot] %s %8.2f ms\n", s};
   sp::Transversal T;
   double match_seconds = 180.0;  // SPL_LU_MATCH_SECONDS: how long the (sequential, host) matching may take
   if (const char *ev = getenv("SPL_LU_MATCH_SECONDS")) match_seconds = atof(ev);
   if (!sp::max_product_transversal(n, Ap, Ai, Ax, T, match_seconds)) return false;
-  if (timing) fprintf(stderr, "[static pivot] transversal done at %.1f ms\n", since());
+  if (timer.on) fprintf(stderr, "[static pivot] transversal done at %.1f ms\n", timer.since());
   std::vector<int> Bp, Bi;
   std::vector<double> Bx;
   sp::permuted_scaled_csc(n, Ap, Ai, Ax, T, Bp, Bi, Bx);
   std::shared_ptr<mf::Tree> tree = std::make_shared<mf::Tree>();
   mf::build_tree(n, Bp.data(), Bi.data(), 256, *tree);
-  if (timing) fprintf(stderr, "[static pivot] B and its tree (%d fronts, %.3g flops) at %.1f ms\n", tree->nfronts, tree->flops, since());
-  {
-    size_t held = (N->AB.n + N->blkinv.n) * sizeof(double);
-    if (N->mfact) held += tree_factor_bytes(N);
-    const size_t avail = device_free_bytes() + held;
-    if (mf_device_bytes(*tree, 1) + (size_t)Bp[(size_t)n] * 24 > avail - avail / 8) return false;
-  }
+  if (timer.on) fprintf(stderr, "[static pivot] B and its tree (%d fronts, %.3g flops) at %.1f ms\n", tree->nfronts, tree->flops, timer.since());
+  if (!factors_fit(N, mf_device_bytes(*tree, 1) + (size_t)Bp[(size_t)n] * 24)) return false;
   void *hBt = nullptr, *hB = nullptr;
   if (spl_matrix_create_csr(n, n, 0, n, Bp.data(), Bi.data(), Bx.data(), &hBt) != SPL_OK) return false;
   if (spl_matrix_create(n, n, Bp.data(), Bi.data(), Bx.data(), &hB) != SPL_OK) { spl_matrix_free(&hBt); return false; }
@@ -697,14 +771,9 @@ bool factor_static_pivot(Numeric *N, const int *Ap, const int *Ai, const double 
     idx[1][(size_t)j] = ind[(size_t)j];  sc[1][(size_t)j] = T.dc[(size_t)j];                           // x_j = dc_j z[inv[j]]
     idx[3][(size_t)j] = ind[(size_t)T.col_of_row[(size_t)j]];  sc[3][(size_t)j] = T.dr[(size_t)j];     // x_i = dr_i z[inv[newrow(i)]]
   }
-  // from here on the old factors are released: failures leave the object without factors (broken)
-  try {
-    N->AB.release();
-    N->blkinv.release();
-    if (N->mfact) { mf_free(N->mfact); N->mfact = nullptr; }
+  rebuild_factors(N, [&] {
     N->tree = tree;
     N->ztree.reset();  // B = Dr P E Dc is not the embedding of a complex matrix: real fronts from here on
-    N->zfront = 0;
     set_ordering(N, tree->perm, tree->inv, s);
     for (int a = 0; a < 4; ++a) {
       N->sp_idx[a].alloc((size_t)n);
@@ -713,42 +782,41 @@ bool factor_static_pivot(Numeric *N, const int *Ap, const int *Ai, const double 
       SPL_HIP(hipMemcpyAsync(N->sp_scale[a].get(), sc[a].data(), (size_t)n * sizeof(double), hipMemcpyHostToDevice, s));
     }
     SPL_HIP(hipStreamSynchronize(s));
-    delete N->spA;
-    delete N->spAt;
-    N->spA = B.release();
-    N->spAt = Bt.release();
-    N->nopiv = 1;
-    N->mf_sym = 0;  // B = Dr P A Dc is not symmetric
+    N->spA = std::move(B);
+    N->spAt = std::move(Bt);
+    // (B is not symmetric and is factored without interchanges of any kind: TreeKind stays all false)
     N->mfact = mf_factor(N->tree, N->spAt->rowptr.get(), N->spAt->colidx.get(), N->spAt->val.get(), N->spA->rowptr.get(),
                          N->spA->colidx.get(), N->spA->val.get(), N->perm.get(), N->inv.get(), s, false, false);
+    N->held = Held::tree_static;
     if (mf_singular(N->mfact)) {  // a zero pivot: these factors are useless; the band fallback rebuilds everything
-      N->sp_stage = 2;
-      return false;
+      release_factors(N);
+      return;
     }
     N->singular = 0;
-    N->sp_stage = 1;
-    if (timing) { (void)hipStreamSynchronize(s); fprintf(stderr, "[static pivot] factored at %.1f ms\n", since()); }
-    return true;
-  } catch (...) {
-    N->broken = 1;
-    throw;
-  }
+    if (timer.on) { (void)hipStreamSynchronize(s); fprintf(stderr, "[static pivot] factored at %.1f ms\n", timer.since()); }
+  });
+  return N->held == Held::tree_static;
 }
 
-// (re)build the band factors of P A P^T from the device copy of A^T's rows (= the CSC arrays);
-// nopiv selects the blocked no-interchange factorisation (band_nopiv.hip) or LAPACK-style
-// partial pivoting.  Throws DeviceError; sets N->singular.
+// Static pivoting with the matrix taken from the object's own device copy (the columns of A are the rows of N->At):
+// what a solve uses, whose `zi` caller passes the complex matrix in Ap / Ai / Ax — not the arrays of the embedding this
+// object factors (umfpack_zi.hip) —, and the numeric calls on handles, which have no host arrays.
+bool factor_static_pivot_of_copy(Numeric *N, hipStream_t s) {
+  if (N->static_pivot_tried || !N->At || !N->At->rowptr.get() || N->At->nnz <= 0) return false;
+  const size_t nnz = (size_t)N->At->nnz;
+  const std::vector<int> p = download(N->At->rowptr.get(), (size_t)N->n + 1, s), i = download(N->At->colidx.get(), nnz, s);
+  const std::vector<double> x = download(N->At->val.get(), nnz, s);
+  return factor_static_pivot(N, p.data(), i.data(), x.data(), s);
+}
+
 // The reverse Cuthill-McKee ordering of an object whose analysis skipped it (symbolic_common: the tree won by a lower
 // bound), from the pattern the object holds: the rows of A^T are the columns of A.
 static void ensure_band_ordering(Numeric *N, hipStream_t s) {
   const int n = N->n;
   if ((int)N->band_perm.size() == n || n == 0) return;
   if (!N->At || !N->At->rowptr.get()) throw DeviceError{SPL_ERROR_index_overflow};
-  const size_t nnz = (size_t)N->At->nnz;
-  std::vector<int> p((size_t)n + 1), i(nnz);
-  SPL_HIP(hipMemcpyAsync(p.data(), N->At->rowptr.get(), ((size_t)n + 1) * sizeof(int), hipMemcpyDeviceToHost, s));
-  SPL_HIP(hipMemcpyAsync(i.data(), N->At->colidx.get(), nnz * sizeof(int), hipMemcpyDeviceToHost, s));
-  SPL_HIP(hipStreamSynchronize(s));
+  const std::vector<int> p = download(N->At->rowptr.get(), (size_t)n + 1, s);
+  const std::vector<int> i = download(N->At->colidx.get(), (size_t)N->At->nnz, s);
   std::vector<int> perm, inv((size_t)n, 0);
   rcm_order(n, p.data(), i.data(), perm);
   for (int k = 0; k < n; ++k) inv[(size_t)perm[(size_t)k]] = k;
@@ -767,47 +835,33 @@ static void ensure_band_ordering(Numeric *N, hipStream_t s) {
   N->ku = ku;
 }
 
-void factor_band(Numeric *N, bool nopiv, hipStream_t s) {
+// (Re)build the band factors of P A P^T from the device copy of A^T's rows (= the CSC arrays); `blocked` selects the
+// blocked no-interchange factorisation (band_nopiv.hip) or LAPACK-style partial pivoting.  Sets N->singular.
+// false: the band does not fit.  That is decided BEFORE anything of the current factors is released: a band that does
+// not fit (a large 3-D matrix whose speculation failed) must leave the object as it was — its speculative factors
+// still answer solves, which then report the error again instead of reading freed memory.
+bool factor_band(Numeric *N, bool blocked, hipStream_t s) {
   const int n = N->n;
-  N->det_checked = 0;
   ensure_band_ordering(N, s);
-  // Will the band fit?  Decided BEFORE anything of the current factors is released: a band that does not
-  // fit (a large 3-D matrix whose speculation failed) must leave the object as it was — its speculative
-  // factors still answer solves, which then report the error again instead of reading freed memory.
-  const int ldab_new = nopiv ? band_nopiv_ldab(N->kl, N->ku) : (2 * N->kl + N->ku + 1);
+  const int ldab_new = blocked ? band_nopiv_ldab(N->kl, N->ku) : (2 * N->kl + N->ku + 1);
   const size_t band_elems = (size_t)ldab_new * (size_t)n;
-  {
-    size_t held = (N->AB.n + N->blkinv.n) * sizeof(double);
-    if (N->mfact) held += tree_factor_bytes(N);
-    const size_t avail = device_free_bytes() + held;
-    if (band_elems * sizeof(double) > avail - avail / 8) throw DeviceError{SPL_ERROR_out_of_memory};  // too wide
-  }
-  try {
-    if (N->mfact || N->tree) {  // leaving the multifrontal path: the band paths use the RCM ordering
-      if (N->mfact) { mf_free(N->mfact); N->mfact = nullptr; }
+  if (!factors_fit(N, band_elems * sizeof(double))) return false;  // too wide
+  rebuild_factors(N, [&] {
+    if (N->tree) {  // leaving the multifrontal path: the band paths use the RCM ordering
       N->tree.reset();
       N->ztree.reset();
-      N->zfront = 0;
       set_ordering(N, N->band_perm, N->band_inv, s);
     }
-    if (N->sp_stage == 1) N->sp_stage = 2;  // the factors of B are gone: solves use the plain gathers again
-    delete N->spA; N->spA = nullptr;
-    delete N->spAt; N->spAt = nullptr;
-    N->nopiv = nopiv ? 1 : 0;
     N->ldab = ldab_new;
-    N->AB.release();
-    N->blkinv.release();
     N->AB.alloc(band_elems);
     SPL_HIP(hipMemsetAsync(N->AB.get(), 0, band_elems * sizeof(double), s));
-    if (nopiv) N->blkinv.alloc(band_nopiv_inverse_elems(n));
-  } catch (...) {
-    N->broken = 1;  // the old factors are gone and the new ones could not be built
-    throw;
-  }
-  if (nopiv) {
+    if (blocked) N->blkinv.alloc(band_nopiv_inverse_elems(n));
+  });
+  N->held = blocked ? Held::band_blocked : Held::band_pivoted;
+  if (blocked) {
     N->singular = band_nopiv_factor(n, N->kl, N->ku, N->ldab, N->AB.get(), N->blkinv.get(), N->At->rowptr.get(),
                                     N->At->colidx.get(), N->At->val.get(), N->inv.get(), s);
-    return;
+    return true;
   }
   // scatter P A P^T into band storage (reads the CSC arrays the At handle already holds)
   const int kv = N->kl + N->ku;
@@ -836,6 +890,73 @@ void factor_band(Numeric *N, bool nopiv, hipStream_t s) {
   SPL_HIP(hipStreamSynchronize(s));
   SPL_HIP(hipGetLastError());
   N->singular = hs.singular;
+  return true;
+}
+
+// ---- the ladder ----------------------------------------------------------------------------------------------------------
+// The one place that holds the order of the factorisations an object may go through and the condition of each rung:
+//   1 speculation        numeric call only: factors without interchanges on the tree (or in the band when the analysis
+//                        chose it) — safe for a matrix that is diagonally dominant by columns, a speculation every
+//                        solve checks otherwise.  SPL_LU_FORCE_PIVOT=1, and =0 on a matrix that is not dominant: straight
+//                        to rung 4.  Does not fit, or a zero pivot in a speculation: on to rung 3 (no rung 2 here).
+//   2 block-pivot retry  rejected solve only: an L D L^T speculation once more on the same tree as LU with threshold
+//                        pivoting inside the diagonal blocks (no host work).  A zero pivot: on to rung 3.
+//   3 static pivoting    B = Dr P A Dc on its own tree, once: from the caller's arrays at numeric time, from the
+//                        object's own copy otherwise.  Still a speculation.
+//     (FGMRES polish)    rejected solve only, once per solve call, when B's factors are held: not a factorisation — the
+//                        solve runs it (Rung::polish) and asks again if that was not enough.
+//   4 pivoted band       partial pivoting in band storage; ends the speculation.  Does not fit: Rung::none, and the
+//                        factors held are intact.
+enum class Rung { speculation, block_pivot_retry, static_pivoting, polish, pivoted_band, none };
+struct LadderCall {
+  bool numeric_call;  // the numeric call asks for its first acceptable factors; else a solve rejected those held
+  const int *Ap, *Ai; const double *Ax;  // numeric call: the caller's CSC arrays, or all null (the object's own copy)
+  bool polished;  // rejected solve: this solve call has made its polish
+};
+
+Rung next_factors(Numeric *N, const LadderCall &at, hipStream_t s) {
+  bool band_only = false;
+  if (at.numeric_call) {
+    const bool force_pivot = env_is("SPL_LU_FORCE_PIVOT", '1'), no_speculation = env_is("SPL_LU_FORCE_PIVOT", '0');
+    N->dominant = !force_pivot && band_is_column_dominant(N->n, N->At->rowptr.get(), N->At->colidx.get(), N->At->val.get(), s);
+    band_only = force_pivot || (no_speculation && !N->dominant);
+    if (!band_only) {
+      // SPL_LU_TEST_SPECULATION_OOM (tests): as if the speculation did not fit.  The analysis left a region without
+      // separators as one giant leaf (Tree::gave_up): that front is not for factoring — straight to static pivoting,
+      // whose transversal gives the matrix its mesh pattern back.
+      bool built = N->dominant || !(getenv("SPL_LU_TEST_SPECULATION_OOM") || (N->tree && N->tree->gave_up));
+      if (built) {
+        try {
+          built = N->tree ? factor_multifrontal(N, false, s) : factor_band(N, true, s);
+        } catch (const DeviceError &e) {
+          // a real allocation failure inside the factorisation: for a speculation the same as "does not fit"
+          if (N->dominant || e.status != SPL_ERROR_out_of_memory) throw;
+          N->broken = 0;  // nobody has seen this object yet, and the next rung builds from nothing
+          built = false;
+        }
+        // The speculation's own ordering does not fit the device: the pattern of A + A^T has no separators — e.g. a
+        // mesh matrix whose rows arrive in random order (tools/fuzz_lu_scale.py, family perm2d: 195 364 unknowns
+        // returned UMFPACK_ERROR_out_of_memory where SuperLU solved).  The transversal of static pivoting puts the
+        // large entries back on the diagonal and B = Dr P A Dc is ordered on its own pattern.
+        if (!built && N->dominant) throw DeviceError{SPL_ERROR_out_of_memory};
+      }
+      N->speculative = N->dominant ? 0 : 1;
+      if (built && !(N->speculative && N->singular)) return Rung::speculation;  // a zero pivot without interchanges proves nothing
+    }
+  } else if (N->held == Held::tree && N->kind.ldlt && !N->block_pivot_retried && !N->static_pivot_tried &&
+             block_pivot_enabled()) {
+    N->block_pivot_retried = true;
+    factor_multifrontal(N, true, s);
+    if (!N->singular) return Rung::block_pivot_retry;
+  }
+  if (!band_only) {
+    if (at.Ap ? factor_static_pivot(N, at.Ap, at.Ai, at.Ax, s) : factor_static_pivot_of_copy(N, s)) return Rung::static_pivoting;
+    // the factors held ARE those of static pivoting and refinement has stalled
+    if (!at.numeric_call && N->held == Held::tree_static && !at.polished) return Rung::polish;
+  }
+  if (!factor_band(N, false, s)) return Rung::none;
+  N->speculative = 0;  // only now may other threads use the object without taking turns
+  return Rung::pivoted_band;
 }
 
 }  // namespace
@@ -1138,8 +1259,6 @@ int umfpack_di_symbolic(int n_row, int n_col, const int Ap[], const int Ai[], co
 
 namespace spl {
 
-static bool factor_static_pivot_of_copy(Numeric *N, hipStream_t s);
-
 int numeric_factor(Symbolic *S, const int *Ap, const int *Ai, const double *Ax, EmbeddingOpts opts, Numeric **NumericOut) {
   const int n = S->n;
   // rows of A^T == the CSC arrays as they are; rows of A by transposing that copy on the device (spl_matrix_create
@@ -1187,24 +1306,14 @@ int numeric_factor_staged(Symbolic *S, EmbeddingOpts opts, const StageImages &st
     // torch kernels, this library's other entry points) like the legacy stream itself, but factorisations and solves
     // issued by different host threads — the contour points of a FEAST iteration — overlap on the device
     hipStream_t s = hipStreamPerThread;
-    const bool timing = getenv("SPL_MF_TIMING") != nullptr;  // phase times on stderr (diagnostic)
-    auto t_last = std::chrono::steady_clock::now();
-    const std::function<void(const char *)> lap = [&](const char *what) {
-      if (!timing) return;
-      (void)hipStreamSynchronize(s);
-      const auto now = std::chrono::steady_clock::now();
-      fprintf(stderr, "[numeric] %-26s %8.2f ms\n", what, std::chrono::duration<double, std::milli>(now - t_last).count());
-      t_last = now;
-    };
+    PhaseTimer timer{"[numeric] %-26s %8.2f ms\n", s};
+    const std::function<void(const char *)> lap = [&](const char *what) { timer.lap(what); };
     N->n = n;
     N->kl = S->kl;
     N->ku = S->ku;
     // device copies of A: rows of A^T (the dominance test, the scatters of the factorisations) and rows of A (the
     // residuals of the refinement)
-    {
-      const int sts = stage(N, s, lap);
-      if (sts != UMFPACK_OK) return sts;
-    }
+    if (const int sts = stage(N, s, lap); sts != UMFPACK_OK) return sts;
     N->ipiv.alloc((size_t)n);
     N->perm.alloc((size_t)n);
     N->inv.alloc((size_t)n);
@@ -1217,42 +1326,10 @@ int numeric_factor_staged(Symbolic *S, EmbeddingOpts opts, const StageImages &st
     }
     set_ordering(N, N->tree ? N->tree->perm : N->band_perm, N->tree ? N->tree->inv : N->band_inv, s);
     lap("ordering, rows of A");
-    // Path: SPL_LU_FORCE_PIVOT=1 -> partial pivoting; =0 -> only provably safe no-interchange
-    // factors (column diagonal dominance); default -> no-interchange factors for every matrix,
-    // as a speculation when dominance does not hold (checked by every solve, see Numeric).
-    const char *force = getenv("SPL_LU_FORCE_PIVOT");
-    const bool force_pivot = force && force[0] == '1', no_speculation = force && force[0] == '0';
-    bool dominant = false;
-    if (!force_pivot)
-      dominant = band_is_column_dominant(n, N->At->rowptr.get(), N->At->colidx.get(), N->At->val.get(), s);
-    N->dominant = dominant ? 1 : 0;
-    if (!force_pivot && (dominant || !no_speculation)) {
-      // SPL_LU_TEST_SPECULATION_OOM (tests): as if the speculation did not fit.  The analysis left a region without
-      // separators as one giant leaf (Tree::gave_up): that front is not for factoring — straight to static pivoting,
-      // whose transversal gives the matrix its mesh pattern back.
-      bool fits = dominant || !(getenv("SPL_LU_TEST_SPECULATION_OOM") || (N->tree && N->tree->gave_up));
-      if (fits) {
-        try {
-          if (N->tree) factor_multifrontal(N, s); else factor_band(N, true, s);
-        } catch (const DeviceError &e) {
-          // The speculation's own ordering does not fit the device: the pattern of A + A^T has no separators — e.g. a
-          // mesh matrix whose rows arrive in random order (tools/fuzz_lu_scale.py, family perm2d: 195 364 unknowns
-          // returned UMFPACK_ERROR_out_of_memory where SuperLU solved).  The transversal of static pivoting puts the
-          // large entries back on the diagonal and B = Dr P A Dc is ordered on its own pattern.
-          if (dominant || e.status != SPL_ERROR_out_of_memory) throw;
-          fits = false;
-        }
-      }
-      N->speculative = dominant ? 0 : 1;
-      if (!fits || (N->speculative && N->singular)) {  // a zero pivot without interchanges proves nothing
-        if (!(Ap ? factor_static_pivot(N, Ap, Ai, Ax, s) : factor_static_pivot_of_copy(N, s))) {
-          N->speculative = 0;
-          factor_band(N, false, s);
-        }
-      }
-    } else {
-      factor_band(N, false, s);
-    }
+    // SPL_LU_FORCE_PIVOT=1 -> partial pivoting; =0 -> only provably safe no-interchange factors (column diagonal
+    // dominance); default -> no-interchange factors for every matrix, as a speculation when dominance does not hold
+    // (checked by every solve, see Numeric): the first rungs of the ladder
+    if (next_factors(N, LadderCall{true, Ap, Ai, Ax, false}, s) == Rung::none) return UMFPACK_ERROR_out_of_memory;
     lap("factorisation");
     *NumericOut = owned.release();
     return N->singular ? UMFPACK_WARNING_singular_matrix : UMFPACK_OK;
@@ -1360,26 +1437,6 @@ int spl_umfpack_di_numeric_dev(void *H, void *SymbolicIn, void **NumericOut) {
 
 namespace spl {
 
-// k systems op(A) X(:,c) = B(:,c) with the factors of N; X, B are n x k column-major on the host.
-// Iterative refinement with UMFPACK's defaults and stopping rules, column by column (irstep = 2;
-// umf_solve): stop when the componentwise backward error is below machine epsilon, or when a
-// step does not at least halve it (a step that raises it is undone).  All columns share every
-// pass over the factors.
-// Static pivoting from a solve: the matrix is taken from the object's own device copy (the columns of A are the
-// rows of N->At), not from the caller's Ap / Ai / Ax — a `zi` caller passes the complex matrix there, whose arrays
-// are not those of the embedding this object factors (umfpack_zi.hip).
-static bool factor_static_pivot_of_copy(Numeric *N, hipStream_t s) {
-  if (N->sp_stage != 0 || !N->At || !N->At->rowptr.get() || N->At->nnz <= 0) return false;
-  const size_t n = (size_t)N->n, nnz = (size_t)N->At->nnz;
-  std::vector<int> p(n + 1), i(nnz);
-  std::vector<double> x(nnz);
-  SPL_HIP(hipMemcpyAsync(p.data(), N->At->rowptr.get(), (n + 1) * sizeof(int), hipMemcpyDeviceToHost, s));
-  SPL_HIP(hipMemcpyAsync(i.data(), N->At->colidx.get(), nnz * sizeof(int), hipMemcpyDeviceToHost, s));
-  SPL_HIP(hipMemcpyAsync(x.data(), N->At->val.get(), nnz * sizeof(double), hipMemcpyDeviceToHost, s));
-  SPL_HIP(hipStreamSynchronize(s));
-  return factor_static_pivot(N, p.data(), i.data(), x.data(), s);
-}
-
 // Flexible GMRES on op x = b, right-preconditioned by the factors held (the solves `factor_solve` runs), from the
 // iterate in x: what static pivoting needs when plain refinement stalls.  The factors of B = Dr P A Dc without
 // interchanges are exact for a nearby matrix; on matrices with values over many orders of magnitude that matrix is
@@ -1454,240 +1511,181 @@ static void gmres_polish(Numeric *N, int sys, const Matrix *op, const double *b,
   SPL_HIP(hipStreamSynchronize(s));
 }
 
-// device_io: X and B are device pointers (spl_umfpack_*_solve_many_dev), else host
-int solve_columns(Numeric *N, int sys, int k, double *X, const double *B, const int *Ap, const int *Ai,
-                  const double *Ax, bool device_io, double *Info, bool caller_holds_turn) {
+namespace {
+
+// One solve_columns call: its work vectors, the counters of its report and the steps of its loop.
+struct SolveCall {
+  Numeric *const N;
+  const int sys, k;
+  const hipStream_t s;
+  PhaseTimer &timer;
   const int n = N->n;
-  if (N->broken) return UMFPACK_ERROR_invalid_Numeric_object;  // a failed refactorisation left no factors
-  return umf_guarded([&] {
-    DeviceGuard g(N->device);
-    // the calling thread's default stream: ordered after and before work on the legacy default stream (the caller's
-    // torch kernels, this library's other entry points) like the legacy stream itself, but factorisations and solves
-    // issued by different host threads — the contour points of a FEAST iteration — overlap on the device
-    hipStream_t s = hipStreamPerThread;
-    if (n == 0 || k == 0) return N->singular ? UMFPACK_WARNING_singular_matrix : UMFPACK_OK;
-    const bool timing = getenv("SPL_MF_TIMING") != nullptr;  // phase times on stderr (diagnostic)
-    auto t_last = std::chrono::steady_clock::now();
-    auto lap = [&](const char *what) {
-      if (!timing) return;
-      (void)hipStreamSynchronize(s);
-      const auto now = std::chrono::steady_clock::now();
-      fprintf(stderr, "[solve] %-28s %8.2f ms\n", what, std::chrono::duration<double, std::milli>(now - t_last).count());
-      t_last = now;
-    };
-    const size_t stride = (size_t)n;
-    const int kalloc = k == 1 ? 1 : (k + kSolveGroup - 1) / kSolveGroup * kSolveGroup;
-    const size_t total = stride * (size_t)kalloc, used = stride * (size_t)k;
-    const dim3 grid((unsigned)((n + 255) / 256), (unsigned)k);
-    // one allocation for all work vectors of the call (each hipMalloc / hipFree is a device round trip)
-    struct Span {
-      double *p;
-      double *get() const { return p; }
-    };
-    DBuf<double> slab(9 * total + (size_t)k);
-    Span db{slab.get()}, dx{slab.get() + total}, dwork{slab.get() + 2 * total}, dr{slab.get() + 3 * total},
-        dd{slab.get() + 4 * total}, dax{slab.get() + 5 * total}, dabs{slab.get() + 6 * total},
-        dxn{slab.get() + 7 * total}, drn{slab.get() + 8 * total}, domega{slab.get() + 9 * total};
-    for (const Span *buf : {&db, &dx, &dwork, &dr, &dd, &dxn, &drn})
-      if (kalloc > k) SPL_HIP(hipMemsetAsync(buf->get() + used, 0, (total - used) * sizeof(double), s));
-    SPL_HIP(hipMemcpyAsync(db.get(), B, used * sizeof(double),
-                           device_io ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, s));
-    // speculative factors may be replaced below: solves on such an object take turns
-    std::unique_lock<std::mutex> turn(N->mu, std::defer_lock);
-    if (N->speculative && !caller_holds_turn) turn.lock();
-    std::vector<double> omega((size_t)k, 0.0), on((size_t)k, 0.0);
-    bool polished = false;
-    int walks = 0, ir_taken = 0, ir_attempted = 0;
-    double delivered = 0.0;
-    lap("buffers, upload of b");
-  again:
-    factor_solve(N, sys, db.get(), dx.get(), dwork.get(), k, stride, s);
-    ++walks;
-    lap("solve with the factors");
-    if (!N->singular) {
-      const Matrix *op = sys == UMFPACK_A ? N->A : N->At;
-      const char *rs = getenv("SPL_LU_RESIDUAL");
-      const bool plain_residual = op->vw != 1 || (rs && rs[0] == 'p');
-      auto backward_error = [&](const double *x, double *r, std::vector<double> &out) {
-        if (!plain_residual) {
-          SPL_HIP(hipMemsetAsync(domega.get(), 0, (size_t)k * sizeof(double), s));
-          if (op->nnz <= 12 * (int64_t)n)  // short rows
-            hipLaunchKernelGGL(residual_dd_kernel<2>, dim3((unsigned)(((size_t)n * 2 + 255) / 256), (unsigned)k), dim3(256), 0, s,
-                               n, op->rowptr64.get(), op->colidx.get(), op->val.get(), x, db.get(), r, domega.get(), stride);
-          else
-            hipLaunchKernelGGL(residual_dd_kernel<8>, dim3((unsigned)(((size_t)n * 8 + 255) / 256), (unsigned)k), dim3(256), 0, s,
-                               n, op->rowptr64.get(), op->colidx.get(), op->val.get(), x, db.get(), r, domega.get(), stride);
-          SPL_HIP(hipMemcpyAsync(out.data(), domega.get(), (size_t)k * sizeof(double), hipMemcpyDeviceToHost, s));
-          SPL_HIP(hipStreamSynchronize(s));
-          return;
-        }
-        for (int c = 0; c < k; ++c) {
-          int st = launch_spmv(op, x + (size_t)c * stride, dax.get() + (size_t)c * stride, 0, s);
-          if (st != SPL_OK) throw DeviceError{st};
-        }
-        hipLaunchKernelGGL(abs_spmv_kernel, dim3((unsigned)(((size_t)n * 8 + 255) / 256), (unsigned)k), dim3(256), 0,
-                           s, n, op->rowptr64.get(), op->colidx.get(), op->val.get(), x, dabs.get(), stride);
-        SPL_HIP(hipMemsetAsync(domega.get(), 0, (size_t)k * sizeof(double), s));
-        hipLaunchKernelGGL(residual_kernel, grid, dim3(256), 0, s, n, db.get(), dax.get(), dabs.get(), r,
-                           domega.get(), stride);
-        SPL_HIP(hipMemcpyAsync(out.data(), domega.get(), (size_t)k * sizeof(double), hipMemcpyDeviceToHost, s));
-        SPL_HIP(hipStreamSynchronize(s));
-      };
-      const double eps = 2.220446049250313e-16;
-      backward_error(dx.get(), dr.get(), omega);
-      lap("residual, backward error");
-      std::vector<char> active((size_t)k);
-      int nactive = 0;
-      for (int c = 0; c < k; ++c) nactive += (active[(size_t)c] = omega[(size_t)c] >= eps);
-      // UMFPACK's default is two steps.  Factors kept as a speculation (no interchanges, no
-      // diagonal dominance) may take more while each step still halves the backward error: static
-      // pivoting with refinement, before the factors are given up for pivoted ones below.
-      const int max_steps = N->speculative ? 10 : 2;
-      const double stall = 0.5;
-      for (int it = 0; it < max_steps && nactive > 0; ++it) {
-        SPL_HIP(hipMemcpyAsync(dxn.get(), dx.get(), used * sizeof(double), hipMemcpyDeviceToDevice, s));
-        ++walks;
-        ++ir_attempted;
-        if (nactive == k) {
-          factor_solve(N, sys, dr.get(), dd.get(), dwork.get(), k, stride, s);
-          hipLaunchKernelGGL(add_kernel, dim3((unsigned)((used + 255) / 256)), dim3(256), 0, s, used, dxn.get(),
-                             dd.get());
-        } else {
-          // Only the columns still being refined go through the factors, side by side: a walk over the tree (or the
-          // band) costs the same for a group of kSolveGroup columns whatever they hold, and the columns of a batch
-          // rarely all need the second step (drn is free until the backward error below).
-          int ka = 0;
-          for (int c = 0; c < k; ++c)
-            if (active[(size_t)c])
-              SPL_HIP(hipMemcpyAsync(drn.get() + (size_t)ka++ * stride, dr.get() + (size_t)c * stride,
-                                     stride * sizeof(double), hipMemcpyDeviceToDevice, s));
-          const int ka_alloc = ka == 1 ? 1 : (ka + kSolveGroup - 1) / kSolveGroup * kSolveGroup;
-          if (ka_alloc > ka) {
-            SPL_HIP(hipMemsetAsync(drn.get() + (size_t)ka * stride, 0, (size_t)(ka_alloc - ka) * stride * sizeof(double), s));
-            SPL_HIP(hipMemsetAsync(dwork.get() + (size_t)ka * stride, 0, (size_t)(ka_alloc - ka) * stride * sizeof(double), s));
-          }
-          factor_solve(N, sys, drn.get(), dd.get(), dwork.get(), ka, stride, s);
-          ka = 0;
-          for (int c = 0; c < k; ++c)
-            if (active[(size_t)c])
-              hipLaunchKernelGGL(add_kernel, dim3((unsigned)((stride + 255) / 256)), dim3(256), 0, s, stride,
-                                 dxn.get() + (size_t)c * stride, dd.get() + (size_t)ka++ * stride);
-        }
-        backward_error(dxn.get(), drn.get(), on);
-        if (timing) {
-          double lo = 1e300, hi = 0.0, lo2 = 1e300, hi2 = 0.0;
-          for (int c = 0; c < k; ++c)
-            if (active[(size_t)c]) {
-              lo = std::min(lo, omega[(size_t)c]), hi = std::max(hi, omega[(size_t)c]);
-              lo2 = std::min(lo2, on[(size_t)c]), hi2 = std::max(hi2, on[(size_t)c]);
-            }
-          fprintf(stderr, "[solve] columns refined in this step: %d of %d, backward errors %.2e .. %.2e -> %.2e .. %.2e\n",
-                  nactive, k, lo, hi, lo2, hi2);
-        }
-        lap("refinement step");
-        bool kept = false;
-        for (int c = 0; c < k; ++c) kept |= active[(size_t)c] && on[(size_t)c] <= omega[(size_t)c];
-        ir_taken += kept ? 1 : 0;
-        for (int c = 0; c < k; ++c) {
-          if (!active[(size_t)c]) continue;
-          const double o_new = on[(size_t)c], o_old = omega[(size_t)c];
-          if (!(o_new <= o_old)) {  // worse (or NaN): keep the previous iterate of this column
-            active[(size_t)c] = 0;
-            --nactive;
-            continue;
-          }
-          const size_t off = (size_t)c * stride;
-          SPL_HIP(hipMemcpyAsync(dx.get() + off, dxn.get() + off, stride * sizeof(double), hipMemcpyDeviceToDevice, s));
-          SPL_HIP(hipMemcpyAsync(dr.get() + off, drn.get() + off, stride * sizeof(double), hipMemcpyDeviceToDevice, s));
-          omega[(size_t)c] = o_new;
-          // UMFPACK's rule: a step that does not halve the backward error ends the refinement (letting the factors of
-          // static pivoting go on while a step still gained a tenth changed nothing: their refinement stops because a
-          // step makes things WORSE, at 1e-10 .. 5e-10 on matrices with values over six orders of magnitude — what
-          // gets them to rounding level is the Krylov polish below)
-          if (o_new > o_old * stall || o_new < eps) {  // stagnated, or converged
-            active[(size_t)c] = 0;
-            --nactive;
-          }
-        }
-        // columns that are done must not move any more: their residual no longer drives a step
-        for (int c = 0; c < k; ++c)
-          if (!active[(size_t)c])
-            SPL_HIP(hipMemsetAsync(dr.get() + (size_t)c * stride, 0, stride * sizeof(double), s));
+  const size_t stride = (size_t)n;
+  const int kalloc = k == 1 ? 1 : (k + kSolveGroup - 1) / kSolveGroup * kSolveGroup;
+  const size_t total = stride * (size_t)kalloc, used = stride * (size_t)k;
+  // one allocation for all work vectors of the call (each hipMalloc / hipFree is a device round trip)
+  DBuf<double> slab{9 * total + (size_t)k};
+  double *const db = slab.get(), *const dx = db + total, *const dwork = db + 2 * total, *const dr = db + 3 * total,
+                *const dd = db + 4 * total, *const dax = db + 5 * total, *const dabs = db + 6 * total,
+                *const dxn = db + 7 * total, *const drn = db + 8 * total, *const domega = db + 9 * total;
+  const Matrix *const op = sys == UMFPACK_A ? N->A : N->At;
+  bool plain_residual = false;
+  std::vector<double> omega = std::vector<double>((size_t)k, 0.0), on = omega;
+  int walks = 0, ir_taken = 0, ir_attempted = 0;
+
+  // b into db (device_io: B is a device pointer, else host); the padding columns of a group are zero
+  void upload(const double *B, bool device_io) {
+    for (double *buf : {db, dx, dwork, dr, dd, dxn, drn})
+      if (kalloc > k) SPL_HIP(hipMemsetAsync(buf + used, 0, (total - used) * sizeof(double), s));
+    SPL_HIP(hipMemcpyAsync(db, B, used * sizeof(double), device_io ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, s));
+    plain_residual = op->vw != 1 || env_is("SPL_LU_RESIDUAL", 'p');
+  }
+
+  // r <- b - op x and out[c] <- the componentwise backward error of column c, for all k columns
+  void backward_error(const double *x, double *r, std::vector<double> &out) {
+    if (!plain_residual) {
+      SPL_HIP(hipMemsetAsync(domega, 0, (size_t)k * sizeof(double), s));
+      const bool short_rows = op->nnz <= 12 * (int64_t)n;
+      const size_t lanes = short_rows ? 2 : 8;  // per row
+      hipLaunchKernelGGL((short_rows ? residual_dd_kernel<2> : residual_dd_kernel<8>),
+                         dim3((unsigned)(((size_t)n * lanes + 255) / 256), (unsigned)k), dim3(256), 0, s, n, op->rowptr64.get(),
+                         op->colidx.get(), op->val.get(), x, db, r, domega, stride);
+    } else {
+      for (int c = 0; c < k; ++c) {
+        int st = launch_spmv(op, x + (size_t)c * stride, dax + (size_t)c * stride, 0, s);
+        if (st != SPL_OK) throw DeviceError{st};
       }
-      // no-interchange factors of a matrix without diagonal dominance: accepted only if every
-      // refined solution is backward stable to rounding level, as pivoted factors would make it
-      double worst = 0.0;
-      for (int c = 0; c < k; ++c) worst = (omega[(size_t)c] <= worst) ? worst : omega[(size_t)c];  // NaN -> worst
-      delivered = worst;
-      if ((turn.owns_lock() || caller_holds_turn) && N->speculative && !(worst <= 1e-13)) {
-        // first the static-pivoting stage (stays on the tree, still checked by this very loop), then, if that
-        // fails too, the band factorisation with partial pivoting
-        // a symmetric matrix whose L D L^T speculation failed: the same tree once more as LU with threshold pivoting
-        // inside the diagonal blocks (no host work), then the static-pivoting stage
-        if (N->mfact && N->mf_sym && !N->mf_piv && !N->block_pivot_retry && N->sp_stage == 0 && N->tree) {
-          const char *bp = getenv("SPL_LU_BLOCK_PIVOT");
-          if (!(bp && bp[0] == '0')) {
-            N->block_pivot_retry = 1;
-            try {
-              factor_multifrontal(N, s);
-            } catch (const DeviceError &) {
-              N->broken = 1;
-              throw;
-            }
-            if (!N->singular) goto again;
-          }
-        }
-        if (factor_static_pivot_of_copy(N, s)) goto again;
-        if (N->sp_stage == 1 && !polished) {
-          // the factors held ARE those of static pivoting and refinement has stalled: a Krylov polish preconditioned
-          // by them (gmres_polish), column by column, then the same test again
-          polished = true;
-          const char *pe = getenv("SPL_LU_GMRES");
-          if (!(pe && pe[0] == '0')) {
-            for (int c = 0; c < k; ++c)
-              if (!(omega[(size_t)c] <= 1e-13))
-                for (int cycle = 0; cycle < 3; ++cycle) {
-                  // the polish writes the column in place: keep the iterate it started from, and put it back when the
-                  // cycle made the backward error worse — omega[c] is then the error of what is delivered
-                  const size_t off = (size_t)c * stride;
-                  SPL_HIP(hipMemcpyAsync(dxn.get() + off, dx.get() + off, stride * sizeof(double), hipMemcpyDeviceToDevice, s));
-                  gmres_polish(N, sys, op, db.get() + off, dx.get() + off, dwork.get(), 20, s);
-                  backward_error(dx.get(), dr.get(), on);
-                  const bool better = on[(size_t)c] < 0.5 * omega[(size_t)c];
-                  if (on[(size_t)c] <= omega[(size_t)c]) omega[(size_t)c] = on[(size_t)c];
-                  else SPL_HIP(hipMemcpyAsync(dx.get() + off, dxn.get() + off, stride * sizeof(double), hipMemcpyDeviceToDevice, s));
-                  if (timing) fprintf(stderr, "[solve] FGMRES cycle %d, column %d: backward error %.2e\n", cycle, c, on[(size_t)c]);
-                  if (omega[(size_t)c] <= 1e-13 || !better) break;
-                }
-            worst = 0.0;
-            for (int c = 0; c < k; ++c) worst = (omega[(size_t)c] <= worst) ? worst : omega[(size_t)c];
-            delivered = worst;
-            lap("FGMRES polish");
-            if (worst <= 1e-13) goto deliver;
-          }
-        }
-        try {
-          factor_band(N, false, s);
-        } catch (const DeviceError &e) {
-          // The band with partial pivoting does not fit (factor_band decides that before it releases anything: the
-          // factors held are intact).  Nothing better can be built on this device; the refined solution at hand
-          // is returned when its componentwise backward error is at the level threshold pivoting itself reaches on
-          // such matrices (tools/fuzz_lu_scale.py, family perm2d: static pivoting + refinement 1e-12 .. 1e-10,
-          // SuperLU 3e-11), as UMFPACK returns whatever its pivoting achieved; anything worse stays an error.
-          if (e.status != SPL_ERROR_out_of_memory || !(worst <= 1e-9)) throw;
-          if (getenv("SPL_MF_TIMING")) fprintf(stderr, "[solve] pivoted band does not fit: keeping the factors held, backward error %.2e\n", worst);
-          goto deliver;
-        }
-        N->speculative = 0;  // only now may other threads use the object without taking turns
-        goto again;
-      }
+      hipLaunchKernelGGL(abs_spmv_kernel, dim3((unsigned)(((size_t)n * 8 + 255) / 256), (unsigned)k), dim3(256), 0,
+                         s, n, op->rowptr64.get(), op->colidx.get(), op->val.get(), x, dabs, stride);
+      SPL_HIP(hipMemsetAsync(domega, 0, (size_t)k * sizeof(double), s));
+      hipLaunchKernelGGL(residual_kernel, dim3((unsigned)((n + 255) / 256), (unsigned)k), dim3(256), 0, s, n, db, dax, dabs, r,
+                         domega, stride);
     }
-  deliver:
-    SPL_HIP(hipMemcpyAsync(X, dx.get(), used * sizeof(double),
-                           device_io ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, s));
+    SPL_HIP(hipMemcpyAsync(out.data(), domega, (size_t)k * sizeof(double), hipMemcpyDeviceToHost, s));
+    SPL_HIP(hipStreamSynchronize(s));
+  }
+
+  // the largest backward error among the columns as they stand (NaN counts as the worst)
+  double worst() const {
+    double w = 0.0;
+    for (int c = 0; c < k; ++c) w = (omega[(size_t)c] <= w) ? w : omega[(size_t)c];
+    return w;
+  }
+
+  // Iterative refinement of dx with UMFPACK's stopping rules, column by column (umf_solve): stop when the componentwise
+  // backward error is below machine epsilon, or when a step does not at least halve it (a step that raises it is
+  // undone).  All columns share every pass over the factors.  Returns worst().
+  double refine() {
+    const double eps = 2.220446049250313e-16;
+    backward_error(dx, dr, omega);
+    timer.lap("residual, backward error");
+    std::vector<char> active((size_t)k);
+    int nactive = 0;
+    for (int c = 0; c < k; ++c) nactive += (active[(size_t)c] = omega[(size_t)c] >= eps);
+    // UMFPACK's default is two steps.  Factors kept as a speculation (no interchanges, no
+    // diagonal dominance) may take more while each step still halves the backward error: static
+    // pivoting with refinement, before the factors are given up for pivoted ones.
+    const int max_steps = N->speculative ? 10 : 2;
+    const double stall = 0.5;
+    for (int it = 0; it < max_steps && nactive > 0; ++it) {
+      SPL_HIP(hipMemcpyAsync(dxn, dx, used * sizeof(double), hipMemcpyDeviceToDevice, s));
+      ++walks;
+      ++ir_attempted;
+      if (nactive == k) {
+        factor_solve(N, sys, dr, dd, dwork, k, stride, s);
+        hipLaunchKernelGGL(add_kernel, dim3((unsigned)((used + 255) / 256)), dim3(256), 0, s, used, dxn, dd);
+      } else {
+        // Only the columns still being refined go through the factors, side by side: a walk over the tree (or the
+        // band) costs the same for a group of kSolveGroup columns whatever they hold, and the columns of a batch
+        // rarely all need the second step (drn is free until the backward error below).
+        int ka = 0;
+        for (int c = 0; c < k; ++c)
+          if (active[(size_t)c])
+            SPL_HIP(hipMemcpyAsync(drn + (size_t)ka++ * stride, dr + (size_t)c * stride, stride * sizeof(double),
+                                   hipMemcpyDeviceToDevice, s));
+        const int ka_alloc = ka == 1 ? 1 : (ka + kSolveGroup - 1) / kSolveGroup * kSolveGroup;
+        if (ka_alloc > ka) {
+          SPL_HIP(hipMemsetAsync(drn + (size_t)ka * stride, 0, (size_t)(ka_alloc - ka) * stride * sizeof(double), s));
+          SPL_HIP(hipMemsetAsync(dwork + (size_t)ka * stride, 0, (size_t)(ka_alloc - ka) * stride * sizeof(double), s));
+        }
+        factor_solve(N, sys, drn, dd, dwork, ka, stride, s);
+        ka = 0;
+        for (int c = 0; c < k; ++c)
+          if (active[(size_t)c])
+            hipLaunchKernelGGL(add_kernel, dim3((unsigned)((stride + 255) / 256)), dim3(256), 0, s, stride,
+                               dxn + (size_t)c * stride, dd + (size_t)ka++ * stride);
+      }
+      backward_error(dxn, drn, on);
+      if (timer.on) {
+        double lo = 1e300, hi = 0.0, lo2 = 1e300, hi2 = 0.0;
+        for (int c = 0; c < k; ++c)
+          if (active[(size_t)c]) {
+            lo = std::min(lo, omega[(size_t)c]), hi = std::max(hi, omega[(size_t)c]);
+            lo2 = std::min(lo2, on[(size_t)c]), hi2 = std::max(hi2, on[(size_t)c]);
+          }
+        fprintf(stderr, "[solve] columns refined in this step: %d of %d, backward errors %.2e .. %.2e -> %.2e .. %.2e\n",
+                nactive, k, lo, hi, lo2, hi2);
+      }
+      timer.lap("refinement step");
+      bool kept = false;
+      for (int c = 0; c < k; ++c) kept |= active[(size_t)c] && on[(size_t)c] <= omega[(size_t)c];
+      ir_taken += kept ? 1 : 0;
+      for (int c = 0; c < k; ++c) {
+        if (!active[(size_t)c]) continue;
+        const double o_new = on[(size_t)c], o_old = omega[(size_t)c];
+        if (!(o_new <= o_old)) {  // worse (or NaN): keep the previous iterate of this column
+          active[(size_t)c] = 0;
+          --nactive;
+          continue;
+        }
+        const size_t off = (size_t)c * stride;
+        SPL_HIP(hipMemcpyAsync(dx + off, dxn + off, stride * sizeof(double), hipMemcpyDeviceToDevice, s));
+        SPL_HIP(hipMemcpyAsync(dr + off, drn + off, stride * sizeof(double), hipMemcpyDeviceToDevice, s));
+        omega[(size_t)c] = o_new;
+        // UMFPACK's rule: a step that does not halve the backward error ends the refinement (letting the factors of
+        // static pivoting go on while a step still gained a tenth changed nothing: their refinement stops because a
+        // step makes things WORSE, at 1e-10 .. 5e-10 on matrices with values over six orders of magnitude — what
+        // gets them to rounding level is the Krylov polish)
+        if (o_new > o_old * stall || o_new < eps) {  // stagnated, or converged
+          active[(size_t)c] = 0;
+          --nactive;
+        }
+      }
+      // columns that are done must not move any more: their residual no longer drives a step
+      for (int c = 0; c < k; ++c)
+        if (!active[(size_t)c]) SPL_HIP(hipMemsetAsync(dr + (size_t)c * stride, 0, stride * sizeof(double), s));
+    }
+    return worst();
+  }
+
+  // Refinement with the factors of static pivoting has stalled: a Krylov polish preconditioned by them (gmres_polish),
+  // column by column.  Returns worst().
+  double polish() {
+    for (int c = 0; c < k; ++c)
+      if (!(omega[(size_t)c] <= 1e-13))
+        for (int cycle = 0; cycle < 3; ++cycle) {
+          // the polish writes the column in place: keep the iterate it started from, and put it back when the
+          // cycle made the backward error worse — omega[c] is then the error of what is delivered
+          const size_t off = (size_t)c * stride;
+          SPL_HIP(hipMemcpyAsync(dxn + off, dx + off, stride * sizeof(double), hipMemcpyDeviceToDevice, s));
+          gmres_polish(N, sys, op, db + off, dx + off, dwork, 20, s);
+          backward_error(dx, dr, on);
+          const bool better = on[(size_t)c] < 0.5 * omega[(size_t)c];
+          if (on[(size_t)c] <= omega[(size_t)c]) omega[(size_t)c] = on[(size_t)c];
+          else SPL_HIP(hipMemcpyAsync(dx + off, dxn + off, stride * sizeof(double), hipMemcpyDeviceToDevice, s));
+          if (timer.on) fprintf(stderr, "[solve] FGMRES cycle %d, column %d: backward error %.2e\n", cycle, c, on[(size_t)c]);
+          if (omega[(size_t)c] <= 1e-13 || !better) break;
+        }
+    timer.lap("FGMRES polish");
+    return worst();
+  }
+
+  // dx to the caller, the report of the call to the object and to Info
+  int deliver(double *X, bool device_io, double delivered, double *Info) {
+    SPL_HIP(hipMemcpyAsync(X, dx, used * sizeof(double), device_io ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, s));
     SPL_HIP(hipStreamSynchronize(s));
     SPL_HIP(hipGetLastError());
-    lap("download of x");
+    timer.lap("download of x");
     N->last_walks = walks;
     N->last_ir_taken = ir_taken;
     N->last_ir_attempted = ir_attempted;
@@ -1700,6 +1698,63 @@ int solve_columns(Numeric *N, int sys, int k, double *X, const double *B, const 
       Info[83] = 0.0;        // the denominator of a row with entries never vanishes unless its whole numerator does)
     }
     return N->singular ? UMFPACK_WARNING_singular_matrix : UMFPACK_OK;
+  }
+};
+
+}  // namespace
+
+// k systems op(A) X(:,c) = B(:,c) with the factors of N; X, B are n x k column-major, device pointers when device_io
+// (spl_umfpack_*_solve_many_dev), else on the host.  Solve and refine (UMFPACK's defaults: irstep = 2); speculative
+// factors are accepted only if every refined column is backward stable to rounding level, as pivoted factors would
+// make it — otherwise the ladder builds the next factors and the call solves again, until it accepts or nothing is left.
+int solve_columns(Numeric *N, int sys, int k, double *X, const double *B, const int *Ap, const int *Ai,
+                  const double *Ax, bool device_io, double *Info, bool caller_holds_turn) {
+  if (N->broken) return UMFPACK_ERROR_invalid_Numeric_object;  // a failed refactorisation left no factors
+  return umf_guarded([&] {
+    DeviceGuard g(N->device);
+    // the calling thread's default stream: ordered after and before work on the legacy default stream (the caller's
+    // torch kernels, this library's other entry points) like the legacy stream itself, but factorisations and solves
+    // issued by different host threads — the contour points of a FEAST iteration — overlap on the device
+    hipStream_t s = hipStreamPerThread;
+    if (N->n == 0 || k == 0) return N->singular ? UMFPACK_WARNING_singular_matrix : UMFPACK_OK;
+    PhaseTimer timer{"[solve] %-28s %8.2f ms\n", s};
+    SolveCall call{N, sys, k, s, timer};
+    call.upload(B, device_io);
+    // speculative factors may be replaced below: solves on such an object take turns
+    std::unique_lock<std::mutex> turn(N->mu, std::defer_lock);
+    if (N->speculative && !caller_holds_turn) turn.lock();
+    bool polished = false;
+    double delivered = 0.0;
+    timer.lap("buffers, upload of b");
+    for (;;) {
+      factor_solve(N, sys, call.db, call.dx, call.dwork, k, call.stride, s);
+      ++call.walks;
+      timer.lap("solve with the factors");
+      if (N->singular) break;
+      double worst = delivered = call.refine();
+      const bool checked = (turn.owns_lock() || caller_holds_turn) && N->speculative;
+      if (!checked || worst <= 1e-13) break;  // accepted
+      Rung next = next_factors(N, LadderCall{false, nullptr, nullptr, nullptr, polished}, s);
+      if (next == Rung::polish) {
+        polished = true;
+        if (!env_is("SPL_LU_GMRES", '0')) {
+          worst = delivered = call.polish();
+          if (worst <= 1e-13) break;
+        }
+        next = next_factors(N, LadderCall{false, nullptr, nullptr, nullptr, polished}, s);
+      }
+      if (next == Rung::none) {
+        // The band with partial pivoting does not fit (factor_band decides that before it releases anything: the
+        // factors held are intact).  Nothing better can be built on this device; the refined solution at hand
+        // is returned when its componentwise backward error is at the level threshold pivoting itself reaches on
+        // such matrices (tools/fuzz_lu_scale.py, family perm2d: static pivoting + refinement 1e-12 .. 1e-10,
+        // SuperLU 3e-11), as UMFPACK returns whatever its pivoting achieved; anything worse stays an error.
+        if (!(worst <= 1e-9)) throw DeviceError{SPL_ERROR_out_of_memory};
+        if (timer.on) fprintf(stderr, "[solve] pivoted band does not fit: keeping the factors held, backward error %.2e\n", worst);
+        break;
+      }
+    }
+    return call.deliver(X, device_io, delivered, Info);
   });
 }
 }  // namespace spl
@@ -1760,9 +1815,12 @@ int spl_umfpack_dimension(void *NumericIn) {
 int spl_umfpack_path(void *NumericIn) {
   Numeric *N = as_numeric(NumericIn);
   if (!N) return -1;
-  if (N->mfact && N->sp_stage == 1) return 5;
-  if (N->mfact) return N->speculative ? 4 : 3;
-  return N->nopiv ? (N->speculative ? 2 : 1) : 0;
+  switch (N->held) {
+    case Held::tree_static: return 5;
+    case Held::tree: return N->speculative ? 4 : 3;
+    case Held::band_blocked: return N->speculative ? 2 : 1;
+    default: return 0;  // band_pivoted; none: a rectangular matrix holds no factors
+  }
 }
 
 int spl_umfpack_stats(void *NumericIn, double out[8]) {
@@ -1771,16 +1829,13 @@ int spl_umfpack_stats(void *NumericIn, double out[8]) {
   for (int i = 0; i < 8; ++i) out[i] = 0.0;
   out[0] = (double)spl_umfpack_path(NumericIn);
   out[1] = (double)N->n;
-  if (N->mfact && N->zfront && N->ztree) {
-    out[4] = (double)mf_device_bytes(*N->ztree, 2);
-    out[5] = 4.0 * (N->mf_sym ? 0.5 * N->ztree->flops : N->ztree->flops);  // a complex multiply-add is four real ones
-    out[6] = (double)N->ztree->nfronts;
-    out[7] = 1.0 + (N->mf_piv ? 2.0 : 0.0);  // bit 0: native complex fronts; bit 1: threshold pivoting inside the diagonal blocks
-  } else if (N->mfact) {
-    out[7] = N->mf_piv ? 2.0 : 0.0;
-    out[4] = (double)mf_device_bytes(*N->tree, 1);
-    out[5] = N->mf_sym ? 0.5 * N->tree->flops : N->tree->flops;  // L D L^T on the same fronts: about half the flops of LU
-    out[6] = (double)N->tree->nfronts;
+  if (const mf::Tree *T = held_tree(N)) {
+    out[4] = (double)mf_device_bytes(*T, N->kind.complex_fronts ? 2 : 1);
+    // L D L^T on the same fronts: about half the flops of LU; a complex multiply-add is four real ones
+    out[5] = (N->kind.complex_fronts ? 4.0 : 1.0) * (N->kind.ldlt ? 0.5 * T->flops : T->flops);
+    out[6] = (double)T->nfronts;
+    // bit 0: native complex fronts; bit 1: threshold pivoting inside the diagonal blocks
+    out[7] = (N->kind.complex_fronts ? 1.0 : 0.0) + (N->kind.block_pivoting ? 2.0 : 0.0);
   } else {
     out[2] = (double)N->kl;
     out[3] = (double)N->ku;
@@ -1803,18 +1858,18 @@ int spl_umfpack_solve_report(void *NumericIn, double out[8]) {
   // pivot block, L21, U12; complex fronts: two planes) —, or the band; 8 bytes each, no index arrays (dense panels);
   // plus the right-hand side in and the solution out
   double entries = 0.0;
-  const mf::Tree *T = N->mfact ? ((N->zfront && N->ztree) ? N->ztree.get() : N->tree.get()) : nullptr;
+  const mf::Tree *T = held_tree(N);
   if (T) {
     for (int f = 0; f < T->nfronts; ++f) {
       const double np = T->np[(size_t)f], nb = T->nb[(size_t)f];
       entries += np * np + 2.0 * np * nb;
     }
-    if (N->zfront && N->ztree) entries *= 2.0;
+    if (N->kind.complex_fronts) entries *= 2.0;
   } else {
     entries = (double)N->n * ((double)N->kl + (double)N->ku + 1.0);
   }
   out[4] = 8.0 * entries + 16.0 * (double)N->n;
-  if (N->mfact) mf_chain_info(N->mfact, out + 5);  // chain matrices: bytes, milliseconds to build, pivots per block
+  if (T) mf_chain_info(N->mfact, out + 5);  // chain matrices: bytes, milliseconds to build, pivots per block
   return 0;
 }
 
@@ -1870,14 +1925,6 @@ void host_product(const std::vector<double> &x, double &m, int64_t &e) {
   e = pm.empty() ? 1 : pe[0];
 }
 
-template <typename T>
-std::vector<T> download(const T *d, size_t n, hipStream_t s) {
-  std::vector<T> h(n);
-  if (n) SPL_HIP(hipMemcpyAsync(h.data(), d, n * sizeof(T), hipMemcpyDeviceToHost, s));
-  SPL_HIP(hipStreamSynchronize(s));
-  return h;
-}
-
 // a fixed right-hand side for the acceptance check of speculative factors: values in [-1, 1) from a hash of the index
 std::vector<double> check_rhs(int n) {
   std::vector<double> b((size_t)n);
@@ -1900,10 +1947,12 @@ DetValue factor_determinant(Numeric *N, hipStream_t s) {
   double sm = 0.5;          // prod of the scales = sm 2^se
   int64_t se = 1;
   DetResult r{};
-  if (N->mfact) {
+  switch (N->held) {
+  case Held::tree:
+  case Held::tree_static: {
     const MfPivots P = mf_pivots(N->mfact);
     r = det_pivots_tree(n, P.arena, P.front_of, P.p0, P.ldp, P.poff, s);
-    if (N->mf_piv && N->sp_stage != 1) {  // (the factors of static pivoting are built without interchanges)
+    if (N->kind.block_pivoting) {
       std::vector<int64_t> slot;
       std::vector<int> jb;
       const mf::Tree &T = *P.tree;
@@ -1914,7 +1963,7 @@ DetValue factor_determinant(Numeric *N, hipStream_t s) {
         }
       odd ^= block_pivot_parity(P.invs, slot, jb, s);
     }
-    if (N->sp_stage == 1) {
+    if (N->held == Held::tree_static) {
       // sp_idx[0][k] = row of A that became row pnd[k] of B, sp_idx[1] = B's inverse ordering (pnd^-1): the row
       // permutation of B = Dr P A Dc is their composition, so its parity is the sum of theirs
       odd ^= perm_parity(download(N->sp_idx[0].get(), (size_t)n, s));
@@ -1925,12 +1974,18 @@ DetValue factor_determinant(Numeric *N, hipStream_t s) {
       scales.insert(scales.end(), dr.begin(), dr.end());
       host_product(scales, sm, se);
     }
-  } else if (N->nopiv) {
+    break;
+  }
+  case Held::band_blocked:
     r = det_pivots_strided(n, N->AB.get() + N->ku, N->ldab, s);  // Band: A(j, j) = AB[ku + j ldab]
-  } else {
+    break;
+  case Held::band_pivoted: {
     r = det_pivots_strided(n, N->AB.get() + N->kl + N->ku, N->ldab, s);  // LAPACK band LU: U(j, j) = AB[kl + ku + j ldab]
     const std::vector<int> ipiv = download(N->ipiv.get(), (size_t)n, s);
     for (int j = 0; j < n; ++j) odd ^= ipiv[(size_t)j] != j ? 1 : 0;
+    break;
+  }
+  case Held::none: break;  // (a broken object: determinant_of has refused it)
   }
   v.neg = r.neg;
   v.zero = r.zero;
@@ -1961,23 +2016,17 @@ int determinant_of(void *NumericIn, DetValue &v, bool *congruence) {
     if (N->speculative && !N->det_checked && !N->singular && N->n > 0) {
       // factors nobody has accepted yet: the check of a solve, with a fixed right-hand side; it may replace them through
       // the fallbacks (block pivoting retry, static pivoting, band with partial pivoting)
-      // (what spl_umfpack_solve_report describes stays the caller's last solve: the check is not one)
-      const int walks = N->last_walks, ir_taken = N->last_ir_taken, ir_attempted = N->last_ir_attempted;
-      const double omega = N->last_omega;
+      KeepSolveReport keep{N};  // the check is not the caller's solve
       const std::vector<double> b = check_rhs(N->n);
       std::vector<double> x((size_t)N->n);
       const int st = solve_columns(N, UMFPACK_A, 1, x.data(), b.data(), nullptr, nullptr, nullptr, false, nullptr, true);
-      N->last_walks = walks;
-      N->last_ir_taken = ir_taken;
-      N->last_ir_attempted = ir_attempted;
-      N->last_omega = omega;
       if (st < 0) return st;
       N->det_checked = 1;
     }
     if (N->broken) return UMFPACK_ERROR_invalid_Numeric_object;
     if (congruence) {
       // a congruence of A: A symmetric, no interchanges, no scaling (paths 1 - 4 without block pivoting)
-      const bool no_interchanges = N->nopiv && N->sp_stage != 1 && !(N->mfact && N->mf_piv);
+      const bool no_interchanges = N->held == Held::band_blocked || (N->held == Held::tree && !N->kind.block_pivoting);
       *congruence = no_interchanges && !N->singular && matrix_is_symmetric(N, s, false);
     }
     if (N->singular) {
@@ -2082,20 +2131,9 @@ int condest_numeric(Numeric *N, int sys, int t, int width, const DeviceSolve &so
       out[0] = out[2] = HUGE_VAL;
       return UMFPACK_WARNING_singular_matrix;
     }
-    // what spl_umfpack_solve_report describes stays the caller's last solve: the estimator's solves are not the caller's
-    struct KeepReport {
-      Numeric *N;
-      int walks = N->last_walks, ir_taken = N->last_ir_taken, ir_attempted = N->last_ir_attempted;
-      double omega = N->last_omega;
-      ~KeepReport() {
-        N->last_walks = walks;
-        N->last_ir_taken = ir_taken;
-        N->last_ir_attempted = ir_attempted;
-        N->last_omega = omega;
-      }
-    } keep{N};
-    // real L D L^T factors: A = A^T, so the transposed solves are solves with A (no transposed chain set is built)
-    const bool sym = width == 1 && !N->embedding && N->mf_sym;
+    KeepSolveReport keep{N};  // the estimator's solves are not the caller's
+    // real L D L^T factors held: A = A^T, so the transposed solves are solves with A (no transposed chain set is built)
+    const bool sym = width == 1 && !N->embedding && N->held == Held::tree && N->kind.ldlt;
     const int sys_y = sym ? UMFPACK_A : sys, sys_z = sym ? UMFPACK_A : UMFPACK_At - sys;
     DBuf<double> dw(witness ? (size_t)N->n : 0);
     CondestResult r;

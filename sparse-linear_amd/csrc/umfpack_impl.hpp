@@ -57,75 +57,106 @@ struct Symbolic {
   bool rectangular = false;
 };
 
+// Which factors a Numeric object holds: the one value every reader switches on (spl_umfpack_path is this value plus
+// `speculative`).  Written by release_factors (none) and by the three factorisations of umfpack.hip, nowhere else.
+//   none          nothing: a rectangular matrix, or between the release of the old factors and the end of a rebuild
+//   band_pivoted  LAPACK band storage AB, partial pivoting recorded in ipiv (RCM ordering)
+//   band_blocked  blocked band factors without interchanges: AB and blkinv (RCM ordering)
+//   tree          multifrontal factors of P A P^T on the nested-dissection tree: mfact (what kind: TreeKind)
+//   tree_static   multifrontal factors of B = Dr P A Dc on B's own tree (static pivoting): mfact, spA / spAt, sp_idx / sp_scale
+enum class Held { none, band_pivoted, band_blocked, tree, tree_static };
+// What the tree factors are (Held::tree; all false for Held::tree_static, whose B is real, unsymmetric and factored
+// without interchanges, and for the band kinds).
+//   complex_fronts  native complex fronts on ztree, else real fronts on tree
+//   ldlt            L D L^T of a symmetric matrix: half the update flops, the transposed system is the system itself
+//   block_pivoting  threshold pivoting inside the diagonal blocks of the fronts was on (never with ldlt)
+struct TreeKind { bool complex_fronts = false, ldlt = false, block_pivoting = false; };
+
 struct Numeric {
   uint32_t magic = kNumMagic;
   int device = 0;
-  int n = 0, kl = 0, ku = 0, ldab = 1;
-  int singular = 0;
+  int n = 0;
+  std::mutex mu;  // the turns of the solves on a speculative object (they may replace the factors)
+
+  // ---- the matrix: set once by the numeric call -------------------------------------------------------------------
   int rectangular = 0;  // 1: of a rectangular matrix (Symbolic::rectangular): no factors, solves return invalid_system
-  int nopiv = 0;  // 1: blocked factorisation without interchanges
-  int mf_sym = 0;  // 1: the multifrontal factors held are those of a symmetric matrix (L D L^T: half the update flops)
-  // Native complex fronts (round 3).  This object holds the real embedding E of a complex matrix (umfpack_zi.hip) for
-  // residuals, refinement and every fallback; with zfront = 1 the multifrontal factors are those of the COMPLEX matrix
-  // on the tree of its own pattern (ztree: half the unknowns, complex fronts in two planes, multifrontal.hip) — a
-  // solve with them is a solve with E (packed complex vectors ARE the real vectors of the embedding), at half the
+  int singular = 0;     // a zero pivot in the factors held (of the structural / numerical rank when rectangular)
+  // 1: diagonally dominant by columns: factors without interchanges are safe.  Otherwise they are a speculation, and the
+  // rows of a pivot block of a front are free to change places (TreeKind::block_pivoting; SPL_LU_BLOCK_PIVOT=0: never).
+  int dominant = 0;
+  // 1: the real embedding E of a complex matrix (umfpack_zi.hip), kept for residuals, refinement and every fallback; its
+  // determinant is |det|^2 of the complex matrix.  pair_swap: rows 2r, 2r+1 of E were swapped; pair_unit: complex
+  // symmetric matrices, the unit-modulus u_r (re, im) of the congruence D A D.
+  int embedding = 0;
+  std::vector<char> pair_swap;
+  std::vector<double> pair_unit;
+  // Native complex fronts (round 3): the tree of the COMPLEX pattern, present when the plain embedding is held and the
+  // fronts may be those of the complex matrix itself (half the unknowns, complex fronts in two planes, multifrontal.hip)
+  // — a solve with them is a solve with E (packed complex vectors ARE the real vectors of the embedding), at half the
   // flops and bytes.  zsym: the complex matrix is symmetric (A == A^T): L D L^T.
   std::shared_ptr<const mf::Tree> ztree;
-  int zfront = 0, zsym = 0;
-  // Threshold pivoting inside the diagonal blocks of the fronts (Band::piv): on for every matrix that is not
-  // diagonally dominant by columns — its factors without interchanges are a speculation, and the rows of a pivot block
-  // are free to change places.  A symmetric matrix is first tried as L D L^T (no interchanges: half the flops); if the
-  // check of a solve rejects those factors, the same tree is factored once more as LU with block pivoting
-  // (block_pivot_retry) before static pivoting takes over.  SPL_LU_BLOCK_PIVOT=0: never.
-  int dominant = 0, mf_piv = 0, block_pivot_retry = 0;
-  DBuf<double> rscale;  // row scales of the block pivoting (new ordering of the tree in use)
-  // set when a refactorisation failed after the previous factors were released: the object holds no
-  // usable factors any more and every later solve returns an error instead of launching kernels
-  std::atomic<int> broken{0};
-  // 1: the matrix is NOT diagonally dominant by columns and the no-interchange factors are a
-  // speculation; solve checks the backward error it computes anyway and, if it is not at
-  // rounding level, refactors with partial pivoting (under `mu`) and solves again
-  std::atomic<int> speculative{0};
-  // 1: the factors held passed the acceptance check a solve runs, made by a determinant call (umfpack_di_get_determinant
-  // and the like) on a speculative object: later determinant calls need only the pivot reduction.  Cleared whenever the
-  // factors are rebuilt.  Solves keep checking as before (speculative is left as it is: ending it would cut their
-  // refinement from 10 steps to 2 and their fallbacks off), so a later solve may still replace factors accepted here.
-  std::atomic<int> det_checked{0};
-  // 1: the real embedding of a complex matrix (umfpack_zi.hip): its determinant is |det|^2 of the complex matrix
-  int embedding = 0;
-  std::mutex mu;
-  DBuf<double> AB;
-  DBuf<double> blkinv;  // no-pivot path: inv(L11), inv(U11) of every diagonal block
-  DBuf<int> ipiv, perm, inv;
-  // multifrontal factors (then AB is empty and perm/inv hold the nested-dissection ordering); the
-  // band ordering is kept for the pivoting fallback
-  mf::Factors *mfact = nullptr;
-  std::shared_ptr<const mf::Tree> tree;
-  std::vector<int> band_perm, band_inv;
+  int zsym = 0;
   Matrix *A = nullptr;   // rows of A   (residual b - A x)
   Matrix *At = nullptr;  // rows of A^T (residual b - A^T x)
-  // set by the `zi` wrapper (umfpack_zi.hip): rows 2r, 2r+1 of the real embedding were swapped
-  std::vector<char> pair_swap;
-  std::vector<double> pair_unit;  // zi wrapper, complex symmetric matrices: unit-modulus u_r (re, im) of the congruence D A D
-  // Static pivoting (static_pivot.hpp): 0 not tried, 1 the factors held are those of B = Dr P A Dc on B's own
-  // tree (still a checked speculation), 2 tried and given up.  spA / spAt: rows of B / of B^T on the device
-  // (what mf_factor scatters); sp_idx / sp_scale: the permutations and scalings around a solve with B's factors,
-  // composed with B's nested-dissection ordering — [0] before, [1] after A x = b; [2] before, [3] after A^T x = b.
-  int sp_stage = 0;
+  std::vector<int> band_perm, band_inv;  // the RCM ordering, kept for the band fallback (empty: ensure_band_ordering)
+
+  // ---- the factors held -----------------------------------------------------------------------------------------------
+  Held held = Held::none;
+  TreeKind kind;            // of Held::tree
+  DBuf<int> perm, inv;      // the ordering of the factors held: RCM for the band kinds, the tree's otherwise
+  int kl = 0, ku = 0, ldab = 1;  // band kinds: the bandwidths under RCM and the leading dimension of AB
+  DBuf<double> AB;          // band kinds
+  DBuf<double> blkinv;      // band_blocked: inv(L11), inv(U11) of every diagonal block
+  DBuf<int> ipiv;           // band_pivoted: the row interchanges
+  mf::Factors *mfact = nullptr;           // tree kinds
+  std::shared_ptr<const mf::Tree> tree;   // tree kinds: the tree of the real fronts (of A's pattern, or of B's)
+  DBuf<double> rscale;  // block pivoting: the row scales that rank the candidates (new ordering of the tree in use)
+  // tree_static (static_pivot.hpp): spA / spAt: rows of B / of B^T on the device (what mf_factor scatters); sp_idx /
+  // sp_scale: the permutations and scalings around a solve with B's factors, composed with B's nested-dissection
+  // ordering — [0] before, [1] after A x = b; [2] before, [3] after A^T x = b.
+  std::unique_ptr<Matrix> spA, spAt;
+  DBuf<int> sp_idx[4];
+  DBuf<double> sp_scale[4];
+  // 1: the factors held passed the acceptance check a solve runs, made by a determinant call (umfpack_di_get_determinant
+  // and the like) on a speculative object: later determinant calls need only the pivot reduction.  Cleared whenever the
+  // factors are released.  Solves keep checking as before (speculative is left as it is: ending it would cut their
+  // refinement from 10 steps to 2 and their fallbacks off), so a later solve may still replace factors accepted here.
+  std::atomic<int> det_checked{0};
+  // set when a rebuild failed after the previous factors were released: the object holds no
+  // usable factors any more and every later solve returns an error instead of launching kernels
+  std::atomic<int> broken{0};
+
+  // ---- the history of the ladder (next_factors, umfpack.hip): every rung is climbed once --------------------------------
+  // 1: the matrix is NOT diagonally dominant by columns and the factors held are still a speculation (no interchanges,
+  // or static pivoting); solve checks the backward error it computes anyway and, if it is not at rounding level, asks
+  // the ladder for the next factors (under `mu`) and solves again.  Cleared when the pivoted band is in place.
+  std::atomic<int> speculative{0};
+  bool block_pivot_retried = false;  // an L D L^T speculation was factored once more as LU with block pivoting
+  bool static_pivot_tried = false;   // static pivoting was attempted, whatever came of it
+
   // the most recent solve call that finished on this object (spl_umfpack_solve_report; UMFPACK reports the like in
   // Info[UMFPACK_IR_TAKEN .. UMFPACK_OMEGA1]): walks over the factors (first solve + refinement steps, whatever path),
   // refinement steps kept / attempted, largest componentwise backward error among the delivered columns
   std::atomic<int> last_walks{0}, last_ir_taken{0}, last_ir_attempted{0};
   std::atomic<double> last_omega{0.0};
-  Matrix *spA = nullptr, *spAt = nullptr;
-  DBuf<int> sp_idx[4];
-  DBuf<double> sp_scale[4];
   ~Numeric() {
     delete A;
     delete At;
-    delete spA;
-    delete spAt;
     if (mfact) mf_free(mfact);
+  }
+};
+
+// Keeps what spl_umfpack_solve_report describes — the caller's last solve — across solves that are not the caller's
+// (the acceptance check of a determinant call, the solves of the condition estimate).
+struct KeepSolveReport {
+  Numeric *N;
+  int walks = N->last_walks, ir_taken = N->last_ir_taken, ir_attempted = N->last_ir_attempted;
+  double omega = N->last_omega;
+  ~KeepSolveReport() {
+    N->last_walks = walks;
+    N->last_ir_taken = ir_taken;
+    N->last_ir_attempted = ir_attempted;
+    N->last_omega = omega;
   }
 };
 
