@@ -124,12 +124,14 @@ struct PanelImage {
   DBuf<int> segc;                 // npanels*nib + 1 (+ padding): first 64-entry chunk of each segment
   DBuf<unsigned> key;             // (local_col << 15) | local_row, segments padded to whole chunks
   DBuf<double> val;
-  DBuf<unsigned> arrive;          // rendezvous counter between generations
+  DBuf<int> ublk;                 // paired storage: index block of every unit (pair of chunks), for the rounds form
+  DBuf<unsigned> arrive;          // [0] rendezvous counter between generations, [1] ring form's error word, [2] rounds form: workgroups gone
   int unroll = 10;                // chunks per wavefront and register set
   int kblocks = 2;                // index blocks per phase (barrier to barrier)
   int pair = 0;                   // 1: paired storage (chunk pairs interleaved, 8-byte key / 16-byte value loads)
   int ablate = 0;                 // timing-only ablation bits (SPL_PANEL_ABLATE with SPL_ALLOW_ABLATION=1)
   int nslices = 1;                // paired form: column slices per panel (8 = one per XCD; csrc/spmv_panel.hip)
+  int rounds = 0;                 // 1: rounds form (fixed-length rounds of 16 * unroll units, per-unit block table)
   int ring = 0;                   // 1: ring form (loader wavefronts hand units to gather wavefronts through LDS slots)
   int ring_nl = 4, ring_depth = 6, ring_gather = 4, ring_slots = 1;  // loaders, units in flight per loader / per gatherer, slots per loader
 };

@@ -97,6 +97,16 @@ __global__ __launch_bounds__(256) void pnl_padseg_kernel(int64_t n, int last, in
   if (i < n) segc[from + i] = last;
 }
 
+// rounds form: the index block of every unit (pair of chunks) of the paired stream; segments are whole pairs,
+// so a unit lies in one block.  Entries behind the last unit stay 0 (they are read, never used).
+__global__ __launch_bounds__(256) void pnl_unitblock_kernel(int64_t nseg, int64_t nib, const int *__restrict__ segc,
+                                                            int *__restrict__ ublk) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= nseg) return;
+  const int ib = (int)(i % nib);
+  for (int c = segc[i] >> 1, e = segc[i + 1] >> 1; c < e; ++c) ublk[c] = ib;
+}
+
 template <typename PtrT>
 __global__ __launch_bounds__(256) void pnl_fill_kernel(int64_t nrows, const PtrT *__restrict__ rowptr,
                                                        const int *__restrict__ colidx,
@@ -443,6 +453,157 @@ __global__ __launch_bounds__(kPanelWaves * 64) void spmv_panelw_kernel(
   }
 }
 
+// ---- rounds form: fixed-length rounds instead of index-block phases ---------------------------------------
+// The paired form ties the barrier-to-barrier phase to index-block boundaries: a phase of K blocks holds
+// 16 U units only on average, and on C2 69 % of the phases are a unit or two longer, which sends one to three
+// wavefronts through the un-pipelined tail loop while the others wait at the barrier: some wavefront of a CU is
+// in that loop during 27 % of the launch (profiles/panel_rounds_before.txt; the tail's load is awaited with
+// vmcnt(0), behind the whole stream of the next phase).  And the register sets cannot be chosen freely: fewer
+// than the mean phase needs means longer tails, more means dummy loads.  Nothing in the result needs either:
+// the block of a unit follows from its position,
+// the barrier is pacing only.  Here a panel's paired stream is one sequence of units and a round is exactly
+// 16 U consecutive units (only a panel's last round is shorter): wavefront i takes units i, i + 16, ... of the
+// round into its U register sets, the next round's units are requested before the barrier, and the block of
+// every unit comes from a per-unit table (PanelImage::ublk, 4 bytes per 1 536 of stream) through the scalar
+// cache — a vector load would sit on vmcnt in front of the gathers (ring_sload below).  No tail loop, no
+// dummy units except behind a panel's end, and any segment size works (empty, shorter or longer than a round).
+// Measured on C2: 4 register sets 0.82 ms (the paired form's best, 5 sets x 2 blocks: 0.91 ms), 3: 0.85, 5: 0.90,
+// 6: 0.95 (profiles/panel_rounds_bench.json).  Column slices stay with the paired form.
+template <int U>
+__device__ inline void panelq_blocks_issue(int (&ib)[U], const int *p) {  // ib[u] = p[16 u], not awaited
+#pragma unroll
+  for (int u = 0; u < U; ++u) asm volatile("s_load_dword %0, %1, %2" : "=s"(ib[u]) : "s"(p), "n"(kPanelWaves * 4 * u) : "memory");
+}
+template <int U>
+__device__ inline void panelq_blocks_wait(int (&ib)[U]) {
+  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+#pragma unroll
+  for (int u = 0; u < U; ++u) asm volatile("" : "+s"(ib[u]));  // every use stays behind the wait
+}
+
+// One round: gather + fold this wavefront's units m0 + wave + 16 u (u < U; panel-relative, the panel has nu)
+// held in (idC, aC, ibC) while its units of the next round are loaded into (idN, aN, ibN).
+template <int U>
+__device__ inline void panelq_round(pnl_u2 (&idC)[U], pnl_d2 (&aC)[U], int (&ibC)[U], pnl_u2 (&idN)[U], pnl_d2 (&aN)[U],
+                                    int (&ibN)[U], int m0, int nu, int c0, int w, const pnl_u2 *__restrict__ key2,
+                                    const pnl_d2 *__restrict__ val2, const int *__restrict__ ublk,
+                                    const double *__restrict__ x, double *yp, int wave, int64_t dummy) {
+  const int lane = threadIdx.x & 63;
+  double xa[U], xb[U];
+  const double *pa[U], *pb[U];
+#pragma unroll
+  for (int u = 0; u < U; ++u) {
+    const bool ok = m0 + wave + kPanelWaves * u < nu;  // wave-uniform; false only in a panel's last round
+    const int64_t xo = (int64_t)ibC[u] << w;
+    pa[u] = x + (ok ? (xo + (int64_t)(idC[u].x >> kRowBits)) : 0);
+    pb[u] = x + (ok ? (xo + (int64_t)(idC[u].y >> kRowBits)) : 0);
+  }
+  __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+  for (int u = 0; u < U; ++u) {  // gathers first ...
+    xa[u] = pnl_gather_issue(pa[u]);
+    xb[u] = pnl_gather_issue(pb[u]);
+  }
+  __builtin_amdgcn_sched_barrier(0);
+  const int mn = m0 + kPanelWaves * U + wave;
+#pragma unroll
+  for (int u = 0; u < U; ++u) {  // ... then the next round's stream, left in flight across the barrier
+    const int m = mn + kPanelWaves * u;
+    const int64_t e = (m < nu ? ((int64_t)(c0 + m) << 6) : dummy) + lane;  // behind the panel: the L2-resident dummy unit
+    idN[u] = __builtin_nontemporal_load(key2 + e);
+    aN[u] = __builtin_nontemporal_load(val2 + e);
+  }
+  panelq_blocks_issue<U>(ibN, ublk + c0 + mn);  // the table carries slack behind the last unit
+  __builtin_amdgcn_sched_barrier(0);
+  // younger than gather j (j = 2u for A, 2u + 1 for B) here: 2U-1-j gathers + 2U stream loads
+#pragma unroll
+  for (int u = 0; u < U; ++u) {
+    if (u == 0) { pnl_gather_wait<4 * U - 1>(xa[u]); pnl_gather_wait<4 * U - 2>(xb[u]); }
+    if (u == 1) { pnl_gather_wait<4 * U - 3>(xa[u]); pnl_gather_wait<4 * U - 4>(xb[u]); }
+    if (u == 2) { pnl_gather_wait<4 * U - 5>(xa[u]); pnl_gather_wait<4 * U - 6>(xb[u]); }
+    if (u == 3) { pnl_gather_wait<(4 * U - 7 > 0 ? 4 * U - 7 : 0)>(xa[u]); pnl_gather_wait<(4 * U - 8 > 0 ? 4 * U - 8 : 0)>(xb[u]); }
+    if (u == 4) { pnl_gather_wait<(4 * U - 9 > 0 ? 4 * U - 9 : 0)>(xa[u]); pnl_gather_wait<(4 * U - 10 > 0 ? 4 * U - 10 : 0)>(xb[u]); }
+    if (u == 5) { pnl_gather_wait<(4 * U - 11 > 0 ? 4 * U - 11 : 0)>(xa[u]); pnl_gather_wait<(4 * U - 12 > 0 ? 4 * U - 12 : 0)>(xb[u]); }
+  }
+  panelq_blocks_wait<U>(ibN);
+#pragma unroll
+  for (int u = 0; u < U; ++u) {
+    if (m0 + wave + kPanelWaves * u >= nu) break;  // wave-uniform
+    pnl_fold(idC[u].x, aC[u].x * xa[u], yp);
+    pnl_fold(idC[u].y, aC[u].y * xb[u], yp);
+  }
+  __builtin_amdgcn_s_barrier();  // pacing only: no fence, vector memory stays in flight
+}
+
+// arrive[0]: rendezvous between generations, arrive[2]: workgroups that have left.  The last one to leave puts
+// both back to zero, so a stream of launches holds nothing but this kernel (the other forms clear arrive[0]
+// with a memset in front of every launch).
+template <int U>
+__global__ __launch_bounds__(kPanelWaves * 64) void spmv_panelq_kernel(
+    int64_t nrows, int64_t npanels, int P, int w, int64_t nib, const int *__restrict__ segc,
+    const int *__restrict__ ublk, const unsigned *__restrict__ key, const double *__restrict__ val,
+    const double *__restrict__ x, double *__restrict__ y, int accumulate, unsigned *__restrict__ arrive,
+    int64_t dummy) {
+  static_assert(U >= 3 && U <= 6, "register sets per wavefront");
+  extern __shared__ __attribute__((aligned(16))) double ylds[];  // P + 1 doubles
+  const pnl_u2 *key2 = reinterpret_cast<const pnl_u2 *>(key);
+  const pnl_d2 *val2 = reinterpret_cast<const pnl_d2 *>(val);
+  const int lane = threadIdx.x & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const int64_t nb = gridDim.x;
+  const int64_t ngen = (npanels + nb - 1) / nb;
+  constexpr int kRound = kPanelWaves * U;
+  for (int64_t g = 0; g < ngen; ++g) {
+    const int64_t p = g * nb + blockIdx.x;
+    if (p >= npanels) break;  // only in the last generation: no rendezvous follows
+    const int64_t row_base = p * P;
+    const int c0 = segc[p * nib] >> 1;  // in units; every segment boundary is a whole pair
+    const int nu = (segc[(p + 1) * nib] >> 1) - c0;
+    pnl_u2 idA[U], idB[U];
+    pnl_d2 aA[U], aB[U];
+    int ibA[U], ibB[U];
+#pragma unroll
+    for (int u = 0; u < U; ++u) {  // prologue: this wavefront's units of round 0
+      const int m = wave + kPanelWaves * u;
+      const int64_t k = (m < nu ? ((int64_t)(c0 + m) << 6) : dummy) + lane;
+      idA[u] = __builtin_nontemporal_load(key2 + k);
+      aA[u] = __builtin_nontemporal_load(val2 + k);
+    }
+    panelq_blocks_issue<U>(ibA, ublk + c0 + wave);
+    panelq_blocks_wait<U>(ibA);
+    for (int i = threadIdx.x; i <= P; i += kPanelWaves * 64)
+      ylds[i] = (accumulate && i < P && row_base + i < nrows) ? y[row_base + i] : 0.0;
+    __syncthreads();
+    for (int m0 = 0; m0 < nu; m0 += 2 * kRound) {
+      panelq_round<U>(idA, aA, ibA, idB, aB, ibB, m0, nu, c0, w, key2, val2, ublk, x, ylds, wave, dummy);
+      if (m0 + kRound < nu)
+        panelq_round<U>(idB, aB, ibB, idA, aA, ibA, m0 + kRound, nu, c0, w, key2, val2, ublk, x, ylds, wave, dummy);
+    }
+    __syncthreads();  // every wavefront's LDS adds are done (s_barrier above does not wait for lgkmcnt)
+    for (int i = threadIdx.x; i < P; i += kPanelWaves * 64)
+      if (row_base + i < nrows) y[row_base + i] = ylds[i];
+    if (g + 1 < ngen) {  // re-align the CUs between generations (bounded, performance only)
+      __syncthreads();
+      if (threadIdx.x == 0) {
+        __hip_atomic_fetch_add(arrive, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        const unsigned target = (unsigned)((g + 1) * nb);
+        const unsigned long long t0 = wall_clock64();  // 100 MHz
+        while (__hip_atomic_load(arrive, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < target) {
+          if (wall_clock64() - t0 > 20000ull) break;  // 200 us: give up, stay correct
+          __builtin_amdgcn_s_sleep(8);
+        }
+      }
+      __syncthreads();
+    }
+  }
+  // leave: whoever arrives last knows that nobody will touch the rendezvous word again in this launch
+  if (threadIdx.x == 0 &&
+      __hip_atomic_fetch_add(arrive + 2, 1u, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_AGENT) == (unsigned)nb - 1u) {
+    __hip_atomic_store(arrive, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    __hip_atomic_store(arrive + 2, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  }
+}
+
 // ---- ring form (round 3): loader wavefronts + gather wavefronts ---------------------------------------
 // What the probes say (tools/probe/lds_dma_mix_probe.hip, profiles/r03_tcp_mix_lds_dma.txt): when every
 // wavefront carries both the HBM stream and the L2 gathers, the two times ADD (vmcnt retires in order, so a
@@ -688,7 +849,8 @@ void build_panel_image(Matrix *m, int P, int w, int pair, hipStream_t s) {
   // padding: column 0 of the block, the dummy row P, value 0
   SPL_HIP(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(b->key.get()), P, entries, s));
   SPL_HIP(hipMemsetAsync(b->val.get(), 0, entries * sizeof(double), s));
-  b->arrive.alloc(2);  // [0] generation rendezvous, [1] ring form: a bounded wait gave up
+  b->arrive.alloc(4);  // [0] generation rendezvous, [1] ring form: a bounded wait gave up, [2] rounds form: workgroups gone
+  SPL_HIP(hipMemsetAsync(b->arrive.get(), 0, 4 * sizeof(unsigned), s));
   SPL_HIP(hipMemsetAsync(counts.get(), 0, ((size_t)nseg + 1) * sizeof(int), s));
   if (m->nrows_local > 0) {
     if (m->rowptr.get())
@@ -708,6 +870,13 @@ void build_panel_image(Matrix *m, int P, int w, int pair, hipStream_t s) {
   if (pair && nchunks > 0)
     hipLaunchKernelGGL(pnl_interleave_kernel, dim3((unsigned)(nchunks / 2)), dim3(128), 0, s, nchunks / 2,
                        b->key.get(), b->val.get());
+  if (pair) {  // rounds form: the index block of every unit; the slack behind the last one is read, never used
+    const size_t units = (size_t)(nchunks / 2) + kPanelSlackChunks;
+    b->ublk.alloc(units);
+    SPL_HIP(hipMemsetAsync(b->ublk.get(), 0, units * sizeof(int), s));
+    hipLaunchKernelGGL(pnl_unitblock_kernel, dim3(blocks_for(nseg, 256)), dim3(256), 0, s, nseg, b->nib,
+                       b->segc.get(), b->ublk.get());
+  }
   SPL_HIP(hipStreamSynchronize(s));
   delete m->panel;
   m->panel = b.release();
@@ -743,6 +912,20 @@ static void launch_panelw_as(const Matrix *m, const PanelImage *b, unsigned nb, 
                      b->arrive.get(), (int64_t)(b->nchunks / 2) << 6, ns);
 }
 
+
+template <int U>
+static void launch_panelq_as(const Matrix *m, const PanelImage *b, unsigned nb, size_t lds, const double *d_x,
+                             double *d_y, int accumulate, hipStream_t s) {
+  static std::atomic<uint64_t> set_{0};
+  if (!(set_.load(std::memory_order_acquire) >> (m->device & 63) & 1u)) {
+    SPL_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&spmv_panelq_kernel<U>),
+                                hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+    set_.fetch_or(1ull << (m->device & 63), std::memory_order_release);
+  }
+  hipLaunchKernelGGL((spmv_panelq_kernel<U>), dim3(nb), dim3(kPanelWaves * 64), lds, s, m->nrows_local, b->npanels,
+                     b->P, b->w, b->nib, b->segc.get(), b->ublk.get(), b->key.get(), b->val.get(), d_x, d_y, accumulate,
+                     b->arrive.get(), (int64_t)(b->nchunks / 2) << 6);
+}
 
 size_t panel_ring_lds_bytes(int P, int nl, int slots) {
   return ((((size_t)P + 1) * sizeof(double) + 15) & ~(size_t)15) + (size_t)nl * slots * (kRingUnitBytes + 8);
@@ -804,11 +987,28 @@ int launch_spmv_panel(const Matrix *m, const double *d_x, double *d_y, int accum
   }
   const size_t lds = ((size_t)b->P + 1) * sizeof(double);
   if (lds > 160 * 1024) return SPL_ERROR_argument_missing;
-  int cus = 0;
-  SPL_HIP(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, m->device));
+  static std::atomic<int> cus_of[64];  // CUs of device d: asked once, not per launch
+  int cus = cus_of[m->device & 63].load(std::memory_order_relaxed);
+  if (cus == 0) {
+    SPL_HIP(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, m->device));
+    cus_of[m->device & 63].store(cus, std::memory_order_relaxed);
+  }
   int64_t nb = cus;
-  const int64_t tasks = b->npanels * (b->nslices > 1 && b->pair && !b->ring ? b->nslices : 1);
+  const int64_t tasks = b->npanels * (b->nslices > 1 && b->pair && !b->ring && !b->rounds ? b->nslices : 1);
   if (nb > tasks) nb = tasks;
+  if (b->rounds) {  // the kernel itself puts the rendezvous word back: nothing else goes on the stream
+    if (!b->pair || !b->ublk.get()) return SPL_ERROR_internal;
+    switch (b->unroll) {
+      case 3: launch_panelq_as<3>(m, b, (unsigned)nb, lds, d_x, d_y, accumulate, s); break;
+      case 4: launch_panelq_as<4>(m, b, (unsigned)nb, lds, d_x, d_y, accumulate, s); break;
+      case 5: launch_panelq_as<5>(m, b, (unsigned)nb, lds, d_x, d_y, accumulate, s); break;
+      case 6: launch_panelq_as<6>(m, b, (unsigned)nb, lds, d_x, d_y, accumulate, s); break;
+      default: return SPL_ERROR_argument_missing;
+    }
+    hipError_t eq = hipGetLastError();
+    if (eq != hipSuccess) { set_last_error("spmv_panelq launch", eq); return SPL_ERROR_device; }
+    return SPL_OK;
+  }
   SPL_HIP(hipMemsetAsync(b->arrive.get(), 0, sizeof(unsigned), s));
   if (b->ring) return launch_panel_ring(m, b, (unsigned)nb, d_x, d_y, accumulate, s);
   const int U = b->unroll, K = b->kblocks;

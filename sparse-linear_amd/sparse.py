@@ -350,7 +350,11 @@ class DeviceMatrix(object):
 
     def build_panel(self, rows_per_panel=0, cols_log2=0, unroll=0, form=0):
         """the column-sorted panel image (csrc/spmv_panel.hip): order-free sums, 1e-10 contract;
-        form 1 / 2: one chunk per load, 1 / 2 index blocks per phase; 4 / 5: paired storage (default)"""
+        form 1 / 2: one chunk per load, 1 / 2 index blocks per phase; 4 / 5: paired storage, 1 / 2 index blocks
+        per phase (the default's heuristic); 6 ... 10: ring form; 11: rounds form on the paired storage — rounds of
+        exactly 16 * unroll pairs of chunks whatever the index blocks are (unroll 3 ... 6, 0: 5), no column slices.
+        With everything 0 on a large matrix the build times the heuristic's neighbours, the rounds form among them,
+        and keeps another candidate only if it is more than 1 % faster."""
         check("spl_matrix_build_panel",
               lib().spl_matrix_build_panel(self.handle, rows_per_panel, cols_log2, unroll, form))
 
