@@ -176,7 +176,12 @@ int spl_matrix_is_complex(void *H);
 int spl_matrix_create_rowblock(int nrows, int ncols, const int *Ap, const int *Ai,
                                const double *Ax, int part, int nparts, void **H);
 /* Build from CSR arrays directly (== the CSC arrays of A^T). Rows [row0,row0+nrows_local)
- * of a matrix with nrows_global rows. */
+ * of a matrix with nrows_global rows.  Column indices need not ascend inside a row: like the CSC entry points the
+ * call sorts the rows that do not (indices and values together); rows that already ascend cost one check.
+ * Duplicate column indices inside a row are NOT merged (that is spl_compress): they stay separate stored entries,
+ * adjacent after the sort and in unspecified relative order.  The SpMV / SpMM kernels add every stored entry;
+ * lin, spgemm, transpose, export_csc and the LU, which rely on strictly ascending indices, are undefined on such a
+ * handle. */
 int spl_matrix_create_csr(int64_t nrows_global, int64_t ncols, int64_t row0, int64_t nrows_local,
                           const int *rowptr, const int *colidx, const double *val, void **H);
 /* Synthetic workloads generated on the device (include/spl_synth.h):

@@ -388,6 +388,12 @@ int spl_matrix_create_csr(int64_t nrows_global, int64_t ncols, int64_t row0, int
     if (st != SPL_OK) return st;
     m->rowptr64.alloc((size_t)nrows_local + 1);
     widen_i32_to_i64(dptr.get(), m->rowptr64.get(), nrows_local + 1, s);
+    // rows with unsorted columns are tolerated as unsorted CSC columns are (upload_csc): lin, spgemm, the transposes
+    // and the reference-order SpMV all walk ascending indices.  A sorted input pays the check only.
+    if (!columns_sorted(dptr.get(), m->colidx.get(), nrows_local, s)) {
+      segmented_sort_pairs(m->rowptr64.get(), nrows_local, m->colidx.get(), m->val.get(), s);
+      SPL_HIP(hipStreamSynchronize(s));
+    }
     return publish(std::move(m), s, H);
   });
 }

@@ -46,3 +46,16 @@ def tuple_to_mat(pkg, m):
 def tuples_equal(a, b):
     return (a[0] == b[0] and a[1] == b[1] and np.array_equal(a[2], b[2]) and np.array_equal(a[3], b[3])
             and np.array_equal(a[4], b[4]))
+
+
+def handle_to_csc_tuple(H):
+    """(nrows_local, ncols, colptr, rowidx, values) of a device handle's block, local row ids: its CSR arrays are the
+    CSC arrays of the transpose, so transpose back on the host side with a stable sort (order inside columns
+    preserved)"""
+    inf = H.info()
+    rp, ci, v = H.export_csr()
+    nr, nc = inf["nrows_local"], inf["ncols"]
+    rows = np.repeat(np.arange(nr, dtype=np.int64), np.diff(rp))
+    order = np.argsort(ci, kind="stable")
+    cp = np.concatenate([[0], np.cumsum(np.bincount(ci, minlength=nc))]).astype(np.int64)
+    return (nr, nc, cp, rows[order], v[order])

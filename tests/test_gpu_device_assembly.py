@@ -6,7 +6,7 @@ thread-per-column kernel it replaces (SPL_LIN_TILED=0) and of orc_lin / orc_lin_
 import numpy as np
 import pytest
 
-from helpers import mat_to_tuple, tuple_to_mat, tuples_equal
+from helpers import handle_to_csc_tuple, mat_to_tuple, tuple_to_mat, tuples_equal
 
 pytestmark = pytest.mark.gpu
 
@@ -23,18 +23,6 @@ def _compress_c(O, nr, nc, r, c, v):
     re = O.compress(nr, nc, r, c, v.real.copy())
     im = O.compress(nr, nc, r, c, v.imag.copy())
     return (nr, nc, re[2], re[3], re[4] + 1j * im[4])
-
-
-def handle_to_csc_tuple(H):
-    """(nrows, ncols, colptr, rowidx, values) of a whole-matrix handle: its CSR arrays are the CSC arrays of the
-    transpose, so transpose back on the host side with a stable sort (order inside columns preserved)"""
-    inf = H.info()
-    rp, ci, v = H.export_csr()
-    nr, nc = inf["nrows_local"], inf["ncols"]
-    rows = np.repeat(np.arange(nr, dtype=np.int64), np.diff(rp))
-    order = np.argsort(ci, kind="stable")
-    cp = np.concatenate([[0], np.cumsum(np.bincount(ci, minlength=nc))]).astype(np.int64)
-    return (nr, nc, cp, rows[order], v[order])
 
 
 _LIN_SHAPES = [(1, 1, 1), (37, 129, 400), (5000, 4000, 90_000), (300, 128 * 7, 30_000)]
