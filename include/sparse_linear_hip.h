@@ -294,14 +294,42 @@ int spl_debug_occupy(int blocks, int threads, double milliseconds, double *d_buf
 int spl_debug_sort_u64(unsigned long long *d_keys, long long n, int nbits, void *stream);
 /* build the column-sorted panel image with an explicit shape (tuning / ablation): panels of
  * rows_per_panel rows (<= 20479: one workgroup's LDS), index blocks of 2^cols_log2 columns
- * (<= 17); 0,0 = choose.  form: 0 default; 1 / 2 = one 64-entry chunk per load instruction with 1 / 2
- * index blocks per barrier phase; 4 / 5 = paired storage (two chunks per 8-byte key / 16-byte value
- * load) with 1 / 2 index blocks per phase.  unroll: 0 default, else chunks ({4,6,8,10,12}) or pairs
- * ({2..6}) per wavefront and register set.  6 / 7 = ring form on the paired storage (a few wavefronts of
- * the workgroup only stream the image and hand it to the others, which only gather and fold, through
- * 1.5 KiB slots in LDS; 1 / 2 index blocks per phase; unroll = units in flight per loader, 0 = 6;
- * rows_per_panel then has to leave room for the slots: 19 700 with the default 4 loaders).  Used by
- * variant 16, and by variant 0 once spl_matrix_set_spmv_order(H, SPL_ORDER_FREE) was called. */
+ * (<= 17); 0,0 = choose.  `form` says which kernel walks the image, `unroll` how deep its pipeline is:
+ *   form                       kernel                                                    unroll (0 = default)
+ *   SPL_PANEL_FORM_DEFAULT     paired, 2 index blocks per phase when cols_log2 = 17,     as for the paired forms; with
+ *                              else 1                                                    0,0,0,0 on a large matrix the
+ *                                                                                        build times the neighbours,
+ *                                                                                        the rounds form among them
+ *   SPL_PANEL_FORM_CHUNK_K1    one 64-entry chunk per load instruction, 1 / 2 index      chunks per wavefront and
+ *   SPL_PANEL_FORM_CHUNK_K2    blocks per barrier phase                                  register set: 4, 6, 8, 10, 12
+ *                                                                                        (0: from the mean phase)
+ *   SPL_PANEL_FORM_PAIRED_K1   paired storage (two chunks per 8-byte key / 16-byte       pairs per wavefront and register
+ *   SPL_PANEL_FORM_PAIRED_K2   value load), 1 / 2 index blocks per phase; the only       set: 2 ... 4 (K1), 3 ... 6 (K2)
+ *                              forms that take column slices (SPL_PANEL_SLICES)          (0: from the mean phase)
+ *   SPL_PANEL_FORM_RING_K1     ring form on the paired storage: a few wavefronts of      units in flight per loader
+ *   ..._K2, _K3, _K4, _K8      the workgroup only stream the image and hand it to the    (0: 6)
+ *                              others, which only gather and fold, through 1.5 KiB
+ *                              slots in LDS; 1 / 2 / 3 / 4 / 8 index blocks per phase;
+ *                              rows_per_panel has to leave room for the slots (19 700
+ *                              with the default 4 loaders)
+ *   SPL_PANEL_FORM_ROUNDS      rounds form on the paired storage: fixed rounds of        pairs per wavefront and register
+ *                              16 * unroll pairs whatever the index blocks are; no       set: 3 ... 6 (0: 5); anything
+ *                              column slices                                             else is refused here
+ * A chunk or paired request between the instantiated counts is served by the nearest kernel; a ring shape
+ * (SPL_PANEL_RING_NL / _SLOTS / _GD with the form's blocks per phase and unroll) that is not instantiated is
+ * refused by the first spl_matrix_spmv_dev with SPL_ERROR_argument_missing.  Any other form code is refused here.
+ * Used by variant 16, and by variant 0 once spl_matrix_set_spmv_order(H, SPL_ORDER_FREE) was called. */
+#define SPL_PANEL_FORM_DEFAULT 0
+#define SPL_PANEL_FORM_CHUNK_K1 1
+#define SPL_PANEL_FORM_CHUNK_K2 2
+#define SPL_PANEL_FORM_PAIRED_K1 4
+#define SPL_PANEL_FORM_PAIRED_K2 5
+#define SPL_PANEL_FORM_RING_K1 6
+#define SPL_PANEL_FORM_RING_K2 7
+#define SPL_PANEL_FORM_RING_K3 8
+#define SPL_PANEL_FORM_RING_K4 9
+#define SPL_PANEL_FORM_RING_K8 10
+#define SPL_PANEL_FORM_ROUNDS 11
 int spl_matrix_build_panel(void *H, int rows_per_panel, int cols_log2, int unroll, int form);
 /* Diagnostics: synchronises the device and returns 1 when a bounded wait of the ring form's hand-over gave
  * up during the last panel SpMV of this handle (its result is then invalid), 0 otherwise, < 0 on error. */

@@ -784,141 +784,25 @@ int spl_matrix_build_panel(void *H, int rows_per_panel, int cols_log2, int unrol
   Matrix *m = as_matrix(H);
   if (!m) return SPL_ERROR_invalid_handle;
   if (m->vw != 1) return SPL_ERROR_argument_missing;
-  const bool auto_shape = rows_per_panel == 0 && cols_log2 == 0, form_was_default = form == 0, unroll_was_default = unroll == 0;
+  if (!panel_code_valid(form, unroll)) return SPL_ERROR_argument_missing;
+  const bool auto_shape = rows_per_panel == 0 && cols_log2 == 0;
   int nslices = 1;
-  if (rows_per_panel == 0 && cols_log2 == 0) choose_panels(m, &rows_per_panel, &cols_log2, (form == 0 || form == 4 || form == 5) ? &nslices : nullptr);
-  else if (const char *ev = getenv("SPL_PANEL_SLICES")) { if (form == 4 || form == 5) nslices = atoi(ev) >= 1 ? atoi(ev) : 1; }
+  if (auto_shape) {
+    choose_panels(m, &rows_per_panel, &cols_log2, panel_code_takes_slices(form) ? &nslices : nullptr);
+  } else if (form != SPL_PANEL_FORM_DEFAULT && panel_code_takes_slices(form)) {  // explicit shape: slices only on request
+    const int f = panel_slices_override();
+    if (f >= 1) nslices = f;
+  }
   if (rows_per_panel < 1 || rows_per_panel > 20479 || cols_log2 < 4 || cols_log2 > 17)
     return SPL_ERROR_argument_missing;
-  if (form != 0 && form != 1 && form != 2 && form != 4 && form != 5 && (form < 6 || form > 11)) return SPL_ERROR_argument_missing;
-  if (form == 11 && unroll != 0 && (unroll < 3 || unroll > 6)) return SPL_ERROR_argument_missing;
   return guarded([&]() -> int {
     DeviceGuard g(m->device);
-    // form: 1 / 2 = one chunk per load, 1 / 2 index blocks per phase; 4 / 5 = paired storage (a pair of
-    // chunks per 8-byte key / 16-byte value load; unroll then counts pairs), 1 / 2 index blocks per phase.
-    // Default: paired, a phase's x window 2 MiB at most (measured on C2, tools/bench_spmv_variants.py:
-    // paired 0.90 ms, one chunk per load 0.96 ms)
-    // 6 / 7 = ring form on the paired storage (loader + gather wavefronts, csrc/spmv_panel.hip), 1 / 2 index
-    // blocks per phase; unroll then counts the units a loader keeps in flight (0: 6)
-    // 11 = rounds form on the paired storage: fixed rounds of 16 * unroll units whatever the index blocks are
-    // (unroll 3 ... 6, 0: 5); no column slices
-    if (form == 0) form = cols_log2 >= 17 ? 5 : 4;
-    const bool pair = form >= 4;
-    const bool rounds = form == 11;
-    const bool ring = form >= 6 && !rounds;
-    // ring forms: 6 / 7 / 8 / 9 / 10 = 1 / 2 / 3 / 4 / 8 index blocks per phase
-    const int kblocks = rounds ? 2 : form == 10 ? 8 : form >= 8 ? form - 5 : (form == 2 || form == 5 || form == 7) ? 2 : 1;
-    if (ring) {
-      int nl = 4, slots = 1;
-      if (const char *ev = getenv("SPL_PANEL_RING_NL")) nl = atoi(ev);
-      if (const char *ev = getenv("SPL_PANEL_RING_SLOTS")) slots = atoi(ev);
-      if (nl < 1 || slots < 1 || panel_ring_lds_bytes(rows_per_panel, nl, slots) > 160 * 1024) return SPL_ERROR_argument_missing;
-    }
-    build_panel_image(m, rows_per_panel, cols_log2, pair ? 1 : 0, nullptr);
-    PanelImage *b = m->panel;
-    b->kblocks = kblocks;
-    b->nslices = pair && !ring && !rounds ? nslices : 1;
-    if (rounds) {
-      b->rounds = 1;
-      b->unroll = unroll > 0 ? unroll : 5;
-      b->ablate = 0;
-      return SPL_OK;
-    }
-    if (ring) {
-      b->ring = 1;
-      b->ring_depth = unroll > 0 ? unroll : 6;
-      if (const char *ev = getenv("SPL_PANEL_RING_NL")) b->ring_nl = atoi(ev);
-      if (const char *ev = getenv("SPL_PANEL_RING_SLOTS")) b->ring_slots = atoi(ev);
-      if (const char *ev = getenv("SPL_PANEL_RING_GD")) b->ring_gather = atoi(ev);
-      b->unroll = 0;
-      b->ablate = 0;
-      return SPL_OK;
-    }
-    if (unroll == 0) {
-      // units (chunks or pairs) per wavefront and phase: the 16 wavefronts share a phase's units evenly and a
-      // phase's length varies by a unit or two.  More loads in flight than the mean needs cost time (the
-      // stream then queues in front of the gathers in the CU's L1): the nearest count, and the longer phases
-      // take the un-pipelined tail loop (measured on C2: 5 pairs 0.90 ms, 6 pairs 0.97 ms).  Those are not
-      // few: on C2 69 % of the phases are longer than 16 * 5 pairs, and some wavefront of a CU sits in the
-      // tail loop during 27 % of the launch (profiles/panel_rounds_before.txt) — what the rounds form
-      // (form 11, a candidate of the autotune below) does away with.
-      const double per_wave = (double)b->nchunks * kblocks / (double)(b->npanels * b->nib > 0 ? b->npanels * b->nib : 1) / 16.0;
-      if (pair) {
-        unroll = (int)(per_wave / 2.0 + 0.5);
-        unroll = unroll < 2 ? 2 : unroll > 6 ? 6 : unroll;
-      } else {
-        const int want = (int)(per_wave + 0.5);
-        unroll = want <= 4 ? 4 : want <= 6 ? 6 : want <= 8 ? 8 : want <= 10 ? 10 : 12;
-      }
-    }
-    const bool autotune = auto_shape && form_was_default && unroll_was_default && pair && m->nnz > (int64_t)1 << 22;
-    if (const char *ev = getenv("SPL_PANEL_UNROLL")) unroll = atoi(ev);
-    b->unroll = unroll;
-    if (autotune && !getenv("SPL_PANEL_UNROLL") && !(getenv("SPL_PANEL_TUNE") && getenv("SPL_PANEL_TUNE")[0] == '0')) {
-      // The register sets per wavefront and the index blocks per phase are worth 5-10 % either way and the
-      // best pair sits next to the heuristic one (C2: 5 pairs, 2 blocks: 0.90 ms; 6 pairs: 0.97; 4: 0.98;
-      // 3 pairs, 1 block: 0.96): time the neighbours once (the image is the same for all of them; about a
-      // hundred launches on a scratch vector) and keep the fastest.  SPL_PANEL_TUNE=0 keeps the heuristic.
-      // Without column slices the rounds form runs on the same image and joins with the same register sets
-      // +- 1 (C2: 4 pairs in rounds 0.82 ms, 5: 0.90, 6: 0.95, 3: 0.85; profiles/panel_rounds_bench.json).
-      DBuf<double> tx((size_t)m->ncols), ty((size_t)m->nrows_local);
-      SPL_HIP(hipMemsetAsync(tx.get(), 0, (size_t)m->ncols * sizeof(double), nullptr));
-      hipEvent_t e0, e1;
-      SPL_HIP(hipEventCreate(&e0));
-      SPL_HIP(hipEventCreate(&e1));
-      struct Cand { int k, u, q; };  // index blocks per phase, register sets, 1: rounds form
-      std::vector<Cand> cands;
-      for (int du = -1; du <= 1; ++du) {
-        const int u2 = unroll + du;
-        if (kblocks == 2 && u2 >= 3 && u2 <= 6) cands.push_back({2, u2, 0});
-        if (kblocks == 1 && u2 >= 2 && u2 <= 4) cands.push_back({1, u2, 0});
-      }
-      if (kblocks == 2) {
-        for (int u1 = (unroll + 1) / 2; u1 <= (unroll + 1) / 2 + 1; ++u1)
-          if (u1 >= 2 && u1 <= 4) cands.push_back({1, u1, 0});
-      }
-      if (b->nslices == 1) {  // the rounds form does not depend on the index blocks: the same register sets +- 1
-        const int uq = unroll < 3 ? 3 : unroll > 6 ? 6 : unroll;
-        for (int u2 = uq - 1; u2 <= uq + 1; ++u2)
-          if (u2 >= 3 && u2 <= 6) cands.push_back({kblocks, u2, 1});
-      }
-      float best = 0.f;
-      int best_k = kblocks, best_u = unroll, best_q = 0;
-      float heur = 0.f;
-      for (const Cand &c : cands) {
-        b->kblocks = c.k;
-        b->unroll = c.u;
-        b->rounds = c.q;
-        SPL_HIP(hipMemsetAsync(b->arrive.get(), 0, 4 * sizeof(unsigned), nullptr));  // the forms clear it differently
-        for (int w = 0; w < 2; ++w) (void)launch_spmv_panel(m, tx.get(), ty.get(), 0, nullptr);
-        SPL_HIP(hipEventRecord(e0, nullptr));
-        for (int r = 0; r < 8; ++r) (void)launch_spmv_panel(m, tx.get(), ty.get(), 0, nullptr);
-        SPL_HIP(hipEventRecord(e1, nullptr));
-        SPL_HIP(hipEventSynchronize(e1));
-        float ms = 0.f;
-        SPL_HIP(hipEventElapsedTime(&ms, e0, e1));
-        if (getenv("SPL_PANEL_VERBOSE"))
-          fprintf(stderr, "[panel] candidate %d pairs x %s: %.4f ms\n", c.u, c.q ? "rounds" : c.k == 2 ? "2 blocks" : "1 block", ms / 8.f);
-        if (c.k == kblocks && c.u == unroll && !c.q) heur = ms;
-        if (best == 0.f || ms < best) { best = ms; best_k = c.k; best_u = c.u; best_q = c.q; }
-      }
-      (void)hipEventDestroy(e0);
-      (void)hipEventDestroy(e1);
-      if (heur > 0.f && best > 0.99f * heur) { best_k = kblocks; best_u = unroll; best_q = 0; }  // within noise: keep the heuristic
-      if (getenv("SPL_PANEL_VERBOSE"))
-        fprintf(stderr, "[panel] heuristic %d pairs x %d blocks: %.4f ms; chosen %d x %d%s: %.4f ms\n", unroll, kblocks,
-                heur / 8.f, best_u, best_k, best_q ? " (rounds)" : "", best / 8.f);
-      b->kblocks = best_k;
-      b->unroll = best_u;
-      b->rounds = best_q;
-      SPL_HIP(hipMemsetAsync(b->arrive.get(), 0, 4 * sizeof(unsigned), nullptr));
-      SPL_HIP(hipStreamSynchronize(nullptr));  // the caller's launches may go to another stream
-    }
-    b->ablate = 0;
-    {
-      const char *ok = getenv("SPL_ALLOW_ABLATION"), *ab = getenv("SPL_PANEL_ABLATE");
-      if (ok && ok[0] == '1' && ab && !pair) b->ablate = atoi(ab) & 7;
-    }
+    const PanelPlan asked = panel_plan_from_code(form, unroll, cols_log2, nslices);
+    if (asked.form == PanelForm::Ring &&
+        (asked.nl < 1 || asked.slots < 1 || panel_ring_lds_bytes(rows_per_panel, asked.nl, asked.slots) > 160 * 1024))
+      return SPL_ERROR_argument_missing;
+    build_panel_image(m, rows_per_panel, cols_log2, asked.form != PanelForm::Chunk, nullptr);
+    m->panel->plan = choose_panel_plan(m, m->panel, form, unroll, nslices, auto_shape);
     return SPL_OK;
   });
 }

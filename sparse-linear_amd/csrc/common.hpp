@@ -117,6 +117,23 @@ struct BlockedImage {
   int lockstep_waves = 16;        // wavefronts (= panels) per lockstep workgroup: 16 or 8; 0 = ablation kernel
 };
 
+// What one launch of the panel SpMV runs (spmv_panel.hip): the form and its numbers.  Made from the ABI's form code
+// by panel_plan_from_code / choose_panel_plan; the kernels that exist are the table in spmv_panel.hip.
+enum class PanelForm {
+  Chunk,   // one chunk per load, phases of kblocks index blocks
+  Paired,  // paired storage (a pair of chunks per 8-byte key / 16-byte value load), phases, optional column slices
+  Rounds,  // paired storage, fixed rounds of 16 * sets units whatever the index blocks are
+  Ring     // paired storage, loader wavefronts hand units to gather wavefronts through LDS slots
+};
+struct PanelPlan {
+  PanelForm form = PanelForm::Chunk;
+  int sets = 0;                   // register sets per wavefront (chunks, or pairs of them); ring: units in flight per loader
+  int kblocks = 2;                // index blocks per phase (barrier to barrier); not used by the rounds form
+  int nslices = 1;                // paired form: column slices per panel (8 = one per XCD)
+  int ablate = 0;                 // chunk form: timing-only ablation bits (SPL_PANEL_ABLATE with SPL_ALLOW_ABLATION=1)
+  int nl = 4, gather = 4, slots = 1;  // ring form: loaders, units in flight per gatherer, slots per loader
+};
+
 // workgroup-wide column-sorted panels of a row block (spmv_panel.hip): the order-free SpMV mode
 struct PanelImage {
   int P = 0, w = 0;               // panel = P rows (one workgroup's LDS), index block = 2^w columns (w <= 17)
@@ -125,15 +142,9 @@ struct PanelImage {
   DBuf<unsigned> key;             // (local_col << 15) | local_row, segments padded to whole chunks
   DBuf<double> val;
   DBuf<int> ublk;                 // paired storage: index block of every unit (pair of chunks), for the rounds form
-  DBuf<unsigned> arrive;          // [0] rendezvous counter between generations, [1] ring form's error word, [2] rounds form: workgroups gone
-  int unroll = 10;                // chunks per wavefront and register set
-  int kblocks = 2;                // index blocks per phase (barrier to barrier)
+  DBuf<unsigned> arrive;          // the sync words: rendezvous between generations, ring form's error word, rounds form's leave count
   int pair = 0;                   // 1: paired storage (chunk pairs interleaved, 8-byte key / 16-byte value loads)
-  int ablate = 0;                 // timing-only ablation bits (SPL_PANEL_ABLATE with SPL_ALLOW_ABLATION=1)
-  int nslices = 1;                // paired form: column slices per panel (8 = one per XCD; csrc/spmv_panel.hip)
-  int rounds = 0;                 // 1: rounds form (fixed-length rounds of 16 * unroll units, per-unit block table)
-  int ring = 0;                   // 1: ring form (loader wavefronts hand units to gather wavefronts through LDS slots)
-  int ring_nl = 4, ring_depth = 6, ring_gather = 4, ring_slots = 1;  // loaders, units in flight per loader / per gatherer, slots per loader
+  PanelPlan plan;                 // what spl_matrix_spmv_dev launches on this image
 };
 
 // sliced-ELL image of a row block (spmv_sell.hip)
@@ -210,6 +221,14 @@ void segmented_sort_pairs_u32(const int64_t *d_ptr64, int64_t nseg, unsigned *d_
                               hipStream_t s);
 // finish a Matrix whose rowptr64/colidx/val are filled: int32 pointers, stats
 void finalize_matrix(Matrix *m, hipStream_t s);
+// CUs of a device, asked once per device, not per launch; 0 when the runtime refuses
+inline int device_cus(int device) {
+  static std::atomic<int> cus_of[64];
+  int cus = cus_of[device & 63].load(std::memory_order_relaxed);
+  if (cus == 0 && hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device) == hipSuccess)
+    cus_of[device & 63].store(cus, std::memory_order_relaxed);
+  return cus;
+}
 int spmv_cus(const Matrix *m);  // CUs the persistent SpMV images are laid out for: the device's minus the reserved ones
 void measure_locality(Matrix *m, hipStream_t s);  // fills new_line_fraction on first call
 
@@ -315,9 +334,18 @@ void build_blocked_image(Matrix *m, int rows_per_panel, int w, hipStream_t s);
 int launch_spmv_blocked(const Matrix *m, const double *d_x, double *d_y, int accumulate, int unroll,
                         hipStream_t s);
 void build_panel_image(Matrix *m, int rows_per_panel, int w, int pair, hipStream_t s);
-int launch_spmv_panel(const Matrix *m, const double *d_x, double *d_y, int accumulate, hipStream_t s);
+// runs `plan` (PanelImage::plan, or a candidate of the tuner) on m's panel image
+int launch_spmv_panel(const Matrix *m, const PanelPlan &plan, const double *d_x, double *d_y, int accumulate, hipStream_t s);
 size_t panel_ring_lds_bytes(int P, int nl, int slots);
 int panel_ring_errors(const Matrix *m, hipStream_t s);
+// the `form` and `unroll` of spl_matrix_build_panel (SPL_PANEL_FORM_*): known to these functions only
+bool panel_code_valid(int form, int unroll);
+bool panel_code_takes_slices(int form);
+int panel_slices_override();  // SPL_PANEL_SLICES, 0: not set
+PanelPlan panel_plan_from_code(int form, int unroll, int cols_log2, int nslices);
+// the plan for a freshly built image: the code's plan, the register sets sized from the image when unroll is 0,
+// and, for the all-default request on a large matrix (may_tune), the fastest of the heuristic's neighbours
+PanelPlan choose_panel_plan(const Matrix *m, const PanelImage *b, int form, int unroll, int nslices, bool may_tune);
 // choose the blocked image's shape for this matrix (0,0 = blocking would not help)
 void choose_blocking(const Matrix *m, int *rows_per_panel, int *w, int *waves);
 void choose_panels(const Matrix *m, int *rows_per_panel, int *w);

@@ -273,7 +273,7 @@ int launch_spmv(const Matrix *m, const double *d_x, double *d_y, int accumulate,
   }
   if (m->variant == 16 || (m->variant == 0 && m->panel && m->order_free)) {
     if (!m->panel) return SPL_ERROR_argument_missing;
-    return launch_spmv_panel(m, d_x, d_y, accumulate, s);
+    return launch_spmv_panel(m, m->panel->plan, d_x, d_y, accumulate, s);
   }
   if (m->variant == 8 || (m->variant == 0 && m->blocked)) {
     if (!m->blocked) return SPL_ERROR_argument_missing;
@@ -325,8 +325,8 @@ int spmv_kernel_in_use(const Matrix *m) {
 // one-generation row block have exactly CUs - r panels (groups of wavefront panels), the grid is that much
 // smaller, and the dispatcher has free CUs for the other kernel (tools/bench_reserved_cus.py).
 int spmv_cus(const Matrix *m) {
-  int cus = 256;
-  (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, m->device);
+  int cus = device_cus(m->device);
+  if (cus == 0) cus = 256;
   int r = m->reserved_cus;
   if (r < 0) {
     const char *e = getenv("SPL_SPMV_RESERVED_CUS");
@@ -368,17 +368,15 @@ void choose_panels(const Matrix *m, int *rows_per_panel, int *w, int *nslices) {
       ns = best;
     }
   }
-  if (const char *ev = getenv("SPL_PANEL_SLICES")) {
-    const int f = atoi(ev);
-    if (nslices && f >= 1 && f != ns) {  // forced (experiments): panels sized for cus / f workgroups per generation
-      ns = f;
-      const int64_t ppg = cus / f > 0 ? cus / f : 1;
-      int64_t ng = (m->nrows_local + ppg * pmax - 1) / (ppg * pmax);
-      if (ng < 1) ng = 1;
-      P = (m->nrows_local + ng * ppg - 1) / (ng * ppg);
-      if (P < 64) P = 64;
-      if (P > pmax) P = pmax;
-    }
+  const int f = panel_slices_override();
+  if (nslices && f >= 1 && f != ns) {  // forced (experiments): panels sized for cus / f workgroups per generation
+    ns = f;
+    const int64_t ppg = cus / f > 0 ? cus / f : 1;
+    int64_t ng = (m->nrows_local + ppg * pmax - 1) / (ppg * pmax);
+    if (ng < 1) ng = 1;
+    P = (m->nrows_local + ng * ppg - 1) / (ng * ppg);
+    if (P < 64) P = 64;
+    if (P > pmax) P = pmax;
   }
   *rows_per_panel = (int)P;
   if (nslices) *nslices = ns;

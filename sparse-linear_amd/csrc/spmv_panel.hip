@@ -34,7 +34,9 @@
 // gather from together), wavefront i takes chunks i, i+16, ... of the phase, keeps U of them in
 // registers, and the stream of the next phase is requested before the barrier that ends this one.
 #include "common.hpp"
+#include <stdio.h>
 #include <atomic>
+#include <initializer_list>
 
 namespace spl {
 
@@ -141,9 +143,93 @@ __device__ inline void pnl_gather_wait(double &v) {
 __device__ inline void pnl_fold(unsigned id, double prod, double *yp) {
   __builtin_amdgcn_ds_atomic_fadd_f64((__attribute__((address_space(3))) double *)(yp + (id & kRowMask)), prod);
 }
+// The counted waits behind a burst of gathers, oldest first: gather u of a register set array is awaited while
+// First - u younger loads stay in flight (one gather per set), or First - 2u and First - 2u - 1 (two per set, A
+// then B).  The immediates are compile-time constants; vmcnt has six bits on gfx9.
+template <int First, int U, int u = 0>
+__device__ __forceinline__ void pnl_gather_wait_seq(double (&xv)[U]) {
+  static_assert(First <= 63 && First - (U - 1) >= 0, "vmcnt immediate out of range");
+  if constexpr (u < U) {
+    pnl_gather_wait<First - u>(xv[u]);
+    pnl_gather_wait_seq<First, U, u + 1>(xv);
+  }
+}
+template <int First, int U, int u = 0>
+__device__ __forceinline__ void pnl_gather_wait_seq(double (&xa)[U], double (&xb)[U]) {
+  static_assert(First <= 63 && First - (2 * U - 1) >= 0, "vmcnt immediate out of range");
+  if constexpr (u < U) {
+    pnl_gather_wait<First - 2 * u>(xa[u]);
+    pnl_gather_wait<First - 2 * u - 1>(xb[u]);
+    pnl_gather_wait_seq<First, U, u + 1>(xa, xb);
+  }
+}
 
-// One phase: gather + fold this wavefront's chunks of the phase [cs, ce) held in (idC, aC) — chunk
-// u of wavefront i is chunk cs + i + 16 u of the panel's stream — while its chunks of the next
+// ---- the frame every form shares: y of a panel in LDS, the write-back, the rendezvous between generations ----
+// the words of PanelImage::arrive
+constexpr int kArrive = 0;     // workgroups that have finished a generation
+constexpr int kRingError = 1;  // ring form: a bounded wait gave up
+constexpr int kLeft = 2;       // rounds form: workgroups that have left the kernel
+
+// ylds[0, P] (P is the dummy row): the panel's rows of y when accumulating into them, else zero
+__device__ __forceinline__ void panel_stage_y(double *ylds, const double *y, int64_t row_base, int64_t nrows, int P, bool take_y) {
+  for (int i = threadIdx.x; i <= P; i += kPanelWaves * 64)
+    ylds[i] = (take_y && i < P && row_base + i < nrows) ? y[row_base + i] : 0.0;
+}
+// Atomic: the panel's row sums are completed by several workgroups (column slices), global_atomic_add_f64, no return
+template <bool Atomic>
+__device__ __forceinline__ void panel_store_y(const double *ylds, double *y, int64_t row_base, int64_t nrows, int P) {
+  for (int i = threadIdx.x; i < P; i += kPanelWaves * 64)
+    if (row_base + i < nrows) {
+      if constexpr (Atomic) unsafeAtomicAdd(y + row_base + i, ylds[i]);
+      else y[row_base + i] = ylds[i];
+    }
+}
+// re-align the nb workgroups after generation g (bounded, performance only)
+__device__ __forceinline__ void panel_rendezvous(unsigned *arrive, int64_t g, int64_t nb) {
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    __hip_atomic_fetch_add(arrive, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    const unsigned target = (unsigned)((g + 1) * nb);
+    const unsigned long long t0 = wall_clock64();  // 100 MHz
+    while (__hip_atomic_load(arrive, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < target) {
+      if (wall_clock64() - t0 > 20000ull) break;  // 200 us: give up, stay correct
+      __builtin_amdgcn_s_sleep(8);
+    }
+  }
+  __syncthreads();
+}
+
+// A phase of the chunk and the paired form: the K index blocks from ib0 on, of the blocks [.., ibe) this workgroup
+// walks.  Boundaries come from the panel's row `sp` of segc (>> Shift: 0 chunks, 1 pairs), clamped to cend, the end
+// of the workgroup's stream: [cs, ce) the phase, mid[j] the first unit of block ib0 + j + 1, [ce, cn) the next phase.
+// ReadAhead (ibe = nib only: segc carries trailing copies of its last entry): load first, select after — the same
+// values, and what the chunk kernels' scalar registers were sized with (profiles/panel_frame_resources.txt).
+template <int K>
+struct PanelPhaseBounds {
+  int cs, ce, cn;
+  int mid[K > 1 ? K - 1 : 1];
+};
+template <int Shift, bool ReadAhead>
+__device__ __forceinline__ int panel_boundary(const int *sp, int64_t ib, int64_t ibe, int cend) {
+  if constexpr (ReadAhead) { const int t = sp[ib] >> Shift; return (ib < ibe) ? t : cend; }
+  else return (ib < ibe) ? sp[ib] >> Shift : cend;
+}
+template <int K, int Shift, bool ReadAhead>
+__device__ __forceinline__ PanelPhaseBounds<K> panel_phase_bounds(const int *sp, int64_t ib0, int64_t ibe, int cend) {
+  PanelPhaseBounds<K> b;
+#pragma unroll
+  for (int j = 0; j + 1 < K; ++j) {
+    const int t = ReadAhead ? sp[ib0 + j + 1] >> Shift : panel_boundary<Shift, false>(sp, ib0 + j + 1, ibe, cend);
+    b.mid[j] = t < cend ? t : cend;
+  }
+  b.cs = sp[ib0] >> Shift;
+  b.ce = panel_boundary<Shift, ReadAhead>(sp, ib0 + K, ibe, cend);
+  b.cn = panel_boundary<Shift, ReadAhead>(sp, ib0 + 2 * K, ibe, cend);
+  return b;
+}
+
+// One phase, the K index blocks from ib0 on: gather + fold this wavefront's chunks of the phase [cs, ce) held in
+// (idC, aC) — chunk u of wavefront i is chunk cs + i + 16 u of the panel's stream — while its chunks of the next
 // phase (which starts at ce) are loaded into (idN, aN).  mid[j] is the first chunk of index block
 // ib0 + j + 1 (K - 1 of them): the x block a chunk gathers from follows from its position.
 // ABL (timing-only ablations, wrong results; refused unless SPL_ALLOW_ABLATION=1): bit 0 every gather reads
@@ -183,18 +269,7 @@ __device__ inline void panel_phase(unsigned (&idC)[U], double (&aC)[U], unsigned
   }
   __builtin_amdgcn_sched_barrier(0);
   constexpr int Y = ((ABL & 2) ? 2 : 3) * U - 1;  // younger than gather u here: U-1-u gathers + 2U stream loads
-  pnl_gather_wait<Y>(xv[0]);
-  if (U > 1) pnl_gather_wait<Y - 1>(xv[U > 1 ? 1 : 0]);
-  if (U > 2) pnl_gather_wait<Y - 2>(xv[U > 2 ? 2 : 0]);
-  if (U > 3) pnl_gather_wait<Y - 3>(xv[U > 3 ? 3 : 0]);
-  if (U > 4) pnl_gather_wait<Y - 4>(xv[U > 4 ? 4 : 0]);
-  if (U > 5) pnl_gather_wait<Y - 5>(xv[U > 5 ? 5 : 0]);
-  if (U > 6) pnl_gather_wait<Y - 6>(xv[U > 6 ? 6 : 0]);
-  if (U > 7) pnl_gather_wait<Y - 7>(xv[U > 7 ? 7 : 0]);
-  if (U > 8) pnl_gather_wait<Y - 8>(xv[U > 8 ? 8 : 0]);
-  if (U > 9) pnl_gather_wait<Y - 9>(xv[U > 9 ? 9 : 0]);
-  if (U > 10) pnl_gather_wait<Y - 10>(xv[U > 10 ? 10 : 0]);
-  if (U > 11) pnl_gather_wait<Y - 11>(xv[U > 11 ? 11 : 0]);
+  pnl_gather_wait_seq<Y, U>(xv);
 #pragma unroll
   for (int u = 0; u < U; ++u) {
     if (cs + wave + kPanelWaves * u >= ce) break;  // wave-uniform
@@ -239,49 +314,23 @@ __global__ __launch_bounds__(kPanelWaves * 64) void spmv_panel_kernel(
       idA[u] = __builtin_nontemporal_load(key + k);
       aA[u] = __builtin_nontemporal_load(val + k);
     }
-    for (int i = threadIdx.x; i <= P; i += kPanelWaves * 64)
-      ylds[i] = (accumulate && i < P && row_base + i < nrows) ? y[row_base + i] : 0.0;
+    panel_stage_y(ylds, y, row_base, nrows, P, accumulate);
     __syncthreads();
     const int cend = sp[nib];
-    for (int64_t ph = 0; ph < nph; ph += 2) {
+    for (int64_t ph = 0; ph < nph; ph += 2) {  // the two register sets take turns
       {
-        const int64_t ib0 = ph * K;
-        int mid[K > 1 ? K - 1 : 1];
-#pragma unroll
-        for (int j = 0; j + 1 < K; ++j) { const int t = sp[ib0 + j + 1]; mid[j] = t < cend ? t : cend; }
-        const int cs = sp[ib0];
-        int ce = sp[ib0 + K]; ce = (ib0 + K < nib) ? ce : cend;
-        int cn = sp[ib0 + 2 * K]; cn = (ib0 + 2 * K < nib) ? cn : cend;
-        panel_phase<U, K, ABL>(idA, aA, idB, aB, cs, mid, ce, ib0, w, key, val, x, ylds, wave, cn - ce, sink, dummy);
+        const PanelPhaseBounds<K> b = panel_phase_bounds<K, 0, true>(sp, ph * K, nib, cend);
+        panel_phase<U, K, ABL>(idA, aA, idB, aB, b.cs, b.mid, b.ce, ph * K, w, key, val, x, ylds, wave, b.cn - b.ce, sink, dummy);
       }
       if (ph + 1 < nph) {
-        const int64_t ib0 = (ph + 1) * K;
-        int mid[K > 1 ? K - 1 : 1];
-#pragma unroll
-        for (int j = 0; j + 1 < K; ++j) { const int t = sp[ib0 + j + 1]; mid[j] = t < cend ? t : cend; }
-        const int cs = sp[ib0];
-        int ce = sp[ib0 + K]; ce = (ib0 + K < nib) ? ce : cend;
-        int cn = sp[ib0 + 2 * K]; cn = (ib0 + 2 * K < nib) ? cn : cend;
-        panel_phase<U, K, ABL>(idB, aB, idA, aA, cs, mid, ce, ib0, w, key, val, x, ylds, wave, cn - ce, sink, dummy);
+        const PanelPhaseBounds<K> b = panel_phase_bounds<K, 0, true>(sp, (ph + 1) * K, nib, cend);
+        panel_phase<U, K, ABL>(idB, aB, idA, aA, b.cs, b.mid, b.ce, (ph + 1) * K, w, key, val, x, ylds, wave, b.cn - b.ce, sink, dummy);
       }
     }
     if (ABL && sink == 1.2345e-300) ylds[0] = sink;  // keeps the ablated arithmetic alive
     __syncthreads();  // every wavefront's LDS adds are done (s_barrier above does not wait for lgkmcnt)
-    for (int i = threadIdx.x; i < P; i += kPanelWaves * 64)
-      if (row_base + i < nrows) y[row_base + i] = ylds[i];
-    if (g + 1 < ngen) {  // re-align the CUs between generations (bounded, performance only)
-      __syncthreads();
-      if (threadIdx.x == 0) {
-        __hip_atomic_fetch_add(arrive, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        const unsigned target = (unsigned)((g + 1) * nb);
-        const unsigned long long t0 = wall_clock64();  // 100 MHz
-        while (__hip_atomic_load(arrive, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < target) {
-          if (wall_clock64() - t0 > 20000ull) break;  // 200 us: give up, stay correct
-          __builtin_amdgcn_s_sleep(8);
-        }
-      }
-      __syncthreads();
-    }
+    panel_store_y<false>(ylds, y, row_base, nrows, P);
+    if (g + 1 < ngen) panel_rendezvous(arrive + kArrive, g, nb);
   }
 }
 
@@ -331,17 +380,7 @@ __device__ inline void panelw_phase(pnl_u2 (&idC)[U], pnl_d2 (&aC)[U], pnl_u2 (&
   }
   __builtin_amdgcn_sched_barrier(0);
   // younger than gather j (j = 2u for A, 2u + 1 for B) here: 2U-1-j gathers + 2U stream loads
-#pragma unroll
-  for (int u = 0; u < U; ++u) {
-    if (u == 0) { pnl_gather_wait<4 * U - 1>(xa[u]); pnl_gather_wait<4 * U - 2>(xb[u]); }
-    if (u == 1) { pnl_gather_wait<4 * U - 3>(xa[u]); pnl_gather_wait<4 * U - 4>(xb[u]); }
-    if (u == 2) { pnl_gather_wait<(4 * U - 5 > 0 ? 4 * U - 5 : 0)>(xa[u]); pnl_gather_wait<(4 * U - 6 > 0 ? 4 * U - 6 : 0)>(xb[u]); }
-    if (u == 3) { pnl_gather_wait<(4 * U - 7 > 0 ? 4 * U - 7 : 0)>(xa[u]); pnl_gather_wait<(4 * U - 8 > 0 ? 4 * U - 8 : 0)>(xb[u]); }
-    if (u == 4) { pnl_gather_wait<(4 * U - 9 > 0 ? 4 * U - 9 : 0)>(xa[u]); pnl_gather_wait<(4 * U - 10 > 0 ? 4 * U - 10 : 0)>(xb[u]); }
-    if (u == 5) { pnl_gather_wait<(4 * U - 11 > 0 ? 4 * U - 11 : 0)>(xa[u]); pnl_gather_wait<(4 * U - 12 > 0 ? 4 * U - 12 : 0)>(xb[u]); }
-    if (u == 6) { pnl_gather_wait<(4 * U - 13 > 0 ? 4 * U - 13 : 0)>(xa[u]); pnl_gather_wait<(4 * U - 14 > 0 ? 4 * U - 14 : 0)>(xb[u]); }
-    if (u == 7) { pnl_gather_wait<(4 * U - 15 > 0 ? 4 * U - 15 : 0)>(xa[u]); pnl_gather_wait<(4 * U - 16 > 0 ? 4 * U - 16 : 0)>(xb[u]); }
-  }
+  pnl_gather_wait_seq<4 * U - 1, U>(xa, xb);
 #pragma unroll
   for (int u = 0; u < U; ++u) {
     if (cs + wave + kPanelWaves * u >= ce) break;  // wave-uniform
@@ -404,52 +443,22 @@ __global__ __launch_bounds__(kPanelWaves * 64) void spmv_panelw_kernel(
       idA[u] = __builtin_nontemporal_load(key2 + k);
       aA[u] = __builtin_nontemporal_load(val2 + k);
     }
-    for (int i = threadIdx.x; i <= P; i += kPanelWaves * 64)
-      ylds[i] = (ns == 1 && accumulate && i < P && row_base + i < nrows) ? y[row_base + i] : 0.0;
+    panel_stage_y(ylds, y, row_base, nrows, P, ns == 1 && accumulate);
     __syncthreads();
-    for (int64_t ph = 0; ph < nph; ph += 2) {
+    for (int64_t ph = 0; ph < nph; ph += 2) {  // the two register sets take turns
       {
-        const int64_t ib0 = ibs + ph * K;
-        int mid[K > 1 ? K - 1 : 1];
-#pragma unroll
-        for (int j = 0; j + 1 < K; ++j) { const int t = (ib0 + j + 1 < ibe) ? sp[ib0 + j + 1] >> 1 : cend; mid[j] = t < cend ? t : cend; }
-        const int cs = sp[ib0] >> 1;
-        const int ce = (ib0 + K < ibe) ? sp[ib0 + K] >> 1 : cend;
-        const int cn = (ib0 + 2 * K < ibe) ? sp[ib0 + 2 * K] >> 1 : cend;
-        panelw_phase<U, K>(idA, aA, idB, aB, cs, mid, ce, ib0, w, key2, val2, x, ylds, wave, cn, dummy);
+        const PanelPhaseBounds<K> b = panel_phase_bounds<K, 1, false>(sp, ibs + ph * K, ibe, cend);
+        panelw_phase<U, K>(idA, aA, idB, aB, b.cs, b.mid, b.ce, ibs + ph * K, w, key2, val2, x, ylds, wave, b.cn, dummy);
       }
       if (ph + 1 < nph) {
-        const int64_t ib0 = ibs + (ph + 1) * K;
-        int mid[K > 1 ? K - 1 : 1];
-#pragma unroll
-        for (int j = 0; j + 1 < K; ++j) { const int t = (ib0 + j + 1 < ibe) ? sp[ib0 + j + 1] >> 1 : cend; mid[j] = t < cend ? t : cend; }
-        const int cs = sp[ib0] >> 1;
-        const int ce = (ib0 + K < ibe) ? sp[ib0 + K] >> 1 : cend;
-        const int cn = (ib0 + 2 * K < ibe) ? sp[ib0 + 2 * K] >> 1 : cend;
-        panelw_phase<U, K>(idB, aB, idA, aA, cs, mid, ce, ib0, w, key2, val2, x, ylds, wave, cn, dummy);
+        const PanelPhaseBounds<K> b = panel_phase_bounds<K, 1, false>(sp, ibs + (ph + 1) * K, ibe, cend);
+        panelw_phase<U, K>(idB, aB, idA, aA, b.cs, b.mid, b.ce, ibs + (ph + 1) * K, w, key2, val2, x, ylds, wave, b.cn, dummy);
       }
     }
     __syncthreads();
-    if (ns == 1) {
-      for (int i = threadIdx.x; i < P; i += kPanelWaves * 64)
-        if (row_base + i < nrows) y[row_base + i] = ylds[i];
-    } else {
-      for (int i = threadIdx.x; i < P; i += kPanelWaves * 64)
-        if (row_base + i < nrows) unsafeAtomicAdd(y + row_base + i, ylds[i]);  // global_atomic_add_f64, no return
-    }
-    if (g + 1 < ngen) {
-      __syncthreads();
-      if (threadIdx.x == 0) {
-        __hip_atomic_fetch_add(arrive, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        const unsigned target = (unsigned)((g + 1) * nb);
-        const unsigned long long t0 = wall_clock64();
-        while (__hip_atomic_load(arrive, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < target) {
-          if (wall_clock64() - t0 > 20000ull) break;
-          __builtin_amdgcn_s_sleep(8);
-        }
-      }
-      __syncthreads();
-    }
+    if (ns == 1) panel_store_y<false>(ylds, y, row_base, nrows, P);
+    else panel_store_y<true>(ylds, y, row_base, nrows, P);
+    if (g + 1 < ngen) panel_rendezvous(arrive + kArrive, g, nb);
   }
 }
 
@@ -516,15 +525,7 @@ __device__ inline void panelq_round(pnl_u2 (&idC)[U], pnl_d2 (&aC)[U], int (&ibC
   panelq_blocks_issue<U>(ibN, ublk + c0 + mn);  // the table carries slack behind the last unit
   __builtin_amdgcn_sched_barrier(0);
   // younger than gather j (j = 2u for A, 2u + 1 for B) here: 2U-1-j gathers + 2U stream loads
-#pragma unroll
-  for (int u = 0; u < U; ++u) {
-    if (u == 0) { pnl_gather_wait<4 * U - 1>(xa[u]); pnl_gather_wait<4 * U - 2>(xb[u]); }
-    if (u == 1) { pnl_gather_wait<4 * U - 3>(xa[u]); pnl_gather_wait<4 * U - 4>(xb[u]); }
-    if (u == 2) { pnl_gather_wait<4 * U - 5>(xa[u]); pnl_gather_wait<4 * U - 6>(xb[u]); }
-    if (u == 3) { pnl_gather_wait<(4 * U - 7 > 0 ? 4 * U - 7 : 0)>(xa[u]); pnl_gather_wait<(4 * U - 8 > 0 ? 4 * U - 8 : 0)>(xb[u]); }
-    if (u == 4) { pnl_gather_wait<(4 * U - 9 > 0 ? 4 * U - 9 : 0)>(xa[u]); pnl_gather_wait<(4 * U - 10 > 0 ? 4 * U - 10 : 0)>(xb[u]); }
-    if (u == 5) { pnl_gather_wait<(4 * U - 11 > 0 ? 4 * U - 11 : 0)>(xa[u]); pnl_gather_wait<(4 * U - 12 > 0 ? 4 * U - 12 : 0)>(xb[u]); }
-  }
+  pnl_gather_wait_seq<4 * U - 1, U>(xa, xb);
   panelq_blocks_wait<U>(ibN);
 #pragma unroll
   for (int u = 0; u < U; ++u) {
@@ -535,9 +536,9 @@ __device__ inline void panelq_round(pnl_u2 (&idC)[U], pnl_d2 (&aC)[U], int (&ibC
   __builtin_amdgcn_s_barrier();  // pacing only: no fence, vector memory stays in flight
 }
 
-// arrive[0]: rendezvous between generations, arrive[2]: workgroups that have left.  The last one to leave puts
-// both back to zero, so a stream of launches holds nothing but this kernel (the other forms clear arrive[0]
-// with a memset in front of every launch).
+// arrive[kArrive]: rendezvous between generations, arrive[kLeft]: workgroups that have left.  The last one to leave
+// puts both back to zero, so a stream of launches holds nothing but this kernel (the other forms clear
+// arrive[kArrive] with a memset in front of every launch).
 template <int U>
 __global__ __launch_bounds__(kPanelWaves * 64) void spmv_panelq_kernel(
     int64_t nrows, int64_t npanels, int P, int w, int64_t nib, const int *__restrict__ segc,
@@ -571,8 +572,7 @@ __global__ __launch_bounds__(kPanelWaves * 64) void spmv_panelq_kernel(
     }
     panelq_blocks_issue<U>(ibA, ublk + c0 + wave);
     panelq_blocks_wait<U>(ibA);
-    for (int i = threadIdx.x; i <= P; i += kPanelWaves * 64)
-      ylds[i] = (accumulate && i < P && row_base + i < nrows) ? y[row_base + i] : 0.0;
+    panel_stage_y(ylds, y, row_base, nrows, P, accumulate);
     __syncthreads();
     for (int m0 = 0; m0 < nu; m0 += 2 * kRound) {
       panelq_round<U>(idA, aA, ibA, idB, aB, ibB, m0, nu, c0, w, key2, val2, ublk, x, ylds, wave, dummy);
@@ -580,27 +580,14 @@ __global__ __launch_bounds__(kPanelWaves * 64) void spmv_panelq_kernel(
         panelq_round<U>(idB, aB, ibB, idA, aA, ibA, m0 + kRound, nu, c0, w, key2, val2, ublk, x, ylds, wave, dummy);
     }
     __syncthreads();  // every wavefront's LDS adds are done (s_barrier above does not wait for lgkmcnt)
-    for (int i = threadIdx.x; i < P; i += kPanelWaves * 64)
-      if (row_base + i < nrows) y[row_base + i] = ylds[i];
-    if (g + 1 < ngen) {  // re-align the CUs between generations (bounded, performance only)
-      __syncthreads();
-      if (threadIdx.x == 0) {
-        __hip_atomic_fetch_add(arrive, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        const unsigned target = (unsigned)((g + 1) * nb);
-        const unsigned long long t0 = wall_clock64();  // 100 MHz
-        while (__hip_atomic_load(arrive, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < target) {
-          if (wall_clock64() - t0 > 20000ull) break;  // 200 us: give up, stay correct
-          __builtin_amdgcn_s_sleep(8);
-        }
-      }
-      __syncthreads();
-    }
+    panel_store_y<false>(ylds, y, row_base, nrows, P);
+    if (g + 1 < ngen) panel_rendezvous(arrive + kArrive, g, nb);
   }
   // leave: whoever arrives last knows that nobody will touch the rendezvous word again in this launch
   if (threadIdx.x == 0 &&
-      __hip_atomic_fetch_add(arrive + 2, 1u, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_AGENT) == (unsigned)nb - 1u) {
-    __hip_atomic_store(arrive, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    __hip_atomic_store(arrive + 2, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      __hip_atomic_fetch_add(arrive + kLeft, 1u, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_AGENT) == (unsigned)nb - 1u) {
+    __hip_atomic_store(arrive + kArrive, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    __hip_atomic_store(arrive + kLeft, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
   }
 }
 
@@ -675,8 +662,7 @@ __global__ __launch_bounds__(kPanelWaves * 64) void spmv_panelr_kernel(
     const int *sp = segc + p * nib;  // in chunks; every boundary is even (whole pairs)
     const int c0 = sp[0] >> 1;
     const int nu = (sp[nib] >> 1) - c0;  // units (pairs of chunks) of this panel
-    for (int i = threadIdx.x; i <= P; i += kPanelWaves * 64)
-      ylds[i] = (accumulate && i < P && row_base + i < nrows) ? y[row_base + i] : 0.0;
+    panel_stage_y(ylds, y, row_base, nrows, P, accumulate);
     if (threadIdx.x < NL * S) { pnl_u2 z = {0u, 0u}; hdr[threadIdx.x] = z; }
     __syncthreads();
     int bar_done = 0;
@@ -707,7 +693,7 @@ __global__ __launch_bounds__(kPanelWaves * 64) void spmv_panelr_kernel(
           unsigned spins = 0;
           while (__builtin_amdgcn_readfirstlane(hdr[sl].x) != 0u) {  // the slot still holds an earlier unit
             __builtin_amdgcn_s_sleep(1);
-            if (++spins > kRingSpinLimit) { ring_fail(arrive + 1); break; }
+            if (++spins > kRingSpinLimit) { ring_fail(arrive + kRingError); break; }
           }
           lds_char *slot = ring + sl * kRingUnitBytes;
           ring_stream_wait<2 * (D - 1)>(kr[d], vr[d]);  // D - 1 younger units stay in flight
@@ -755,7 +741,7 @@ __global__ __launch_bounds__(kPanelWaves * 64) void spmv_panelr_kernel(
             h = hdr[sl];
             if (__builtin_amdgcn_readfirstlane(h.x) == (unsigned)(t + 1)) break;
             __builtin_amdgcn_s_sleep(1);
-            if (++spins > kRingSpinLimit) { ring_fail(arrive + 1); break; }
+            if (++spins > kRingSpinLimit) { ring_fail(arrive + kRingError); break; }
           }
           const int ib = __builtin_amdgcn_readfirstlane(h.y);
           const lds_char *slot = ring + sl * kRingUnitBytes;
@@ -789,21 +775,8 @@ __global__ __launch_bounds__(kPanelWaves * 64) void spmv_panelr_kernel(
     }
     while (bar_done < nph) { __builtin_amdgcn_s_barrier(); ++bar_done; }
     __syncthreads();
-    for (int i = threadIdx.x; i < P; i += kPanelWaves * 64)
-      if (row_base + i < nrows) y[row_base + i] = ylds[i];
-    if (g + 1 < ngen) {
-      __syncthreads();
-      if (threadIdx.x == 0) {
-        __hip_atomic_fetch_add(arrive, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        const unsigned target = (unsigned)((g + 1) * nb);
-        const unsigned long long t0 = wall_clock64();
-        while (__hip_atomic_load(arrive, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < target) {
-          if (wall_clock64() - t0 > 20000ull) break;
-          __builtin_amdgcn_s_sleep(8);
-        }
-      }
-      __syncthreads();
-    }
+    panel_store_y<false>(ylds, y, row_base, nrows, P);
+    if (g + 1 < ngen) panel_rendezvous(arrive + kArrive, g, nb);
   }
 }
 
@@ -882,102 +855,148 @@ void build_panel_image(Matrix *m, int P, int w, int pair, hipStream_t s) {
   m->panel = b.release();
 }
 
-template <int U, int K, int ABL = 0>
-static void launch_panel_as(const Matrix *m, const PanelImage *b, unsigned nb, size_t lds, const double *d_x,
-                            double *d_y, int accumulate, hipStream_t s) {
-  static std::atomic<uint64_t> set_{0};  // bit d: attribute set on device d (it is per device)
-  if (!(set_.load(std::memory_order_acquire) >> (m->device & 63) & 1u)) {
-    SPL_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&spmv_panel_kernel<U, K, ABL>),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    set_.fetch_or(1ull << (m->device & 63), std::memory_order_release);
+// ---- the launch plan --------------------------------------------------------------------------------
+// One kernel launcher for every form: the dynamic-LDS attribute is per kernel and per device.
+template <auto Kernel, class... Args>
+static void launch_panel_kernel(int device, unsigned grid, size_t lds, hipStream_t s, Args... args) {
+  static std::atomic<uint64_t> set_{0};  // bit d: attribute set on device d
+  if (!(set_.load(std::memory_order_acquire) >> (device & 63) & 1u)) {
+    SPL_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(Kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                160 * 1024));
+    set_.fetch_or(1ull << (device & 63), std::memory_order_release);
   }
-  hipLaunchKernelGGL((spmv_panel_kernel<U, K, ABL>), dim3(nb), dim3(kPanelWaves * 64), lds, s, m->nrows_local,
-                     b->npanels, b->P, b->w, b->nib, b->segc.get(), b->key.get(), b->val.get(), d_x, d_y,
-                     accumulate, b->arrive.get(), (int64_t)b->nchunks << 6);
-}
-
-template <int U, int K>
-static void launch_panelw_as(const Matrix *m, const PanelImage *b, unsigned nb, size_t lds, const double *d_x,
-                             double *d_y, int accumulate, hipStream_t s) {
-  static std::atomic<uint64_t> set_{0};
-  if (!(set_.load(std::memory_order_acquire) >> (m->device & 63) & 1u)) {
-    SPL_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&spmv_panelw_kernel<U, K>),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    set_.fetch_or(1ull << (m->device & 63), std::memory_order_release);
-  }
-  const int ns = b->nslices > 1 ? b->nslices : 1;
-  if (ns > 1 && !accumulate) SPL_HIP(hipMemsetAsync(d_y, 0, (size_t)m->nrows_local * sizeof(double), s));
-  hipLaunchKernelGGL((spmv_panelw_kernel<U, K>), dim3(nb), dim3(kPanelWaves * 64), lds, s, m->nrows_local, b->npanels,
-                     b->P, b->w, b->nib, b->segc.get(), b->key.get(), b->val.get(), d_x, d_y, accumulate,
-                     b->arrive.get(), (int64_t)(b->nchunks / 2) << 6, ns);
-}
-
-
-template <int U>
-static void launch_panelq_as(const Matrix *m, const PanelImage *b, unsigned nb, size_t lds, const double *d_x,
-                             double *d_y, int accumulate, hipStream_t s) {
-  static std::atomic<uint64_t> set_{0};
-  if (!(set_.load(std::memory_order_acquire) >> (m->device & 63) & 1u)) {
-    SPL_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&spmv_panelq_kernel<U>),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    set_.fetch_or(1ull << (m->device & 63), std::memory_order_release);
-  }
-  hipLaunchKernelGGL((spmv_panelq_kernel<U>), dim3(nb), dim3(kPanelWaves * 64), lds, s, m->nrows_local, b->npanels,
-                     b->P, b->w, b->nib, b->segc.get(), b->ublk.get(), b->key.get(), b->val.get(), d_x, d_y, accumulate,
-                     b->arrive.get(), (int64_t)(b->nchunks / 2) << 6);
+  hipLaunchKernelGGL(Kernel, dim3(grid), dim3(kPanelWaves * 64), lds, s, args...);
 }
 
 size_t panel_ring_lds_bytes(int P, int nl, int slots) {
   return ((((size_t)P + 1) * sizeof(double) + 15) & ~(size_t)15) + (size_t)nl * slots * (kRingUnitBytes + 8);
 }
 
+namespace {
+
+constexpr size_t kPanelLdsLimit = 160 * 1024;
+
+struct PanelLaunchArgs { const Matrix *m; const PanelImage *b; unsigned nb; const double *x; double *y; int accumulate; hipStream_t s; };
+
+inline size_t panel_lds_bytes(const PanelImage *b) { return ((size_t)b->P + 1) * sizeof(double); }
+inline void clear_word(const PanelLaunchArgs &a, int word) {
+  SPL_HIP(hipMemsetAsync(a.b->arrive.get() + word, 0, sizeof(unsigned), a.s));
+}
+// the chunk, paired and ring kernels take the same arguments up to `arrive`; tail: the dummy unit behind the stream, ...
+template <auto Kernel, class... Tail>
+void launch_on_image(const PanelLaunchArgs &a, size_t lds, Tail... tail) {
+  const PanelImage *b = a.b;
+  launch_panel_kernel<Kernel>(a.m->device, a.nb, lds, a.s, a.m->nrows_local, b->npanels, b->P, b->w, b->nib, b->segc.get(),
+                              b->key.get(), b->val.get(), a.x, a.y, a.accumulate, b->arrive.get(), tail...);
+}
+// what each form puts on the stream besides its kernel is written here, once per form
+template <int U, int K, int ABL>
+void run_chunk(const PanelLaunchArgs &a, const PanelPlan &) {
+  clear_word(a, kArrive);
+  launch_on_image<&spmv_panel_kernel<U, K, ABL>>(a, panel_lds_bytes(a.b), (int64_t)a.b->nchunks << 6);
+}
+template <int U, int K>
+void run_paired(const PanelLaunchArgs &a, const PanelPlan &plan) {
+  clear_word(a, kArrive);
+  if (plan.nslices > 1 && !a.accumulate)  // the slices of a panel add their parts into y
+    SPL_HIP(hipMemsetAsync(a.y, 0, (size_t)a.m->nrows_local * sizeof(double), a.s));
+  launch_on_image<&spmv_panelw_kernel<U, K>>(a, panel_lds_bytes(a.b), (int64_t)(a.b->nchunks / 2) << 6, plan.nslices);
+}
+template <int U>
+void run_rounds(const PanelLaunchArgs &a, const PanelPlan &) {  // the kernel itself puts the rendezvous word back
+  const PanelImage *b = a.b;
+  launch_panel_kernel<&spmv_panelq_kernel<U>>(a.m->device, a.nb, panel_lds_bytes(b), a.s, a.m->nrows_local, b->npanels, b->P, b->w,
+                                              b->nib, b->segc.get(), b->ublk.get(), b->key.get(), b->val.get(), a.x, a.y,
+                                              a.accumulate, b->arrive.get(), (int64_t)(b->nchunks / 2) << 6);
+}
 template <int NL, int D, int GD, int K, int S>
-static void launch_panelr_as(const Matrix *m, const PanelImage *b, unsigned nb, const double *d_x, double *d_y,
-                             int accumulate, hipStream_t s) {
-  static std::atomic<uint64_t> set_{0};
-  if (!(set_.load(std::memory_order_acquire) >> (m->device & 63) & 1u)) {
-    SPL_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&spmv_panelr_kernel<NL, D, GD, K, S>),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    set_.fetch_or(1ull << (m->device & 63), std::memory_order_release);
-  }
-  hipLaunchKernelGGL((spmv_panelr_kernel<NL, D, GD, K, S>), dim3(nb), dim3(kPanelWaves * 64),
-                     panel_ring_lds_bytes(b->P, NL, S), s, m->nrows_local, b->npanels, b->P, b->w, b->nib, b->segc.get(),
-                     b->key.get(), b->val.get(), d_x, d_y, accumulate, b->arrive.get(), (int64_t)(b->nchunks / 2) << 6);
+void run_ring(const PanelLaunchArgs &a, const PanelPlan &) {
+  clear_word(a, kArrive);
+  clear_word(a, kRingError);
+  launch_on_image<&spmv_panelr_kernel<NL, D, GD, K, S>>(a, panel_ring_lds_bytes(a.b->P, NL, S), (int64_t)(a.b->nchunks / 2) << 6);
 }
 
-static int launch_panel_ring(const Matrix *m, const PanelImage *b, unsigned nb, const double *d_x, double *d_y,
-                             int accumulate, hipStream_t s) {
-  if (!b->pair) return SPL_ERROR_internal;
-  const int nl = b->ring_nl, S = b->ring_slots, D = b->ring_depth, GD = b->ring_gather, K = b->kblocks;
-  if (panel_ring_lds_bytes(b->P, nl, S) > 160 * 1024) return SPL_ERROR_argument_missing;
-  SPL_HIP(hipMemsetAsync(b->arrive.get() + 1, 0, sizeof(unsigned), s));
-#define SPL_RING(NLv, Dv, GDv, Kv, Sv) \
-  if (nl == NLv && D == Dv && GD == GDv && K == Kv && S == Sv) { launch_panelr_as<NLv, Dv, GDv, Kv, Sv>(m, b, nb, d_x, d_y, accumulate, s); launched = true; }
-  bool launched = false;
-  // only shapes that compile without scratch: a spilled register with a gather still in flight would be stale
-  SPL_RING(4, 4, 4, 2, 1) SPL_RING(4, 6, 4, 2, 1) SPL_RING(4, 8, 4, 2, 1) SPL_RING(4, 6, 3, 2, 1)
-  SPL_RING(4, 6, 4, 1, 1) SPL_RING(4, 6, 4, 2, 3) SPL_RING(4, 4, 3, 2, 1) SPL_RING(4, 5, 4, 2, 1)
-  SPL_RING(2, 8, 2, 2, 1) SPL_RING(8, 3, 4, 2, 1) SPL_RING(8, 4, 4, 2, 1)
-  SPL_RING(4, 6, 4, 3, 1) SPL_RING(4, 6, 4, 4, 1) SPL_RING(4, 6, 4, 3, 3) SPL_RING(4, 6, 4, 4, 3) SPL_RING(4, 4, 4, 2, 3)
-  SPL_RING(4, 6, 3, 2, 3) SPL_RING(4, 6, 4, 1, 3) SPL_RING(4, 4, 4, 4, 1) SPL_RING(4, 4, 4, 3, 1) SPL_RING(8, 4, 4, 4, 1)
-  SPL_RING(8, 4, 4, 2, 2) SPL_RING(4, 4, 4, 8, 1) SPL_RING(4, 6, 4, 8, 1)
-#undef SPL_RING
-  if (!launched) return SPL_ERROR_argument_missing;
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) { set_last_error("spmv_panelr launch", e); return SPL_ERROR_device; }
-  return SPL_OK;
+// The table of instantiations: a plan runs iff normalise() maps it to one of these.  (nslices is a launch
+// argument of the paired kernels, not an instantiation.)
+struct PanelKernel {
+  PanelForm form;
+  int sets, kblocks, ablate, nl, gather, slots;
+  void (*run)(const PanelLaunchArgs &, const PanelPlan &);
+  const char *where;
+};
+template <int U, int K, int ABL = 0>
+constexpr PanelKernel chunk() {
+  return {PanelForm::Chunk, U, K, ABL, 0, 0, 0, &run_chunk<U, K, ABL>, ABL ? "spmv_panel ablation launch" : "spmv_panel launch"};
 }
+template <int U, int K>
+constexpr PanelKernel paired() { return {PanelForm::Paired, U, K, 0, 0, 0, 0, &run_paired<U, K>, "spmv_panelw launch"}; }
+template <int U>
+constexpr PanelKernel rounds() { return {PanelForm::Rounds, U, 0, 0, 0, 0, 0, &run_rounds<U>, "spmv_panelq launch"}; }
+template <int NL, int D, int GD, int K, int S>
+constexpr PanelKernel ring() {
+  return {PanelForm::Ring, D, K, 0, NL, GD, S, &run_ring<NL, D, GD, K, S>, "spmv_panelr launch"};
+}
+const PanelKernel kPanelKernels[] = {
+    rounds<3>(), rounds<4>(), rounds<5>(), rounds<6>(),
+    paired<2, 1>(), paired<3, 1>(), paired<4, 1>(), paired<3, 2>(), paired<4, 2>(), paired<5, 2>(), paired<6, 2>(),
+    chunk<4, 1>(), chunk<6, 1>(), chunk<8, 1>(), chunk<10, 1>(), chunk<12, 1>(),
+    chunk<4, 2>(), chunk<6, 2>(), chunk<8, 2>(), chunk<10, 2>(), chunk<12, 2>(),
+    // timing-only (wrong results): the two-stage kernel, 12 chunks, 2 blocks per phase
+    chunk<12, 2, 1>(), chunk<12, 2, 2>(), chunk<12, 2, 3>(), chunk<12, 2, 4>(), chunk<12, 2, 5>(), chunk<12, 2, 6>(),
+    chunk<12, 2, 7>(),
+    // ring (loaders, loader depth, gatherer depth, blocks per phase, slots): only shapes that compile without
+    // scratch — a spilled register with a gather still in flight would be stale
+    ring<4, 4, 4, 2, 1>(), ring<4, 6, 4, 2, 1>(), ring<4, 8, 4, 2, 1>(), ring<4, 6, 3, 2, 1>(), ring<4, 6, 4, 1, 1>(),
+    ring<4, 6, 4, 2, 3>(), ring<4, 4, 3, 2, 1>(), ring<4, 5, 4, 2, 1>(), ring<2, 8, 2, 2, 1>(), ring<8, 3, 4, 2, 1>(),
+    ring<8, 4, 4, 2, 1>(), ring<4, 6, 4, 3, 1>(), ring<4, 6, 4, 4, 1>(), ring<4, 6, 4, 3, 3>(), ring<4, 6, 4, 4, 3>(),
+    ring<4, 4, 4, 2, 3>(), ring<4, 6, 3, 2, 3>(), ring<4, 6, 4, 1, 3>(), ring<4, 4, 4, 4, 1>(), ring<4, 4, 4, 3, 1>(),
+    ring<8, 4, 4, 4, 1>(), ring<8, 4, 4, 2, 2>(), ring<4, 4, 4, 8, 1>(), ring<4, 6, 4, 8, 1>()};
+
+// A request between the instantiated register counts is served by a fixed neighbour, and fields the form does
+// not use are dropped; rounds and ring requests are left alone (no entry in the table: the launch refuses).
+PanelPlan normalise(PanelPlan p) {
+  const auto one_of = [](int v, std::initializer_list<int> ok) { for (int o : ok) if (v == o) return true; return false; };
+  switch (p.form) {
+    case PanelForm::Chunk:
+      p.kblocks = p.kblocks == 1 ? 1 : 2;
+      if (!one_of(p.sets, {4, 6, 8, 10})) p.sets = 12;
+      if (p.ablate) { p.sets = 12; p.kblocks = 2; }
+      break;
+    case PanelForm::Paired:
+      p.kblocks = p.kblocks == 1 ? 1 : 2;
+      if (p.kblocks == 1 && !one_of(p.sets, {2, 4})) p.sets = 3;
+      if (p.kblocks == 2 && !one_of(p.sets, {3, 4, 5})) p.sets = 6;
+      break;
+    case PanelForm::Rounds: p.kblocks = 0; break;
+    case PanelForm::Ring: break;
+  }
+  if (p.form != PanelForm::Chunk) p.ablate = 0;
+  if (p.form != PanelForm::Paired) p.nslices = 1;
+  if (p.form != PanelForm::Ring) p.nl = p.gather = p.slots = 0;
+  return p;
+}
+
+const PanelKernel *find_panel_kernel(const PanelPlan &p) {  // p normalised
+  for (const PanelKernel &k : kPanelKernels)
+    if (k.form == p.form && k.sets == p.sets && k.kblocks == p.kblocks && k.ablate == p.ablate && k.nl == p.nl &&
+        k.gather == p.gather && k.slots == p.slots)
+      return &k;
+  return nullptr;
+}
+
+}  // namespace
 
 int panel_ring_errors(const Matrix *m, hipStream_t s) {
   const PanelImage *b = m->panel;
   if (!b || !b->arrive.get()) return 0;
   unsigned e = 0;
-  SPL_HIP(hipMemcpyAsync(&e, b->arrive.get() + 1, sizeof(unsigned), hipMemcpyDeviceToHost, s));
+  SPL_HIP(hipMemcpyAsync(&e, b->arrive.get() + kRingError, sizeof(unsigned), hipMemcpyDeviceToHost, s));
   SPL_HIP(hipStreamSynchronize(s));
   return (int)e;
 }
 
-int launch_spmv_panel(const Matrix *m, const double *d_x, double *d_y, int accumulate, hipStream_t s) {
+int launch_spmv_panel(const Matrix *m, const PanelPlan &requested, const double *d_x, double *d_y, int accumulate,
+                      hipStream_t s) {
   const PanelImage *b = m->panel;
   if (!b) return SPL_ERROR_internal;
   if (b->npanels == 0) return SPL_OK;
@@ -985,88 +1004,152 @@ int launch_spmv_panel(const Matrix *m, const double *d_x, double *d_y, int accum
     if (!accumulate) SPL_HIP(hipMemsetAsync(d_y, 0, (size_t)m->nrows_local * sizeof(double), s));
     return SPL_OK;
   }
-  const size_t lds = ((size_t)b->P + 1) * sizeof(double);
-  if (lds > 160 * 1024) return SPL_ERROR_argument_missing;
-  static std::atomic<int> cus_of[64];  // CUs of device d: asked once, not per launch
-  int cus = cus_of[m->device & 63].load(std::memory_order_relaxed);
-  if (cus == 0) {
-    SPL_HIP(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, m->device));
-    cus_of[m->device & 63].store(cus, std::memory_order_relaxed);
-  }
+  if (panel_lds_bytes(b) > kPanelLdsLimit) return SPL_ERROR_argument_missing;
+  const PanelPlan plan = normalise(requested);
+  // every form but the chunk form reads the paired storage, the rounds form its unit table too
+  if ((plan.form != PanelForm::Chunk) != (b->pair != 0)) return SPL_ERROR_internal;
+  if (plan.form == PanelForm::Rounds && !b->ublk.get()) return SPL_ERROR_internal;
+  if (plan.form == PanelForm::Ring && panel_ring_lds_bytes(b->P, plan.nl, plan.slots) > kPanelLdsLimit)
+    return SPL_ERROR_argument_missing;
+  const PanelKernel *k = find_panel_kernel(plan);
+  if (!k) return SPL_ERROR_argument_missing;
+  const int cus = device_cus(m->device);
+  if (cus == 0) { set_last_error_text("hipDeviceGetAttribute(MultiprocessorCount) failed"); return SPL_ERROR_device; }
   int64_t nb = cus;
-  const int64_t tasks = b->npanels * (b->nslices > 1 && b->pair && !b->ring && !b->rounds ? b->nslices : 1);
+  const int64_t tasks = b->npanels * plan.nslices;
   if (nb > tasks) nb = tasks;
-  if (b->rounds) {  // the kernel itself puts the rendezvous word back: nothing else goes on the stream
-    if (!b->pair || !b->ublk.get()) return SPL_ERROR_internal;
-    switch (b->unroll) {
-      case 3: launch_panelq_as<3>(m, b, (unsigned)nb, lds, d_x, d_y, accumulate, s); break;
-      case 4: launch_panelq_as<4>(m, b, (unsigned)nb, lds, d_x, d_y, accumulate, s); break;
-      case 5: launch_panelq_as<5>(m, b, (unsigned)nb, lds, d_x, d_y, accumulate, s); break;
-      case 6: launch_panelq_as<6>(m, b, (unsigned)nb, lds, d_x, d_y, accumulate, s); break;
-      default: return SPL_ERROR_argument_missing;
-    }
-    hipError_t eq = hipGetLastError();
-    if (eq != hipSuccess) { set_last_error("spmv_panelq launch", eq); return SPL_ERROR_device; }
-    return SPL_OK;
-  }
-  SPL_HIP(hipMemsetAsync(b->arrive.get(), 0, sizeof(unsigned), s));
-  if (b->ring) return launch_panel_ring(m, b, (unsigned)nb, d_x, d_y, accumulate, s);
-  const int U = b->unroll, K = b->kblocks;
-  if (b->ablate) {  // timing-only (wrong results): the two-stage kernel, 12 chunks, 2 blocks per phase
-    switch (b->ablate) {
-      case 1: launch_panel_as<12, 2, 1>(m, b, (unsigned)nb, lds, d_x, d_y, accumulate, s); break;
-      case 2: launch_panel_as<12, 2, 2>(m, b, (unsigned)nb, lds, d_x, d_y, accumulate, s); break;
-      case 3: launch_panel_as<12, 2, 3>(m, b, (unsigned)nb, lds, d_x, d_y, accumulate, s); break;
-      case 4: launch_panel_as<12, 2, 4>(m, b, (unsigned)nb, lds, d_x, d_y, accumulate, s); break;
-      case 5: launch_panel_as<12, 2, 5>(m, b, (unsigned)nb, lds, d_x, d_y, accumulate, s); break;
-      case 6: launch_panel_as<12, 2, 6>(m, b, (unsigned)nb, lds, d_x, d_y, accumulate, s); break;
-      default: launch_panel_as<12, 2, 7>(m, b, (unsigned)nb, lds, d_x, d_y, accumulate, s); break;
-    }
-    hipError_t ea = hipGetLastError();
-    if (ea != hipSuccess) { set_last_error("spmv_panel ablation launch", ea); return SPL_ERROR_device; }
-    return SPL_OK;
-  }
-  if (b->pair) {  // paired storage: only the paired kernel reads it
-    if (K == 1) {
-      switch (U) {
-        case 2: launch_panelw_as<2, 1>(m, b, (unsigned)nb, lds, d_x, d_y, accumulate, s); break;
-        case 4: launch_panelw_as<4, 1>(m, b, (unsigned)nb, lds, d_x, d_y, accumulate, s); break;
-        default: launch_panelw_as<3, 1>(m, b, (unsigned)nb, lds, d_x, d_y, accumulate, s); break;
-      }
-    } else {
-      switch (U) {
-        case 3: launch_panelw_as<3, 2>(m, b, (unsigned)nb, lds, d_x, d_y, accumulate, s); break;
-        case 4: launch_panelw_as<4, 2>(m, b, (unsigned)nb, lds, d_x, d_y, accumulate, s); break;
-        case 5: launch_panelw_as<5, 2>(m, b, (unsigned)nb, lds, d_x, d_y, accumulate, s); break;
-        default: launch_panelw_as<6, 2>(m, b, (unsigned)nb, lds, d_x, d_y, accumulate, s); break;
-      }
-    }
-    hipError_t ew = hipGetLastError();
-    if (ew != hipSuccess) { set_last_error("spmv_panelw launch", ew); return SPL_ERROR_device; }
-    return SPL_OK;
-  }
-#define SPL_PNL(UU, KK) launch_panel_as<UU, KK>(m, b, (unsigned)nb, lds, d_x, d_y, accumulate, s)
-  if (K == 1) {
-    switch (U) {
-      case 4: SPL_PNL(4, 1); break;
-      case 6: SPL_PNL(6, 1); break;
-      case 8: SPL_PNL(8, 1); break;
-      case 10: SPL_PNL(10, 1); break;
-      default: SPL_PNL(12, 1); break;
-    }
-  } else {
-    switch (U) {
-      case 4: SPL_PNL(4, 2); break;
-      case 6: SPL_PNL(6, 2); break;
-      case 8: SPL_PNL(8, 2); break;
-      case 10: SPL_PNL(10, 2); break;
-      default: SPL_PNL(12, 2); break;
-    }
-  }
-#undef SPL_PNL
+  k->run(PanelLaunchArgs{m, b, (unsigned)nb, d_x, d_y, accumulate, s}, plan);
   hipError_t e = hipGetLastError();
-  if (e != hipSuccess) { set_last_error("spmv_panel launch", e); return SPL_ERROR_device; }
+  if (e != hipSuccess) { set_last_error(k->where, e); return SPL_ERROR_device; }
   return SPL_OK;
+}
+
+// ---- choosing the plan ------------------------------------------------------------------------------
+static int env_int(const char *name, int otherwise) {
+  const char *ev = getenv(name);
+  return ev ? atoi(ev) : otherwise;
+}
+
+int panel_slices_override() { return env_int("SPL_PANEL_SLICES", 0); }  // 0: not set
+
+bool panel_code_valid(int form, int unroll) {  // the codes are 0 ... 11 without 3; rounds of 3 ... 6 register sets
+  if (form == SPL_PANEL_FORM_ROUNDS) return unroll == 0 || (unroll >= 3 && unroll <= 6);
+  return form >= SPL_PANEL_FORM_DEFAULT && form <= SPL_PANEL_FORM_RING_K8 && form != 3;
+}
+
+bool panel_code_takes_slices(int form) {
+  return form == SPL_PANEL_FORM_DEFAULT || form == SPL_PANEL_FORM_PAIRED_K1 || form == SPL_PANEL_FORM_PAIRED_K2;
+}
+
+// The ABI's numeric codes and the defaults, nowhere else.  sets == 0 (chunk and paired form with unroll 0) is
+// left for choose_panel_plan, which sizes it from the image.
+PanelPlan panel_plan_from_code(int form, int unroll, int cols_log2, int nslices) {
+  // the default: paired, a phase's x window 2 MiB at most (measured on C2, tools/bench_spmv_variants.py:
+  // paired 0.90 ms, one chunk per load 0.96 ms)
+  if (form == SPL_PANEL_FORM_DEFAULT) form = cols_log2 >= 17 ? SPL_PANEL_FORM_PAIRED_K2 : SPL_PANEL_FORM_PAIRED_K1;
+  PanelPlan p;
+  p.sets = unroll > 0 ? unroll : 0;
+  p.nslices = 1;
+  switch (form) {
+    case SPL_PANEL_FORM_CHUNK_K1: p.form = PanelForm::Chunk; p.kblocks = 1; break;
+    case SPL_PANEL_FORM_CHUNK_K2: p.form = PanelForm::Chunk; p.kblocks = 2; break;
+    case SPL_PANEL_FORM_PAIRED_K1: p.form = PanelForm::Paired; p.kblocks = 1; p.nslices = nslices; break;
+    case SPL_PANEL_FORM_PAIRED_K2: p.form = PanelForm::Paired; p.kblocks = 2; p.nslices = nslices; break;
+    case SPL_PANEL_FORM_ROUNDS: p.form = PanelForm::Rounds; p.kblocks = 2; if (p.sets == 0) p.sets = 5; break;
+    default:  // the ring forms, codes 6 ... 10: 1 / 2 / 3 / 4 / 8 index blocks per phase; sets is the depth of a loader
+      p.form = PanelForm::Ring;
+      p.kblocks = form == SPL_PANEL_FORM_RING_K8 ? 8 : form - SPL_PANEL_FORM_RING_K1 + 1;
+      if (p.sets == 0) p.sets = 6;
+      p.nl = env_int("SPL_PANEL_RING_NL", 4);
+      p.slots = env_int("SPL_PANEL_RING_SLOTS", 1);
+      p.gather = env_int("SPL_PANEL_RING_GD", 4);
+      break;
+  }
+  return p;
+}
+
+// The register sets per wavefront and the index blocks per phase are worth 5-10 % either way and the best pair sits
+// next to the heuristic one (C2: 5 pairs, 2 blocks: 0.90 ms; 6 pairs: 0.97; 4: 0.98; 3 pairs, 1 block: 0.96): time
+// the neighbours once (same image; about a hundred launches on a scratch vector) and keep the fastest.  Without column
+// slices the rounds form joins with the same register sets +- 1 (C2: 4 pairs 0.82 ms; profiles/panel_rounds_bench.json).
+static PanelPlan tune_panel_plan(const Matrix *m, const PanelImage *b, const PanelPlan &heuristic) {
+  const int unroll = heuristic.sets, kblocks = heuristic.kblocks;
+  const bool verbose = getenv("SPL_PANEL_VERBOSE") != nullptr;
+  DBuf<double> tx((size_t)m->ncols), ty((size_t)m->nrows_local);
+  SPL_HIP(hipMemsetAsync(tx.get(), 0, (size_t)m->ncols * sizeof(double), nullptr));
+  hipEvent_t e0, e1;
+  SPL_HIP(hipEventCreate(&e0));
+  SPL_HIP(hipEventCreate(&e1));
+  std::vector<PanelPlan> cands;
+  const auto add = [&](PanelForm form, int k, int u) { PanelPlan c = heuristic; c.form = form; c.kblocks = k; c.sets = u; cands.push_back(c); };
+  for (int du = -1; du <= 1; ++du) {
+    const int u2 = unroll + du;
+    if (kblocks == 2 && u2 >= 3 && u2 <= 6) add(PanelForm::Paired, 2, u2);
+    if (kblocks == 1 && u2 >= 2 && u2 <= 4) add(PanelForm::Paired, 1, u2);
+  }
+  if (kblocks == 2) {
+    for (int u1 = (unroll + 1) / 2; u1 <= (unroll + 1) / 2 + 1; ++u1)
+      if (u1 >= 2 && u1 <= 4) add(PanelForm::Paired, 1, u1);
+  }
+  if (heuristic.nslices == 1) {  // the rounds form does not depend on the index blocks: the same register sets +- 1
+    const int uq = unroll < 3 ? 3 : unroll > 6 ? 6 : unroll;
+    for (int u2 = uq - 1; u2 <= uq + 1; ++u2)
+      if (u2 >= 3 && u2 <= 6) add(PanelForm::Rounds, kblocks, u2);
+  }
+  float best_ms = 0.f, heur_ms = 0.f;
+  PanelPlan best = heuristic;
+  for (const PanelPlan &c : cands) {
+    const bool q = c.form == PanelForm::Rounds;
+    SPL_HIP(hipMemsetAsync(b->arrive.get(), 0, 4 * sizeof(unsigned), nullptr));  // the forms clear it differently
+    for (int w = 0; w < 2; ++w) (void)launch_spmv_panel(m, c, tx.get(), ty.get(), 0, nullptr);
+    SPL_HIP(hipEventRecord(e0, nullptr));
+    for (int r = 0; r < 8; ++r) (void)launch_spmv_panel(m, c, tx.get(), ty.get(), 0, nullptr);
+    SPL_HIP(hipEventRecord(e1, nullptr));
+    SPL_HIP(hipEventSynchronize(e1));
+    float ms = 0.f;
+    SPL_HIP(hipEventElapsedTime(&ms, e0, e1));
+    if (verbose)
+      fprintf(stderr, "[panel] candidate %d pairs x %s: %.4f ms\n", c.sets, q ? "rounds" : c.kblocks == 2 ? "2 blocks" : "1 block", ms / 8.f);
+    if (c.kblocks == kblocks && c.sets == unroll && !q) heur_ms = ms;
+    if (best_ms == 0.f || ms < best_ms) { best_ms = ms; best = c; }
+  }
+  (void)hipEventDestroy(e0);
+  (void)hipEventDestroy(e1);
+  if (heur_ms > 0.f && best_ms > 0.99f * heur_ms) best = heuristic;  // within noise: keep the heuristic
+  if (verbose)
+    fprintf(stderr, "[panel] heuristic %d pairs x %d blocks: %.4f ms; chosen %d x %d%s: %.4f ms\n", unroll, kblocks,
+            heur_ms / 8.f, best.sets, best.kblocks, best.form == PanelForm::Rounds ? " (rounds)" : "", best_ms / 8.f);
+  SPL_HIP(hipMemsetAsync(b->arrive.get(), 0, 4 * sizeof(unsigned), nullptr));
+  SPL_HIP(hipStreamSynchronize(nullptr));  // the caller's launches may go to another stream
+  return best;
+}
+
+PanelPlan choose_panel_plan(const Matrix *m, const PanelImage *b, int form, int unroll, int nslices, bool may_tune) {
+  PanelPlan plan = panel_plan_from_code(form, unroll, b->w, nslices);
+  if (plan.form == PanelForm::Rounds || plan.form == PanelForm::Ring) return normalise(plan);
+  if (unroll == 0) {
+    // units (chunks or pairs) per wavefront and phase: the 16 wavefronts share a phase's units evenly.  More loads
+    // in flight than the mean needs cost time (the stream then queues in front of the gathers in the CU's L1): the
+    // nearest count, and the longer phases take the un-pipelined tail loop (C2: 5 pairs 0.90 ms, 6 pairs 0.97 ms;
+    // 69 % of the phases have a tail, profiles/panel_rounds_before.txt — what the rounds form does away with)
+    const double per_wave = (double)b->nchunks * plan.kblocks / (double)(b->npanels * b->nib > 0 ? b->npanels * b->nib : 1) / 16.0;
+    if (plan.form == PanelForm::Paired) {
+      const int pairs = (int)(per_wave / 2.0 + 0.5);
+      plan.sets = pairs < 2 ? 2 : pairs > 6 ? 6 : pairs;
+    } else {
+      const int want = (int)(per_wave + 0.5);
+      plan.sets = want <= 4 ? 4 : want <= 6 ? 6 : want <= 8 ? 8 : want <= 10 ? 10 : 12;
+    }
+  }
+  const char *forced = getenv("SPL_PANEL_UNROLL"), *tune = getenv("SPL_PANEL_TUNE");
+  if (forced) plan.sets = atoi(forced);
+  // only the all-default request on a large matrix is tuned; SPL_PANEL_TUNE=0 keeps the heuristic
+  if (may_tune && form == SPL_PANEL_FORM_DEFAULT && unroll == 0 && m->nnz > (int64_t)1 << 22 && !forced &&
+      !(tune && tune[0] == '0'))
+    plan = tune_panel_plan(m, b, plan);
+  const char *ok = getenv("SPL_ALLOW_ABLATION"), *ab = getenv("SPL_PANEL_ABLATE");
+  if (ok && ok[0] == '1' && ab && plan.form == PanelForm::Chunk) plan.ablate = atoi(ab) & 7;
+  return normalise(plan);  // the plan the image records is the one that runs
 }
 
 }  // namespace spl

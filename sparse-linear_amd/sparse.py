@@ -176,6 +176,12 @@ class DeviceMatrix(object):
     callee-allocated, freed through ``void **``; Umfpack.hs:63-65)."""
     ORDER_REFERENCE = 0
     ORDER_FREE = 1
+    # the `form` argument of build_panel (SPL_PANEL_FORM_* of include/sparse_linear_hip.h)
+    PANEL_FORM_DEFAULT = 0
+    PANEL_FORM_CHUNK_K1, PANEL_FORM_CHUNK_K2 = 1, 2
+    PANEL_FORM_PAIRED_K1, PANEL_FORM_PAIRED_K2 = 4, 5
+    PANEL_FORM_RING_K1, PANEL_FORM_RING_K2, PANEL_FORM_RING_K3, PANEL_FORM_RING_K4, PANEL_FORM_RING_K8 = 6, 7, 8, 9, 10
+    PANEL_FORM_ROUNDS = 11
 
     def __init__(self, handle):
         self._h = C.c_void_p(handle)
@@ -350,9 +356,10 @@ class DeviceMatrix(object):
 
     def build_panel(self, rows_per_panel=0, cols_log2=0, unroll=0, form=0):
         """the column-sorted panel image (csrc/spmv_panel.hip): order-free sums, 1e-10 contract;
-        form 1 / 2: one chunk per load, 1 / 2 index blocks per phase; 4 / 5: paired storage, 1 / 2 index blocks
-        per phase (the default's heuristic); 6 ... 10: ring form; 11: rounds form on the paired storage — rounds of
-        exactly 16 * unroll pairs of chunks whatever the index blocks are (unroll 3 ... 6, 0: 5), no column slices.
+        form (PANEL_FORM_*) CHUNK_K1 / _K2: one chunk per load, 1 / 2 index blocks per phase; PAIRED_K1 / _K2: paired
+        storage, 1 / 2 index blocks per phase (the default's heuristic); RING_K1 ... _K8: ring form; ROUNDS: rounds form on
+        the paired storage — rounds of exactly 16 * unroll pairs of chunks whatever the index blocks are (unroll 3 ... 6,
+        0: 5), no column slices.  What unroll counts per form: include/sparse_linear_hip.h.
         With everything 0 on a large matrix the build times the heuristic's neighbours, the rounds form among them,
         and keeps another candidate only if it is more than 1 % faster."""
         check("spl_matrix_build_panel",

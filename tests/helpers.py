@@ -59,3 +59,48 @@ def handle_to_csc_tuple(H):
     order = np.argsort(ci, kind="stable")
     cp = np.concatenate([[0], np.cumsum(np.bincount(ci, minlength=nc))]).astype(np.int64)
     return (nr, nc, cp, rows[order], v[order])
+
+
+# ---- the order-free panel SpMV (csrc/spmv_panel.hip): what every form has to meet -------------------------
+EPS = np.finfo(float).eps
+
+
+def panel_stream(torch):
+    return torch.cuda.current_stream().cuda_stream
+
+
+def panel_run(torch, H, x):
+    n = H.info()["nrows_local"]
+    y = torch.zeros(n, dtype=torch.float64, device="cuda")
+    H.spmv_dev(x.data_ptr(), y.data_ptr(), stream=panel_stream(torch))
+    torch.cuda.synchronize()
+    return y.cpu().numpy()
+
+
+def panel_check(torch, O, H, ncols):
+    """the three-part contract on whatever H holds: product, rounding bound, accumulate form"""
+    nrows = H.info()["nrows_local"]
+    rp, ci, v = H.export_csr()
+    rp32 = rp.astype(np.int32)
+    xh = O.gen_vector(ncols)
+    x = torch.from_numpy(xh).cuda()
+    y = panel_run(torch, H, x)
+    yo = np.zeros(nrows)
+    O.csr_gaxpy32(rp32, ci, v, xh, yo)
+    bad = O.count_not_close(y, yo, 1e-10)
+    sabs = np.zeros(nrows)
+    O.csr_gaxpy32(rp32, ci, np.abs(v), np.abs(xh), sabs)  # sum |a x| per row
+    lens = np.diff(rp)
+    excess = np.abs(y - yo) - 2.0 * np.maximum(lens, 1) * EPS * sabs
+    print("not close at 1e-10: %d; largest |y - yo| / (2 len eps sum|a x|): %.3g"
+          % (bad, float(np.max(np.abs(y - yo) / np.maximum(2.0 * np.maximum(lens, 1) * EPS * sabs, 1e-300)))))
+    assert bad == 0
+    assert np.all(excess <= 0.0)
+    y0 = O.gen_vector(nrows, seed=7)
+    yd = torch.from_numpy(y0.copy()).cuda()
+    H.spmv_dev(x.data_ptr(), yd.data_ptr(), accumulate=True, stream=panel_stream(torch))
+    torch.cuda.synchronize()
+    ya = y0.copy()
+    O.csr_gaxpy32(rp32, ci, v, xh, ya)
+    assert O.count_not_close(yd.cpu().numpy(), ya, 1e-10) == 0
+    assert H.panel_errors() == 0

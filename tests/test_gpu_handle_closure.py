@@ -346,7 +346,7 @@ def select_kernel(H, kernel):
         H.set_variant(15)
         assert H.spmv_kernel() == 15 and H.info()["blocked_rows"] == -64
     else:
-        H.build_panel(1000, 10, 0, 11 if kernel == "rounds" else 0)
+        H.build_panel(1000, 10, 0, H.PANEL_FORM_ROUNDS if kernel == "rounds" else H.PANEL_FORM_DEFAULT)
         H.set_variant(16)
         assert H.spmv_kernel() == 16 and H.info()["blocked_rows"] == 1000
 

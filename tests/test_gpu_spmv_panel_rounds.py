@@ -10,51 +10,9 @@ word between generations back to zero: there is no memset in front of a launch).
 import numpy as np
 import pytest
 
+from helpers import panel_check as _check, panel_run as _run, panel_stream as _stream
+
 pytestmark = pytest.mark.gpu
-
-ROUNDS = 11  # the `form` argument of build_panel
-EPS = np.finfo(float).eps
-
-
-def _stream(torch):
-    return torch.cuda.current_stream().cuda_stream
-
-
-def _run(torch, H, x):
-    n = H.info()["nrows_local"]
-    y = torch.zeros(n, dtype=torch.float64, device="cuda")
-    H.spmv_dev(x.data_ptr(), y.data_ptr(), stream=_stream(torch))
-    torch.cuda.synchronize()
-    return y.cpu().numpy()
-
-
-def _check(torch, O, H, ncols):
-    """the three-part contract on whatever H holds: product, rounding bound, accumulate form"""
-    nrows = H.info()["nrows_local"]
-    rp, ci, v = H.export_csr()
-    rp32 = rp.astype(np.int32)
-    xh = O.gen_vector(ncols)
-    x = torch.from_numpy(xh).cuda()
-    y = _run(torch, H, x)
-    yo = np.zeros(nrows)
-    O.csr_gaxpy32(rp32, ci, v, xh, yo)
-    bad = O.count_not_close(y, yo, 1e-10)
-    sabs = np.zeros(nrows)
-    O.csr_gaxpy32(rp32, ci, np.abs(v), np.abs(xh), sabs)  # sum |a x| per row
-    lens = np.diff(rp)
-    excess = np.abs(y - yo) - 2.0 * np.maximum(lens, 1) * EPS * sabs
-    print("not close at 1e-10: %d; largest |y - yo| / (2 len eps sum|a x|): %.3g"
-          % (bad, float(np.max(np.abs(y - yo) / np.maximum(2.0 * np.maximum(lens, 1) * EPS * sabs, 1e-300)))))
-    assert bad == 0
-    assert np.all(excess <= 0.0)
-    y0 = O.gen_vector(nrows, seed=7)
-    yd = torch.from_numpy(y0.copy()).cuda()
-    H.spmv_dev(x.data_ptr(), yd.data_ptr(), accumulate=True, stream=_stream(torch))
-    torch.cuda.synchronize()
-    ya = y0.copy()
-    O.csr_gaxpy32(rp32, ci, v, xh, ya)
-    assert O.count_not_close(yd.cpu().numpy(), ya, 1e-10) == 0
-    assert H.panel_errors() == 0
 
 
 @pytest.mark.parametrize("n,K,P,w,unroll", [
@@ -73,7 +31,7 @@ def _check(torch, O, H, ncols):
 def test_rounds_match_oracle(gpu, pkg, O, n, K, P, w, unroll):
     torch = gpu
     H = pkg.DeviceMatrix.synthetic("random", n, K)
-    H.build_panel(P, w, unroll, ROUNDS)
+    H.build_panel(P, w, unroll, pkg.DeviceMatrix.PANEL_FORM_ROUNDS)
     H.set_variant(16)
     assert H.spmv_kernel() == 16 and H.info()["blocked_rows"] == P
     _check(torch, O, H, n)
@@ -96,7 +54,7 @@ def test_rounds_exact_multiple_of_a_round(gpu, pkg, O, unroll, nib):
     A = O.compress(nr, nc, r, c, rng.uniform(0.5, 1.5, len(r)))
     H = pkg.DeviceMatrix.from_csc(pkg.Matrix(nc, nr, A[2], A[3], A[4]))
     assert H.info()["nnz"] == 12 * nr
-    H.build_panel(P, int(np.log2(wb)), unroll, ROUNDS)
+    H.build_panel(P, int(np.log2(wb)), unroll, pkg.DeviceMatrix.PANEL_FORM_ROUNDS)
     H.set_variant(16)
     _check(torch, O, H, nc)
 
@@ -111,7 +69,7 @@ def test_rounds_exact_on_integers(gpu, pkg, O):
     yo = O.mulV(A, xh)
     for P, w, unroll in [(2500, 11, 5), (2500, 8, 3), (20479, 16, 6), (700, 13, 4)]:
         H = pkg.DeviceMatrix.from_csc(pkg.Matrix(n, n, A[2], A[3], A[4]))
-        H.build_panel(P, w, unroll, ROUNDS)
+        H.build_panel(P, w, unroll, pkg.DeviceMatrix.PANEL_FORM_ROUNDS)
         H.set_variant(16)
         assert np.array_equal(_run(torch, H, torch.from_numpy(xh).cuda()), yo)
         H.free()
@@ -131,7 +89,7 @@ def test_rounds_empty_rows_segments_and_ragged_edges(gpu, pkg, O, unroll):
     rows, cols = rows[keep], cols[keep]
     A = O.compress(nr, nc, rows, cols, rng.uniform(0.5, 1.5, len(rows)))
     H = pkg.DeviceMatrix.from_csc(pkg.Matrix(nc, nr, A[2], A[3], A[4]))
-    H.build_panel(1000, 10, unroll, ROUNDS)
+    H.build_panel(1000, 10, unroll, pkg.DeviceMatrix.PANEL_FORM_ROUNDS)
     H.set_variant(16)
     xh = rng.uniform(0.5, 1.5, nc)
     y = _run(torch, H, torch.from_numpy(xh).cuda())
@@ -139,10 +97,10 @@ def test_rounds_empty_rows_segments_and_ragged_edges(gpu, pkg, O, unroll):
     assert O.count_not_close(y, yo, 1e-10) == 0 and np.all(y[::7] == 0.0)
     _check(torch, O, H, nc)
     # w = 4: 257 index blocks, most of them empty in any one panel of 64 rows
-    H.build_panel(64, 4, unroll, ROUNDS)
+    H.build_panel(64, 4, unroll, pkg.DeviceMatrix.PANEL_FORM_ROUNDS)
     _check(torch, O, H, nc)
     Z = pkg.DeviceMatrix.from_csc(pkg.zeros(300, 200))
-    Z.build_panel(64, 4, unroll, ROUNDS)
+    Z.build_panel(64, 4, unroll, pkg.DeviceMatrix.PANEL_FORM_ROUNDS)
     Z.set_variant(16)
     assert np.array_equal(_run(torch, Z, torch.ones(200, dtype=torch.float64, device="cuda")), np.zeros(300))
 
@@ -152,7 +110,7 @@ def test_rounds_rmat(gpu, pkg, O, P, w, unroll):
     """the skewed matrix of the existing synthetic generator: segment sizes from empty to many rounds"""
     torch = gpu
     H = pkg.DeviceMatrix.rmat(17, 16, (0.57, 0.19, 0.19))
-    H.build_panel(P, w, unroll, ROUNDS)
+    H.build_panel(P, w, unroll, pkg.DeviceMatrix.PANEL_FORM_ROUNDS)
     H.set_variant(16)
     _check(torch, O, H, 1 << 17)
 
@@ -165,7 +123,7 @@ def test_rounds_repeated_launches_without_synchronise(gpu, pkg, O, unroll):
     torch = gpu
     n = 40_000
     H = pkg.DeviceMatrix.synthetic("random", n, 20)
-    H.build_panel(64, 12, unroll, ROUNDS)
+    H.build_panel(64, 12, unroll, pkg.DeviceMatrix.PANEL_FORM_ROUNDS)
     H.set_variant(16)
     rp, ci, v = H.export_csr()
     xh = O.gen_vector(n)
@@ -189,7 +147,7 @@ def test_rounds_arguments(gpu, pkg):
     H = pkg.DeviceMatrix.synthetic("random", 5000, 5)
     for bad in (1, 2, 7, 12):
         with pytest.raises(Exception):
-            H.build_panel(512, 10, bad, ROUNDS)
-    H.build_panel(512, 10, 0, ROUNDS)
+            H.build_panel(512, 10, bad, pkg.DeviceMatrix.PANEL_FORM_ROUNDS)
+    H.build_panel(512, 10, 0, pkg.DeviceMatrix.PANEL_FORM_ROUNDS)
     H.set_variant(16)
     assert H.spmv_kernel() == 16

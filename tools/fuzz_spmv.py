@@ -87,7 +87,8 @@ def main():
             H.optimize()
             H.set_variant(15)
         plans.append(("sell", sell))
-        for form in (1, 2, 4, 5):
+        D = pkg.DeviceMatrix
+        for form in (D.PANEL_FORM_CHUNK_K1, D.PANEL_FORM_CHUNK_K2, D.PANEL_FORM_PAIRED_K1, D.PANEL_FORM_PAIRED_K2):
             def panel(form=form):
                 P = int(rng.choice([0, 64, 777, 4096, 20479]))
                 w = int(rng.choice([0, 4, 9, 13, 17]))
