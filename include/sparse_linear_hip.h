@@ -94,6 +94,11 @@ int spl_gaxpy_t(int nrows, int ncols, const int *Ap, const int *Ai, const double
  * (hmatrix's default order); C is nrows x bcols row-major. */
 int spl_mulm(int nrows, int ncols, const int *Ap, const int *Ai, const double *Ax,
              int brows, int bcols, const double *B, double *C);
+/* mulM on Complex Double (the reference's second SPECIALIZE instance, Sparse.hs:475): Az, Bz and Cz hold packed
+ * (re, im) pairs, Bz and Cz row-major as above.  Statuses and guards are spl_mulm's.  Every column of C is
+ * bit-identical to one complex axpy_ on that column of B (the kernel of spl_matrix_spmv_many_dev). */
+int spl_mulm_z(int nrows, int ncols, const int *Ap, const int *Ai, const double *Az,
+               int brows, int bcols, const double *Bz, double *Cz);
 
 /* mm / (*) (Sparse.hs:691-702): C = A B.  Union pattern (cancellation keeps a
  * stored zero), row indices ascending, Cp = exclusive prefix sum.  Outputs are
@@ -167,7 +172,8 @@ int spl_matrix_create(int nrows, int ncols, const int *Ap, const int *Ai, const 
  * _spmv_dev take packed complex vectors (2 * ncols and 2 * nrows doubles; xlen, ylen still count entries) and
  * compute  y <- a * x + y  per stored entry in ascending column order with Data.Complex's arithmetic, every
  * real operation separately rounded (csrc/spmv_z.hip: 20 bytes per stored entry instead of the 48 of the real
- * 2n x 2n embedding).  Other handle operations (spgemm, export, spmm, images) are for real handles. */
+ * 2n x 2n embedding).  spl_matrix_spmv_many_dev is the fused product of such a handle with k vectors at once.
+ * Other handle operations (spgemm, export, spmm, images) are for real handles. */
 int spl_matrix_create_z(int nrows, int ncols, const int *Ap, const int *Ai, const double *Az, void **H);
 /* 1 for a handle made by spl_matrix_create_z, 0 for a real one */
 int spl_matrix_is_complex(void *H);
@@ -242,6 +248,25 @@ int spl_matrix_spmv_dev(void *H, const double *d_x, double *d_y, int accumulate,
 /* Device-resident sparse x dense (mulM): d_B is ncols x k, d_C is nrows_local x k, both
  * row-major DEVICE arrays; A is read once for all k columns.  accumulate != 0: C <- A B + C. */
 int spl_matrix_spmm_dev(void *H, const double *d_B, double *d_C, int k, int accumulate, void *stream);
+/* Device-resident SpMV on k vectors at once:  Y[:, j] = A X[:, j] (+ Y[:, j] when accumulate != 0),  j = 0 .. k-1.
+ * d_X and d_Y are COLUMN-major device arrays — one vector after the other, the layout of the batched solves
+ * (spl_umfpack_*_solve_many_dev) — with leading dimensions ldx >= ncols and ldy >= nrows_local counted in entries: a
+ * double on a real handle, a packed (re, im) pair on a complex one.  Row-block handles are served (X has ncols rows,
+ * Y nrows_local).  X and Y must not overlap; entries of X and Y beyond row ncols / nrows_local of a column are neither
+ * read nor written.  The kernel is enqueued on `stream`; the call does not synchronise.  A is read once per 16 vectors.
+ * Order: every (row, vector) sum folds  a * x + acc  over the row's stored entries in ascending column order, every
+ * real operation separately rounded, the complex product in Data.Complex's order — for rows of ANY length, so vector
+ * j's result is the reference's axpy_ on that column bit for bit, and spl_matrix_spmv_dev's in SPL_ORDER_REFERENCE
+ * wherever that kernel keeps the order (rows within one chunk of the CSR-stream kernels).  The call always reads the
+ * CSR image: spl_matrix_set_spmv_order and the blocked / sliced-ELL / panel images do not change it.  With k = 1 it is
+ * no faster than spl_matrix_spmv_dev, and slower on rows longer than a chunk (csrc/spmv_many.hip; measured figures:
+ * DESIGN.md).
+ * Against spl_matrix_spmm_dev: this call takes column-major vectors and complex handles; that one a row-major real B.
+ * Statuses: SPL_ERROR_invalid_handle (H is no matrix handle); SPL_ERROR_n_nonpositive (k < 0); k == 0: SPL_OK, nothing
+ * is touched; SPL_ERROR_argument_missing (k > 0 and a needed pointer is NULL or not aligned to an entry, 8 or 16
+ * bytes); SPL_ERROR_dimension_mismatch (k > 1 and ldx < ncols or ldy < nrows_local). */
+int spl_matrix_spmv_many_dev(void *H, int k, const double *d_X, int64_t ldx, double *d_Y, int64_t ldy,
+                             int accumulate, void *stream);
 /* select a kernel variant for spl_matrix_spmv_dev (tuning / ablation only): 0 = default
  * (whatever spl_matrix_optimize chose), 1-6 CSR-stream shapes, 7 sub-wavefront kernel, 8
  * column-blocked image, 9-11 gather cache policies, 15 sliced-ELL image, 16 column-sorted panel

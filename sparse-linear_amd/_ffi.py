@@ -90,6 +90,7 @@ def _declare(L):
         "spl_mulv": tup + [i, c_dbl_p, c_dbl_p],
         "spl_gaxpy_t": tup + [i, c_dbl_p, i, c_dbl_p],
         "spl_mulm": tup + [i, i, c_dbl_p, c_dbl_p],
+        "spl_mulm_z": tup + [i, i, c_dbl_p, c_dbl_p],
         "spl_transpose": tup + [c_int_p, c_int_p, c_dbl_p],
         "spl_spgemm": tup + tup + [c_int_p, c_int_p, c_void_pp, c_void_pp, c_void_pp],
         "spl_spgemm_z": tup + tup + [c_int_p, c_int_p, c_void_pp, c_void_pp, c_void_pp],
@@ -118,6 +119,7 @@ def _declare(L):
         "spl_matrix_gaxpy": [C.c_void_p, i, c_dbl_p, i, c_dbl_p],
         "spl_matrix_spmv_dev": [C.c_void_p, C.c_void_p, C.c_void_p, i, C.c_void_p],
         "spl_matrix_spmm_dev": [C.c_void_p, C.c_void_p, C.c_void_p, i, i, C.c_void_p],
+        "spl_matrix_spmv_many_dev": [C.c_void_p, i, C.c_void_p, i64, C.c_void_p, i64, i, C.c_void_p],
         "spl_matrix_set_variant": [C.c_void_p, i],
         "spl_matrix_optimize": [C.c_void_p],
         "spl_matrix_build_blocked": [C.c_void_p, i, i, i],

@@ -943,6 +943,49 @@ int spl_matrix_spmm_dev(void *H, const double *d_B, double *d_C, int k, int accu
   });
 }
 
+int spl_matrix_spmv_many_dev(void *H, int k, const double *d_X, int64_t ldx, double *d_Y, int64_t ldy, int accumulate,
+                             void *stream) {
+  Matrix *m = as_matrix(H);
+  if (!m) return SPL_ERROR_invalid_handle;
+  if (k < 0) return SPL_ERROR_n_nonpositive;
+  if (k == 0) return SPL_OK;
+  if ((m->ncols > 0 && !d_X) || (m->nrows_local > 0 && !d_Y)) return SPL_ERROR_argument_missing;
+  const uintptr_t entry = (uintptr_t)(8 * m->vw);  // the kernel loads and stores whole entries
+  if ((uintptr_t)d_X % entry != 0 || (uintptr_t)d_Y % entry != 0) return SPL_ERROR_argument_missing;
+  if (k > 1 && (ldx < m->ncols || ldy < m->nrows_local)) return SPL_ERROR_dimension_mismatch;
+  return guarded([&]() -> int {
+    DeviceGuard g(m->device);
+    return launch_spmv_many(m, k, d_X, ldx, d_Y, ldy, accumulate, as_stream(stream));
+  });
+}
+
+// mulM on Complex Double (the reference's SPECIALIZE instance, Sparse.hs:475): one axpy_ per column of B there; here the
+// packed-complex image of A and one multi-vector product.  B and C are row-major like spl_mulm's; the kernel wants one
+// vector after the other, so both are turned on the device (the call is bounded by its copies over PCIe).
+int spl_mulm_z(int nrows, int ncols, const int *Ap, const int *Ai, const double *Az, int brows, int bcols,
+               const double *Bz, double *Cz) {
+  if (nrows >= 0 && ncols >= 0 && ncols != brows) return SPL_ERROR_dimension_mismatch;  // Sparse.hs:478
+  if (bcols < 0) return SPL_ERROR_n_nonpositive;
+  if ((int64_t)brows * bcols > 0 && !Bz) return SPL_ERROR_argument_missing;
+  if ((int64_t)nrows * bcols > 0 && !Cz) return SPL_ERROR_argument_missing;
+  return guarded([&]() -> int {
+    std::unique_ptr<Matrix> m;
+    int st = build_from_csc(2, nrows, ncols, Ap, Ai, Az, 0, 1, m);
+    if (st != SPL_OK) return st;
+    hipStream_t s = nullptr;
+    finalize_matrix(m.get(), s);
+    const size_t nb = (size_t)brows * bcols, nc = (size_t)nrows * bcols;
+    DBuf<double> dB, dX(2 * nb), dY(2 * nc), dC(2 * nc);
+    upload(dB, Bz, 2 * nb, s);
+    st = transpose_dense(brows, bcols, 2, dB.get(), dX.get(), s);
+    if (st == SPL_OK) st = launch_spmv_many(m.get(), bcols, dX.get(), brows, dY.get(), nrows, 0, s);
+    if (st == SPL_OK) st = transpose_dense(bcols, nrows, 2, dY.get(), dC.get(), s);
+    if (st == SPL_OK && nc) SPL_HIP(hipMemcpyAsync(Cz, dC.get(), 2 * nc * sizeof(double), hipMemcpyDeviceToHost, s));
+    SPL_HIP(hipStreamSynchronize(s));
+    return st;
+  });
+}
+
 int spl_transpose(int nrows, int ncols, const int *Ap, const int *Ai, const double *Ax, int *Tp, int *Ti,
                   double *Tx) {
   int st = check_tuple(nrows, ncols, Ap, Ai, Ax);

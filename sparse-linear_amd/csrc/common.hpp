@@ -322,6 +322,13 @@ void generate_vector(uint64_t seed, int64_t j0, int64_t j1, double *d_x, hipStre
 int launch_spmv(const Matrix *m, const double *d_x, double *d_y, int accumulate, hipStream_t s);
 // C (nrows_local x k, row-major) = A B (+ C) for a row-major dense B (ncols x k): one pass over A
 int launch_spmm(const Matrix *m, const double *d_B, double *d_C, int k, int accumulate, hipStream_t s);
+// Y[:, j] = A X[:, j] (+ Y[:, j]), j < k, on the CSR image of a real or complex handle (spmv_many.hip): X and Y
+// column-major with leading dimensions ldx, ldy in entries (a double, or a packed pair); every (row, vector) sum in
+// the reference's order whatever the row's length; SPL_OK at once for nrows_local == 0 or k == 0
+int launch_spmv_many(const Matrix *m, int k, const double *d_X, int64_t ldx, double *d_Y, int64_t ldy, int accumulate,
+                     hipStream_t s);
+// d_out (cols x rows, row-major) = transpose of d_in (rows x cols, row-major); vw doubles per entry
+int transpose_dense(int64_t rows, int64_t cols, int vw, const double *d_in, double *d_out, hipStream_t s);
 // Complex Double (spmv_z.hip): d_x, d_y packed (re, im) pairs
 int launch_spmv_z(const Matrix *m, const double *d_x, double *d_y, int accumulate, hipStream_t s);
 void fill_positions(int64_t n, double *d_out, hipStream_t s);

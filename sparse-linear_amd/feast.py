@@ -52,16 +52,29 @@ def _positions(union, part):
     return pos
 
 
+def _multivector():
+    """SPL_FEAST_MULTIVECTOR=0: one spl_matrix_spmv_dev per subspace vector, as the reference maps axpy_ over the slices
+    (for A/B measurement; the same bits on rows within one chunk of the CSR-stream kernels, which is every matrix a
+    FEAST problem brings)"""
+    return os.environ.get("SPL_FEAST_MULTIVECTOR", "1") != "0"
+
+
 def _apply(mat, V):
-    """rows of the result = mat * rows of V (ijob 30 / 40, Feast.hs:203-208): one SpMV of the hot path per
-    subspace vector, device pointers in and out (spl_matrix_spmv_dev), nothing leaves HBM"""
+    """rows of the result = mat * rows of V (ijob 30 / 40, Feast.hs:203-208), device pointers in and out, nothing leaves
+    HBM: ONE product call for the whole subspace (spl_matrix_spmv_many_dev on the (m0, n) tensor, whose rows are the
+    vectors one after the other: leading dimension n), the matrix streamed once per 16 vectors instead of once per
+    vector.  Returns (result, product calls enqueued)."""
     import torch
     out = torch.empty_like(V)
     h = mat.device_handle()
     stream = torch.cuda.current_stream(V.device).cuda_stream
+    if _multivector():
+        n = V.shape[1]
+        h.spmv_many_dev(V.data_ptr(), n, out.data_ptr(), n, V.shape[0], False, stream)
+        return out, 1
     for j in range(V.shape[0]):
         h.spmv_dev(V[j].data_ptr(), out[j].data_ptr(), False, stream)
-    return out
+    return out, V.shape[0]
 
 
 _pool = None
@@ -169,11 +182,12 @@ def geigSH_(params, m0, interval, matA, matB=None, guess=None):
     keep_factors = os.environ.get("SPL_FEAST_KEEP_FACTORS", "1") != "0"
     kept = {}          # contour point -> (mat, fact)
     kept_lock = threading.Lock()
-    counts = {"factorisations": 0, "factors_reused": 0}
+    counts = {"factorisations": 0, "factors_reused": 0, "spmv_calls": 0}
     alloc_s0 = _ffi.device_alloc_seconds()
     for it in range(20):
         t0 = time.perf_counter()
-        BY = _apply(opB, Y)                                                    # ijob 40
+        BY, calls = _apply(opB, Y)                                             # ijob 40
+        counts["spmv_calls"] += calls
         rhs = BY if BY.dtype == torch.complex128 else BY.to(torch.complex128)
         t0 = tick("spmv", t0)
         def contour_point(i):
@@ -272,8 +286,9 @@ def geigSH_(params, m0, interval, matA, matB=None, guess=None):
         del parts
         t0 = tick("contour", t0)
         # Rayleigh-Ritz on the filtered subspace (dense, m0 x m0)
-        AQ = _apply(opA, Q)                                                    # ijob 30
-        BQ = _apply(opB, Q)                                                    # ijob 40
+        AQ, calls_a = _apply(opA, Q)                                           # ijob 30
+        BQ, calls_b = _apply(opB, Q)                                           # ijob 40
+        counts["spmv_calls"] += calls_a + calls_b
         t0 = tick("spmv", t0)
         Aq = (Q.conj() @ AQ.T).cpu().numpy()
         Bq = (Q.conj() @ BQ.T).cpu().numpy()

@@ -346,6 +346,14 @@ class DeviceMatrix(object):
               lib().spl_matrix_spmm_dev(self.handle, C.c_void_p(b_ptr), C.c_void_p(c_ptr), int(k),
                                         1 if accumulate else 0, C.c_void_p(stream)))
 
+    def spmv_many_dev(self, x_ptr, ldx, y_ptr, ldy, k, accumulate=False, stream=0):
+        """Y[:, j] = A X[:, j] (+ Y[:, j]) for k vectors stored one after the other (column-major device arrays with
+        leading dimensions ldx, ldy in entries: doubles, or packed complex pairs on a complex handle); A is read once
+        per 16 vectors, every sum in the reference's order (csrc/spmv_many.hip); no sync"""
+        check("spl_matrix_spmv_many_dev",
+              lib().spl_matrix_spmv_many_dev(self.handle, int(k), C.c_void_p(x_ptr), int(ldx), C.c_void_p(y_ptr),
+                                             int(ldy), 1 if accumulate else 0, C.c_void_p(stream)))
+
     def optimize(self):
         """one-time analysis; may build the column-blocked image (csrc/spmv_blocked.hip)"""
         check("spl_matrix_optimize", lib().spl_matrix_optimize(self.handle))
@@ -578,6 +586,18 @@ def mulVT(mat, x):
 
 def mulM(matA, matB):
     """sparse x dense (Sparse.hs:473-498); matB is a 2-D array (rows x cols)."""
+    if matA.is_complex or np.iscomplexobj(matB):
+        # Complex Double (the SPECIALIZE instance of Sparse.hs:475): the real operand is promoted as mulV promotes it
+        B = np.ascontiguousarray(matB, dtype=C128)
+        if matA.ncols != B.shape[0]:
+            _oops("mulM", "inner dimension mismatch")
+        _ffi.require_gpu()
+        m = matA if matA.is_complex else cmap(lambda v: v.astype(C128), matA)
+        nr, nc, ap, ai, az = m._tuple32()
+        out = np.zeros((nr, B.shape[1]), dtype=C128)
+        check("spl_mulm_z", lib().spl_mulm_z(nr, nc, p_i32(ap), p_i32(ai), p_f64(az), B.shape[0], B.shape[1],
+                                            p_f64(B.view(F64)), p_f64(out.view(F64))))
+        return out
     B = np.ascontiguousarray(matB, dtype=F64)
     if matA.ncols != B.shape[0]:
         _oops("mulM", "inner dimension mismatch")
