@@ -173,7 +173,11 @@ int spl_matrix_create(int nrows, int ncols, const int *Ap, const int *Ai, const 
  * compute  y <- a * x + y  per stored entry in ascending column order with Data.Complex's arithmetic, every
  * real operation separately rounded (csrc/spmv_z.hip: 20 bytes per stored entry instead of the 48 of the real
  * 2n x 2n embedding).  spl_matrix_spmv_many_dev is the fused product of such a handle with k vectors at once.
- * Other handle operations (spgemm, export, spmm, images) are for real handles. */
+ * spl_matrix_lin, _transpose, _ctrans, _hermitian, _spgemm, _export_csr and the LU from handles take complex handles
+ * as well.  Still for real handles only: spl_matrix_export_csc, spl_matrix_export_csr_rows, spl_matrix_spmm_dev and
+ * the SpMV images (spl_matrix_build_blocked / _build_panel, the sliced-ELL image; spl_matrix_optimize and
+ * spl_matrix_set_variant(H, 0) are accepted and do nothing).  The CSC fields of a complex handle are
+ * spl_matrix_export_csr of its spl_matrix_transpose. */
 int spl_matrix_create_z(int nrows, int ncols, const int *Ap, const int *Ai, const double *Az, void **H);
 /* 1 for a handle made by spl_matrix_create_z, 0 for a real one */
 int spl_matrix_is_complex(void *H);
@@ -186,8 +190,8 @@ int spl_matrix_create_rowblock(int nrows, int ncols, const int *Ap, const int *A
  * call sorts the rows that do not (indices and values together); rows that already ascend cost one check.
  * Duplicate column indices inside a row are NOT merged (that is spl_compress): they stay separate stored entries,
  * adjacent after the sort and in unspecified relative order.  The SpMV / SpMM kernels add every stored entry;
- * lin, spgemm, transpose, export_csc and the LU, which rely on strictly ascending indices, are undefined on such a
- * handle. */
+ * lin, spgemm, transpose, ctrans, hermitian, export_csc and the LU, which rely on strictly ascending indices, are
+ * undefined on such a handle. */
 int spl_matrix_create_csr(int64_t nrows_global, int64_t ncols, int64_t row0, int64_t nrows_local,
                           const int *rowptr, const int *colidx, const double *val, void **H);
 /* Synthetic workloads generated on the device (include/spl_synth.h):
@@ -201,7 +205,12 @@ int spl_matrix_create_rmat(int scale, int edge_factor, double a, double b, doubl
                            void **H);
 /* C = A * B on device-resident operands (mm, Sparse.hs:691-702); C gets 64-bit row
  * pointers, so nnz(C) >= 2^31 is fine.  *products (may be NULL) receives the number of
- * intermediate products. */
+ * intermediate products.  A may be a row block, B must be whole.
+ * Two complex handles give a complex C: the pattern of the real product of the two patterns, every value the sum
+ * over ascending k of A[i,k] * B[k,j] in Data.Complex's arithmetic, started from 0 — bit for bit spl_spgemm_z.  (The
+ * handles hold row-major images, so the column-wise kernel runs with the operands exchanged and forms b * a; with
+ * separately rounded operations the packed product is bitwise commutative.)  One real and one complex operand:
+ * SPL_ERROR_argument_missing and *HC = NULL (spl_matrix_to_complex first, the rule of spl_matrix_lin). */
 int spl_matrix_spgemm(void *HA, void *HB, void **HC, int64_t *products);
 void spl_matrix_free(void **H);
 
@@ -224,12 +233,28 @@ int spl_matrix_export_csr_rows(void *H, int64_t row0, int64_t row1, int64_t *row
  *   scalar kind; alpha / beta are (re, im) pairs, the imaginary parts must be 0 for real handles (complex scalars
  *   on real matrices: spl_matrix_to_complex first, as the reference's `cmap (:+ 0)` does, Feast.hs:214).
  * spl_matrix_to_complex: the Complex Double handle (x :+ 0) of a real one.
- * spl_matrix_transpose: handle of A^T (Sparse.hs:301-329); whole real matrices.
+ * spl_matrix_transpose: handle of A^T (Sparse.hs:301-329), real or complex (the values are moved unchanged); whole
+ *   matrices only, a row block is refused with SPL_ERROR_argument_missing.
+ * spl_matrix_ctrans: handle of the conjugate transpose, `omap conj . transpose` (Sparse.hs:371-375).  On a real handle
+ *   it is spl_matrix_transpose; on a complex one every value arrives as (re, -im), the sign of the imaginary part
+ *   flipped as `conjugate` does (+0.0 becomes -0.0), in the same pass that moves the values.  Statuses and refusals
+ *   are spl_matrix_transpose's.
+ * spl_matrix_hermitian: *result = 1 if `ctrans m == m` under the derived Eq of Sparse.hs:78 (dimensions, pointers,
+ *   indices and values, the values with IEEE ==), else 0 (`hermitian`, Sparse.hs:377-379).  Real and complex handles,
+ *   whole matrices only.  A matrix that is not square is SPL_OK with *result = 0.  IEEE ==: a NaN anywhere gives 0,
+ *   -0.0 equals +0.0 (a real symmetric matrix promoted by spl_matrix_to_complex is Hermitian), a diagonal entry needs
+ *   a zero imaginary part, a stored zero whose mirror is not stored gives 0.  The transpose is not built: one kernel
+ *   looks every stored entry's mirror up by bisection (csrc/hermitian.hip).  The call synchronises.  Statuses:
+ *   SPL_ERROR_invalid_handle; SPL_ERROR_argument_missing (result == NULL, or a row block); SPL_ERROR_index_overflow
+ *   (nnz >= 2^31).  Like lin and spgemm it relies on strictly ascending indices: undefined on a handle made by
+ *   spl_matrix_create_csr from rows with duplicate indices.
  * spl_matrix_compress_dev: COO triples in DEVICE memory -> handle (compress / fromTriples, Sparse.hs:184-280):
  *   bounds checked rows first, then columns (*bad = first offending position, may be NULL), duplicates summed. */
 int spl_matrix_lin(void *HA, const double alpha[2], void *HB, const double beta[2], void **HC);
 int spl_matrix_to_complex(void *H, void **HZ);
 int spl_matrix_transpose(void *H, void **HT);
+int spl_matrix_ctrans(void *H, void **HC);
+int spl_matrix_hermitian(void *H, int *result);
 int spl_matrix_compress_dev(int nrows, int ncols, int64_t ntriples, const int *d_rows, const int *d_cols,
                             const double *d_vals, void **H, int64_t *bad);
 /* transpose the block on the device (Sparse.hs:301-329) and copy out its

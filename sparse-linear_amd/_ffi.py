@@ -110,6 +110,8 @@ def _declare(L):
         "spl_matrix_lin": [C.c_void_p, c_dbl_p, C.c_void_p, c_dbl_p, c_void_pp],
         "spl_matrix_to_complex": [C.c_void_p, c_void_pp],
         "spl_matrix_transpose": [C.c_void_p, c_void_pp],
+        "spl_matrix_ctrans": [C.c_void_p, c_void_pp],
+        "spl_matrix_hermitian": [C.c_void_p, c_int_p],
         "spl_matrix_compress_dev": [i, i, i64, C.c_void_p, C.c_void_p, C.c_void_p, c_void_pp, c_i64_p],
         "spl_matrix_info": [C.c_void_p, c_i64_p],
         "spl_matrix_export_csr": [C.c_void_p, c_i64_p, c_int_p, c_dbl_p],

@@ -455,19 +455,24 @@ int spl_matrix_spgemm(void *HA, void *HB, void **HC, int64_t *products) {
   if (!A || !B) return SPL_ERROR_invalid_handle;
   if (!HC) return SPL_ERROR_argument_missing;
   *HC = nullptr;
-  if (A->vw != 1 || B->vw != 1) return SPL_ERROR_argument_missing;  // complex products: through the host mirror
+  if (A->vw != B->vw) return SPL_ERROR_argument_missing;  // one real, one complex: spl_matrix_to_complex first
   if (A->ncols != B->nrows_global || B->row0 != 0 || B->nrows_local != B->nrows_global)
     return SPL_ERROR_dimension_mismatch;  // Sparse.hs:694 (B must be whole; A may be a row block)
   if (!A->rowptr.get() || !B->rowptr.get()) return SPL_ERROR_index_overflow;
   return guarded([&]() -> int {
     DeviceGuard g(A->device);
     hipStream_t s = nullptr;
-    std::unique_ptr<Matrix> C = make_matrix(A->device, A->nrows_global, B->ncols, A->row0, A->nrows_local);
+    std::unique_ptr<Matrix> C = make_matrix(A->device, A->nrows_global, B->ncols, A->row0, A->nrows_local, A->vw);
     // rows of A*B = columns of (A*B)^T = B^T * A^T: the CSR arrays of B and A are the CSC
     // arrays of B^T and A^T, so the column-wise kernel runs on them unchanged
-    spgemm_device(B->ncols, B->nrows_global, B->rowptr.get(), B->colidx.get(), B->val.get(), A->nrows_local,
-                  A->rowptr.get(), A->colidx.get(), A->val.get(), C->rowptr64, C->colidx, C->val, &C->nnz,
-                  products, s);
+    if (A->vw == 1)
+      spgemm_device(B->ncols, B->nrows_global, B->rowptr.get(), B->colidx.get(), B->val.get(), A->nrows_local,
+                    A->rowptr.get(), A->colidx.get(), A->val.get(), C->rowptr64, C->colidx, C->val, &C->nnz,
+                    products, s);
+    else  // the value kernel then forms b * a for the reference's a * b: the same bits, every operation rounded once
+      spgemm_device_z(B->ncols, B->nrows_global, B->rowptr.get(), B->colidx.get(), B->val.get(), A->nrows_local,
+                      A->rowptr.get(), A->colidx.get(), A->val.get(), C->rowptr64, C->colidx, C->val, &C->nnz,
+                      products, s);
     return publish(std::move(C), s, HC);
   });
 }
@@ -535,25 +540,56 @@ int spl_matrix_to_complex(void *H, void **HZ) {
   });
 }
 
-// handle of the transpose (Sparse.hs:301-329 on the device, no host round trip); whole matrices only
-int spl_matrix_transpose(void *H, void **HT) {
+namespace {
+// handle of the transpose of a whole matrix, real or complex (Sparse.hs:301-329 on the device, no host round trip);
+// conjugate: of the conjugate transpose (Sparse.hs:371-375), which on a real handle is the same thing
+int transpose_handle(void *H, void **HT, bool conjugate) {
   Matrix *A = as_matrix(H);
   if (!A) return SPL_ERROR_invalid_handle;
   if (!HT) return SPL_ERROR_argument_missing;
   *HT = nullptr;
-  if (A->vw != 1 || A->row0 != 0 || A->nrows_local != A->nrows_global) return SPL_ERROR_argument_missing;
+  if (A->row0 != 0 || A->nrows_local != A->nrows_global) return SPL_ERROR_argument_missing;
   if (!A->rowptr.get()) return SPL_ERROR_index_overflow;
   return guarded([&]() -> int {
     DeviceGuard g(A->device);
     hipStream_t s = nullptr;
-    std::unique_ptr<Matrix> C = make_matrix(A->device, A->ncols, A->nrows_global, 0, A->ncols);
+    std::unique_ptr<Matrix> C = make_matrix(A->device, A->ncols, A->nrows_global, 0, A->ncols, A->vw);
     C->nnz = A->nnz;
     C->rowptr64.alloc((size_t)A->ncols + 1);
     C->colidx.alloc((size_t)A->nnz);
-    C->val.alloc((size_t)A->nnz);
-    transpose_compressed(A->rowptr.get(), A->colidx.get(), A->val.get(), A->nrows_local, A->ncols, A->nnz,
-                         C->rowptr64.get(), C->colidx.get(), C->val.get(), s);
+    C->val.alloc((size_t)A->nnz * (size_t)A->vw);
+    if (A->vw == 1) {
+      transpose_compressed(A->rowptr.get(), A->colidx.get(), A->val.get(), A->nrows_local, A->ncols, A->nnz,
+                           C->rowptr64.get(), C->colidx.get(), C->val.get(), s);
+    } else {
+      // packed complex, as build_from_csc: transpose the pattern with the entry positions as payload, then gather
+      // the 16-byte values along the permutation — conjugating them in that pass when asked to
+      DBuf<double> pos((size_t)A->nnz), perm((size_t)A->nnz);
+      fill_positions(A->nnz, pos.get(), s);
+      transpose_compressed(A->rowptr.get(), A->colidx.get(), pos.get(), A->nrows_local, A->ncols, A->nnz,
+                           C->rowptr64.get(), C->colidx.get(), perm.get(), s);
+      gather_complex_values(A->nnz, perm.get(), A->val.get(), C->val.get(), s, conjugate);
+      SPL_HIP(hipStreamSynchronize(s));  // perm is released on return
+    }
     return publish(std::move(C), s, HT);
+  });
+}
+}  // namespace
+
+int spl_matrix_transpose(void *H, void **HT) { return transpose_handle(H, HT, false); }
+
+int spl_matrix_ctrans(void *H, void **HC) { return transpose_handle(H, HC, true); }
+
+// hermitian m = ctrans m == m (Sparse.hs:377-379) without building ctrans m (hermitian.hip); synchronises
+int spl_matrix_hermitian(void *H, int *result) {
+  Matrix *A = as_matrix(H);
+  if (!A) return SPL_ERROR_invalid_handle;
+  if (!result || A->row0 != 0 || A->nrows_local != A->nrows_global) return SPL_ERROR_argument_missing;
+  if (!A->rowptr.get()) return SPL_ERROR_index_overflow;
+  return guarded([&]() -> int {
+    DeviceGuard g(A->device);
+    *result = hermitian_device(A, nullptr);
+    return SPL_OK;
   });
 }
 
@@ -1095,7 +1131,7 @@ int spl_spgemm_z(int nrowsA, int ncolsA, const int *Ap, const int *Ai, const dou
   return binary_one_shot(2, {nrowsA, ncolsA, Ap, Ai, Az}, {nrowsB, ncolsB, Bp, Bi, Bz}, nrowsA, ncolsB, nrowsC, ncolsC,
                          Cp, Ci, Cz, [&](DeviceCsc &A, DeviceCsc &B, DeviceResult &C, hipStream_t s) {
                            spgemm_device_z(nrowsA, ncolsA, A.p.get(), A.i.get(), A.x.get(), ncolsB, B.p.get(),
-                                           B.i.get(), B.x.get(), C.p, C.i, C.x, &C.nnz, s);
+                                           B.i.get(), B.x.get(), C.p, C.i, C.x, &C.nnz, nullptr, s);
                          });
 }
 

@@ -293,7 +293,7 @@ void spgemm_device(int64_t nrowsA, int64_t ncolsA, const int *Ap, const int *Ai,
 // mm on packed Complex Double (spgemm_z.hip): pattern from the real kernels, values in the reference's order
 void spgemm_device_z(int64_t nrowsA, int64_t ncolsA, const int *Ap, const int *Ai, const double *Az, int64_t ncolsB,
                      const int *Bp, const int *Bi, const double *Bz, DBuf<int64_t> &Cp, DBuf<int> &Ci,
-                     DBuf<double> &Cz, int64_t *nnzC, hipStream_t s);
+                     DBuf<double> &Cz, int64_t *nnzC, int64_t *products, hipStream_t s);
 
 // ---- blocked band LU without interchanges (band_nopiv.hip) --------------------------------------
 bool band_is_column_dominant(int n, const int *d_Ap, const int *d_Ai, const double *d_Ax, hipStream_t s);
@@ -332,7 +332,12 @@ int transpose_dense(int64_t rows, int64_t cols, int vw, const double *d_in, doub
 // Complex Double (spmv_z.hip): d_x, d_y packed (re, im) pairs
 int launch_spmv_z(const Matrix *m, const double *d_x, double *d_y, int accumulate, hipStream_t s);
 void fill_positions(int64_t n, double *d_out, hipStream_t s);
-void gather_complex_values(int64_t n, const double *d_pos, const double *d_in, double *d_out, hipStream_t s);
+// d_out[i] = d_in[d_pos[i]] on packed pairs; conjugate: (re, -im), the sign bit flipped (conj of Data.Complex)
+void gather_complex_values(int64_t n, const double *d_pos, const double *d_in, double *d_out, hipStream_t s,
+                           bool conjugate = false);
+// `ctrans m == m` (Sparse.hs:377-379 under the derived Eq) on the CSR image of a whole square handle with strictly
+// ascending indices, real or packed complex: 1 or 0, without building the transpose (hermitian.hip); synchronises s
+int hermitian_device(const Matrix *m, hipStream_t s);
 int64_t sell_padded_entries(const Matrix *m, hipStream_t s);
 void build_sell_image(Matrix *m, hipStream_t s);
 int launch_spmv_sell(const Matrix *m, const double *d_x, double *d_y, int accumulate, hipStream_t s);

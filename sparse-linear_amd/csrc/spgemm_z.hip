@@ -109,12 +109,12 @@ __global__ __launch_bounds__(256) void mm_values_z_kernel(
 // C = A B on packed-complex device CSC arrays with sorted columns; Cz gets 2 * nnz(C) doubles
 void spgemm_device_z(int64_t nrowsA, int64_t ncolsA, const int *Ap, const int *Ai, const double *Az, int64_t ncolsB,
                      const int *Bp, const int *Bi, const double *Bz, DBuf<int64_t> &Cp, DBuf<int> &Ci,
-                     DBuf<double> &Cz, int64_t *nnzC, hipStream_t s) {
+                     DBuf<double> &Cz, int64_t *nnzC, int64_t *products, hipStream_t s) {
   {
     // pattern: the real kernels on the two patterns; they read nnz doubles of "values" — the first halves of
     // the packed arrays serve, the products are thrown away
     DBuf<double> unused;
-    spgemm_device(nrowsA, ncolsA, Ap, Ai, Az, ncolsB, Bp, Bi, Bz, Cp, Ci, unused, nnzC, nullptr, s);
+    spgemm_device(nrowsA, ncolsA, Ap, Ai, Az, ncolsB, Bp, Bi, Bz, Cp, Ci, unused, nnzC, products, s);
   }
   Cz.alloc((size_t)*nnzC * 2);
   if (*nnzC == 0 || ncolsB == 0) return;

@@ -94,10 +94,16 @@ __global__ __launch_bounds__(256) void iota_f64_kernel(int64_t n, double *__rest
   if (i < n) out[i] = (double)i;
 }
 
+// Conj: the value arrives as (re, -im) — a negation, so +0.0 becomes -0.0 as `conjugate` makes it
+template <bool Conj>
 __global__ __launch_bounds__(256) void gather_z_kernel(int64_t n, const double *__restrict__ pos, const double2v *__restrict__ in,
                                                        double2v *__restrict__ out) {
   const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i < n) out[i] = in[(int64_t)pos[i]];
+  if (i < n) {
+    double2v v = in[(int64_t)pos[i]];
+    if (Conj) v.y = -v.y;
+    out[i] = v;
+  }
 }
 
 }  // namespace
@@ -126,10 +132,16 @@ int launch_spmv_z(const Matrix *m, const double *d_x, double *d_y, int accumulat
 void fill_positions(int64_t n, double *d_out, hipStream_t s) {
   if (n > 0) hipLaunchKernelGGL(iota_f64_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, n, d_out);
 }
-void gather_complex_values(int64_t n, const double *d_pos, const double *d_in, double *d_out, hipStream_t s) {
-  if (n > 0)
-    hipLaunchKernelGGL(gather_z_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, n, d_pos,
-                       reinterpret_cast<const double2v *>(d_in), reinterpret_cast<double2v *>(d_out));
+void gather_complex_values(int64_t n, const double *d_pos, const double *d_in, double *d_out, hipStream_t s,
+                           bool conjugate) {
+  if (n <= 0) return;
+  const dim3 grid((unsigned)((n + 255) / 256));
+  const double2v *in = reinterpret_cast<const double2v *>(d_in);
+  double2v *out = reinterpret_cast<double2v *>(d_out);
+  if (conjugate)
+    hipLaunchKernelGGL(gather_z_kernel<true>, grid, dim3(256), 0, s, n, d_pos, in, out);
+  else
+    hipLaunchKernelGGL(gather_z_kernel<false>, grid, dim3(256), 0, s, n, d_pos, in, out);
 }
 
 }  // namespace spl

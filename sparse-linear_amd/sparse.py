@@ -260,7 +260,7 @@ class DeviceMatrix(object):
         return cls(h.value)
 
     def spgemm(self, other):
-        """device-resident C = self * other; returns (DeviceMatrix C, number of products)"""
+        """device-resident C = self * other, both real or both complex; returns (DeviceMatrix C, number of products)"""
         h = C.c_void_p()
         prod = C.c_int64(0)
         check("spl_matrix_spgemm", lib().spl_matrix_spgemm(self.handle, other.handle, C.byref(h), C.byref(prod)))
@@ -281,10 +281,22 @@ class DeviceMatrix(object):
         return DeviceMatrix(h.value)
 
     def transpose(self):
-        """device-resident transpose (Sparse.hs:301-329)"""
+        """device-resident transpose (Sparse.hs:301-329), real or complex; whole matrices"""
         h = C.c_void_p()
         check("spl_matrix_transpose", lib().spl_matrix_transpose(self.handle, C.byref(h)))
         return DeviceMatrix(h.value)
+
+    def ctrans(self):
+        """device-resident conjugate transpose (Sparse.hs:371-375); on a real handle the transpose"""
+        h = C.c_void_p()
+        check("spl_matrix_ctrans", lib().spl_matrix_ctrans(self.handle, C.byref(h)))
+        return DeviceMatrix(h.value)
+
+    def hermitian(self):
+        """`ctrans m == m` (Sparse.hs:377-379) decided on the device without building ctrans m; synchronises"""
+        r = C.c_int(0)
+        check("spl_matrix_hermitian", lib().spl_matrix_hermitian(self.handle, C.byref(r)))
+        return bool(r.value)
 
     @classmethod
     def compress_dev(cls, nrows, ncols, ntriples, rows_ptr, cols_ptr, vals_ptr):
