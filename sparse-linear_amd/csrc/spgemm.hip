@@ -2133,6 +2133,7 @@ void spgemm_device(int64_t nrowsA, int64_t ncolsA, const int *Ap, const int *Ai,
 #undef SPL_NUMERIC_WAVE
 #undef SPL_NUMERIC_BLOCK
   lap("numeric: wavefront and workgroup bins");
+  int plan_dense = 0;  // columns that reached the dense accumulators (for the plan line)
   if (ndense > 0) {
     DBuf<unsigned long long> dstamps;
     if (getenv("SPL_SPGEMM_STAMPS")) {
@@ -2140,6 +2141,7 @@ void spgemm_device(int64_t nrowsA, int64_t ncolsA, const int *Ap, const int *Ai,
       SPL_HIP(hipMemsetAsync(dstamps.get(), 0, 4 * sizeof(unsigned long long), s));
     }
     const int nfb = run_range(true, numeric_counts, slots, out_i, out_x);
+    plan_dense = nfb;
     lap("numeric: heavy columns, row ranges");
     if (nfb > 0) {
       ensure_pool(nfb);
@@ -2156,6 +2158,13 @@ void spgemm_device(int64_t nrowsA, int64_t ncolsA, const int *Ap, const int *Ai,
               "column %llu ticks; medium %d, xlarge %d + %d columns\n", ndense, pool, h[0], h[1], h[2], nmedium, nxlarge, nxback);
     }
   }
+  // which kernels served this product: the form, the flags every dispatch decision above depends on and the number of
+  // columns in each list (tests/test_gpu_spgemm_bins.py compares this line with a host mirror of the rules)
+  if (timing)
+    fprintf(stderr, "[spgemm] plan: rows=%lld single_pass=%d ordered=%d shape=%s x_heavy=%d range=%d key32=%d/%d/%d medium=%d "
+            "xlarge=%d xback=%d heavy=%d dense=%d\n", (long long)nrowsA, single_pass ? 1 : 0, ordered ? 1 : 0,
+            !ordered ? "none" : large_shape ? "large" : "small", x_heavy, use_range ? 1 : 0, key32_s ? 1 : 0, key32_m ? 1 : 0,
+            key32_x ? 1 : 0, nmedium, nxlarge, nxback, ndense, plan_dense);
   if (ordered) {
     // ---- every column to its final place, in column order
     // capacity of the result: the exact lengths of the columns computed beforehand + the products of the others

@@ -2,7 +2,8 @@
 """Fuzz of mm (Sparse.hs:691-702) on structures the R-MAT generator never makes: hub columns in A, heavy and empty
 columns in B, rows crowded into narrow ranges, rectangular shapes, real and complex values — through every form of
 the SpGEMM (automatic choice, ordered single pass in both column shapes, compacting single pass, symbolic + numeric two-pass, split sort
-keys), each compared with the oracle bit for bit (structure and values).
+keys, bin X on its own, no row-range kernel; every case takes the automatic choice and five of the seven forced forms, in
+rotation), each compared with the oracle bit for bit (structure and values).
 python tools/fuzz_spgemm.py [seed] [cases]"""
 import os
 import sys
@@ -15,8 +16,10 @@ sys.path.insert(0, ROOT)
 
 FORMS = ({}, {"SPL_SPGEMM_ORDERED": "1", "SPL_SPGEMM_ORDERED_SHAPE": "small"},
          {"SPL_SPGEMM_ORDERED": "1", "SPL_SPGEMM_ORDERED_SHAPE": "large"}, {"SPL_SPGEMM_ORDERED": "0"},
-         {"SPL_SPGEMM_TWO_PASS": "1"}, {"SPL_SPGEMM_SPLIT_KEYS": "1"})
-KEYS = ("SPL_SPGEMM_ORDERED", "SPL_SPGEMM_ORDERED_SHAPE", "SPL_SPGEMM_TWO_PASS", "SPL_SPGEMM_SPLIT_KEYS")
+         {"SPL_SPGEMM_TWO_PASS": "1"}, {"SPL_SPGEMM_SPLIT_KEYS": "1"}, {"SPL_SPGEMM_X_AS_HEAVY": "0"},
+         {"SPL_SPGEMM_RANGE": "0"})
+KEYS = ("SPL_SPGEMM_ORDERED", "SPL_SPGEMM_ORDERED_SHAPE", "SPL_SPGEMM_TWO_PASS", "SPL_SPGEMM_SPLIT_KEYS",
+        "SPL_SPGEMM_X_AS_HEAVY", "SPL_SPGEMM_RANGE")
 
 
 def pattern(rng, kind, nr, nc, k):
@@ -44,10 +47,12 @@ def main():
     rng = np.random.default_rng(seed)
     bad = calls = 0
     for case in range(ncase):
-        m = int(rng.choice([1, 5, 64, 300, 2049, 6000, 20000]))
+        # (2^21 + 1 rows: beyond the ordered form, bin X as heavy and the row-range kernel; rows cost nothing, so the
+        # number of entries of A is capped as if there were 20 000 of them)
+        m = int(rng.choice([1, 5, 64, 300, 2049, 6000, 20000, (1 << 21) + 1]))
         n = int(rng.choice([1, 7, 128, 700, 4000, 12000]))
         p = int(rng.choice([1, 3, 100, 900, 5000]))
-        ka, kb = int(rng.integers(0, 12 * max(m, n) + 1)), int(rng.integers(0, 8 * max(n, p) + 1))
+        ka, kb = int(rng.integers(0, 12 * max(min(m, 20000), n) + 1)), int(rng.integers(0, 8 * max(n, p) + 1))
         cplx = case % 4 == 3
         ra, ca = pattern(rng, case % 4 if not cplx else 1, m, n, ka)
         rb, cb = pattern(rng, (case // 4) % 4, n, p, kb)
@@ -61,7 +66,10 @@ def main():
         else:
             ref = O.mm(A, B)
         Am, Bm = pkg.Matrix(n, m, A[2], A[3], A[4]), pkg.Matrix(p, n, B[2], B[3], B[4])
-        for form in FORMS:
+        # the automatic choice and five of the seven forced forms, in rotation: six products per case
+        start = case % (len(FORMS) - 1)
+        forced = [FORMS[1 + (start + t) % (len(FORMS) - 1)] for t in range(5)]
+        for form in [FORMS[0]] + forced:
             for k_ in KEYS:
                 os.environ.pop(k_, None)
             os.environ.update(form)
