@@ -173,8 +173,8 @@ int spl_matrix_create(int nrows, int ncols, const int *Ap, const int *Ai, const 
  * compute  y <- a * x + y  per stored entry in ascending column order with Data.Complex's arithmetic, every
  * real operation separately rounded (csrc/spmv_z.hip: 20 bytes per stored entry instead of the 48 of the real
  * 2n x 2n embedding).  spl_matrix_spmv_many_dev is the fused product of such a handle with k vectors at once.
- * spl_matrix_lin, _transpose, _ctrans, _hermitian, _spgemm, _export_csr and the LU from handles take complex handles
- * as well.  Still for real handles only: spl_matrix_export_csc, spl_matrix_export_csr_rows, spl_matrix_spmm_dev and
+ * spl_matrix_lin, _transpose, _ctrans, _hermitian, _spgemm, _kronecker, _assemble_blocks, _take_diag_dev, _export_csr
+ * and the LU from handles take complex handles as well, and spl_matrix_diag_dev makes one.  Still for real handles only: spl_matrix_export_csc, spl_matrix_export_csr_rows, spl_matrix_spmm_dev and
  * the SpMV images (spl_matrix_build_blocked / _build_panel, the sliced-ELL image; spl_matrix_optimize and
  * spl_matrix_set_variant(H, 0) are accepted and do nothing).  The CSC fields of a complex handle are
  * spl_matrix_export_csr of its spl_matrix_transpose. */
@@ -257,6 +257,43 @@ int spl_matrix_ctrans(void *H, void **HC);
 int spl_matrix_hermitian(void *H, int *result);
 int spl_matrix_compress_dev(int nrows, int ncols, int64_t ntriples, const int *d_rows, const int *d_cols,
                             const double *d_vals, void **H, int64_t *bad);
+/* ---- the structural constructors on handles: a model problem is assembled where it will be factored --------------
+ * Common to the four calls below: operands are whole matrices (a row block: SPL_ERROR_argument_missing, as
+ * spl_matrix_transpose answers), all of one value kind and on one device (a real with a complex operand, or two
+ * devices: SPL_ERROR_argument_missing and a NULL output; spl_matrix_to_complex first, the rule of spl_matrix_lin).
+ * Something that is no matrix handle: SPL_ERROR_invalid_handle.  A NULL output pointer: SPL_ERROR_argument_missing.
+ * All argument checks come before the device is touched (without a GPU the calls answer the same up to there, and
+ * SPL_ERROR_device after).  The results are ordinary handles — 64-bit row pointers always, int32 ones when nnz fits —
+ * and nnz >= 2^31 is fine.  Like lin and spgemm the calls rely on strictly ascending indices in their operands.
+ *
+ * spl_matrix_kronecker: C = A (x) B (`kronecker`, Sparse.hs:597-634): column ja * ncolsB + jb holds the rows
+ *   ia * nrowsB + ib, ia outer, with the values b * a — structure and values bit for bit the reference's; on complex
+ *   handles b * a in Data.Complex's order, (br*ar - bi*ai) :+ (br*ai + bi*ar), every real operation rounded once.
+ *   Nothing is counted on the device: the row starts and nnz(C) = nnz(A) nnz(B) are known in closed form, one kernel
+ *   writes pointers, indices and values.  SPL_ERROR_index_overflow when nrowsA * nrowsB or ncolsA * ncolsB reaches
+ *   2^31.  Synchronises (the handle is finished before it is returned, like every result handle).
+ * spl_matrix_assemble_blocks: hcat / vcat / fromBlocks / fromBlocksDiag / blockDiag (Sparse.hs:500-595, 661-667) in one
+ *   call: block b = H[b] is placed at (row_off[b], col_off[b]) of an nrowsC x ncolsC result.  The blocks are disjoint
+ *   rectangles and may be listed in any order: the result does not depend on it.  Blocks without rows or without
+ *   columns are legal; nblocks == 0 gives `zeros` (Sparse.hs:673-679) of that shape, real, on the current device.
+ *   Values are moved, never combined.  hcat: row_off = 0, col_off = running widths; vcat: col_off = 0, row_off =
+ *   running heights; fromBlocks: both; blockDiag: both running.  The number of launches does not depend on nblocks.
+ *   Statuses: SPL_ERROR_dimension_mismatch (a block leaves the result, or two blocks overlap: decided on the host from
+ *   the rectangles); SPL_ERROR_n_nonpositive (nblocks, nrowsC or ncolsC < 0); SPL_ERROR_index_overflow (nrowsC or
+ *   ncolsC >= 2^31); SPL_ERROR_argument_missing (H, row_off or col_off NULL with nblocks > 0).  Synchronises.
+ * spl_matrix_take_diag_dev: d_out[c] = A[c,c], or 0 where nothing is stored, c < min(nrows, ncols) (`takeDiag`,
+ *   Sparse.hs:640-650).  d_out is DEVICE memory: doubles, or packed (re, im) pairs on a complex handle.  The kernel is
+ *   enqueued on `stream`; the call does not synchronise.  d_out == NULL with min(nrows, ncols) > 0:
+ *   SPL_ERROR_argument_missing.
+ * spl_matrix_diag_dev: `diag` (Sparse.hs:652-659) of n values in DEVICE memory on the current device, value_width 1
+ *   (doubles) or 2 (packed pairs: a complex handle).  d_values == NULL: ones, i.e. `ident n` (Sparse.hs:669-671) without
+ *   an upload.  n == 0 is the 0 x 0 matrix.  SPL_ERROR_n_nonpositive (n < 0); SPL_ERROR_argument_missing (another
+ *   width); SPL_ERROR_index_overflow (n >= 2^31).  Synchronises. */
+int spl_matrix_kronecker(void *HA, void *HB, void **HC);
+int spl_matrix_assemble_blocks(int nblocks, void *const *H, const int64_t *row_off, const int64_t *col_off,
+                               int64_t nrowsC, int64_t ncolsC, void **HC);
+int spl_matrix_take_diag_dev(void *H, double *d_out, void *stream);
+int spl_matrix_diag_dev(int64_t n, const double *d_values, int value_width, void **H);
 /* transpose the block on the device (Sparse.hs:301-329) and copy out its
  * column-major image: colptr[ncols+1], rowidx[nnz_local] (LOCAL row ids, ascending
  * inside a column), val[nnz_local] — i.e. the reference's own CSC Matrix fields */

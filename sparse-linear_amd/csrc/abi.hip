@@ -593,6 +593,95 @@ int spl_matrix_hermitian(void *H, int *result) {
   });
 }
 
+// ---- the structural constructors, handle to handle (csrc/assemble_handles.hip) ------------------------------------
+namespace {
+bool whole(const Matrix *m) { return m->row0 == 0 && m->nrows_local == m->nrows_global; }
+}  // namespace
+
+// C = A (x) B (`kronecker`, Sparse.hs:597-634).  A handle holds the ROW-major image, i.e. the CSC fields of the
+// transpose, and (A (x) B)^T = A^T (x) B^T: the reference's walk — for every entry of A's column, every entry of B's,
+// index ia * nrowsB + ib, value b * a — applied to the two row images writes the row image of A (x) B, so the handle
+// that comes out is the reference's result, structure and values.
+int spl_matrix_kronecker(void *HA, void *HB, void **HC) {
+  Matrix *A = as_matrix(HA), *B = as_matrix(HB);
+  if (!A || !B) return SPL_ERROR_invalid_handle;
+  if (!HC) return SPL_ERROR_argument_missing;
+  *HC = nullptr;
+  if (!whole(A) || !whole(B)) return SPL_ERROR_argument_missing;
+  if (A->vw != B->vw || A->device != B->device) return SPL_ERROR_argument_missing;  // spl_matrix_to_complex first
+  const int64_t nrowsC = A->nrows_global * B->nrows_global, ncolsC = A->ncols * B->ncols;  // both factors < 2^31
+  if (nrowsC >= 0x80000000LL || ncolsC >= 0x80000000LL) return SPL_ERROR_index_overflow;
+  return guarded([&]() -> int {
+    DeviceGuard g(A->device);
+    hipStream_t s = nullptr;
+    std::unique_ptr<Matrix> C = make_matrix(A->device, nrowsC, ncolsC, 0, nrowsC, A->vw);
+    kronecker_handles(A, B, C.get(), s);
+    return publish(std::move(C), s, HC);
+  });
+}
+
+// hcat / vcat / fromBlocks / fromBlocksDiag / blockDiag (Sparse.hs:500-595, 661-667) as one placement of blocks.  In the
+// reference column c of the result is the blocks' columns one after the other by ascending row offset; on the row
+// images the same holds with rows and columns exchanged: row r is the rows of the blocks that cover it by ascending
+// COLUMN offset.  The rectangles are disjoint, so either way every entry lands where the reference puts it.
+int spl_matrix_assemble_blocks(int nblocks, void *const *H, const int64_t *row_off, const int64_t *col_off,
+                               int64_t nrowsC, int64_t ncolsC, void **HC) {
+  if (nblocks < 0) return SPL_ERROR_n_nonpositive;
+  if (nblocks > 0 && !H) return SPL_ERROR_argument_missing;
+  std::vector<const Matrix *> blk((size_t)nblocks);
+  for (int b = 0; b < nblocks; ++b)
+    if (!(blk[(size_t)b] = as_matrix(H[b]))) return SPL_ERROR_invalid_handle;
+  if (!HC || (nblocks > 0 && (!row_off || !col_off))) return SPL_ERROR_argument_missing;
+  *HC = nullptr;
+  if (nrowsC < 0 || ncolsC < 0) return SPL_ERROR_n_nonpositive;
+  for (int b = 0; b < nblocks; ++b) {
+    if (!whole(blk[(size_t)b])) return SPL_ERROR_argument_missing;
+    if (blk[(size_t)b]->vw != blk[0]->vw || blk[(size_t)b]->device != blk[0]->device) return SPL_ERROR_argument_missing;
+  }
+  if (nrowsC >= 0x80000000LL || ncolsC >= 0x80000000LL) return SPL_ERROR_index_overflow;
+  std::vector<int> cut, lptr, list;
+  const int st = blocks_table(nblocks, blk.data(), row_off, col_off, nrowsC, ncolsC, cut, lptr, list);
+  if (st != SPL_OK) return st;
+  return guarded([&]() -> int {
+    const int dev = nblocks > 0 ? blk[0]->device : current_device();  // no block: `zeros` on the current device
+    DeviceGuard g(dev);
+    hipStream_t s = nullptr;
+    std::unique_ptr<Matrix> C = make_matrix(dev, nrowsC, ncolsC, 0, nrowsC, nblocks > 0 ? blk[0]->vw : 1);
+    assemble_handles(nblocks, blk.data(), row_off, col_off, cut, lptr, list, C.get(), s);
+    return publish(std::move(C), s, HC);
+  });
+}
+
+// d_out[c] = A[c, c] or 0 (`takeDiag`, Sparse.hs:640-650): the diagonal of the row image is the diagonal
+int spl_matrix_take_diag_dev(void *H, double *d_out, void *stream) {
+  Matrix *A = as_matrix(H);
+  if (!A) return SPL_ERROR_invalid_handle;
+  if (!whole(A)) return SPL_ERROR_argument_missing;
+  const int64_t n = A->nrows_global < A->ncols ? A->nrows_global : A->ncols;
+  if (n > 0 && !d_out) return SPL_ERROR_argument_missing;
+  return guarded([&]() -> int {
+    DeviceGuard g(A->device);
+    take_diag_handle(A, n, d_out, as_stream(stream));
+    return SPL_OK;
+  });
+}
+
+// `diag` (Sparse.hs:652-659) of n values in device memory; without values `ident n` (Sparse.hs:669-671)
+int spl_matrix_diag_dev(int64_t n, const double *d_values, int value_width, void **H) {
+  if (!H) return SPL_ERROR_argument_missing;
+  *H = nullptr;
+  if (n < 0) return SPL_ERROR_n_nonpositive;
+  if (value_width != 1 && value_width != 2) return SPL_ERROR_argument_missing;
+  if (n >= 0x80000000LL) return SPL_ERROR_index_overflow;
+  return guarded([&]() -> int {
+    const int dev = current_device();
+    hipStream_t s = nullptr;
+    std::unique_ptr<Matrix> C = make_matrix(dev, n, n, 0, n, value_width);
+    diag_handle(d_values, C.get(), s);
+    return publish(std::move(C), s, H);
+  });
+}
+
 // COO triples in device memory -> handle (compress / fromTriples, Sparse.hs:184-280: bounds checked rows first,
 // then columns; duplicates summed in input order).  *bad receives the first offending position on
 // SPL_ERROR_index_out_of_bounds (may be NULL).

@@ -253,6 +253,19 @@ void blocks_assemble_device(int nblocks, const int *ncols_b, const int *const *d
                             const double *const *d_Bx, int vw, const int *row_off, const int *col_off, int64_t ncolsC,
                             DBuf<int64_t> &Cp, DBuf<int> &Ci, DBuf<double> &Cx, int64_t *nnzC, hipStream_t s);
 
+// ---- the structural constructors on handles (assemble_handles.hip) -----------------------------------------
+// C's dimensions, block and value kind are set by the caller; these fill rowptr64 / colidx / val / nnz on stream s
+void kronecker_handles(const Matrix *A, const Matrix *B, Matrix *C, hipStream_t s);
+// host: the interval table of nblocks placed rectangles; SPL_ERROR_dimension_mismatch when one leaves the
+// nrowsC x ncolsC result or two overlap
+int blocks_table(int nblocks, const Matrix *const *blk, const int64_t *row_off, const int64_t *col_off, int64_t nrowsC,
+                 int64_t ncolsC, std::vector<int> &cut, std::vector<int> &lptr, std::vector<int> &list);
+void assemble_handles(int nblocks, const Matrix *const *blk, const int64_t *row_off, const int64_t *col_off,
+                      const std::vector<int> &cut, const std::vector<int> &lptr, const std::vector<int> &list, Matrix *C,
+                      hipStream_t s);
+void take_diag_handle(const Matrix *A, int64_t n, double *d, hipStream_t s);  // enqueues; does not synchronise
+void diag_handle(const double *d_values, Matrix *C, hipStream_t s);           // d_values == nullptr: ones
+
 // ---- multifrontal LU without interchanges (multifrontal.hip, mf_symbolic.hpp) ------------------
 namespace mf {
 struct Tree;

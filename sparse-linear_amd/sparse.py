@@ -15,7 +15,9 @@ the shared library or a GPU is missing they raise.
 The purely structural combinators (``hcat``, ``vcat``, ``fromBlocks*``,
 ``kronecker``, ``diag``, ``ident``, ``zeros``, ``takeDiag``, ``pack`` …) only
 rearrange index arrays; they are host-side numpy here (SURVEY.md §8f rank 4
-lists their device versions as "next").
+lists their device versions as "next").  ``DeviceMatrix`` has them handle to
+handle (``kronecker``, ``assemble`` / ``hcat`` / ``vcat`` / ``from_blocks*`` /
+``block_diag``, ``take_diag``, ``diag_dev`` / ``ident``): nothing crosses PCIe.
 """
 import ctypes as C
 import weakref
@@ -297,6 +299,112 @@ class DeviceMatrix(object):
         r = C.c_int(0)
         check("spl_matrix_hermitian", lib().spl_matrix_hermitian(self.handle, C.byref(r)))
         return bool(r.value)
+
+    def kronecker(self, other):
+        """device-resident Kronecker product self (x) other (Sparse.hs:597-634), both real or both complex; whole
+        matrices.  nnz may exceed 2^31"""
+        h = C.c_void_p()
+        check("spl_matrix_kronecker", lib().spl_matrix_kronecker(self.handle, other.handle, C.byref(h)))
+        return DeviceMatrix(h.value)
+
+    @classmethod
+    def assemble(cls, blocks, row_off, col_off, nrows, ncols):
+        """block b placed at (row_off[b], col_off[b]) of an nrows x ncols result (spl_matrix_assemble_blocks): disjoint
+        rectangles in any order, all real or all complex; no block at all gives `zeros`"""
+        blocks = list(blocks)
+        k = len(blocks)
+        if k == 0:
+            _ffi.require_gpu()
+        hs = (C.c_void_p * max(k, 1))(*[b.handle.value for b in blocks])
+        ro = np.ascontiguousarray(row_off, dtype=I64).reshape(-1)
+        co = np.ascontiguousarray(col_off, dtype=I64).reshape(-1)
+        if len(ro) != k or len(co) != k:
+            _oops("assemble", "%d blocks, but %d row offsets and %d column offsets" % (k, len(ro), len(co)))
+        h = C.c_void_p()
+        check("spl_matrix_assemble_blocks",
+              lib().spl_matrix_assemble_blocks(k, hs, _ffi.p_i64(ro), _ffi.p_i64(co), int(nrows), int(ncols), C.byref(h)))
+        return cls(h.value)
+
+    @classmethod
+    def hcat(cls, mats):
+        """hcat (Sparse.hs:504-522) of handles"""
+        mats = list(mats)
+        if not mats:
+            _oops("hcat", "empty list")
+        dims = [(m.info()["nrows_global"], m.info()["ncols"]) for m in mats]
+        if any(d[0] != dims[0][0] for d in dims):
+            _oops("hcat", "nrows mismatch")
+        widths = [d[1] for d in dims]
+        return cls.assemble(mats, [0] * len(mats), np.concatenate([[0], np.cumsum(widths)])[:-1], dims[0][0], sum(widths))
+
+    @classmethod
+    def vcat(cls, mats):
+        """vcat (Sparse.hs:528-559) of handles"""
+        mats = list(mats)
+        if not mats:
+            _oops("vcat", "empty list")
+        dims = [(m.info()["nrows_global"], m.info()["ncols"]) for m in mats]
+        if any(d[1] != dims[0][1] for d in dims):
+            _oops("vcat", "ncols mismatch")
+        heights = [d[0] for d in dims]
+        return cls.assemble(mats, np.concatenate([[0], np.cumsum(heights)])[:-1], [0] * len(mats), sum(heights), dims[0][1])
+
+    @classmethod
+    def from_blocks(cls, blocks):
+        """fromBlocks (Sparse.hs:563-587) on a grid of handles, None = zero block: the dimension rules and messages of
+        the host fromBlocks, the dimensions taken from info()"""
+        dims = {}
+
+        def dim(m, key):
+            if id(m) not in dims:
+                dims[id(m)] = m.info()
+            return dims[id(m)][key]
+
+        placed, ro, co, nrows, ncols = _block_grid(blocks, lambda m: dim(m, "nrows_global"), lambda m: dim(m, "ncols"))
+        return cls.assemble(placed, ro, co, nrows, ncols)
+
+    @classmethod
+    def from_blocks_diag(cls, blocks):
+        """fromBlocksDiag (Sparse.hs:589-597): a grid of handles given by (super-)diagonals"""
+        return cls.from_blocks(_diag_grid(blocks))
+
+    @classmethod
+    def block_diag(cls, mats):
+        """blockDiag (Sparse.hs:661-667): one placement, however many blocks"""
+        mats = list(mats)
+        n = len(mats)
+        return cls.from_blocks_diag([mats] + [[None] * n for _ in range(n - 1)])
+
+    def take_diag_dev(self, out_ptr, stream=0):
+        """out[c] = A[c, c] or 0, c < min(nrows, ncols) (Sparse.hs:640-650); out_ptr is a device pointer (int) to
+        doubles, or packed (re, im) pairs on a complex handle; enqueues on `stream`, no sync"""
+        check("spl_matrix_take_diag_dev",
+              lib().spl_matrix_take_diag_dev(self.handle, C.c_void_p(out_ptr), C.c_void_p(stream)))
+
+    def take_diag(self):
+        """the diagonal as a numpy vector (float64 or complex128)"""
+        import torch
+        inf = self.info()
+        n = min(inf["nrows_global"], inf["ncols"])
+        cplx = self.is_complex
+        with torch.cuda.device(inf["device"]):
+            out = torch.empty(max(n, 1), dtype=torch.complex128 if cplx else torch.float64, device="cuda")
+            self.take_diag_dev(out.data_ptr(), torch.cuda.current_stream().cuda_stream)
+            return out[:n].cpu().numpy()
+
+    @classmethod
+    def diag_dev(cls, n, values_ptr=None, complex=False):
+        """diag (Sparse.hs:652-659) of n values in device memory (doubles, or packed pairs with complex=True);
+        values_ptr None: ones"""
+        h = C.c_void_p()
+        check("spl_matrix_diag_dev",
+              lib().spl_matrix_diag_dev(int(n), C.c_void_p(values_ptr), 2 if complex else 1, C.byref(h)))
+        return cls(h.value)
+
+    @classmethod
+    def ident(cls, n, complex=False):
+        """ident n (Sparse.hs:669-671), made on the device"""
+        return cls.diag_dev(n, None, complex)
 
     @classmethod
     def compress_dev(cls, nrows, ncols, ntriples, rows_ptr, cols_ptr, vals_ptr):
@@ -795,18 +903,17 @@ def vjoin(a, b):
     return vcat([a, b])
 
 
-def fromBlocks(blocks):
-    """[[Maybe Matrix]] -> Matrix, None = zero block (Sparse.hs:563-587): vcat . map hcat . adjustDims in one
-    device assembly — block (r, c) sits at (sum of the heights above, sum of the widths to the left), listed
-    row-major so that blocks sharing columns come by ascending row offset."""
+def _block_grid(blocks, height, width):
+    """adjustDims of fromBlocks (Sparse.hs:563-587) for a grid with None = zero block: (placed blocks listed row-major,
+    their row offsets, their column offsets, nrows, ncols); height / width read a block's dimensions"""
     rows = [list(r) for r in blocks]
     ncb = max(len(r) for r in rows)
     cols = [[r[c] for r in rows if c < len(r)] for c in range(ncb)]
 
-    def spec(groups, attr, what):
+    def spec(groups, dim, what):
         out = []
         for g in groups:
-            ds = [getattr(m, attr) for m in g if m is not None]
+            ds = [dim(m) for m in g if m is not None]
             if not ds:
                 _oops("fromBlocks", "underspecified " + what)
             if any(d != ds[0] for d in ds):
@@ -814,8 +921,8 @@ def fromBlocks(blocks):
             out.append(ds[0])
         return out
 
-    heights = spec(rows, "nrows", "heights")
-    widths = spec(cols, "ncols", "widths")
+    heights = spec(rows, height, "heights")
+    widths = spec(cols, width, "widths")
     roff = np.concatenate([[0], np.cumsum(heights)])
     # hcat of a block row fails in the reference when the rows' widths differ in total (vcat: ncols mismatch)
     totals = [sum(widths[:len(r)]) for r in rows]
@@ -827,15 +934,13 @@ def fromBlocks(blocks):
         for c, m in enumerate(row):
             if m is not None:
                 placed.append(m)
-                ro.append(roff[r])
-                co.append(coff[c])
-    if not placed:  # every block a zero block cannot happen: heights would be underspecified
-        return zeros(int(roff[-1]), totals[0])
-    return _assemble(placed, ro, co, int(roff[-1]), totals[0])
+                ro.append(int(roff[r]))
+                co.append(int(coff[c]))
+    return placed, ro, co, int(roff[-1]), int(totals[0])
 
 
-def fromBlocksDiag(blocks):
-    """blocks given by (super-)diagonals (Sparse.hs:589-597)."""
+def _diag_grid(blocks):
+    """fromBlocksDiag's rearrangement (Sparse.hs:589-597): blocks given by (super-)diagonals -> a grid for fromBlocks"""
     blocks = [list(b) for b in blocks]
     n = len(blocks)
     trans = [[b[i] for b in blocks if i < len(b)] for i in range(max(len(b) for b in blocks))]
@@ -844,7 +949,22 @@ def fromBlocksDiag(blocks):
         as_ = as_ + [None] * (n - len(as_))
         cut = len(as_) - k
         out.append(as_[cut:] + as_[:cut])
-    return fromBlocks(out)
+    return out
+
+
+def fromBlocks(blocks):
+    """[[Maybe Matrix]] -> Matrix, None = zero block (Sparse.hs:563-587): vcat . map hcat . adjustDims in one
+    device assembly — block (r, c) sits at (sum of the heights above, sum of the widths to the left), listed
+    row-major so that blocks sharing columns come by ascending row offset."""
+    placed, ro, co, nrows, ncols = _block_grid(blocks, lambda m: m.nrows, lambda m: m.ncols)
+    if not placed:  # every block a zero block cannot happen: heights would be underspecified
+        return zeros(nrows, ncols)
+    return _assemble(placed, ro, co, nrows, ncols)
+
+
+def fromBlocksDiag(blocks):
+    """blocks given by (super-)diagonals (Sparse.hs:589-597)."""
+    return fromBlocks(_diag_grid(blocks))
 
 
 def blockDiag(mats):
