@@ -299,6 +299,61 @@ int spl_matrix_diag_dev(int64_t n, const double *d_values, int value_width, void
  * inside a column), val[nnz_local] — i.e. the reference's own CSC Matrix fields */
 int spl_matrix_export_csc(void *H, int64_t *colptr, int *rowidx, double *val);
 
+/* ---- compressed arrays and triples that are already in DEVICE memory, in and out: a matrix need not cross PCIe ----
+ * The three imports build a handle from arrays on the current device, the two exports write a handle's arrays into
+ * device memory the caller allocated (sizes from spl_matrix_info).  A torch.sparse_csr / _csc / _coo tensor on the GPU
+ * becomes a handle, and a result handle a tensor, without a host copy (DeviceMatrix.from_torch / to_torch).
+ *   index_width  4 (int32) or 8 (int64): the width of the pointer array and of the index array alike
+ *   value_width  1 (doubles) or 2 (packed (re, im) pairs: the handle is complex)
+ * Imports.  All d_* arguments are device pointers on the current device.  The arrays are borrowed for the call and
+ *   copied: they may be freed or overwritten when it returns.  The work runs on the default stream, like that of every
+ *   call that makes a handle, and the call synchronises; a caller that filled the arrays on a non-blocking stream
+ *   synchronises that stream first (the rule of spl_umfpack_*_solve_many_dev).  The result is a whole-matrix handle like
+ *   any other: 64-bit row pointers always, int32 ones when nnz fits, accepted by every operation, the LU from handles
+ *   included.  Range checks are made in the source width BEFORE narrowing: with index_width 8 an index of 2^32 + 3 is
+ *   out of range, not column 3, and the same holds for pointers.  Values are moved as bits (NaN payloads, infinities,
+ *   -0.0 unchanged).
+ * spl_matrix_create_csr_dev: the contract of spl_matrix_create_csr for a whole matrix.  rowptr[0] == 0, pointers
+ *   monotone, nnz = rowptr[nrows] >= 0, every column in [0, ncols), else SPL_ERROR_invalid_matrix; a last pointer that
+ *   promises more entries than the device allocations of d_colidx / d_val hold is refused the same way before they
+ *   are read (where the runtime knows the allocation).  Rows whose columns do not ascend are sorted, indices and values
+ *   together; a sorted input pays only the check: pointers and indices are each read once and written once, the values
+ *   copied once, and nnz is the one 8-byte read-back before the indices.  Duplicate column indices stay separate
+ *   entries (the caveat of spl_matrix_create_csr).
+ * spl_matrix_create_csc_dev: the reference's own column-major fields, the contract of spl_matrix_create / _create_z
+ *   (rows inside a column in any order); the row image is made by the order-preserving device transpose.
+ *   nnz >= 2^31: SPL_ERROR_index_overflow, as spl_matrix_export_csc answers.
+ * spl_matrix_compress_dev_wide: spl_matrix_compress_dev for 64-bit indices and / or complex values.  Bounds are checked
+ *   rows first, then columns; *bad (may be NULL) receives the first offending position, the status is
+ *   SPL_ERROR_index_out_of_bounds.  Duplicates are summed in input order, for complex values the real and the imaginary
+ *   parts separately in that order (complex addition is componentwise: the reference's compress at Complex Double).
+ *   With index_width 4 and value_width 1 the result has the bits of spl_matrix_compress_dev.  ntriples >= 2^31:
+ *   SPL_ERROR_index_overflow.
+ * Exports.  They write exactly the arrays spl_matrix_export_csr / _export_csc write to the host, with the chosen index
+ *   width: pointers[n + 1], indices[nnz], values[nnz * value width].  spl_matrix_export_csr_dev serves row blocks as
+ *   spl_matrix_export_csr does (pointers relative to the block).  spl_matrix_export_csc_dev serves complex handles too
+ *   (spl_matrix_export_csc still refuses them).  index_width 4 with nnz >= 2^31: SPL_ERROR_index_overflow; the CSC export
+ *   answers the same for any width when nnz >= 2^31.  Both run on the default stream and synchronise before returning.
+ * Argument checks, all before the device is touched, in this order:
+ *   1. H == NULL (imports): SPL_ERROR_argument_missing; otherwise *H = NULL first
+ *   2. H is no matrix handle (exports): SPL_ERROR_invalid_handle
+ *   3. a negative dimension or count: SPL_ERROR_n_nonpositive
+ *   4. nrows or ncols >= 2^31: SPL_ERROR_index_overflow
+ *   5. another index_width or value_width, a NULL pointer array, or an array not aligned to its element (4 or 8 bytes):
+ *      SPL_ERROR_argument_missing
+ *   NULL index or value arrays with nnz > 0 are SPL_ERROR_argument_missing too: for the compressed imports after the
+ *   read-back of nnz, for the triples and the exports at once.  Without a GPU a well-formed call answers
+ *   SPL_ERROR_device. */
+int spl_matrix_create_csr_dev(int64_t nrows, int64_t ncols, int index_width, const void *d_rowptr,
+                              const void *d_colidx, const double *d_val, int value_width, void **H);
+int spl_matrix_create_csc_dev(int64_t nrows, int64_t ncols, int index_width, const void *d_colptr,
+                              const void *d_rowidx, const double *d_val, int value_width, void **H);
+int spl_matrix_compress_dev_wide(int64_t nrows, int64_t ncols, int64_t ntriples, int index_width,
+                                 const void *d_rows, const void *d_cols, const double *d_vals,
+                                 int value_width, void **H, int64_t *bad);
+int spl_matrix_export_csr_dev(void *H, int index_width, void *d_rowptr, void *d_colidx, double *d_val);
+int spl_matrix_export_csc_dev(void *H, int index_width, void *d_colptr, void *d_rowidx, double *d_val);
+
 /* y = A x  /  y <- A x + y  with HOST vectors (upload, run, download) */
 int spl_matrix_mulv(void *H, int xlen, const double *x, double *y);
 int spl_matrix_gaxpy(void *H, int xlen, const double *x, int ylen, double *y);

@@ -113,6 +113,11 @@ def _declare(L):
         "spl_matrix_ctrans": [C.c_void_p, c_void_pp],
         "spl_matrix_hermitian": [C.c_void_p, c_int_p],
         "spl_matrix_compress_dev": [i, i, i64, C.c_void_p, C.c_void_p, C.c_void_p, c_void_pp, c_i64_p],
+        "spl_matrix_create_csr_dev": [i64, i64, i, C.c_void_p, C.c_void_p, C.c_void_p, i, c_void_pp],
+        "spl_matrix_create_csc_dev": [i64, i64, i, C.c_void_p, C.c_void_p, C.c_void_p, i, c_void_pp],
+        "spl_matrix_compress_dev_wide": [i64, i64, i64, i, C.c_void_p, C.c_void_p, C.c_void_p, i, c_void_pp, c_i64_p],
+        "spl_matrix_export_csr_dev": [C.c_void_p, i, C.c_void_p, C.c_void_p, C.c_void_p],
+        "spl_matrix_export_csc_dev": [C.c_void_p, i, C.c_void_p, C.c_void_p, C.c_void_p],
         "spl_matrix_kronecker": [C.c_void_p, C.c_void_p, c_void_pp],
         "spl_matrix_assemble_blocks": [i, c_void_pp, c_i64_p, c_i64_p, i64, i64, c_void_pp],
         "spl_matrix_take_diag_dev": [C.c_void_p, C.c_void_p, C.c_void_p],

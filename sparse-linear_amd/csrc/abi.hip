@@ -716,6 +716,177 @@ int spl_matrix_compress_dev(int nrows, int ncols, int64_t ntriples, const int *d
   });
 }
 
+// ---- compressed arrays and triples that are already in device memory (csrc/device_arrays.hip) ---------------------
+namespace {
+
+bool aligned_to(const void *p, size_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) == 0; }
+
+// the argument ladder the three imports share, everything that can be said before the device is touched
+int import_arguments(int64_t nrows, int64_t ncols, int64_t count, int index_width, int value_width, void **H) {
+  if (!H) return SPL_ERROR_argument_missing;
+  *H = nullptr;
+  if (nrows < 0 || ncols < 0 || count < 0) return SPL_ERROR_n_nonpositive;
+  if (nrows >= 0x80000000LL || ncols >= 0x80000000LL) return SPL_ERROR_index_overflow;
+  if ((index_width != 4 && index_width != 8) || (value_width != 1 && value_width != 2)) return SPL_ERROR_argument_missing;
+  return SPL_OK;
+}
+
+// A checked, narrowed copy of compressed device arrays: nmajor slices over nminor indices.  ascending == nullptr: the
+// order inside the slices is not looked at.  Values are not touched.
+struct ImportedPattern {
+  DBuf<int64_t> p64;
+  DBuf<int> idx;
+  int64_t nnz = 0;
+};
+int import_pattern(int index_width, const void *d_ptr, const void *d_idx, const double *d_val, int vw, int64_t nmajor,
+                   int64_t nminor, bool csc, ImportedPattern &out, bool *ascending, hipStream_t s) {
+  out.p64.alloc((size_t)nmajor + 1);
+  out.nnz = import_pointers(index_width, d_ptr, nmajor, out.p64.get(), s);
+  if (out.nnz < 0) return SPL_ERROR_invalid_matrix;
+  if (out.nnz > 0 && (!d_idx || !d_val)) return SPL_ERROR_argument_missing;
+  if (out.nnz == 0) {
+    out.idx.alloc(0);
+    return SPL_OK;
+  }
+  // a last pointer that promises more than the caller's allocations hold is refused before a byte of them is read
+  if (out.nnz >= (1LL << 48) || !device_range_holds(d_idx, (size_t)out.nnz * (size_t)index_width) ||
+      !device_range_holds(d_val, (size_t)out.nnz * (size_t)vw * sizeof(double)))
+    return SPL_ERROR_invalid_matrix;
+  if (csc && out.nnz >= 0x7fffffffLL) return SPL_ERROR_index_overflow;  // the transpose walks int32 pointers (export_csc)
+  out.idx.alloc((size_t)out.nnz);
+  return import_indices(index_width, d_idx, out.nnz, nminor, out.p64.get(), nmajor, out.idx.get(), ascending, s);
+}
+
+// sort the rows of m that do not ascend, values of m->vw doubles along with their indices
+void sort_rows(Matrix *m, hipStream_t s) {
+  if (m->vw == 1) {
+    segmented_sort_pairs(m->rowptr64.get(), m->nrows_local, m->colidx.get(), m->val.get(), s);
+  } else {
+    // packed complex, as upload_csc: sort the entry positions with the indices, gather the 16-byte values along them
+    DBuf<double> pos((size_t)m->nnz), sorted((size_t)m->nnz * 2);
+    fill_positions(m->nnz, pos.get(), s);
+    segmented_sort_pairs(m->rowptr64.get(), m->nrows_local, m->colidx.get(), pos.get(), s);
+    gather_complex_values(m->nnz, pos.get(), m->val.get(), sorted.get(), s);
+    SPL_HIP(hipStreamSynchronize(s));
+    m->val = std::move(sorted);
+  }
+  SPL_HIP(hipStreamSynchronize(s));
+}
+
+// the column-major image of a whole handle on the device: dcp[ncols + 1], dri[nnz], dv[nnz * vw]
+void csc_image(const Matrix *m, int64_t *dcp, int *dri, double *dv, hipStream_t s) {
+  if (m->vw == 1) {
+    transpose_compressed(m->rowptr.get(), m->colidx.get(), m->val.get(), m->nrows_local, m->ncols, m->nnz, dcp, dri, dv, s);
+  } else {
+    DBuf<double> pos((size_t)m->nnz), perm((size_t)m->nnz);
+    fill_positions(m->nnz, pos.get(), s);
+    transpose_compressed(m->rowptr.get(), m->colidx.get(), pos.get(), m->nrows_local, m->ncols, m->nnz, dcp, dri,
+                         perm.get(), s);
+    gather_complex_values(m->nnz, perm.get(), m->val.get(), dv, s);
+    SPL_HIP(hipStreamSynchronize(s));  // perm is released on return
+  }
+}
+
+}  // namespace
+
+int spl_matrix_create_csr_dev(int64_t nrows, int64_t ncols, int index_width, const void *d_rowptr, const void *d_colidx,
+                              const double *d_val, int value_width, void **H) {
+  int st = import_arguments(nrows, ncols, 0, index_width, value_width, H);
+  if (st != SPL_OK) return st;
+  if (!d_rowptr || !aligned_to(d_rowptr, (size_t)index_width) || !aligned_to(d_colidx, (size_t)index_width) ||
+      !aligned_to(d_val, sizeof(double)))
+    return SPL_ERROR_argument_missing;
+  return guarded([&]() -> int {
+    const int dev = current_device();
+    hipStream_t s = nullptr;
+    ImportedPattern P;
+    bool ascending = true;
+    int st = import_pattern(index_width, d_rowptr, d_colidx, d_val, value_width, nrows, ncols, false, P, &ascending, s);
+    if (st != SPL_OK) return st;
+    std::unique_ptr<Matrix> m = make_matrix(dev, nrows, ncols, 0, nrows, value_width);
+    m->nnz = P.nnz;
+    m->rowptr64 = std::move(P.p64);
+    m->colidx = std::move(P.idx);
+    m->val.alloc((size_t)P.nnz * (size_t)value_width);
+    if (P.nnz)  // values are moved as bits
+      SPL_HIP(hipMemcpyAsync(m->val.get(), d_val, (size_t)P.nnz * (size_t)value_width * sizeof(double),
+                             hipMemcpyDeviceToDevice, s));
+    if (!ascending) sort_rows(m.get(), s);
+    return publish(std::move(m), s, H);
+  });
+}
+
+int spl_matrix_create_csc_dev(int64_t nrows, int64_t ncols, int index_width, const void *d_colptr, const void *d_rowidx,
+                              const double *d_val, int value_width, void **H) {
+  int st = import_arguments(nrows, ncols, 0, index_width, value_width, H);
+  if (st != SPL_OK) return st;
+  if (!d_colptr || !aligned_to(d_colptr, (size_t)index_width) || !aligned_to(d_rowidx, (size_t)index_width) ||
+      !aligned_to(d_val, sizeof(double)))
+    return SPL_ERROR_argument_missing;
+  return guarded([&]() -> int {
+    const int dev = current_device();
+    hipStream_t s = nullptr;
+    ImportedPattern P;
+    // rows inside a column in any order, as spl_matrix_create takes them: the transpose orders the row image
+    int st = import_pattern(index_width, d_colptr, d_rowidx, d_val, value_width, ncols, nrows, true, P, nullptr, s);
+    if (st != SPL_OK) return st;
+    DBuf<int> p32((size_t)ncols + 1);
+    narrow_i64_to_i32(P.p64.get(), p32.get(), ncols + 1, s);
+    std::unique_ptr<Matrix> m = make_matrix(dev, nrows, ncols, 0, nrows, value_width);
+    m->nnz = P.nnz;
+    m->rowptr64.alloc((size_t)nrows + 1);
+    m->colidx.alloc((size_t)P.nnz);
+    m->val.alloc((size_t)P.nnz * (size_t)value_width);
+    if (value_width == 1) {  // the values go from the caller's array straight to their place in the row image
+      transpose_compressed(p32.get(), P.idx.get(), d_val, ncols, nrows, P.nnz, m->rowptr64.get(), m->colidx.get(),
+                           m->val.get(), s);
+    } else {  // as build_from_csc: the pattern with the entry positions as payload, the pairs gathered along them
+      DBuf<double> pos((size_t)P.nnz), perm((size_t)P.nnz);
+      fill_positions(P.nnz, pos.get(), s);
+      transpose_compressed(p32.get(), P.idx.get(), pos.get(), ncols, nrows, P.nnz, m->rowptr64.get(), m->colidx.get(),
+                           perm.get(), s);
+      gather_complex_values(P.nnz, perm.get(), d_val, m->val.get(), s);
+      SPL_HIP(hipStreamSynchronize(s));
+    }
+    return publish(std::move(m), s, H);
+  });
+}
+
+int spl_matrix_compress_dev_wide(int64_t nrows, int64_t ncols, int64_t ntriples, int index_width, const void *d_rows,
+                                 const void *d_cols, const double *d_vals, int value_width, void **H, int64_t *bad) {
+  int st = import_arguments(nrows, ncols, ntriples, index_width, value_width, H);
+  if (st != SPL_OK) return st;
+  if (ntriples >= 0x7fffffffLL) return SPL_ERROR_index_overflow;  // the sort key keeps the input position in 32 bits
+  if (ntriples > 0 && (!d_rows || !d_cols || !d_vals)) return SPL_ERROR_argument_missing;
+  if (!aligned_to(d_rows, (size_t)index_width) || !aligned_to(d_cols, (size_t)index_width) ||
+      !aligned_to(d_vals, sizeof(double)))
+    return SPL_ERROR_argument_missing;
+  return guarded([&]() -> int {
+    const int dev = current_device();
+    hipStream_t s = nullptr;
+    // as spl_matrix_compress_dev: the row image is the compress of the exchanged triples, and a bounds-only pass in the
+    // caller's order first keeps the reference's order of complaints (rows, then columns)
+    {
+      DBuf<int> none_i;
+      DBuf<double> none_v;
+      DBuf<int> probe((size_t)ncols + 1);
+      int64_t nz = 0, where = -1;
+      int st = compress_device_wide(index_width, value_width, nrows, ncols, ntriples, d_rows, d_cols, d_vals, probe.get(),
+                                    none_i, none_v, &nz, &where, s, /*check_only=*/true);
+      if (st != SPL_OK) { if (bad) *bad = where; return st; }
+    }
+    std::unique_ptr<Matrix> C = make_matrix(dev, nrows, ncols, 0, nrows, value_width);
+    DBuf<int> ptr32((size_t)nrows + 1);
+    int64_t where = -1;
+    int st = compress_device_wide(index_width, value_width, ncols, nrows, ntriples, d_cols, d_rows, d_vals, ptr32.get(),
+                                  C->colidx, C->val, &C->nnz, &where, s, false);
+    if (st != SPL_OK) { if (bad) *bad = where; return st; }
+    C->rowptr64.alloc((size_t)nrows + 1);
+    widen_i32_to_i64(ptr32.get(), C->rowptr64.get(), nrows + 1, s);
+    return publish(std::move(C), s, H);
+  });
+}
+
 void spl_matrix_free(void **H) {
   if (!H || !*H) return;
   Matrix *m = as_matrix(*H);
@@ -806,6 +977,69 @@ int spl_matrix_export_csc(void *H, int64_t *colptr, int *rowidx, double *val) {
       SPL_HIP(hipMemcpy(rowidx, dri.get(), (size_t)m->nnz * sizeof(int), hipMemcpyDeviceToHost));
       SPL_HIP(hipMemcpy(val, dv.get(), (size_t)m->nnz * sizeof(double), hipMemcpyDeviceToHost));
     }
+    return SPL_OK;
+  });
+}
+
+namespace {
+// the ladder of the two device exports; *m receives the handle
+int export_arguments(void *H, int index_width, const void *d_ptr, const void *d_idx, const double *d_val, Matrix **m) {
+  *m = as_matrix(H);
+  if (!*m) return SPL_ERROR_invalid_handle;
+  if (index_width != 4 && index_width != 8) return SPL_ERROR_argument_missing;
+  if (!d_ptr || !aligned_to(d_ptr, (size_t)index_width) || !aligned_to(d_idx, (size_t)index_width) ||
+      !aligned_to(d_val, sizeof(double)))
+    return SPL_ERROR_argument_missing;
+  if ((*m)->nnz > 0 && (!d_idx || !d_val)) return SPL_ERROR_argument_missing;
+  if (index_width == 4 && (*m)->nnz >= 0x7fffffffLL) return SPL_ERROR_index_overflow;
+  return SPL_OK;
+}
+}  // namespace
+
+int spl_matrix_export_csr_dev(void *H, int index_width, void *d_rowptr, void *d_colidx, double *d_val) {
+  Matrix *m = nullptr;
+  int st = export_arguments(H, index_width, d_rowptr, d_colidx, d_val, &m);
+  if (st != SPL_OK) return st;
+  return guarded([&]() -> int {
+    DeviceGuard g(m->device);
+    hipStream_t s = nullptr;
+    const int64_t np = m->nrows_local + 1;
+    if (index_width == 8) {
+      SPL_HIP(hipMemcpyAsync(d_rowptr, m->rowptr64.get(), (size_t)np * sizeof(int64_t), hipMemcpyDeviceToDevice, s));
+      if (m->nnz) widen_i32_to_i64(m->colidx.get(), static_cast<int64_t *>(d_colidx), m->nnz, s);
+    } else {
+      narrow_i64_to_i32(m->rowptr64.get(), static_cast<int *>(d_rowptr), np, s);
+      if (m->nnz)
+        SPL_HIP(hipMemcpyAsync(d_colidx, m->colidx.get(), (size_t)m->nnz * sizeof(int), hipMemcpyDeviceToDevice, s));
+    }
+    if (m->nnz)
+      SPL_HIP(hipMemcpyAsync(d_val, m->val.get(), (size_t)m->nnz * (size_t)m->vw * sizeof(double),
+                             hipMemcpyDeviceToDevice, s));
+    SPL_HIP(hipStreamSynchronize(s));
+    return SPL_OK;
+  });
+}
+
+int spl_matrix_export_csc_dev(void *H, int index_width, void *d_colptr, void *d_rowidx, double *d_val) {
+  Matrix *m = nullptr;
+  int st = export_arguments(H, index_width, d_colptr, d_rowidx, d_val, &m);
+  if (st != SPL_OK) return st;
+  if (!m->rowptr.get()) return SPL_ERROR_index_overflow;  // as spl_matrix_export_csc
+  return guarded([&]() -> int {
+    DeviceGuard g(m->device);
+    hipStream_t s = nullptr;
+    // the transpose writes what has the caller's width straight into the caller's arrays (the values always); only the
+    // array of the other width passes through a temporary and one converting copy.  nnz == 0: only pointers are written.
+    if (index_width == 8) {
+      DBuf<int> dri((size_t)m->nnz);
+      csc_image(m, static_cast<int64_t *>(d_colptr), dri.get(), d_val, s);
+      if (m->nnz) widen_i32_to_i64(dri.get(), static_cast<int64_t *>(d_rowidx), m->nnz, s);
+    } else {
+      DBuf<int64_t> dcp((size_t)m->ncols + 1);
+      csc_image(m, dcp.get(), static_cast<int *>(d_rowidx), d_val, s);
+      narrow_i64_to_i32(dcp.get(), static_cast<int *>(d_colptr), m->ncols + 1, s);
+    }
+    SPL_HIP(hipStreamSynchronize(s));  // the temporaries are released on return
     return SPL_OK;
   });
 }

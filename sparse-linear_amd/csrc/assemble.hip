@@ -26,27 +26,34 @@ inline unsigned blocks_for(int64_t n, int per_block, int64_t cap = 1 << 20) {
   return (unsigned)b;
 }
 
-__global__ __launch_bounds__(256) void bounds_kernel(const int *__restrict__ idx, int64_t nnz, int bound,
+// IT: the width the caller's indices have (int, or int64_t for spl_matrix_compress_dev_wide); the bound is compared in
+// that width, so 2^32 + 3 is out of range and not column 3.  Past the bounds check every index fits an int.
+template <typename IT>
+__global__ __launch_bounds__(256) void bounds_kernel(const IT *__restrict__ idx, int64_t nnz, int64_t bound,
                                                      unsigned long long *__restrict__ first_bad) {
   int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   const int64_t stride = (int64_t)gridDim.x * blockDim.x;
   unsigned long long bad = ~0ull;
   for (; i < nnz; i += stride) {
-    const int v = idx[i];
+    const int64_t v = (int64_t)idx[i];
     if ((v < 0 || v >= bound) && (unsigned long long)i < bad) bad = (unsigned long long)i;
   }
   if (bad != ~0ull) atomicMin(first_bad, bad);
 }
 
-__global__ __launch_bounds__(256) void count_kernel(const int *__restrict__ idx, int64_t nnz,
+template <typename IT>
+__global__ __launch_bounds__(256) void count_kernel(const IT *__restrict__ idx, int64_t nnz,
                                                     int *__restrict__ counts) {
   int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   const int64_t stride = (int64_t)gridDim.x * blockDim.x;
-  for (; i < nnz; i += stride) atomicAdd(&counts[idx[i]], 1);
+  for (; i < nnz; i += stride) atomicAdd(&counts[(int)idx[i]], 1);
 }
 
-__global__ __launch_bounds__(256) void coo_bucket_kernel(const int *__restrict__ rows,
-                                                         const int *__restrict__ cols,
+// VW = 2 (packed complex): nothing is carried beside the key — its low word is the input position, and dedup_sum_kernel
+// gathers the 16-byte values of a run from the caller's array through it
+template <typename IT, int VW>
+__global__ __launch_bounds__(256) void coo_bucket_kernel(const IT *__restrict__ rows,
+                                                         const IT *__restrict__ cols,
                                                          const double *__restrict__ vals, int64_t nnz,
                                                          const int64_t *__restrict__ colptr,
                                                          int *__restrict__ cursor, int64_t *__restrict__ key,
@@ -54,10 +61,10 @@ __global__ __launch_bounds__(256) void coo_bucket_kernel(const int *__restrict__
   int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   const int64_t stride = (int64_t)gridDim.x * blockDim.x;
   for (; i < nnz; i += stride) {
-    const int c = cols[i];
+    const int c = (int)cols[i];
     const int64_t pos = colptr[c] + (int64_t)atomicAdd(&cursor[c], 1);
     key[pos] = ((int64_t)rows[i] << 32) | i;  // nnz < 2^31: the position fits the low word
-    val[pos] = vals[i];
+    if (VW == 1) val[pos] = vals[i];
   }
 }
 
@@ -77,7 +84,10 @@ __global__ __launch_bounds__(256) void mark_row_changes_kernel(const int64_t *__
     if (i == 0 || (key[i] >> 32) != (key[i - 1] >> 32)) head[i] = 1;
 }
 
-// every run head sums its run left to right and writes the compacted entry
+// every run head sums its run left to right and writes the compacted entry.  VW = 1: val is the array sorted beside
+// the keys.  VW = 2: val is the caller's array of (re, im) pairs, read at the input position each key carries; the two
+// parts are summed separately in that same order (complex addition is componentwise).
+template <int VW>
 __global__ __launch_bounds__(256) void dedup_sum_kernel(const int64_t *__restrict__ key,
                                                         const double *__restrict__ val,
                                                         const int *__restrict__ head,
@@ -88,11 +98,23 @@ __global__ __launch_bounds__(256) void dedup_sum_kernel(const int64_t *__restric
   const int64_t stride = (int64_t)gridDim.x * blockDim.x;
   for (; i < nnz; i += stride) {
     if (!head[i]) continue;
-    double acc = val[i];
-    for (int64_t q = i + 1; q < nnz && !head[q]; ++q) acc = acc + val[q];  // x' + x, Sparse.hs:272-273
     const int64_t o = outpos[i];
     out_idx[o] = (int)(key[i] >> 32);
-    out_val[o] = acc;
+    if (VW == 1) {
+      double acc = val[i];
+      for (int64_t q = i + 1; q < nnz && !head[q]; ++q) acc = acc + val[q];  // x' + x, Sparse.hs:272-273
+      out_val[o] = acc;
+    } else {
+      int64_t p = key[i] & 0xffffffffLL;
+      double re = val[2 * p], im = val[2 * p + 1];
+      for (int64_t q = i + 1; q < nnz && !head[q]; ++q) {
+        p = key[q] & 0xffffffffLL;
+        re = re + val[2 * p];
+        im = im + val[2 * p + 1];
+      }
+      out_val[2 * o] = re;
+      out_val[2 * o + 1] = im;
+    }
   }
 }
 
@@ -332,10 +354,11 @@ size_t lin_tile_lds_bytes() {
 }  // namespace
 
 // COO (device arrays) -> CSC.  Returns SPL_OK / SPL_ERROR_index_out_of_bounds.
-// Outputs: d_newptr[ncols+1] (int32), out_idx/out_val allocated with nnz_out entries.
-int compress_device(int nrows, int ncols, int64_t nnz, const int *d_rows, const int *d_cols,
-                    const double *d_vals, int *d_newptr, DBuf<int> &out_idx, DBuf<double> &out_val,
-                    int64_t *nnz_out, int64_t *bad, hipStream_t s, bool check_only) {
+// Outputs: d_newptr[ncols+1] (int32), out_idx/out_val allocated with nnz_out entries (vw doubles per value).
+template <typename IT>
+static int compress_impl(int64_t nrows, int64_t ncols, int64_t nnz, const IT *d_rows, const IT *d_cols,
+                         const double *d_vals, int vw, int *d_newptr, DBuf<int> &out_idx, DBuf<double> &out_val,
+                         int64_t *nnz_out, int64_t *bad, hipStream_t s, bool check_only) {
   *nnz_out = 0;
   if (nnz == 0) {
     SPL_HIP(hipMemsetAsync(d_newptr, 0, ((size_t)ncols + 1) * sizeof(int), s));
@@ -347,7 +370,7 @@ int compress_device(int nrows, int ncols, int64_t nnz, const int *d_rows, const 
   DBuf<unsigned long long> first_bad(1);
   for (int pass = 0; pass < 2; ++pass) {  // rows, then columns (Sparse.hs:196-212)
     SPL_HIP(hipMemsetAsync(first_bad.get(), 0xff, sizeof(unsigned long long), s));
-    hipLaunchKernelGGL(bounds_kernel, dim3(blocks_for(nnz, 256, 8192)), dim3(256), 0, s,
+    hipLaunchKernelGGL(bounds_kernel<IT>, dim3(blocks_for(nnz, 256, 8192)), dim3(256), 0, s,
                        pass == 0 ? d_rows : d_cols, nnz, pass == 0 ? nrows : ncols, first_bad.get());
     unsigned long long h = 0;
     SPL_HIP(hipMemcpyAsync(&h, first_bad.get(), sizeof(h), hipMemcpyDeviceToHost, s));
@@ -361,14 +384,18 @@ int compress_device(int nrows, int ncols, int64_t nnz, const int *d_rows, const 
   DBuf<int> counts((size_t)ncols);
   DBuf<int64_t> colptr((size_t)ncols + 1);
   SPL_HIP(hipMemsetAsync(counts.get(), 0, (size_t)(ncols ? ncols : 1) * sizeof(int), s));
-  hipLaunchKernelGGL(count_kernel, dim3(blocks_for(nnz, 256, 16384)), dim3(256), 0, s, d_cols, nnz,
+  hipLaunchKernelGGL(count_kernel<IT>, dim3(blocks_for(nnz, 256, 16384)), dim3(256), 0, s, d_cols, nnz,
                      counts.get());
   exclusive_scan_i32_to_i64(counts.get(), colptr.get(), ncols, s);
   SPL_HIP(hipMemsetAsync(counts.get(), 0, (size_t)(ncols ? ncols : 1) * sizeof(int), s));
   DBuf<int64_t> key((size_t)nnz);
-  DBuf<double> val((size_t)nnz);
-  hipLaunchKernelGGL(coo_bucket_kernel, dim3(blocks_for(nnz, 256, 16384)), dim3(256), 0, s, d_rows, d_cols,
-                     d_vals, nnz, colptr.get(), counts.get(), key.get(), val.get());
+  DBuf<double> val((size_t)nnz);  // vw == 2: only the payload the segmented sort insists on, never read
+  if (vw == 1)
+    hipLaunchKernelGGL((coo_bucket_kernel<IT, 1>), dim3(blocks_for(nnz, 256, 16384)), dim3(256), 0, s, d_rows, d_cols,
+                       d_vals, nnz, colptr.get(), counts.get(), key.get(), val.get());
+  else
+    hipLaunchKernelGGL((coo_bucket_kernel<IT, 2>), dim3(blocks_for(nnz, 256, 16384)), dim3(256), 0, s, d_rows, d_cols,
+                       d_vals, nnz, colptr.get(), counts.get(), key.get(), val.get());
   segmented_sort_pairs64(colptr.get(), ncols, key.get(), val.get(), s);
   // run heads: first entry of a column, or a row change
   DBuf<int> head((size_t)nnz);
@@ -383,14 +410,36 @@ int compress_device(int nrows, int ncols, int64_t nnz, const int *d_rows, const 
   SPL_HIP(hipMemcpyAsync(&nz, outpos.get() + nnz, sizeof(int64_t), hipMemcpyDeviceToHost, s));
   SPL_HIP(hipStreamSynchronize(s));
   out_idx.alloc((size_t)nz);
-  out_val.alloc((size_t)nz);
-  hipLaunchKernelGGL(dedup_sum_kernel, dim3(blocks_for(nnz, 256, 16384)), dim3(256), 0, s, key.get(),
-                     val.get(), head.get(), outpos.get(), nnz, out_idx.get(), out_val.get());
+  out_val.alloc((size_t)nz * (size_t)vw);
+  if (vw == 1)
+    hipLaunchKernelGGL(dedup_sum_kernel<1>, dim3(blocks_for(nnz, 256, 16384)), dim3(256), 0, s, key.get(),
+                       val.get(), head.get(), outpos.get(), nnz, out_idx.get(), out_val.get());
+  else
+    hipLaunchKernelGGL(dedup_sum_kernel<2>, dim3(blocks_for(nnz, 256, 16384)), dim3(256), 0, s, key.get(),
+                       d_vals, head.get(), outpos.get(), nnz, out_idx.get(), out_val.get());
   hipLaunchKernelGGL(remap_ptr_kernel, dim3(blocks_for(ncols + 1, 256, 8192)), dim3(256), 0, s, colptr.get(),
                      outpos.get(), (int64_t)ncols, nnz, d_newptr);
   SPL_HIP(hipStreamSynchronize(s));
   *nnz_out = nz;
   return SPL_OK;
+}
+
+int compress_device(int nrows, int ncols, int64_t nnz, const int *d_rows, const int *d_cols,
+                    const double *d_vals, int *d_newptr, DBuf<int> &out_idx, DBuf<double> &out_val,
+                    int64_t *nnz_out, int64_t *bad, hipStream_t s, bool check_only) {
+  return compress_impl<int>(nrows, ncols, nnz, d_rows, d_cols, d_vals, 1, d_newptr, out_idx, out_val, nnz_out, bad, s,
+                            check_only);
+}
+
+int compress_device_wide(int index_width, int vw, int64_t nrows, int64_t ncols, int64_t nnz, const void *d_rows,
+                         const void *d_cols, const double *d_vals, int *d_newptr, DBuf<int> &out_idx,
+                         DBuf<double> &out_val, int64_t *nnz_out, int64_t *bad, hipStream_t s, bool check_only) {
+  if (index_width == 8)
+    return compress_impl<int64_t>(nrows, ncols, nnz, static_cast<const int64_t *>(d_rows),
+                                  static_cast<const int64_t *>(d_cols), d_vals, vw, d_newptr, out_idx, out_val, nnz_out,
+                                  bad, s, check_only);
+  return compress_impl<int>(nrows, ncols, nnz, static_cast<const int *>(d_rows), static_cast<const int *>(d_cols),
+                            d_vals, vw, d_newptr, out_idx, out_val, nnz_out, bad, s, check_only);
 }
 
 // columns strictly ascending?  (valid Matrix invariant, tests/Test/LinearAlgebra.hs:57-58)

@@ -236,6 +236,10 @@ void measure_locality(Matrix *m, hipStream_t s);  // fills new_line_fraction on 
 int compress_device(int nrows, int ncols, int64_t nnz, const int *d_rows, const int *d_cols,
                     const double *d_vals, int *d_newptr, DBuf<int> &out_idx, DBuf<double> &out_val,
                     int64_t *nnz_out, int64_t *bad, hipStream_t s, bool check_only = false);
+// the same for indices of index_width 4 or 8 bytes, compared with the bounds in that width, and values of vw doubles
+int compress_device_wide(int index_width, int vw, int64_t nrows, int64_t ncols, int64_t nnz, const void *d_rows,
+                         const void *d_cols, const double *d_vals, int *d_newptr, DBuf<int> &out_idx,
+                         DBuf<double> &out_val, int64_t *nnz_out, int64_t *bad, hipStream_t s, bool check_only = false);
 bool columns_sorted(const int *d_ptr, const int *d_idx, int64_t ncols, hipStream_t s);
 void lin_device(double alpha, const int *Ap, const int *Ai, const double *Ax, double beta, const int *Bp,
                 const int *Bi, const double *Bx, int64_t ncols, DBuf<int64_t> &Cp, DBuf<int> &Ci,
@@ -252,6 +256,19 @@ void take_diag_device(const int *Ap, const int *Ai, const double *Ax, int n, dou
 void blocks_assemble_device(int nblocks, const int *ncols_b, const int *const *d_Bp, const int *const *d_Bi,
                             const double *const *d_Bx, int vw, const int *row_off, const int *col_off, int64_t ncolsC,
                             DBuf<int64_t> &Cp, DBuf<int> &Ci, DBuf<double> &Cx, int64_t *nnzC, hipStream_t s);
+
+// ---- compressed arrays in device memory, in and out (device_arrays.hip) --------------------------------------------
+// index_width: bytes per element of the caller's pointer and index arrays, 4 or 8; every comparison is made in that width
+// Pointers: [0] == 0, none negative, none above its successor; copied to out_ptr64[nmajor + 1] in the same pass.
+// Returns nnz = ptr[nmajor], or -1 for an invalid array (one 8-byte read-back; synchronises s).
+int64_t import_pointers(int index_width, const void *d_ptr, int64_t nmajor, int64_t *out_ptr64, hipStream_t s);
+// Indices: each in [0, nminor), narrowed to out_idx[nnz] in the same pass.  SPL_OK or SPL_ERROR_invalid_matrix.
+// ascending != nullptr: also *ascending = every slice of d_ptr64 ascends strictly.  Synchronises s.
+int import_indices(int index_width, const void *d_idx, int64_t nnz, int64_t nminor, const int64_t *d_ptr64,
+                   int64_t nmajor, int *out_idx, bool *ascending, hipStream_t s);
+// false when the runtime knows the allocation d_p lies in and fewer than `bytes` bytes of it follow d_p: a pointer array
+// whose last entry promises more entries than the caller's arrays can hold is refused before anything is read
+bool device_range_holds(const void *d_p, size_t bytes);
 
 // ---- the structural constructors on handles (assemble_handles.hip) -----------------------------------------
 // C's dimensions, block and value kind are set by the caller; these fill rowptr64 / colidx / val / nnz on stream s

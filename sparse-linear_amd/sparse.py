@@ -17,7 +17,10 @@ The purely structural combinators (``hcat``, ``vcat``, ``fromBlocks*``,
 rearrange index arrays; they are host-side numpy here (SURVEY.md §8f rank 4
 lists their device versions as "next").  ``DeviceMatrix`` has them handle to
 handle (``kronecker``, ``assemble`` / ``hcat`` / ``vcat`` / ``from_blocks*`` /
-``block_diag``, ``take_diag``, ``diag_dev`` / ``ident``): nothing crosses PCIe.
+``block_diag``, ``take_diag``, ``diag_dev`` / ``ident``): nothing crosses PCIe.  CSR / CSC / COO arrays that already
+lie in device memory, a sparse torch tensor on the GPU among them, enter and leave a handle the same way
+(``from_csr_dev``, ``from_csc_dev``, ``compress_dev``, ``export_csr_dev``, ``export_csc_dev``, ``from_torch``,
+``to_torch``).
 """
 import ctypes as C
 import weakref
@@ -407,15 +410,136 @@ class DeviceMatrix(object):
         return cls.diag_dev(n, None, complex)
 
     @classmethod
-    def compress_dev(cls, nrows, ncols, ntriples, rows_ptr, cols_ptr, vals_ptr):
-        """COO triples in device memory (int32, int32, float64 device pointers) -> handle (Sparse.hs:184-280)"""
+    def compress_dev(cls, nrows, ncols, ntriples, rows_ptr, cols_ptr, vals_ptr, index_width=4, complex=False):
+        """COO triples in device memory -> handle (Sparse.hs:184-280).  The default is int32 indices and float64 values
+        (spl_matrix_compress_dev); index_width=8 takes int64 indices, complex=True packed (re, im) pairs
+        (spl_matrix_compress_dev_wide)"""
         _ffi.require_gpu()
         h = C.c_void_p()
         bad = C.c_int64(-1)
-        st = lib().spl_matrix_compress_dev(nrows, ncols, ntriples, C.c_void_p(rows_ptr), C.c_void_p(cols_ptr),
-                                           C.c_void_p(vals_ptr), C.byref(h), C.byref(bad))
-        check("spl_matrix_compress_dev", st)
+        if index_width == 4 and not complex:
+            st = lib().spl_matrix_compress_dev(nrows, ncols, ntriples, C.c_void_p(rows_ptr), C.c_void_p(cols_ptr),
+                                               C.c_void_p(vals_ptr), C.byref(h), C.byref(bad))
+            check("spl_matrix_compress_dev", st)
+        else:
+            st = lib().spl_matrix_compress_dev_wide(nrows, ncols, ntriples, int(index_width), C.c_void_p(rows_ptr),
+                                                    C.c_void_p(cols_ptr), C.c_void_p(vals_ptr), 2 if complex else 1,
+                                                    C.byref(h), C.byref(bad))
+            if st == SPL_ERROR_index_out_of_bounds:
+                raise _ffi.SparseLinearError("spl_matrix_compress_dev_wide", st, "first offending triple: %d" % bad.value)
+            check("spl_matrix_compress_dev_wide", st)
         return cls(h.value)
+
+    @classmethod
+    def from_csr_dev(cls, nrows, ncols, rowptr_ptr, colidx_ptr, val_ptr, index_width=4, complex=False):
+        """CSR arrays in device memory (device pointers as ints; int32 or int64 pointers and indices, float64 values or
+        packed pairs) -> whole-matrix handle (spl_matrix_create_csr_dev).  The arrays are copied; synchronises"""
+        _ffi.require_gpu()
+        h = C.c_void_p()
+        check("spl_matrix_create_csr_dev",
+              lib().spl_matrix_create_csr_dev(int(nrows), int(ncols), int(index_width), C.c_void_p(rowptr_ptr),
+                                              C.c_void_p(colidx_ptr), C.c_void_p(val_ptr), 2 if complex else 1,
+                                              C.byref(h)))
+        return cls(h.value)
+
+    @classmethod
+    def from_csc_dev(cls, nrows, ncols, colptr_ptr, rowidx_ptr, val_ptr, index_width=4, complex=False):
+        """the reference's CSC fields in device memory -> whole-matrix handle (spl_matrix_create_csc_dev)"""
+        _ffi.require_gpu()
+        h = C.c_void_p()
+        check("spl_matrix_create_csc_dev",
+              lib().spl_matrix_create_csc_dev(int(nrows), int(ncols), int(index_width), C.c_void_p(colptr_ptr),
+                                              C.c_void_p(rowidx_ptr), C.c_void_p(val_ptr), 2 if complex else 1,
+                                              C.byref(h)))
+        return cls(h.value)
+
+    def export_csr_dev(self, rowptr_ptr, colidx_ptr, val_ptr, index_width=4):
+        """the arrays of export_csr written into device memory the caller allocated: rowptr[nrows_local + 1] and
+        colidx[nnz] of index_width bytes per element, val[nnz] doubles (2 nnz on a complex handle); synchronises"""
+        check("spl_matrix_export_csr_dev",
+              lib().spl_matrix_export_csr_dev(self.handle, int(index_width), C.c_void_p(rowptr_ptr),
+                                              C.c_void_p(colidx_ptr), C.c_void_p(val_ptr)))
+
+    def export_csc_dev(self, colptr_ptr, rowidx_ptr, val_ptr, index_width=4):
+        """the reference's CSC fields written into device memory: colptr[ncols + 1], rowidx[nnz], val[nnz] (2 nnz doubles
+        on a complex handle, which export_csc does not serve); synchronises"""
+        check("spl_matrix_export_csc_dev",
+              lib().spl_matrix_export_csc_dev(self.handle, int(index_width), C.c_void_p(colptr_ptr),
+                                              C.c_void_p(rowidx_ptr), C.c_void_p(val_ptr)))
+
+    @classmethod
+    def from_torch(cls, t):
+        """handle of a 2-D torch.sparse_csr / sparse_csc / sparse_coo tensor on a GPU, float64 or complex128, int32 or
+        int64 indices, without a host copy.  COO triples go through compress as they are (no coalesce(): duplicates are
+        summed in input order).  Nothing is cast or moved silently: other dtypes, CPU tensors, batch or dense dimensions
+        and strided tensors are refused.  Synchronises torch's current stream, then the import runs on the tensor's
+        device"""
+        import torch
+        if not isinstance(t, torch.Tensor):
+            raise TypeError("from_torch: a torch.Tensor is needed, got %s" % type(t).__name__)
+        layouts = (torch.sparse_csr, torch.sparse_csc, torch.sparse_coo)
+        if t.layout not in layouts:
+            raise TypeError("from_torch: layout %s; sparse_csr, sparse_csc or sparse_coo is needed" % t.layout)
+        if t.dtype not in (torch.float64, torch.complex128):
+            raise TypeError("from_torch: dtype %s; float64 or complex128 is needed (nothing is cast)" % t.dtype)
+        if t.dim() != 2:
+            raise ValueError("from_torch: %d dimensions; batch dimensions are not served" % t.dim())
+        if t.dense_dim() != 0:
+            raise ValueError("from_torch: dense (hybrid) dimensions are not served")
+        if t.device.type != "cuda":
+            raise ValueError("from_torch: the tensor is on %s; it is not moved to a GPU silently" % t.device)
+        nrows, ncols = int(t.shape[0]), int(t.shape[1])
+        cplx = t.dtype == torch.complex128
+        if t.layout == torch.sparse_csr:
+            ptr, idx, val = t.crow_indices(), t.col_indices(), t.values()
+        elif t.layout == torch.sparse_csc:
+            ptr, idx, val = t.ccol_indices(), t.row_indices(), t.values()
+        else:
+            ptr, idx, val = None, t._indices(), t._values()
+        if idx.dtype not in (torch.int32, torch.int64):
+            raise TypeError("from_torch: index dtype %s" % idx.dtype)
+        width = 8 if idx.dtype == torch.int64 else 4
+        with torch.cuda.device(t.device):
+            idx, val = idx.contiguous(), val.contiguous()  # copies on the device, and only when needed
+            if ptr is None:
+                rows, cols = idx[0], idx[1]  # contiguous rows of the 2 x nnz index tensor
+                n = int(val.shape[0])
+                torch.cuda.current_stream().synchronize()
+                return cls.compress_dev(nrows, ncols, n, rows.data_ptr() if n else 0, cols.data_ptr() if n else 0,
+                                        val.data_ptr() if n else 0, index_width=width, complex=cplx)
+            ptr = ptr.contiguous()
+            torch.cuda.current_stream().synchronize()
+            make = cls.from_csr_dev if t.layout == torch.sparse_csr else cls.from_csc_dev
+            return make(nrows, ncols, ptr.data_ptr(), idx.data_ptr(), val.data_ptr(), index_width=width, complex=cplx)
+
+    def to_torch(self, layout=None, index_dtype=None):
+        """the matrix as a torch.sparse_csr (default) or sparse_csc tensor on the handle's device, index_dtype
+        torch.int64 (default) or torch.int32, values float64 or, for a complex handle, complex128 over the packed pairs.
+        The three tensors are allocated by torch and filled on the device.  Whole matrices only"""
+        import torch
+        layout = torch.sparse_csr if layout is None else layout
+        index_dtype = torch.int64 if index_dtype is None else index_dtype
+        if layout not in (torch.sparse_csr, torch.sparse_csc):
+            raise ValueError("to_torch: layout %s; torch.sparse_csr or torch.sparse_csc is needed" % layout)
+        if index_dtype not in (torch.int32, torch.int64):
+            raise TypeError("to_torch: index dtype %s; torch.int32 or torch.int64 is needed" % index_dtype)
+        inf = self.info()
+        if inf["row0"] != 0 or inf["nrows_local"] != inf["nrows_global"]:
+            raise ValueError("to_torch: a row block (rows %d .. %d of %d) is not a whole matrix"
+                             % (inf["row0"], inf["row0"] + inf["nrows_local"], inf["nrows_global"]))
+        nrows, ncols, nnz = inf["nrows_global"], inf["ncols"], inf["nnz"]
+        csr = layout == torch.sparse_csr
+        dev = torch.device("cuda", inf["device"])
+        with torch.cuda.device(dev):
+            ptr = torch.empty((nrows if csr else ncols) + 1, dtype=index_dtype, device=dev)
+            idx = torch.empty(nnz, dtype=index_dtype, device=dev)
+            val = torch.empty(nnz, dtype=torch.complex128 if self.is_complex else torch.float64, device=dev)
+            torch.cuda.current_stream().synchronize()
+            export = self.export_csr_dev if csr else self.export_csc_dev
+            export(ptr.data_ptr(), idx.data_ptr() if nnz else 0, val.data_ptr() if nnz else 0,
+                   index_width=8 if index_dtype == torch.int64 else 4)
+            make = torch.sparse_csr_tensor if csr else torch.sparse_csc_tensor
+            return make(ptr, idx, val, size=(nrows, ncols))
 
     def info(self):
         buf = (C.c_int64 * 8)()
