@@ -173,7 +173,7 @@ int spl_matrix_create(int nrows, int ncols, const int *Ap, const int *Ai, const 
  * compute  y <- a * x + y  per stored entry in ascending column order with Data.Complex's arithmetic, every
  * real operation separately rounded (csrc/spmv_z.hip: 20 bytes per stored entry instead of the 48 of the real
  * 2n x 2n embedding).  spl_matrix_spmv_many_dev is the fused product of such a handle with k vectors at once.
- * spl_matrix_lin, _transpose, _ctrans, _hermitian, _spgemm, _kronecker, _assemble_blocks, _take_diag_dev, _export_csr
+ * spl_matrix_lin, _transpose, _ctrans, _hermitian, _spgemm, _kronecker, _assemble_blocks, _submatrix, _select, _take_diag_dev, _export_csr
  * and the LU from handles take complex handles as well, and spl_matrix_diag_dev makes one.  Still for real handles only: spl_matrix_export_csc, spl_matrix_export_csr_rows, spl_matrix_spmm_dev and
  * the SpMV images (spl_matrix_build_blocked / _build_panel, the sliced-ELL image; spl_matrix_optimize and
  * spl_matrix_set_variant(H, 0) are accepted and do nothing).  The CSC fields of a complex handle are
@@ -294,6 +294,52 @@ int spl_matrix_assemble_blocks(int nblocks, void *const *H, const int64_t *row_o
                                int64_t nrowsC, int64_t ncolsC, void **HC);
 int spl_matrix_take_diag_dev(void *H, double *d_out, void *stream);
 int spl_matrix_diag_dev(int64_t n, const double *d_values, int value_width, void **H);
+/* ---- taking a handle apart: windows, and rows / columns by index (csrc/submatrix.hip) ------------------------------
+ * The inverse of spl_matrix_assemble_blocks, under the constructors' common rules: the operand is a whole matrix (a row
+ * block: SPL_ERROR_argument_missing), real or complex; the result is an ordinary handle on the operand's device, 64-bit
+ * row pointers always, int32 ones when nnz fits; values are moved as bits (NaN payloads, infinities and -0.0 pass
+ * unchanged); all argument checks come before the device is touched; the work runs on the default stream and the call
+ * synchronises before returning.  Like lin and spgemm both rely on strictly ascending indices in their operand.
+ *
+ * spl_matrix_submatrix: C[i, j] = A[r0 + i, c0 + j], i < nr, j < nc: C is nr x nc, its indices relative to the window.
+ *   This is the operation that the signature and the two guards of the reference's `subMatrix (r0, c0) (nr, nc)`
+ *   (Sparse.hs:704-729) document.  The reference's body is untested and does not compute it — `U.slice ix0 nix` passes an
+ *   end where a length belongs, the kept row indices are not shifted by r0, and `computePtrs nc _indices` builds column
+ *   pointers from row indices — so its bits are NOT reproduced; the documented operation is provided.  Checks, in order:
+ *   1. H is no matrix handle: SPL_ERROR_invalid_handle
+ *   2. HC == NULL: SPL_ERROR_argument_missing; otherwise *HC = NULL first
+ *   3. a negative r0, c0, nr or nc: SPL_ERROR_n_nonpositive
+ *   4. r0 + nr > nrows or c0 + nc > ncols: SPL_ERROR_dimension_mismatch (the reference's two errorWithStackTrace sites,
+ *      "range exceeds input row size" / "... column size")
+ *   5. a row block: SPL_ERROR_argument_missing
+ *   nr == 0 or nc == 0 is legal and gives `zeros nr nc`.  Per result row the kept run is found by bisection between
+ *   lower_bound(c0) and lower_bound(c0 + nc); nnz(C) is the one 8-byte read-back.  A window of whole rows (c0 == 0,
+ *   nc == ncols) searches nothing: a pointer shift and two device-to-device copies.
+ * spl_matrix_select: C[i, j] = A[I[i], J[j]]: C is nI x nJ.  d_I and d_J are index arrays in DEVICE memory on the
+ *   handle's device, index_width 4 (int32) or 8 (int64) bytes per entry for both; as for spl_matrix_create_csr_dev range
+ *   checks are made in the source width BEFORE narrowing (an 8-byte index of 2^32 + 3 is out of bounds, not column 3).
+ *   d_I == NULL: all rows in order, and nI must equal nrows; d_J == NULL: the same for the columns.  I may repeat rows
+ *   (the rows are copied) and come in any order.  J may come in any order but must not repeat a column.  Every result
+ *   row has strictly ascending indices whatever the order of J: when J ascends the rows come out in order and nothing
+ *   is sorted, otherwise the rows are sorted, values along with their indices.  Nothing is handed out by atomics: the
+ *   result is the same bits from run to run.  A permutation P A Q is I = p, J = q; `toColumns` over a range is
+ *   d_I = NULL, J = c0 .. c1; a rank's row block of a matrix assembled on the device is I = row0 .. row1, d_J = NULL.
+ *   Checks, in order, 1 - 6 before the device is touched:
+ *   1. H is no matrix handle: SPL_ERROR_invalid_handle
+ *   2. HC == NULL: SPL_ERROR_argument_missing; otherwise *HC = NULL first
+ *   3. a negative nI or nJ: SPL_ERROR_n_nonpositive
+ *   4. nI or nJ >= 2^31: SPL_ERROR_index_overflow
+ *   5. another index_width, or an array not aligned to its element: SPL_ERROR_argument_missing
+ *   6. d_I == NULL with nI != nrows, or d_J == NULL with nJ != ncols: SPL_ERROR_dimension_mismatch
+ *   7. a row block: SPL_ERROR_argument_missing
+ *   8. an index outside [0, nrows) or [0, ncols): SPL_ERROR_index_out_of_bounds, and *bad (may be NULL) receives the
+ *      first offending position; I is checked first, then J, as spl_matrix_compress_dev orders rows and columns
+ *   9. a column named twice in J: SPL_ERROR_invalid_matrix
+ *   Results that feed the LU keep the project's contract for solves, 1e-10 relative (north_star): a symmetric
+ *   permutation select(p, p) of a Hermitian handle is Hermitian, and its factors solve the permuted system. */
+int spl_matrix_submatrix(void *H, int64_t r0, int64_t c0, int64_t nr, int64_t nc, void **HC);
+int spl_matrix_select(void *H, int64_t nI, const void *d_I, int64_t nJ, const void *d_J, int index_width, void **HC,
+                      int64_t *bad);
 /* transpose the block on the device (Sparse.hs:301-329) and copy out its
  * column-major image: colptr[ncols+1], rowidx[nnz_local] (LOCAL row ids, ascending
  * inside a column), val[nnz_local] — i.e. the reference's own CSC Matrix fields */

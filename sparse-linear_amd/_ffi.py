@@ -122,6 +122,8 @@ def _declare(L):
         "spl_matrix_assemble_blocks": [i, c_void_pp, c_i64_p, c_i64_p, i64, i64, c_void_pp],
         "spl_matrix_take_diag_dev": [C.c_void_p, C.c_void_p, C.c_void_p],
         "spl_matrix_diag_dev": [i64, C.c_void_p, i, c_void_pp],
+        "spl_matrix_submatrix": [C.c_void_p, i64, i64, i64, i64, c_void_pp],
+        "spl_matrix_select": [C.c_void_p, i64, C.c_void_p, i64, C.c_void_p, i, c_void_pp, c_i64_p],
         "spl_matrix_info": [C.c_void_p, c_i64_p],
         "spl_matrix_export_csr": [C.c_void_p, c_i64_p, c_int_p, c_dbl_p],
         "spl_matrix_export_csc": [C.c_void_p, c_i64_p, c_int_p, c_dbl_p],

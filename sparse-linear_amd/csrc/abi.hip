@@ -887,6 +887,60 @@ int spl_matrix_compress_dev_wide(int64_t nrows, int64_t ncols, int64_t ntriples,
   });
 }
 
+// ---- taking a handle apart (csrc/submatrix.hip) ---------------------------------------------------------------------
+// C[i, j] = A[r0 + i, c0 + j]: what the signature and the two guards of `subMatrix` (Sparse.hs:704-729) mean.  The
+// reference's own body is not reproduced (it slices with an end where a length belongs, keeps the row indices
+// unshifted and builds the column pointers from row indices).  On the row image a window is, per result row, the run
+// of the source row between two lower bounds.
+int spl_matrix_submatrix(void *H, int64_t r0, int64_t c0, int64_t nr, int64_t nc, void **HC) {
+  Matrix *A = as_matrix(H);
+  if (!A) return SPL_ERROR_invalid_handle;
+  if (!HC) return SPL_ERROR_argument_missing;
+  *HC = nullptr;
+  if (r0 < 0 || c0 < 0 || nr < 0 || nc < 0) return SPL_ERROR_n_nonpositive;
+  // the reference's two guards, written so that the sums cannot overflow
+  if (nr > A->nrows_global || r0 > A->nrows_global - nr) return SPL_ERROR_dimension_mismatch;
+  if (nc > A->ncols || c0 > A->ncols - nc) return SPL_ERROR_dimension_mismatch;
+  if (!whole(A)) return SPL_ERROR_argument_missing;
+  return guarded([&]() -> int {
+    DeviceGuard g(A->device);
+    hipStream_t s = nullptr;
+    std::unique_ptr<Matrix> C = make_matrix(A->device, nr, nc, 0, nr, A->vw);
+    submatrix_handle(A, r0, c0, C.get(), s);
+    return publish(std::move(C), s, HC);
+  });
+}
+
+// C[i, j] = A[I[i], J[j]]: rows may repeat and come in any order, columns come in any order and each at most once
+int spl_matrix_select(void *H, int64_t nI, const void *d_I, int64_t nJ, const void *d_J, int index_width, void **HC,
+                      int64_t *bad) {
+  Matrix *A = as_matrix(H);
+  if (!A) return SPL_ERROR_invalid_handle;
+  if (!HC) return SPL_ERROR_argument_missing;
+  *HC = nullptr;
+  if (nI < 0 || nJ < 0) return SPL_ERROR_n_nonpositive;
+  if (nI >= 0x80000000LL || nJ >= 0x80000000LL) return SPL_ERROR_index_overflow;
+  if ((index_width != 4 && index_width != 8) || !aligned_to(d_I, (size_t)index_width) ||
+      !aligned_to(d_J, (size_t)index_width))
+    return SPL_ERROR_argument_missing;
+  if ((!d_I && nI != A->nrows_global) || (!d_J && nJ != A->ncols)) return SPL_ERROR_dimension_mismatch;
+  if (!whole(A)) return SPL_ERROR_argument_missing;
+  return guarded([&]() -> int {
+    DeviceGuard g(A->device);
+    hipStream_t s = nullptr;
+    std::unique_ptr<Matrix> C = make_matrix(A->device, nI, nJ, 0, nI, A->vw);
+    bool ascending = true;
+    int64_t where = -1;
+    const int st = select_handle(A, index_width, d_I, d_J, C.get(), &ascending, &where, s);
+    if (st != SPL_OK) {
+      if (st == SPL_ERROR_index_out_of_bounds && bad) *bad = where;
+      return st;
+    }
+    if (!ascending && C->nnz > 0) sort_rows(C.get(), s);
+    return publish(std::move(C), s, HC);
+  });
+}
+
 void spl_matrix_free(void **H) {
   if (!H || !*H) return;
   Matrix *m = as_matrix(*H);

@@ -283,6 +283,15 @@ void assemble_handles(int nblocks, const Matrix *const *blk, const int64_t *row_
 void take_diag_handle(const Matrix *A, int64_t n, double *d, hipStream_t s);  // enqueues; does not synchronise
 void diag_handle(const double *d_values, Matrix *C, hipStream_t s);           // d_values == nullptr: ones
 
+// ---- windows and selections of handles (submatrix.hip) -------------------------------------------------------
+// C's dimensions and value kind are set by the caller, A is whole and the arguments are checked; both synchronise s
+void submatrix_handle(const Matrix *A, int64_t r0, int64_t c0, Matrix *C, hipStream_t s);
+// C[i, j] = A[I[i], J[j]], source order kept inside the rows; *ascending == false: the caller sorts them.  nullptr for
+// d_I / d_J: all rows / columns.  SPL_ERROR_index_out_of_bounds (*bad: first offending position, I before J) or
+// SPL_ERROR_invalid_matrix (a column named twice)
+int select_handle(const Matrix *A, int index_width, const void *d_I, const void *d_J, Matrix *C, bool *ascending,
+                  int64_t *bad, hipStream_t s);
+
 // ---- multifrontal LU without interchanges (multifrontal.hip, mf_symbolic.hpp) ------------------
 namespace mf {
 struct Tree;

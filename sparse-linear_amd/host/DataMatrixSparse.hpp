@@ -212,6 +212,39 @@ inline std::vector<double> takeDiag(const Matrix &a) {
   return d;
 }
 
+// subMatrix (r0, c0) (nr, nc) (Sparse.hs:704-729): the nr x nc window at (r0, c0), indices relative to the window.  The
+// reference's body does not compute that (an end passed as a length, row indices not shifted, pointers built from row
+// indices): its two guards and messages are kept, the documented operation is computed — one upload, the window on the
+// device (spl_matrix_submatrix), one export
+inline Matrix subMatrix(std::pair<Int, Int> origin, std::pair<Int, Int> shape, const Matrix &a) {
+  const Int r0 = origin.first, c0 = origin.second, nr = shape.first, nc = shape.second;
+  if (r0 < 0 || c0 < 0 || nr < 0 || nc < 0) detail::oops("subMatrix", "negative origin or size");
+  if (r0 + nr > a.nrows) detail::oops("subMatrix", "range exceeds input row size");
+  if (c0 + nc > a.ncols) detail::oops("subMatrix", "range exceeds input column size");
+  detail::Const ca(a);
+  void *h = nullptr, *hc = nullptr;
+  detail::check("subMatrix", spl_matrix_create(ca.nrows, ca.ncols, ca.p.data(), ca.i.data(), ca.x, &h));
+  int st = spl_matrix_submatrix(h, r0, c0, nr, nc, &hc);
+  spl_matrix_free(&h);
+  detail::check("subMatrix", st);
+  int64_t info[8] = {0};
+  st = spl_matrix_info(hc, info);
+  const size_t nz = st < 0 ? 0 : (size_t)info[4];
+  std::vector<int64_t> cp((size_t)nc + 1);
+  std::vector<int> ri(nz ? nz : 1);
+  Matrix c;
+  c.nrows = nr;
+  c.ncols = nc;
+  c.values.resize(nz ? nz : 1);
+  if (st >= 0) st = spl_matrix_export_csc(hc, cp.data(), ri.data(), c.values.data());
+  spl_matrix_free(&hc);
+  detail::check("subMatrix", st);
+  c.values.resize(nz);
+  c.pointers.assign(cp.begin(), cp.end());
+  c.indices.assign(ri.begin(), ri.begin() + (std::ptrdiff_t)nz);
+  return c;
+}
+
 // hcat / vcat / fromBlocks (Sparse.hs:504-587): one device assembly (spl_assemble_blocks); nullptr = Nothing
 namespace detail {
 inline Matrix assemble(const std::vector<const Matrix *> &blocks, const std::vector<int> &row_off,

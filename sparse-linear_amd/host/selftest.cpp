@@ -125,6 +125,11 @@ int main() {
     EXPECT(fromBlocks({{&i2, nullptr}, {nullptr, &i3}}) == ident(5));
     EXPECT(transpose(hjoin(A, A)) == vjoin(transpose(A), transpose(A)));
     EXPECT(nonZero(vcat({A, A, A})) == 3 * nonZero(A));
+    // subMatrix undoes the joins: the four n x n corner windows of A are T + 2 I, -I, -I, T + 2 I
+    EXPECT(subMatrix({n * n - n, 0}, {n, n * n}, vjoin(A, A)) == subMatrix({n * n - n, 0}, {n, n * n}, A));
+    EXPECT(subMatrix({0, 0}, {n, n}, A) == T + diag(std::vector<double>((size_t)n, 2.0)));
+    EXPECT(subMatrix({n, 0}, {n, n}, A) == diag(std::vector<double>((size_t)n, -1.0)));
+    EXPECT(subMatrix({3, 7}, {0, 5}, A) == zeros(0, 5));
     std::vector<std::vector<double>> xs, bs;
     for (int j = 0; j < 3; ++j) {
       std::vector<double> x((size_t)(n * n));

@@ -20,7 +20,8 @@ handle (``kronecker``, ``assemble`` / ``hcat`` / ``vcat`` / ``from_blocks*`` /
 ``block_diag``, ``take_diag``, ``diag_dev`` / ``ident``): nothing crosses PCIe.  CSR / CSC / COO arrays that already
 lie in device memory, a sparse torch tensor on the GPU among them, enter and leave a handle the same way
 (``from_csr_dev``, ``from_csc_dev``, ``compress_dev``, ``export_csr_dev``, ``export_csc_dev``, ``from_torch``,
-``to_torch``).
+``to_torch``).  A handle is taken apart the same way: ``submatrix`` / ``A[a:b, c:d]`` for a window, ``select`` /
+``A[rows, cols]`` for rows and columns by index (a permutation ``P A Q`` among them); ``subMatrix`` is the host route.
 """
 import ctypes as C
 import weakref
@@ -377,6 +378,82 @@ class DeviceMatrix(object):
         mats = list(mats)
         n = len(mats)
         return cls.from_blocks_diag([mats] + [[None] * n for _ in range(n - 1)])
+
+    def submatrix(self, r0, c0, nr, nc):
+        """the window self[r0 : r0 + nr, c0 : c0 + nc] as a handle of its own, indices relative to the window
+        (spl_matrix_submatrix): what `subMatrix (r0, c0) (nr, nc)` of the reference documents; whole matrices, real or
+        complex; nothing crosses PCIe"""
+        h = C.c_void_p()
+        check("spl_matrix_submatrix",
+              lib().spl_matrix_submatrix(self.handle, int(r0), int(c0), int(nr), int(nc), C.byref(h)))
+        return DeviceMatrix(h.value)
+
+    def select(self, rows=None, cols=None):
+        """C[i, j] = self[rows[i], cols[j]] as a handle (spl_matrix_select).  rows / cols: torch int32 or int64 tensors
+        on the handle's device, or anything torch.as_tensor takes (uploaded as int64); None = all of them in order.
+        rows may repeat, cols may not; every result row ascends whatever the order of cols.  A permutation P A Q is
+        select(p, q)"""
+        import torch
+        inf = self.info()
+        dev = torch.device("cuda", inf["device"])
+
+        def index_tensor(a, what):
+            if a is None:
+                return None
+            if not isinstance(a, torch.Tensor):
+                a = torch.as_tensor(a, dtype=torch.int64)
+            if a.dtype not in (torch.int32, torch.int64):
+                raise TypeError("select: %s of dtype %s; int32 or int64 is needed" % (what, a.dtype))
+            if a.dim() != 1:
+                raise TypeError("select: %s with %d dimensions; a 1-D index array is needed" % (what, a.dim()))
+            return a.to(dev).contiguous()
+
+        with torch.cuda.device(dev):
+            ti, tj = index_tensor(rows, "rows"), index_tensor(cols, "cols")
+            if ti is not None and tj is not None and ti.dtype != tj.dtype:  # one width for both arrays
+                ti, tj = ti.to(torch.int64), tj.to(torch.int64)
+            given = ti if ti is not None else tj
+            width = 4 if given is not None and given.dtype == torch.int32 else 8
+            n_i = inf["nrows_global"] if ti is None else int(ti.shape[0])
+            n_j = inf["ncols"] if tj is None else int(tj.shape[0])
+            # an empty tensor has no storage to point at; any aligned non-NULL address says "given, and empty"
+            p_i = None if ti is None else C.c_void_p(ti.data_ptr() if n_i else 8)
+            p_j = None if tj is None else C.c_void_p(tj.data_ptr() if n_j else 8)
+            torch.cuda.current_stream().synchronize()  # the call runs on the default stream
+            h = C.c_void_p()
+            bad = C.c_int64(-1)
+            st = lib().spl_matrix_select(self.handle, n_i, p_i, n_j, p_j, width, C.byref(h), C.byref(bad))
+        if st == SPL_ERROR_index_out_of_bounds:
+            raise _ffi.SparseLinearError("spl_matrix_select", st, "first offending position: %d" % bad.value)
+        check("spl_matrix_select", st)
+        return DeviceMatrix(h.value)
+
+    def __getitem__(self, key):
+        """self[a:b, c:d] (step 1 or None) is submatrix; self[rows, cols] with two 1-D index tensors or lists is select.
+        Strided slices, masks, scalars and mixtures are not served: TypeError"""
+        import builtins
+        if not (isinstance(key, tuple) and len(key) == 2):
+            raise TypeError("DeviceMatrix[...] takes a pair: two slices, or two index arrays")
+        a, b = key
+        if isinstance(a, builtins.slice) and isinstance(b, builtins.slice):
+            if a.step not in (None, 1) or b.step not in (None, 1):
+                raise TypeError("DeviceMatrix[...]: strided slices are not served")
+            inf = self.info()
+            r0, r1, _ = a.indices(inf["nrows_global"])
+            c0, c1, _ = b.indices(inf["ncols"])
+            return self.submatrix(r0, c0, max(r1 - r0, 0), max(c1 - c0, 0))
+
+        def is_index_array(v):
+            if isinstance(v, (list, tuple, np.ndarray)):
+                v = np.asarray(v)
+                return v.ndim == 1 and (v.size == 0 or v.dtype.kind in "iu")
+            return hasattr(v, "dim") and hasattr(v, "data_ptr") and v.dim() == 1 and not v.dtype.is_floating_point \
+                and str(v.dtype) in ("torch.int32", "torch.int64")
+
+        if is_index_array(a) and is_index_array(b):
+            as_ix = lambda v: np.asarray(v, dtype=I64) if isinstance(v, (list, tuple, np.ndarray)) else v  # noqa: E731
+            return self.select(as_ix(a), as_ix(b))
+        raise TypeError("DeviceMatrix[...] takes two slices with step 1, or two 1-D index arrays")
 
     def take_diag_dev(self, out_ptr, stream=0):
         """out[c] = A[c, c] or 0, c < min(nrows, ncols) (Sparse.hs:640-650); out_ptr is a device pointer (int) to
@@ -1115,6 +1192,30 @@ def kronecker(matA, matB):
                              p_i32(b[3]), p_f64(b[4]), C.byref(nr), C.byref(nc), C.byref(cp), C.byref(ci),
                              C.byref(cx))
     return _take_matrix("spl_kronecker", st, nr, nc, cp, ci, cx)
+
+
+def subMatrix(origin, shape, mat):
+    """subMatrix (r0, c0) (nr, nc) mat: the nr x nc window of `mat` whose top left corner is (r0, c0), indices relative
+    to the window — the operation the signature and the two guards of Sparse.hs:704-729 document.  The reference's body
+    is untested and does not compute it: (1) `U.slice ix0 nix` passes an END where a LENGTH belongs, (2) the kept row
+    indices are not shifted by r0, (3) `computePtrs nc _indices` builds the column pointers from ROW indices.  Those
+    bits are not reproduced; the documented operation is what is computed, on the device: one upload, the handle call
+    (spl_matrix_submatrix), one export."""
+    r0, c0 = (int(v) for v in origin)
+    nr, nc = (int(v) for v in shape)
+    if min(r0, c0, nr, nc) < 0:
+        _oops("subMatrix", "negative origin or size")
+    if r0 + nr > mat.nrows:
+        _oops("subMatrix", "range exceeds input row size")
+    if c0 + nc > mat.ncols:
+        _oops("subMatrix", "range exceeds input column size")
+    _ffi.require_gpu()
+    if mat.is_complex:
+        # the CSC fields of a complex handle are export_csr of its transpose (include/sparse_linear_hip.h)
+        cp, ri, v = DeviceMatrix.from_csc_complex(mat).submatrix(r0, c0, nr, nc).transpose().export_csr()
+    else:
+        cp, ri, v = DeviceMatrix.from_csc(mat).submatrix(r0, c0, nr, nc).export_csc()
+    return Matrix(nc, nr, cp, ri, v.copy())
 
 
 def pack(mat):
