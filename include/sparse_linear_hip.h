@@ -141,12 +141,13 @@ int spl_kronecker(int nrowsA, int ncolsA, const int *Ap, const int *Ai, const do
 
 /* hcat / vcat / fromBlocks / fromBlocksDiag (Sparse.hs:500-595) in one call: nblocks CSC blocks (block b is
  * nrows[b] x ncols[b] with arrays Ap[b], Ai[b], Ax[b]) are placed at (row_off[b], col_off[b]) of an
- * nrowsC x ncolsC result.  Column c of the result is the concatenation, in list order, of the columns of the
- * blocks that cover it, rows shifted by the block's row offset (vcat's copyWithOffset, Sparse.hs:551-559):
- * blocks sharing columns must be listed by ascending row offset, as vcat stacks them.  hcat: row_off = 0,
- * col_off = running widths; vcat: col_off = 0, row_off = running heights; fromBlocks: both.  value_width = 1
- * (double) or 2 (packed Complex Double: the entries are moved, never combined).  Outputs malloc()'d as for
- * spl_spgemm; SPL_ERROR_dimension_mismatch if a block leaves the result. */
+ * nrowsC x ncolsC result.  Column c of the result is the concatenation, by ascending row offset, of the columns of
+ * the blocks that cover it, rows shifted by the block's row offset (vcat's copyWithOffset, Sparse.hs:551-559); the
+ * order the blocks are listed in does not matter.  Inside a block's column the entries are moved in the order they
+ * have.  hcat: row_off = 0, col_off = running widths; vcat: col_off = 0, row_off = running heights; fromBlocks: both.
+ * value_width = 1 (double) or 2 (packed Complex Double: the entries are moved, never combined).  Outputs malloc()'d
+ * as for spl_spgemm; SPL_ERROR_dimension_mismatch if a block leaves the result or two blocks overlap,
+ * SPL_ERROR_index_overflow if the blocks' entries together do not fit int32. */
 int spl_assemble_blocks(int nblocks, const int *nrows, const int *ncols, const int *const *Ap, const int *const *Ai,
                         const double *const *Ax, int value_width, const int *row_off, const int *col_off, int nrowsC,
                         int ncolsC, int **Cp, int **Ci, double **Cx);

@@ -147,6 +147,21 @@ std::unique_ptr<Matrix> make_matrix(int device, int64_t nrows_global, int64_t nc
   return m;
 }
 
+// An nrows x ncols CSC tuple that upload_csc (columns sorted) or upload_validated (columns as they are) put on the
+// device, as an unpublished handle: its arrays, unchanged, are the ROW image of the transpose (ncols rows, nrows
+// columns).  What kronecker_handles, assemble_handles and take_diag_handle read is filled (rowptr64 / colidx / val / nnz,
+// the dimensions, vw); the handle is not finalized.  The arrays move out of d.
+std::unique_ptr<Matrix> transposed_image(int device, int nrows, int ncols, int vw, DeviceCsc &d, hipStream_t s) {
+  std::unique_ptr<Matrix> m = make_matrix(device, ncols, nrows, 0, ncols, vw);
+  m->nnz = d.nnz;
+  m->rowptr64.alloc((size_t)ncols + 1);
+  widen_i32_to_i64(d.p.get(), m->rowptr64.get(), (int64_t)ncols + 1, s);
+  m->rowptr = std::move(d.p);
+  m->colidx = std::move(d.i);
+  m->val = std::move(d.x);
+  return m;
+}
+
 // finish a handle whose rowptr64 / colidx / val are filled and hand it to the caller
 int publish(std::unique_ptr<Matrix> m, hipStream_t s, void **H) {
   finalize_matrix(m.get(), s);
@@ -252,8 +267,9 @@ struct DeviceResult {
 };
 
 // the body of the one-shot binary operations (spl_spgemm, spl_lin, spl_kronecker and their complex forms), after the
-// caller's argument checks: upload A and B with vw doubles per value, op(A, B, C, s) on the device, download the
-// nrowsC x ncolsC result into the caller's *Cp / *Ci / *Cx; the shape is written on success only
+// caller's argument checks: upload A and B with vw doubles per value, op(A, B, C, s) on the device (it may refuse with
+// a status before it allocates anything of C), download the nrowsC x ncolsC result into the caller's *Cp / *Ci / *Cx;
+// the shape is written on success only
 template <typename Op>
 int binary_one_shot(int vw, const HostCsc &a, const HostCsc &b, int64_t nrowsC, int64_t ncolsC, int *nrowsC_out,
                     int *ncolsC_out, int **Cp, int **Ci, double **Cx, Op &&op) {
@@ -266,7 +282,8 @@ int binary_one_shot(int vw, const HostCsc &a, const HostCsc &b, int64_t nrowsC, 
     st = upload_csc(b.nrows, b.ncols, b.p, b.i, b.x, vw, B, s);
     if (st != SPL_OK) return st;
     DeviceResult C;
-    op(A, B, C, s);
+    st = op(A, B, C, s);
+    if (st != SPL_OK) return st;
     st = download_result(ncolsC, C.nnz, vw, C.p.get(), C.i.get(), C.x.get(), Cp, Ci, Cx, s);
     if (st != SPL_OK) return st;
     *nrowsC_out = (int)nrowsC;
@@ -1440,6 +1457,7 @@ int spl_spgemm(int nrowsA, int ncolsA, const int *Ap, const int *Ai, const doubl
                          Cp, Ci, Cx, [&](DeviceCsc &A, DeviceCsc &B, DeviceResult &C, hipStream_t s) {
                            spgemm_device(nrowsA, ncolsA, A.p.get(), A.i.get(), A.x.get(), ncolsB, B.p.get(), B.i.get(),
                                          B.x.get(), C.p, C.i, C.x, &C.nnz, nullptr, s);
+                           return SPL_OK;
                          });
 }
 
@@ -1459,28 +1477,33 @@ int spl_assemble_blocks(int nblocks, const int *nrows, const int *ncols, const i
     if (!Ap[b]) return SPL_ERROR_argument_missing;
   }
   return guarded([&]() -> int {
-    (void)current_device();
+    const int dev = current_device();
     hipStream_t s = nullptr;
-    std::vector<DBuf<int>> dp((size_t)nblocks), di((size_t)nblocks);
-    std::vector<DBuf<double>> dx((size_t)nblocks);
-    std::vector<const int *> pp((size_t)nblocks), pi((size_t)nblocks);
-    std::vector<const double *> px((size_t)nblocks);
+    // the images of the blocks' transposes, placed with rows and columns exchanged: that is the transpose of the result,
+    // whose row image is the result's CSC fields
+    std::vector<std::unique_ptr<Matrix>> image((size_t)nblocks);
+    std::vector<const Matrix *> blk((size_t)nblocks);
+    std::vector<int64_t> roff((size_t)nblocks), coff((size_t)nblocks);
+    int64_t nnzC = 0;
     for (int b = 0; b < nblocks; ++b) {
       const int64_t nz = Ap[b][ncols[b]];
       if (nz < 0 || (nz > 0 && (!Ai[b] || !Ax[b]))) return SPL_ERROR_argument_missing;
-      upload(dp[(size_t)b], Ap[b], (size_t)ncols[b] + 1, s);
-      upload(di[(size_t)b], Ai[b], (size_t)nz, s);
-      upload(dx[(size_t)b], Ax[b], (size_t)nz * (size_t)value_width, s);
-      int st = validate_compressed(dp[(size_t)b].get(), di[(size_t)b].get(), ncols[b], nrows[b], nz, s);
+      DeviceCsc d;
+      int st = upload_validated(nrows[b], ncols[b], Ap[b], Ai[b], Ax[b], value_width, d, s);
       if (st != SPL_OK) return st;
-      pp[(size_t)b] = dp[(size_t)b].get();
-      pi[(size_t)b] = di[(size_t)b].get();
-      px[(size_t)b] = dx[(size_t)b].get();
+      image[(size_t)b] = transposed_image(dev, nrows[b], ncols[b], value_width, d, s);
+      blk[(size_t)b] = image[(size_t)b].get();
+      roff[(size_t)b] = col_off[b];
+      coff[(size_t)b] = row_off[b];
+      nnzC += nz;
     }
-    DeviceResult C;
-    blocks_assemble_device(nblocks, ncols, pp.data(), pi.data(), px.data(), value_width, row_off, col_off, ncolsC, C.p,
-                           C.i, C.x, &C.nnz, s);
-    return download_result(ncolsC, C.nnz, value_width, C.p.get(), C.i.get(), C.x.get(), Cp, Ci, Cx, s);
+    std::vector<int> cut, lptr, list;
+    int st = blocks_table(nblocks, blk.data(), roff.data(), coff.data(), ncolsC, nrowsC, cut, lptr, list);
+    if (st != SPL_OK) return st;
+    if (nnzC >= 0x7fffffffLL) return SPL_ERROR_index_overflow;
+    std::unique_ptr<Matrix> C = make_matrix(dev, ncolsC, nrowsC, 0, ncolsC, value_width);
+    assemble_handles(nblocks, blk.data(), roff.data(), coff.data(), cut, lptr, list, C.get(), s);
+    return download_result(ncolsC, C->nnz, value_width, C->rowptr64.get(), C->colidx.get(), C->val.get(), Cp, Ci, Cx, s);
   });
 }
 
@@ -1495,6 +1518,7 @@ int spl_lin(double alpha, int nrowsA, int ncolsA, const int *Ap, const int *Ai, 
                          Cp, Ci, Cx, [&](DeviceCsc &A, DeviceCsc &B, DeviceResult &C, hipStream_t s) {
                            lin_device(alpha, A.p.get(), A.i.get(), A.x.get(), beta, B.p.get(), B.i.get(), B.x.get(),
                                       ncolsA, C.p, C.i, C.x, &C.nnz, s);
+                           return SPL_OK;
                          });
 }
 
@@ -1509,6 +1533,7 @@ int spl_spgemm_z(int nrowsA, int ncolsA, const int *Ap, const int *Ai, const dou
                          Cp, Ci, Cz, [&](DeviceCsc &A, DeviceCsc &B, DeviceResult &C, hipStream_t s) {
                            spgemm_device_z(nrowsA, ncolsA, A.p.get(), A.i.get(), A.x.get(), ncolsB, B.p.get(),
                                            B.i.get(), B.x.get(), C.p, C.i, C.x, &C.nnz, nullptr, s);
+                           return SPL_OK;
                          });
 }
 
@@ -1523,6 +1548,7 @@ int spl_lin_z(const double alpha[2], int nrowsA, int ncolsA, const int *Ap, cons
                          Cp, Ci, Cz, [&](DeviceCsc &A, DeviceCsc &B, DeviceResult &C, hipStream_t s) {
                            lin_device_z(alpha, A.p.get(), A.i.get(), A.x.get(), beta, B.p.get(), B.i.get(), B.x.get(),
                                         ncolsA, C.p, C.i, C.x, &C.nnz, s);
+                           return SPL_OK;
                          });
 }
 
@@ -1536,9 +1562,20 @@ int spl_kronecker(int nrowsA, int ncolsA, const int *Ap, const int *Ai, const do
     return SPL_ERROR_index_overflow;  // the seam is int32 (Foreign.hs:24-28)
   return binary_one_shot(1, {nrowsA, ncolsA, Ap, Ai, Ax}, {nrowsB, ncolsB, Bp, Bi, Bx}, (int64_t)nrowsA * nrowsB,
                          (int64_t)ncolsA * ncolsB, nrowsC, ncolsC, Cp, Ci, Cx,
-                         [&](DeviceCsc &A, DeviceCsc &B, DeviceResult &C, hipStream_t s) {
-                           kronecker_device(nrowsB, A.p.get(), A.i.get(), A.x.get(), ncolsA, B.p.get(), B.i.get(),
-                                            B.x.get(), ncolsB, C.p, C.i, C.x, &C.nnz, s);
+                         [&](DeviceCsc &A, DeviceCsc &B, DeviceResult &C, hipStream_t s) -> int {
+                           if (A.nnz * B.nnz >= 0x7fffffffLL) return SPL_ERROR_index_overflow;
+                           // (A (x) B)^T = A^T (x) B^T: the row image of the result's transpose is its CSC fields
+                           const int dev = current_device();
+                           const int64_t nr = (int64_t)nrowsA * nrowsB, nc = (int64_t)ncolsA * ncolsB;
+                           std::unique_ptr<Matrix> At = transposed_image(dev, nrowsA, ncolsA, 1, A, s),
+                                                   Bt = transposed_image(dev, nrowsB, ncolsB, 1, B, s),
+                                                   Ct = make_matrix(dev, nc, nr, 0, nc);
+                           kronecker_handles(At.get(), Bt.get(), Ct.get(), s);
+                           C.p = std::move(Ct->rowptr64);
+                           C.i = std::move(Ct->colidx);
+                           C.x = std::move(Ct->val);
+                           C.nnz = Ct->nnz;
+                           return SPL_OK;
                          });
 }
 
@@ -1547,14 +1584,15 @@ int spl_take_diag(int nrows, int ncols, const int *Ap, const int *Ai, const doub
   const int n = nrows < ncols ? nrows : ncols;
   if (n > 0 && !d) return SPL_ERROR_argument_missing;
   return guarded([&]() -> int {
-    (void)current_device();
+    const int dev = current_device();
     hipStream_t s = nullptr;
     DeviceCsc A;
     int st = upload_csc(nrows, ncols, Ap, Ai, Ax, 1, A, s);
     if (st != SPL_OK) return st;
     if (n == 0) return SPL_OK;
     DBuf<double> dd((size_t)n);
-    take_diag_device(A.p.get(), A.i.get(), A.x.get(), n, dd.get(), s);
+    std::unique_ptr<Matrix> At = transposed_image(dev, nrows, ncols, 1, A, s);  // the diagonal is its own transpose
+    take_diag_handle(At.get(), n, dd.get(), s);
     SPL_HIP(hipMemcpyAsync(d, dd.get(), (size_t)n * sizeof(double), hipMemcpyDeviceToHost, s));
     SPL_HIP(hipStreamSynchronize(s));
     SPL_HIP(hipGetLastError());

@@ -1,5 +1,6 @@
 // assemble.hip — COO -> CSC (`compress`, Sparse.hs:184-255) and the sparse linear
-// combination alpha*A + beta*B (`lin` over `glin`, Sparse.hs:401-431) in HBM.
+// combination alpha*A + beta*B (`lin` over `glin`, Sparse.hs:401-431) in HBM.  The structural constructors (kronecker,
+// block placement, takeDiag) are in assemble_handles.hip, for host tuples and handles alike.
 //
 // compress: bounds check (rows first, then columns: Sparse.hs:196-212), bucket by
 // column (histogram + scan + cursor scatter), sort every column by the 64-bit key
@@ -521,147 +522,6 @@ void lin_device_z(const double alpha[2], const int *Ap, const int *Ai, const dou
                   const int *Bp, const int *Bi, const double *Bz, int64_t ncols, DBuf<int64_t> &Cp, DBuf<int> &Ci,
                   DBuf<double> &Cz, int64_t *nnzC, hipStream_t s) {
   lin_device_any(2, alpha[0], alpha[1], Ap, Ai, Az, beta[0], beta[1], Bp, Bi, Bz, ncols, Cp, Ci, Cz, nnzC, s);
-}
-
-// ---- kronecker / takeDiag (Sparse.hs:597-648) --------------------------------------------------
-namespace {
-
-// lengths of the columns of C = A (x) B: column ja * ncolsB + jb has len(A[:,ja]) * len(B[:,jb]) entries
-__global__ void kron_count_kernel(const int *__restrict__ Ap, const int *__restrict__ Bp, int64_t ncolsA,
-                                  int64_t ncolsB, int64_t *__restrict__ counts) {
-  const int64_t j = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (j >= ncolsA * ncolsB) return;
-  const int64_t ja = j / ncolsB, jb = j % ncolsB;
-  counts[j] = (int64_t)(Ap[ja + 1] - Ap[ja]) * (int64_t)(Bp[jb + 1] - Bp[jb]);
-}
-
-// one wavefront per output column: entry e of the column is (a = e / lenB, b = e % lenB) -> row
-// ia * nrowsB + ib (ascending, as the rows of both operands ascend), value b * a
-__global__ __launch_bounds__(256) void kron_fill_kernel(const int *__restrict__ Ap, const int *__restrict__ Ai,
-                                                        const double *__restrict__ Ax,
-                                                        const int *__restrict__ Bp, const int *__restrict__ Bi,
-                                                        const double *__restrict__ Bx, int64_t ncolsA,
-                                                        int64_t ncolsB, int nrowsB,
-                                                        const int64_t *__restrict__ Cp, int *__restrict__ Ci,
-                                                        double *__restrict__ Cx) {
-  const int lane = threadIdx.x & 63;
-  const int64_t j = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
-  if (j >= ncolsA * ncolsB) return;
-  const int64_t ja = j / ncolsB, jb = j % ncolsB;
-  const int pa = Ap[ja], pb = Bp[jb], lb = Bp[jb + 1] - pb;
-  const int64_t base = Cp[j], len = Cp[j + 1] - base;
-  for (int64_t e = lane; e < len; e += 64) {
-    const int ea = (int)(e / lb), eb = (int)(e % lb);
-    Ci[base + e] = Ai[pa + ea] * nrowsB + Bi[pb + eb];
-    Cx[base + e] = Bx[pb + eb] * Ax[pa + ea];  // U.map (* a) bs
-  }
-}
-
-// d[c] = A[c, c] or 0: 8 lanes search column c (rows ascend, at most one hit)
-__global__ __launch_bounds__(256) void take_diag_kernel(const int *__restrict__ Ap, const int *__restrict__ Ai,
-                                                        const double *__restrict__ Ax, int n,
-                                                        double *__restrict__ d) {
-  const int c = (int)((blockIdx.x * (unsigned)blockDim.x + threadIdx.x) >> 3), part = threadIdx.x & 7;
-  double v = 0.0;
-  if (c < n)
-    for (int p = Ap[c] + part; p < Ap[c + 1]; p += 8)
-      if (Ai[p] == c) v = Ax[p];
-  // exactly one lane can hold a hit; OR the bit patterns together (0.0 is all-zero bits)
-  unsigned long long bits = (unsigned long long)__double_as_longlong(v);
-  bits |= __shfl_xor(bits, 1, 64);
-  bits |= __shfl_xor(bits, 2, 64);
-  bits |= __shfl_xor(bits, 4, 64);
-  if (c < n && part == 0) d[c] = __longlong_as_double((long long)bits);
-}
-
-}  // namespace
-
-// C = A (x) B on device CSC arrays; Cp is 64-bit (the caller checks the int32 seam)
-void kronecker_device(int nrowsB, const int *Ap, const int *Ai, const double *Ax, int64_t ncolsA, const int *Bp,
-                      const int *Bi, const double *Bx, int64_t ncolsB, DBuf<int64_t> &Cp, DBuf<int> &Ci,
-                      DBuf<double> &Cx, int64_t *nnzC, hipStream_t s) {
-  const int64_t nc = ncolsA * ncolsB;
-  Cp.alloc((size_t)nc + 1);
-  DBuf<int64_t> counts((size_t)(nc ? nc : 1));
-  if (nc > 0)
-    hipLaunchKernelGGL(kron_count_kernel, dim3(blocks_for(nc, 256)), dim3(256), 0, s, Ap, Bp, ncolsA, ncolsB,
-                       counts.get());
-  exclusive_scan_i64(counts.get(), Cp.get(), nc, s);
-  int64_t nz = 0;
-  SPL_HIP(hipMemcpyAsync(&nz, Cp.get() + nc, sizeof(int64_t), hipMemcpyDeviceToHost, s));
-  SPL_HIP(hipStreamSynchronize(s));
-  *nnzC = nz;
-  if (nz >= 0x7fffffffLL) return;  // does not fit the int32 seam: the caller reports the overflow
-  Ci.alloc((size_t)nz);
-  Cx.alloc((size_t)nz);
-  if (nz > 0)
-    hipLaunchKernelGGL(kron_fill_kernel, dim3(blocks_for(nc, 4)), dim3(256), 0, s, Ap, Ai, Ax, Bp, Bi, Bx, ncolsA,
-                       ncolsB, nrowsB, Cp.get(), Ci.get(), Cx.get());
-  SPL_HIP(hipStreamSynchronize(s));
-}
-
-// ---- block assembly: hcat / vcat / fromBlocks / fromBlocksDiag (Sparse.hs:500-595) -----------------------
-// The result's column c is the concatenation, in list order, of column c - col_off[b] of every block b that
-// covers it, row indices shifted by row_off[b] (vcat's copyWithOffset, Sparse.hs:551-559; hcat is the case of
-// disjoint column ranges, fromBlocks = vcat . map hcat places block (r, c) at the summed heights / widths).
-// Blocks that share columns must be listed by ascending row offset (they are: vcat stacks in list order), so
-// every result column ascends.
-__global__ __launch_bounds__(256) void blocks_count_kernel(int ncols_b, const int *__restrict__ Bp, int col_off,
-                                                          int *__restrict__ len) {
-  const int c = blockIdx.x * blockDim.x + threadIdx.x;
-  if (c < ncols_b) len[col_off + c] += Bp[c + 1] - Bp[c];  // one launch per block, in stream order: no race
-}
-
-// one wavefront per column of the block: copy it behind what earlier blocks put into that result column
-__global__ __launch_bounds__(256) void blocks_copy_kernel(int ncols_b, const int *__restrict__ Bp, const int *__restrict__ Bi,
-                                                         const double *__restrict__ Bx, int vw, int row_off, int col_off,
-                                                         int64_t *__restrict__ cursor, int *__restrict__ Ci,
-                                                         double *__restrict__ Cx) {
-  const int lane = threadIdx.x & 63;
-  const int c = blockIdx.x * 4 + (threadIdx.x >> 6);
-  if (c >= ncols_b) return;
-  const int s = Bp[c], n = Bp[c + 1] - s;
-  const int64_t dst = cursor[col_off + c];
-  for (int t = lane; t < n; t += 64) {
-    Ci[dst + t] = Bi[s + t] + row_off;
-    for (int k = 0; k < vw; ++k) Cx[(dst + t) * vw + k] = Bx[(size_t)(s + t) * vw + k];
-  }
-  __builtin_amdgcn_wave_barrier();
-  if (lane == 0) cursor[col_off + c] = dst + n;
-}
-
-void blocks_assemble_device(int nblocks, const int *ncols_b, const int *const *d_Bp, const int *const *d_Bi,
-                            const double *const *d_Bx, int vw, const int *row_off, const int *col_off, int64_t ncolsC,
-                            DBuf<int64_t> &Cp, DBuf<int> &Ci, DBuf<double> &Cx, int64_t *nnzC, hipStream_t s) {
-  DBuf<int> len((size_t)ncolsC + 1);
-  SPL_HIP(hipMemsetAsync(len.get(), 0, ((size_t)ncolsC + 1) * sizeof(int), s));
-  for (int b = 0; b < nblocks; ++b)
-    if (ncols_b[b] > 0)
-      hipLaunchKernelGGL(blocks_count_kernel, dim3((unsigned)((ncols_b[b] + 255) / 256)), dim3(256), 0, s, ncols_b[b], d_Bp[b],
-                         col_off[b], len.get());
-  Cp.alloc((size_t)ncolsC + 1);
-  exclusive_scan_i32_to_i64(len.get(), Cp.get(), ncolsC, s);
-  int64_t nz = 0;
-  SPL_HIP(hipMemcpyAsync(&nz, Cp.get() + ncolsC, sizeof(int64_t), hipMemcpyDeviceToHost, s));
-  SPL_HIP(hipStreamSynchronize(s));
-  *nnzC = nz;
-  Ci.alloc((size_t)nz);
-  Cx.alloc((size_t)nz * (size_t)vw);
-  if (nz == 0) return;
-  DBuf<int64_t> cursor((size_t)ncolsC + 1);
-  SPL_HIP(hipMemcpyAsync(cursor.get(), Cp.get(), ((size_t)ncolsC + 1) * sizeof(int64_t), hipMemcpyDeviceToDevice, s));
-  for (int b = 0; b < nblocks; ++b)
-    if (ncols_b[b] > 0)
-      hipLaunchKernelGGL(blocks_copy_kernel, dim3((unsigned)((ncols_b[b] + 3) / 4)), dim3(256), 0, s, ncols_b[b], d_Bp[b], d_Bi[b],
-                         d_Bx[b], vw, row_off[b], col_off[b], cursor.get(), Ci.get(), Cx.get());
-  SPL_HIP(hipGetLastError());
-  SPL_HIP(hipStreamSynchronize(s));
-}
-
-void take_diag_device(const int *Ap, const int *Ai, const double *Ax, int n, double *d, hipStream_t s) {
-  if (n > 0)
-    hipLaunchKernelGGL(take_diag_kernel, dim3((unsigned)(((size_t)n * 8 + 255) / 256)), dim3(256), 0, s, Ap, Ai, Ax,
-                       n, d);
 }
 
 }  // namespace spl

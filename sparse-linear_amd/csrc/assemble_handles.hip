@@ -4,7 +4,9 @@
 //
 // A handle holds the ROW-major image: its (rowptr64, colidx, val) are the CSC fields of the transpose.  Every kernel
 // here walks that image; what the reference does per column these do per row, on the transposes (see the comment
-// above each entry point in abi.hip for why that gives the reference's result).
+// above each entry point in abi.hip for why that gives the reference's result).  The host-tuple calls spl_kronecker,
+// spl_assemble_blocks and spl_take_diag run the same kernels: a caller's CSC 5-tuple, uploaded as it is, is the row image
+// of its transpose, and all three operations commute with transposition (blocks with their offsets exchanged).
 //
 // All of them are store streams: 12 (real) or 20 (complex) bytes written per entry, the operands small and read
 // through the caches.  The work is therefore shaped to the OUTPUT: a group of G = 1, 2, 4 ... 64 lanes takes one result
@@ -14,34 +16,11 @@
 // dimensions fit 32 bits (the callers refuse dimensions of 2^31 and more).
 #include <algorithm>
 
-#include "common.hpp"
+#include "row_groups.hpp"
 
 namespace spl {
 
 namespace {
-
-constexpr int kAsmThreads = 256;
-
-inline unsigned grid_rows(int64_t rows, int group, int64_t cap = 1 << 16) {
-  const int64_t per_block = kAsmThreads / group;
-  int64_t b = (rows + per_block - 1) / per_block;
-  if (b < 1) b = 1;
-  if (b > cap) b = cap;
-  return (unsigned)b;
-}
-
-// smallest power of two >= mean (1 ... 64): the lanes one result row gets
-inline int group_for(double mean) {
-  int g = 1;
-  while (g < 64 && (double)g < mean) g <<= 1;
-  return g;
-}
-
-template <int VW>
-__device__ inline void store_value(double *__restrict__ x, int64_t o, double re, double im) {
-  if (VW == 1) x[o] = re;
-  else *reinterpret_cast<double2 *>(x + 2 * o) = make_double2(re, im);  // 16-byte aligned: the buffer is, o counts pairs
-}
 
 // ---- kronecker ------------------------------------------------------------------------------------------------
 // Row r = ra * nrowsB + rb of C = A (x) B is, for every entry (ca, a) of row ra of A in order and every entry (cb, b)
@@ -53,12 +32,12 @@ __device__ inline void store_value(double *__restrict__ x, int64_t o, double re,
 // group's last lane, whose first pair is ((G-1) / lenB, (G-1) % lenB), by a shuffle.  After that the pair advances by
 // counters.  The rows themselves advance by counters as well (the grid's stride as a pair, from the host).
 template <int G, int VW>
-__global__ __launch_bounds__(kAsmThreads) void kron_rows_kernel(
+__global__ __launch_bounds__(kRowThreads) void kron_rows_kernel(
     const int64_t *__restrict__ Ap, const int *__restrict__ Aj, const double *__restrict__ Ax,
     const int64_t *__restrict__ Bp, const int *__restrict__ Bj, const double *__restrict__ Bx, unsigned nrowsB,
     unsigned ncolsB, int64_t nnzB, int64_t nrowsC, int64_t nnzC, unsigned stride_a, unsigned stride_b,
     int64_t *__restrict__ Cp, int *__restrict__ Cj, double *__restrict__ Cx) {
-  constexpr int kGroups = kAsmThreads / G;
+  constexpr int kGroups = kRowThreads / G;
   const unsigned lane = threadIdx.x % G;
   int64_t r = (int64_t)blockIdx.x * kGroups + threadIdx.x / G;
   const int64_t stride = (int64_t)gridDim.x * kGroups;  // == stride_a * nrowsB + stride_b
@@ -103,25 +82,6 @@ __global__ __launch_bounds__(kAsmThreads) void kron_rows_kernel(
   }
 }
 
-template <int VW>
-void launch_kron(int group, unsigned grid, hipStream_t s, const Matrix *A, const Matrix *B, int64_t nrowsC, int64_t nnzC,
-                 unsigned stride_a, unsigned stride_b, int64_t *Cp, int *Cj, double *Cx) {
-#define SPL_KRON(G)                                                                                                   \
-  hipLaunchKernelGGL((kron_rows_kernel<G, VW>), dim3(grid), dim3(kAsmThreads), 0, s, A->rowptr64.get(),               \
-                     A->colidx.get(), A->val.get(), B->rowptr64.get(), B->colidx.get(), B->val.get(),                 \
-                     (unsigned)B->nrows_local, (unsigned)B->ncols, B->nnz, nrowsC, nnzC, stride_a, stride_b, Cp, Cj, Cx)
-  switch (group) {
-    case 1: SPL_KRON(1); break;
-    case 2: SPL_KRON(2); break;
-    case 4: SPL_KRON(4); break;
-    case 8: SPL_KRON(8); break;
-    case 16: SPL_KRON(16); break;
-    case 32: SPL_KRON(32); break;
-    default: SPL_KRON(64); break;
-  }
-#undef SPL_KRON
-}
-
 // ---- block assembly -------------------------------------------------------------------------------------------
 // What the device knows of a placed block, and the table that says which blocks cover a result row: the rows are cut
 // at every block boundary into intervals [cut[i], cut[i+1]), and list[lptr[i] .. lptr[i+1]) names the blocks covering
@@ -146,12 +106,12 @@ __device__ inline int find_interval(const int *__restrict__ cut, int nint, int r
 }
 
 template <int G>
-__global__ __launch_bounds__(kAsmThreads) void blocks_len_kernel(const PlacedBlock *__restrict__ blk,
+__global__ __launch_bounds__(kRowThreads) void blocks_len_kernel(const PlacedBlock *__restrict__ blk,
                                                                  const int *__restrict__ cut, int nint,
                                                                  const int *__restrict__ lptr,
                                                                  const int *__restrict__ list, int nrowsC,
                                                                  int *__restrict__ len) {
-  constexpr int kGroups = kAsmThreads / G;
+  constexpr int kGroups = kRowThreads / G;
   const int lane = threadIdx.x % G;
   int64_t r = (int64_t)blockIdx.x * kGroups + threadIdx.x / G;
   const int64_t stride = (int64_t)gridDim.x * kGroups;
@@ -163,20 +123,19 @@ __global__ __launch_bounds__(kAsmThreads) void blocks_len_kernel(const PlacedBlo
       const int64_t *p = b.p + ((int)r - b.row_off);
       n += (int)(p[1] - p[0]);
     }
-#pragma unroll
-    for (int w = 1; w < G; w <<= 1) n += __shfl_xor(n, w, G);  // all lanes of the group are here: r is theirs in common
+    n = group_sum<G>(n);  // all lanes of the group are here: r is theirs in common
     if (lane == 0) len[r] = n;  // <= ncolsC < 2^31
   }
 }
 
 template <int G, int VW>
-__global__ __launch_bounds__(kAsmThreads) void blocks_copy_rows_kernel(const PlacedBlock *__restrict__ blk,
+__global__ __launch_bounds__(kRowThreads) void blocks_copy_rows_kernel(const PlacedBlock *__restrict__ blk,
                                                                        const int *__restrict__ cut, int nint,
                                                                        const int *__restrict__ lptr,
                                                                        const int *__restrict__ list, int nrowsC,
                                                                        const int64_t *__restrict__ Cp,
                                                                        int *__restrict__ Cj, double *__restrict__ Cx) {
-  constexpr int kGroups = kAsmThreads / G;
+  constexpr int kGroups = kRowThreads / G;
   const int lane = threadIdx.x % G;
   int64_t r = (int64_t)blockIdx.x * kGroups + threadIdx.x / G;
   const int64_t stride = (int64_t)gridDim.x * kGroups;
@@ -199,14 +158,14 @@ __global__ __launch_bounds__(kAsmThreads) void blocks_copy_rows_kernel(const Pla
 }
 
 // ---- diagonals --------------------------------------------------------------------------------------------------
-// d[c] = A[c, c] or 0: 8 lanes search row c of the row image (columns ascend, at most one hit), as take_diag_kernel
-// of assemble.hip does on a column; on 64-bit pointers, and for packed complex values too
+// d[c] = A[c, c] or 0: 8 lanes search row c of the row image (at most one hit); on 64-bit pointers, real or packed
+// complex values
 template <int VW>
-__global__ __launch_bounds__(kAsmThreads) void take_diag_rows_kernel(const int64_t *__restrict__ Ap,
+__global__ __launch_bounds__(kRowThreads) void take_diag_rows_kernel(const int64_t *__restrict__ Ap,
                                                                      const int *__restrict__ Aj,
                                                                      const double *__restrict__ Ax, int64_t n,
                                                                      double *__restrict__ d) {
-  const int64_t c = ((int64_t)blockIdx.x * kAsmThreads + threadIdx.x) >> 3;
+  const int64_t c = ((int64_t)blockIdx.x * kRowThreads + threadIdx.x) >> 3;
   const int part = threadIdx.x & 7;
   double v[VW];
 #pragma unroll
@@ -230,11 +189,11 @@ __global__ __launch_bounds__(kAsmThreads) void take_diag_rows_kernel(const int64
 
 // diag (Sparse.hs:652-659): pointers 0 .. n, indices 0 .. n-1, the values copied — or ones (ident) when there are none
 template <int VW>
-__global__ __launch_bounds__(kAsmThreads) void diag_kernel(int64_t n, const double *__restrict__ values,
+__global__ __launch_bounds__(kRowThreads) void diag_kernel(int64_t n, const double *__restrict__ values,
                                                            int64_t *__restrict__ Cp, int *__restrict__ Cj,
                                                            double *__restrict__ Cx) {
-  int64_t i = (int64_t)blockIdx.x * kAsmThreads + threadIdx.x;
-  const int64_t stride = (int64_t)gridDim.x * kAsmThreads;
+  int64_t i = (int64_t)blockIdx.x * kRowThreads + threadIdx.x;
+  const int64_t stride = (int64_t)gridDim.x * kRowThreads;
   for (; i <= n; i += stride) {
     Cp[i] = i;
     if (i < n) {
@@ -252,25 +211,22 @@ __global__ __launch_bounds__(kAsmThreads) void diag_kernel(int64_t n, const doub
 void kronecker_handles(const Matrix *A, const Matrix *B, Matrix *C, hipStream_t s) {
   const int64_t nrowsC = C->nrows_local;
   const int64_t nnzC = A->nnz * B->nnz;
-  C->nnz = nnzC;
-  C->rowptr64.alloc((size_t)nrowsC + 1);
-  C->colidx.alloc((size_t)nnzC);
-  C->val.alloc((size_t)nnzC * (size_t)C->vw);
+  allocate_result(C, nnzC);
   if (nrowsC == 0) {
-    SPL_HIP(hipMemsetAsync(C->rowptr64.get(), 0, sizeof(int64_t), s));
+    zero_pointers(C, s);
     return;
   }
   const int group = group_for((double)nnzC / (double)nrowsC);
   const unsigned grid = grid_rows(nrowsC, group);
-  const int64_t stride = (int64_t)grid * (kAsmThreads / group);
+  const int64_t stride = (int64_t)grid * (kRowThreads / group);
   const int64_t nrowsB = B->nrows_local;  // > 0, as nrowsC is
   const unsigned stride_a = (unsigned)(stride / nrowsB), stride_b = (unsigned)(stride % nrowsB);
-  if (C->vw == 1)
-    launch_kron<1>(group, grid, s, A, B, nrowsC, nnzC, stride_a, stride_b, C->rowptr64.get(), C->colidx.get(),
-                   C->val.get());
-  else
-    launch_kron<2>(group, grid, s, A, B, nrowsC, nnzC, stride_a, stride_b, C->rowptr64.get(), C->colidx.get(),
-                   C->val.get());
+  for_group_and_width(group, C->vw, [&](auto g, auto vw) {
+    hipLaunchKernelGGL((kron_rows_kernel<decltype(g)::value, decltype(vw)::value>), dim3(grid), dim3(kRowThreads), 0, s,
+                       A->rowptr64.get(), A->colidx.get(), A->val.get(), B->rowptr64.get(), B->colidx.get(),
+                       B->val.get(), (unsigned)B->nrows_local, (unsigned)B->ncols, B->nnz, nrowsC, nnzC, stride_a,
+                       stride_b, C->rowptr64.get(), C->colidx.get(), C->val.get());
+  });
   SPL_HIP(hipGetLastError());
 }
 
@@ -328,12 +284,9 @@ void assemble_handles(int nblocks, const Matrix *const *blk, const int64_t *row_
   const int nint = (int)cut.size() - 1;
   int64_t nnzC = 0;
   for (int b = 0; b < nblocks; ++b) nnzC += blk[b]->nnz;
-  C->nnz = nnzC;
-  C->rowptr64.alloc((size_t)nrowsC + 1);
-  C->colidx.alloc((size_t)nnzC);
-  C->val.alloc((size_t)nnzC * (size_t)C->vw);
+  allocate_result(C, nnzC);
   if (nrowsC == 0 || nnzC == 0) {
-    SPL_HIP(hipMemsetAsync(C->rowptr64.get(), 0, ((size_t)nrowsC + 1) * sizeof(int64_t), s));
+    zero_pointers(C, s);
     return;
   }
   std::vector<PlacedBlock> hb((size_t)nblocks);
@@ -363,39 +316,16 @@ void assemble_handles(int nblocks, const Matrix *const *blk, const int64_t *row_
     covered += (int64_t)(lptr[(size_t)i + 1] - lptr[(size_t)i]) * (cut[(size_t)i + 1] - cut[(size_t)i]);
   const int g1 = group_for((double)covered / (double)nrowsC);
   const int g2 = group_for((double)nnzC / (double)nrowsC);
-#define SPL_LEN(G)                                                                                                    \
-  hipLaunchKernelGGL((blocks_len_kernel<G>), dim3(grid_rows(nrowsC, G)), dim3(kAsmThreads), 0, s, d_blk, d_cut, nint, \
-                     d_lptr, d_list, (int)nrowsC, len.get())
-  switch (g1) {
-    case 1: SPL_LEN(1); break;
-    case 2: SPL_LEN(2); break;
-    case 4: SPL_LEN(4); break;
-    case 8: SPL_LEN(8); break;
-    case 16: SPL_LEN(16); break;
-    case 32: SPL_LEN(32); break;
-    default: SPL_LEN(64); break;
-  }
-#undef SPL_LEN
+  for_group_and_width(g1, C->vw, [&](auto g, auto) {
+    hipLaunchKernelGGL((blocks_len_kernel<decltype(g)::value>), dim3(grid_rows(nrowsC, g)), dim3(kRowThreads), 0, s,
+                       d_blk, d_cut, nint, d_lptr, d_list, (int)nrowsC, len.get());
+  });
   exclusive_scan_i32_to_i64(len.get(), C->rowptr64.get(), nrowsC, s);
-#define SPL_COPY(G)                                                                                                   \
-  do {                                                                                                                \
-    if (C->vw == 1)                                                                                                   \
-      hipLaunchKernelGGL((blocks_copy_rows_kernel<G, 1>), dim3(grid_rows(nrowsC, G)), dim3(kAsmThreads), 0, s, d_blk, \
-                         d_cut, nint, d_lptr, d_list, (int)nrowsC, C->rowptr64.get(), C->colidx.get(), C->val.get()); \
-    else                                                                                                              \
-      hipLaunchKernelGGL((blocks_copy_rows_kernel<G, 2>), dim3(grid_rows(nrowsC, G)), dim3(kAsmThreads), 0, s, d_blk, \
-                         d_cut, nint, d_lptr, d_list, (int)nrowsC, C->rowptr64.get(), C->colidx.get(), C->val.get()); \
-  } while (0)
-  switch (g2) {
-    case 1: SPL_COPY(1); break;
-    case 2: SPL_COPY(2); break;
-    case 4: SPL_COPY(4); break;
-    case 8: SPL_COPY(8); break;
-    case 16: SPL_COPY(16); break;
-    case 32: SPL_COPY(32); break;
-    default: SPL_COPY(64); break;
-  }
-#undef SPL_COPY
+  for_group_and_width(g2, C->vw, [&](auto g, auto vw) {
+    hipLaunchKernelGGL((blocks_copy_rows_kernel<decltype(g)::value, decltype(vw)::value>), dim3(grid_rows(nrowsC, g)),
+                       dim3(kRowThreads), 0, s, d_blk, d_cut, nint, d_lptr, d_list, (int)nrowsC, C->rowptr64.get(),
+                       C->colidx.get(), C->val.get());
+  });
   SPL_HIP(hipGetLastError());
   SPL_HIP(hipStreamSynchronize(s));  // `len` and `table` are released on return
 }
@@ -403,12 +333,12 @@ void assemble_handles(int nblocks, const Matrix *const *blk, const int64_t *row_
 // d[c] = A[c, c] (or 0), c < n = min(nrows, ncols), enqueued on s; d holds n entries of the handle's value kind
 void take_diag_handle(const Matrix *A, int64_t n, double *d, hipStream_t s) {
   if (n <= 0) return;
-  const unsigned grid = (unsigned)(((size_t)n * 8 + kAsmThreads - 1) / kAsmThreads);
+  const unsigned grid = (unsigned)(((size_t)n * 8 + kRowThreads - 1) / kRowThreads);
   if (A->vw == 1)
-    hipLaunchKernelGGL((take_diag_rows_kernel<1>), dim3(grid), dim3(kAsmThreads), 0, s, A->rowptr64.get(),
+    hipLaunchKernelGGL((take_diag_rows_kernel<1>), dim3(grid), dim3(kRowThreads), 0, s, A->rowptr64.get(),
                        A->colidx.get(), A->val.get(), n, d);
   else
-    hipLaunchKernelGGL((take_diag_rows_kernel<2>), dim3(grid), dim3(kAsmThreads), 0, s, A->rowptr64.get(),
+    hipLaunchKernelGGL((take_diag_rows_kernel<2>), dim3(grid), dim3(kRowThreads), 0, s, A->rowptr64.get(),
                        A->colidx.get(), A->val.get(), n, d);
   SPL_HIP(hipGetLastError());
 }
@@ -416,17 +346,13 @@ void take_diag_handle(const Matrix *A, int64_t n, double *d, hipStream_t s) {
 // the n x n diagonal matrix of n values in device memory (nullptr: ones); C's dimensions and value kind are set
 void diag_handle(const double *d_values, Matrix *C, hipStream_t s) {
   const int64_t n = C->nrows_local;
-  C->nnz = n;
-  C->rowptr64.alloc((size_t)n + 1);
-  C->colidx.alloc((size_t)n);
-  C->val.alloc((size_t)n * (size_t)C->vw);
-  int64_t blocks = (n + 1 + kAsmThreads - 1) / kAsmThreads;
-  if (blocks > 65536) blocks = 65536;
+  allocate_result(C, n);
+  const unsigned blocks = grid_flat(n + 1);
   if (C->vw == 1)
-    hipLaunchKernelGGL((diag_kernel<1>), dim3((unsigned)blocks), dim3(kAsmThreads), 0, s, n, d_values,
+    hipLaunchKernelGGL((diag_kernel<1>), dim3(blocks), dim3(kRowThreads), 0, s, n, d_values,
                        C->rowptr64.get(), C->colidx.get(), C->val.get());
   else
-    hipLaunchKernelGGL((diag_kernel<2>), dim3((unsigned)blocks), dim3(kAsmThreads), 0, s, n, d_values,
+    hipLaunchKernelGGL((diag_kernel<2>), dim3(blocks), dim3(kRowThreads), 0, s, n, d_values,
                        C->rowptr64.get(), C->colidx.get(), C->val.get());
   SPL_HIP(hipGetLastError());
 }

@@ -248,15 +248,6 @@ void lin_device_z(const double alpha[2], const int *Ap, const int *Ai, const dou
                   const int *Bp, const int *Bi, const double *Bz, int64_t ncols, DBuf<int64_t> &Cp, DBuf<int> &Ci,
                   DBuf<double> &Cz, int64_t *nnzC, hipStream_t s);
 
-void kronecker_device(int nrowsB, const int *Ap, const int *Ai, const double *Ax, int64_t ncolsA, const int *Bp,
-                      const int *Bi, const double *Bx, int64_t ncolsB, DBuf<int64_t> &Cp, DBuf<int> &Ci,
-                      DBuf<double> &Cx, int64_t *nnzC, hipStream_t s);
-void take_diag_device(const int *Ap, const int *Ai, const double *Ax, int n, double *d, hipStream_t s);
-// place blocks at (row_off, col_off) of a result with ncolsC columns; vw = doubles per value (1 real, 2 complex)
-void blocks_assemble_device(int nblocks, const int *ncols_b, const int *const *d_Bp, const int *const *d_Bi,
-                            const double *const *d_Bx, int vw, const int *row_off, const int *col_off, int64_t ncolsC,
-                            DBuf<int64_t> &Cp, DBuf<int> &Ci, DBuf<double> &Cx, int64_t *nnzC, hipStream_t s);
-
 // ---- compressed arrays in device memory, in and out (device_arrays.hip) --------------------------------------------
 // index_width: bytes per element of the caller's pointer and index arrays, 4 or 8; every comparison is made in that width
 // Pointers: [0] == 0, none negative, none above its successor; copied to out_ptr64[nmajor + 1] in the same pass.

@@ -13,48 +13,11 @@
 // (pointer).  A window of whole rows (c0 == 0, nc == ncols) searches nothing, scans nothing and is two device-to-device
 // copies behind a pointer shift.  A selection reads the indices of its source rows twice (count, copy) and looks every
 // one up in a column map of 4 ncols bytes, which stays in the caches.
-#include "common.hpp"
+#include "row_groups.hpp"
 
 namespace spl {
 
 namespace {
-
-constexpr int kSubThreads = 256;
-
-inline unsigned grid_rows(int64_t rows, int group, int64_t cap = 1 << 16) {
-  const int64_t per_block = kSubThreads / group;
-  int64_t b = (rows + per_block - 1) / per_block;
-  if (b < 1) b = 1;
-  if (b > cap) b = cap;
-  return (unsigned)b;
-}
-
-inline unsigned grid_flat(int64_t n, int64_t cap = 1 << 16) {
-  int64_t b = (n + kSubThreads - 1) / kSubThreads;
-  if (b < 1) b = 1;
-  if (b > cap) b = cap;
-  return (unsigned)b;
-}
-
-// smallest power of two >= mean (1 ... 64): the lanes one result row gets
-inline int group_for(double mean) {
-  int g = 1;
-  while (g < 64 && (double)g < mean) g <<= 1;
-  return g;
-}
-
-template <int VW>
-__device__ inline void move_value(const double *__restrict__ src, int64_t p, double *__restrict__ dst, int64_t o) {
-  if (VW == 1) dst[o] = src[p];
-  else *reinterpret_cast<double2 *>(dst + 2 * o) = *reinterpret_cast<const double2 *>(src + 2 * p);  // both 16-byte aligned
-}
-
-template <int G>
-__device__ inline int group_sum(int v) {
-#pragma unroll
-  for (int w = 1; w < G; w <<= 1) v += __shfl_xor(v, w, G);
-  return v;
-}
 
 // entries of the ascending run j[a .. b) that are < x
 __device__ inline int count_less(const int *__restrict__ j, int64_t a, int64_t b, int x) {
@@ -72,11 +35,11 @@ __device__ inline int count_less(const int *__restrict__ j, int64_t a, int64_t b
 // each — "how many entries are below x" adds up over the pieces — so a row of 300 entries costs each lane three probes.
 // first[r] keeps where the run starts: the copy pass does not search again.
 template <int G>
-__global__ __launch_bounds__(kSubThreads) void window_len_kernel(const int64_t *__restrict__ Ap,
+__global__ __launch_bounds__(kRowThreads) void window_len_kernel(const int64_t *__restrict__ Ap,
                                                                  const int *__restrict__ Aj, int64_t r0, int64_t nr,
                                                                  int c0, int c1, int *__restrict__ len,
                                                                  int64_t *__restrict__ first) {
-  constexpr int kGroups = kSubThreads / G;
+  constexpr int kGroups = kRowThreads / G;
   const int lane = threadIdx.x % G;
   int64_t r = (int64_t)blockIdx.x * kGroups + threadIdx.x / G;
   const int64_t stride = (int64_t)gridDim.x * kGroups;
@@ -97,12 +60,12 @@ __global__ __launch_bounds__(kSubThreads) void window_len_kernel(const int64_t *
 }
 
 template <int G, int VW>
-__global__ __launch_bounds__(kSubThreads) void window_copy_kernel(const int *__restrict__ Aj,
+__global__ __launch_bounds__(kRowThreads) void window_copy_kernel(const int *__restrict__ Aj,
                                                                   const double *__restrict__ Ax,
                                                                   const int64_t *__restrict__ first, int64_t nr, int c0,
                                                                   const int64_t *__restrict__ Cp, int *__restrict__ Cj,
                                                                   double *__restrict__ Cx) {
-  constexpr int kGroups = kSubThreads / G;
+  constexpr int kGroups = kRowThreads / G;
   const int lane = threadIdx.x % G;
   int64_t r = (int64_t)blockIdx.x * kGroups + threadIdx.x / G;
   const int64_t stride = (int64_t)gridDim.x * kGroups;
@@ -117,10 +80,10 @@ __global__ __launch_bounds__(kSubThreads) void window_copy_kernel(const int *__r
 }
 
 // whole rows: Cp[i] = Ap[r0 + i] - Ap[r0], i <= nr
-__global__ __launch_bounds__(kSubThreads) void shift_pointers_kernel(const int64_t *__restrict__ Ap, int64_t r0,
+__global__ __launch_bounds__(kRowThreads) void shift_pointers_kernel(const int64_t *__restrict__ Ap, int64_t r0,
                                                                      int64_t nr, int64_t *__restrict__ Cp) {
-  int64_t i = (int64_t)blockIdx.x * kSubThreads + threadIdx.x;
-  const int64_t stride = (int64_t)gridDim.x * kSubThreads;
+  int64_t i = (int64_t)blockIdx.x * kRowThreads + threadIdx.x;
+  const int64_t stride = (int64_t)gridDim.x * kRowThreads;
   const int64_t base = Ap[r0];
   for (; i <= nr; i += stride) Cp[i] = Ap[r0 + i] - base;
 }
@@ -135,10 +98,10 @@ struct SelectFlags {
 
 // I: every entry in [0, nrows), compared in the source width, and narrowed to rows[]
 template <typename T>
-__global__ __launch_bounds__(kSubThreads) void check_rows_kernel(const T *__restrict__ I, int64_t nI, int64_t nrows,
+__global__ __launch_bounds__(kRowThreads) void check_rows_kernel(const T *__restrict__ I, int64_t nI, int64_t nrows,
                                                                  int *__restrict__ rows, SelectFlags *__restrict__ f) {
-  int64_t k = (int64_t)blockIdx.x * kSubThreads + threadIdx.x;
-  const int64_t stride = (int64_t)gridDim.x * kSubThreads;
+  int64_t k = (int64_t)blockIdx.x * kRowThreads + threadIdx.x;
+  const int64_t stride = (int64_t)gridDim.x * kRowThreads;
   for (; k < nI; k += stride) {
     const T i = I[k];
     const bool ok = i >= 0 && i < (T)nrows;
@@ -150,10 +113,10 @@ __global__ __launch_bounds__(kSubThreads) void check_rows_kernel(const T *__rest
 // J: map[J[k]] = k over a map filled with -1.  A slot that was taken already names a repeated column, an entry outside
 // [0, ncols) records its position; whether J ascends is seen on the way (then the result rows need no sort)
 template <typename T>
-__global__ __launch_bounds__(kSubThreads) void scatter_cols_kernel(const T *__restrict__ J, int64_t nJ, int64_t ncols,
+__global__ __launch_bounds__(kRowThreads) void scatter_cols_kernel(const T *__restrict__ J, int64_t nJ, int64_t ncols,
                                                                    int *__restrict__ map, SelectFlags *__restrict__ f) {
-  int64_t k = (int64_t)blockIdx.x * kSubThreads + threadIdx.x;
-  const int64_t stride = (int64_t)gridDim.x * kSubThreads;
+  int64_t k = (int64_t)blockIdx.x * kRowThreads + threadIdx.x;
+  const int64_t stride = (int64_t)gridDim.x * kRowThreads;
   for (; k < nJ; k += stride) {
     const T j = J[k];
     if (j < 0 || j >= (T)ncols) {
@@ -169,12 +132,12 @@ __global__ __launch_bounds__(kSubThreads) void scatter_cols_kernel(const T *__re
 __device__ inline int64_t source_row(const int *__restrict__ rows, int64_t r) { return rows ? (int64_t)rows[r] : r; }
 
 template <int G>
-__global__ __launch_bounds__(kSubThreads) void select_len_kernel(const int64_t *__restrict__ Ap,
+__global__ __launch_bounds__(kRowThreads) void select_len_kernel(const int64_t *__restrict__ Ap,
                                                                  const int *__restrict__ Aj,
                                                                  const int *__restrict__ rows,
                                                                  const int *__restrict__ map, int64_t nI,
                                                                  int *__restrict__ len) {
-  constexpr int kGroups = kSubThreads / G;
+  constexpr int kGroups = kRowThreads / G;
   const int lane = threadIdx.x % G;
   int64_t r = (int64_t)blockIdx.x * kGroups + threadIdx.x / G;
   const int64_t stride = (int64_t)gridDim.x * kGroups;
@@ -198,14 +161,14 @@ __global__ __launch_bounds__(kSubThreads) void select_len_kernel(const int64_t *
 // loop bound does not depend on the lane), so the group's bits of the ballot are complete whatever the other groups of
 // the wavefront are doing.
 template <int G, int VW>
-__global__ __launch_bounds__(kSubThreads) void select_copy_kernel(const int64_t *__restrict__ Ap,
+__global__ __launch_bounds__(kRowThreads) void select_copy_kernel(const int64_t *__restrict__ Ap,
                                                                   const int *__restrict__ Aj,
                                                                   const double *__restrict__ Ax,
                                                                   const int *__restrict__ rows,
                                                                   const int *__restrict__ map, int64_t nI,
                                                                   const int64_t *__restrict__ Cp, int *__restrict__ Cj,
                                                                   double *__restrict__ Cx) {
-  constexpr int kGroups = kSubThreads / G;
+  constexpr int kGroups = kRowThreads / G;
   constexpr unsigned long long kGroupMask = G == 64 ? ~0ull : ((1ull << (G & 63)) - 1ull);
   const int lane = threadIdx.x % G;
   const int shift = (threadIdx.x & 63) - lane;  // the group's first lane in its wavefront
@@ -233,35 +196,6 @@ __global__ __launch_bounds__(kSubThreads) void select_copy_kernel(const int64_t 
   }
 }
 
-#define SPL_FOR_GROUP(group, LAUNCH) \
-  switch (group) {                   \
-    case 1: LAUNCH(1); break;        \
-    case 2: LAUNCH(2); break;        \
-    case 4: LAUNCH(4); break;        \
-    case 8: LAUNCH(8); break;        \
-    case 16: LAUNCH(16); break;      \
-    case 32: LAUNCH(32); break;      \
-    default: LAUNCH(64); break;      \
-  }
-
-// C's pointers are scanned: read nnz back (the one 8-byte read-back) and make room for indices and values
-void allocate_entries(Matrix *C, hipStream_t s) {
-  int64_t nnz = 0;
-  SPL_HIP(hipMemcpyAsync(&nnz, C->rowptr64.get() + C->nrows_local, sizeof(int64_t), hipMemcpyDeviceToHost, s));
-  SPL_HIP(hipStreamSynchronize(s));
-  C->nnz = nnz;
-  C->colidx.alloc((size_t)nnz);
-  C->val.alloc((size_t)nnz * (size_t)C->vw);
-}
-
-void empty_result(Matrix *C, hipStream_t s) {
-  C->nnz = 0;
-  C->rowptr64.alloc((size_t)C->nrows_local + 1);
-  C->colidx.alloc(0);
-  C->val.alloc(0);
-  SPL_HIP(hipMemsetAsync(C->rowptr64.get(), 0, ((size_t)C->nrows_local + 1) * sizeof(int64_t), s));
-}
-
 }  // namespace
 
 // C = A[r0 : r0 + nr, c0 : c0 + nc] on the row image of a whole handle; the caller checked the window against A's
@@ -275,7 +209,7 @@ void submatrix_handle(const Matrix *A, int64_t r0, int64_t c0, Matrix *C, hipStr
   C->rowptr64.alloc((size_t)nr + 1);
   if (c0 == 0 && nc == A->ncols) {
     // whole rows: their entries lie one behind the other in A and keep their column indices
-    hipLaunchKernelGGL(shift_pointers_kernel, dim3(grid_flat(nr + 1)), dim3(kSubThreads), 0, s, A->rowptr64.get(), r0, nr,
+    hipLaunchKernelGGL(shift_pointers_kernel, dim3(grid_flat(nr + 1)), dim3(kRowThreads), 0, s, A->rowptr64.get(), r0, nr,
                        C->rowptr64.get());
     SPL_HIP(hipGetLastError());
     int64_t start = 0;
@@ -295,27 +229,20 @@ void submatrix_handle(const Matrix *A, int64_t r0, int64_t c0, Matrix *C, hipStr
   const int c1 = (int)(c0 + nc);  // <= ncols < 2^31
   // lanes per row: the length pass cuts the SOURCE rows into pieces, the copy pass walks the kept entries
   const int g1 = group_for((double)A->nnz / (double)A->nrows_local);
-#define SPL_WLEN(G)                                                                                                  \
-  hipLaunchKernelGGL((window_len_kernel<G>), dim3(grid_rows(nr, G)), dim3(kSubThreads), 0, s, A->rowptr64.get(),      \
-                     A->colidx.get(), r0, nr, (int)c0, c1, len.get(), first.get())
-  SPL_FOR_GROUP(g1, SPL_WLEN)
-#undef SPL_WLEN
+  for_group_and_width(g1, C->vw, [&](auto g, auto) {
+    hipLaunchKernelGGL((window_len_kernel<decltype(g)::value>), dim3(grid_rows(nr, g)), dim3(kRowThreads), 0, s,
+                       A->rowptr64.get(), A->colidx.get(), r0, nr, (int)c0, c1, len.get(), first.get());
+  });
   SPL_HIP(hipGetLastError());
   exclusive_scan_i32_to_i64(len.get(), C->rowptr64.get(), nr, s);
   allocate_entries(C, s);
   if (C->nnz > 0) {
     const int g2 = group_for((double)C->nnz / (double)nr);
-#define SPL_WCOPY(G)                                                                                                 \
-  do {                                                                                                               \
-    if (C->vw == 1)                                                                                                  \
-      hipLaunchKernelGGL((window_copy_kernel<G, 1>), dim3(grid_rows(nr, G)), dim3(kSubThreads), 0, s, A->colidx.get(), \
-                         A->val.get(), first.get(), nr, (int)c0, C->rowptr64.get(), C->colidx.get(), C->val.get());  \
-    else                                                                                                             \
-      hipLaunchKernelGGL((window_copy_kernel<G, 2>), dim3(grid_rows(nr, G)), dim3(kSubThreads), 0, s, A->colidx.get(), \
-                         A->val.get(), first.get(), nr, (int)c0, C->rowptr64.get(), C->colidx.get(), C->val.get());  \
-  } while (0)
-    SPL_FOR_GROUP(g2, SPL_WCOPY)
-#undef SPL_WCOPY
+    for_group_and_width(g2, C->vw, [&](auto g, auto vw) {
+      hipLaunchKernelGGL((window_copy_kernel<decltype(g)::value, decltype(vw)::value>), dim3(grid_rows(nr, g)),
+                         dim3(kRowThreads), 0, s, A->colidx.get(), A->val.get(), first.get(), nr, (int)c0,
+                         C->rowptr64.get(), C->colidx.get(), C->val.get());
+    });
     SPL_HIP(hipGetLastError());
   }
   SPL_HIP(hipStreamSynchronize(s));  // `len` and `first` are released on return
@@ -341,20 +268,20 @@ int select_handle(const Matrix *A, int index_width, const void *d_I, const void 
     if (d_I && nI > 0) {
       rows.alloc((size_t)nI);
       if (index_width == 8)
-        hipLaunchKernelGGL((check_rows_kernel<int64_t>), dim3(grid_flat(nI)), dim3(kSubThreads), 0, s,
+        hipLaunchKernelGGL((check_rows_kernel<int64_t>), dim3(grid_flat(nI)), dim3(kRowThreads), 0, s,
                            static_cast<const int64_t *>(d_I), nI, A->nrows_local, rows.get(), flags.get());
       else
-        hipLaunchKernelGGL((check_rows_kernel<int>), dim3(grid_flat(nI)), dim3(kSubThreads), 0, s,
+        hipLaunchKernelGGL((check_rows_kernel<int>), dim3(grid_flat(nI)), dim3(kRowThreads), 0, s,
                            static_cast<const int *>(d_I), nI, A->nrows_local, rows.get(), flags.get());
     }
     if (d_J && nJ > 0) {
       map.alloc((size_t)A->ncols);
       SPL_HIP(hipMemsetAsync(map.get(), 0xFF, (size_t)A->ncols * sizeof(int), s));  // -1 everywhere
       if (index_width == 8)
-        hipLaunchKernelGGL((scatter_cols_kernel<int64_t>), dim3(grid_flat(nJ)), dim3(kSubThreads), 0, s,
+        hipLaunchKernelGGL((scatter_cols_kernel<int64_t>), dim3(grid_flat(nJ)), dim3(kRowThreads), 0, s,
                            static_cast<const int64_t *>(d_J), nJ, A->ncols, map.get(), flags.get());
       else
-        hipLaunchKernelGGL((scatter_cols_kernel<int>), dim3(grid_flat(nJ)), dim3(kSubThreads), 0, s,
+        hipLaunchKernelGGL((scatter_cols_kernel<int>), dim3(grid_flat(nJ)), dim3(kRowThreads), 0, s,
                            static_cast<const int *>(d_J), nJ, A->ncols, map.get(), flags.get());
     }
     SPL_HIP(hipGetLastError());
@@ -377,28 +304,19 @@ int select_handle(const Matrix *A, int index_width, const void *d_I, const void 
   C->rowptr64.alloc((size_t)nI + 1);
   // lanes per row, both passes walk the source rows: their mean length (that of A; I may name any of them)
   const int g = group_for((double)A->nnz / (double)A->nrows_local);
-#define SPL_SLEN(G)                                                                                                  \
-  hipLaunchKernelGGL((select_len_kernel<G>), dim3(grid_rows(nI, G)), dim3(kSubThreads), 0, s, A->rowptr64.get(),      \
-                     A->colidx.get(), d_rows, d_map, nI, len.get())
-  SPL_FOR_GROUP(g, SPL_SLEN)
-#undef SPL_SLEN
+  for_group_and_width(g, C->vw, [&](auto gc, auto) {
+    hipLaunchKernelGGL((select_len_kernel<decltype(gc)::value>), dim3(grid_rows(nI, gc)), dim3(kRowThreads), 0, s,
+                       A->rowptr64.get(), A->colidx.get(), d_rows, d_map, nI, len.get());
+  });
   SPL_HIP(hipGetLastError());
   exclusive_scan_i32_to_i64(len.get(), C->rowptr64.get(), nI, s);
   allocate_entries(C, s);
   if (C->nnz > 0) {
-#define SPL_SCOPY(G)                                                                                                 \
-  do {                                                                                                               \
-    if (C->vw == 1)                                                                                                  \
-      hipLaunchKernelGGL((select_copy_kernel<G, 1>), dim3(grid_rows(nI, G)), dim3(kSubThreads), 0, s,                \
-                         A->rowptr64.get(), A->colidx.get(), A->val.get(), d_rows, d_map, nI, C->rowptr64.get(),     \
-                         C->colidx.get(), C->val.get());                                                             \
-    else                                                                                                             \
-      hipLaunchKernelGGL((select_copy_kernel<G, 2>), dim3(grid_rows(nI, G)), dim3(kSubThreads), 0, s,                \
-                         A->rowptr64.get(), A->colidx.get(), A->val.get(), d_rows, d_map, nI, C->rowptr64.get(),     \
-                         C->colidx.get(), C->val.get());                                                             \
-  } while (0)
-    SPL_FOR_GROUP(g, SPL_SCOPY)
-#undef SPL_SCOPY
+    for_group_and_width(g, C->vw, [&](auto gc, auto vw) {
+      hipLaunchKernelGGL((select_copy_kernel<decltype(gc)::value, decltype(vw)::value>), dim3(grid_rows(nI, gc)),
+                         dim3(kRowThreads), 0, s, A->rowptr64.get(), A->colidx.get(), A->val.get(), d_rows, d_map, nI,
+                         C->rowptr64.get(), C->colidx.get(), C->val.get());
+    });
     SPL_HIP(hipGetLastError());
   }
   SPL_HIP(hipStreamSynchronize(s));  // `rows`, `map` and `len` are released on return

@@ -1043,8 +1043,8 @@ def takeDiag(mat):
 
 
 def _assemble(blocks, row_off, col_off, nrows, ncols):
-    """place CSC blocks at (row_off, col_off) of an nrows x ncols result on the device (spl_assemble_blocks,
-    csrc/assemble.hip): the one kernel pair behind hcat / vcat / fromBlocks / fromBlocksDiag"""
+    """place CSC blocks at (row_off, col_off) of an nrows x ncols result on the device (spl_assemble_blocks, the
+    kernels of csrc/assemble_handles.hip): the one call behind hcat / vcat / fromBlocks / fromBlocksDiag"""
     _ffi.require_gpu()
     k = len(blocks)
     cplx = any(m.is_complex for m in blocks)
@@ -1155,8 +1155,8 @@ def _diag_grid(blocks):
 
 def fromBlocks(blocks):
     """[[Maybe Matrix]] -> Matrix, None = zero block (Sparse.hs:563-587): vcat . map hcat . adjustDims in one
-    device assembly — block (r, c) sits at (sum of the heights above, sum of the widths to the left), listed
-    row-major so that blocks sharing columns come by ascending row offset."""
+    device assembly — block (r, c) sits at (sum of the heights above, sum of the widths to the left); the call
+    stacks blocks that share columns by ascending row offset whatever order they are listed in."""
     placed, ro, co, nrows, ncols = _block_grid(blocks, lambda m: m.nrows, lambda m: m.ncols)
     if not placed:  # every block a zero block cannot happen: heights would be underspecified
         return zeros(nrows, ncols)
