@@ -174,7 +174,8 @@ int spl_matrix_create(int nrows, int ncols, const int *Ap, const int *Ai, const 
  * compute  y <- a * x + y  per stored entry in ascending column order with Data.Complex's arithmetic, every
  * real operation separately rounded (csrc/spmv_z.hip: 20 bytes per stored entry instead of the 48 of the real
  * 2n x 2n embedding).  spl_matrix_spmv_many_dev is the fused product of such a handle with k vectors at once.
- * spl_matrix_lin, _transpose, _ctrans, _hermitian, _spgemm, _kronecker, _assemble_blocks, _submatrix, _select, _take_diag_dev, _export_csr
+ * spl_matrix_lin, _transpose, _ctrans, _hermitian, _spgemm, _kronecker, _assemble_blocks, _submatrix, _select, _take_diag_dev, _export_csr,
+ * the entry-wise layer (_map, _scale_rows_cols, _filter, _band, _reduce_dev, _norm)
  * and the LU from handles take complex handles as well, and spl_matrix_diag_dev makes one.  Still for real handles only: spl_matrix_export_csc, spl_matrix_export_csr_rows, spl_matrix_spmm_dev and
  * the SpMV images (spl_matrix_build_blocked / _build_panel, the sliced-ELL image; spl_matrix_optimize and
  * spl_matrix_set_variant(H, 0) are accepted and do nothing).  The CSC fields of a complex handle are
@@ -341,6 +342,106 @@ int spl_matrix_diag_dev(int64_t n, const double *d_values, int value_width, void
 int spl_matrix_submatrix(void *H, int64_t r0, int64_t c0, int64_t nr, int64_t nc, void **HC);
 int spl_matrix_select(void *H, int64_t nI, const void *d_I, int64_t nJ, const void *d_J, int index_width, void **HC,
                       int64_t *bad);
+/* ---- the entry-wise layer on handles: maps, scaling, filters and reductions (csrc/entrywise.hip) --------------------
+ * `cmap` / `scale` (Sparse.hs:119-125), the Num instance's negate / abs / signum (Sparse.hs:110-112), conj, the parts
+ * and `mag` of Data.Complex.Enhanced, and what a user of handles needs around them: dropping stored zeros, bands and
+ * triangles, diag(r) A diag(c), and the abs-sums and norms that produce such scalings.  Common to the six calls:
+ * operands are real or complex handles, borrowed and not modified; results that are handles are ordinary handles on the
+ * operand's device — 64-bit row pointers always, int32 ones when nnz fits, no SpMV image; every argument check comes
+ * before the device is touched (without a GPU the calls answer the same up to there, and SPL_ERROR_device after); the
+ * work of the calls that return a handle or a scalar runs on the default stream and they synchronise.  Like lin the
+ * calls rely on strictly ascending indices.  A row block is accepted by spl_matrix_map, _scale_rows_cols, _filter,
+ * _band and the row-wise reductions, and the result is the same block (same row0 and nrows_global); the column-wise
+ * reductions and the norms refuse one with SPL_ERROR_argument_missing.  Every floating-point operation named below is
+ * rounded once (no FMA).  Nothing is handed out by atomics and no floating-point atomic add exists: two calls on the
+ * same handle give the same bits.
+ *
+ * magnitude (x :+ y) is GHC's, not hypot:  scaleFloat k (sqrt (sqr (scaleFloat (-k) x) + sqr (scaleFloat (-k) y))),
+ *   k = max (exponent x) (exponent y), `exponent` being frexp's exponent and exponent 0 = 0: two ldexp, two products,
+ *   one sum, one correctly rounded sqrt, one ldexp.  Pinned bit for bit for finite parts, subnormals and 1e300
+ *   included.  With a part that is not finite the result is inf if either part is infinite, else NaN: the reference's
+ *   own answer there is an artefact of `decodeFloat` on inf / NaN (a large finite number) and is NOT reproduced.
+ *
+ * spl_matrix_map: the pattern is copied and one streaming pass runs over the values; stored zeros stay (`cmap` never
+ *   prunes).  `scalar` (re, im) is read by SPL_MAP_scale only and may be NULL otherwise.
+ *   Real handles, Haskell's results at Double bit for bit: negate flips the sign bit (zeros and NaNs included, payloads
+ *   kept); abs clears it; signum is 1 for x > 0, -1 for x < 0, else x itself (+-0 and NaN pass through); conj and real
+ *   copy; imag gives the same pattern with +0.0 values; scale gives v * s.
+ *   Complex handles, Haskell's at Complex Double: negate negates both parts; conj is (re, -im), the sign bit flipped as
+ *   spl_matrix_ctrans does; real and imag return REAL handles; scale is (a :+ b) * (c :+ d) = (ac - bd) :+ (ad + bc)
+ *   with v = a :+ b; abs is magnitude z :+ 0 (a complex handle: `omap abs` keeps the type); signum is 0 :+ 0 when z == 0
+ *   (IEEE ==), else x / r :+ y / r with r = magnitude z.
+ *   Checks, in order:
+ *   1. H is no matrix handle: SPL_ERROR_invalid_handle
+ *   2. HC == NULL: SPL_ERROR_argument_missing; otherwise *HC = NULL first
+ *   3. an unknown op: SPL_ERROR_argument_missing
+ *   4. SPL_MAP_scale with scalar == NULL: SPL_ERROR_argument_missing
+ *   5. SPL_MAP_scale on a real handle with scalar[1] != 0: SPL_ERROR_argument_missing (the rule of spl_matrix_lin)
+ * spl_matrix_scale_rows_cols: C[i,j] = (r[i] * a[i,j]) * c[j], in that order, each product rounded once; on complex
+ *   handles r and c are packed (re, im) pairs and the products Data.Complex's, (r * a) then (that * c).  d_r and d_c are
+ *   DEVICE memory on the handle's device, nrows_local and ncols entries.  Either may be NULL, meaning ones, and then
+ *   that product is not formed at all (bits pass through); both NULL is a copy.  Checks, in order:
+ *   1. H is no matrix handle: SPL_ERROR_invalid_handle
+ *   2. HC == NULL: SPL_ERROR_argument_missing; otherwise *HC = NULL first
+ *   3. a vector not aligned to 8 bytes: SPL_ERROR_argument_missing
+ * spl_matrix_filter: a result with fewer entries, the order inside every row kept.  SPL_KEEP_nonzero drops an entry iff
+ *   it == 0 (+-0.0 go, NaN stays; a complex entry goes iff both parts == 0); `param` is not read.  SPL_KEEP_abs_above
+ *   drops an entry iff |a| <= param[0] (NaN entries stay; complex |a| is the magnitude above, which is 0 for a pair
+ *   like 0 :+ 5e-324 — exponent 0 = 0 is the larger exponent and the unscaled square vanishes — so a tolerance of 0
+ *   drops a little more than SPL_KEEP_nonzero on complex handles, and the same on real ones).  Two passes: kept entries
+ *   counted per row, a scan, a stable compacting write (positions from a ballot); nnz is the one 8-byte read-back.
+ *   Checks, in order:
+ *   1. H is no matrix handle: SPL_ERROR_invalid_handle
+ *   2. HC == NULL: SPL_ERROR_argument_missing; otherwise *HC = NULL first
+ *   3. an unknown keep: SPL_ERROR_argument_missing
+ *   4. SPL_KEEP_abs_above with param == NULL, or a tolerance that is negative or NaN: SPL_ERROR_argument_missing
+ * spl_matrix_band: keeps the entries with lo <= j - i <= hi, i the GLOBAL row (row0 + local row); indices are not
+ *   shifted.  INT64_MIN / INT64_MAX open an end; lo > hi gives `zeros` of the operand's shape.  tril(k) is
+ *   (INT64_MIN, k), triu(k) is (k, INT64_MAX).  The kept entries are one run per row, found by bisection.  Checks:
+ *   1. H is no matrix handle: SPL_ERROR_invalid_handle
+ *   2. HC == NULL: SPL_ERROR_argument_missing; otherwise *HC = NULL first
+ * spl_matrix_reduce_dev: d_out (DEVICE memory, real doubles for both value kinds) receives per row (axis 1,
+ *   nrows_local doubles) or per column (axis 0, ncols doubles) the sum (SPL_REDUCE_abs_sum) or the largest
+ *   (SPL_REDUCE_abs_max) of |a| over the stored entries; an empty slice gives +0.0; a NaN in a slice comes out as a
+ *   NaN.  The work is enqueued on `stream` and the call does not synchronise, as spl_matrix_take_diag_dev (the column
+ *   sums hold temporaries and do synchronise).  A row's sum is formed by its group of lanes in a fixed tree; a column's
+ *   sum is the row sum of the order-preserving transpose of the moduli.  For every slice
+ *   |got - exact| <= (len + 4) 2^-53 sum|a|.  Checks, in order:
+ *   1. H is no matrix handle: SPL_ERROR_invalid_handle
+ *   2. an unknown what or axis: SPL_ERROR_argument_missing
+ *   3. axis 0 on a row block: SPL_ERROR_argument_missing
+ *   4. d_out == NULL (or not aligned to 8 bytes) with a non-empty axis: SPL_ERROR_argument_missing
+ *   5. axis 0 with nnz >= 2^31: SPL_ERROR_index_overflow
+ * spl_matrix_norm: *result = the 1-norm (largest column abs-sum), the infinity norm (largest row abs-sum), the
+ *   Frobenius norm or the max norm (largest |a|) of a whole matrix; no entries: 0.  The Frobenius norm scales by the max
+ *   norm first (m sqrt(sum (|a| / m)^2)), so 1e200 or 1e-200 entries give the representable answer; its relative error
+ *   is at most (nnz + 4) 2^-53.  Synchronises.  Checks, in order:
+ *   1. H is no matrix handle: SPL_ERROR_invalid_handle
+ *   2. result == NULL: SPL_ERROR_argument_missing
+ *   3. an unknown which: SPL_ERROR_argument_missing
+ *   4. a row block: SPL_ERROR_argument_missing
+ *   5. SPL_NORM_one with nnz >= 2^31: SPL_ERROR_index_overflow */
+#define SPL_MAP_negate 0
+#define SPL_MAP_abs 1
+#define SPL_MAP_signum 2
+#define SPL_MAP_conj 3
+#define SPL_MAP_real 4
+#define SPL_MAP_imag 5
+#define SPL_MAP_scale 6
+#define SPL_KEEP_nonzero 0
+#define SPL_KEEP_abs_above 1
+#define SPL_REDUCE_abs_sum 0
+#define SPL_REDUCE_abs_max 1
+#define SPL_NORM_one 0
+#define SPL_NORM_inf 1
+#define SPL_NORM_fro 2
+#define SPL_NORM_max 3
+int spl_matrix_map(void *H, int op, const double scalar[2], void **HC);
+int spl_matrix_scale_rows_cols(void *H, const double *d_r, const double *d_c, void **HC);
+int spl_matrix_filter(void *H, int keep, const double param[1], void **HC);
+int spl_matrix_band(void *H, int64_t lo, int64_t hi, void **HC);
+int spl_matrix_reduce_dev(void *H, int what, int axis, double *d_out, void *stream);
+int spl_matrix_norm(void *H, int which, double *result);
 /* transpose the block on the device (Sparse.hs:301-329) and copy out its
  * column-major image: colptr[ncols+1], rowidx[nnz_local] (LOCAL row ids, ascending
  * inside a column), val[nnz_local] — i.e. the reference's own CSC Matrix fields */

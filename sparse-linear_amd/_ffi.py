@@ -29,6 +29,12 @@ SPL_ERROR_index_overflow = -22
 SPL_ERROR_device = -30
 SPL_ERROR_internal = -911
 
+# the entry-wise layer on handles (spl_matrix_map, _filter, _reduce_dev, _norm)
+SPL_MAP_negate, SPL_MAP_abs, SPL_MAP_signum, SPL_MAP_conj, SPL_MAP_real, SPL_MAP_imag, SPL_MAP_scale = range(7)
+SPL_KEEP_nonzero, SPL_KEEP_abs_above = 0, 1
+SPL_REDUCE_abs_sum, SPL_REDUCE_abs_max = 0, 1
+SPL_NORM_one, SPL_NORM_inf, SPL_NORM_fro, SPL_NORM_max = range(4)
+
 
 class BackendUnavailable(RuntimeError):
     """The HIP shared library is not built / not loadable."""
@@ -124,6 +130,12 @@ def _declare(L):
         "spl_matrix_diag_dev": [i64, C.c_void_p, i, c_void_pp],
         "spl_matrix_submatrix": [C.c_void_p, i64, i64, i64, i64, c_void_pp],
         "spl_matrix_select": [C.c_void_p, i64, C.c_void_p, i64, C.c_void_p, i, c_void_pp, c_i64_p],
+        "spl_matrix_map": [C.c_void_p, i, c_dbl_p, c_void_pp],
+        "spl_matrix_scale_rows_cols": [C.c_void_p, C.c_void_p, C.c_void_p, c_void_pp],
+        "spl_matrix_filter": [C.c_void_p, i, c_dbl_p, c_void_pp],
+        "spl_matrix_band": [C.c_void_p, i64, i64, c_void_pp],
+        "spl_matrix_reduce_dev": [C.c_void_p, i, i, C.c_void_p, C.c_void_p],
+        "spl_matrix_norm": [C.c_void_p, i, c_dbl_p],
         "spl_matrix_info": [C.c_void_p, c_i64_p],
         "spl_matrix_export_csr": [C.c_void_p, c_i64_p, c_int_p, c_dbl_p],
         "spl_matrix_export_csc": [C.c_void_p, c_i64_p, c_int_p, c_dbl_p],

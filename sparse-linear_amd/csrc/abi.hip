@@ -958,6 +958,114 @@ int spl_matrix_select(void *H, int64_t nI, const void *d_I, int64_t nJ, const vo
   });
 }
 
+// ---- the entry-wise layer on handles (csrc/entrywise.hip) ------------------------------------------------------------
+// `cmap` with the functions the reference itself maps (Sparse.hs:110-125, Data.Complex.Enhanced): the pattern stays,
+// stored zeros included.  The result is the operand's block; SPL_MAP_real / _imag of a complex handle are real.
+int spl_matrix_map(void *H, int op, const double scalar[2], void **HC) {
+  Matrix *A = as_matrix(H);
+  if (!A) return SPL_ERROR_invalid_handle;
+  if (!HC) return SPL_ERROR_argument_missing;
+  *HC = nullptr;
+  if (op < SPL_MAP_negate || op > SPL_MAP_scale) return SPL_ERROR_argument_missing;
+  double sre = 1.0, sim = 0.0;
+  if (op == SPL_MAP_scale) {
+    if (!scalar) return SPL_ERROR_argument_missing;
+    sre = scalar[0];
+    sim = scalar[1];
+    if (A->vw == 1 && sim != 0.0) return SPL_ERROR_argument_missing;  // complex scalars: spl_matrix_to_complex first
+  }
+  return guarded([&]() -> int {
+    DeviceGuard g(A->device);
+    hipStream_t s = nullptr;
+    const int vw = (op == SPL_MAP_real || op == SPL_MAP_imag) ? 1 : A->vw;
+    std::unique_ptr<Matrix> C = make_matrix(A->device, A->nrows_global, A->ncols, A->row0, A->nrows_local, vw);
+    map_handle(A, op, sre, sim, C.get(), s);
+    return publish(std::move(C), s, HC);
+  });
+}
+
+// diag(r) A diag(c) without the two SpGEMMs: (r[i] * a) * c[j], a vector that is NULL is not multiplied with
+int spl_matrix_scale_rows_cols(void *H, const double *d_r, const double *d_c, void **HC) {
+  Matrix *A = as_matrix(H);
+  if (!A) return SPL_ERROR_invalid_handle;
+  if (!HC) return SPL_ERROR_argument_missing;
+  *HC = nullptr;
+  if (!aligned_to(d_r, sizeof(double)) || !aligned_to(d_c, sizeof(double))) return SPL_ERROR_argument_missing;
+  return guarded([&]() -> int {
+    DeviceGuard g(A->device);
+    hipStream_t s = nullptr;
+    std::unique_ptr<Matrix> C = make_matrix(A->device, A->nrows_global, A->ncols, A->row0, A->nrows_local, A->vw);
+    scale_rows_cols_handle(A, d_r, d_c, C.get(), s);
+    return publish(std::move(C), s, HC);
+  });
+}
+
+// the reference never prunes (explicit zeros are first-class); this is the pass a user asks for
+int spl_matrix_filter(void *H, int keep, const double param[1], void **HC) {
+  Matrix *A = as_matrix(H);
+  if (!A) return SPL_ERROR_invalid_handle;
+  if (!HC) return SPL_ERROR_argument_missing;
+  *HC = nullptr;
+  if (keep != SPL_KEEP_nonzero && keep != SPL_KEEP_abs_above) return SPL_ERROR_argument_missing;
+  double tol = 0.0;
+  if (keep == SPL_KEEP_abs_above) {
+    if (!param || !(param[0] >= 0.0)) return SPL_ERROR_argument_missing;  // negative, or NaN
+    tol = param[0];
+  }
+  return guarded([&]() -> int {
+    DeviceGuard g(A->device);
+    hipStream_t s = nullptr;
+    std::unique_ptr<Matrix> C = make_matrix(A->device, A->nrows_global, A->ncols, A->row0, A->nrows_local, A->vw);
+    filter_handle(A, keep, tol, C.get(), s);
+    return publish(std::move(C), s, HC);
+  });
+}
+
+// lo <= j - i <= hi with i the global row: tril, triu and the pieces of A = L + D + U
+int spl_matrix_band(void *H, int64_t lo, int64_t hi, void **HC) {
+  Matrix *A = as_matrix(H);
+  if (!A) return SPL_ERROR_invalid_handle;
+  if (!HC) return SPL_ERROR_argument_missing;
+  *HC = nullptr;
+  return guarded([&]() -> int {
+    DeviceGuard g(A->device);
+    hipStream_t s = nullptr;
+    std::unique_ptr<Matrix> C = make_matrix(A->device, A->nrows_global, A->ncols, A->row0, A->nrows_local, A->vw);
+    band_handle(A, lo, hi, C.get(), s);
+    return publish(std::move(C), s, HC);
+  });
+}
+
+int spl_matrix_reduce_dev(void *H, int what, int axis, double *d_out, void *stream) {
+  Matrix *A = as_matrix(H);
+  if (!A) return SPL_ERROR_invalid_handle;
+  if ((what != SPL_REDUCE_abs_sum && what != SPL_REDUCE_abs_max) || (axis != 0 && axis != 1))
+    return SPL_ERROR_argument_missing;
+  if (axis == 0 && !whole(A)) return SPL_ERROR_argument_missing;
+  const int64_t n = axis == 1 ? A->nrows_local : A->ncols;
+  if (n > 0 && (!d_out || !aligned_to(d_out, sizeof(double)))) return SPL_ERROR_argument_missing;
+  if (axis == 0 && what == SPL_REDUCE_abs_sum && A->nnz > 0 && !A->rowptr.get()) return SPL_ERROR_index_overflow;
+  return guarded([&]() -> int {
+    DeviceGuard g(A->device);
+    reduce_handle(A, what, axis, d_out, as_stream(stream));
+    return SPL_OK;
+  });
+}
+
+int spl_matrix_norm(void *H, int which, double *result) {
+  Matrix *A = as_matrix(H);
+  if (!A) return SPL_ERROR_invalid_handle;
+  if (!result) return SPL_ERROR_argument_missing;
+  if (which < SPL_NORM_one || which > SPL_NORM_max) return SPL_ERROR_argument_missing;
+  if (!whole(A)) return SPL_ERROR_argument_missing;
+  if (which == SPL_NORM_one && A->nnz > 0 && !A->rowptr.get()) return SPL_ERROR_index_overflow;
+  return guarded([&]() -> int {
+    DeviceGuard g(A->device);
+    *result = norm_handle(A, which, nullptr);
+    return SPL_OK;
+  });
+}
+
 void spl_matrix_free(void **H) {
   if (!H || !*H) return;
   Matrix *m = as_matrix(*H);

@@ -283,6 +283,17 @@ void submatrix_handle(const Matrix *A, int64_t r0, int64_t c0, Matrix *C, hipStr
 int select_handle(const Matrix *A, int index_width, const void *d_I, const void *d_J, Matrix *C, bool *ascending,
                   int64_t *bad, hipStream_t s);
 
+// ---- entry-wise maps, scaling, filters and reductions on handles (entrywise.hip) -----------------------------
+// C's dimensions, block and value kind are set by the caller and the arguments are checked; the four that make a
+// handle fill rowptr64 / colidx / val / nnz and synchronise s.  A may be a row block.
+void map_handle(const Matrix *A, int op, double sre, double sim, Matrix *C, hipStream_t s);
+void scale_rows_cols_handle(const Matrix *A, const double *d_r, const double *d_c, Matrix *C, hipStream_t s);
+void filter_handle(const Matrix *A, int keep, double tol, Matrix *C, hipStream_t s);
+void band_handle(const Matrix *A, int64_t lo, int64_t hi, Matrix *C, hipStream_t s);  // lo > hi: `zeros`
+// enqueues on s; the column sums (axis 0, abs_sum) hold temporaries and synchronise s
+void reduce_handle(const Matrix *A, int what, int axis, double *d_out, hipStream_t s);
+double norm_handle(const Matrix *A, int which, hipStream_t s);  // synchronises s
+
 // ---- multifrontal LU without interchanges (multifrontal.hip, mf_symbolic.hpp) ------------------
 namespace mf {
 struct Tree;

@@ -1,5 +1,5 @@
 // row_groups.hpp — the launch frame of the kernels that give every result row a group of lanes (assemble_handles.hip,
-// submatrix.hip).  A group of G = 1, 2, 4 ... 64 lanes takes one result row, consecutive groups take consecutive rows,
+// submatrix.hip, entrywise.hip).  A group of G = 1, 2, 4 ... 64 lanes takes one result row, consecutive groups take consecutive rows,
 // and the host picks G from the mean row length; VW is the doubles per stored value (1 real, 2 packed complex).
 #pragma once
 
@@ -60,6 +60,33 @@ __device__ inline int group_sum(int v) {
   return v;
 }
 
+// entries of the ascending run j[a .. b) that are < x
+__device__ inline int count_less(const int *__restrict__ j, int64_t a, int64_t b, int x) {
+  int64_t lo = a, hi = b;  // j[a .. lo) < x <= j[hi .. b)
+  while (lo < hi) {
+    const int64_t mid = lo + ((hi - lo) >> 1);
+    if (j[mid] < x) lo = mid + 1; else hi = mid;
+  }
+  return (int)(lo - a);
+}
+
+// The run of the ascending row j[s .. s + n) whose indices lie in [c0, c1), between lower_bound(c0) and lower_bound(c1):
+// *len entries from position *first on.  The G lanes of the group cut the row into G pieces and bisect one each — "how
+// many entries are below x" adds up over the pieces — so a row of 300 entries costs each lane three probes.  Every lane
+// of the group must be here, and every lane receives the result.
+template <int G>
+__device__ inline void run_in_row(const int *__restrict__ j, int64_t s, int n, int lane, int c0, int c1, int *len,
+                                  int64_t *first) {
+  const int piece = (n + G - 1) / G;
+  const int a = min(lane * piece, n), b = min(a + piece, n);  // lane * piece <= 63 * ceil(n / 64) < 2^31
+  int below0 = count_less(j, s + a, s + b, c0);
+  int below1 = count_less(j, s + a, s + b, c1);
+  below0 = group_sum<G>(below0);
+  below1 = group_sum<G>(below1);
+  *len = below1 - below0;
+  *first = s + below0;
+}
+
 template <int VW>
 __device__ inline void store_value(double *__restrict__ x, int64_t o, double re, double im) {
   if (VW == 1) x[o] = re;
@@ -70,6 +97,27 @@ template <int VW>
 __device__ inline void move_value(const double *__restrict__ src, int64_t p, double *__restrict__ dst, int64_t o) {
   if (VW == 1) dst[o] = src[p];
   else *reinterpret_cast<double2 *>(dst + 2 * o) = *reinterpret_cast<const double2 *>(src + 2 * p);  // both 16-byte aligned
+}
+
+// The copy pass behind run_in_row: result row r is the run of Cp[r + 1] - Cp[r] entries that starts at source position
+// first[r] (no second search), its indices moved down by `shift` (a window's first column; 0: as they are)
+template <int G, int VW>
+__global__ __launch_bounds__(kRowThreads) void run_copy_kernel(const int *__restrict__ Aj, const double *__restrict__ Ax,
+                                                               const int64_t *__restrict__ first, int64_t nr, int shift,
+                                                               const int64_t *__restrict__ Cp, int *__restrict__ Cj,
+                                                               double *__restrict__ Cx) {
+  constexpr int kGroups = kRowThreads / G;
+  const int lane = threadIdx.x % G;
+  int64_t r = (int64_t)blockIdx.x * kGroups + threadIdx.x / G;
+  const int64_t stride = (int64_t)gridDim.x * kGroups;
+  for (; r < nr; r += stride) {
+    const int64_t o = Cp[r], p = first[r];
+    const int n = (int)(Cp[r + 1] - o);
+    for (int e = lane; e < n; e += G) {
+      Cj[o + e] = Aj[p + e] - shift;
+      move_value<VW>(Ax, p + e, Cx, o + e);
+    }
+  }
 }
 
 // ---- room for a result whose dimensions and value kind the caller set ------------------------------------------------

@@ -19,21 +19,10 @@ namespace spl {
 
 namespace {
 
-// entries of the ascending run j[a .. b) that are < x
-__device__ inline int count_less(const int *__restrict__ j, int64_t a, int64_t b, int x) {
-  int64_t lo = a, hi = b;  // j[a .. lo) < x <= j[hi .. b)
-  while (lo < hi) {
-    const int64_t mid = lo + ((hi - lo) >> 1);
-    if (j[mid] < x) lo = mid + 1; else hi = mid;
-  }
-  return (int)(lo - a);
-}
-
 // ---- window -------------------------------------------------------------------------------------------------------
 // Result row r is the entries of source row r0 + r whose column lies in [c0, c1): the run between lower_bound(c0) and
-// lower_bound(c1) of the row's ascending indices.  The G lanes of the group cut the row into G pieces and bisect one
-// each — "how many entries are below x" adds up over the pieces — so a row of 300 entries costs each lane three probes.
-// first[r] keeps where the run starts: the copy pass does not search again.
+// lower_bound(c1) of the row's ascending indices, found by the group's bisection (run_in_row of row_groups.hpp).
+// first[r] keeps where the run starts: the copy pass (run_copy_kernel there) does not search again.
 template <int G>
 __global__ __launch_bounds__(kRowThreads) void window_len_kernel(const int64_t *__restrict__ Ap,
                                                                  const int *__restrict__ Aj, int64_t r0, int64_t nr,
@@ -45,36 +34,12 @@ __global__ __launch_bounds__(kRowThreads) void window_len_kernel(const int64_t *
   const int64_t stride = (int64_t)gridDim.x * kGroups;
   for (; r < nr; r += stride) {
     const int64_t s = Ap[r0 + r];
-    const int n = (int)(Ap[r0 + r + 1] - s);
-    const int piece = (n + G - 1) / G;
-    const int a = min(lane * piece, n), b = min(a + piece, n);  // lane * piece <= 63 * ceil(n / 64) < 2^31
-    int below0 = count_less(Aj, s + a, s + b, c0);
-    int below1 = count_less(Aj, s + a, s + b, c1);
-    below0 = group_sum<G>(below0);  // every lane of the group is here: r is theirs in common
-    below1 = group_sum<G>(below1);
+    int n;
+    int64_t p;
+    run_in_row<G>(Aj, s, (int)(Ap[r0 + r + 1] - s), lane, c0, c1, &n, &p);  // every lane of the group is here
     if (lane == 0) {
-      len[r] = below1 - below0;
-      first[r] = s + below0;
-    }
-  }
-}
-
-template <int G, int VW>
-__global__ __launch_bounds__(kRowThreads) void window_copy_kernel(const int *__restrict__ Aj,
-                                                                  const double *__restrict__ Ax,
-                                                                  const int64_t *__restrict__ first, int64_t nr, int c0,
-                                                                  const int64_t *__restrict__ Cp, int *__restrict__ Cj,
-                                                                  double *__restrict__ Cx) {
-  constexpr int kGroups = kRowThreads / G;
-  const int lane = threadIdx.x % G;
-  int64_t r = (int64_t)blockIdx.x * kGroups + threadIdx.x / G;
-  const int64_t stride = (int64_t)gridDim.x * kGroups;
-  for (; r < nr; r += stride) {
-    const int64_t o = Cp[r], p = first[r];
-    const int n = (int)(Cp[r + 1] - o);
-    for (int e = lane; e < n; e += G) {
-      Cj[o + e] = Aj[p + e] - c0;
-      move_value<VW>(Ax, p + e, Cx, o + e);
+      len[r] = n;
+      first[r] = p;
     }
   }
 }
@@ -239,7 +204,7 @@ void submatrix_handle(const Matrix *A, int64_t r0, int64_t c0, Matrix *C, hipStr
   if (C->nnz > 0) {
     const int g2 = group_for((double)C->nnz / (double)nr);
     for_group_and_width(g2, C->vw, [&](auto g, auto vw) {
-      hipLaunchKernelGGL((window_copy_kernel<decltype(g)::value, decltype(vw)::value>), dim3(grid_rows(nr, g)),
+      hipLaunchKernelGGL((run_copy_kernel<decltype(g)::value, decltype(vw)::value>), dim3(grid_rows(nr, g)),
                          dim3(kRowThreads), 0, s, A->colidx.get(), A->val.get(), first.get(), nr, (int)c0,
                          C->rowptr64.get(), C->colidx.get(), C->val.get());
     });

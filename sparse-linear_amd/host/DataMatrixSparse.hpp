@@ -245,6 +245,64 @@ inline Matrix subMatrix(std::pair<Int, Int> origin, std::pair<Int, Int> shape, c
   return c;
 }
 
+// The entry-wise layer on device handles (include/sparse_linear_hip.h, csrc/entrywise.hip): thin wrappers that throw on
+// a negative status.  Handles are the C ABI's `void *`; a result belongs to the caller, who frees it with
+// spl_matrix_free.  Vectors and outputs named d_* are device memory on the handle's device.
+namespace Device {
+// cmap with one of the reference's own functions (SPL_MAP_*); `scalar` (re, im) is read by SPL_MAP_scale only
+inline void *map(void *h, int op, const double *scalar = nullptr) {
+  void *c = nullptr;
+  detail::check("map", spl_matrix_map(h, op, scalar, &c));
+  return c;
+}
+inline void *negate(void *h) { return map(h, SPL_MAP_negate); }
+inline void *abs(void *h) { return map(h, SPL_MAP_abs); }
+inline void *signum(void *h) { return map(h, SPL_MAP_signum); }
+inline void *conj(void *h) { return map(h, SPL_MAP_conj); }
+inline void *real(void *h) { return map(h, SPL_MAP_real); }
+inline void *imag(void *h) { return map(h, SPL_MAP_imag); }
+inline void *scale(double re, double im, void *h) {  // scale x m (Sparse.hs:123-125)
+  const double s[2] = {re, im};
+  return map(h, SPL_MAP_scale, s);
+}
+// diag(r) A diag(c); nullptr = ones, not multiplied with
+inline void *scaleRowsCols(void *h, const double *d_r, const double *d_c) {
+  void *c = nullptr;
+  detail::check("scaleRowsCols", spl_matrix_scale_rows_cols(h, d_r, d_c, &c));
+  return c;
+}
+inline void *dropZeros(void *h) {
+  void *c = nullptr;
+  detail::check("dropZeros", spl_matrix_filter(h, SPL_KEEP_nonzero, nullptr, &c));
+  return c;
+}
+inline void *dropSmall(void *h, double tol) {
+  void *c = nullptr;
+  detail::check("dropSmall", spl_matrix_filter(h, SPL_KEEP_abs_above, &tol, &c));
+  return c;
+}
+// lo <= j - i <= hi; INT64_MIN / INT64_MAX open an end
+inline void *band(void *h, int64_t lo, int64_t hi) {
+  void *c = nullptr;
+  detail::check("band", spl_matrix_band(h, lo, hi, &c));
+  return c;
+}
+inline void *tril(void *h, int64_t k = 0) { return band(h, INT64_MIN, k); }
+inline void *triu(void *h, int64_t k = 0) { return band(h, k, INT64_MAX); }
+// per row (axis 1) or column (axis 0) into d_out; enqueued on `stream`
+inline void absSums(void *h, int axis, double *d_out, void *stream = nullptr) {
+  detail::check("absSums", spl_matrix_reduce_dev(h, SPL_REDUCE_abs_sum, axis, d_out, stream));
+}
+inline void absMax(void *h, int axis, double *d_out, void *stream = nullptr) {
+  detail::check("absMax", spl_matrix_reduce_dev(h, SPL_REDUCE_abs_max, axis, d_out, stream));
+}
+inline double norm(void *h, int which) {  // SPL_NORM_one, _inf, _fro, _max
+  double r = 0.0;
+  detail::check("norm", spl_matrix_norm(h, which, &r));
+  return r;
+}
+}  // namespace Device
+
 // hcat / vcat / fromBlocks (Sparse.hs:504-587): one device assembly (spl_assemble_blocks); nullptr = Nothing
 namespace detail {
 inline Matrix assemble(const std::vector<const Matrix *> &blocks, const std::vector<int> &row_off,

@@ -22,6 +22,9 @@ lie in device memory, a sparse torch tensor on the GPU among them, enter and lea
 (``from_csr_dev``, ``from_csc_dev``, ``compress_dev``, ``export_csr_dev``, ``export_csc_dev``, ``from_torch``,
 ``to_torch``).  A handle is taken apart the same way: ``submatrix`` / ``A[a:b, c:d]`` for a window, ``select`` /
 ``A[rows, cols]`` for rows and columns by index (a permutation ``P A Q`` among them); ``subMatrix`` is the host route.
+Its values are worked on entry by entry the same way: ``map`` / ``negate`` / ``abs`` / ``signum`` / ``conj`` / ``real`` /
+``imag`` / ``scale``, ``scale_rows_cols``, ``drop_zeros`` / ``drop_small``, ``band`` / ``tril`` / ``triu``, ``abs_sums`` /
+``abs_max`` / ``norm``; the host ``cmap`` and ``scale`` below stay numpy.
 """
 import ctypes as C
 import weakref
@@ -454,6 +457,151 @@ class DeviceMatrix(object):
             as_ix = lambda v: np.asarray(v, dtype=I64) if isinstance(v, (list, tuple, np.ndarray)) else v  # noqa: E731
             return self.select(as_ix(a), as_ix(b))
         raise TypeError("DeviceMatrix[...] takes two slices with step 1, or two 1-D index arrays")
+
+    # ---- the entry-wise layer (csrc/entrywise.hip): maps, scaling, filters, reductions; row blocks are accepted ----
+    MAP_OPS = {"negate": _ffi.SPL_MAP_negate, "abs": _ffi.SPL_MAP_abs, "signum": _ffi.SPL_MAP_signum,
+               "conj": _ffi.SPL_MAP_conj, "real": _ffi.SPL_MAP_real, "imag": _ffi.SPL_MAP_imag,
+               "scale": _ffi.SPL_MAP_scale}
+
+    def map(self, op, scalar=None):
+        """`cmap` with one of the reference's own functions on the device (spl_matrix_map): op is 'negate', 'abs',
+        'signum', 'conj', 'real', 'imag' or 'scale' (with `scalar`).  The pattern stays, stored zeros included; on a
+        complex handle 'real' and 'imag' give real handles and 'abs' is `magnitude z :+ 0`"""
+        if op not in self.MAP_OPS:
+            raise ValueError("map: op %r; one of %s is needed" % (op, ", ".join(sorted(self.MAP_OPS))))
+        s = None
+        if op == "scale":
+            if scalar is None:
+                raise ValueError("map: 'scale' needs a scalar")
+            s = (C.c_double * 2)(complex(scalar).real, complex(scalar).imag)
+        h = C.c_void_p()
+        check("spl_matrix_map", lib().spl_matrix_map(self.handle, self.MAP_OPS[op], s, C.byref(h)))
+        return DeviceMatrix(h.value)
+
+    def negate(self):
+        return self.map("negate")
+
+    def abs(self):
+        return self.map("abs")
+
+    def signum(self):
+        return self.map("signum")
+
+    def conj(self):
+        return self.map("conj")
+
+    def real(self):
+        return self.map("real")
+
+    def imag(self):
+        return self.map("imag")
+
+    def scale(self, x):
+        """`scale x` (Sparse.hs:123-125): every stored value times x; a scalar with an imaginary part needs a complex
+        handle (to_complex first, the rule of lin)"""
+        return self.map("scale", x)
+
+    def __neg__(self):
+        return self.map("negate")
+
+    def __abs__(self):
+        return self.map("abs")
+
+    def scale_rows_cols(self, r=None, c=None):
+        """diag(r) self diag(c) as a handle (spl_matrix_scale_rows_cols): C[i, j] = (r[i] * a[i, j]) * c[j].  r / c:
+        torch tensors on the handle's device, or anything torch.as_tensor takes; float64 on a real handle, float64 or
+        complex128 on a complex one; nrows_local and ncols entries; None = ones, and that product is not formed"""
+        import torch
+        inf = self.info()
+        dev = torch.device("cuda", inf["device"])
+        cplx = self.is_complex
+        want = torch.complex128 if cplx else torch.float64
+
+        def vector(a, n, what):
+            if a is None:
+                return None
+            if not isinstance(a, torch.Tensor):
+                a = torch.as_tensor(np.asarray(a))  # a list of Python floats is float64, as numpy reads it
+            if a.dtype not in ((torch.float64, torch.complex128) if cplx else (torch.float64,)):
+                raise TypeError("scale_rows_cols: %s of dtype %s; %s is needed" % (what, a.dtype, want))
+            if a.dim() != 1:
+                raise TypeError("scale_rows_cols: %s with %d dimensions; a vector is needed" % (what, a.dim()))
+            if int(a.shape[0]) != n:
+                raise ValueError("scale_rows_cols: %s has %d entries, %d are needed" % (what, int(a.shape[0]), n))
+            return a.to(device=dev, dtype=want).contiguous()
+
+        with torch.cuda.device(dev):
+            tr, tc = vector(r, inf["nrows_local"], "r"), vector(c, inf["ncols"], "c")
+            p_r = None if tr is None or tr.numel() == 0 else C.c_void_p(tr.data_ptr())
+            p_c = None if tc is None or tc.numel() == 0 else C.c_void_p(tc.data_ptr())
+            torch.cuda.current_stream().synchronize()  # the call runs on the default stream
+            h = C.c_void_p()
+            check("spl_matrix_scale_rows_cols", lib().spl_matrix_scale_rows_cols(self.handle, p_r, p_c, C.byref(h)))
+        return DeviceMatrix(h.value)
+
+    def drop_zeros(self):
+        """the handle without its stored zeros (spl_matrix_filter, SPL_KEEP_nonzero): +0.0 and -0.0 go, NaN stays, a
+        complex entry goes iff both parts are zero; the order inside the rows is kept"""
+        h = C.c_void_p()
+        check("spl_matrix_filter", lib().spl_matrix_filter(self.handle, _ffi.SPL_KEEP_nonzero, None, C.byref(h)))
+        return DeviceMatrix(h.value)
+
+    def drop_small(self, tol):
+        """the handle without the entries with |a| <= tol (SPL_KEEP_abs_above); NaN entries stay"""
+        t = (C.c_double * 1)(float(tol))
+        h = C.c_void_p()
+        check("spl_matrix_filter", lib().spl_matrix_filter(self.handle, _ffi.SPL_KEEP_abs_above, t, C.byref(h)))
+        return DeviceMatrix(h.value)
+
+    def band(self, lo=None, hi=None):
+        """the entries with lo <= j - i <= hi, i the global row (spl_matrix_band); None opens an end; lo > hi gives
+        `zeros` of the shape"""
+        i64 = np.iinfo(np.int64)
+        lo = i64.min if lo is None else min(max(int(lo), i64.min), i64.max)
+        hi = i64.max if hi is None else min(max(int(hi), i64.min), i64.max)
+        h = C.c_void_p()
+        check("spl_matrix_band", lib().spl_matrix_band(self.handle, lo, hi, C.byref(h)))
+        return DeviceMatrix(h.value)
+
+    def tril(self, k=0):
+        """the entries on and below the k-th diagonal: j - i <= k"""
+        return self.band(None, k)
+
+    def triu(self, k=0):
+        """the entries on and above the k-th diagonal: j - i >= k"""
+        return self.band(k, None)
+
+    def _reduce(self, what, axis):
+        import torch
+        if axis not in (0, 1):
+            raise ValueError("axis %r; 0 (per column) or 1 (per row) is needed" % (axis,))
+        inf = self.info()
+        n = inf["nrows_local"] if axis == 1 else inf["ncols"]
+        with torch.cuda.device(inf["device"]):
+            out = torch.empty(n, dtype=torch.float64, device="cuda")
+            check("spl_matrix_reduce_dev",
+                  lib().spl_matrix_reduce_dev(self.handle, what, axis, C.c_void_p(out.data_ptr() if n else 0),
+                                              C.c_void_p(torch.cuda.current_stream().cuda_stream)))
+        return out
+
+    def abs_sums(self, axis):
+        """sum of |a| over every row (axis 1) or column (axis 0) as a float64 torch tensor on the device, in a fixed
+        order: two calls give the same bits.  Enqueued on torch's current stream"""
+        return self._reduce(_ffi.SPL_REDUCE_abs_sum, axis)
+
+    def abs_max(self, axis):
+        """largest |a| of every row (axis 1) or column (axis 0), exact; an empty slice gives 0, a NaN is carried"""
+        return self._reduce(_ffi.SPL_REDUCE_abs_max, axis)
+
+    def norm(self, which="fro"):
+        """1 (largest column abs-sum), inf (largest row abs-sum), 'fro' or 'max', as a float; whole matrices"""
+        codes = {1: _ffi.SPL_NORM_one, "1": _ffi.SPL_NORM_one, float("inf"): _ffi.SPL_NORM_inf,
+                 "inf": _ffi.SPL_NORM_inf, "fro": _ffi.SPL_NORM_fro, "max": _ffi.SPL_NORM_max}
+        if which not in codes:
+            raise ValueError("norm: %r; one of 1, inf, 'fro', 'max' is needed" % (which,))
+        r = C.c_double(0.0)
+        check("spl_matrix_norm", lib().spl_matrix_norm(self.handle, codes[which], C.byref(r)))
+        return float(r.value)
 
     def take_diag_dev(self, out_ptr, stream=0):
         """out[c] = A[c, c] or 0, c < min(nrows, ncols) (Sparse.hs:640-650); out_ptr is a device pointer (int) to
