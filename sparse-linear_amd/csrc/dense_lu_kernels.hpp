@@ -7,6 +7,7 @@
 #include <algorithm>
 
 #include "common.hpp"
+#include "mf_levels.hpp"  // NB, SB: the tables of the multifrontal levels are built on them
 
 // dense-kernel work with no bit-parity contract (parity of the solve step is defined on the
 // solution): allow fused multiply-adds here although the library default is -ffp-contract=off
@@ -14,8 +15,6 @@
 
 namespace spl {
 namespace {
-
-constexpr int NB = 64;   // panel width
 
 // View of the matrix being factored.  Band storage: A(i,j) = AB[(ku + i) + j*(ldab-1)], doff = ku.
 // A dense column-major matrix with leading dimension ld is the same thing with doff = 0,
@@ -1561,7 +1560,6 @@ __device__ __forceinline__ void front_factor_by_workgroup_z(const Band &b, int n
 // and then updates its own 64 rows of `in` outside the super block.
 //   MODE 0: L z = c (unit lower, forward)     1: U x = z (backward)
 //   MODE 2: U^T z = c (lower, forward)        3: L^T x = z (unit upper, backward)
-constexpr int SB = 4;
 
 // Workgroups of SW = 16 wavefronts: these kernels are chains of short latency-bound phases, and the
 // wider workgroup shortens every phase (more loads in flight per row).

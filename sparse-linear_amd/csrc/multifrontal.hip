@@ -23,6 +23,7 @@
 // a speculation that every solve checks — umfpack.hip).
 #include <stdio.h>
 #include <chrono>
+#include <list>
 #include <map>
 #include <memory>
 #include <mutex>
@@ -30,7 +31,7 @@
 #include <vector>
 
 #include "dense_lu_kernels.hpp"
-#include "mf_symbolic.hpp"
+#include "mf_levels.hpp"
 
 namespace spl {
 
@@ -177,8 +178,6 @@ __device__ __forceinline__ int item_of_tile(const int64_t *__restrict__ prefix, 
   }
   return lo;
 }
-
-constexpr int kTileCols = 16;  // a workgroup moves 64 rows x 16 columns: 4 columns per thread
 
 // parent += Schur complement of the listed children.  Flat 1-D grid over the 64 x 16 tiles of all
 // children (prefix = tiles before each child): no workgroup is launched for nothing, whatever the
@@ -400,8 +399,6 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(Z ? 1 : 3, 
   else update_tile<true>(b, g, tx, ty, singular, next, next + NB * NB, dsm);
 }
 
-constexpr int kSmallFront = 128;   // fronts up to this size are factored by one workgroup each
-constexpr int kMidFront = 4096;    // ... up to this size in lockstep with the others of their level
 constexpr int kStreams = 8;        // larger fronts of a level are spread over this many streams
 
 // ---- solves ---------------------------------------------------------------------------------------
@@ -410,11 +407,6 @@ constexpr int kStreams = 8;        // larger fronts of a level are spread over t
 constexpr int kSolveThreads = 1024;  // one workgroup per front, 16 wavefronts for the coupling loops ...
 template <int NR>
 constexpr int solve_threads() { return (NR >= 16 || NR <= 2) ? 512 : kSolveThreads; }  // ... 8 with 16 columns (256 registers per thread) and with one or two (levels of thousands of small fronts: four workgroups per CU instead of two)
-constexpr int kSolveRowBlocks = 4;   // blocks of 64 rows per workgroup in the lockstep solve steps
-// fronts above this size are solved by many workgroups, in lockstep (round 5: 256 -> 128 — with the pivot blocks as chains of
-// matrix-vector products the many-workgroup path is the faster one for all but the leaves: 100^3 11.4 -> 10.3 ms per solve,
-// 64^3 4.9 -> 4.1, 40^3 2.45 -> 2.06, complex 100^3 18.6 -> 17.6; 64 gives the same)
-constexpr int kBigSolve = 128;
 
 // The panels of a front as the solves see them.  M is the triangular system a front contributes:
 // M(i, j) = F(i, j), or F(j, i) for the transposed systems, where F(i, j) lives in P for j < np and in
@@ -814,7 +806,6 @@ __global__ __launch_bounds__(solve_waves<NR>() * 64) void big_super_pipe_kernel(
 // read side by side), lane sums by recursive halving.
 template <int NR>
 constexpr int gemv_waves() { return NR >= 16 ? 8 : 16; }  // (the partial sums: GW x 64 x NR doubles of LDS)
-constexpr int kGemvChunk = 512;
 // FWD (round 4): the same product for the FORWARD pass of the untransposed systems, the boundary rows' share of it:
 // W[np + i][:] -= sum_t L21(i, t) Z[t][:], i < nb, with L21 = rows np .. fs of the pivot columns (in P) and Z the solved
 // pivots.  Rounds 1 - 3 did this inside the super-block steps (a step updated ALL rows below it): every workgroup of a
@@ -1013,61 +1004,28 @@ __global__ __launch_bounds__(256) void big_boundary_t_kernel(const int *__restri
 
 namespace mf {
 
-// Everything about the levels that depends on the tree and the size limits only — which fronts of a depth go to which
-// kernel, the prefix sums that turn a level into flat grids (factorisation and solves alike) —: built by the first
-// factorisation of a tree on a device and shared by all that follow (round 4; a refactorisation used to rebuild and
-// upload it: 1.8 ms of 134 at 100^3, 0.8 of 7 ms at 32^3, some 440 small copies).  Read-only once built.
+// The level tables of mf_levels.hpp — which fronts of a depth go to which kernel, the prefix sums that turn a level into
+// flat grids (factorisation and solves alike) — with their device copies: built by the first factorisation of a tree on a
+// device and shared by all that follow (round 4; a refactorisation used to rebuild and upload them: 1.8 ms of 134 at
+// 100^3, 0.8 of 7 ms at 32^3, some 440 small copies).  Read-only once built.
 struct LevelPlan {
-  int small_limit = 0, mid_limit = 0, mid_paired = 0;  // what it was built for (with big_solve below)
-  std::vector<DBuf<int>> level_lists;                // fronts of each depth
-  std::vector<DBuf<int>> small_lists;                // ... those factored by one workgroup each
-  std::vector<int> small_counts;
-  std::vector<DBuf<int>> solve_lists;                // ... those solved by one workgroup each
-  std::vector<int> solve_counts;
-  std::vector<DBuf<int>> child_lists[2];             // children (by slot) of the fronts of each depth
-  std::vector<int> child_counts[2];
-  std::vector<int> child_maxnb[2];                   // ... and the largest boundary among them
-  std::vector<std::vector<int>> h_small, h_child[2];  // host copies (ascending ids) of small_lists / child_lists
-  // tiles (64 x 16) before each item of child_lists (Schur complements) and of level_lists (P and
-  // U panels): the flat grids of extend-add and compaction
-  std::vector<std::vector<int64_t>> h_ctile[2], h_ptile, h_utile, h_atile;  // h_atile: groups of 32 pivots (assembly)
-  std::vector<DBuf<int64_t>> ctile[2], ptile, utile, atile;
-  int big_solve = 0;  // fronts above this size are solved by many workgroups (kBigSolve; SPL_MF_BIGSOLVE)
-  int64_t gemv_scratch = 0;  // doubles per right-hand-side column the chunked boundary product of a level needs at most
-  // those fronts, per depth, and the flat grids of their lockstep solve kernels: segments of
-  // count + 1 prefix sums (workgroups before each front), in this order: untransposed forward
-  // steps [0, steps), transposed forward steps, backward steps, then the boundary kernel of the
-  // transposed forward pass, gather, gemv, scatter
-  struct BigLevel {
-    int count = 0, steps = 0;
-    int row_blocks = 1;  // blocks of 64 rows per workgroup in the super-block steps (levels that fill the chip: more)
+  const LevelTables t;
+  struct Big {  // the fronts of one depth that many workgroups solve: BigLevel and its device copy
+    using Grid = BigLevel::Grid;
+    const BigLevel *h = nullptr;
+    int count = 0, steps = 0, row_blocks = 1;
     DBuf<int> list;
-    std::vector<int64_t> h;
     DBuf<int64_t> d;
-    // kind 0 fwd, 1 fwd^T, 2 bwd, 3 boundary^T, 4 gather, 5 gemv (transposed), 6 scatter, 7 gemv in chunks, 8 its
-    // reduction, 9 offsets of the fronts in its scratch (doubles per column); 10, 11, 12: the same three for the
-    // forward boundary product (nb rows x np columns)
-    // 13, 14: the pipelined passes over the pivot block (forward, backward): launches [0, steps]
-    size_t seg(int kind, int k = 0) const {
-      size_t which;
-      if (kind < 3) which = (size_t)kind * (size_t)steps + (size_t)k;
-      else if (kind < 13) which = (size_t)3 * steps + (size_t)(kind - 3);
-      else which = (size_t)3 * steps + 10 + (size_t)(kind - 13) * (size_t)(steps + 1) + (size_t)k;
-      return which * (size_t)(count + 1);
-    }
-    unsigned total(int kind, int k = 0) const { return (unsigned)h[seg(kind, k) + (size_t)count]; }
-    const int64_t *prefix(int kind, int k = 0) const { return d.get() + seg(kind, k); }
+    unsigned total(Grid grid, int k = 0) const { return h->total(grid, k); }
+    const int64_t *prefix(Grid grid, int k = 0) const { return d.get() + h->seg(grid, k); }
   };
-  std::vector<BigLevel> big;
-  // the lockstep medium fronts of each depth (whole level) and the prefix arrays of their steps:
-  // [step][phase 0 = panel solves, 1 = update][count + 1]
-  struct Mid {
-    int count = 0, steps = 0;
-    DBuf<int> list;
-    std::vector<int64_t> h;
-    DBuf<int64_t> d;
+  struct Level {  // device copies of T.by_depth[d] and of LevelTables::Level
+    DBuf<int> fronts, small, solve, child[2], mid;
+    DBuf<int64_t> ptile, utile, atile, ctile[2], mid_prefix;
+    Big big;
   };
-  std::vector<Mid> mid;
+  std::vector<Level> dev;
+  explicit LevelPlan(LevelTables tables) : t(std::move(tables)), dev(t.levels.size()) {}
 };
 
 struct Factors {
@@ -1078,7 +1036,7 @@ struct Factors {
   DBuf<double> arena, invs;  // factor panels, inverses of the diagonal blocks
 
   std::shared_ptr<LevelPlan> lp;  // lists and grids of the levels (shared with the other factorisations of this tree)
-  using BigLevel = LevelPlan::BigLevel;
+  using BigLevel = LevelPlan::Big;
   int singular = 0;
   int zm = 1;         // 2: complex fronts in two planes (TreeView::zm)
   // the pivot blocks of the large fronts as chains of matrix-vector products (mf_chain.hpp): built by the first
@@ -1160,394 +1118,203 @@ void mf_chain_info(const mf::Factors *F, double out[3]) {
     }
 }
 
-namespace {
-
-// Transient memory plan of the numeric factorisation.  With cut = 0 the tree is processed level by
-// level as a whole: the whole fronts of a level and of its children are alive together.  With
-// cut = K > 0 the subtrees hanging below depth K are processed one after the other (each needs
-// only its own share of every level), the Schur complement of each subtree root waits in the
-// `cut` buffer, and the top K levels come last.  The smallest K that fits the budget is used.
-struct Plan {
-  int cut = 0;
-  std::vector<int64_t> foff;         // offset of every whole front inside its region (per segment and level)
-  std::vector<int64_t> cboff;        // offset of the saved Schur complement of a subtree root, or -1
-  std::vector<int> first;            // smallest id of the subtree of every front
-  std::vector<int> roots;            // the fronts at depth `cut` (ascending ids); empty for cut = 0
-  int64_t region_elems[2] = {0, 0}, cut_elems = 0;
-  int64_t transient_elems() const { return region_elems[0] + region_elems[1] + cut_elems; }
-};
-
-Plan make_plan(const mf::Tree &T, int cut) {
-  Plan P;
-  P.cut = cut;
-  const int nf = T.nfronts, nd = T.maxdepth + 1;
-  P.foff.assign((size_t)nf, 0);
-  P.cboff.assign((size_t)nf, -1);
-  P.first.resize((size_t)nf);
-  for (int f = 0; f < nf; ++f) P.first[(size_t)f] = f;
-  for (int f = 0; f < nf; ++f)
-    if (T.parent[(size_t)f] >= 0)
-      P.first[(size_t)T.parent[(size_t)f]] = std::min(P.first[(size_t)T.parent[(size_t)f]], P.first[(size_t)f]);
-  auto front_elems = [&](int f) {
-    return ((int64_t)T.ld[(size_t)f] * std::max(T.fs(f), 1) + 15) / 16 * 16;
-  };
-  // lays out the fronts with ids in [lo, hi] and depths in [dtop, nd): returns nothing, grows the regions
-  auto layout = [&](int lo, int hi, int dtop) {
-    for (int d = dtop; d < nd; ++d) {
-      const std::vector<int> &L = T.by_depth[(size_t)d];
-      int64_t off = 0;
-      for (auto it = std::lower_bound(L.begin(), L.end(), lo); it != L.end() && *it <= hi; ++it) {
-        P.foff[(size_t)*it] = off;
-        off += front_elems(*it);
-      }
-      P.region_elems[d & 1] = std::max(P.region_elems[d & 1], off);
-    }
-  };
-  if (cut <= 0 || cut >= nd) {
-    P.cut = 0;
-    layout(0, nf - 1, 0);
-    return P;
-  }
-  P.roots = T.by_depth[(size_t)cut];
-  for (int r : P.roots) {
-    layout(P.first[(size_t)r], r, cut);
-    P.cboff[(size_t)r] = P.cut_elems;
-    P.cut_elems += ((int64_t)T.nb[(size_t)r] * T.nb[(size_t)r] + 15) / 16 * 16;
-  }
-  // the top: depths < cut (their lists hold nothing else)
-  for (int d = 0; d < cut; ++d) {
-    int64_t off = 0;
-    for (int f : T.by_depth[(size_t)d]) {
-      P.foff[(size_t)f] = off;
-      off += front_elems(f);
-    }
-    P.region_elems[d & 1] = std::max(P.region_elems[d & 1], off);
-  }
-  return P;
-}
-
-}  // namespace
-
 size_t mf_device_bytes(const mf::Tree &T, int zm) {  // resident part; the transient part is planned in mf_factor
   return ((size_t)zm * ((size_t)T.panel_elems + (size_t)T.inv_elems) + 3 * (size_t)zm * (size_t)T.work_elems) * sizeof(double) +
          ((size_t)T.bidx.size() + (size_t)T.rel_elems + 14 * (size_t)T.nfronts + (size_t)T.n) * sizeof(int64_t);
 }
 
-// numeric factorisation of P A P^T; d_Ap/d_Ai/d_Ax: CSC arrays of A on the device, d_Rp/d_Rj/d_Rx: its CSR
-// arrays, d_perm: new -> old, d_inv: old -> new
 namespace {
-template <bool Z>
-mf::Factors *mf_factor_t(std::shared_ptr<const mf::Tree> tree, const int *d_Ap, const int *d_Ai, const double *d_Ax,
-                         const int *d_Rp, const int *d_Rj, const double *d_Rx, const int *d_perm, const int *d_inv,
-                         hipStream_t s, bool symmetric, bool pivot, const double *d_rscale) {
-  constexpr int ZM = Z ? 2 : 1;
-  if (symmetric) pivot = false;  // L D L^T needs symmetric interchanges
-  const mf::Tree &T = *tree;
-  const bool timing = getenv("SPL_MF_TIMING") != nullptr;  // phase times on stderr (diagnostic)
-  auto clock_now = [] { return std::chrono::steady_clock::now(); };
-  auto t_start = clock_now();
-  auto lap = [&](const char *what) {
-    if (!timing) return;
-    (void)hipDeviceSynchronize();
-    const auto now = clock_now();
-    fprintf(stderr, "[mf_factor] %-52s %8.1f ms\n", what, std::chrono::duration<double, std::milli>(now - t_start).count());
-    t_start = now;
-  };
-  std::unique_ptr<mf::Factors> Fp(new mf::Factors());
-  mf::Factors &F = *Fp;
-  F.tree = tree;
-  F.zm = ZM;
-  const int big_solve = getenv("SPL_MF_BIGSOLVE") ? std::max(64, atoi(getenv("SPL_MF_BIGSOLVE"))) : kBigSolve;
-  const int nd = T.maxdepth + 1, nf = T.nfronts;
-  const int small_limit = getenv("SPL_MF_SMALL") ? std::max(64, atoi(getenv("SPL_MF_SMALL"))) : kSmallFront;  // tuning knob
-  // medium fronts (kSmallFront < size <= mid_limit) go through the lockstep kernels; SPL_MF_MID=0
-  // sends them down the per-front pipeline instead (ablation)
-  const int mid_limit = (getenv("SPL_MF_MID") && atoi(getenv("SPL_MF_MID")) == 0) ? small_limit
-                        : std::max(getenv("SPL_MF_MIDMAX") ? atoi(getenv("SPL_MF_MIDMAX")) : kMidFront, small_limit);
-  const bool mid_paired = !(getenv("SPL_MF_MIDPAIR") && atoi(getenv("SPL_MF_MIDPAIR")) == 0);  // 0: K = 64 every step (ablation)
-  // ---- memory plan: the smallest cut depth whose transient part fits next to the resident part
-  Plan plan;
-  {
-    const size_t free_b = device_free_bytes();
-    const double budget = (double)free_b - (double)free_b / 16 - (double)mf_device_bytes(T, ZM);
-    const char *force = getenv("SPL_MF_CUT");  // tests: force a cut depth
-    bool ok = false;
-    for (int cut = force ? std::max(0, std::min(atoi(force), nd - 1)) : 0; cut < std::max(nd, 1) && cut <= 10; ++cut) {
-      plan = make_plan(T, cut);
-      if ((double)plan.transient_elems() * sizeof(double) * ZM <= budget || force) { ok = true; break; }
-    }
-    if (!ok) throw DeviceError{SPL_ERROR_out_of_memory};
-    if (timing)
-      fprintf(stderr, "[mf_factor] %spanels %.1f GB, transient %.1f GB at cut depth %d (free %.1f GB)\n",
-              Z ? "complex fronts: " : "", ZM * T.panel_elems * 8e-9, ZM * plan.transient_elems() * 8e-9, plan.cut,
-              free_b * 1e-9);
-  }
-  // the device copy of the tree and the relative indices: built once per tree and device, then shared
-  {
-    std::lock_guard<std::mutex> lk(T.device_cache_mu);
-    int dev = 0;
-    SPL_HIP(hipGetDevice(&dev));
-    std::shared_ptr<DeviceTree> cached = std::static_pointer_cast<DeviceTree>(T.device_cache);
-    if (!cached || cached->device != dev) {
-      std::shared_ptr<DeviceTree> fresh = std::make_shared<DeviceTree>();
-      DeviceTree &N = *fresh;
-      N.device = dev;
-      upload_vec(N.p0, T.p0, s);
-      upload_vec(N.np, T.np, s);
-      upload_vec(N.nb, T.nb, s);
-      upload_vec(N.ld, T.ld, s);
-      upload_vec(N.parent, T.parent, s);
-      upload_vec(N.front_of, T.front_of, s);
-      upload_vec(N.bidx, T.bidx, s);
-      upload_vec(N.bptr, T.bptr, s);
-      upload_vec(N.ioff, T.ioff, s);
-      upload_vec(N.woff, T.woff, s);
-      upload_vec(N.roff, T.roff, s);
-      upload_vec(N.depth, T.depth, s);
-      upload_vec(N.ldp, T.ldp, s);
-      upload_vec(N.ldu, T.ldu, s);
-      upload_vec(N.poff, T.poff, s);
-      upload_vec(N.uoff, T.uoff, s);
-      N.rel.alloc((size_t)T.rel_elems);
-      const TreeView v{N.p0.get(),   N.np.get(),   N.nb.get(),   N.ld.get(),   N.parent.get(), N.front_of.get(),
-                       N.bidx.get(), N.rel.get(),  N.depth.get(), N.ldp.get(), N.ldu.get(),    N.bptr.get(),
-                       nullptr,      N.ioff.get(), N.woff.get(), N.roff.get(), N.poff.get(),   N.uoff.get(),
-                       {nullptr, nullptr}, nullptr, nullptr, nullptr, 0, 1, 0, nullptr};
-      if (nf > 0) hipLaunchKernelGGL(rel_kernel, dim3((unsigned)nf), dim3(256), 0, s, nf, v, N.rel.get());
-      SPL_HIP(hipStreamSynchronize(s));  // the host vectors of the tree may go away with it
-      SPL_HIP(hipGetLastError());
-      T.device_cache = fresh;
-      cached = fresh;
-    }
-    F.D = cached;
-  }
-  DeviceTree &D = *F.D;
-  upload_vec(F.d_foff, plan.foff, s);
-  upload_vec(F.d_cboff, plan.cboff, s);
-  lap("tree uploads (queued)");
-  F.arena.alloc((size_t)ZM * (size_t)T.panel_elems);
-  F.invs.alloc((size_t)ZM * (size_t)T.inv_elems);
-  DBuf<double> region0((size_t)ZM * (size_t)plan.region_elems[0]), region1((size_t)ZM * (size_t)plan.region_elems[1]),
-      cutbuf((size_t)ZM * (size_t)plan.cut_elems);  // transient
-  lap("hipMalloc");
-  F.view = TreeView{D.p0.get(),    D.np.get(),   D.nb.get(),   D.ld.get(),   D.parent.get(), D.front_of.get(),
-                    D.bidx.get(),  D.rel.get(),  D.depth.get(), D.ldp.get(), D.ldu.get(),    D.bptr.get(),
-                    F.d_foff.get(), D.ioff.get(), D.woff.get(), D.roff.get(), D.poff.get(),  D.uoff.get(),
-                    {region0.get(), region1.get()}, F.arena.get(), F.d_cboff.get(), cutbuf.get(), symmetric ? 1 : 0, ZM,
-                    pivot ? 1 : diag_form_without_interchanges(), pivot ? d_rscale : nullptr};
-  std::vector<std::vector<int>> staged;  // host copies must outlive the asynchronous uploads
-  // the medium fronts among the fronts [b0, b1) of a level's list, the number of block steps of the longest and the
-  // prefix arrays of all steps: [step][phase 0 = panel solves, 1 = update][count + 1]
-  auto mid_fronts_of = [&](const std::vector<int> &fronts, int b0, int b1, std::vector<int> &mid, int &steps,
-                           std::vector<int64_t> &pre) {
-    mid.clear();
-    steps = 0;
-    for (int i = b0; i < b1; ++i) {
-      const int f = fronts[(size_t)i];
-      if (T.np[(size_t)f] == 0 || T.fs(f) <= small_limit || T.fs(f) > mid_limit) continue;
-      mid.push_back(f);
-      steps = std::max(steps, (T.np[(size_t)f] + NB - 1) / NB);
-    }
-    const int count = (int)mid.size();
-    pre.assign((size_t)steps * 2 * (size_t)(count + 1), 0);
-    for (int st = 0; st < steps; ++st) {
-      int64_t *pt = pre.data() + ((size_t)st * 2) * (size_t)(count + 1), *pu = pt + (count + 1);
-      for (int k = 0; k < count; ++k) {
-        const int f = mid[(size_t)k], np = T.np[(size_t)f], j0 = st * NB;
-        int64_t tt = 0, tu = 0;
-        if (j0 < np) {
-          const int jb = std::min(NB, np - j0), rest = T.fs(f) - (j0 + jb);
-          const int64_t nt = (rest + 63) / 64;
-          tt = 2 * nt;
-          tu = nt * nt;
-          if (mid_paired && !(st & 1) && np >= j0 + jb + NB) tu = 2 * nt - 1;  // (the L-shaped pass of an even step)
-        }
-        pt[k + 1] = pt[k] + tt;
-        pu[k + 1] = pu[k] + tu;
-      }
-    }
-  };
-  // the lists and grids of the levels: from the tree's cache, or built now (and kept there)
-  std::unique_lock<std::mutex> plan_lock(T.device_cache_mu);
-  {
-    std::shared_ptr<mf::LevelPlan> have = std::static_pointer_cast<mf::LevelPlan>(D.level_plan);
-    if (have && have->small_limit == small_limit && have->big_solve == big_solve && have->mid_limit == mid_limit &&
-        have->mid_paired == (mid_paired ? 1 : 0))
-      F.lp = have;
-  }
-  const bool build_plan = !F.lp;
-  if (build_plan) {
-  F.lp = std::make_shared<mf::LevelPlan>();
-  F.lp->small_limit = small_limit;
-  F.lp->big_solve = big_solve;
-  F.lp->mid_limit = mid_limit;
-  F.lp->mid_paired = mid_paired ? 1 : 0;
-  F.lp->level_lists.resize((size_t)nd);
-  F.lp->small_lists.resize((size_t)nd);
-  F.lp->small_counts.assign((size_t)nd, 0);
-  F.lp->solve_lists.resize((size_t)nd);
-  F.lp->big.resize((size_t)nd);
-  F.lp->solve_counts.assign((size_t)nd, 0);
-  F.lp->h_small.assign((size_t)nd, std::vector<int>());
-  for (int sl = 0; sl < 2; ++sl) {
-    F.lp->child_lists[sl].resize((size_t)nd);
-    F.lp->child_counts[sl].assign((size_t)nd, 0);
-    F.lp->child_maxnb[sl].assign((size_t)nd, 0);
-    F.lp->h_child[sl].assign((size_t)nd, std::vector<int>());
-  }
-  // the flat grids of the lockstep solve kernels for the large fronts `large` of one depth
-  auto build_big = [&](mf::Factors::BigLevel &B, std::vector<int> large) {
-    B.count = (int)large.size();
-    constexpr int span = SB * NB;
-    for (int f : large) B.steps = std::max(B.steps, (T.np[(size_t)f] + span - 1) / span);
-    if (B.count > 0) {
-      // every workgroup of a step redoes the in-super-block solve: where the first step alone
-      // would launch thousands of workgroups, each takes kSolveRowBlocks blocks of rows instead
-      int64_t first_step = 0;
-      for (int f : large) first_step += (T.fs(f) + 63) / 64;
-      B.row_blocks = first_step >= 4096 ? kSolveRowBlocks : 1;
-      const int rbk = B.row_blocks;
-      B.h.assign((size_t)(3 * B.steps + 10 + 2 * (B.steps + 1)) * (size_t)(B.count + 1), 0);
-      auto fill = [&](int kind, int k, auto groups_of) {
-        int64_t *pre = B.h.data() + B.seg(kind, k);
-        for (int i = 0; i < B.count; ++i) pre[i + 1] = pre[i] + groups_of(large[(size_t)i]);
-      };
-      for (int k = 0; k < B.steps; ++k) {
-        auto fwd_rows = [&](int f, int n) -> int64_t {  // workgroups of forward step k of a pass over n rows
-          const int np = T.np[(size_t)f], j0 = k * span;
-          if (j0 >= np) return 0;
-          const int jbs = std::min(span, np - j0);
-          return std::max(1, ((n - (j0 + jbs) + 63) / 64 + rbk - 1) / rbk);
-        };
-        fill(0, k, [&](int f) { return fwd_rows(f, T.fs(f)); });
-        fill(1, k, [&](int f) { return fwd_rows(f, T.np[(size_t)f]); });
-        fill(2, k, [&](int f) -> int64_t {
-          const int np = T.np[(size_t)f], nsup = (np + span - 1) / span;
-          if (k >= nsup) return 0;
-          return std::max(1, (((nsup - 1 - k) * span + 63) / 64 + rbk - 1) / rbk);
-        });
-      }
-      for (int k = 0; k <= B.steps; ++k) {  // the pipelined passes: lead groups of step k + bulk groups of step k - 1
-        auto groups = [&](int f, bool forward) -> int64_t {
-          const int np = T.np[(size_t)f], nsup = (np + span - 1) / span;
-          auto beyond = [&](int st) {  // rows of the pivot block still to be updated by step st
-            const int j0 = (forward ? st : nsup - 1 - st) * span, jbs = std::min(span, np - j0);
-            return forward ? np - (j0 + jbs) : j0;
-          };
-          int64_t g = 0;
-          if (k < nsup) g += std::max(1, std::min(SB, (beyond(k) + 63) / 64));
-          if (k >= 1 && k - 1 < nsup) {
-            const int rest = beyond(k - 1) - span;
-            if (rest > 0) g += ((rest + 63) / 64 + rbk - 1) / rbk;
-          }
-          return g;
-        };
-        fill(13, k, [&](int f) { return groups(f, true); });
-        fill(14, k, [&](int f) { return groups(f, false); });
-      }
-      fill(3, 0, [&](int f) -> int64_t { return (T.nb[(size_t)f] + 3) / 4; });
-      fill(4, 0, [&](int f) -> int64_t { return (T.nb[(size_t)f] + 255) / 256; });
-      fill(5, 0, [&](int f) -> int64_t { return T.nb[(size_t)f] > 0 ? (T.np[(size_t)f] + 63) / 64 : 0; });
-      fill(6, 0, [&](int f) -> int64_t { return (T.np[(size_t)f] + 255) / 256; });
-      auto chunks = [&](int f) -> int64_t { return (T.nb[(size_t)f] + kGemvChunk - 1) / kGemvChunk; };
-      fill(7, 0, [&](int f) -> int64_t { return (int64_t)((T.np[(size_t)f] + 63) / 64) * chunks(f); });
-      fill(8, 0, [&](int f) -> int64_t { return chunks(f) > 1 ? (T.np[(size_t)f] + 255) / 256 : 0; });
-      fill(9, 0, [&](int f) -> int64_t { return chunks(f) > 1 ? chunks(f) * T.np[(size_t)f] : 0; });
-      F.lp->gemv_scratch = std::max(F.lp->gemv_scratch, B.h[B.seg(9) + (size_t)B.count]);
-      auto fchunks = [&](int f) -> int64_t { return (T.np[(size_t)f] + kGemvChunk - 1) / kGemvChunk; };
-      fill(10, 0, [&](int f) -> int64_t { return (int64_t)((T.nb[(size_t)f] + (T.np[(size_t)f] & 15) + 63) / 64) * fchunks(f); });
-      fill(11, 0, [&](int f) -> int64_t { return fchunks(f) > 1 ? (T.nb[(size_t)f] + 255) / 256 : 0; });
-      fill(12, 0, [&](int f) -> int64_t { return fchunks(f) > 1 ? fchunks(f) * T.nb[(size_t)f] : 0; });
-      F.lp->gemv_scratch = std::max(F.lp->gemv_scratch, B.h[B.seg(12) + (size_t)B.count]);
-      staged.push_back(std::move(large));
-      upload_vec(B.list, staged.back(), s);
-      upload_vec(B.d, B.h, s);
-    }
-      };
-  staged.reserve((size_t)nd);
-  for (int d = 0; d < nd; ++d) {
-    upload_vec(F.lp->level_lists[(size_t)d], T.by_depth[(size_t)d], s);
-    for (int f : T.by_depth[(size_t)d])
-      if (T.np[(size_t)f] > 0 && T.fs(f) <= small_limit) F.lp->h_small[(size_t)d].push_back(f);
-    F.lp->small_counts[(size_t)d] = (int)F.lp->h_small[(size_t)d].size();
-    upload_vec(F.lp->small_lists[(size_t)d], F.lp->h_small[(size_t)d], s);
-    std::vector<int> one_wg;
-    for (int f : T.by_depth[(size_t)d])
-      if (T.fs(f) <= F.lp->big_solve) one_wg.push_back(f);
-    F.lp->solve_counts[(size_t)d] = (int)one_wg.size();
-    staged.push_back(std::move(one_wg));
-    upload_vec(F.lp->solve_lists[(size_t)d], staged.back(), s);
-    {
-      std::vector<int> large;
-      for (int f : T.by_depth[(size_t)d])
-        if (T.fs(f) > F.lp->big_solve && T.np[(size_t)f] > 0) large.push_back(f);
-      build_big(F.lp->big[(size_t)d], std::move(large));
-    }
-    if (d + 1 < nd) {
-      for (int c : T.by_depth[(size_t)d + 1]) F.lp->h_child[T.slot[(size_t)c]][(size_t)d].push_back(c);
-      for (int sl = 0; sl < 2; ++sl) {
-        F.lp->child_counts[sl][(size_t)d] = (int)F.lp->h_child[sl][(size_t)d].size();
-        for (int c : F.lp->h_child[sl][(size_t)d]) F.lp->child_maxnb[sl][(size_t)d] = std::max(F.lp->child_maxnb[sl][(size_t)d], T.nb[(size_t)c]);
-        upload_vec(F.lp->child_lists[sl][(size_t)d], F.lp->h_child[sl][(size_t)d], s);
-      }
-    }
-  }
-  {
-    auto tiles = [](int64_t rows, int64_t cols) { return ((rows + 63) / 64) * ((cols + kTileCols - 1) / kTileCols); };
-    F.lp->h_ptile.assign((size_t)nd, std::vector<int64_t>());
-    F.lp->h_utile.assign((size_t)nd, std::vector<int64_t>());
-    F.lp->h_atile.assign((size_t)nd, std::vector<int64_t>());
-    F.lp->ptile.resize((size_t)nd);
-    F.lp->utile.resize((size_t)nd);
-    F.lp->atile.resize((size_t)nd);
+
+// queues the device copies of a plan's tables on s (they stay in the plan: nothing to keep alive but T.by_depth)
+void upload_level_plan(mf::LevelPlan &P, const mf::Tree &T, hipStream_t s) {
+  for (size_t d = 0; d < P.dev.size(); ++d) {
+    const mf::LevelTables::Level &H = P.t.levels[d];
+    mf::LevelPlan::Level &V = P.dev[d];
+    upload_vec(V.fronts, T.by_depth[d], s);
+    upload_vec(V.small, H.small, s);
+    upload_vec(V.solve, H.solve, s);
+    upload_vec(V.ptile, H.ptile, s);
+    upload_vec(V.utile, H.utile, s);
+    upload_vec(V.atile, H.atile, s);
     for (int sl = 0; sl < 2; ++sl) {
-      F.lp->h_ctile[sl].assign((size_t)nd, std::vector<int64_t>());
-      F.lp->ctile[sl].resize((size_t)nd);
+      if (d + 1 < P.dev.size()) upload_vec(V.child[sl], H.child[sl], s);
+      upload_vec(V.ctile[sl], H.ctile[sl], s);
     }
-    for (int d = 0; d < nd; ++d) {
-      std::vector<int64_t> &pp = F.lp->h_ptile[(size_t)d], &uu = F.lp->h_utile[(size_t)d], &aa = F.lp->h_atile[(size_t)d];
-      pp.assign(1, 0);
-      uu.assign(1, 0);
-      aa.assign(1, 0);
-      for (int f : T.by_depth[(size_t)d]) {
-        pp.push_back(pp.back() + tiles(T.fs(f), T.np[(size_t)f]));
-        uu.push_back(uu.back() + tiles(T.np[(size_t)f], T.nb[(size_t)f]));
-        aa.push_back(aa.back() + (T.np[(size_t)f] + 31) / 32);
-      }
-      upload_vec(F.lp->ptile[(size_t)d], pp, s);
-      upload_vec(F.lp->utile[(size_t)d], uu, s);
-      upload_vec(F.lp->atile[(size_t)d], aa, s);
-      for (int sl = 0; sl < 2; ++sl) {
-        std::vector<int64_t> &cc = F.lp->h_ctile[sl][(size_t)d];
-        cc.assign(1, 0);
-        for (int c : F.lp->h_child[sl][(size_t)d]) cc.push_back(cc.back() + tiles(T.nb[(size_t)c], T.nb[(size_t)c]));
-        upload_vec(F.lp->ctile[sl][(size_t)d], cc, s);
-      }
+    V.big.h = &H.big;
+    V.big.count = H.big.count;
+    V.big.steps = H.big.steps;
+    V.big.row_blocks = H.big.row_blocks;
+    if (H.big.count > 0) {
+      upload_vec(V.big.list, H.big.list, s);
+      upload_vec(V.big.d, H.big.h, s);
+    }
+    if (H.mid.count > 0) {
+      upload_vec(V.mid, H.mid.list, s);
+      upload_vec(V.mid_prefix, H.mid.h, s);
     }
   }
-  // the lockstep medium fronts of every (whole) level and the prefix arrays of their steps
-  F.lp->mid.resize((size_t)nd);
-  for (int d = 0; d < nd; ++d) {
-    mf::LevelPlan::Mid &M = F.lp->mid[(size_t)d];
-    std::vector<int> mid;
-    mid_fronts_of(T.by_depth[(size_t)d], 0, (int)T.by_depth[(size_t)d].size(), mid, M.steps, M.h);
-    M.count = (int)mid.size();
-    if (M.count == 0) continue;
-    upload_vec(M.list, mid, s);
-    upload_vec(M.d, M.h, s);
-    staged.push_back(std::move(mid));
-  }
+}
+
+// the tree's own arrays as the kernels see them; what belongs to one factorisation (foff, regions, arena, cboff, cut,
+// rscale) is null, sym 0, zm 1, piv 0
+TreeView make_tree_view(const DeviceTree &D) {
+  TreeView v{};
+  v.p0 = D.p0.get();
+  v.np = D.np.get();
+  v.nb = D.nb.get();
+  v.ld = D.ld.get();
+  v.parent = D.parent.get();
+  v.front_of = D.front_of.get();
+  v.bidx = D.bidx.get();
+  v.rel = D.rel.get();
+  v.depth = D.depth.get();
+  v.ldp = D.ldp.get();
+  v.ldu = D.ldu.get();
+  v.bptr = D.bptr.get();
+  v.ioff = D.ioff.get();
+  v.woff = D.woff.get();
+  v.roff = D.roff.get();
+  v.poff = D.poff.get();
+  v.uoff = D.uoff.get();
+  v.zm = 1;
+  return v;
+}
+
+// the device copy of the tree and the relative indices: built once per tree and device, then shared
+std::shared_ptr<DeviceTree> device_tree_for(const mf::Tree &T, hipStream_t s) {
+  std::lock_guard<std::mutex> lk(T.device_cache_mu);
+  int dev = 0;
+  SPL_HIP(hipGetDevice(&dev));
+  std::shared_ptr<DeviceTree> cached = std::static_pointer_cast<DeviceTree>(T.device_cache);
+  if (cached && cached->device == dev) return cached;
+  std::shared_ptr<DeviceTree> fresh = std::make_shared<DeviceTree>();
+  DeviceTree &N = *fresh;
+  N.device = dev;
+  upload_vec(N.p0, T.p0, s);
+  upload_vec(N.np, T.np, s);
+  upload_vec(N.nb, T.nb, s);
+  upload_vec(N.ld, T.ld, s);
+  upload_vec(N.parent, T.parent, s);
+  upload_vec(N.front_of, T.front_of, s);
+  upload_vec(N.bidx, T.bidx, s);
+  upload_vec(N.bptr, T.bptr, s);
+  upload_vec(N.ioff, T.ioff, s);
+  upload_vec(N.woff, T.woff, s);
+  upload_vec(N.roff, T.roff, s);
+  upload_vec(N.depth, T.depth, s);
+  upload_vec(N.ldp, T.ldp, s);
+  upload_vec(N.ldu, T.ldu, s);
+  upload_vec(N.poff, T.poff, s);
+  upload_vec(N.uoff, T.uoff, s);
+  N.rel.alloc((size_t)T.rel_elems);
+  if (T.nfronts > 0)
+    hipLaunchKernelGGL(rel_kernel, dim3((unsigned)T.nfronts), dim3(256), 0, s, T.nfronts, make_tree_view(N), N.rel.get());
+  SPL_HIP(hipStreamSynchronize(s));  // the host vectors of the tree may go away with it
+  SPL_HIP(hipGetLastError());
+  T.device_cache = fresh;
+  return fresh;
+}
+
+// the lists and grids of the levels: from the tree's cache, or built now (and kept there)
+std::shared_ptr<mf::LevelPlan> level_plan_for(DeviceTree &D, const mf::Tree &T, const mf::FactorKnobs &knobs, hipStream_t s,
+                                              bool *built) {
+  std::lock_guard<std::mutex> lk(T.device_cache_mu);
+  std::shared_ptr<mf::LevelPlan> have = std::static_pointer_cast<mf::LevelPlan>(D.level_plan);
+  *built = !(have && have->t.built_for(knobs));
+  if (!*built) return have;
+  have = std::make_shared<mf::LevelPlan>(mf::build_level_tables(T, knobs));
+  upload_level_plan(*have, T, s);
   SPL_HIP(hipStreamSynchronize(s));
-  staged.clear();
-  D.level_plan = F.lp;
-  }  // build_plan
-  plan_lock.unlock();
-  lap(build_plan ? "level lists (built)" : "level lists (from the tree's cache)");
-  DBuf<int> singular(1);
-  SPL_HIP(hipMemsetAsync(singular.get(), 0, sizeof(int), s));
-  set_factor_attributes();
-  static std::atomic<uint64_t> attr_set{0};  // one bit per device
-  if (first_use_on_this_device(attr_set)) {
+  D.level_plan = have;
+  return have;
+}
+
+struct PhaseTimer {  // SPL_MF_TIMING: the time since the last lap, the device's queued work included, on stderr
+  bool on;
+  std::chrono::steady_clock::time_point last = std::chrono::steady_clock::now();
+  void lap(const char *what) {
+    if (!on) return;
+    (void)hipDeviceSynchronize();
+    const auto now = std::chrono::steady_clock::now();
+    fprintf(stderr, "[mf_factor] %-52s %8.1f ms\n", what, std::chrono::duration<double, std::milli>(now - last).count());
+    last = now;
+  }
+};
+
+// memory plan: the smallest cut depth whose transient part fits next to the resident part
+mf::Plan plan_transient(const mf::Tree &T, int zm, const mf::FactorKnobs &knobs) {
+  const int nd = T.maxdepth + 1;
+  const size_t free_b = device_free_bytes();
+  const double budget = (double)free_b - (double)free_b / 16 - (double)mf_device_bytes(T, zm);
+  const bool force = knobs.forced_cut >= 0;
+  for (int cut = force ? std::min(knobs.forced_cut, nd - 1) : 0; cut < std::max(nd, 1) && cut <= 10; ++cut) {
+    mf::Plan plan = mf::make_plan(T, cut);
+    if (!((double)plan.transient_elems() * sizeof(double) * zm <= budget || force)) continue;
+    if (knobs.timing)
+      fprintf(stderr, "[mf_factor] %spanels %.1f GB, transient %.1f GB at cut depth %d (free %.1f GB)\n",
+              zm == 2 ? "complex fronts: " : "", zm * T.panel_elems * 8e-9, zm * plan.transient_elems() * 8e-9, plan.cut,
+              free_b * 1e-9);
+    return plan;
+  }
+  throw DeviceError{SPL_ERROR_out_of_memory};
+}
+
+// what mf_factor is given: d_Ap/d_Ai/d_Ax: CSC arrays of A on the device, d_Rp/d_Rj/d_Rx: its CSR arrays, d_perm:
+// new -> old, d_inv: old -> new
+struct FactorInput {
+  const int *d_Ap, *d_Ai;
+  const double *d_Ax;
+  const int *d_Rp, *d_Rj;
+  const double *d_Rx;
+  const int *d_perm, *d_inv;
+  bool symmetric, pivot;
+  const double *d_rscale;
+};
+
+// The walk of a numeric factorisation over the levels, bottom-up: the launches of one factorisation and what they share.
+template <bool Z>
+struct FactorWalk {
+  static constexpr int ZM = Z ? 2 : 1;
+  const mf::Tree &T;
+  const mf::FactorKnobs &knobs;
+  const mf::Plan &plan;
+  const FactorInput &in;
+  mf::Factors &F;
+  double *region[2];  // whole fronts of the even / odd levels
+  int *singular;
+  hipStream_t s;
+  PhaseTimer &timer;
+  const int nd = T.maxdepth + 1, nf = T.nfronts;
+  // Assembly beside the factorisation (round 4): the fronts of a level live in the region the level two below it
+  // used, which is free as soon as the level between them has taken its children's Schur complements.  So while
+  // level d is factored, stream `aux` moves the panels of level d + 1 to the arena, then zeroes that region and
+  // scatters the entries of A of level d - 1 into it: of the three parts of an assembly only the extend-add stays on
+  // the chain of the levels (at 100^3: 12 of 27 ms).  SPL_MF_OVERLAP=0: everything on the main stream, as before.
+  const bool overlap = knobs.overlap;
+  hipStream_t aux = F.side[2 * kStreams];
+  struct Events {
+    hipEvent_t taken = nullptr, prepared = nullptr;  // extend-add of a level queued; region of the next level ready
+    Events() {
+      SPL_HIP(hipEventCreateWithFlags(&taken, hipEventDisableTiming));
+      SPL_HIP(hipEventCreateWithFlags(&prepared, hipEventDisableTiming));
+    }
+    ~Events() {
+      if (taken) (void)hipEventDestroy(taken);
+      if (prepared) (void)hipEventDestroy(prepared);
+    }
+  } ev;
+  // the medium fronts of the subtrees of a cut tree: their lists are made on the way, alive until the factorisation has run
+  struct SubMid {
+    mf::Mid h;
+    DBuf<int> list;
+    DBuf<int64_t> prefix;
+  };
+  std::list<SubMid> sub_mids;
+
+  static void set_attributes() {
+    set_factor_attributes();
+    static std::atomic<uint64_t> attr_set{0};  // one bit per device
+    if (!first_use_on_this_device(attr_set)) return;
     SPL_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&front_factor_kernel<Z>),
                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)(Z ? kFrontLdsZ : 2 * kTileBytes)));
     SPL_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&mid_trsm_kernel<Z>),
@@ -1560,66 +1327,155 @@ mf::Factors *mf_factor_t(std::shared_ptr<const mf::Tree> tree, const int *d_Ap, 
     }
     mark_used_on_this_device(attr_set);
   }
-  F.make_streams();
-  hipStream_t *side = F.side;
-  auto region_of = [&](int d) { return (d & 1) ? region1.get() : region0.get(); };
-  std::vector<DBuf<int>> mid_lists;          // (subtrees of a cut tree: their lists are made on the way) alive until the factorisation has run
-  std::vector<DBuf<int64_t>> mid_prefixes;
-  std::vector<std::vector<int64_t>> staged64;
+
+  const mf::LevelTables::Level &tab(int d) const { return F.lp->t.levels[(size_t)d]; }
+  const mf::LevelPlan::Level &dev(int d) const { return F.lp->dev[(size_t)d]; }
   // [begin, end) of the ids lo..hi inside an ascending list
-  auto range_of = [](const std::vector<int> &L, int lo, int hi, int &begin, int &end) {
+  static void range_of(const std::vector<int> &L, int lo, int hi, int &begin, int &end) {
     begin = (int)(std::lower_bound(L.begin(), L.end(), lo) - L.begin());
     end = (int)(std::upper_bound(L.begin(), L.end(), hi) - L.begin());
-  };
-  auto compact_fronts = [&](int d, int lo, int hi, hipStream_t q) {  // factor panels of the fronts lo..hi of level d -> arena
+  }
+
+  void compact_fronts(int d, int lo, int hi, hipStream_t q) {  // factor panels of the fronts lo..hi of level d -> arena
     int b0, b1;
     range_of(T.by_depth[(size_t)d], lo, hi, b0, b1);
     if (b1 == b0) return;
-    const int64_t tp = F.lp->h_ptile[(size_t)d][(size_t)b1] - F.lp->h_ptile[(size_t)d][(size_t)b0];
-    const int64_t tu = F.lp->h_utile[(size_t)d][(size_t)b1] - F.lp->h_utile[(size_t)d][(size_t)b0];
+    const int64_t tp = tab(d).ptile[(size_t)b1] - tab(d).ptile[(size_t)b0];
+    const int64_t tu = tab(d).utile[(size_t)b1] - tab(d).utile[(size_t)b0];
     if (tp > 0)
-      hipLaunchKernelGGL(compact_kernel<Z>, dim3((unsigned)tp), dim3(256), 0, q, F.lp->level_lists[(size_t)d].get() + b0,
-                         F.lp->ptile[(size_t)d].get() + b0, b1 - b0, F.view, 0);
+      hipLaunchKernelGGL(compact_kernel<Z>, dim3((unsigned)tp), dim3(256), 0, q, dev(d).fronts.get() + b0,
+                         dev(d).ptile.get() + b0, b1 - b0, F.view, 0);
     if (tu > 0)
-      hipLaunchKernelGGL(compact_kernel<Z>, dim3((unsigned)tu), dim3(256), 0, q, F.lp->level_lists[(size_t)d].get() + b0,
-                         F.lp->utile[(size_t)d].get() + b0, b1 - b0, F.view, 1);
-  };
-  // Assembly beside the factorisation (round 4): the fronts of a level live in the region the level two below it
-  // used, which is free as soon as the level between them has taken its children's Schur complements.  So while
-  // level d is factored, stream `aux` moves the panels of level d + 1 to the arena, then zeroes that region and
-  // scatters the entries of A of level d - 1 into it: of the three parts of an assembly only the extend-add stays on
-  // the chain of the levels (at 100^3: 12 of 27 ms).  SPL_MF_OVERLAP=0: everything on the main stream, as before.
-  const bool overlap = !(getenv("SPL_MF_OVERLAP") && atoi(getenv("SPL_MF_OVERLAP")) == 0);
-  hipStream_t aux = side[2 * kStreams];
-  struct Events {
-    hipEvent_t taken = nullptr, prepared = nullptr;  // extend-add of a level queued; region of the next level ready
-    ~Events() {
-      if (taken) (void)hipEventDestroy(taken);
-      if (prepared) (void)hipEventDestroy(prepared);
-    }
-  } ev;
-  SPL_HIP(hipEventCreateWithFlags(&ev.taken, hipEventDisableTiming));
-  SPL_HIP(hipEventCreateWithFlags(&ev.prepared, hipEventDisableTiming));
+      hipLaunchKernelGGL(compact_kernel<Z>, dim3((unsigned)tu), dim3(256), 0, q, dev(d).fronts.get() + b0,
+                         dev(d).utile.get() + b0, b1 - b0, F.view, 1);
+  }
+
   // the fronts lo..hi of level d start from zero in their region and receive their entries of A
-  auto prepare_level = [&](int d, int lo, int hi, hipStream_t q) -> int64_t {
+  int64_t prepare_level(int d, int lo, int hi, hipStream_t q) {
     int b0, b1;
     range_of(T.by_depth[(size_t)d], lo, hi, b0, b1);
     if (b1 == b0) return 0;
     int64_t extent = 0;
     for (int i = b0; i < b1; ++i) {
       const int f = T.by_depth[(size_t)d][(size_t)i];
-      extent = std::max(extent, plan.foff[(size_t)f] + ((int64_t)T.ld[(size_t)f] * std::max(T.fs(f), 1) + 15) / 16 * 16);
+      extent = std::max(extent, plan.foff[(size_t)f] + mf::front_elems(T, f));
     }
-    SPL_HIP(hipMemsetAsync(region_of(d), 0, (size_t)ZM * (size_t)extent * sizeof(double), q));
-    const int64_t groups = F.lp->h_atile[(size_t)d][(size_t)b1] - F.lp->h_atile[(size_t)d][(size_t)b0];
+    SPL_HIP(hipMemsetAsync(region[d & 1], 0, (size_t)ZM * (size_t)extent * sizeof(double), q));
+    const int64_t groups = tab(d).atile[(size_t)b1] - tab(d).atile[(size_t)b0];
     if (groups > 0)
-      hipLaunchKernelGGL(assemble_kernel<Z>, dim3((unsigned)groups), dim3(256), 0, q, F.lp->level_lists[(size_t)d].get() + b0,
-                         F.lp->atile[(size_t)d].get() + b0, b1 - b0, F.view, d_perm, d_inv, d_Ap, d_Ai, d_Ax, d_Rp, d_Rj, d_Rx);
+      hipLaunchKernelGGL(assemble_kernel<Z>, dim3((unsigned)groups), dim3(256), 0, q, dev(d).fronts.get() + b0,
+                         dev(d).atile.get() + b0, b1 - b0, F.view, in.d_perm, in.d_inv, in.d_Ap, in.d_Ai, in.d_Ax, in.d_Rp,
+                         in.d_Rj, in.d_Rx);
     return extent;
-  };
+  }
+
+  // the fronts of level d take the Schur complements of their children lo..hi, one child slot after the other (two
+  // children of a parent may touch the same entry: a fixed order keeps the sums reproducible)
+  void extend_add(int d, int lo, int hi) {
+    for (int sl = 0; sl < 2; ++sl) {
+      int c0, c1;
+      range_of(tab(d).child[sl], lo, hi, c0, c1);
+      if (c1 == c0) continue;
+      const int64_t tc = tab(d).ctile[sl][(size_t)c1] - tab(d).ctile[sl][(size_t)c0];
+      if (tc > 0)
+        hipLaunchKernelGGL(extend_add_kernel<Z>, dim3((unsigned)tc), dim3(256), 0, s, dev(d).child[sl].get() + c0,
+                           dev(d).ctile[sl].get() + c0, c1 - c0, F.view);
+    }
+  }
+
+  void factor_small(int d, int lo, int hi) {  // one launch, one workgroup each
+    int s0, s1;
+    range_of(tab(d).small, lo, hi, s0, s1);
+    if (s1 > s0)
+      hipLaunchKernelGGL(front_factor_kernel<Z>, dim3((unsigned)(s1 - s0)), dim3(256), Z ? kFrontLdsZ : 2 * kTileBytes, s,
+                         dev(d).small.get() + s0, F.view, F.invs.get(), singular);
+  }
+
+  // medium fronts among [b0, b1) of the level's list: lockstep over block steps, one flat launch per phase and step
+  void factor_mid(int d, int b0, int b1) {
+    const mf::Mid *M = &tab(d).mid;  // the whole level: from the plan
+    const int *dl = dev(d).mid.get();
+    const int64_t *dp = dev(d).mid_prefix.get();
+    if (!(b0 == 0 && b1 == (int)T.by_depth[(size_t)d].size())) {  // a subtree of a cut tree
+      mf::Mid sub = mf::mid_fronts(T, T.by_depth[(size_t)d], b0, b1, knobs);
+      if (sub.count == 0) return;
+      sub_mids.emplace_back();
+      SubMid &S = sub_mids.back();
+      S.h = std::move(sub);
+      upload_vec(S.list, S.h.list, s);
+      upload_vec(S.prefix, S.h.h, s);
+      M = &S.h;
+      dl = S.list.get();
+      dp = S.prefix.get();
+    }
+    const int count = M->count;
+    if (count == 0) return;
+    hipLaunchKernelGGL(mid_diag_kernel<Z>, dim3((unsigned)count), dim3(256), Z ? kDiagLdsZ : kTileBytes + 2 * NB * sizeof(double),
+                       s, dl, F.view, F.invs.get(), singular);
+    for (int st = 0; st < M->steps; ++st) {
+      const int64_t nt = M->sum(st, 0), nu = M->sum(st, 1);
+      if (nt > 0)
+        hipLaunchKernelGGL(mid_trsm_kernel<Z>, dim3((unsigned)nt), dim3(256), Z ? kTrsmLdsZ : kTrsmLds, s, dl,
+                           dp + M->seg(st, 0), count, st, F.view, F.invs.get());
+      if (nu > 0)
+        hipLaunchKernelGGL(mid_update_kernel<Z>, dim3((unsigned)(nu + count)), dim3(256),
+                           Z ? kDiagLdsZ : kTileBytes + 2 * NB * sizeof(double), s, dl, dp + M->seg(st, 1), count, st, F.view,
+                           F.invs.get(), singular, knobs.mid_paired ? 1 : 0);
+    }
+  }
+
+  // large fronts among [b0, b1): the multi-launch blocked factorisation, independent fronts spread over side streams
+  void factor_large(int d, int b0, int b1) {
+    int turn = 0;
+    for (int i = b0; i < b1; ++i) {
+      const int f = T.by_depth[(size_t)d][(size_t)i];
+      if (T.np[(size_t)f] == 0 || T.fs(f) <= knobs.mid_limit) continue;
+      const Band b = dense_view(region[d & 1] + (size_t)ZM * (size_t)plan.foff[(size_t)f], T.fs(f), T.ld[(size_t)f],
+                                in.symmetric ? 1 : 0, Z ? (size_t)mf::front_elems(T, f) : 0,
+                                in.pivot ? 1 : diag_form_without_interchanges(),
+                                in.pivot && in.d_rscale ? in.d_rscale + T.p0[(size_t)f] : nullptr);
+      const int lane = turn++ % kStreams;
+      factor_loop<Z>(b, T.np[(size_t)f], F.invs.get() + (size_t)ZM * (size_t)T.ioff[(size_t)f], singular, F.side[lane],
+                     F.side[kStreams + lane]);
+    }
+    for (int i = 0; i < kStreams && i < turn; ++i) SPL_HIP(hipStreamSynchronize(F.side[i]));
+  }
+
+  // SPL_MF_TIMING, after the assembly of level d and after its factorisation
+  void report(int d, int lo, int hi, int64_t extent) {
+    double ea = 0.0, cp = 0.0;  // entries the extend-add moves, entries of the children's panels
+    for (int sl = 0; sl < 2; ++sl) {
+      int c0, c1;
+      range_of(tab(d).child[sl], lo, hi, c0, c1);
+      for (int i = c0; i < c1; ++i) {
+        const int c = tab(d).child[sl][(size_t)i];
+        const double q = T.nb[(size_t)c], pp = T.np[(size_t)c];
+        ea += in.symmetric ? q * (q + 1) / 2 : q * q;
+        cp += pp * (pp + 2 * q);
+      }
+    }
+    char what[96];
+    snprintf(what, sizeof what, "level %d: assembly (zero %.0f, extend-add %.0f, panels %.0f MB)", d, ZM * extent * 8e-6,
+             ZM * ea * 24e-6, ZM * cp * 16e-6);
+    timer.lap(what);
+  }
+  void report(int d, int b0, int b1) {
+    int big = 0;
+    double fl = 0.0;
+    for (int i = b0; i < b1; ++i) {
+      const int f = T.by_depth[(size_t)d][(size_t)i];
+      big = std::max(big, T.fs(f));
+      const double p = T.np[(size_t)f], q = T.nb[(size_t)f];
+      fl += 2.0 / 3.0 * p * p * p + 2.0 * p * p * q + 2.0 * p * q * q;
+    }
+    char what[96];
+    snprintf(what, sizeof what, "level %d: %d fronts, max %d, %.3g LU flops", d, b1 - b0, big, fl * ZM * ZM);
+    timer.lap(what);
+  }
+
   // levels dbot .. dtop (bottom-up) of the fronts with ids lo..hi.  children_saved: the children of
   // level plan.cut - 1 are subtree roots, already compacted, their Schur complements in the cut buffer
-  auto process = [&](int lo, int hi, int dtop, int dbot, bool children_saved) {
+  void process(int lo, int hi, int dtop, int dbot, bool children_saved) {
     int prepared_level = -1;  // the level whose region stream `aux` has been told to prepare
     int64_t prepared_extent = 0;
     for (int d = dbot; d >= dtop; --d) {
@@ -1630,19 +1486,9 @@ mf::Factors *mf_factor_t(std::shared_ptr<const mf::Tree> tree, const int *d_Ap, 
       int64_t extent = prepared_extent;
       if (prepared_level == d) SPL_HIP(hipStreamWaitEvent(s, ev.prepared, 0));
       else extent = prepare_level(d, lo, hi, s);
-      // ... and the Schur complements of the children, one child slot after the other (two children
-      // of a parent may touch the same entry: a fixed order keeps the sums reproducible)
+      // ... and the Schur complements of the children
       if (d + 1 < nd) {
-        for (int sl = 0; sl < 2; ++sl) {
-          int c0, c1;
-          range_of(F.lp->h_child[sl][(size_t)d], lo, hi, c0, c1);
-          if (c1 == c0) continue;
-          const int64_t tc = F.lp->h_ctile[sl][(size_t)d][(size_t)c1] - F.lp->h_ctile[sl][(size_t)d][(size_t)c0];
-          if (tc > 0)
-            hipLaunchKernelGGL(extend_add_kernel<Z>, dim3((unsigned)tc), dim3(256), 0, s,
-                               F.lp->child_lists[sl][(size_t)d].get() + c0, F.lp->ctile[sl][(size_t)d].get() + c0, c1 - c0,
-                               F.view);
-        }
+        extend_add(d, lo, hi);
         // the children are done with: keep their panels, their region is free again (subtree
         // roots were compacted when their subtree finished)
         if (overlap) {
@@ -1656,127 +1502,78 @@ mf::Factors *mf_factor_t(std::shared_ptr<const mf::Tree> tree, const int *d_Ap, 
         SPL_HIP(hipEventRecord(ev.prepared, aux));
         prepared_level = d - 1;
       }
-      // small fronts: one launch, one workgroup each; large fronts: the multi-launch blocked
-      // factorisation, independent fronts spread over side streams
       SPL_HIP(hipStreamSynchronize(s));
-      if (timing) {
-        double ea = 0.0, cp = 0.0;  // entries the extend-add moves, entries of the children's panels
-        if (d + 1 < nd)
-          for (int sl = 0; sl < 2; ++sl) {
-            int c0, c1;
-            range_of(F.lp->h_child[sl][(size_t)d], lo, hi, c0, c1);
-            for (int i = c0; i < c1; ++i) {
-              const int c = F.lp->h_child[sl][(size_t)d][(size_t)i];
-              const double q = T.nb[(size_t)c], pp = T.np[(size_t)c];
-              ea += symmetric ? q * (q + 1) / 2 : q * q;
-              cp += pp * (pp + 2 * q);
-            }
-          }
-        char what[96];
-        snprintf(what, sizeof what, "level %d: assembly (zero %.0f, extend-add %.0f, panels %.0f MB)", d, ZM * extent * 8e-6,
-                 ZM * ea * 24e-6, ZM * cp * 16e-6);
-        lap(what);
-      }
-      int s0, s1;
-      range_of(F.lp->h_small[(size_t)d], lo, hi, s0, s1);
-      if (s1 > s0)
-        hipLaunchKernelGGL(front_factor_kernel<Z>, dim3((unsigned)(s1 - s0)), dim3(256), Z ? kFrontLdsZ : 2 * kTileBytes, s,
-                           F.lp->small_lists[(size_t)d].get() + s0, F.view, F.invs.get(), singular.get());
-      // medium fronts: lockstep over block steps, one flat launch per phase and step
-      {
-        int count = 0, steps = 0;
-        const int *dl = nullptr;
-        const int64_t *dp = nullptr;
-        const std::vector<int64_t> *hpp = nullptr;
-        if (b0 == 0 && b1 == (int)T.by_depth[(size_t)d].size()) {  // the whole level: from the plan
-          const mf::LevelPlan::Mid &M = F.lp->mid[(size_t)d];
-          count = M.count;
-          steps = M.steps;
-          dl = M.list.get();
-          dp = M.d.get();
-          hpp = &M.h;
-        } else {  // a subtree of a cut tree
-          std::vector<int> mid;
-          std::vector<int64_t> pre;
-          mid_fronts_of(T.by_depth[(size_t)d], b0, b1, mid, steps, pre);
-          count = (int)mid.size();
-          if (count > 0) {
-            mid_lists.emplace_back();
-            mid_prefixes.emplace_back();
-            upload_vec(mid_lists.back(), mid, s);
-            upload_vec(mid_prefixes.back(), pre, s);
-            staged.push_back(std::move(mid));
-            staged64.push_back(std::move(pre));
-            dl = mid_lists.back().get();
-            dp = mid_prefixes.back().get();
-            hpp = &staged64.back();
-          }
-        }
-        if (count > 0) {
-          const std::vector<int64_t> &hp = *hpp;
-          hipLaunchKernelGGL(mid_diag_kernel<Z>, dim3((unsigned)count), dim3(256),
-                             Z ? kDiagLdsZ : kTileBytes + 2 * NB * sizeof(double), s, dl, F.view, F.invs.get(), singular.get());
-          for (int st = 0; st < steps; ++st) {
-            const size_t base = ((size_t)st * 2) * (size_t)(count + 1);
-            const int64_t nt = hp[base + (size_t)count], nu = hp[base + (size_t)(count + 1) + (size_t)count];
-            if (nt > 0)
-              hipLaunchKernelGGL(mid_trsm_kernel<Z>, dim3((unsigned)nt), dim3(256), Z ? kTrsmLdsZ : kTrsmLds, s, dl,
-                                 dp + base, count, st, F.view, F.invs.get());
-            if (nu > 0)
-              hipLaunchKernelGGL(mid_update_kernel<Z>, dim3((unsigned)(nu + count)), dim3(256),
-                                 Z ? kDiagLdsZ : kTileBytes + 2 * NB * sizeof(double), s, dl,
-                                 dp + base + (size_t)(count + 1), count, st, F.view, F.invs.get(), singular.get(),
-                                 mid_paired ? 1 : 0);
-          }
-        }
-      }
-      int turn = 0;
-      for (int i = b0; i < b1; ++i) {
-        const int f = T.by_depth[(size_t)d][(size_t)i];
-        if (T.np[(size_t)f] == 0 || T.fs(f) <= mid_limit) continue;
-        const size_t plane = Z ? (size_t)(((int64_t)T.ld[(size_t)f] * std::max(T.fs(f), 1) + 15) / 16 * 16) : 0;
-        const Band b = dense_view(region_of(d) + (size_t)ZM * (size_t)plan.foff[(size_t)f], T.fs(f), T.ld[(size_t)f],
-                                  symmetric ? 1 : 0, plane, pivot ? 1 : diag_form_without_interchanges(),
-                                  pivot && d_rscale ? d_rscale + T.p0[(size_t)f] : nullptr);
-        const int lane = turn++ % kStreams;
-        factor_loop<Z>(b, T.np[(size_t)f], F.invs.get() + (size_t)ZM * (size_t)T.ioff[(size_t)f], singular.get(), side[lane],
-                       side[kStreams + lane]);
-      }
-      if (turn > 0)
-        for (int i = 0; i < kStreams && i < turn; ++i) SPL_HIP(hipStreamSynchronize(side[i]));
-      if (timing) {
-        int big = 0;
-        double fl = 0.0;
-        for (int i = b0; i < b1; ++i) {
-          const int f = T.by_depth[(size_t)d][(size_t)i];
-          big = std::max(big, T.fs(f));
-          const double p = T.np[(size_t)f], q = T.nb[(size_t)f];
-          fl += 2.0 / 3.0 * p * p * p + 2.0 * p * p * q + 2.0 * p * q * q;
-        }
-        char what[96];
-        snprintf(what, sizeof what, "level %d: %d fronts, max %d, %.3g LU flops", d, b1 - b0, big, fl * ZM * ZM);
-        lap(what);
-      }
+      if (timer.on) report(d, lo, hi, extent);
+      factor_small(d, lo, hi);
+      factor_mid(d, b0, b1);
+      factor_large(d, b0, b1);
+      if (timer.on) report(d, b0, b1);
     }
     if (overlap) SPL_HIP(hipStreamSynchronize(aux));  // the panels of the last level but one are in the arena
-  };
-  if (plan.cut == 0) {
-    process(0, nf - 1, 0, nd - 1, false);
-    compact_fronts(0, 0, nf - 1, s);
-  } else {
-    for (int r : plan.roots) {  // one subtree after the other; its root's Schur complement is saved
-      process(plan.first[(size_t)r], r, plan.cut, nd - 1, false);
-      compact_fronts(plan.cut, r, r, s);
-      const int nb = T.nb[(size_t)r];
-      const int64_t ntile = (int64_t)((nb + 63) / 64) * ((nb + 3) / 4);
-      if (ntile > 0) hipLaunchKernelGGL(save_cb_kernel<Z>, dim3((unsigned)ntile), dim3(256), 0, s, r, F.view);
-      SPL_HIP(hipStreamSynchronize(s));
-    }
-    process(0, nf - 1, 0, plan.cut - 1, true);  // the top of the tree
-    compact_fronts(0, 0, nf - 1, s);
   }
-  SPL_HIP(hipStreamSynchronize(s));
-  lap("levels");
+
+  void run() {  // the whole tree, or the subtrees of a cut tree and then its top
+    if (plan.cut == 0) {
+      process(0, nf - 1, 0, nd - 1, false);
+    } else {
+      for (int r : plan.roots) {  // one subtree after the other; its root's Schur complement is saved
+        process(plan.first[(size_t)r], r, plan.cut, nd - 1, false);
+        compact_fronts(plan.cut, r, r, s);
+        const int nb = T.nb[(size_t)r];
+        const int64_t ntile = (int64_t)((nb + 63) / 64) * ((nb + 3) / 4);
+        if (ntile > 0) hipLaunchKernelGGL(save_cb_kernel<Z>, dim3((unsigned)ntile), dim3(256), 0, s, r, F.view);
+        SPL_HIP(hipStreamSynchronize(s));
+      }
+      process(0, nf - 1, 0, plan.cut - 1, true);  // the top of the tree
+    }
+    compact_fronts(0, 0, nf - 1, s);
+    SPL_HIP(hipStreamSynchronize(s));
+  }
+};
+
+// numeric factorisation of P A P^T
+template <bool Z>
+mf::Factors *mf_factor_t(std::shared_ptr<const mf::Tree> tree, FactorInput in, hipStream_t s) {
+  constexpr int ZM = Z ? 2 : 1;
+  if (in.symmetric) in.pivot = false;  // L D L^T needs symmetric interchanges
+  const mf::Tree &T = *tree;
+  const mf::FactorKnobs knobs = mf::read_factor_knobs();
+  PhaseTimer timer{knobs.timing};
+  std::unique_ptr<mf::Factors> Fp(new mf::Factors());
+  mf::Factors &F = *Fp;
+  F.tree = tree;
+  F.zm = ZM;
+  const mf::Plan plan = plan_transient(T, ZM, knobs);
+  F.D = device_tree_for(T, s);
+  upload_vec(F.d_foff, plan.foff, s);
+  upload_vec(F.d_cboff, plan.cboff, s);
+  timer.lap("tree uploads (queued)");
+  F.arena.alloc((size_t)ZM * (size_t)T.panel_elems);
+  F.invs.alloc((size_t)ZM * (size_t)T.inv_elems);
+  DBuf<double> region0((size_t)ZM * (size_t)plan.region_elems[0]), region1((size_t)ZM * (size_t)plan.region_elems[1]),
+      cutbuf((size_t)ZM * (size_t)plan.cut_elems);  // transient
+  timer.lap("hipMalloc");
+  F.view = make_tree_view(*F.D);
+  F.view.foff = F.d_foff.get();
+  F.view.region[0] = region0.get();
+  F.view.region[1] = region1.get();
+  F.view.arena = F.arena.get();
+  F.view.cboff = F.d_cboff.get();
+  F.view.cut = cutbuf.get();
+  F.view.sym = in.symmetric ? 1 : 0;
+  F.view.zm = ZM;
+  F.view.piv = in.pivot ? 1 : diag_form_without_interchanges();
+  F.view.rscale = in.pivot ? in.d_rscale : nullptr;
+  bool built = false;
+  F.lp = level_plan_for(*F.D, T, knobs, s, &built);
+  timer.lap(built ? "level lists (built)" : "level lists (from the tree's cache)");
+  DBuf<int> singular(1);
+  SPL_HIP(hipMemsetAsync(singular.get(), 0, sizeof(int), s));
+  FactorWalk<Z>::set_attributes();
+  F.make_streams();
+  FactorWalk<Z> walk{T, knobs, plan, in, F, {region0.get(), region1.get()}, singular.get(), s, timer};
+  walk.run();
+  timer.lap("levels");
   SPL_HIP(hipMemcpyAsync(&F.singular, singular.get(), sizeof(int), hipMemcpyDeviceToHost, s));
   SPL_HIP(hipStreamSynchronize(s));
   SPL_HIP(hipGetLastError());
@@ -1791,15 +1588,15 @@ mf::Factors *mf_factor_t(std::shared_ptr<const mf::Tree> tree, const int *d_Ap, 
 mf::Factors *mf_factor(std::shared_ptr<const mf::Tree> tree, const int *d_Ap, const int *d_Ai, const double *d_Ax,
                        const int *d_Rp, const int *d_Rj, const double *d_Rx, const int *d_perm, const int *d_inv,
                        hipStream_t s, bool symmetric, bool zfront, bool pivot, const double *d_rscale) {
-  return zfront ? mf_factor_t<true>(tree, d_Ap, d_Ai, d_Ax, d_Rp, d_Rj, d_Rx, d_perm, d_inv, s, symmetric, pivot, d_rscale)
-                : mf_factor_t<false>(tree, d_Ap, d_Ai, d_Ax, d_Rp, d_Rj, d_Rx, d_perm, d_inv, s, symmetric, pivot, d_rscale);
+  const FactorInput in{d_Ap, d_Ai, d_Ax, d_Rp, d_Rj, d_Rx, d_perm, d_inv, symmetric, pivot, d_rscale};
+  return zfront ? mf_factor_t<true>(tree, in, s) : mf_factor_t<false>(tree, in, s);
 }
 
 // NR columns (c + r * stride) through the tree: up with L (or U^T), down with U (or L^T).  Per level:
 // the fronts of up to big_solve rows by one workgroup each, the larger ones in lockstep — one flat
 // launch per super-block step over all of them (Factors::BigLevel).
 template <int MODE, int NR, bool Z = false>
-static void launch_big_super(const mf::Factors &F, const mf::Factors::BigLevel &B, int kind, int step, double *work,
+static void launch_big_super(const mf::Factors &F, const mf::Factors::BigLevel &B, mf::BigLevel::Grid kind, int step, double *work,
                              double *zbuf, hipStream_t s, int pivots_only = 0, double *x = nullptr, size_t xstride = 0) {
   constexpr size_t lds = (size_t)((SB + 2) * NB + solve_waves<NR>() * 64) * NR * sizeof(double);
   static std::atomic<uint64_t> attr_set{0};  // one mask per instantiation, one bit per device
@@ -1815,7 +1612,7 @@ static void launch_big_super(const mf::Factors &F, const mf::Factors::BigLevel &
 }
 
 template <int MODE, int NR, bool Z = false>
-static void launch_big_pipe(const mf::Factors &F, const mf::Factors::BigLevel &B, int kind, double *work, double *zbuf,
+static void launch_big_pipe(const mf::Factors &F, const mf::Factors::BigLevel &B, mf::BigLevel::Grid kind, double *work, double *zbuf,
                             double *cbuf, hipStream_t s, double *x = nullptr, size_t xstride = 0) {
   constexpr size_t lds = (size_t)((SB + 2) * NB + solve_waves<NR>() * 64) * NR * sizeof(double);
   static std::atomic<uint64_t> attr_set{0};  // one mask per instantiation, one bit per device
@@ -1852,9 +1649,9 @@ static void build_chain_t(const mf::Factors &F, hipStream_t s) {
   Cn.levels.assign((size_t)nd, mf::Factors::Chain::Level());
   Cn.h.clear();
   for (int d = 0; d < nd; ++d) {
-    std::vector<int> large;  // (the order of LevelPlan::BigLevel::list)
+    std::vector<int> large;  // (the order of mf::BigLevel::list)
     for (int f : T.by_depth[(size_t)d])
-      if (T.fs(f) > F.lp->big_solve && T.np[(size_t)f] > 0) large.push_back(f);
+      if (T.fs(f) > F.lp->t.big_solve && T.np[(size_t)f] > 0) large.push_back(f);
     mf::Factors::Chain::Level &L = Cn.levels[(size_t)d];
     L.count = (int)large.size();
     if (L.count == 0) continue;
@@ -1948,7 +1745,7 @@ static void launch_big_chain(const mf::Factors &F, int depth, double *work, doub
                              size_t xstride = 0) {
   const mf::Factors::Chain &Cn = MODE >= 2 ? F.chain_t : F.chain;
   const mf::Factors::Chain::Level &L = Cn.levels[(size_t)depth];
-  const mf::Factors::BigLevel &B = F.lp->big[(size_t)depth];
+  const mf::Factors::BigLevel &B = F.lp->dev[(size_t)depth].big;
   constexpr int cls = NR >= 16 ? 1 : 0;  // (workgroups of 8 wavefronts: grids of their own)
   // LDS: the bulk groups' v, res and partial sums; levels without bulk groups (one block per front): the lead groups' u
   const size_t lds_bulk = (size_t)(Cn.span + NB + solve_waves<NR>() * 64) * NR * sizeof(double);
@@ -1990,17 +1787,19 @@ struct SolveLevel {
   const mf::Factors::BigLevel *big;
   int depth;
 };
-static SolveLevel whole_level(const mf::LevelPlan &lp, int d, int nd) {
+static SolveLevel whole_level(const mf::LevelPlan &lp, int d) {
+  const mf::LevelTables::Level &H = lp.t.levels[(size_t)d];
+  const mf::LevelPlan::Level &V = lp.dev[(size_t)d];
   SolveLevel L;
   L.depth = d;
-  L.solve_list = lp.solve_lists[(size_t)d].get();
-  L.solve_count = lp.solve_counts[(size_t)d];
-  L.child_maxnb = d + 1 < nd ? std::max(lp.child_maxnb[0][(size_t)d], lp.child_maxnb[1][(size_t)d]) : 0;
+  L.solve_list = V.solve.get();
+  L.solve_count = (int)H.solve.size();
+  L.child_maxnb = std::max(H.child_maxnb[0], H.child_maxnb[1]);
   for (int sl = 0; sl < 2; ++sl) {
-    L.child_list[sl] = d + 1 < nd ? lp.child_lists[sl][(size_t)d].get() : nullptr;
-    L.child_count[sl] = d + 1 < nd ? lp.child_counts[sl][(size_t)d] : 0;
+    L.child_list[sl] = V.child[sl].get();  // (null below the deepest level: no children)
+    L.child_count[sl] = (int)H.child[sl].size();
   }
-  L.big = &lp.big[(size_t)d];
+  L.big = &V.big;
   return L;
 }
 // NR columns through the tree, up with L (or U^T) and down with U (or L^T), level by level on the caller's stream.
@@ -2019,6 +1818,7 @@ static void solve_columns_on_tree(const mf::Factors &F, double *c, size_t stride
   const int nd = T.maxdepth + 1;
   double *invs = F.invs.get();
   constexpr int FWD = TRANS ? 2 : 0, BWD = TRANS ? 3 : 1;
+  using Grid = mf::BigLevel::Grid;
   const bool timing = getenv("SPL_MF_TIMING") != nullptr;  // per-level times on stderr (diagnostic; the walk is then not split)
   auto t_last = std::chrono::steady_clock::now();
   auto lap = [&](const char *dir, int d) {
@@ -2032,15 +1832,15 @@ static void solve_columns_on_tree(const mf::Factors &F, double *c, size_t stride
     double bytes = 0.0;
     int maxnp = 0;
     for (int f : T.by_depth[(size_t)d]) {
-      const bool is_big = T.fs(f) > F.lp->big_solve && T.np[(size_t)f] > 0;
+      const bool is_big = T.fs(f) > F.lp->t.big_solve && T.np[(size_t)f] > 0;
       if (is_big != large) continue;
       const double np = T.np[(size_t)f], nb = T.fs(f) - T.np[(size_t)f];
       bytes += (np * np * 0.5 + np * nb) * 8.0 * F.zm;
       maxnp = std::max(maxnp, T.np[(size_t)f]);
     }
     fprintf(stderr, "[mf_solve] %s level %2d: %4d large of %6zu fronts %8.2f ms  %8.1f MB %6.2f TB/s  steps %d max np %d\n", dir, d,
-            F.lp->big[(size_t)d].count, T.by_depth[(size_t)d].size(), ms, bytes * 1e-6, ms > 0 ? bytes / ms * 1e-9 : 0.0,
-            large ? F.lp->big[(size_t)d].steps : 0, maxnp);
+            F.lp->dev[(size_t)d].big.count, T.by_depth[(size_t)d].size(), ms, bytes * 1e-6, ms > 0 ? bytes / ms * 1e-9 : 0.0,
+            large ? F.lp->dev[(size_t)d].big.steps : 0, maxnp);
     t_last = now;
   };
   // (split: SPL_MF_SPLIT_FWD=0 restores the steps over all fs rows of rounds 1 - 3; pipe: SPL_MF_PIPE=0 restores one
@@ -2074,10 +1874,10 @@ static void solve_columns_on_tree(const mf::Factors &F, double *c, size_t stride
       // bulk groups' reload of the solved super block costs more than the overlap gains: FEAST 80^3 solve stage 2.95 -> 3.05 s)
       const bool pipe = pipe_on && (TRANS || pivots_only) && NR <= 2;
       if (chain_on && (TRANS || pivots_only)) launch_big_chain<FWD, NR, Z>(F, L.depth, work, zbuf, q);
-      else if (pipe) launch_big_pipe<FWD, NR, Z>(F, B, 13, work, zbuf, cbuf, q);
+      else if (pipe) launch_big_pipe<FWD, NR, Z>(F, B, Grid::pipe_fwd, work, zbuf, cbuf, q);
       else
-        for (int k = 0; k < B.steps; ++k) launch_big_super<FWD, NR, Z>(F, B, (TRANS || pivots_only) ? 1 : 0, k, work, zbuf, q, pivots_only ? 1 : 0);
-      if (pivots_only && B.total(10) > 0) {
+        for (int k = 0; k < B.steps; ++k) launch_big_super<FWD, NR, Z>(F, B, (TRANS || pivots_only) ? Grid::fwd_t : Grid::fwd, k, work, zbuf, q, pivots_only ? 1 : 0);
+      if (pivots_only && B.total(Grid::fwd_gemv) > 0) {
         constexpr size_t lds = (size_t)std::max(kGemvChunk, gemv_waves<NR>() * 64) * NR * sizeof(double);
         static std::atomic<uint64_t> attr_set{0};  // one mask per instantiation, one bit per device
         if (first_use_on_this_device(attr_set)) {
@@ -2085,15 +1885,15 @@ static void solve_columns_on_tree(const mf::Factors &F, double *c, size_t stride
                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
           mark_used_on_this_device(attr_set);
         }
-        hipLaunchKernelGGL(HIP_KERNEL_NAME(big_gemv_chunk_kernel<NR, Z, true>), dim3(B.total(10)), dim3(gemv_waves<NR>() * 64), lds, q,
-                           B.list.get(), B.prefix(10), B.count, F.view, work, zbuf, B.prefix(12), scr);
-        if (B.total(11) > 0)
-          hipLaunchKernelGGL(HIP_KERNEL_NAME(big_gemv_reduce_kernel<NR, true>), dim3(B.total(11)), dim3(256), 0, q, B.list.get(),
-                             B.prefix(11), B.count, F.view, work, zbuf, B.prefix(12), scr);
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(big_gemv_chunk_kernel<NR, Z, true>), dim3(B.total(Grid::fwd_gemv)), dim3(gemv_waves<NR>() * 64), lds, q,
+                           B.list.get(), B.prefix(Grid::fwd_gemv), B.count, F.view, work, zbuf, B.prefix(Grid::fwd_gemv_offsets), scr);
+        if (B.total(Grid::fwd_gemv_reduce) > 0)
+          hipLaunchKernelGGL(HIP_KERNEL_NAME(big_gemv_reduce_kernel<NR, true>), dim3(B.total(Grid::fwd_gemv_reduce)), dim3(256), 0, q, B.list.get(),
+                             B.prefix(Grid::fwd_gemv_reduce), B.count, F.view, work, zbuf, B.prefix(Grid::fwd_gemv_offsets), scr);
       }
-      if (TRANS && B.total(3) > 0)
-        hipLaunchKernelGGL(HIP_KERNEL_NAME(big_boundary_t_kernel<NR, Z>), dim3(B.total(3)), dim3(256), 0, q, B.list.get(),
-                           B.prefix(3), B.count, F.view, work, zbuf);
+      if (TRANS && B.total(Grid::boundary_t) > 0)
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(big_boundary_t_kernel<NR, Z>), dim3(B.total(Grid::boundary_t)), dim3(256), 0, q, B.list.get(),
+                           B.prefix(Grid::boundary_t), B.count, F.view, work, zbuf);
     }
   };
   // ... and on the way down
@@ -2103,7 +1903,7 @@ static void solve_columns_on_tree(const mf::Factors &F, double *c, size_t stride
                          dim3(solve_threads<NR>()), 0, q, L.solve_list, F.view, invs, work, c, stride);
     const mf::Factors::BigLevel &B = *L.big;
     if (B.count > 0) {
-      if (B.total(4) > 0) {  // (fronts with a boundary; its part of the solution is read from x inside the product)
+      if (B.total(Grid::gather) > 0) {  // (fronts with a boundary; its part of the solution is read from x inside the product)
         {
           constexpr size_t lds = (size_t)(TRANS ? kGemvChunk : std::max(kGemvChunk, gemv_waves<NR>() * 64)) * NR * sizeof(double);
           static std::atomic<uint64_t> attr_set{0};  // one mask per instantiation, one bit per device
@@ -2117,22 +1917,22 @@ static void solve_columns_on_tree(const mf::Factors &F, double *c, size_t stride
             mark_used_on_this_device(attr_set);
           }
           if (TRANS)
-            hipLaunchKernelGGL(HIP_KERNEL_NAME(big_gemv_chunk_t_kernel<NR, Z>), dim3(B.total(7)), dim3(gemv_waves<NR>() * 64), lds,
-                               q, B.list.get(), B.prefix(7), B.count, F.view, work, zbuf, B.prefix(9), scr, (const double *)c, stride);
+            hipLaunchKernelGGL(HIP_KERNEL_NAME(big_gemv_chunk_t_kernel<NR, Z>), dim3(B.total(Grid::gemv)), dim3(gemv_waves<NR>() * 64), lds,
+                               q, B.list.get(), B.prefix(Grid::gemv), B.count, F.view, work, zbuf, B.prefix(Grid::gemv_offsets), scr, (const double *)c, stride);
           else
-            hipLaunchKernelGGL(HIP_KERNEL_NAME(big_gemv_chunk_kernel<NR, Z>), dim3(B.total(7)), dim3(gemv_waves<NR>() * 64), lds, q,
-                               B.list.get(), B.prefix(7), B.count, F.view, work, zbuf, B.prefix(9), scr, (const double *)c, stride);
-          if (B.total(8) > 0)
-            hipLaunchKernelGGL(HIP_KERNEL_NAME(big_gemv_reduce_kernel<NR>), dim3(B.total(8)), dim3(256), 0, q, B.list.get(),
-                               B.prefix(8), B.count, F.view, work, zbuf, B.prefix(9), scr);
+            hipLaunchKernelGGL(HIP_KERNEL_NAME(big_gemv_chunk_kernel<NR, Z>), dim3(B.total(Grid::gemv)), dim3(gemv_waves<NR>() * 64), lds, q,
+                               B.list.get(), B.prefix(Grid::gemv), B.count, F.view, work, zbuf, B.prefix(Grid::gemv_offsets), scr, (const double *)c, stride);
+          if (B.total(Grid::gemv_reduce) > 0)
+            hipLaunchKernelGGL(HIP_KERNEL_NAME(big_gemv_reduce_kernel<NR>), dim3(B.total(Grid::gemv_reduce)), dim3(256), 0, q, B.list.get(),
+                               B.prefix(Grid::gemv_reduce), B.count, F.view, work, zbuf, B.prefix(Grid::gemv_offsets), scr);
         }
       }
       // the pivot block alone; columns of Z / W are fs apart
       // (the solved pivots go to x from inside these steps: round 4 had a scatter launch per level behind them)
       if (chain_on) launch_big_chain<BWD, NR, Z>(F, L.depth, work, zbuf, q, c, stride);
-      else if (pipe_on && NR <= 2) launch_big_pipe<BWD, NR, Z>(F, B, 14, work, zbuf, cbuf, q, c, stride);
+      else if (pipe_on && NR <= 2) launch_big_pipe<BWD, NR, Z>(F, B, Grid::pipe_bwd, work, zbuf, cbuf, q, c, stride);
       else
-        for (int k = 0; k < B.steps; ++k) launch_big_super<BWD, NR, Z>(F, B, 2, k, work, zbuf, q, 0, c, stride);
+        for (int k = 0; k < B.steps; ++k) launch_big_super<BWD, NR, Z>(F, B, Grid::bwd, k, work, zbuf, q, 0, c, stride);
     }
   };
 
@@ -2141,7 +1941,7 @@ static void solve_columns_on_tree(const mf::Factors &F, double *c, size_t stride
   hipLaunchKernelGGL(HIP_KERNEL_NAME(solve_init_kernel<NR, Z>), dim3((unsigned)T.nfronts, 8), dim3(256), 0, s, F.view, c, stride,
                      work);
   for (int d = nd - 1; d >= 0; --d) {
-    const SolveLevel L = whole_level(*F.lp, d, nd);
+    const SolveLevel L = whole_level(*F.lp, d);
     if (!timing) { up_level(L, gscr, s); continue; }
     // (timed: the one-workgroup fronts and the large ones apart, as the level table of profiles/ wants them)
     SolveLevel small = L, large = L;
@@ -2155,7 +1955,7 @@ static void solve_columns_on_tree(const mf::Factors &F, double *c, size_t stride
     lap("up large  ", d);
   }
   for (int d = 0; d < nd; ++d) {
-    const SolveLevel L = whole_level(*F.lp, d, nd);
+    const SolveLevel L = whole_level(*F.lp, d);
     if (!timing) { down_level(L, gscr, s); continue; }
     SolveLevel small = L, large = L;
     static const mf::Factors::BigLevel none;
@@ -2179,11 +1979,11 @@ void mf_solve(const mf::Factors *Fp, int sys, double *d_c, int k, size_t stride,
   // side is two real columns of the work matrices: one at a time, or eight together (= kSolveGroup columns of the caller)
   constexpr int kGroupZ = 8;
   const int nr = z ? (k == 1 ? 2 : 2 * kGroupZ) : (k == 1 ? 1 : kSolveGroup);
-  const size_t elems = ((size_t)T.work_elems * 3 + (size_t)F.lp->gemv_scratch) * (size_t)nr;  // work, z and carry matrices of all fronts, scratch
+  const size_t elems = ((size_t)T.work_elems * 3 + (size_t)F.lp->t.gemv_scratch) * (size_t)nr;  // work, z and carry matrices of all fronts, scratch
   // every walk of this call on stream q, with the work matrices at `base`
   auto run = [&](double *base, hipStream_t q) {
     double *wk = base, *zb = base + (size_t)T.work_elems * nr, *gs = zb + (size_t)T.work_elems * nr;
-    double *cb = gs + (size_t)F.lp->gemv_scratch * nr;
+    double *cb = gs + (size_t)F.lp->t.gemv_scratch * nr;
     if (z) {
       if (k == 1) {
         if (sys == 0) solve_columns_on_tree<false, 2, true>(F, d_c, stride, wk, zb, gs, cb, q);
