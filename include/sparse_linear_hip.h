@@ -532,6 +532,69 @@ int spl_matrix_spmm_dev(void *H, const double *d_B, double *d_C, int k, int accu
  * bytes); SPL_ERROR_dimension_mismatch (k > 1 and ldx < ncols or ldy < nrows_local). */
 int spl_matrix_spmv_many_dev(void *H, int k, const double *d_X, int64_t ldx, double *d_Y, int64_t ldy,
                              int accumulate, void *stream);
+/* ---- sparse triangular solves on handles (csrc/trisolve.hip, csrc/tri_levels.hpp) ----------------------------------
+ * T x = b, T^T x = b or T^H x = b for k right-hand sides in device memory, T a triangle of a whole square handle, real
+ * or complex: the kernel of Gauss-Seidel / SOR sweeps and of applying an incomplete or externally computed
+ * factorisation, between spl_matrix_band (tril / triu) and spl_matrix_spmv_many_dev.
+ *   uplo  SPL_TRI_lower: the entries of A with j <= i;  SPL_TRI_upper: those with j >= i.  Entries on the other side of
+ *         the diagonal are not read: A need not be triangular (a Gauss-Seidel sweep passes the full matrix).
+ *   diag  SPL_DIAG_stored: d_i is the stored a_ii, 0 for a row without one;  SPL_DIAG_unit: d_i = 1, a stored diagonal
+ *         is ignored.
+ *   op    SPL_OP_n: T x = b;  SPL_OP_t: T^T x = b;  SPL_OP_h: T^H x = b (on a real handle SPL_OP_t).
+ * Arithmetic, the contract of spl_matrix_spmv_many_dev: for SPL_OP_n row i computes
+ *     acc = b_i;   acc = acc - t_ij * x_j  over the stored off-diagonal entries of row i of T in ASCENDING column order;
+ *     x_i = acc / d_i   (unit diagonal: x_i = acc, no division)
+ *   with every real operation separately rounded and the division a correctly rounded IEEE division (no stored
+ *   reciprocal).  SPL_OP_t / _h run the same loop over the rows of the order-preserving transpose of T (ascending in
+ *   the original row index), conjugated first for _h.  Complex handles use Data.Complex's arithmetic:
+ *   (a :+ b)(c :+ d) = (a c - b d) :+ (a d + b c), componentwise -, and the scaled quotient
+ *     (x :+ y) / (x' :+ y'):  k = -max(e(x'), e(y')), e the frexp exponent and e(0) = 0;  x'' = ldexp(x', k),
+ *     y'' = ldexp(y', k);  d = x' x'' + y' y'';  (x x'' + y y'') / d :+ (y x'' - x y'') / d.
+ *   The result depends on neither the level schedule nor k nor any launch shape: it is the serial loop bit for bit, for
+ *   rows of any length.  A zero or missing diagonal gives what IEEE arithmetic gives (inf, NaN); the solve never refuses.
+ * spl_trisolve_analyze: the object is allocated by the callee, written through T, carries its own magic word and is
+ *   freed by spl_trisolve_free (idempotent, any thread).  H is borrowed: the object keeps its own device copy of the
+ *   triangle, permuted so that the rows of a level are contiguous, and its tables, so H may be freed on return.  The
+ *   pattern is downloaded once and the levels, level(i) = 1 + max level(j) over the off-diagonal entries of row i,
+ *   computed in one pass on the host; the call runs on the default stream and synchronises.  The launch plan cuts the
+ *   levels into segments: a level of at least SPL_TRSV_SMALL_ROWS rows (default 64) is one launch with a group of
+ *   lanes per row, a run of smaller levels one launch of a single workgroup that walks at most
+ *   SPL_TRSV_SEGMENT_LEVELS levels (default 1024) with a workgroup barrier between them.  Both environment variables
+ *   are read once per analysis and clamped (1 ... 2^30, 1 ... 65536).  No kernel waits for another workgroup.
+ *   Returns SPL_OK, or SPL_WARNING_singular_matrix (1, the object exists) when diag is SPL_DIAG_stored and some d_i is
+ *   missing or exactly zero (complex: both parts).  Errors, checked in this order before the device is touched:
+ *   SPL_ERROR_invalid_handle (H is NULL or no matrix handle); SPL_ERROR_argument_missing (T is NULL or a code is
+ *   unknown; otherwise *T = NULL first); SPL_ERROR_dimension_mismatch (not square); SPL_ERROR_invalid_matrix (a
+ *   row-block handle, or one without 32-bit row pointers, nnz >= 2^31); then SPL_ERROR_device without a GPU.
+ * spl_trisolve_solve_dev: d_B and d_X are COLUMN-major device arrays with leading dimensions ldb, ldx counted in
+ *   entries (a double, or a packed pair), the layout of spl_matrix_spmv_many_dev.  d_X == d_B with ldx == ldb (in
+ *   place) is allowed; any other overlap is undefined.  Entries beyond row n of a column are neither read nor written.
+ *   The kernels are enqueued on `stream` and the call does not synchronise — except the FIRST call with SPL_OP_t or
+ *   SPL_OP_h, which builds the transposed image and its schedule on the default stream and synchronises; later calls
+ *   do not.  The right-hand sides go through in groups of 8; every column has the bits of a single-column solve.
+ *   Concurrent solves on one object from several host threads are safe (no scratch; the lazy build runs under a lock).
+ *   Statuses: SPL_ERROR_invalid_handle (T is no such object); SPL_ERROR_n_nonpositive (k < 0); k == 0 or n == 0:
+ *   SPL_OK, nothing is touched; SPL_ERROR_argument_missing (op unknown, a pointer NULL or not aligned to an entry, 8
+ *   or 16 bytes); SPL_ERROR_dimension_mismatch (k > 1 and ldb < n or ldx < n).
+ * spl_trisolve_solve: the same with HOST arrays, n x k column-major without padding, packed complex; B == X is allowed.
+ * spl_trisolve_info: [0] n, [1] stored entries of the triangle (stored diagonals included, also with a unit diagonal),
+ *   [2] levels, [3] kernel launches one SPL_OP_n solve of up to 8 columns makes, [4] rows i with d_i missing or zero (0
+ *   with a unit diagonal), [5] longest row of the triangle (counted as [1]), [6] bytes of device memory held, [7] flags:
+ *   bit 0 complex, bit 1 upper, bit 2 unit diagonal, bit 3 a transposed image is built. */
+#define SPL_TRI_lower 0
+#define SPL_TRI_upper 1
+#define SPL_DIAG_stored 0
+#define SPL_DIAG_unit 1
+#define SPL_OP_n 0
+#define SPL_OP_t 1
+#define SPL_OP_h 2
+int spl_trisolve_analyze(void *H, int uplo, int diag, void **T);
+int spl_trisolve_solve_dev(void *T, int op, int k, const double *d_B, int64_t ldb, double *d_X, int64_t ldx,
+                           void *stream);
+int spl_trisolve_solve(void *T, int op, int k, const double *B, double *X);
+int spl_trisolve_info(void *T, int64_t info[8]);
+void spl_trisolve_free(void **T);
+
 /* select a kernel variant for spl_matrix_spmv_dev (tuning / ablation only): 0 = default
  * (whatever spl_matrix_optimize chose), 1-6 CSR-stream shapes, 7 sub-wavefront kernel, 8
  * column-blocked image, 9-11 gather cache policies, 15 sliced-ELL image, 16 column-sorted panel

@@ -34,6 +34,10 @@ SPL_MAP_negate, SPL_MAP_abs, SPL_MAP_signum, SPL_MAP_conj, SPL_MAP_real, SPL_MAP
 SPL_KEEP_nonzero, SPL_KEEP_abs_above = 0, 1
 SPL_REDUCE_abs_sum, SPL_REDUCE_abs_max = 0, 1
 SPL_NORM_one, SPL_NORM_inf, SPL_NORM_fro, SPL_NORM_max = range(4)
+# sparse triangular solves on handles (spl_trisolve_*)
+SPL_TRI_lower, SPL_TRI_upper = 0, 1
+SPL_DIAG_stored, SPL_DIAG_unit = 0, 1
+SPL_OP_n, SPL_OP_t, SPL_OP_h = 0, 1, 2
 
 
 class BackendUnavailable(RuntimeError):
@@ -145,6 +149,10 @@ def _declare(L):
         "spl_matrix_spmv_dev": [C.c_void_p, C.c_void_p, C.c_void_p, i, C.c_void_p],
         "spl_matrix_spmm_dev": [C.c_void_p, C.c_void_p, C.c_void_p, i, i, C.c_void_p],
         "spl_matrix_spmv_many_dev": [C.c_void_p, i, C.c_void_p, i64, C.c_void_p, i64, i, C.c_void_p],
+        "spl_trisolve_analyze": [C.c_void_p, i, i, c_void_pp],
+        "spl_trisolve_solve_dev": [C.c_void_p, i, i, C.c_void_p, i64, C.c_void_p, i64, C.c_void_p],
+        "spl_trisolve_solve": [C.c_void_p, i, i, c_dbl_p, c_dbl_p],
+        "spl_trisolve_info": [C.c_void_p, c_i64_p],
         "spl_matrix_set_variant": [C.c_void_p, i],
         "spl_matrix_optimize": [C.c_void_p],
         "spl_matrix_build_blocked": [C.c_void_p, i, i, i],
@@ -171,6 +179,9 @@ def _declare(L):
         fn.argtypes = args
     L.spl_matrix_free.restype = None
     L.spl_matrix_free.argtypes = [c_void_pp]
+    if hasattr(L, "spl_trisolve_free"):
+        L.spl_trisolve_free.restype = None
+        L.spl_trisolve_free.argtypes = [c_void_pp]
     if hasattr(L, "spl_peer_exchange_free"):
         L.spl_peer_exchange_free.restype = None
         L.spl_peer_exchange_free.argtypes = [c_void_pp]

@@ -1497,6 +1497,90 @@ int spl_matrix_spmv_many_dev(void *H, int k, const double *d_X, int64_t ldx, dou
   });
 }
 
+// ---- sparse triangular solves on handles (csrc/trisolve.hip) ---------------------------------------------------------
+// The analysis keeps its own permuted copy of the triangle and the level tables: H is borrowed for the call.
+int spl_trisolve_analyze(void *H, int uplo, int diag, void **T) {
+  Matrix *A = as_matrix(H);
+  if (!A) return SPL_ERROR_invalid_handle;
+  if (!T) return SPL_ERROR_argument_missing;
+  *T = nullptr;
+  if ((uplo != SPL_TRI_lower && uplo != SPL_TRI_upper) || (diag != SPL_DIAG_stored && diag != SPL_DIAG_unit))
+    return SPL_ERROR_argument_missing;
+  if (A->nrows_global != A->ncols) return SPL_ERROR_dimension_mismatch;
+  if (!whole(A) || !A->rowptr.get()) return SPL_ERROR_invalid_matrix;
+  return guarded([&]() -> int {
+    (void)current_device();
+    DeviceGuard g(A->device);
+    TriSolver *S = nullptr;
+    const int st = trisolve_analyze(A, uplo, diag, &S);
+    *T = S;
+    return st;
+  });
+}
+
+int spl_trisolve_solve_dev(void *T, int op, int k, const double *d_B, int64_t ldb, double *d_X, int64_t ldx,
+                           void *stream) {
+  TriSolver *S = as_trisolver(T);
+  if (!S) return SPL_ERROR_invalid_handle;
+  if (k < 0) return SPL_ERROR_n_nonpositive;
+  if (k == 0 || trisolve_rows(S) == 0) return SPL_OK;
+  if (op != SPL_OP_n && op != SPL_OP_t && op != SPL_OP_h) return SPL_ERROR_argument_missing;
+  if (!d_B || !d_X) return SPL_ERROR_argument_missing;
+  const uintptr_t entry = (uintptr_t)(8 * trisolve_width(S));  // the kernels load and store whole entries
+  if ((uintptr_t)d_B % entry != 0 || (uintptr_t)d_X % entry != 0) return SPL_ERROR_argument_missing;
+  if (k > 1 && (ldb < trisolve_rows(S) || ldx < trisolve_rows(S))) return SPL_ERROR_dimension_mismatch;
+  return guarded([&]() -> int {
+    DeviceGuard g(trisolve_device(S));
+    return trisolve_solve(S, op, k, d_B, ldb, d_X, ldx, as_stream(stream));
+  });
+}
+
+// host arrays, n x k column-major without padding: up, solved in place on the device, down
+int spl_trisolve_solve(void *T, int op, int k, const double *B, double *X) {
+  TriSolver *S = as_trisolver(T);
+  if (!S) return SPL_ERROR_invalid_handle;
+  if (k < 0) return SPL_ERROR_n_nonpositive;
+  if (k == 0 || trisolve_rows(S) == 0) return SPL_OK;
+  if (op != SPL_OP_n && op != SPL_OP_t && op != SPL_OP_h) return SPL_ERROR_argument_missing;
+  if (!B || !X) return SPL_ERROR_argument_missing;
+  return guarded([&]() -> int {
+    DeviceGuard g(trisolve_device(S));
+    hipStream_t s = nullptr;
+    const int64_t n = trisolve_rows(S);
+    const size_t count = (size_t)n * (size_t)k * (size_t)trisolve_width(S);
+    DBuf<double> d(count);
+    SPL_HIP(hipMemcpyAsync(d.get(), B, count * sizeof(double), hipMemcpyHostToDevice, s));
+    const int st = trisolve_solve(S, op, k, d.get(), n, d.get(), n, s);
+    if (st != SPL_OK) {
+      (void)hipStreamSynchronize(s);
+      return st;
+    }
+    SPL_HIP(hipMemcpyAsync(X, d.get(), count * sizeof(double), hipMemcpyDeviceToHost, s));
+    SPL_HIP(hipStreamSynchronize(s));
+    return SPL_OK;
+  });
+}
+
+int spl_trisolve_info(void *T, int64_t info[8]) {
+  TriSolver *S = as_trisolver(T);
+  if (!S) return SPL_ERROR_invalid_handle;
+  if (!info) return SPL_ERROR_argument_missing;
+  trisolve_info(S, info);
+  return SPL_OK;
+}
+
+void spl_trisolve_free(void **T) {
+  if (!T || !*T) return;
+  TriSolver *S = as_trisolver(*T);
+  *T = nullptr;
+  if (!S) return;
+  int prev = -1;
+  const bool have_prev = hipGetDevice(&prev) == hipSuccess;
+  (void)hipSetDevice(trisolve_device(S));  // may run on a finalizer thread with another current device
+  trisolve_delete(S);
+  if (have_prev) (void)hipSetDevice(prev);
+}
+
 // mulM on Complex Double (the reference's SPECIALIZE instance, Sparse.hs:475): one axpy_ per column of B there; here the
 // packed-complex image of A and one multi-vector product.  B and C are row-major like spl_mulm's; the kernel wants one
 // vector after the other, so both are turned on the device (the call is bounded by its copies over PCIe).

@@ -294,6 +294,19 @@ void band_handle(const Matrix *A, int64_t lo, int64_t hi, Matrix *C, hipStream_t
 void reduce_handle(const Matrix *A, int what, int axis, double *d_out, hipStream_t s);
 double norm_handle(const Matrix *A, int which, hipStream_t s);  // synchronises s
 
+// ---- sparse triangular solves on handles (trisolve.hip, tri_levels.hpp) ----------------------------------------
+struct TriSolver;
+TriSolver *as_trisolver(void *t);  // nullptr unless t carries the object's magic word
+// A: whole, square, 32-bit row pointers (the caller checked).  SPL_OK or SPL_WARNING_singular_matrix; synchronises
+int trisolve_analyze(const Matrix *A, int uplo, int diag, TriSolver **out);
+// enqueues on s; the first solve with a transposed op builds that image under the object's lock and synchronises
+int trisolve_solve(TriSolver *T, int op, int k, const double *d_B, int64_t ldb, double *d_X, int64_t ldx, hipStream_t s);
+void trisolve_info(const TriSolver *T, int64_t info[8]);
+int trisolve_device(const TriSolver *T);
+int trisolve_rows(const TriSolver *T);
+int trisolve_width(const TriSolver *T);  // doubles per entry: 1 real, 2 packed complex
+void trisolve_delete(TriSolver *T);
+
 // ---- multifrontal LU without interchanges (multifrontal.hip, mf_symbolic.hpp) ------------------
 namespace mf {
 struct Tree;

@@ -303,6 +303,61 @@ inline double norm(void *h, int which) {  // SPL_NORM_one, _inf, _fro, _max
 }
 }  // namespace Device
 
+// Sparse triangular solves (include/sparse_linear_hip.h, csrc/trisolve.hip): owner of the `void *T` of
+// spl_trisolve_analyze for the lower (j <= i) or upper (j >= i) triangle of a square matrix; the other side of the
+// diagonal is not read.  Every solve is the serial substitution loop bit for bit.  Movable, not copyable.
+class TriangularSolver {
+ public:
+  // from a device handle, which is borrowed for the call only
+  TriangularSolver(void *h, int uplo, int diag = SPL_DIAG_stored) {
+    const int st = spl_trisolve_analyze(h, uplo, diag, &t_);
+    detail::check("triangular", st);
+    singular_ = st == SPL_WARNING_singular_matrix;
+  }
+  // from a host matrix: uploaded, analysed, and the handle released again
+  TriangularSolver(const Matrix &m, int uplo, int diag = SPL_DIAG_stored) {
+    detail::Const ca(m);
+    void *h = nullptr;
+    detail::check("triangular", spl_matrix_create(ca.nrows, ca.ncols, ca.p.data(), ca.i.data(), ca.x, &h));
+    const int st = spl_trisolve_analyze(h, uplo, diag, &t_);
+    spl_matrix_free(&h);
+    detail::check("triangular", st);
+    singular_ = st == SPL_WARNING_singular_matrix;
+  }
+  TriangularSolver(const TriangularSolver &) = delete;
+  TriangularSolver &operator=(const TriangularSolver &) = delete;
+  TriangularSolver(TriangularSolver &&o) noexcept : t_(o.t_), singular_(o.singular_) { o.t_ = nullptr; }
+  ~TriangularSolver() { spl_trisolve_free(&t_); }
+  bool singular() const { return singular_; }  // some d_i is missing or zero: the solves give IEEE's inf / NaN
+  // [0] n, [1] stored entries, [2] levels, [3] launches per solve, [4] zero diagonals, [5] longest row, [6] device
+  // bytes, [7] flags
+  std::vector<int64_t> info() const {
+    std::vector<int64_t> out(8, 0);
+    detail::check("triangular info", spl_trisolve_info(t_, out.data()));
+    return out;
+  }
+  // host vectors: n x k column-major (packed complex on a complex object); op SPL_OP_n, _t or _h
+  std::vector<double> solve(const std::vector<double> &b, int k = 1, int op = SPL_OP_n) const {
+    const std::vector<int64_t> inf = info();
+    const size_t want = (size_t)inf[0] * (size_t)(k > 0 ? k : 0) * ((inf[7] & 1) ? 2 : 1);
+    if (k >= 0 && b.size() != want)
+      detail::oops("solveTriangular", "right-hand side of " + std::to_string(b.size()) + " doubles; " +
+                                          std::to_string(want) + " are needed");
+    std::vector<double> x(b.size());
+    detail::check("solveTriangular", spl_trisolve_solve(t_, op, k, b.data(), x.data()));
+    return x;
+  }
+  // device arrays, column-major with leading dimensions in entries; enqueued on `stream`
+  void solveDev(const double *d_b, int64_t ldb, double *d_x, int64_t ldx, int k = 1, int op = SPL_OP_n,
+                void *stream = nullptr) const {
+    detail::check("solveTriangular", spl_trisolve_solve_dev(t_, op, k, d_b, ldb, d_x, ldx, stream));
+  }
+
+ private:
+  void *t_ = nullptr;
+  bool singular_ = false;
+};
+
 // hcat / vcat / fromBlocks (Sparse.hs:504-587): one device assembly (spl_assemble_blocks); nullptr = Nothing
 namespace detail {
 inline Matrix assemble(const std::vector<const Matrix *> &blocks, const std::vector<int> &row_off,

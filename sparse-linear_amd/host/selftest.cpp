@@ -176,6 +176,33 @@ int main() {
     for (Int i = 0; i < n; ++i) { ny += std::fabs(y[(size_t)i]); nx += std::fabs(ce.witness[(size_t)i]); }
     EXPECT(std::fabs(ny / nx - ce.norm_inv) < 1e-8 * ce.norm_inv);
   }
+  // a 4 x 4 lower bidiagonal solve worked out by hand: every quotient and difference below is exact
+  //   [ 2         ] x0 = 2 / 2 = 1            transposed:  x3 = 10 / 8 = 1.25
+  //   [ 1  4      ] x1 = (6 - 1) / 4 = 1.25                x2 = (5 - 3 * 1.25) / 5 = 0.25
+  //   [   -2  5   ] x2 = (5 + 2.5) / 5 = 1.5               x1 = (6 + 2 * 0.25) / 4 = 1.625
+  //   [       3 8 ] x3 = (10 - 4.5) / 8 = 0.6875           x0 = (2 - 1.625) / 2 = 0.1875
+  {
+    const Matrix L = fromTriples(4, 4, {{0, 0, 2.0}, {1, 0, 1.0}, {1, 1, 4.0}, {2, 1, -2.0}, {2, 2, 5.0}, {3, 2, 3.0},
+                                        {3, 3, 8.0}, {0, 3, 99.0}});  // the entry above the diagonal is not read
+    const std::vector<double> b{2.0, 6.0, 5.0, 10.0};
+    TriangularSolver T(L, SPL_TRI_lower);
+    EXPECT(!T.singular());
+    const std::vector<int64_t> inf = T.info();
+    EXPECT(inf[0] == 4 && inf[1] == 7 && inf[2] == 4 && inf[3] == 1 && inf[4] == 0 && inf[5] == 2);
+    EXPECT((T.solve(b) == std::vector<double>{1.0, 1.25, 1.5, 0.6875}));
+    EXPECT((T.solve(b, 1, SPL_OP_t) == std::vector<double>{0.1875, 1.625, 0.25, 1.25}));
+    bool threw = false;
+    try { T.solve({1.0, 2.0, 3.0}); } catch (const std::runtime_error &e) {  // a vector shorter than n
+      threw = std::string(e.what()).find("solveTriangular: right-hand side of 3 doubles; 4 are needed") == 0;
+    }
+    EXPECT(threw);
+    // unit diagonal: x = (2, 6 - 2, 5 + 8, 10 - 39)
+    TriangularSolver U1(L, SPL_TRI_lower, SPL_DIAG_unit);
+    EXPECT((U1.solve(b) == std::vector<double>{2.0, 4.0, 13.0, -29.0}));
+    // the upper triangle of the same matrix: its diagonal and the one entry above it
+    TriangularSolver Up(L, SPL_TRI_upper);
+    EXPECT((Up.solve(b) == std::vector<double>{(2.0 - 99.0 * 1.25) / 2.0, 1.5, 1.0, 1.25}));
+  }
   // work arrays of 256 KiB and more are kept for reuse (at most 2 GiB of them); releasing gives them back once
   EXPECT(U::releaseCachedMemory() <= (size_t)2 << 30);
   EXPECT(U::releaseCachedMemory() == 0);

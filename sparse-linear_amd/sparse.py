@@ -24,7 +24,8 @@ lie in device memory, a sparse torch tensor on the GPU among them, enter and lea
 ``A[rows, cols]`` for rows and columns by index (a permutation ``P A Q`` among them); ``subMatrix`` is the host route.
 Its values are worked on entry by entry the same way: ``map`` / ``negate`` / ``abs`` / ``signum`` / ``conj`` / ``real`` /
 ``imag`` / ``scale``, ``scale_rows_cols``, ``drop_zeros`` / ``drop_small``, ``band`` / ``tril`` / ``triu``, ``abs_sums`` /
-``abs_max`` / ``norm``; the host ``cmap`` and ``scale`` below stay numpy.
+``abs_max`` / ``norm``; the host ``cmap`` and ``scale`` below stay numpy.  Systems with a handle's lower or upper triangle
+are solved on the device by ``DeviceMatrix.triangular`` / ``TriangularSolver`` (``solveTriangular`` from a host Matrix).
 """
 import ctypes as C
 import weakref
@@ -823,6 +824,18 @@ class DeviceMatrix(object):
               lib().spl_matrix_spmv_many_dev(self.handle, int(k), C.c_void_p(x_ptr), int(ldx), C.c_void_p(y_ptr),
                                              int(ldy), 1 if accumulate else 0, C.c_void_p(stream)))
 
+    def triangular(self, uplo="lower", unit=False):
+        """a TriangularSolver for the lower (j <= i) or upper (j >= i) triangle of this whole square handle
+        (spl_trisolve_analyze); the other side of the diagonal is not read, so a Gauss-Seidel sweep passes the full
+        matrix.  unit: d_i = 1 and a stored diagonal is ignored.  The handle may be freed afterwards"""
+        if uplo not in TriangularSolver.UPLO:
+            raise ValueError("triangular: uplo %r; 'lower' or 'upper' is needed" % (uplo,))
+        t = C.c_void_p()
+        st = check("spl_trisolve_analyze",
+                   lib().spl_trisolve_analyze(self.handle, TriangularSolver.UPLO[uplo],
+                                              _ffi.SPL_DIAG_unit if unit else _ffi.SPL_DIAG_stored, C.byref(t)))
+        return TriangularSolver(t.value, st)
+
     def optimize(self):
         """one-time analysis; may build the column-blocked image (csrc/spmv_blocked.hip)"""
         check("spl_matrix_optimize", lib().spl_matrix_optimize(self.handle))
@@ -901,6 +914,122 @@ class DeviceMatrix(object):
         check("spl_matrix_spmv_dev",
               lib().spl_matrix_spmv_dev(self.handle, C.c_void_p(x_ptr), C.c_void_p(y_ptr),
                                         1 if accumulate else 0, C.c_void_p(stream)))
+
+
+class TriangularSolver(object):
+    """Owner of a ``void *T`` from ``spl_trisolve_analyze``: the level-scheduled solves T x = b, T^T x = b, T^H x = b
+    on the device (csrc/trisolve.hip).  Every result is the serial substitution loop bit for bit, whatever the schedule
+    and the number of right-hand sides.  ``singular``: the analysis found a missing or zero d_i (the solves then give
+    IEEE's inf / NaN, they never refuse)."""
+    UPLO = {"lower": _ffi.SPL_TRI_lower, "upper": _ffi.SPL_TRI_upper}
+    TRANS = {"N": _ffi.SPL_OP_n, "T": _ffi.SPL_OP_t, "H": _ffi.SPL_OP_h}
+
+    def __init__(self, handle, status=0):
+        self._t = C.c_void_p(handle)
+        self.singular = status == _ffi.SPL_WARNING_singular_matrix
+        self._finalizer = weakref.finalize(self, TriangularSolver._free, self._t)
+
+    @staticmethod
+    def _free(t):
+        try:
+            lib().spl_trisolve_free(C.byref(t))
+        except Exception:  # interpreter shutdown
+            pass
+
+    def free(self):
+        self._finalizer()
+
+    @property
+    def handle(self):
+        if not self._t.value:
+            raise _ffi.SparseLinearError("TriangularSolver", _ffi.SPL_ERROR_invalid_handle)
+        return self._t
+
+    @classmethod
+    def _op(cls, trans):
+        if trans not in cls.TRANS:
+            raise ValueError("trans %r; 'N', 'T' or 'H' is needed" % (trans,))
+        return cls.TRANS[trans]
+
+    def info(self):
+        out = np.zeros(8, dtype=I64)
+        check("spl_trisolve_info", lib().spl_trisolve_info(self.handle, _ffi.p_i64(out)))
+        keys = ("n", "stored", "levels", "launches", "zero_diagonals", "longest_row", "device_bytes", "flags")
+        d = dict(zip(keys, (int(v) for v in out)))
+        d.update(complex=bool(d["flags"] & 1), upper=bool(d["flags"] & 2), unit=bool(d["flags"] & 4),
+                 transposed_built=bool(d["flags"] & 8))
+        return d
+
+    def solve_dev(self, b_ptr, ldb, x_ptr, ldx, k, trans="N", stream=0):
+        """device pointers (ints) to column-major arrays with leading dimensions in entries (doubles, or packed complex
+        pairs); x_ptr == b_ptr with ldx == ldb solves in place; enqueues on `stream`, no sync (the first 'T' / 'H'
+        solve builds the transposed image and synchronises)"""
+        op = self._op(trans)
+        check("spl_trisolve_solve_dev",
+              lib().spl_trisolve_solve_dev(self.handle, op, int(k), C.c_void_p(b_ptr), int(ldb), C.c_void_p(x_ptr),
+                                           int(ldx), C.c_void_p(stream)))
+
+    def solve(self, b, trans="N"):
+        """x with T x = b (trans 'N'), T^T x = b ('T') or T^H x = b ('H').  b: a numpy array (the result is one) or a
+        torch tensor on the device (the result is one, enqueued on torch's current stream); 1-D, or 2-D in Fortran order
+        (one right-hand side after the other); float64 on a real object, complex128 on a complex one"""
+        op = self._op(trans)
+        inf = self.info()
+        n, cplx = inf["n"], inf["complex"]
+        try:
+            import torch
+            is_tensor = isinstance(b, torch.Tensor)
+        except ImportError:  # pragma: no cover
+            is_tensor = False
+        if is_tensor:
+            want = torch.complex128 if cplx else torch.float64
+            if b.dtype != want:
+                _oops("solveTriangular", "right-hand side of dtype %s; %s is needed" % (b.dtype, want))
+            if b.dim() not in (1, 2) or int(b.shape[0]) != n:
+                _oops("solveTriangular", "right-hand side of shape %s; %d rows are needed" % (tuple(b.shape), n))
+            if not b.is_cuda:
+                _oops("solveTriangular", "a torch right-hand side must lie on the device; pass a numpy array otherwise")
+            k = 1 if b.dim() == 1 else int(b.shape[1])
+            # a column's entries must follow each other whatever k is: an (n, 1) slice of a row-major tensor has
+            # strides (k, 1) and is refused like any other row-major operand
+            if b.dim() == 2 and n > 1 and (b.stride(0) != 1 or (k > 1 and b.stride(1) < n)):
+                _oops("solveTriangular", "a 2-D right-hand side must be in Fortran order (column after column)")
+            if b.dim() == 1 and n > 1 and b.stride(0) != 1:
+                _oops("solveTriangular", "a 1-D right-hand side must be contiguous")
+            with torch.cuda.device(b.device):
+                x = torch.empty_strided(tuple(b.shape), (1,) if b.dim() == 1 else (1, max(n, 1)), dtype=want,
+                                        device=b.device)
+                if n and k:
+                    ldb = n if b.dim() == 1 or k == 1 else int(b.stride(1))
+                    self.solve_dev(b.data_ptr(), ldb, x.data_ptr(), max(n, 1), k, trans,
+                                   torch.cuda.current_stream().cuda_stream)
+            return x
+        a = np.asarray(b)
+        want = C128 if cplx else F64
+        if a.dtype != want:
+            _oops("solveTriangular", "right-hand side of dtype %s; %s is needed" % (a.dtype, np.dtype(want)))
+        if a.ndim not in (1, 2) or a.shape[0] != n:
+            _oops("solveTriangular", "right-hand side of shape %s; %d rows are needed" % (a.shape, n))
+        if a.ndim == 2 and a.shape[1] > 1 and n > 1 and not a.flags.f_contiguous:
+            _oops("solveTriangular", "a 2-D right-hand side must be in Fortran order (column after column)")
+        k = 1 if a.ndim == 1 else a.shape[1]
+        src = np.ascontiguousarray(a.ravel(order="F"))  # one column after the other; no copy when a is laid out so
+        x = np.empty(a.size, dtype=want)
+        if n and k:
+            check("spl_trisolve_solve",
+                  lib().spl_trisolve_solve(self.handle, op, k, p_f64(src.view(F64)), p_f64(x.view(F64))))
+        return x.reshape(a.shape, order="F")
+
+
+def solveTriangular(mat, b, lower=True, unit=False, trans="N"):
+    """x with T x = b for the lower / upper triangle T of the host Matrix `mat` (its transpose or conjugate transpose
+    with trans 'T' / 'H'), solved on the device; b as TriangularSolver.solve takes it"""
+    TriangularSolver._op(trans)
+    T = mat.device_handle().triangular("lower" if lower else "upper", unit)
+    try:
+        return T.solve(b, trans)
+    finally:
+        T.free()
 
 
 # ---- accessors ------------------------------------------------------------------------------
