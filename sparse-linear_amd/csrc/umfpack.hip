@@ -1585,7 +1585,14 @@ struct SolveCall {
     // UMFPACK's default is two steps.  Factors kept as a speculation (no interchanges, no
     // diagonal dominance) may take more while each step still halves the backward error: static
     // pivoting with refinement, before the factors are given up for pivoted ones.
-    const int max_steps = N->speculative ? 10 : 2;
+    // SPL_LU_IRSTEP=k (0 .. 10), read per call, replaces both: with 0 the backward error above is that of the raw walk
+    // over the factors, which is then what is delivered and reported (tests/test_gpu_first_walk.py).
+    int max_steps = N->speculative ? 10 : 2;
+    if (const char *e = getenv("SPL_LU_IRSTEP")) {
+      char *end = nullptr;
+      const long v = strtol(e, &end, 10);
+      if (end != e && *end == '\0' && v >= 0 && v <= 10) max_steps = (int)v;
+    }
     const double stall = 0.5;
     for (int it = 0; it < max_steps && nactive > 0; ++it) {
       SPL_HIP(hipMemcpyAsync(dxn, dx, used * sizeof(double), hipMemcpyDeviceToDevice, s));

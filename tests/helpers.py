@@ -61,6 +61,71 @@ def handle_to_csc_tuple(H):
     return (nr, nc, cp, rows[order], v[order])
 
 
+# ---- the componentwise backward error of a delivered solution, evaluated exactly (tests/first_walk_cases.py) -------
+def two_product(a, b):
+    """p, e with p = fl(a * b) and a * b == p + e exactly, elementwise (Veltkamp's split, Dekker's product: no fused
+    multiply-add needed; exact unless a partial product over- or underflows, which the unit-sized test data cannot do)"""
+    a, b = np.asarray(a, dtype=np.float64), np.asarray(b, dtype=np.float64)
+    p = a * b
+    ca, cb = 134217729.0 * a, 134217729.0 * b  # 2^27 + 1
+    ah, bh = ca - (ca - a), cb - (cb - b)
+    al, bl = a - ah, b - bh
+    e = ((ah * bh - p) + ah * bl + al * bh) + al * bl
+    return p, e
+
+
+def real_embedding(S):
+    """the 2n x 2n real matrix of a complex S for interleaved unknowns (re x_0, im x_0, re x_1, ...): block (i, j) is
+    [[Re, -Im], [Im, Re]] (csrc/umfpack_zi.hip); zeros of either part are not stored"""
+    import scipy.sparse as sp
+    C = sp.coo_matrix(S)
+    n = C.shape[0]
+    r, c, re, im = C.row, C.col, C.data.real, C.data.imag
+    E = sp.csr_matrix((np.concatenate([re, -im, im, re]),
+                       (np.concatenate([2 * r, 2 * r, 2 * r + 1, 2 * r + 1]),
+                        np.concatenate([2 * c, 2 * c + 1, 2 * c, 2 * c + 1]))), shape=(2 * n, 2 * C.shape[1]))
+    E.eliminate_zeros()
+    return E
+
+
+def exact_backward_error(S, x, b):
+    """max_i |r_i| / (sum_k |a_ik| |x_k| + |b_i|) with r = b - S x, for a scipy matrix S: every product is split into
+    its rounded value and its rounding error, and each row is summed by math.fsum, so r_i and the denominator are the
+    correctly rounded values of the exact ones — no extended type of the host, no rounding of a plain S @ x - b.
+    Complex data is measured on the real embedding (real_embedding above).  A row with r_i != 0 over a zero
+    denominator gives inf.  x, b: one vector each (the result is a float), or k of them as a list or the rows of a
+    2-D array (a list of k floats)."""
+    import math
+
+    import scipy.sparse as sp
+    if not isinstance(x, np.ndarray) or x.ndim == 2:
+        return [exact_backward_error(S, np.asarray(xc), np.asarray(bc)) for xc, bc in zip(x, b)]
+    if np.iscomplexobj(S.data if sp.issparse(S) else S) or np.iscomplexobj(x) or np.iscomplexobj(b):
+        S = real_embedding(sp.csr_matrix(S).astype(np.complex128))
+        x = np.ascontiguousarray(x, dtype=np.complex128).view(np.float64)
+        b = np.ascontiguousarray(b, dtype=np.complex128).view(np.float64)
+    S = sp.csr_matrix(S)
+    x, b = np.asarray(x, dtype=np.float64), np.asarray(b, dtype=np.float64)
+    assert S.shape == (len(b), len(x))
+    if not (np.all(np.isfinite(x)) and np.all(np.isfinite(b))):
+        return float("inf")
+    p, e = two_product(S.data, x[S.indices])
+    ap, ae = np.abs(p), np.where(p < 0.0, -e, e)  # |a x| == |p| + sign(p) e exactly (|e| <= ulp(p) / 2)
+    ptr = S.indptr.tolist()
+    p, e, ap, ae, bl = p.tolist(), e.tolist(), ap.tolist(), ae.tolist(), b.tolist()
+    worst = 0.0
+    for i in range(S.shape[0]):
+        lo, hi = ptr[i], ptr[i + 1]
+        r = abs(math.fsum([bl[i]] + [-v for v in p[lo:hi]] + [-v for v in e[lo:hi]]))
+        if r == 0.0:
+            continue
+        den = math.fsum([abs(bl[i])] + ap[lo:hi] + ae[lo:hi])
+        w = r / den if den > 0.0 else float("inf")
+        if not w <= worst:
+            worst = w
+    return worst
+
+
 # ---- the order-free panel SpMV (csrc/spmv_panel.hip): what every form has to meet -------------------------
 EPS = np.finfo(float).eps
 
