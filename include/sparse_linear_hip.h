@@ -595,6 +595,54 @@ int spl_trisolve_solve(void *T, int op, int k, const double *B, double *X);
 int spl_trisolve_info(void *T, int64_t info[8]);
 void spl_trisolve_free(void **T);
 
+/* ---- ILU(0) on handles (csrc/ilu0.hip, csrc/tri_levels.hpp) ----------------------------------------------------------
+ * The incomplete LU factorisation without fill of a whole square handle, real or complex: the producer of what the
+ * triangular solves above apply.  L (unit lower, its ones not stored) and U live in ONE ordinary matrix handle F with
+ * A's own pattern, so F goes to spl_trisolve_analyze as it is: (F, SPL_TRI_lower, SPL_DIAG_unit) is L and
+ * (F, SPL_TRI_upper, SPL_DIAG_stored) is U, and M^-1 b = U^-1 (L^-1 b) is two spl_trisolve_solve_dev calls.
+ * Arithmetic: the serial IKJ loop on a copy of A's values, rows in CSR order with strictly ascending columns,
+ *     for i = 0 ... n-1:
+ *       for each stored (i,k) with k < i, ascending k:
+ *         a_ik = a_ik / u_kk              u_kk: the final stored diagonal of row k, 0 when row k stores none
+ *         for each stored (i,j) with j > k, ascending j:
+ *           if (k,j) is stored in row k:   a_ij = a_ij - a_ik * a_kj
+ *   with every real operation separately rounded and the division a correctly rounded IEEE division (no stored
+ *   reciprocal); complex handles use Data.Complex's product and scaled quotient, exactly those of the triangular
+ *   solves above.  Every entry receives its updates in ascending k, each one product and one difference, so the result
+ *   depends on neither the level schedule nor the lanes a row gets nor any launch shape: it is the serial loop bit for
+ *   bit, for rows of any length.  A zero or missing pivot gives what IEEE arithmetic gives (inf, NaN); the
+ *   factorisation never refuses on values.
+ * spl_ilu0_analyze: the plan is allocated by the callee, written through P, carries its own magic word and is freed by
+ *   spl_ilu0_free.  H is borrowed: the plan keeps its own device copy of the pattern (row pointers, columns), the
+ *   positions of the diagonals and the level tables, and no values, so H may be freed on return and ONE plan factors
+ *   real and complex handles alike.  The pattern is downloaded once; row i waits for the rows k < i of its lower
+ *   pattern, which is the dependency structure of the lower triangular solve, and the levels and the launch plan are
+ *   those of spl_trisolve_analyze (SPL_TRSV_SMALL_ROWS, SPL_TRSV_SEGMENT_LEVELS, read once per analysis; the lanes per
+ *   row follow the mean length of the whole rows).  The call runs on the default stream and synchronises.  No kernel
+ *   waits for another workgroup.  Returns SPL_OK.  Errors, checked in this order before the device is touched:
+ *   SPL_ERROR_invalid_handle (H is NULL or no matrix handle); SPL_ERROR_argument_missing (P is NULL; otherwise
+ *   *P = NULL first); SPL_ERROR_dimension_mismatch (not square); SPL_ERROR_invalid_matrix (a row-block handle, or one
+ *   without 32-bit row pointers, nnz >= 2^31); then SPL_ERROR_device without a GPU.
+ * spl_ilu0_factor: F receives a NEW ordinary matrix handle (freed by spl_matrix_free) with the pattern of H and the
+ *   L\U values, real when H is real and complex when H is complex.  H may be ANY whole handle with the analysed
+ *   pattern: new values on an old pattern are a refactorisation without an analysis.  The pattern is compared on the
+ *   device (n, nnz, then every row pointer and column); a difference gives SPL_ERROR_invalid_matrix and no F.  The call
+ *   runs on the default stream and synchronises.  Returns SPL_OK, or SPL_WARNING_singular_matrix (1, F exists) when
+ *   some final u_kk is missing or exactly zero (complex: both parts).  Concurrent factorisations on one plan from
+ *   several host threads are safe (the plan holds no scratch).  Errors: SPL_ERROR_invalid_handle (P is no plan or H no
+ *   matrix handle); SPL_ERROR_argument_missing (F is NULL; otherwise *F = NULL first); SPL_ERROR_invalid_matrix (H is a
+ *   row block, has no 32-bit row pointers, lies on another device, or has another pattern).
+ * spl_ilu0_info: [0] n, [1] nnz, [2] levels, [3] kernel launches one factorisation makes, [4] rows without a stored
+ *   diagonal, [5] longest row, [6] bytes of device memory held, [7] factorisations done so far.
+ * spl_ilu0_free: idempotent, any thread; NULL and a pointer to NULL are accepted; a pointer to what is no plan is
+ *   nulled and nothing is released.
+ * spl_matrix_ilu0: analyze + factor + free in one call, with the statuses of the two. */
+int spl_ilu0_analyze(void *H, void **P);
+int spl_ilu0_factor(void *P, void *H, void **F);
+int spl_ilu0_info(void *P, int64_t info[8]);
+void spl_ilu0_free(void **P);
+int spl_matrix_ilu0(void *H, void **F);
+
 /* select a kernel variant for spl_matrix_spmv_dev (tuning / ablation only): 0 = default
  * (whatever spl_matrix_optimize chose), 1-6 CSR-stream shapes, 7 sub-wavefront kernel, 8
  * column-blocked image, 9-11 gather cache policies, 15 sliced-ELL image, 16 column-sorted panel

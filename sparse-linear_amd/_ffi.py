@@ -153,6 +153,10 @@ def _declare(L):
         "spl_trisolve_solve_dev": [C.c_void_p, i, i, C.c_void_p, i64, C.c_void_p, i64, C.c_void_p],
         "spl_trisolve_solve": [C.c_void_p, i, i, c_dbl_p, c_dbl_p],
         "spl_trisolve_info": [C.c_void_p, c_i64_p],
+        "spl_ilu0_analyze": [C.c_void_p, c_void_pp],
+        "spl_ilu0_factor": [C.c_void_p, C.c_void_p, c_void_pp],
+        "spl_ilu0_info": [C.c_void_p, c_i64_p],
+        "spl_matrix_ilu0": [C.c_void_p, c_void_pp],
         "spl_matrix_set_variant": [C.c_void_p, i],
         "spl_matrix_optimize": [C.c_void_p],
         "spl_matrix_build_blocked": [C.c_void_p, i, i, i],
@@ -182,6 +186,9 @@ def _declare(L):
     if hasattr(L, "spl_trisolve_free"):
         L.spl_trisolve_free.restype = None
         L.spl_trisolve_free.argtypes = [c_void_pp]
+    if hasattr(L, "spl_ilu0_free"):
+        L.spl_ilu0_free.restype = None
+        L.spl_ilu0_free.argtypes = [c_void_pp]
     if hasattr(L, "spl_peer_exchange_free"):
         L.spl_peer_exchange_free.restype = None
         L.spl_peer_exchange_free.argtypes = [c_void_pp]

@@ -1581,6 +1581,77 @@ void spl_trisolve_free(void **T) {
   if (have_prev) (void)hipSetDevice(prev);
 }
 
+// ---- ILU(0) on handles (csrc/ilu0.hip) ---------------------------------------------------------------------------------
+// The plan keeps its own device copy of the pattern and the level tables, no values: H is borrowed for the call.
+int spl_ilu0_analyze(void *H, void **P) {
+  Matrix *A = as_matrix(H);
+  if (!A) return SPL_ERROR_invalid_handle;
+  if (!P) return SPL_ERROR_argument_missing;
+  *P = nullptr;
+  if (A->nrows_global != A->ncols) return SPL_ERROR_dimension_mismatch;
+  if (!whole(A) || !A->rowptr.get()) return SPL_ERROR_invalid_matrix;
+  return guarded([&]() -> int {
+    (void)current_device();
+    DeviceGuard g(A->device);
+    IluPlan *S = nullptr;
+    const int st = ilu0_analyze(A, &S);
+    *P = S;
+    return st;
+  });
+}
+
+// F: a new ordinary handle with H's pattern and the L\U values; H any whole handle with the analysed pattern
+int spl_ilu0_factor(void *P, void *H, void **F) {
+  IluPlan *S = as_ilu_plan(P);
+  Matrix *A = as_matrix(H);
+  if (!S || !A) return SPL_ERROR_invalid_handle;
+  if (!F) return SPL_ERROR_argument_missing;
+  *F = nullptr;
+  if (!whole(A) || !A->rowptr.get() || A->device != ilu0_device(S)) return SPL_ERROR_invalid_matrix;
+  return guarded([&]() -> int {
+    DeviceGuard g(A->device);
+    hipStream_t s = nullptr;
+    std::unique_ptr<Matrix> C = make_matrix(A->device, A->nrows_global, A->ncols, 0, A->nrows_local, A->vw);
+    const int st = ilu0_factor(S, A, C.get(), s);
+    if (st < 0) return st;
+    publish(std::move(C), s, F);
+    return st;
+  });
+}
+
+int spl_ilu0_info(void *P, int64_t info[8]) {
+  IluPlan *S = as_ilu_plan(P);
+  if (!S) return SPL_ERROR_invalid_handle;
+  if (!info) return SPL_ERROR_argument_missing;
+  ilu0_info(S, info);
+  return SPL_OK;
+}
+
+void spl_ilu0_free(void **P) {
+  if (!P || !*P) return;
+  IluPlan *S = as_ilu_plan(*P);
+  *P = nullptr;
+  if (!S) return;
+  int prev = -1;
+  const bool have_prev = hipGetDevice(&prev) == hipSuccess;
+  (void)hipSetDevice(ilu0_device(S));  // may run on a finalizer thread with another current device
+  ilu0_delete(S);
+  if (have_prev) (void)hipSetDevice(prev);
+}
+
+// analyze + factor + free: the one-shot form
+int spl_matrix_ilu0(void *H, void **F) {
+  if (!as_matrix(H)) return SPL_ERROR_invalid_handle;
+  if (!F) return SPL_ERROR_argument_missing;
+  *F = nullptr;
+  void *plan = nullptr;
+  int st = spl_ilu0_analyze(H, &plan);
+  if (st < 0) return st;
+  st = spl_ilu0_factor(plan, H, F);
+  spl_ilu0_free(&plan);
+  return st;
+}
+
 // mulM on Complex Double (the reference's SPECIALIZE instance, Sparse.hs:475): one axpy_ per column of B there; here the
 // packed-complex image of A and one multi-vector product.  B and C are row-major like spl_mulm's; the kernel wants one
 // vector after the other, so both are turned on the device (the call is bounded by its copies over PCIe).

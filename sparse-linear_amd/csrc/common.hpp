@@ -307,6 +307,19 @@ int trisolve_rows(const TriSolver *T);
 int trisolve_width(const TriSolver *T);  // doubles per entry: 1 real, 2 packed complex
 void trisolve_delete(TriSolver *T);
 
+// ---- ILU(0) on handles (ilu0.hip, tri_levels.hpp): the producer of what the triangular solves apply -------------
+struct IluPlan;
+IluPlan *as_ilu_plan(void *p);  // nullptr unless p carries the object's magic word
+// A: whole, square, 32-bit row pointers (the caller checked).  SPL_OK; synchronises
+int ilu0_analyze(const Matrix *A, IluPlan **out);
+// A: whole, 32-bit row pointers, on the plan's device (the caller checked); C: dimensions and value kind set by the
+// caller.  SPL_ERROR_invalid_matrix (A's pattern is not the analysed one; C stays empty), else C holds A's pattern and
+// the L\U values (rowptr64 / colidx / val / nnz): SPL_OK or SPL_WARNING_singular_matrix.  Synchronises s
+int ilu0_factor(IluPlan *P, const Matrix *A, Matrix *C, hipStream_t s);
+void ilu0_info(const IluPlan *P, int64_t info[8]);
+int ilu0_device(const IluPlan *P);
+void ilu0_delete(IluPlan *P);
+
 // ---- multifrontal LU without interchanges (multifrontal.hip, mf_symbolic.hpp) ------------------
 namespace mf {
 struct Tree;

@@ -358,6 +358,110 @@ class TriangularSolver {
   bool singular_ = false;
 };
 
+// ILU(0) (include/sparse_linear_hip.h, csrc/ilu0.hip): the incomplete LU factorisation without fill of a square real
+// matrix, the serial IKJ loop bit for bit.  Owner of the plan of spl_ilu0_analyze, of the factor handle (L unit lower
+// and U in one matrix of A's pattern) and of the two triangular solvers built from it.  Movable, not copyable.
+class ILU0 {
+ public:
+  explicit ILU0(const Matrix &m) {
+    const Handle h(upload(m));
+    try {
+      detail::check("ilu0", spl_ilu0_analyze(h.h, &p_));
+      factorHandle("ilu0", h.h);
+    } catch (...) {  // no destructor runs for an object whose constructor throws
+      spl_ilu0_free(&p_);
+      throw;
+    }
+  }
+  ILU0(const ILU0 &) = delete;
+  ILU0 &operator=(const ILU0 &) = delete;
+  ILU0(ILU0 &&o) noexcept
+      : p_(o.p_), f_(o.f_), lower_(std::move(o.lower_)), upper_(std::move(o.upper_)), singular_(o.singular_) {
+    o.p_ = nullptr;
+    o.f_ = nullptr;
+  }
+  ~ILU0() {
+    lower_.reset();
+    upper_.reset();
+    spl_matrix_free(&f_);
+    spl_ilu0_free(&p_);
+  }
+  bool singular() const { return singular_; }  // some final u_kk is missing or zero: the factors hold IEEE's inf / NaN
+  // [0] n, [1] nnz, [2] levels, [3] launches per factorisation, [4] rows without a stored diagonal, [5] longest row,
+  // [6] device bytes, [7] factorisations so far
+  std::vector<int64_t> info() const {
+    std::vector<int64_t> out(8, 0);
+    detail::check("ilu0 info", spl_ilu0_info(p_, out.data()));
+    return out;
+  }
+  // new values on the analysed pattern: no analysis.  When this throws (a matrix of another pattern is refused, an
+  // analysis of a triangle fails) the object keeps the factors and solvers it had
+  void refactor(const Matrix &m) {
+    const Handle h(upload(m));
+    factorHandle("ilu0 refactor", h.h);
+  }
+  void *factorsHandle() const { return f_; }  // borrowed: an ordinary matrix handle with A's pattern
+  const TriangularSolver &lower() const { return *lower_; }  // L: unit diagonal
+  const TriangularSolver &upper() const { return *upper_; }  // U: stored diagonal
+  // L\U as a host matrix of A's pattern
+  Matrix factors() const {
+    int64_t inf[8] = {0};
+    detail::check("ilu0 factors", spl_matrix_info(f_, inf));
+    const size_t nz = (size_t)inf[4];
+    std::vector<int64_t> cp((size_t)inf[1] + 1);
+    std::vector<int> ri(nz ? nz : 1);
+    Matrix c;
+    c.nrows = (Int)inf[0];
+    c.ncols = (Int)inf[1];
+    c.values.resize(nz ? nz : 1);
+    detail::check("ilu0 factors", spl_matrix_export_csc(f_, cp.data(), ri.data(), c.values.data()));
+    c.values.resize(nz);
+    c.pointers.assign(cp.begin(), cp.end());
+    c.indices.assign(ri.begin(), ri.begin() + (std::ptrdiff_t)nz);
+    return c;
+  }
+  // U^-1 L^-1 b (SPL_OP_n) or L^-T U^-T b (SPL_OP_t) for host vectors, n x k column-major
+  std::vector<double> solve(const std::vector<double> &b, int k = 1, int op = SPL_OP_n) const {
+    return op == SPL_OP_n ? upper_->solve(lower_->solve(b, k, op), k, op) : lower_->solve(upper_->solve(b, k, op), k, op);
+  }
+
+ private:
+  // a matrix handle that is freed when the scope is left, by return or by exception
+  struct Handle {
+    void *h;
+    explicit Handle(void *handle) : h(handle) {}
+    Handle(const Handle &) = delete;
+    Handle &operator=(const Handle &) = delete;
+    ~Handle() { spl_matrix_free(&h); }
+    void *release() { void *r = h; h = nullptr; return r; }
+  };
+  static void *upload(const Matrix &m) {
+    detail::Const ca(m);
+    void *h = nullptr;
+    detail::check("ilu0", spl_matrix_create(ca.nrows, ca.ncols, ca.p.data(), ca.i.data(), ca.x, &h));
+    return h;
+  }
+  // factors h on the plan and builds the two solvers; the object takes them only when all three exist
+  void factorHandle(const char *where, void *h) {
+    void *f = nullptr;
+    const int st = spl_ilu0_factor(p_, h, &f);
+    detail::check(where, st);
+    Handle factors(f);
+    std::unique_ptr<TriangularSolver> lower(new TriangularSolver(f, SPL_TRI_lower, SPL_DIAG_unit));
+    std::unique_ptr<TriangularSolver> upper(new TriangularSolver(f, SPL_TRI_upper, SPL_DIAG_stored));
+    lower_ = std::move(lower);
+    upper_ = std::move(upper);
+    spl_matrix_free(&f_);
+    f_ = factors.release();
+    singular_ = st == SPL_WARNING_singular_matrix;
+  }
+  void *p_ = nullptr, *f_ = nullptr;
+  std::unique_ptr<TriangularSolver> lower_, upper_;
+  bool singular_ = false;
+};
+
+inline ILU0 ilu0(const Matrix &m) { return ILU0(m); }
+
 // hcat / vcat / fromBlocks (Sparse.hs:504-587): one device assembly (spl_assemble_blocks); nullptr = Nothing
 namespace detail {
 inline Matrix assemble(const std::vector<const Matrix *> &blocks, const std::vector<int> &row_off,

@@ -203,6 +203,32 @@ int main() {
     TriangularSolver Up(L, SPL_TRI_upper);
     EXPECT((Up.solve(b) == std::vector<double>{(2.0 - 99.0 * 1.25) / 2.0, 1.5, 1.0, 1.25}));
   }
+  // ILU(0) of a 4 x 4 tridiagonal matrix, where it is the LU factorisation; every operation below is exact
+  //   [ 2    1            ]   [ 1              ] [ 2  1       ]      row 1: 1 / 2 = 0.5,  4.5 - 0.5 * 1 = 4
+  //   [ 1    4.5   1      ] = [ 0.5  1         ] [    4  1    ]      row 2: 1 / 4 = 0.25, 8.25 - 0.25 * 1 = 8
+  //   [      1     8.25 1 ]   [      0.25 1    ] [       8  1 ]      row 3: 4 / 8 = 0.5,  16.5 - 0.5 * 1 = 16
+  //   [            4 16.5 ]   [           0.5 1] [         16 ]
+  {
+    const Matrix A = fromTriples(4, 4, {{0, 0, 2.0}, {0, 1, 1.0}, {1, 0, 1.0}, {1, 1, 4.5}, {1, 2, 1.0}, {2, 1, 1.0},
+                                        {2, 2, 8.25}, {2, 3, 1.0}, {3, 2, 4.0}, {3, 3, 16.5}});
+    ILU0 F = ilu0(A);
+    EXPECT(!F.singular());
+    const std::vector<int64_t> inf = F.info();
+    EXPECT(inf[0] == 4 && inf[1] == 10 && inf[2] == 4 && inf[3] == 1 && inf[4] == 0 && inf[5] == 3 && inf[7] == 1);
+    const Matrix LU = F.factors();  // column after column, like A
+    EXPECT(LU.pointers == A.pointers && LU.indices == A.indices);
+    EXPECT((LU.values == std::vector<double>{2.0, 0.5, 1.0, 4.0, 0.25, 1.0, 8.0, 0.5, 1.0, 16.0}));
+    // A (1, 2, 3, 4)^T = (4, 13, 30.75, 78)^T;  L y = b: y = (4, 11, 28, 64);  U x = y
+    EXPECT((F.solve({4.0, 13.0, 30.75, 78.0}) == std::vector<double>{1.0, 2.0, 3.0, 4.0}));
+    // new values on the pattern: 2 A factors to the same L and 2 U, without an analysis
+    F.refactor(fromTriples(4, 4, {{0, 0, 4.0}, {0, 1, 2.0}, {1, 0, 2.0}, {1, 1, 9.0}, {1, 2, 2.0}, {2, 1, 2.0},
+                                  {2, 2, 16.5}, {2, 3, 2.0}, {3, 2, 8.0}, {3, 3, 33.0}}));
+    EXPECT((F.factors().values == std::vector<double>{4.0, 0.5, 2.0, 8.0, 0.25, 2.0, 16.0, 0.5, 2.0, 32.0}));
+    EXPECT(F.info()[7] == 2);
+    bool threw = false;
+    try { F.refactor(ident(4)); } catch (const std::runtime_error &) { threw = true; }  // another pattern
+    EXPECT(threw && F.info()[7] == 2);
+  }
   // work arrays of 256 KiB and more are kept for reuse (at most 2 GiB of them); releasing gives them back once
   EXPECT(U::releaseCachedMemory() <= (size_t)2 << 30);
   EXPECT(U::releaseCachedMemory() == 0);

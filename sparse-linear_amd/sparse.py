@@ -25,7 +25,8 @@ lie in device memory, a sparse torch tensor on the GPU among them, enter and lea
 Its values are worked on entry by entry the same way: ``map`` / ``negate`` / ``abs`` / ``signum`` / ``conj`` / ``real`` /
 ``imag`` / ``scale``, ``scale_rows_cols``, ``drop_zeros`` / ``drop_small``, ``band`` / ``tril`` / ``triu``, ``abs_sums`` /
 ``abs_max`` / ``norm``; the host ``cmap`` and ``scale`` below stay numpy.  Systems with a handle's lower or upper triangle
-are solved on the device by ``DeviceMatrix.triangular`` / ``TriangularSolver`` (``solveTriangular`` from a host Matrix).
+are solved on the device by ``DeviceMatrix.triangular`` / ``TriangularSolver`` (``solveTriangular`` from a host Matrix),
+and ``DeviceMatrix.ilu0`` / ``ILU0`` (``ilu0`` from a host Matrix) produces the incomplete factors those solvers apply.
 """
 import ctypes as C
 import weakref
@@ -836,6 +837,11 @@ class DeviceMatrix(object):
                                               _ffi.SPL_DIAG_unit if unit else _ffi.SPL_DIAG_stored, C.byref(t)))
         return TriangularSolver(t.value, st)
 
+    def ilu0(self):
+        """the ILU(0) factorisation of this whole square handle (spl_ilu0_analyze + spl_ilu0_factor): an ILU0 object
+        with the factors as a handle of this pattern and the two triangular solvers built from it"""
+        return ILU0(self)
+
     def optimize(self):
         """one-time analysis; may build the column-blocked image (csrc/spmv_blocked.hip)"""
         check("spl_matrix_optimize", lib().spl_matrix_optimize(self.handle))
@@ -1030,6 +1036,96 @@ def solveTriangular(mat, b, lower=True, unit=False, trans="N"):
         return T.solve(b, trans)
     finally:
         T.free()
+
+
+class ILU0(object):
+    """The incomplete LU factorisation without fill of a whole square device handle (csrc/ilu0.hip): the serial IKJ
+    loop bit for bit, whatever the schedule.  ``factors`` is a DeviceMatrix with A's pattern that holds L (unit lower,
+    its ones not stored) and U; ``lower`` / ``upper`` are the TriangularSolvers built from it (unit / stored diagonal);
+    ``singular``: some final u_kk is missing or exactly zero (the factors then hold IEEE's inf / NaN).  The plan of
+    ``spl_ilu0_analyze`` is kept: ``refactor(A)`` factors new values on the same pattern without an analysis."""
+    INFO_KEYS = ("n", "nnz", "levels", "launches", "missing_diagonals", "longest_row", "device_bytes", "factorisations")
+
+    def __init__(self, A):
+        self._p = C.c_void_p()
+        self.factors = self.lower = self.upper = None
+        self.singular = False
+        self._finalizer = weakref.finalize(self, ILU0._free, self._p)
+        check("spl_ilu0_analyze", lib().spl_ilu0_analyze(A.handle, C.byref(self._p)))
+        self.refactor(A)
+
+    @staticmethod
+    def _free(p):
+        try:
+            lib().spl_ilu0_free(C.byref(p))
+        except Exception:  # interpreter shutdown
+            pass
+
+    @property
+    def plan(self):
+        if not self._p.value:
+            raise _ffi.SparseLinearError("ILU0", _ffi.SPL_ERROR_invalid_handle)
+        return self._p
+
+    def _drop_factors(self):
+        for part in (self.lower, self.upper, self.factors):
+            if part is not None:
+                part.free()
+        self.factors = self.lower = self.upper = None
+
+    def free(self):
+        self._drop_factors()
+        self._finalizer()
+
+    def info(self):
+        out = np.zeros(8, dtype=I64)
+        check("spl_ilu0_info", lib().spl_ilu0_info(self.plan, _ffi.p_i64(out)))
+        return dict(zip(self.INFO_KEYS, (int(v) for v in out)))
+
+    def refactor(self, A):
+        """new values on the analysed pattern (A: any whole handle with it, real or complex): the factors and the two
+        solvers are replaced once all three exist; when a step raises (a handle of another pattern is refused, an
+        analysis fails) the object keeps what it had"""
+        f = C.c_void_p()
+        st = check("spl_ilu0_factor", lib().spl_ilu0_factor(self.plan, A.handle, C.byref(f)))
+        factors = DeviceMatrix(f.value)
+        lower = upper = None
+        try:
+            lower = factors.triangular("lower", unit=True)
+            upper = factors.triangular("upper")
+        except Exception:
+            for part in (lower, factors):
+                if part is not None:
+                    part.free()
+            raise
+        self._drop_factors()
+        self.factors, self.lower, self.upper = factors, lower, upper
+        self.singular = st == _ffi.SPL_WARNING_singular_matrix
+        return self
+
+    def _solvers(self, trans):
+        TriangularSolver._op(trans)
+        if self.lower is None or self.upper is None:
+            raise _ffi.SparseLinearError("ILU0", _ffi.SPL_ERROR_invalid_handle)
+        # (L U)^-1 = U^-1 L^-1;  (L U)^-T = L^-T U^-T
+        return (self.lower, self.upper) if trans == "N" else (self.upper, self.lower)
+
+    def apply_dev(self, b_ptr, ldb, x_ptr, ldx, k, trans="N", stream=0):
+        """x = U^-1 L^-1 b (trans 'N'), L^-T U^-T b ('T') or L^-H U^-H b ('H') in two solve_dev calls on `stream`, no
+        sync; device pointers and leading dimensions as TriangularSolver.solve_dev takes them, in place allowed"""
+        first, second = self._solvers(trans)
+        first.solve_dev(b_ptr, ldb, x_ptr, ldx, k, trans, stream)
+        second.solve_dev(x_ptr, ldx, x_ptr, ldx, k, trans, stream)
+
+    def solve(self, b, trans="N"):
+        """the same for a host array b (1-D, or 2-D in Fortran order), as TriangularSolver.solve takes it"""
+        first, second = self._solvers(trans)
+        return second.solve(first.solve(b, trans), trans)
+
+
+def ilu0(mat):
+    """the ILU0 object of the host Matrix `mat`, factored on the device"""
+    return mat.device_handle().ilu0()
 
 
 # ---- accessors ------------------------------------------------------------------------------
