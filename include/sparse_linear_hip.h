@@ -643,6 +643,108 @@ int spl_ilu0_info(void *P, int64_t info[8]);
 void spl_ilu0_free(void **P);
 int spl_matrix_ilu0(void *H, void **F);
 
+/* ---- the fixed-order inner product, preconditioned CG and BiCGSTAB on handles (csrc/krylov.hip) -----------------------
+ * A x = b on the device without a factorisation of A: the operator is spl_matrix_spmv_dev on a whole square handle, real
+ * or complex, the preconditioner is made of the objects above, and every scalar of the iteration stays in device memory.
+ * The contract is the one of the other handle operations: the result is a serial restatement's bit for bit, whatever
+ * the launch shapes are.
+ *
+ * fold(v, len): v is cut into chunks of 4096 consecutive entries, the last one may be short.  In a chunk, lane t of 256
+ *   starts from +0.0 and adds the entries t, t + 256, t + 512 ... in ascending order; the 256 lane sums are then folded
+ *   as s[t] = s[t] + s[t + h], t < h, for h = 128, 64 ... 1, and s[0] is the chunk's partial.  The partials are folded
+ *   by the same fold until one value is left (two levels up to 4096^2 entries, three beyond); fold of nothing is +0.0.
+ * <a,b> = fold of the entry-wise products: a_i * b_i on real vectors, conj(a_i) * b_i with Data.Complex's product
+ *   ((a :+ b) * (c :+ d) = (a c - b d) :+ (a d + b c), applied to (a_re, -a_im) and b) on packed complex ones, the real
+ *   and the imaginary parts folded apart; every real operation separately rounded.  |r|^2 is the real part of <r,r>.
+ *   The order is a function of len alone: no floating-point atomic, no kernel that waits for another workgroup, and
+ *   the grid (SPL_KRYLOV_GRID, workgroups of a chunk kernel at most, default 2048) does not show in the bits.
+ * spl_vector_dot_dev: d_out[0] (and d_out[1], value_width 2) = <a,b> of n entries of value_width doubles each, all in
+ *   DEVICE memory.  Enqueued on `stream`, no synchronisation.  Every CALL takes a block of its own from the device pool
+ *   for the partials (one whose previous user has finished on the device, told by an event recorded behind that user's
+ *   last kernel, or a new one), so calls from several host threads, on one stream or on several, never share partials;
+ *   a handful of finished blocks is kept for reuse, whatever the number of streams and calls.  n < 0: SPL_ERROR_n_nonpositive; n == 0 writes +0.0; a value_width outside {1, 2}, a NULL pointer
+ *   (d_a, d_b with n > 0; d_out always) or one not aligned to an entry (8 or 16 bytes): SPL_ERROR_argument_missing.
+ *
+ * spl_krylov_create: the object is allocated by the callee, written through K, carries its own magic word and is freed
+ *   by spl_krylov_free (idempotent, any thread; NULL, a pointer to NULL and a pointer to what is no such object are
+ *   accepted).  A is BORROWED and must outlive K; the operator is spl_matrix_spmv_dev on A as the caller configured it
+ *   (images, variant, order mode).  In SPL_ORDER_FREE the SpMV's sums are not in the reference's order and the bit
+ *   contract of this section is VOID; everything else holds.  (In SPL_ORDER_REFERENCE the SpMV's own caveats apply: a row
+ *   of more than 512 entries is summed by a wavefront tree.)  The object owns its work vectors (4 for CG, 8 for
+ *   BiCGSTAB), the partials of the fold and a status block in device memory: iteration counter, done, reason, rho,
+ *   alpha, beta, omega, |r|^2, |b|^2, the threshold.  Solves on one object are serialised under its lock.
+ *   Errors, checked in this order before the device is touched: SPL_ERROR_invalid_handle (A is NULL or no matrix
+ *   handle); SPL_ERROR_argument_missing (K is NULL; otherwise *K = NULL first; then an unknown method);
+ *   SPL_ERROR_dimension_mismatch (not square); SPL_ERROR_invalid_matrix (a row-block handle); then SPL_ERROR_device
+ *   without a GPU.
+ * spl_krylov_set_preconditioner: z = M^-1 r = T2^-1 (d_mid (.) (T1^-1 r)), every part may be NULL (the identity).  T1
+ *   and T2 are spl_trisolve objects, applied with SPL_OP_n and k = 1; d_mid is a DEVICE vector of n entries (packed
+ *   pairs on a complex object), multiplied entry by entry, d_mid_i * v_i (Data.Complex's product).  All are borrowed.
+ *   No preconditioner: all NULL.  Jacobi: d_mid = 1 / diag(A).  ILU(0): T1 = (F, lower, unit), T2 = (F, upper, stored).
+ *   Symmetric Gauss-Seidel: T1 = (A, lower, stored), d_mid = diag(A), T2 = (A, upper, stored).  Errors:
+ *   SPL_ERROR_invalid_handle (K, or a part that is not NULL, is no such object); SPL_ERROR_argument_missing (d_mid not
+ *   aligned to an entry); SPL_ERROR_dimension_mismatch (a triangular object of another size, value kind or device).
+ * The scalars: q = a / b is the IEEE division, on complex objects Data.Complex's scaled quotient (that of the
+ *   triangular solves); every vector update is one product and one sum or difference per entry, each rounded once:
+ *   x_i = x_i + alpha * p_i.  A scalar is zero when all its parts are, non-finite when one part is.
+ *   threshold = max(rtol * sqrt(|b|^2), atol);  met(v): sqrt(v) <= threshold.
+ * SPL_KRYLOV_cg, standard preconditioned CG:
+ *     r = b - A x   (use_x0 == 0: r = b and x = 0, no SpMV);  it = 0;  history[0] = sqrt(|r|^2)
+ *     |r|^2 or |b|^2 not finite: reason 3;  met(|r|^2): reason 0;  max_iter == 0: reason 1
+ *     z = M^-1 r;  rho = <r,z>  (zero or non-finite: reason 2);  p = z
+ *     repeat:  q = A p;  d = <p,q>  (zero or non-finite: reason 2);  alpha = rho / d
+ *              x = x + alpha p;  r = r - alpha q;  it = it + 1;  history[it] = sqrt(|r|^2)
+ *              |r|^2 not finite: reason 3;  met(|r|^2): reason 0;  it == max_iter: reason 1
+ *              z = M^-1 r;  rho' = <r,z>  (zero or non-finite: reason 2);  beta = rho' / rho;  rho = rho'
+ *              p = z + beta p
+ *   Without a preconditioner z is r, and <r,z> is the <r,r> the residual step has just folded, bit for bit (both
+ *   parts, when complex): it is not computed again.
+ * SPL_KRYLOV_bicgstab, van der Vorst's method, preconditioned from the right:
+ *     r = b - A x as above, rhat = r, the same checks of iteration 0
+ *     repeat:  rho' = <rhat,r>  (zero or non-finite: reason 2)
+ *              first pass: p = r;  later: beta = (rho' / rho) * (alpha / omega);  p = r + beta (p - omega v)
+ *              rho = rho';  y = M^-1 p;  v = A y;  d = <rhat,v>  (zero or non-finite: reason 2);  alpha = rho / d
+ *              s = r - alpha v;  x = x + alpha y
+ *              |s|^2 not finite: reason 3;  met(|s|^2): it = it + 1, history[it] = sqrt(|s|^2), reason 0
+ *              z = M^-1 s;  t = A z;  omega = <t,s> / <t,t>  (<t,t> or omega zero or non-finite: reason 2)
+ *              x = x + omega z;  r = s - omega t;  it = it + 1;  history[it] = sqrt(|r|^2)
+ *              |r|^2 not finite: reason 3;  met(|r|^2): reason 0;  it == max_iter: reason 1
+ *   The first reason met ends the solve: nothing after it is computed, x is the iterate of that moment (after a
+ *   breakdown behind BiCGSTAB's half step x holds the half step, and it counts the completed iterations).  A breakdown
+ *   never hangs and never refuses.
+ * spl_krylov_solve_dev: d_b and d_x are DEVICE vectors of n entries, not the same array; use_x0 != 0 takes d_x as the
+ *   start, otherwise d_x is only written.  The kernels are enqueued on `stream`.  Convergence is decided on the device:
+ *   the kernel that completes |r|^2 sets `done`, and every vector kernel of the solver returns without touching a
+ *   vector once it is set.  The host copies the status block into pinned memory and synchronises `stream` every
+ *   check_every iterations (0: the default, 16) and stops launching once `done` is set, so x, the iteration count and
+ *   the history do NOT depend on check_every; only the launches issued for nothing do.  The call returns after a last
+ *   synchronisation.  result = {iterations, reason (0 converged, 1 max_iter, 2 breakdown, 3 non-finite), SpMVs issued,
+ *   preconditioner applications issued}.  history may be NULL; otherwise it is a HOST array of max_iter + 1 doubles
+ *   that receives sqrt(|r_it|^2) of the recurrence for it = 0 ... iterations.  On the device the history takes room
+ *   for the iterations that were ISSUED (grown at the looks at the status block), not for max_iter: a large max_iter
+ *   as "no limit" costs nothing there; the host array is the caller's.  Returns SPL_OK whenever it ran: the
+ *   outcome is in result.  b = 0 (and no start) gives x = 0 after 0 iterations, reason 0.  n == 0: SPL_OK, result all
+ *   0, history[0] = 0.  Errors, in this order: SPL_ERROR_invalid_handle (K); SPL_ERROR_argument_missing (result NULL);
+ *   SPL_ERROR_n_nonpositive (max_iter < 0); SPL_ERROR_argument_missing (rtol or atol negative or NaN, check_every < 0);
+ *   SPL_ERROR_index_overflow (a history of 2^31 entries or more); SPL_ERROR_argument_missing (d_b or d_x NULL, the
+ *   same, or not aligned to an entry).
+ * spl_krylov_solve: the same with HOST vectors (packed complex), on the default stream with the default check_every;
+ *   x is read only with use_x0 != 0.
+ * spl_krylov_info: [0] n, [1] method, [2] flags (1 complex, 2 T1 set, 4 d_mid set, 8 T2 set), [3] bytes of device memory
+ *   held, [4] solves so far, [5] iterations of the last solve, [6] kernel launches per iteration of the last solve (the
+ *   SpMV counted as one), [7] reserved, 0. */
+#define SPL_KRYLOV_cg 0
+#define SPL_KRYLOV_bicgstab 1
+int spl_vector_dot_dev(int64_t n, int value_width, const double *d_a, const double *d_b, double *d_out, void *stream);
+int spl_krylov_create(void *A, int method, void **K);
+int spl_krylov_set_preconditioner(void *K, void *T1, const double *d_mid, void *T2);
+int spl_krylov_solve_dev(void *K, const double *d_b, double *d_x, int use_x0, double rtol, double atol, int64_t max_iter,
+                         int check_every, int64_t result[4], double *history, void *stream);
+int spl_krylov_solve(void *K, const double *b, double *x, int use_x0, double rtol, double atol, int64_t max_iter,
+                     int64_t result[4], double *history);
+int spl_krylov_info(void *K, int64_t info[8]);
+void spl_krylov_free(void **K);
+
 /* select a kernel variant for spl_matrix_spmv_dev (tuning / ablation only): 0 = default
  * (whatever spl_matrix_optimize chose), 1-6 CSR-stream shapes, 7 sub-wavefront kernel, 8
  * column-blocked image, 9-11 gather cache policies, 15 sliced-ELL image, 16 column-sorted panel

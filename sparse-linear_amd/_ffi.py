@@ -38,6 +38,8 @@ SPL_NORM_one, SPL_NORM_inf, SPL_NORM_fro, SPL_NORM_max = range(4)
 SPL_TRI_lower, SPL_TRI_upper = 0, 1
 SPL_DIAG_stored, SPL_DIAG_unit = 0, 1
 SPL_OP_n, SPL_OP_t, SPL_OP_h = 0, 1, 2
+# preconditioned CG and BiCGSTAB on handles (spl_krylov_*)
+SPL_KRYLOV_cg, SPL_KRYLOV_bicgstab = 0, 1
 
 
 class BackendUnavailable(RuntimeError):
@@ -157,6 +159,12 @@ def _declare(L):
         "spl_ilu0_factor": [C.c_void_p, C.c_void_p, c_void_pp],
         "spl_ilu0_info": [C.c_void_p, c_i64_p],
         "spl_matrix_ilu0": [C.c_void_p, c_void_pp],
+        "spl_vector_dot_dev": [i64, i, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p],
+        "spl_krylov_create": [C.c_void_p, i, c_void_pp],
+        "spl_krylov_set_preconditioner": [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p],
+        "spl_krylov_solve_dev": [C.c_void_p, C.c_void_p, C.c_void_p, i, d, d, i64, i, c_i64_p, c_dbl_p, C.c_void_p],
+        "spl_krylov_solve": [C.c_void_p, c_dbl_p, c_dbl_p, i, d, d, i64, c_i64_p, c_dbl_p],
+        "spl_krylov_info": [C.c_void_p, c_i64_p],
         "spl_matrix_set_variant": [C.c_void_p, i],
         "spl_matrix_optimize": [C.c_void_p],
         "spl_matrix_build_blocked": [C.c_void_p, i, i, i],
@@ -189,6 +197,9 @@ def _declare(L):
     if hasattr(L, "spl_ilu0_free"):
         L.spl_ilu0_free.restype = None
         L.spl_ilu0_free.argtypes = [c_void_pp]
+    if hasattr(L, "spl_krylov_free"):
+        L.spl_krylov_free.restype = None
+        L.spl_krylov_free.argtypes = [c_void_pp]
     if hasattr(L, "spl_peer_exchange_free"):
         L.spl_peer_exchange_free.restype = None
         L.spl_peer_exchange_free.argtypes = [c_void_pp]

@@ -1652,6 +1652,142 @@ int spl_matrix_ilu0(void *H, void **F) {
   return st;
 }
 
+// ---- the fixed-order inner product, preconditioned CG and BiCGSTAB on handles (csrc/krylov.hip) ------------------------
+int spl_vector_dot_dev(int64_t n, int value_width, const double *d_a, const double *d_b, double *d_out, void *stream) {
+  if (n < 0) return SPL_ERROR_n_nonpositive;
+  if (value_width != 1 && value_width != 2) return SPL_ERROR_argument_missing;
+  if (!d_out || (n > 0 && (!d_a || !d_b))) return SPL_ERROR_argument_missing;
+  const uintptr_t entry = (uintptr_t)(8 * value_width);  // the kernels load and store whole entries
+  if ((uintptr_t)d_a % entry != 0 || (uintptr_t)d_b % entry != 0 || (uintptr_t)d_out % entry != 0)
+    return SPL_ERROR_argument_missing;
+  return guarded([&]() -> int {
+    return vector_dot(current_device(), n, value_width, d_a, d_b, d_out, as_stream(stream));
+  });
+}
+
+// A is borrowed: the object keeps the pointer and its own work vectors
+int spl_krylov_create(void *A, int method, void **K) {
+  Matrix *M = as_matrix(A);
+  if (!M) return SPL_ERROR_invalid_handle;
+  if (!K) return SPL_ERROR_argument_missing;
+  *K = nullptr;
+  if (method != SPL_KRYLOV_cg && method != SPL_KRYLOV_bicgstab) return SPL_ERROR_argument_missing;
+  if (M->nrows_global != M->ncols) return SPL_ERROR_dimension_mismatch;
+  if (!whole(M)) return SPL_ERROR_invalid_matrix;
+  return guarded([&]() -> int {
+    (void)current_device();
+    DeviceGuard g(M->device);
+    Krylov *S = nullptr;
+    const int st = krylov_create(M, method, &S);
+    *K = S;
+    return st;
+  });
+}
+
+int spl_krylov_set_preconditioner(void *K, void *T1, const double *d_mid, void *T2) {
+  Krylov *S = as_krylov(K);
+  if (!S) return SPL_ERROR_invalid_handle;
+  TriSolver *parts[2] = {nullptr, nullptr};
+  void *given[2] = {T1, T2};
+  for (int i = 0; i < 2; ++i) {
+    if (!given[i]) continue;
+    parts[i] = as_trisolver(given[i]);
+    if (!parts[i]) return SPL_ERROR_invalid_handle;
+  }
+  if ((uintptr_t)d_mid % (uintptr_t)(8 * krylov_width(S)) != 0) return SPL_ERROR_argument_missing;
+  for (TriSolver *T : parts)
+    if (T && (trisolve_rows(T) != krylov_rows(S) || trisolve_width(T) != krylov_width(S) ||
+              trisolve_device(T) != krylov_device(S)))
+      return SPL_ERROR_dimension_mismatch;
+  krylov_set_preconditioner(S, parts[0], d_mid, parts[1]);
+  return SPL_OK;
+}
+
+namespace {
+// what both solve calls refuse before anything else is looked at
+int check_krylov_solve(const Krylov *S, double rtol, double atol, int64_t max_iter, int check_every,
+                       const int64_t *result, const double *history) {
+  if (!S) return SPL_ERROR_invalid_handle;
+  if (!result) return SPL_ERROR_argument_missing;
+  if (max_iter < 0) return SPL_ERROR_n_nonpositive;
+  if (!(rtol >= 0.0) || !(atol >= 0.0) || check_every < 0) return SPL_ERROR_argument_missing;  // a NaN is refused too
+  if (history && max_iter >= ((int64_t)1 << 31)) return SPL_ERROR_index_overflow;
+  return SPL_OK;
+}
+void empty_krylov_result(int64_t result[4], double *history) {
+  result[0] = result[1] = result[2] = result[3] = 0;
+  if (history) history[0] = 0.0;
+}
+}  // namespace
+
+int spl_krylov_solve_dev(void *K, const double *d_b, double *d_x, int use_x0, double rtol, double atol, int64_t max_iter,
+                         int check_every, int64_t result[4], double *history, void *stream) {
+  Krylov *S = as_krylov(K);
+  const int refused = check_krylov_solve(S, rtol, atol, max_iter, check_every, result, history);
+  if (refused != SPL_OK) return refused;
+  if (krylov_rows(S) == 0) {
+    empty_krylov_result(result, history);
+    return SPL_OK;
+  }
+  if (!d_b || !d_x || d_b == d_x) return SPL_ERROR_argument_missing;
+  const uintptr_t entry = (uintptr_t)(8 * krylov_width(S));  // the kernels load and store whole entries
+  if ((uintptr_t)d_b % entry != 0 || (uintptr_t)d_x % entry != 0) return SPL_ERROR_argument_missing;
+  return guarded([&]() -> int {
+    DeviceGuard g(krylov_device(S));
+    return krylov_solve(S, d_b, d_x, use_x0 ? 1 : 0, rtol, atol, max_iter, check_every, result, history, as_stream(stream));
+  });
+}
+
+// host vectors of n entries, packed complex: up, solved on the default stream with the default check interval, down
+int spl_krylov_solve(void *K, const double *b, double *x, int use_x0, double rtol, double atol, int64_t max_iter,
+                     int64_t result[4], double *history) {
+  Krylov *S = as_krylov(K);
+  const int refused = check_krylov_solve(S, rtol, atol, max_iter, 0, result, history);
+  if (refused != SPL_OK) return refused;
+  if (krylov_rows(S) == 0) {
+    empty_krylov_result(result, history);
+    return SPL_OK;
+  }
+  if (!b || !x) return SPL_ERROR_argument_missing;
+  return guarded([&]() -> int {
+    DeviceGuard g(krylov_device(S));
+    hipStream_t s = nullptr;
+    const size_t count = (size_t)krylov_rows(S) * (size_t)krylov_width(S);
+    DBuf<double> d(2 * count);
+    double *d_b = d.get(), *d_x = d.get() + count;
+    SPL_HIP(hipMemcpyAsync(d_b, b, count * sizeof(double), hipMemcpyHostToDevice, s));
+    if (use_x0) SPL_HIP(hipMemcpyAsync(d_x, x, count * sizeof(double), hipMemcpyHostToDevice, s));
+    const int st = krylov_solve(S, d_b, d_x, use_x0 ? 1 : 0, rtol, atol, max_iter, 0, result, history, s);
+    if (st != SPL_OK) {
+      (void)hipStreamSynchronize(s);
+      return st;
+    }
+    SPL_HIP(hipMemcpyAsync(x, d_x, count * sizeof(double), hipMemcpyDeviceToHost, s));
+    SPL_HIP(hipStreamSynchronize(s));
+    return SPL_OK;
+  });
+}
+
+int spl_krylov_info(void *K, int64_t info[8]) {
+  Krylov *S = as_krylov(K);
+  if (!S) return SPL_ERROR_invalid_handle;
+  if (!info) return SPL_ERROR_argument_missing;
+  krylov_info(S, info);
+  return SPL_OK;
+}
+
+void spl_krylov_free(void **K) {
+  if (!K || !*K) return;
+  Krylov *S = as_krylov(*K);
+  *K = nullptr;
+  if (!S) return;
+  int prev = -1;
+  const bool have_prev = hipGetDevice(&prev) == hipSuccess;
+  (void)hipSetDevice(krylov_device(S));  // may run on a finalizer thread with another current device
+  krylov_delete(S);
+  if (have_prev) (void)hipSetDevice(prev);
+}
+
 // mulM on Complex Double (the reference's SPECIALIZE instance, Sparse.hs:475): one axpy_ per column of B there; here the
 // packed-complex image of A and one multi-vector product.  B and C are row-major like spl_mulm's; the kernel wants one
 // vector after the other, so both are turned on the device (the call is bounded by its copies over PCIe).

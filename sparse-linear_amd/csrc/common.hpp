@@ -320,6 +320,24 @@ void ilu0_info(const IluPlan *P, int64_t info[8]);
 int ilu0_device(const IluPlan *P);
 void ilu0_delete(IluPlan *P);
 
+// ---- the fixed-order inner product, preconditioned CG and BiCGSTAB on handles (krylov.hip) ----------------------
+// <a,b> of n entries of vw doubles each to d_out (vw doubles, device memory); enqueues on s, no synchronisation
+int vector_dot(int device, int64_t n, int vw, const double *d_a, const double *d_b, double *d_out, hipStream_t s);
+struct Krylov;
+Krylov *as_krylov(void *k);  // nullptr unless k carries the object's magic word
+// A: whole and square (the caller checked); borrowed.  SPL_OK
+int krylov_create(const Matrix *A, int method, Krylov **out);
+// the parts are borrowed and of K's size and value kind (the caller checked); nullptr: the part is the identity
+void krylov_set_preconditioner(Krylov *K, TriSolver *T1, const double *d_mid, TriSolver *T2);
+// n > 0 and the arguments are checked by the caller; enqueues on s and synchronises it (the outcome is read back)
+int krylov_solve(Krylov *K, const double *d_b, double *d_x, int use_x0, double rtol, double atol, int64_t max_iter,
+                 int check_every, int64_t result[4], double *history, hipStream_t s);
+void krylov_info(Krylov *K, int64_t info[8]);
+int krylov_device(const Krylov *K);
+int64_t krylov_rows(const Krylov *K);
+int krylov_width(const Krylov *K);  // doubles per entry: 1 real, 2 packed complex
+void krylov_delete(Krylov *K);
+
 // ---- multifrontal LU without interchanges (multifrontal.hip, mf_symbolic.hpp) ------------------
 namespace mf {
 struct Tree;

@@ -27,6 +27,8 @@ Its values are worked on entry by entry the same way: ``map`` / ``negate`` / ``a
 ``abs_max`` / ``norm``; the host ``cmap`` and ``scale`` below stay numpy.  Systems with a handle's lower or upper triangle
 are solved on the device by ``DeviceMatrix.triangular`` / ``TriangularSolver`` (``solveTriangular`` from a host Matrix),
 and ``DeviceMatrix.ilu0`` / ``ILU0`` (``ilu0`` from a host Matrix) produces the incomplete factors those solvers apply.
+``DeviceMatrix.krylov`` / ``KrylovSolver`` (``cg`` / ``bicgstab`` from a host Matrix) solve ``A x = b`` with them:
+preconditioned CG and BiCGSTAB whose scalars stay on the device; ``vector_dot_dev`` is their fixed-order inner product.
 """
 import ctypes as C
 import weakref
@@ -842,6 +844,11 @@ class DeviceMatrix(object):
         with the factors as a handle of this pattern and the two triangular solvers built from it"""
         return ILU0(self)
 
+    def krylov(self, method="cg", M=None):
+        """a KrylovSolver for this whole square handle (spl_krylov_create): 'cg' or 'bicgstab', with the preconditioner
+        M (None, an ILU0, 'jacobi', 'sgs' or a (T1, mid, T2) triple).  The handle is borrowed: the solver keeps it alive"""
+        return KrylovSolver(self, method, M)
+
     def optimize(self):
         """one-time analysis; may build the column-blocked image (csrc/spmv_blocked.hip)"""
         check("spl_matrix_optimize", lib().spl_matrix_optimize(self.handle))
@@ -1126,6 +1133,211 @@ class ILU0(object):
 def ilu0(mat):
     """the ILU0 object of the host Matrix `mat`, factored on the device"""
     return mat.device_handle().ilu0()
+
+
+def vector_dot_dev(n, a_ptr, b_ptr, out_ptr, is_complex=False, stream=0):
+    """out = <a,b> of n entries in the fixed order of include/sparse_linear_hip.h (conj(a) . b on packed complex
+    vectors, is_complex=True); device pointers (ints), out one double or one packed pair; enqueues on `stream`, no sync"""
+    check("spl_vector_dot_dev",
+          lib().spl_vector_dot_dev(int(n), 2 if is_complex else 1, C.c_void_p(a_ptr), C.c_void_p(b_ptr),
+                                   C.c_void_p(out_ptr), C.c_void_p(stream)))
+
+
+class KrylovSolver(object):
+    """Owner of a ``void *K`` from ``spl_krylov_create``: preconditioned CG or BiCGSTAB on a whole square device handle
+    (csrc/krylov.hip), real or complex, every scalar of the iteration in device memory.  The iterates, the iteration
+    count and the residual history are those of the serial restatement in include/sparse_linear_hip.h bit for bit.
+
+    ``M``: None; an ``ILU0``; ``"jacobi"`` (1 / diag(A)); ``"sgs"`` (symmetric Gauss-Seidel: tril(A), diag(A), triu(A));
+    or a triple ``(T1, mid, T2)`` of a TriangularSolver or None, a torch device vector of n entries or None, and a
+    TriangularSolver or None, applied as ``z = T2^-1 (mid * (T1^-1 r))``.  The object keeps references to A and to the
+    parts of M, so nothing it borrows is collected under it; ``parts`` is the triple in use."""
+    METHODS = {"cg": _ffi.SPL_KRYLOV_cg, "bicgstab": _ffi.SPL_KRYLOV_bicgstab}
+    REASONS = ("converged", "max_iter", "breakdown", "non_finite")
+    INFO_KEYS = ("n", "method", "flags", "device_bytes", "solves", "iterations", "launches_per_iteration", "reserved")
+    DEFAULT_MAXITER = 20000
+
+    def __init__(self, A, method="cg", M=None):
+        if method not in self.METHODS:
+            raise ValueError("KrylovSolver: method %r; 'cg' or 'bicgstab' is needed" % (method,))
+        self._k = C.c_void_p()
+        self._finalizer = weakref.finalize(self, KrylovSolver._free, self._k)
+        self.A = A
+        self.method = method
+        self.parts = (None, None, None)
+        self._owned = []  # what "jacobi" and "sgs" made here
+        self._M = M       # an ILU0 stays alive with its solvers
+        check("spl_krylov_create", lib().spl_krylov_create(A.handle, self.METHODS[method], C.byref(self._k)))
+        self.set_preconditioner(M)
+
+    @staticmethod
+    def _free(k):
+        try:
+            lib().spl_krylov_free(C.byref(k))
+        except Exception:  # interpreter shutdown
+            pass
+
+    def free(self):
+        self._finalizer()
+        for part in self._owned:
+            part.free()
+        self._owned = []
+
+    @property
+    def handle(self):
+        if not self._k.value:
+            raise _ffi.SparseLinearError("KrylovSolver", _ffi.SPL_ERROR_invalid_handle)
+        return self._k
+
+    def _diagonal(self):
+        import torch
+        inf = self.A.info()
+        with torch.cuda.device(inf["device"]):
+            d = torch.empty(max(inf["nrows_global"], 1), dtype=torch.complex128 if self.A.is_complex else torch.float64,
+                            device="cuda")
+            self.A.take_diag_dev(d.data_ptr(), torch.cuda.current_stream().cuda_stream)
+            torch.cuda.current_stream().synchronize()
+        return d[:inf["nrows_global"]]
+
+    def set_preconditioner(self, M):
+        """replaces the preconditioner (the forms of the class docstring)"""
+        owned = []
+        if M is None:
+            parts = (None, None, None)
+        elif isinstance(M, ILU0):
+            parts = (M.lower, None, M.upper)
+        elif isinstance(M, str) and M == "jacobi":
+            parts = (None, 1.0 / self._diagonal(), None)
+        elif isinstance(M, str) and M == "sgs":
+            lower, upper = self.A.triangular("lower"), self.A.triangular("upper")
+            owned = [lower, upper]
+            parts = (lower, self._diagonal(), upper)
+        elif isinstance(M, (tuple, list)) and len(M) == 3:
+            parts = tuple(M)
+        else:
+            raise ValueError("KrylovSolver: M %r; None, an ILU0, 'jacobi', 'sgs' or a (T1, mid, T2) triple is needed" % (M,))
+        t1, mid, t2 = parts
+        if mid is not None:
+            n, cplx = self.info()["n"], self.A.is_complex
+            import torch
+            want = torch.complex128 if cplx else torch.float64
+            if not (isinstance(mid, torch.Tensor) and mid.is_cuda and mid.dtype == want and mid.dim() == 1
+                    and int(mid.shape[0]) == n and (n <= 1 or mid.stride(0) == 1)):
+                _oops("KrylovSolver", "the middle part must be a contiguous torch device vector of %d %s entries" % (n, want))
+        check("spl_krylov_set_preconditioner",
+              lib().spl_krylov_set_preconditioner(self.handle, t1.handle if t1 is not None else None,
+                                                  C.c_void_p(mid.data_ptr()) if mid is not None else None,
+                                                  t2.handle if t2 is not None else None))
+        for part in self._owned:
+            part.free()
+        self._owned, self.parts, self._M = owned, parts, M
+
+    def info(self):
+        out = np.zeros(8, dtype=I64)
+        check("spl_krylov_info", lib().spl_krylov_info(self.handle, _ffi.p_i64(out)))
+        d = dict(zip(self.INFO_KEYS, (int(v) for v in out)))
+        d.update(complex=bool(d["flags"] & 1), T1=bool(d["flags"] & 2), mid=bool(d["flags"] & 4), T2=bool(d["flags"] & 8))
+        return d
+
+    @classmethod
+    def _result(cls, result, history):
+        it, reason = int(result[0]), int(result[1])
+        out = {"iterations": it, "reason": reason, "reason_name": cls.REASONS[reason], "converged": reason == 0,
+               "spmvs": int(result[2]), "preconditioner_applications": int(result[3])}
+        if history is not None:
+            out["history"] = history[:it + 1].copy()
+        return out
+
+    def _maxiter(self, maxiter):
+        if maxiter is None:
+            return min(10 * self.info()["n"], self.DEFAULT_MAXITER)
+        return int(maxiter)
+
+    def solve_dev(self, b_ptr, x_ptr, use_x0=False, rtol=1e-8, atol=0.0, maxiter=None, check_every=0, history=True,
+                  stream=0):
+        """device pointers (ints) to b and x (n doubles, or packed pairs); use_x0: x holds the start.  Enqueues on
+        `stream` and returns after the solve's last synchronisation with the result dict (iterations, reason, spmvs,
+        preconditioner_applications, history)"""
+        maxiter = self._maxiter(maxiter)
+        result = np.zeros(4, dtype=I64)
+        hist = np.zeros(maxiter + 1, dtype=F64) if history else None
+        check("spl_krylov_solve_dev",
+              lib().spl_krylov_solve_dev(self.handle, C.c_void_p(b_ptr), C.c_void_p(x_ptr), 1 if use_x0 else 0,
+                                         float(rtol), float(atol), maxiter, int(check_every), _ffi.p_i64(result),
+                                         p_f64(hist) if history else None, C.c_void_p(stream)))
+        return self._result(result, hist)
+
+    def solve(self, b, x0=None, rtol=1e-8, atol=0.0, maxiter=None, check_every=0):
+        """(x, result dict) with A x = b.  b (and x0): numpy arrays, or torch tensors on the device (x is one then and
+        the solve runs on torch's current stream); float64 on a real object, complex128 on a complex one"""
+        inf = self.info()
+        n, cplx = inf["n"], inf["complex"]
+        try:
+            import torch
+            is_tensor = isinstance(b, torch.Tensor)
+        except ImportError:  # pragma: no cover
+            is_tensor = False
+        if is_tensor:
+            want = torch.complex128 if cplx else torch.float64
+            for v, what in ((b, "right-hand side"), (x0, "start")):
+                if v is None:
+                    continue
+                if not (isinstance(v, torch.Tensor) and v.is_cuda and v.dtype == want and tuple(v.shape) == (n,)):
+                    _oops("KrylovSolver.solve", "the %s must be a device tensor of %d %s entries" % (what, n, want))
+            with torch.cuda.device(b.device):
+                bb = b.contiguous()
+                x = torch.empty(max(n, 1), dtype=want, device=b.device)[:n]
+                if x0 is not None:
+                    x.copy_(x0)
+                res = self.solve_dev(bb.data_ptr(), x.data_ptr(), x0 is not None, rtol, atol, maxiter, check_every,
+                                     True, torch.cuda.current_stream().cuda_stream)
+            return x, res
+        want = C128 if cplx else F64
+        a = np.ascontiguousarray(b)
+        if a.dtype != want or a.shape != (n,):
+            _oops("KrylovSolver.solve", "right-hand side of dtype %s and shape %s; %d %s entries are needed"
+                  % (a.dtype, a.shape, n, np.dtype(want)))
+        x = np.zeros(n, dtype=want)
+        if x0 is not None:
+            x0 = np.asarray(x0)
+            if x0.dtype != want or x0.shape != (n,):
+                _oops("KrylovSolver.solve", "a start of dtype %s and shape %s; %d %s entries are needed"
+                      % (x0.dtype, x0.shape, n, np.dtype(want)))
+            x[:] = x0
+        maxiter = self._maxiter(maxiter)
+        if check_every:  # the host-vector call has no such argument: through device tensors
+            import torch
+            with torch.cuda.device(self.A.info()["device"]):
+                db = torch.from_numpy(a).cuda()
+                dx = torch.from_numpy(x).cuda()
+                res = self.solve_dev(db.data_ptr(), dx.data_ptr(), x0 is not None, rtol, atol, maxiter, check_every,
+                                     True, torch.cuda.current_stream().cuda_stream)
+                return dx.cpu().numpy(), res
+        result = np.zeros(4, dtype=I64)
+        hist = np.zeros(maxiter + 1, dtype=F64)
+        check("spl_krylov_solve",
+              lib().spl_krylov_solve(self.handle, p_f64(a.view(F64)), p_f64(x.view(F64)), 1 if x0 is not None else 0,
+                                     float(rtol), float(atol), maxiter, _ffi.p_i64(result), p_f64(hist)))
+        return x, self._result(result, hist)
+
+
+def _krylov(method, mat, b, M, x0, rtol, atol, maxiter):
+    K = mat.device_handle().krylov(method, M)
+    try:
+        return K.solve(b, x0, rtol, atol, maxiter)
+    finally:
+        K.free()
+
+
+def cg(mat, b, M=None, x0=None, rtol=1e-8, atol=0.0, maxiter=None):
+    """(x, result dict) with mat x = b by preconditioned CG on the device; mat: a host Matrix, Hermitian positive
+    definite; M as KrylovSolver takes it"""
+    return _krylov("cg", mat, b, M, x0, rtol, atol, maxiter)
+
+
+def bicgstab(mat, b, M=None, x0=None, rtol=1e-8, atol=0.0, maxiter=None):
+    """(x, result dict) with mat x = b by right-preconditioned BiCGSTAB on the device; mat: a host Matrix"""
+    return _krylov("bicgstab", mat, b, M, x0, rtol, atol, maxiter)
 
 
 # ---- accessors ------------------------------------------------------------------------------
