@@ -745,6 +745,50 @@ int spl_krylov_solve(void *K, const double *b, double *x, int use_x0, double rto
 int spl_krylov_info(void *K, int64_t info[8]);
 void spl_krylov_free(void **K);
 
+/* ---- multicolour ordering on handles (csrc/coloring.hip) --------------------------------------------------------------
+ * The levels of a triangular solve and of ILU(0) are a property of the ordering.  Colour the adjacency graph so that no
+ * two neighbours share a colour and number the unknowns colour by colour: a row of the lower triangle of P A P^T then
+ * depends on rows of earlier colours only, and spl_trisolve_analyze / spl_ilu0_analyze find at most as many levels as
+ * there are colours.  The price is convergence: a multicolour ILU(0) or Gauss-Seidel is a weaker preconditioner.
+ *
+ * Graph: the vertices are 0 ... n-1; {i, j}, i != j, is an edge when a_ij or a_ji is stored, stored zeros included.
+ *   Values are never read: a real and a complex handle of one pattern give the same result.
+ * Priority: h(v) = the splitmix64 finaliser of v + 0x9E3779B97F4A7C15 (seed + 1), all mod 2^64:
+ *     z = v + 0x9E3779B97F4A7C15 (seed + 1);  z = (z ^ z >> 30) 0xBF58476D1CE4E5B9;  z = (z ^ z >> 27) 0x94D049BB133111EB;
+ *     h = z ^ z >> 31
+ *   u PRECEDES v when h(u) > h(v), or when they are equal and u < v: a strict total order.
+ * colour(v) = the smallest c >= 0 that no neighbour preceding v has;
+ * round(v)  = 1 + the largest round(u) over the neighbours u that precede v, 1 when there are none.
+ *   The colours are those of the serial first-fit colouring taken in priority order, which is the fixed point of
+ *   Jones-Plassmann rounds: functions of the pattern and the seed alone.  d_colors holds exactly those integers, whatever
+ *   the grid (SPL_COLOR_GRID, workgroups of a launch at most, default 2048), the order of the worklist and the host's
+ *   looks at it are.
+ * spl_matrix_color: order must be SPL_COLOR_hash.  d_colors: n int32 in DEVICE memory.  d_perm (may be NULL): n int32 in
+ *   device memory; perm[k] is the old index of new row k, the vertices sorted by colour and then by ascending index (the
+ *   stable order), the form spl_matrix_select takes as I and J: P A P^T = select(A, perm, perm).  *offsets (offsets may
+ *   be NULL): a HOST array of info[1] + 1 int64 with the class boundaries in perm, allocated by the callee and released
+ *   with spl_free.  One launch is one round: every vertex of the worklist whose preceding neighbours all carried a
+ *   colour when the launch began takes its colour.  No kernel waits for another workgroup.  The host reads the number
+ *   of vertices left every SPL_COLOR_CHECK_EVERY rounds (read once per call, 1 ... 4096, default 8); a round on an empty
+ *   worklist does nothing.  The call runs on the default stream and synchronises.
+ *   info: [0] n, [1] colours, [2] rounds = the largest round(v), [3] largest class, [4] smallest class, [5] largest
+ *   degree of the graph, [6] kernel launches of csrc/coloring.hip issued (those inside the scan and the sort are not
+ *   counted), [7] 0.  n == 0: SPL_OK, 0 colours, offsets = {0}.  No off-diagonal entry: one colour, the identity.
+ *   Errors, checked in this order before the device is touched: SPL_ERROR_invalid_handle (H is NULL or no matrix
+ *   handle); SPL_ERROR_argument_missing (d_colors or info is NULL; *offsets = NULL first when offsets is given);
+ *   SPL_ERROR_argument_missing (an unknown order, or d_colors / d_perm not aligned to 4 bytes);
+ *   SPL_ERROR_dimension_mismatch (not square); SPL_ERROR_invalid_matrix (a row-block handle, or one without 32-bit row
+ *   pointers, nnz >= 2^31); then SPL_ERROR_device without a GPU.
+ * spl_vector_permute_dev: out[k] = in[perm[k]] (inverse == 0) or out[perm[k]] = in[k] (inverse != 0) for n entries of
+ *   value_width doubles (1, or 2: packed complex), all in DEVICE memory, moved as bits; d_in and d_out are different
+ *   arrays.  perm is trusted: it is the array spl_matrix_color wrote.  Enqueued on `stream`, no synchronisation.
+ *   n < 0: SPL_ERROR_n_nonpositive; n == 0 does nothing; a value_width outside {1, 2}, with n > 0 a NULL pointer or
+ *   d_in == d_out, a pointer not aligned to its entries (4, and 8 or 16 bytes): SPL_ERROR_argument_missing. */
+#define SPL_COLOR_hash 0
+int spl_matrix_color(void *H, int order, uint64_t seed, int *d_colors, int *d_perm, int64_t **offsets, int64_t info[8]);
+int spl_vector_permute_dev(int64_t n, int value_width, const int *d_perm, int inverse, const double *d_in, double *d_out,
+                           void *stream);
+
 /* select a kernel variant for spl_matrix_spmv_dev (tuning / ablation only): 0 = default
  * (whatever spl_matrix_optimize chose), 1-6 CSR-stream shapes, 7 sub-wavefront kernel, 8
  * column-blocked image, 9-11 gather cache policies, 15 sliced-ELL image, 16 column-sorted panel

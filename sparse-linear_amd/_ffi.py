@@ -40,6 +40,8 @@ SPL_DIAG_stored, SPL_DIAG_unit = 0, 1
 SPL_OP_n, SPL_OP_t, SPL_OP_h = 0, 1, 2
 # preconditioned CG and BiCGSTAB on handles (spl_krylov_*)
 SPL_KRYLOV_cg, SPL_KRYLOV_bicgstab = 0, 1
+# multicolour ordering on handles (spl_matrix_color)
+SPL_COLOR_hash = 0
 
 
 class BackendUnavailable(RuntimeError):
@@ -165,6 +167,8 @@ def _declare(L):
         "spl_krylov_solve_dev": [C.c_void_p, C.c_void_p, C.c_void_p, i, d, d, i64, i, c_i64_p, c_dbl_p, C.c_void_p],
         "spl_krylov_solve": [C.c_void_p, c_dbl_p, c_dbl_p, i, d, d, i64, c_i64_p, c_dbl_p],
         "spl_krylov_info": [C.c_void_p, c_i64_p],
+        "spl_matrix_color": [C.c_void_p, i, u64, C.c_void_p, C.c_void_p, C.POINTER(c_i64_p), c_i64_p],
+        "spl_vector_permute_dev": [i64, i, C.c_void_p, i, C.c_void_p, C.c_void_p, C.c_void_p],
         "spl_matrix_set_variant": [C.c_void_p, i],
         "spl_matrix_optimize": [C.c_void_p],
         "spl_matrix_build_blocked": [C.c_void_p, i, i, i],

@@ -1788,6 +1788,39 @@ void spl_krylov_free(void **K) {
   if (have_prev) (void)hipSetDevice(prev);
 }
 
+// ---- multicolour ordering on handles (csrc/coloring.hip) --------------------------------------------------------------
+// H is borrowed for the call; d_colors and d_perm are the caller's device arrays, *offsets a malloc()'d host array
+int spl_matrix_color(void *H, int order, uint64_t seed, int *d_colors, int *d_perm, int64_t **offsets, int64_t info[8]) {
+  Matrix *A = as_matrix(H);
+  if (!A) return SPL_ERROR_invalid_handle;
+  if (offsets) *offsets = nullptr;
+  if (!d_colors || !info) return SPL_ERROR_argument_missing;
+  if (order != SPL_COLOR_hash) return SPL_ERROR_argument_missing;
+  if ((uintptr_t)d_colors % sizeof(int) != 0 || (uintptr_t)d_perm % sizeof(int) != 0) return SPL_ERROR_argument_missing;
+  if (A->nrows_global != A->ncols) return SPL_ERROR_dimension_mismatch;
+  if (!whole(A) || A->nnz >= (int64_t)0x7fffffff || (A->nrows_local > 0 && !A->rowptr.get())) return SPL_ERROR_invalid_matrix;
+  return guarded([&]() -> int {
+    (void)current_device();
+    DeviceGuard g(A->device);
+    return color_handle(A, seed, d_colors, d_perm, offsets, info);
+  });
+}
+
+int spl_vector_permute_dev(int64_t n, int value_width, const int *d_perm, int inverse, const double *d_in, double *d_out,
+                           void *stream) {
+  if (n < 0) return SPL_ERROR_n_nonpositive;
+  if (value_width != 1 && value_width != 2) return SPL_ERROR_argument_missing;
+  if (n > 0 && (!d_perm || !d_in || !d_out || d_in == d_out)) return SPL_ERROR_argument_missing;
+  const uintptr_t entry = (uintptr_t)(8 * value_width);  // the kernel loads and stores whole entries
+  if ((uintptr_t)d_perm % sizeof(int) != 0 || (uintptr_t)d_in % entry != 0 || (uintptr_t)d_out % entry != 0)
+    return SPL_ERROR_argument_missing;
+  return guarded([&]() -> int {
+    (void)current_device();
+    if (n > 0) vector_permute(n, value_width, d_perm, inverse, d_in, d_out, as_stream(stream));
+    return SPL_OK;
+  });
+}
+
 // mulM on Complex Double (the reference's SPECIALIZE instance, Sparse.hs:475): one axpy_ per column of B there; here the
 // packed-complex image of A and one multi-vector product.  B and C are row-major like spl_mulm's; the kernel wants one
 // vector after the other, so both are turned on the device (the call is bounded by its copies over PCIe).

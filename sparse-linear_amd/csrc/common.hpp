@@ -338,6 +338,13 @@ int64_t krylov_rows(const Krylov *K);
 int krylov_width(const Krylov *K);  // doubles per entry: 1 real, 2 packed complex
 void krylov_delete(Krylov *K);
 
+// ---- multicolour ordering on handles (coloring.hip) -----------------------------------------------------------------
+// A: whole, square, 32-bit row pointers (the caller checked).  d_colors: n ints; d_perm: n ints or nullptr; offsets:
+// nullptr, or where a malloc()'d array of info[1] + 1 class boundaries goes.  Default stream; synchronises.  SPL_OK
+int color_handle(const Matrix *A, uint64_t seed, int *d_colors, int *d_perm, int64_t **offsets, int64_t info[8]);
+// out[k] = in[perm[k]] (inverse == 0) or out[perm[k]] = in[k], entries of vw doubles moved as bits; n > 0; enqueues on s
+void vector_permute(int64_t n, int vw, const int *d_perm, int inverse, const double *d_in, double *d_out, hipStream_t s);
+
 // ---- multifrontal LU without interchanges (multifrontal.hip, mf_symbolic.hpp) ------------------
 namespace mf {
 struct Tree;

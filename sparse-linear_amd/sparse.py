@@ -849,6 +849,11 @@ class DeviceMatrix(object):
         M (None, an ILU0, 'jacobi', 'sgs' or a (T1, mid, T2) triple).  The handle is borrowed: the solver keeps it alive"""
         return KrylovSolver(self, method, M)
 
+    def coloring(self, seed=0):
+        """the multicolour ordering of this whole square handle (spl_matrix_color): a Coloring with colors, perm and
+        offsets; ``coloring().krylov(method, M)`` solves with the preconditioner built in that ordering"""
+        return Coloring(self, seed)
+
     def optimize(self):
         """one-time analysis; may build the column-blocked image (csrc/spmv_blocked.hip)"""
         check("spl_matrix_optimize", lib().spl_matrix_optimize(self.handle))
@@ -1338,6 +1343,115 @@ def cg(mat, b, M=None, x0=None, rtol=1e-8, atol=0.0, maxiter=None):
 def bicgstab(mat, b, M=None, x0=None, rtol=1e-8, atol=0.0, maxiter=None):
     """(x, result dict) with mat x = b by right-preconditioned BiCGSTAB on the device; mat: a host Matrix"""
     return _krylov("bicgstab", mat, b, M, x0, rtol, atol, maxiter)
+
+
+def vector_permute_dev(n, perm_ptr, in_ptr, out_ptr, inverse=False, is_complex=False, stream=0):
+    """out[k] = in[perm[k]], or with inverse out[perm[k]] = in[k], for n entries moved as bits (spl_vector_permute_dev);
+    device pointers (ints), perm int32, in and out different arrays; enqueues on `stream`, no sync"""
+    check("spl_vector_permute_dev",
+          lib().spl_vector_permute_dev(int(n), 2 if is_complex else 1, C.c_void_p(perm_ptr), 1 if inverse else 0,
+                                       C.c_void_p(in_ptr), C.c_void_p(out_ptr), C.c_void_p(stream)))
+
+
+class Coloring(object):
+    """The multicolour ordering of a whole square device handle (csrc/coloring.hip, spl_matrix_color): ``colors`` and
+    ``perm`` are torch int32 device tensors of n entries, ``offsets`` a numpy array of ncolors + 1 class boundaries in
+    ``perm``.  colors is the serial first-fit colouring in the priority order of the seed's hash, exactly; perm lists
+    the vertices by colour and then by ascending index.  ``permute(A)`` is P A P^T, whose triangular solves and ILU(0)
+    have at most ``ncolors`` levels; ``krylov`` solves with it and answers in the original numbering."""
+    INFO_KEYS = ("n", "colors", "rounds", "largest_class", "smallest_class", "max_degree", "launches", "reserved")
+
+    def __init__(self, A, seed=0):
+        handle = A.handle  # a freed handle is refused here
+        _ffi.require_gpu()
+        import torch
+        inf = A.info()
+        n = inf["nrows_global"]
+        self.A, self.seed, self.n = A, int(seed), n
+        dev = torch.device("cuda", inf["device"])
+        out = np.zeros(8, dtype=I64)
+        off = _ffi.c_i64_p()
+        with torch.cuda.device(dev):
+            colors = torch.empty(max(n, 1), dtype=torch.int32, device=dev)
+            perm = torch.empty(max(n, 1), dtype=torch.int32, device=dev)
+            torch.cuda.current_stream().synchronize()  # the call runs on the default stream
+            check("spl_matrix_color",
+                  lib().spl_matrix_color(handle, _ffi.SPL_COLOR_hash, self.seed, C.c_void_p(colors.data_ptr()),
+                                         C.c_void_p(perm.data_ptr()), C.byref(off), _ffi.p_i64(out)))
+        self._info = tuple(int(v) for v in out)
+        self.ncolors = self._info[1]
+        self.colors, self.perm = colors[:n], perm[:n]
+        self.offsets = _ffi.take_malloced(off, self.ncolors + 1, C.c_int64, I64)
+
+    def info(self):
+        return dict(zip(self.INFO_KEYS, self._info))
+
+    def permute(self, A=None):
+        """P A P^T as a new handle: A.select(perm, perm); A: the coloured handle, or another of its size"""
+        return (self.A if A is None else A).select(self.perm, self.perm)
+
+    def _move(self, v, inverse, what):
+        import torch
+        is_tensor = isinstance(v, torch.Tensor)
+        t = v if is_tensor else torch.from_numpy(np.ascontiguousarray(v)).to(self.perm.device)
+        if not (t.is_cuda and t.dtype in (torch.float64, torch.complex128) and tuple(t.shape) == (self.n,)):
+            _oops(what, "a float64 or complex128 vector of %d entries, numpy or on the device, is needed" % self.n)
+        with torch.cuda.device(t.device):
+            t = t.contiguous()
+            out = torch.empty(max(self.n, 1), dtype=t.dtype, device=t.device)[:self.n]
+            vector_permute_dev(self.n, self.perm.data_ptr(), t.data_ptr(), out.data_ptr(), inverse,
+                               t.dtype == torch.complex128, torch.cuda.current_stream().cuda_stream)
+            return out if is_tensor else out.cpu().numpy()
+
+    def to_permuted(self, v):
+        """v in the new numbering, out[k] = v[perm[k]]: a numpy array for a numpy array, a device tensor for one"""
+        return self._move(v, False, "Coloring.to_permuted")
+
+    def from_permuted(self, v):
+        """back to the original numbering, out[perm[k]] = v[k]"""
+        return self._move(v, True, "Coloring.from_permuted")
+
+    def krylov(self, method="cg", M=None):
+        """a MulticolorKrylov: CG or BiCGSTAB on P A P^T with the preconditioner built there from None, 'jacobi',
+        'sgs', 'ilu0' or a (T1, mid, T2) triple in the new numbering"""
+        return MulticolorKrylov(self, method, M)
+
+
+class MulticolorKrylov(object):
+    """KrylovSolver on B = P A P^T of a Coloring.  ``solve`` permutes b (and x0), runs the ordinary solver on B and
+    returns x in the original numbering with the usual result dict.  ``B``, ``solver`` and, for M = 'ilu0', ``ilu``
+    (the ILU0 of B made here) are open to the caller; free() releases all three.  The solver borrows ilu's two
+    triangular solvers: after ``ilu.refactor(...)``, which replaces them, call ``solver.set_preconditioner(ilu)``."""
+
+    def __init__(self, coloring, method="cg", M=None):
+        if method not in KrylovSolver.METHODS:
+            raise ValueError("Coloring.krylov: method %r; 'cg' or 'bicgstab' is needed" % (method,))
+        self.coloring = coloring
+        self.B = coloring.permute()
+        self.ilu = None
+        if isinstance(M, str) and M == "ilu0":
+            self.ilu = M = ILU0(self.B)
+        self.solver = KrylovSolver(self.B, method, M)
+
+    def solve(self, b, x0=None, rtol=1e-8, atol=0.0, maxiter=None, check_every=0):
+        c = self.coloring
+        x, res = self.solver.solve(c.to_permuted(b), None if x0 is None else c.to_permuted(x0), rtol, atol, maxiter,
+                                   check_every)
+        return c.from_permuted(x), res
+
+    def info(self):
+        return self.solver.info()
+
+    def free(self):
+        self.solver.free()
+        if self.ilu is not None:
+            self.ilu.free()
+        self.B.free()
+
+
+def multicolor(mat, seed=0):
+    """the Coloring of the host Matrix `mat`, computed on the device"""
+    return mat.device_handle().coloring(seed)
 
 
 # ---- accessors ------------------------------------------------------------------------------
