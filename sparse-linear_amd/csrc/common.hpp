@@ -132,6 +132,7 @@ struct PanelPlan {
   int nslices = 1;                // paired form: column slices per panel (8 = one per XCD)
   int ablate = 0;                 // chunk form: timing-only ablation bits (SPL_PANEL_ABLATE with SPL_ALLOW_ABLATION=1)
   int nl = 4, gather = 4, slots = 1;  // ring form: loaders, units in flight per gatherer, slots per loader
+  int meet = 1;                   // rounds form: 1 = all workgroups meet between their panels (the rendezvous), 0 = each goes on at once
 };
 
 // workgroup-wide column-sorted panels of a row block (spmv_panel.hip): the order-free SpMV mode

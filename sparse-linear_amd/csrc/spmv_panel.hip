@@ -539,12 +539,16 @@ __device__ inline void panelq_round(pnl_u2 (&idC)[U], pnl_d2 (&aC)[U], int (&ibC
 // arrive[kArrive]: rendezvous between generations, arrive[kLeft]: workgroups that have left.  The last one to leave
 // puts both back to zero, so a stream of launches holds nothing but this kernel (the other forms clear
 // arrive[kArrive] with a memset in front of every launch).
+// meet = 0: no rendezvous, a workgroup starts its next panel at once.  The rendezvous is pacing only (it keeps an
+// XCD's CUs in the same x window); on C2 a workgroup waits 20 us of an 817 us launch there for the slowest of 256
+// (profiles/panel_claims_before.txt), and without it a step is 2.3 % shorter.  Which is better depends on the
+// matrix, so the build's one-time timing decides (tune_panel_plan); an explicit request keeps the rendezvous.
 template <int U>
 __global__ __launch_bounds__(kPanelWaves * 64) void spmv_panelq_kernel(
     int64_t nrows, int64_t npanels, int P, int w, int64_t nib, const int *__restrict__ segc,
     const int *__restrict__ ublk, const unsigned *__restrict__ key, const double *__restrict__ val,
     const double *__restrict__ x, double *__restrict__ y, int accumulate, unsigned *__restrict__ arrive,
-    int64_t dummy) {
+    int64_t dummy, int meet) {
   static_assert(U >= 3 && U <= 6, "register sets per wavefront");
   extern __shared__ __attribute__((aligned(16))) double ylds[];  // P + 1 doubles
   const pnl_u2 *key2 = reinterpret_cast<const pnl_u2 *>(key);
@@ -581,7 +585,7 @@ __global__ __launch_bounds__(kPanelWaves * 64) void spmv_panelq_kernel(
     }
     __syncthreads();  // every wavefront's LDS adds are done (s_barrier above does not wait for lgkmcnt)
     panel_store_y<false>(ylds, y, row_base, nrows, P);
-    if (g + 1 < ngen) panel_rendezvous(arrive + kArrive, g, nb);
+    if (g + 1 < ngen && meet) panel_rendezvous(arrive + kArrive, g, nb);
   }
   // leave: whoever arrives last knows that nobody will touch the rendezvous word again in this launch
   if (threadIdx.x == 0 &&
@@ -903,11 +907,11 @@ void run_paired(const PanelLaunchArgs &a, const PanelPlan &plan) {
   launch_on_image<&spmv_panelw_kernel<U, K>>(a, panel_lds_bytes(a.b), (int64_t)(a.b->nchunks / 2) << 6, plan.nslices);
 }
 template <int U>
-void run_rounds(const PanelLaunchArgs &a, const PanelPlan &) {  // the kernel itself puts the rendezvous word back
+void run_rounds(const PanelLaunchArgs &a, const PanelPlan &plan) {  // the kernel itself puts the rendezvous word back
   const PanelImage *b = a.b;
   launch_panel_kernel<&spmv_panelq_kernel<U>>(a.m->device, a.nb, panel_lds_bytes(b), a.s, a.m->nrows_local, b->npanels, b->P, b->w,
                                               b->nib, b->segc.get(), b->ublk.get(), b->key.get(), b->val.get(), a.x, a.y,
-                                              a.accumulate, b->arrive.get(), (int64_t)(b->nchunks / 2) << 6);
+                                              a.accumulate, b->arrive.get(), (int64_t)(b->nchunks / 2) << 6, plan.meet);
 }
 template <int NL, int D, int GD, int K, int S>
 void run_ring(const PanelLaunchArgs &a, const PanelPlan &) {
@@ -973,6 +977,7 @@ PanelPlan normalise(PanelPlan p) {
   if (p.form != PanelForm::Chunk) p.ablate = 0;
   if (p.form != PanelForm::Paired) p.nslices = 1;
   if (p.form != PanelForm::Ring) p.nl = p.gather = p.slots = 0;
+  if (p.form != PanelForm::Rounds) p.meet = 1;
   return p;
 }
 
@@ -1055,7 +1060,12 @@ PanelPlan panel_plan_from_code(int form, int unroll, int cols_log2, int nslices)
     case SPL_PANEL_FORM_CHUNK_K2: p.form = PanelForm::Chunk; p.kblocks = 2; break;
     case SPL_PANEL_FORM_PAIRED_K1: p.form = PanelForm::Paired; p.kblocks = 1; p.nslices = nslices; break;
     case SPL_PANEL_FORM_PAIRED_K2: p.form = PanelForm::Paired; p.kblocks = 2; p.nslices = nslices; break;
-    case SPL_PANEL_FORM_ROUNDS: p.form = PanelForm::Rounds; p.kblocks = 2; if (p.sets == 0) p.sets = 5; break;
+    case SPL_PANEL_FORM_ROUNDS:
+      p.form = PanelForm::Rounds;
+      p.kblocks = 2;
+      if (p.sets == 0) p.sets = 5;
+      p.meet = env_int("SPL_PANEL_RENDEZVOUS", 1) != 0;  // tests and ablations: an explicit request without the rendezvous
+      break;
     default:  // the ring forms, codes 6 ... 10: 1 / 2 / 3 / 4 / 8 index blocks per phase; sets is the depth of a loader
       p.form = PanelForm::Ring;
       p.kblocks = form == SPL_PANEL_FORM_RING_K8 ? 8 : form - SPL_PANEL_FORM_RING_K1 + 1;
@@ -1094,10 +1104,14 @@ static PanelPlan tune_panel_plan(const Matrix *m, const PanelImage *b, const Pan
   if (heuristic.nslices == 1) {  // the rounds form does not depend on the index blocks: the same register sets +- 1
     const int uq = unroll < 3 ? 3 : unroll > 6 ? 6 : unroll;
     for (int u2 = uq - 1; u2 <= uq + 1; ++u2)
-      if (u2 >= 3 && u2 <= 6) add(PanelForm::Rounds, kblocks, u2);
+      if (u2 >= 3 && u2 <= 6) {  // with and without the rendezvous between a workgroup's panels
+        add(PanelForm::Rounds, kblocks, u2);
+        add(PanelForm::Rounds, kblocks, u2);
+        cands.back().meet = 0;
+      }
   }
-  float best_ms = 0.f, heur_ms = 0.f;
-  PanelPlan best = heuristic;
+  float best_ms = 0.f, heur_ms = 0.f, best_meet_ms = 0.f;
+  PanelPlan best = heuristic, best_meet = heuristic;
   for (const PanelPlan &c : cands) {
     const bool q = c.form == PanelForm::Rounds;
     SPL_HIP(hipMemsetAsync(b->arrive.get(), 0, 4 * sizeof(unsigned), nullptr));  // the forms clear it differently
@@ -1109,16 +1123,21 @@ static PanelPlan tune_panel_plan(const Matrix *m, const PanelImage *b, const Pan
     float ms = 0.f;
     SPL_HIP(hipEventElapsedTime(&ms, e0, e1));
     if (verbose)
-      fprintf(stderr, "[panel] candidate %d pairs x %s: %.4f ms\n", c.sets, q ? "rounds" : c.kblocks == 2 ? "2 blocks" : "1 block", ms / 8.f);
+      fprintf(stderr, "[panel] candidate %d pairs x %s: %.4f ms\n", c.sets,
+              q ? (c.meet ? "rounds" : "rounds, no rendezvous") : c.kblocks == 2 ? "2 blocks" : "1 block", ms / 8.f);
     if (c.kblocks == kblocks && c.sets == unroll && !q) heur_ms = ms;
     if (best_ms == 0.f || ms < best_ms) { best_ms = ms; best = c; }
+    if (c.meet && (best_meet_ms == 0.f || ms < best_meet_ms)) { best_meet_ms = ms; best_meet = c; }
   }
   (void)hipEventDestroy(e0);
   (void)hipEventDestroy(e1);
+  // dropping the rendezvous has to pay by more than 1 % too, against the best candidate that keeps it
+  if (!best.meet && best_meet_ms > 0.f && best_ms > 0.99f * best_meet_ms) { best = best_meet; best_ms = best_meet_ms; }
   if (heur_ms > 0.f && best_ms > 0.99f * heur_ms) best = heuristic;  // within noise: keep the heuristic
   if (verbose)
     fprintf(stderr, "[panel] heuristic %d pairs x %d blocks: %.4f ms; chosen %d x %d%s: %.4f ms\n", unroll, kblocks,
-            heur_ms / 8.f, best.sets, best.kblocks, best.form == PanelForm::Rounds ? " (rounds)" : "", best_ms / 8.f);
+            heur_ms / 8.f, best.sets, best.kblocks,
+            best.form == PanelForm::Rounds ? (best.meet ? " (rounds)" : " (rounds, no rendezvous)") : "", best_ms / 8.f);
   SPL_HIP(hipMemsetAsync(b->arrive.get(), 0, 4 * sizeof(unsigned), nullptr));
   SPL_HIP(hipStreamSynchronize(nullptr));  // the caller's launches may go to another stream
   return best;

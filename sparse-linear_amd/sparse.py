@@ -868,7 +868,7 @@ class DeviceMatrix(object):
         storage, 1 / 2 index blocks per phase (the default's heuristic); RING_K1 ... _K8: ring form; ROUNDS: rounds form on
         the paired storage — rounds of exactly 16 * unroll pairs of chunks whatever the index blocks are (unroll 3 ... 6,
         0: 5), no column slices.  What unroll counts per form: include/sparse_linear_hip.h.
-        With everything 0 on a large matrix the build times the heuristic's neighbours, the rounds form among them,
+        With everything 0 on a large matrix the build times the heuristic's neighbours, the rounds form with and without its rendezvous among them,
         and keeps another candidate only if it is more than 1 % faster."""
         check("spl_matrix_build_panel",
               lib().spl_matrix_build_panel(self.handle, rows_per_panel, cols_log2, unroll, form))
