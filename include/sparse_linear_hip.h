@@ -789,6 +789,105 @@ int spl_matrix_color(void *H, int order, uint64_t seed, int *d_colors, int *d_pe
 int spl_vector_permute_dev(int64_t n, int value_width, const int *d_perm, int inverse, const double *d_in, double *d_out,
                            void *stream);
 
+/* ---- aggregation AMG on handles (csrc/amg.hip) --------------------------------------------------------------------------
+ * A multigrid cycle is a short sequence of SpMVs and vector updates per level, and it cuts the iteration count of CG and
+ * BiCGSTAB by an order of magnitude where ILU(0) walks hundreds of dependent levels.  The hierarchy is smoothed (or
+ * plain) aggregation on the constant, built handle to handle from the public operations above, so every level's bits
+ * are defined by theirs; the cycle is a fixed linear operator with the Krylov section's bit contract.
+ *
+ * spl_matrix_aggregate.  Graph and priority are EXACTLY those of spl_matrix_color: {i, j}, i != j, is an edge when a_ij
+ *   or a_ji is stored, stored zeros included; values are never read; h(v) is the same finaliser with the same seed
+ *   formula; u precedes v when h(u) > h(v), or they are equal and u < v.
+ *   Roots: the greedy maximal independent set of distance 2 in priority order.  Walk the vertices in priority order; an
+ *   undecided vertex becomes a root, and every undecided vertex within graph distance <= 2 of it is out (paths run
+ *   through any vertex, decided or not).  The device finds them in rounds: every undecided vertex that precedes all
+ *   other vertices within distance <= 2 that were undecided WHEN THE ROUND BEGAN becomes a root, then every undecided
+ *   vertex within distance <= 2 of a new root is out.  Roots and round count are functions of the pattern and the seed
+ *   alone.  A round is four launches (two propagations of the first undecided vertex over closed neighbourhoods, two
+ *   marking passes), each reading what the one before it finished; no kernel waits for another workgroup, there is no
+ *   floating-point operation, and the integer atomics only count.  Neither the grid (SPL_AMG_GRID, workgroups of a
+ *   launch at most, default 2048) nor the host's check interval (SPL_AMG_CHECK_EVERY rounds between two looks at the
+ *   number of undecided vertices, 1 ... 4096, default 8; a round that finds nobody undecided does nothing) shows in any
+ *   output.
+ *   Aggregates: aggregate k is rooted at the k-th root in ascending vertex index.  Phase 1: every neighbour of a root
+ *   joins that root (unique: two roots are never within distance 2).  Phase 2: every remaining vertex takes the
+ *   aggregate of that neighbour, among its neighbours assigned in phase 1, which precedes the others (one exists, by
+ *   maximality).  A vertex without edges is its own aggregate.
+ *   d_agg: n int32 in DEVICE memory.  d_roots (may be NULL): n int32 in device memory, of which the first info[1] are
+ *   written.  info: [0] n, [1] aggregates, [2] rounds, [3] largest aggregate, [4] smallest aggregate, [5] largest
+ *   degree, [6] kernel launches of csrc/amg.hip issued, [7] vertices assigned in phase 2.  n == 0: SPL_OK, 0 aggregates.
+ *   The handle may be real or complex.  The call runs on the default stream and synchronises.  Errors, in this order
+ *   before the device is touched: SPL_ERROR_invalid_handle; SPL_ERROR_argument_missing (d_agg or info NULL);
+ *   SPL_ERROR_argument_missing (d_agg / d_roots not aligned to 4 bytes); SPL_ERROR_dimension_mismatch (not square);
+ *   SPL_ERROR_invalid_matrix (a row-block handle, or one without 32-bit row pointers); then SPL_ERROR_device.
+ *
+ * spl_amg_create.  opt (may be NULL: all 0): [0] seed; [1] sweeps nu, 0 -> 1, allowed 1 ... 4; [2] coarse_size, 0 -> 256;
+ *   [3] max_levels, 0 -> 16, allowed 1 ... 64; [4] coarse_sweeps, 0 -> 4, allowed 1 ... 64; [5] flags, bit 0: plain
+ *   (unsmoothed) prolongator; [6], [7] must be 0.  A_0 = A is BORROWED and must outlive M.  Level l with matrix A_l of
+ *   n_l rows is the composition of the public handle operations, in this order:
+ *     1. d = take_diag(A_l);  dinv_i = 1 / d_i  (IEEE division; Data.Complex's quotient of (1 :+ 0) on complex handles)
+ *     2. nrm = norm_inf(scale_rows_cols(A_l, r = dinv))
+ *     3. omega = 4.0 / (3.0 * nrm), two rounded operations
+ *     4. w_i = omega * dinv_i  ((omega :+ 0) times dinv_i by Data.Complex's product on complex handles)
+ *     5. the level is the coarsest when n_l <= coarse_size, or l + 1 == max_levels, or aggregation gives n_{l+1} == n_l
+ *     6. agg = spl_matrix_aggregate(A_l, seed);  T = the n_l x n_{l+1} handle with one entry 1.0 per row at column
+ *        agg[i], made by spl_matrix_create_csr_dev
+ *     7. P = lin(1, T, -1, spgemm(scale_rows_cols(A_l, r = w), T));  plain: P = T
+ *     8. R = ctrans(P)  (transpose on real handles)
+ *     9. A_{l+1} = spgemm(R, spgemm(A_l, P)), in that association
+ *   A zero or missing diagonal gives inf / NaN in w and sets bit 0 of spl_amg_info's [7]: a warning, never a refusal
+ *   (ILU(0)'s policy); the solve that uses such a cycle ends with a non-finite outcome.  M owns every level's handles
+ *   but A_0, the weights and the work vectors.  Setup runs on the default stream and synchronises.  Errors, before
+ *   the device is touched: SPL_ERROR_invalid_handle; SPL_ERROR_argument_missing (M NULL; otherwise *M = NULL first);
+ *   SPL_ERROR_argument_missing (an option out of range or a reserved one nonzero); SPL_ERROR_dimension_mismatch (not
+ *   square); SPL_ERROR_invalid_matrix (a row-block handle, or one without 32-bit row pointers); then SPL_ERROR_device.
+ * spl_amg_level lends level `level`: *HA, *HP, *HR (P and R NULL on the coarsest level), *d_w (the device vector of n_l
+ *   entries) and dims = {n_l, n_{l+1} or 0}; every output may be NULL.  The handles are M's: they are not freed by the
+ *   caller and die with M.  A level outside [0, levels): SPL_ERROR_argument_missing.
+ * spl_amg_info: [0] n, [1] levels, [2] sum of nnz(A_l), [3] nnz(A_0), [4] coarsest n, [5] first tail level or -1,
+ *   [6] bytes of device memory held, [7] flags (1 a zero diagonal was seen, 2 complex).
+ *
+ * spl_amg_apply_dev: x = cycle(0, b), a fixed linear operator:
+ *     cycle(l, b):  x = w (.) b                                  (the first sweep from x = 0)
+ *       coarsest:   (coarse_sweeps - 1) times  t = A_l x;  x = x + w (.) (b - t);           return x
+ *       otherwise:  (nu - 1) times the same sweep
+ *                   t = A_l x;  r = b - t;  b' = R r;  e = cycle(l + 1, b');  x = x + P e
+ *                   nu times the sweep;                                                      return x
+ *   Every entry-wise operation is one difference, one product (Data.Complex's on complex handles, w first) and one sum,
+ *   each rounded once.  A_l x, R r and x + P e are spl_matrix_spmv_dev on the level handles in SPL_ORDER_REFERENCE, the
+ *   last with `accumulate`: a * x + acc in ascending column order from +0.0 (from x_i when accumulating).  (An R of
+ *   at most 16384 rows with 32 entries and more a row on average goes a wavefront a row instead: 64 products at a
+ *   time, each rounded on its own, added in that same order whatever the row's length: the serial sum exactly, and
+ *   the same bits as the SpMV for rows of up to 512 entries.)  The result is
+ *   therefore a serial restatement's bit for bit, with the SpMV's caveat for rows of more than 512 entries, as in the
+ *   Krylov section; SPL_ORDER_FREE on A voids the bits of level 0 only, in the way that section says.  The cycle is
+ *   symmetric for a Hermitian A (equal pre- and post-sweeps, the first from zero, coarse Jacobi from zero), which is
+ *   what CG needs.
+ *   The tail: the levels from the first level l on such that l and every deeper level has n <= SPL_AMG_TAIL_ROWS (read
+ *   by spl_amg_create; default 1024, 0 disables, larger values are clamped to 1024) and no row of A, P or R longer than
+ *   512 entries.  Their whole sub-cycle, down and up, is ONE launch of ONE workgroup: a lane owns a row and walks its
+ *   entries serially in ascending column order, so the bits are those of the launch-per-step path by construction; the
+ *   vectors are M's work vectors, with workgroup barriers between the steps; nothing waits on another workgroup.
+ *   Applications on one object are serialised under its lock, and one enqueued on another stream than the one before it
+ *   waits for that one on the device.  The call enqueues on `stream` and does not synchronise.  d_b and d_x are DEVICE
+ *   vectors of n entries (packed pairs on complex handles), d_b != d_x.  n == 0: SPL_OK.  Errors:
+ *   SPL_ERROR_invalid_handle; SPL_ERROR_argument_missing (a NULL or misaligned pointer, or d_b == d_x).
+ * spl_amg_apply: the same with HOST vectors, on the default stream; synchronises.
+ * spl_krylov_set_preconditioner_amg: z = cycle(0, r) as the M^-1 of the Krylov section.  M is BORROWED and may serve
+ *   several solvers.  It and spl_krylov_set_preconditioner exclude each other: each call clears what the other set;
+ *   M == NULL clears.  spl_krylov_info's [2] gains flag 16.  The cycle's kernels do not read the solver's `done`: they
+ *   write only z and M's own vectors, which nothing reads once `done` is set, so the protocol needs nothing from them.
+ *   Errors: SPL_ERROR_invalid_handle (K, or M neither NULL nor an AMG object); SPL_ERROR_dimension_mismatch (another
+ *   size, value kind or device). */
+int spl_matrix_aggregate(void *H, uint64_t seed, int *d_agg, int *d_roots, int64_t info[8]);
+int spl_amg_create(void *A, const int64_t opt[8], void **M);
+int spl_amg_info(void *M, int64_t info[8]);
+int spl_amg_level(void *M, int level, void **HA, void **HP, void **HR, const double **d_w, int64_t dims[2]);
+int spl_amg_apply_dev(void *M, const double *d_b, double *d_x, void *stream);
+int spl_amg_apply(void *M, const double *b, double *x);
+void spl_amg_free(void **M);
+int spl_krylov_set_preconditioner_amg(void *K, void *M);
+
 /* select a kernel variant for spl_matrix_spmv_dev (tuning / ablation only): 0 = default
  * (whatever spl_matrix_optimize chose), 1-6 CSR-stream shapes, 7 sub-wavefront kernel, 8
  * column-blocked image, 9-11 gather cache policies, 15 sliced-ELL image, 16 column-sorted panel

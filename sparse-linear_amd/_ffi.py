@@ -169,6 +169,13 @@ def _declare(L):
         "spl_krylov_info": [C.c_void_p, c_i64_p],
         "spl_matrix_color": [C.c_void_p, i, u64, C.c_void_p, C.c_void_p, C.POINTER(c_i64_p), c_i64_p],
         "spl_vector_permute_dev": [i64, i, C.c_void_p, i, C.c_void_p, C.c_void_p, C.c_void_p],
+        "spl_matrix_aggregate": [C.c_void_p, u64, C.c_void_p, C.c_void_p, c_i64_p],
+        "spl_amg_create": [C.c_void_p, c_i64_p, c_void_pp],
+        "spl_amg_info": [C.c_void_p, c_i64_p],
+        "spl_amg_level": [C.c_void_p, i, c_void_pp, c_void_pp, c_void_pp, c_void_pp, c_i64_p],
+        "spl_amg_apply_dev": [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p],
+        "spl_amg_apply": [C.c_void_p, c_dbl_p, c_dbl_p],
+        "spl_krylov_set_preconditioner_amg": [C.c_void_p, C.c_void_p],
         "spl_matrix_set_variant": [C.c_void_p, i],
         "spl_matrix_optimize": [C.c_void_p],
         "spl_matrix_build_blocked": [C.c_void_p, i, i, i],
@@ -204,6 +211,9 @@ def _declare(L):
     if hasattr(L, "spl_krylov_free"):
         L.spl_krylov_free.restype = None
         L.spl_krylov_free.argtypes = [c_void_pp]
+    if hasattr(L, "spl_amg_free"):
+        L.spl_amg_free.restype = None
+        L.spl_amg_free.argtypes = [c_void_pp]
     if hasattr(L, "spl_peer_exchange_free"):
         L.spl_peer_exchange_free.restype = None
         L.spl_peer_exchange_free.argtypes = [c_void_pp]

@@ -1821,6 +1821,132 @@ int spl_vector_permute_dev(int64_t n, int value_width, const int *d_perm, int in
   });
 }
 
+// ---- aggregation AMG on handles (csrc/amg.hip) ---------------------------------------------------------------------------
+// H is borrowed for the call; d_agg and d_roots are the caller's device arrays
+int spl_matrix_aggregate(void *H, uint64_t seed, int *d_agg, int *d_roots, int64_t info[8]) {
+  Matrix *A = as_matrix(H);
+  if (!A) return SPL_ERROR_invalid_handle;
+  if (!d_agg || !info) return SPL_ERROR_argument_missing;
+  if ((uintptr_t)d_agg % sizeof(int) != 0 || (uintptr_t)d_roots % sizeof(int) != 0) return SPL_ERROR_argument_missing;
+  if (A->nrows_global != A->ncols) return SPL_ERROR_dimension_mismatch;
+  if (!whole(A) || A->nnz >= (int64_t)0x7fffffff || (A->nrows_local > 0 && !A->rowptr.get())) return SPL_ERROR_invalid_matrix;
+  return guarded([&]() -> int {
+    (void)current_device();
+    DeviceGuard g(A->device);
+    return aggregate_handle(A, seed, d_agg, d_roots, info);
+  });
+}
+
+// A is borrowed: the object keeps the pointer; every other level, the weights and the work vectors are its own
+int spl_amg_create(void *A, const int64_t opt[8], void **M) {
+  Matrix *H = as_matrix(A);
+  if (!H) return SPL_ERROR_invalid_handle;
+  if (!M) return SPL_ERROR_argument_missing;
+  *M = nullptr;
+  int64_t o[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+  if (opt) memcpy(o, opt, sizeof(o));
+  if (o[1] == 0) o[1] = 1;
+  if (o[2] == 0) o[2] = 256;
+  if (o[3] == 0) o[3] = 16;
+  if (o[4] == 0) o[4] = 4;
+  if (o[1] < 1 || o[1] > 4 || o[2] < 0 || o[3] < 1 || o[3] > 64 || o[4] < 1 || o[4] > 64 || (o[5] & ~(int64_t)1) != 0 ||
+      o[6] != 0 || o[7] != 0)
+    return SPL_ERROR_argument_missing;
+  if (H->nrows_global != H->ncols) return SPL_ERROR_dimension_mismatch;
+  if (!whole(H) || H->nnz >= (int64_t)0x7fffffff || (H->nrows_local > 0 && !H->rowptr.get())) return SPL_ERROR_invalid_matrix;
+  return guarded([&]() -> int {
+    (void)current_device();
+    DeviceGuard g(H->device);
+    Amg *S = nullptr;
+    const int st = amg_create(H, o, &S);
+    *M = S;
+    return st;
+  });
+}
+
+int spl_amg_info(void *M, int64_t info[8]) {
+  Amg *S = as_amg(M);
+  if (!S) return SPL_ERROR_invalid_handle;
+  if (!info) return SPL_ERROR_argument_missing;
+  amg_info(S, info);
+  return SPL_OK;
+}
+
+// the handles and the weights are lent: they live as long as M does and are not the caller's to free
+int spl_amg_level(void *M, int level, void **HA, void **HP, void **HR, const double **d_w, int64_t dims[2]) {
+  Amg *S = as_amg(M);
+  if (!S) return SPL_ERROR_invalid_handle;
+  int64_t info[8];
+  amg_info(S, info);
+  if (level < 0 || level >= info[1]) return SPL_ERROR_argument_missing;
+  amg_level(S, level, HA, HP, HR, d_w, dims);
+  return SPL_OK;
+}
+
+int spl_amg_apply_dev(void *M, const double *d_b, double *d_x, void *stream) {
+  Amg *S = as_amg(M);
+  if (!S) return SPL_ERROR_invalid_handle;
+  if (amg_rows(S) == 0) return SPL_OK;
+  if (!d_b || !d_x || d_b == d_x) return SPL_ERROR_argument_missing;
+  const uintptr_t entry = (uintptr_t)(8 * amg_width(S));  // the kernels load and store whole entries
+  if ((uintptr_t)d_b % entry != 0 || (uintptr_t)d_x % entry != 0) return SPL_ERROR_argument_missing;
+  return guarded([&]() -> int {
+    DeviceGuard g(amg_device(S));
+    return amg_apply(S, d_b, d_x, as_stream(stream), nullptr);
+  });
+}
+
+// host vectors of n entries, packed complex: up, one cycle on the default stream, down
+int spl_amg_apply(void *M, const double *b, double *x) {
+  Amg *S = as_amg(M);
+  if (!S) return SPL_ERROR_invalid_handle;
+  if (amg_rows(S) == 0) return SPL_OK;
+  if (!b || !x) return SPL_ERROR_argument_missing;
+  return guarded([&]() -> int {
+    DeviceGuard g(amg_device(S));
+    hipStream_t s = nullptr;
+    const size_t count = (size_t)amg_rows(S) * (size_t)amg_width(S);
+    DBuf<double> d(2 * count);
+    double *d_b = d.get(), *d_x = d.get() + count;
+    SPL_HIP(hipMemcpyAsync(d_b, b, count * sizeof(double), hipMemcpyHostToDevice, s));
+    const int st = amg_apply(S, d_b, d_x, s, nullptr);
+    if (st != SPL_OK) {
+      (void)hipStreamSynchronize(s);
+      return st;
+    }
+    SPL_HIP(hipMemcpyAsync(x, d_x, count * sizeof(double), hipMemcpyDeviceToHost, s));
+    SPL_HIP(hipStreamSynchronize(s));
+    return SPL_OK;
+  });
+}
+
+void spl_amg_free(void **M) {
+  if (!M || !*M) return;
+  Amg *S = as_amg(*M);
+  *M = nullptr;
+  if (!S) return;
+  int prev = -1;
+  const bool have_prev = hipGetDevice(&prev) == hipSuccess;
+  (void)hipSetDevice(amg_device(S));  // may run on a finalizer thread with another current device
+  amg_delete(S);
+  if (have_prev) (void)hipSetDevice(prev);
+}
+
+// M is borrowed and may serve several solvers; NULL takes the preconditioner away
+int spl_krylov_set_preconditioner_amg(void *K, void *M) {
+  Krylov *S = as_krylov(K);
+  if (!S) return SPL_ERROR_invalid_handle;
+  Amg *P = nullptr;
+  if (M) {
+    P = as_amg(M);
+    if (!P) return SPL_ERROR_invalid_handle;
+    if (amg_rows(P) != krylov_rows(S) || amg_width(P) != krylov_width(S) || amg_device(P) != krylov_device(S))
+      return SPL_ERROR_dimension_mismatch;
+  }
+  krylov_set_preconditioner_amg(S, P);
+  return SPL_OK;
+}
+
 // mulM on Complex Double (the reference's SPECIALIZE instance, Sparse.hs:475): one axpy_ per column of B there; here the
 // packed-complex image of A and one multi-vector product.  B and C are row-major like spl_mulm's; the kernel wants one
 // vector after the other, so both are turned on the device (the call is bounded by its copies over PCIe).

@@ -29,26 +29,13 @@
 namespace spl {
 namespace {
 
-constexpr uint64_t kGolden = 0x9E3779B97F4A7C15ull;
+constexpr uint64_t kGolden = kColorGolden;
 constexpr int kCheckEveryDefault = 8, kCheckEveryMax = 4096;
 constexpr int kHistBins = 256;  // colours counted in LDS; higher ones go to memory one by one
 constexpr int kPending = 1024;  // waiting vertices a workgroup collects in LDS before they go to the next worklist
 constexpr int kGridDefault = 2048;  // workgroups of a launch at most: eight per CU
 
-__host__ __device__ inline uint64_t priority(uint64_t v, uint64_t base) {  // base = kGolden * (seed + 1)
-  uint64_t z = v + base;
-  z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-  z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-  return z ^ (z >> 31);
-}
-
-// A's pattern and the pattern of its transpose (rows unordered)
-struct ColorGraph {
-  const int *ptr;       // n + 1
-  const int *col;       // nnz
-  const int64_t *tptr;  // n + 1
-  const int *tcol;      // nnz
-};
+__host__ __device__ inline uint64_t priority(uint64_t v, uint64_t base) { return color_priority(v, base); }
 
 template <int G>
 __device__ inline unsigned long long group_or(unsigned long long v) {
@@ -255,6 +242,41 @@ void for_group(int group, F &&f) {
 
 }  // namespace
 
+// The transposed pattern of A (n > 0) into buf, and the view of both sides; aggregation (amg.hip) walks the same graph
+ColorGraph build_color_graph(const Matrix *A, int64_t grid_cap, ColorGraphBuffers &buf, int64_t *launches, hipStream_t s) {
+  const int n = (int)A->nrows_local;
+  const int64_t nnz = A->nnz;
+  const int G = group_for((double)nnz / (double)n);
+  buf.counts.alloc((size_t)n);
+  buf.tcol.alloc((size_t)nnz);
+  buf.tptr.alloc((size_t)n + 1);
+  SPL_HIP(hipMemsetAsync(buf.counts.get(), 0, (size_t)n * sizeof(int), s));
+  if (nnz > 0) {
+    hipLaunchKernelGGL(color_count_columns_kernel, dim3(grid_flat(nnz, grid_cap)), dim3(kRowThreads), 0, s,
+                       A->colidx.get(), nnz, buf.counts.get());
+    ++*launches;
+  }
+  exclusive_scan_i32_to_i64(buf.counts.get(), buf.tptr.get(), n, s);
+  SPL_HIP(hipMemsetAsync(buf.counts.get(), 0, (size_t)n * sizeof(int), s));
+  if (nnz > 0) {
+    for_group(G, [&](auto g) {
+      hipLaunchKernelGGL((color_fill_transpose_kernel<decltype(g)::value>), dim3(grid_rows(n, G, grid_cap)),
+                         dim3(kRowThreads), 0, s, A->rowptr.get(), A->colidx.get(), n, buf.tptr.get(), buf.counts.get(),
+                         buf.tcol.get());
+    });
+    ++*launches;
+  }
+  return ColorGraph{A->rowptr.get(), A->colidx.get(), buf.tptr.get(), buf.tcol.get()};
+}
+
+// *d_max_degree (zeroed by the caller) receives the largest number of distinct neighbours; enqueues one launch on s
+void color_graph_max_degree(const ColorGraph &graph, int n, int G, int64_t grid_cap, int *d_max_degree, hipStream_t s) {
+  for_group(G, [&](auto g) {
+    hipLaunchKernelGGL((color_degree_kernel<decltype(g)::value>), dim3(grid_rows(n, G, grid_cap)), dim3(kRowThreads), 0, s,
+                       graph, n, d_max_degree);
+  });
+}
+
 // A: whole, square, 32-bit row pointers (the caller checked); d_colors n ints, d_perm n ints or nullptr, offsets
 // nullptr or the place for a malloc()'d array of info[1] + 1 entries.  Default stream; synchronises
 int color_handle(const Matrix *A, uint64_t seed, int *d_colors, int *d_perm, int64_t **offsets, int64_t info[8]) {
@@ -278,31 +300,11 @@ int color_handle(const Matrix *A, uint64_t seed, int *d_colors, int *d_perm, int
   const uint64_t base = kGolden * (seed + 1);
 
   // the transposed pattern
-  DBuf<int> counts((size_t)n), tcol((size_t)nnz);
-  DBuf<int64_t> tptr((size_t)n + 1);
-  SPL_HIP(hipMemsetAsync(counts.get(), 0, (size_t)n * sizeof(int), s));
-  if (nnz > 0) {
-    hipLaunchKernelGGL(color_count_columns_kernel, dim3(grid_flat(nnz, grid_cap)), dim3(kRowThreads), 0, s,
-                       A->colidx.get(), nnz, counts.get());
-    ++launches;
-  }
-  exclusive_scan_i32_to_i64(counts.get(), tptr.get(), n, s);
-  SPL_HIP(hipMemsetAsync(counts.get(), 0, (size_t)n * sizeof(int), s));
-  if (nnz > 0) {
-    for_group(G, [&](auto g) {
-      hipLaunchKernelGGL((color_fill_transpose_kernel<decltype(g)::value>), dim3(grid_rows(n, G, grid_cap)),
-                         dim3(kRowThreads), 0, s, A->rowptr.get(), A->colidx.get(), n, tptr.get(), counts.get(),
-                         tcol.get());
-    });
-    ++launches;
-  }
-  const ColorGraph graph{A->rowptr.get(), A->colidx.get(), tptr.get(), tcol.get()};
+  ColorGraphBuffers sides;
+  const ColorGraph graph = build_color_graph(A, grid_cap, sides, &launches, s);
   DBuf<int> scalars(2);  // [0] largest degree, [1] largest colour
   SPL_HIP(hipMemsetAsync(scalars.get(), 0, 2 * sizeof(int), s));
-  for_group(G, [&](auto g) {
-    hipLaunchKernelGGL((color_degree_kernel<decltype(g)::value>), dim3(grid_rows(n, G, grid_cap)), dim3(kRowThreads), 0, s,
-                       graph, n, scalars.get());
-  });
+  color_graph_max_degree(graph, n, G, grid_cap, scalars.get(), s);
   ++launches;
   SPL_HIP(hipGetLastError());
 

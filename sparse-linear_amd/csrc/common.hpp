@@ -345,6 +345,51 @@ void krylov_delete(Krylov *K);
 int color_handle(const Matrix *A, uint64_t seed, int *d_colors, int *d_perm, int64_t **offsets, int64_t info[8]);
 // out[k] = in[perm[k]] (inverse == 0) or out[perm[k]] = in[k], entries of vw doubles moved as bits; n > 0; enqueues on s
 void vector_permute(int64_t n, int vw, const int *d_perm, int inverse, const double *d_in, double *d_out, hipStream_t s);
+// The priority both the colouring and the aggregation order the vertices by: the splitmix64 finaliser of v + base,
+// base = kColorGolden * (seed + 1); u precedes v when h(u) > h(v), or they are equal and u < v
+constexpr uint64_t kColorGolden = 0x9E3779B97F4A7C15ull;
+__host__ __device__ inline uint64_t color_priority(uint64_t v, uint64_t base) {
+  uint64_t z = v + base;
+  z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
+  z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
+  return z ^ (z >> 31);
+}
+// The graph both the colouring and the aggregation walk: A's pattern and the pattern of its transpose (rows unordered);
+// {i, j}, i != j, is an edge when it is stored on either side
+struct ColorGraph {
+  const int *ptr;       // n + 1
+  const int *col;       // nnz
+  const int64_t *tptr;  // n + 1
+  const int *tcol;      // nnz
+};
+struct ColorGraphBuffers {
+  DBuf<int> counts, tcol;
+  DBuf<int64_t> tptr;
+};
+// A: whole, square, 32-bit row pointers, n > 0.  The transposed pattern goes to buf; *launches grows by the kernels
+ColorGraph build_color_graph(const Matrix *A, int64_t grid_cap, ColorGraphBuffers &buf, int64_t *launches, hipStream_t s);
+// *d_max_degree (zeroed by the caller): the largest number of distinct neighbours; G lanes a vertex; one launch on s
+void color_graph_max_degree(const ColorGraph &graph, int n, int G, int64_t grid_cap, int *d_max_degree, hipStream_t s);
+
+// ---- aggregation AMG on handles (amg.hip) ---------------------------------------------------------------------------
+// A: whole, square, 32-bit row pointers (the caller checked).  d_agg: n ints; d_roots: n ints or nullptr.  Default
+// stream; synchronises.  SPL_OK
+int aggregate_handle(const Matrix *A, uint64_t seed, int *d_agg, int *d_roots, int64_t info[8]);
+struct Amg;
+Amg *as_amg(void *m);  // nullptr unless m carries the object's magic word
+// A: whole and square (the caller checked), borrowed; opt: the eight options with the defaults filled in and checked
+int amg_create(Matrix *A, const int64_t opt[8], Amg **out);
+void amg_info(Amg *M, int64_t info[8]);
+// level in [0, levels): the level's handles (P and R nullptr on the coarsest), its weights and {n_l, n_{l+1} or 0}
+void amg_level(Amg *M, int level, void **HA, void **HP, void **HR, const double **d_w, int64_t dims[2]);
+// x = cycle(0, b); d_b != d_x (the caller checked); enqueues on s.  *launches (may be nullptr): kernels enqueued
+int amg_apply(Amg *M, const double *d_b, double *d_x, hipStream_t s, int64_t *launches);
+int amg_device(const Amg *M);
+int64_t amg_rows(const Amg *M);
+int amg_width(const Amg *M);  // doubles per entry: 1 real, 2 packed complex
+void amg_delete(Amg *M);
+// M: borrowed, of K's size, value kind and device (the caller checked), or nullptr; clears the triangular parts
+void krylov_set_preconditioner_amg(Krylov *K, Amg *M);
 
 // ---- multifrontal LU without interchanges (multifrontal.hip, mf_symbolic.hpp) ------------------
 namespace mf {

@@ -537,6 +537,7 @@ struct Krylov {
   const Matrix *A = nullptr;                 // borrowed
   TriSolver *T1 = nullptr, *T2 = nullptr;    // borrowed
   const double *d_mid = nullptr;             // borrowed
+  Amg *amg = nullptr;                        // borrowed; set: the three parts above are not
   int nvec = 0;
   DBuf<double> work;     // nvec vectors
   DBuf<double> scratch;  // partials of the fold
@@ -547,7 +548,7 @@ struct Krylov {
   std::mutex lock;       // one solve at a time
   int64_t solves = 0, last_iterations = 0, last_launches = 0;
   double *vec(int i) const { return work.get() + (size_t)i * (size_t)n * (size_t)vw; }
-  bool preconditioned() const { return T1 || T2 || d_mid; }
+  bool preconditioned() const { return T1 || T2 || d_mid || amg; }
 };
 
 Krylov *as_krylov(void *k) {
@@ -580,6 +581,14 @@ void krylov_set_preconditioner(Krylov *K, TriSolver *T1, const double *d_mid, Tr
   K->T1 = T1;
   K->d_mid = d_mid;
   K->T2 = T2;
+  K->amg = nullptr;
+}
+
+void krylov_set_preconditioner_amg(Krylov *K, Amg *M) {
+  std::lock_guard<std::mutex> hold(K->lock);
+  K->T1 = K->T2 = nullptr;
+  K->d_mid = nullptr;
+  K->amg = M;
 }
 
 namespace {
@@ -628,9 +637,16 @@ struct Run {
     ++launches;
     return launch_spmv(K->A, x, y, 0, s);
   }
-  // out = T2^-1 (d_mid (.) (T1^-1 in)); called only when a part is set
+  // out = T2^-1 (d_mid (.) (T1^-1 in)), or the AMG cycle of `in`; called only when a part is set.  The cycle's
+  // kernels do not read `done`: they write `out` and the AMG object's own vectors only, which nothing reads once it is set
   int apply(const double *in, double *out) {
     ++applications;
+    if (K->amg) {
+      int64_t enqueued = 0;
+      const int e = amg_apply(K->amg, in, out, s, &enqueued);
+      launches += enqueued;
+      return e;
+    }
     const double *cur = in;
     int64_t info[8];
     if (K->T1) {
@@ -821,7 +837,7 @@ void krylov_info(Krylov *K, int64_t info[8]) {
   std::lock_guard<std::mutex> hold(K->lock);
   info[0] = K->n;
   info[1] = K->method;
-  info[2] = (K->vw == 2 ? 1 : 0) | (K->T1 ? 2 : 0) | (K->d_mid ? 4 : 0) | (K->T2 ? 8 : 0);
+  info[2] = (K->vw == 2 ? 1 : 0) | (K->T1 ? 2 : 0) | (K->d_mid ? 4 : 0) | (K->T2 ? 8 : 0) | (K->amg ? 16 : 0);
   info[3] = (int64_t)K->bytes;
   info[4] = K->solves;
   info[5] = K->last_iterations;

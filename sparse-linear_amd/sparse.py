@@ -29,6 +29,8 @@ are solved on the device by ``DeviceMatrix.triangular`` / ``TriangularSolver`` (
 and ``DeviceMatrix.ilu0`` / ``ILU0`` (``ilu0`` from a host Matrix) produces the incomplete factors those solvers apply.
 ``DeviceMatrix.krylov`` / ``KrylovSolver`` (``cg`` / ``bicgstab`` from a host Matrix) solve ``A x = b`` with them:
 preconditioned CG and BiCGSTAB whose scalars stay on the device; ``vector_dot_dev`` is their fixed-order inner product.
+``DeviceMatrix.amg`` / ``AMG`` (``amg`` from a host Matrix) build an aggregation multigrid hierarchy from the handle
+operations above, and its V-cycle is a preconditioner the solvers take (``M=<AMG>`` or ``M="amg"``).
 """
 import ctypes as C
 import weakref
@@ -854,6 +856,39 @@ class DeviceMatrix(object):
         offsets; ``coloring().krylov(method, M)`` solves with the preconditioner built in that ordering"""
         return Coloring(self, seed)
 
+    @classmethod
+    def _borrowed(cls, handle, owner):
+        """a view of a handle that `owner` frees: free() and the collector leave the handle alone"""
+        view = cls.__new__(cls)
+        view._h = C.c_void_p(handle)
+        view._finalizer = lambda: None
+        view._owner = owner
+        return view
+
+    def aggregate(self, seed=0):
+        """the aggregation of this whole square handle's graph (spl_matrix_aggregate): a dict with ``agg`` (n) and
+        ``roots`` (one per aggregate) as torch int32 device tensors and ``info`` (AMG.AGGREGATE_KEYS)"""
+        handle = self.handle
+        _ffi.require_gpu()
+        import torch
+        inf = self.info()
+        n = inf["nrows_global"]
+        dev = torch.device("cuda", inf["device"])
+        out = np.zeros(8, dtype=I64)
+        with torch.cuda.device(dev):
+            agg = torch.empty(max(n, 1), dtype=torch.int32, device=dev)
+            roots = torch.empty(max(n, 1), dtype=torch.int32, device=dev)
+            torch.cuda.current_stream().synchronize()  # the call runs on the default stream
+            check("spl_matrix_aggregate",
+                  lib().spl_matrix_aggregate(handle, int(seed), C.c_void_p(agg.data_ptr()), C.c_void_p(roots.data_ptr()),
+                                             _ffi.p_i64(out)))
+        return {"agg": agg[:n], "roots": roots[:int(out[1])], "info": dict(zip(AMG.AGGREGATE_KEYS, (int(v) for v in out)))}
+
+    def amg(self, **options):
+        """the aggregation AMG hierarchy of this whole square handle (spl_amg_create): an AMG object; options: seed,
+        sweeps, coarse_size, max_levels, coarse_sweeps, plain.  The handle is borrowed: the object keeps it alive"""
+        return AMG(self, **options)
+
     def optimize(self):
         """one-time analysis; may build the column-blocked image (csrc/spmv_blocked.hip)"""
         check("spl_matrix_optimize", lib().spl_matrix_optimize(self.handle))
@@ -1156,7 +1191,9 @@ class KrylovSolver(object):
     ``M``: None; an ``ILU0``; ``"jacobi"`` (1 / diag(A)); ``"sgs"`` (symmetric Gauss-Seidel: tril(A), diag(A), triu(A));
     or a triple ``(T1, mid, T2)`` of a TriangularSolver or None, a torch device vector of n entries or None, and a
     TriangularSolver or None, applied as ``z = T2^-1 (mid * (T1^-1 r))``.  The object keeps references to A and to the
-    parts of M, so nothing it borrows is collected under it; ``parts`` is the triple in use."""
+    parts of M, so nothing it borrows is collected under it; ``parts`` is the triple in use.  An ``AMG`` object, or
+    ``"amg"`` (one built here with the defaults and freed with the solver), makes its V-cycle the preconditioner
+    instead of the triple; ``amg`` is the one in use."""
     METHODS = {"cg": _ffi.SPL_KRYLOV_cg, "bicgstab": _ffi.SPL_KRYLOV_bicgstab}
     REASONS = ("converged", "max_iter", "breakdown", "non_finite")
     INFO_KEYS = ("n", "method", "flags", "device_bytes", "solves", "iterations", "launches_per_iteration", "reserved")
@@ -1170,7 +1207,8 @@ class KrylovSolver(object):
         self.A = A
         self.method = method
         self.parts = (None, None, None)
-        self._owned = []  # what "jacobi" and "sgs" made here
+        self.amg = None   # the AMG in use: M itself, or the one "amg" made here
+        self._owned = []  # what "jacobi", "sgs" and "amg" made here
         self._M = M       # an ILU0 stays alive with its solvers
         check("spl_krylov_create", lib().spl_krylov_create(A.handle, self.METHODS[method], C.byref(self._k)))
         self.set_preconditioner(M)
@@ -1207,6 +1245,16 @@ class KrylovSolver(object):
     def set_preconditioner(self, M):
         """replaces the preconditioner (the forms of the class docstring)"""
         owned = []
+        if isinstance(M, AMG) or (isinstance(M, str) and M == "amg"):
+            cycle = M
+            if isinstance(M, str):  # built here with the defaults, and freed with the solver
+                cycle = AMG(self.A)
+                owned = [cycle]
+            check("spl_krylov_set_preconditioner_amg", lib().spl_krylov_set_preconditioner_amg(self.handle, cycle.handle))
+            for part in self._owned:
+                part.free()
+            self._owned, self.parts, self._M, self.amg = owned, (None, None, None), cycle, cycle
+            return
         if M is None:
             parts = (None, None, None)
         elif isinstance(M, ILU0):
@@ -1220,7 +1268,8 @@ class KrylovSolver(object):
         elif isinstance(M, (tuple, list)) and len(M) == 3:
             parts = tuple(M)
         else:
-            raise ValueError("KrylovSolver: M %r; None, an ILU0, 'jacobi', 'sgs' or a (T1, mid, T2) triple is needed" % (M,))
+            raise ValueError("KrylovSolver: M %r; None, an ILU0, an AMG, 'jacobi', 'sgs', 'amg' or a (T1, mid, T2) triple "
+                             "is needed" % (M,))
         t1, mid, t2 = parts
         if mid is not None:
             n, cplx = self.info()["n"], self.A.is_complex
@@ -1235,13 +1284,14 @@ class KrylovSolver(object):
                                                   t2.handle if t2 is not None else None))
         for part in self._owned:
             part.free()
-        self._owned, self.parts, self._M = owned, parts, M
+        self._owned, self.parts, self._M, self.amg = owned, parts, M, None
 
     def info(self):
         out = np.zeros(8, dtype=I64)
         check("spl_krylov_info", lib().spl_krylov_info(self.handle, _ffi.p_i64(out)))
         d = dict(zip(self.INFO_KEYS, (int(v) for v in out)))
-        d.update(complex=bool(d["flags"] & 1), T1=bool(d["flags"] & 2), mid=bool(d["flags"] & 4), T2=bool(d["flags"] & 8))
+        d.update(complex=bool(d["flags"] & 1), T1=bool(d["flags"] & 2), mid=bool(d["flags"] & 4), T2=bool(d["flags"] & 8),
+                 amg=bool(d["flags"] & 16))
         return d
 
     @classmethod
@@ -1343,6 +1393,120 @@ def cg(mat, b, M=None, x0=None, rtol=1e-8, atol=0.0, maxiter=None):
 def bicgstab(mat, b, M=None, x0=None, rtol=1e-8, atol=0.0, maxiter=None):
     """(x, result dict) with mat x = b by right-preconditioned BiCGSTAB on the device; mat: a host Matrix"""
     return _krylov("bicgstab", mat, b, M, x0, rtol, atol, maxiter)
+
+
+class _DeviceArray(object):
+    """n entries of device memory the library lends, in the form torch.as_tensor reads without a copy"""
+
+    def __init__(self, ptr, n, typestr):
+        self.__cuda_array_interface__ = {"shape": (int(n),), "typestr": typestr, "data": (int(ptr), False), "version": 2}
+
+
+class AMG(object):
+    """Owner of a ``void *M`` from ``spl_amg_create``: the aggregation AMG hierarchy of a whole square device handle and
+    its V-cycle (csrc/amg.hip), real or complex.  Every level is the composition of the public handle operations that
+    include/sparse_linear_hip.h lists, and ``apply`` is that header's cycle bit for bit.  ``KrylovSolver(A, method, M=amg)``
+    takes it as the preconditioner; one AMG may serve several solvers.  The object keeps a reference to A, which it
+    borrows as level 0."""
+    OPTIONS = ("seed", "sweeps", "coarse_size", "max_levels", "coarse_sweeps", "plain")
+    INFO_KEYS = ("n", "levels", "nnz_total", "nnz_fine", "coarsest_n", "tail_first", "device_bytes", "flags")
+    AGGREGATE_KEYS = ("n", "aggregates", "rounds", "largest", "smallest", "max_degree", "launches", "phase2")
+
+    def __init__(self, A, **options):
+        unknown = sorted(set(options) - set(self.OPTIONS))
+        if unknown:
+            raise TypeError("AMG: unknown option %s; the options are %s" % (", ".join(unknown), ", ".join(self.OPTIONS)))
+        self._m = C.c_void_p()
+        self._finalizer = weakref.finalize(self, AMG._free, self._m)
+        self.A = A
+        opt = np.zeros(8, dtype=I64)
+        opt[0] = int(options.get("seed", 0))
+        opt[1] = int(options.get("sweeps", 0))
+        opt[2] = int(options.get("coarse_size", 0))
+        opt[3] = int(options.get("max_levels", 0))
+        opt[4] = int(options.get("coarse_sweeps", 0))
+        opt[5] = 1 if options.get("plain", False) else 0
+        check("spl_amg_create", lib().spl_amg_create(A.handle, _ffi.p_i64(opt), C.byref(self._m)))
+
+    @staticmethod
+    def _free(m):
+        try:
+            lib().spl_amg_free(C.byref(m))
+        except Exception:  # interpreter shutdown
+            pass
+
+    def free(self):
+        self._finalizer()
+
+    @property
+    def handle(self):
+        if not self._m.value:
+            raise _ffi.SparseLinearError("AMG", _ffi.SPL_ERROR_invalid_handle)
+        return self._m
+
+    def info(self):
+        out = np.zeros(8, dtype=I64)
+        check("spl_amg_info", lib().spl_amg_info(self.handle, _ffi.p_i64(out)))
+        d = dict(zip(self.INFO_KEYS, (int(v) for v in out)))
+        d.update(zero_diagonal=bool(d["flags"] & 1), complex=bool(d["flags"] & 2),
+                 operator_complexity=d["nnz_total"] / float(d["nnz_fine"]) if d["nnz_fine"] else 1.0)
+        return d
+
+    @property
+    def levels(self):
+        return self.info()["levels"]
+
+    def level(self, l):
+        """level l as a dict: ``A``, ``P``, ``R`` (borrowed DeviceMatrix views that do not free; P and R None on the
+        coarsest level), ``w`` (a copy of the weights as a torch device tensor) and ``dims`` = (n_l, n_{l+1} or 0)"""
+        import torch
+        ha, hp, hr, pw = C.c_void_p(), C.c_void_p(), C.c_void_p(), C.c_void_p()
+        dims = np.zeros(2, dtype=I64)
+        check("spl_amg_level",
+              lib().spl_amg_level(self.handle, int(l), C.byref(ha), C.byref(hp), C.byref(hr), C.byref(pw), _ffi.p_i64(dims)))
+        inf = self.info()
+        n = int(dims[0])
+        with torch.cuda.device(self.A.info()["device"]):
+            if n:
+                lent = _DeviceArray(pw.value, n, "<c16" if inf["complex"] else "<f8")
+                w = torch.as_tensor(lent, device="cuda").clone()  # the object's memory is read, the copy is the caller's
+            else:
+                w = torch.empty(0, dtype=torch.complex128 if inf["complex"] else torch.float64, device="cuda")
+        view = lambda h: DeviceMatrix._borrowed(h.value, self) if h.value else None  # noqa: E731
+        return {"A": view(ha), "P": view(hp), "R": view(hr), "w": w, "dims": (n, int(dims[1]))}
+
+    def apply_dev(self, b_ptr, x_ptr, stream=0):
+        """x = cycle(0, b): device pointers (ints) to n doubles, or packed pairs; b and x different arrays; enqueues on
+        `stream`, no sync"""
+        check("spl_amg_apply_dev",
+              lib().spl_amg_apply_dev(self.handle, C.c_void_p(b_ptr), C.c_void_p(x_ptr), C.c_void_p(stream)))
+
+    def apply(self, b):
+        """the cycle of b: a numpy array for a numpy array, a device tensor (on torch's current stream) for one"""
+        inf = self.info()
+        n, cplx = inf["n"], inf["complex"]
+        import torch
+        if isinstance(b, torch.Tensor):
+            want = torch.complex128 if cplx else torch.float64
+            if not (b.is_cuda and b.dtype == want and tuple(b.shape) == (n,)):
+                _oops("AMG.apply", "a device tensor of %d %s entries is needed" % (n, want))
+            with torch.cuda.device(b.device):
+                bb = b.contiguous()
+                x = torch.empty(max(n, 1), dtype=want, device=b.device)[:n]
+                self.apply_dev(bb.data_ptr(), x.data_ptr(), torch.cuda.current_stream().cuda_stream)
+            return x
+        want = C128 if cplx else F64
+        a = np.ascontiguousarray(b)
+        if a.dtype != want or a.shape != (n,):
+            _oops("AMG.apply", "a vector of dtype %s and shape %s; %d %s entries are needed" % (a.dtype, a.shape, n, np.dtype(want)))
+        x = np.zeros(n, dtype=want)
+        check("spl_amg_apply", lib().spl_amg_apply(self.handle, p_f64(a.view(F64)), p_f64(x.view(F64))))
+        return x
+
+
+def amg(mat, **options):
+    """the AMG object of the host Matrix `mat`, built on the device"""
+    return mat.device_handle().amg(**options)
 
 
 def vector_permute_dev(n, perm_ptr, in_ptr, out_ptr, inverse=False, is_complex=False, stream=0):
