@@ -888,6 +888,81 @@ int spl_amg_apply(void *M, const double *b, double *x);
 void spl_amg_free(void **M);
 int spl_krylov_set_preconditioner_amg(void *K, void *M);
 
+/* ---- restarted GMRES on handles and the fused multi-vector inner product (csrc/gmres.hip) ------------------------------
+ * spl_vector_dots_dev: d_out[i] = <V[:, i], w>, i = 0 ... k - 1, of n entries of value_width doubles each, all in DEVICE
+ *   memory (complex: packed pairs, conjugate on the left).  Column i starts at d_V + i * ldv * value_width doubles,
+ *   ldv >= n.  Each value is BIT FOR BIT what spl_vector_dot_dev(n, value_width, V[:, i], w, ...) writes: the same chunks
+ *   of 4096, 256 lanes, halving tree and fold of partials; the order is a function of n alone, there is no floating-point
+ *   atomic and no kernel waits for another workgroup, and SPL_KRYLOV_GRID does not show in the bits.  ONE pass computes
+ *   all k: a workgroup loads its chunk of w once and streams the columns past it; the levels of the fold run on k *
+ *   value_width planes at once.  Enqueued on `stream`, no synchronisation; the partials are a pool block per call.
+ *   1 <= k <= 128; n == 0 writes +0.0 k times.  Errors, in this order: n < 0 SPL_ERROR_n_nonpositive; value_width not
+ *   1 or 2, k outside 1 ... 128, ldv < n, a NULL pointer (d_V and d_w only when n > 0) or one that is not aligned to an
+ *   entry: SPL_ERROR_argument_missing.
+ *
+ * spl_gmres_create: a solver object for the whole square handle A with restart length `restart`, 1 ... 128 (it may
+ *   exceed n).  Ownership, borrowing, the lock (one solve at a time) and the error order are spl_krylov_create's;
+ *   SPL_ERROR_argument_missing for a restart outside the range comes where "unknown method" comes there.  The object
+ *   holds restart + 3 vectors (the basis v_0 ... v_restart, where slot j + 1 receives w before it is normalised, u and
+ *   M^-1 u), the partials, the tables of a cycle (Hessenberg column / R, rotations, g, y) and a status block, all in
+ *   device memory: info[3] has the bytes.  The operator is spl_matrix_spmv_dev as the caller configured it;
+ *   SPL_ORDER_FREE voids the bit contract.
+ * spl_gmres_set_preconditioner, spl_gmres_set_preconditioner_amg: as the spl_krylov_ calls; M^-1 is applied from the
+ *   right.
+ *
+ * The method.  Every real operation is rounded once; a product of two entries is Data.Complex's, a real number times an
+ * entry and an entry over a real number are done part by part; sqrt is IEEE's; threshold = max(rtol sqrt(Re<b,b>), atol)
+ * and met(rho) means sqrt(rho) <= threshold, as above.
+ *   cycle start:  r = b - A x  (first cycle with use_x0 == 0: r = b, x = 0, no product)
+ *                 rho = Re<r,r>;  residual[0] = sqrt(rho);  first cycle: history[0] = residual[1] = sqrt(rho), <b,b>
+ *                 rho or <b,b> not finite: reason 3;  met(rho): reason 0;  it == max_iter: reason 1
+ *                 beta = sqrt(rho);  v_0 = r / beta;  g_0 = beta
+ *   step j:       z = M^-1 v_j (no preconditioner: z IS v_j);  w = A z
+ *                 c1_i = <v_i, w>, i = 0 ... j  (one pass);  w = ((w - c1_0 v_0) - c1_1 v_1) - ...  (ascending i)
+ *                 c2_i = <v_i, w>;  w = w - sum c2_i v_i the same way;  h_i = c1_i + c2_i;  eta = sqrt(Re<w,w>)
+ *                 an h_i or eta not finite: reason 3, the step is dropped and the cycle closes with k = j columns
+ *                 i = 0 ... j-1:  (h_i, h_(i+1)) <- (conj(c_i) h_i + s_i h_(i+1),  c_i h_(i+1) - s_i h_i)
+ *                 t = sqrt((Re h_j)^2 + (Im h_j)^2 + eta^2), left to right
+ *                 t == 0: reason 2, the step is dropped, close with k = j;  t not finite: reason 3, likewise
+ *                 c_j = h_j / t;  s_j = eta / t;  R_ij = h_i (i < j);  R_jj = t
+ *                 g_(j+1) = -(s_j g_j);  g_j = conj(c_j) g_j;  it = it + 1;  history[it] = |g_(j+1)|
+ *                 (sqrt(re^2 + im^2); real: the absolute value)
+ *                 close with k = j + 1 when history[it] <= threshold, or eta == 0, or j + 1 == restart, or
+ *                 it == max_iter;  otherwise v_(j+1) = w / eta and go on
+ *   close:        k == 0: x unchanged.  Otherwise i = k-1 ... 0:  a = g_i;  a = a - R_il y_l, l = i+1 ... k-1 ascending;
+ *                 y_i = a / R_ii;  u = y_0 v_0;  u = u + y_l v_l ascending;  x = x + M^-1 u (or + u)
+ *                 residual[1] = history[it];  a reason set inside the cycle ends the solve here; otherwise: cycle start
+ * s_j is real because the subdiagonal entry is a norm, and no rotation divides by |h_j|.  The estimate history[it] only
+ * ENDS a cycle: reason 0 is decided at a cycle start alone, on the true residual of the x that is returned, so the last
+ * cycle is sometimes a single step.
+ *
+ * spl_gmres_solve_dev: vectors, use_x0, rtol, atol, max_iter and the argument errors as spl_krylov_solve_dev, with
+ *   `residual` NULL refused where `result` NULL is.  No scalar leaves the device during a cycle: the scalar work of a
+ *   step and the back-substitution of a close are one launch of one workgroup each.  The host cannot know a cycle's
+ *   length: it issues the launches of all `restart` steps and the close, and every kernel of a step returns without
+ *   touching a vector once the cycle is closed or the solve is done.  The host reads the status block after every
+ *   check_every-th cycle (0: every cycle); x, the counts, the history and the residuals do not depend on check_every,
+ *   only the launches issued for nothing do.  No captured graph, no kernel that waits for another workgroup, no
+ *   floating-point atomic.  result = {iterations, reason (as spl_krylov_solve_dev), cycles started, SpMVs issued,
+ *   preconditioner applications issued, 0}; residual = {|b - A x| as the last cycle start computed it, the estimate at
+ *   the last close}; history: NULL or max_iter + 1 doubles on the HOST.  n == 0: SPL_OK and zeros.  b = 0 without a
+ *   start: x = 0, 0 iterations, reason 0.
+ * spl_gmres_solve: the same with HOST vectors, on the default stream, a look after every cycle.
+ * spl_gmres_info: [0] n, [1] restart, [2] flags as spl_krylov_info's (16: AMG), [3] bytes of device memory, [4] solves,
+ *   [5] iterations of the last solve, [6] launches of the last solve, [7] 0.
+ * spl_gmres_free: idempotent, as spl_krylov_free. */
+int spl_vector_dots_dev(int64_t n, int value_width, int k, const double *d_V, int64_t ldv, const double *d_w, double *d_out,
+                        void *stream);
+int spl_gmres_create(void *A, int restart, void **G);
+int spl_gmres_set_preconditioner(void *G, void *T1, const double *d_mid, void *T2);
+int spl_gmres_set_preconditioner_amg(void *G, void *M);
+int spl_gmres_solve_dev(void *G, const double *d_b, double *d_x, int use_x0, double rtol, double atol, int64_t max_iter,
+                        int check_every, int64_t result[6], double *history, double residual[2], void *stream);
+int spl_gmres_solve(void *G, const double *b, double *x, int use_x0, double rtol, double atol, int64_t max_iter,
+                    int64_t result[6], double *history, double residual[2]);
+int spl_gmres_info(void *G, int64_t info[8]);
+void spl_gmres_free(void **G);
+
 /* select a kernel variant for spl_matrix_spmv_dev (tuning / ablation only): 0 = default
  * (whatever spl_matrix_optimize chose), 1-6 CSR-stream shapes, 7 sub-wavefront kernel, 8
  * column-blocked image, 9-11 gather cache policies, 15 sliced-ELL image, 16 column-sorted panel

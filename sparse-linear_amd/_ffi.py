@@ -176,6 +176,13 @@ def _declare(L):
         "spl_amg_apply_dev": [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p],
         "spl_amg_apply": [C.c_void_p, c_dbl_p, c_dbl_p],
         "spl_krylov_set_preconditioner_amg": [C.c_void_p, C.c_void_p],
+        "spl_vector_dots_dev": [i64, i, i, C.c_void_p, i64, C.c_void_p, C.c_void_p, C.c_void_p],
+        "spl_gmres_create": [C.c_void_p, i, c_void_pp],
+        "spl_gmres_set_preconditioner": [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p],
+        "spl_gmres_set_preconditioner_amg": [C.c_void_p, C.c_void_p],
+        "spl_gmres_solve_dev": [C.c_void_p, C.c_void_p, C.c_void_p, i, d, d, i64, i, c_i64_p, c_dbl_p, c_dbl_p, C.c_void_p],
+        "spl_gmres_solve": [C.c_void_p, c_dbl_p, c_dbl_p, i, d, d, i64, c_i64_p, c_dbl_p, c_dbl_p],
+        "spl_gmres_info": [C.c_void_p, c_i64_p],
         "spl_matrix_set_variant": [C.c_void_p, i],
         "spl_matrix_optimize": [C.c_void_p],
         "spl_matrix_build_blocked": [C.c_void_p, i, i, i],
@@ -211,6 +218,9 @@ def _declare(L):
     if hasattr(L, "spl_krylov_free"):
         L.spl_krylov_free.restype = None
         L.spl_krylov_free.argtypes = [c_void_pp]
+    if hasattr(L, "spl_gmres_free"):
+        L.spl_gmres_free.restype = None
+        L.spl_gmres_free.argtypes = [c_void_pp]
     if hasattr(L, "spl_amg_free"):
         L.spl_amg_free.restype = None
         L.spl_amg_free.argtypes = [c_void_pp]

@@ -1947,6 +1947,161 @@ int spl_krylov_set_preconditioner_amg(void *K, void *M) {
   return SPL_OK;
 }
 
+// ---- restarted GMRES on handles and the fused multi-vector inner product (csrc/gmres.hip) -------------------------------
+int spl_vector_dots_dev(int64_t n, int value_width, int k, const double *d_V, int64_t ldv, const double *d_w, double *d_out,
+                        void *stream) {
+  if (n < 0) return SPL_ERROR_n_nonpositive;
+  if (value_width != 1 && value_width != 2) return SPL_ERROR_argument_missing;
+  if (k < 1 || k > 128 || ldv < n) return SPL_ERROR_argument_missing;
+  if (!d_out || (n > 0 && (!d_V || !d_w))) return SPL_ERROR_argument_missing;
+  const uintptr_t entry = (uintptr_t)(8 * value_width);  // the kernels load and store whole entries
+  if ((uintptr_t)d_V % entry != 0 || (uintptr_t)d_w % entry != 0 || (uintptr_t)d_out % entry != 0)
+    return SPL_ERROR_argument_missing;
+  return guarded([&]() -> int {
+    return vector_dots(current_device(), n, value_width, k, d_V, ldv, d_w, d_out, as_stream(stream));
+  });
+}
+
+// A is borrowed: the object keeps the pointer, its restart + 3 vectors and its tables
+int spl_gmres_create(void *A, int restart, void **G) {
+  Matrix *M = as_matrix(A);
+  if (!M) return SPL_ERROR_invalid_handle;
+  if (!G) return SPL_ERROR_argument_missing;
+  *G = nullptr;
+  if (restart < 1 || restart > 128) return SPL_ERROR_argument_missing;
+  if (M->nrows_global != M->ncols) return SPL_ERROR_dimension_mismatch;
+  if (!whole(M)) return SPL_ERROR_invalid_matrix;
+  return guarded([&]() -> int {
+    (void)current_device();
+    DeviceGuard g(M->device);
+    Gmres *S = nullptr;
+    const int st = gmres_create(M, restart, &S);
+    *G = S;
+    return st;
+  });
+}
+
+int spl_gmres_set_preconditioner(void *G, void *T1, const double *d_mid, void *T2) {
+  Gmres *S = as_gmres(G);
+  if (!S) return SPL_ERROR_invalid_handle;
+  TriSolver *parts[2] = {nullptr, nullptr};
+  void *given[2] = {T1, T2};
+  for (int i = 0; i < 2; ++i) {
+    if (!given[i]) continue;
+    parts[i] = as_trisolver(given[i]);
+    if (!parts[i]) return SPL_ERROR_invalid_handle;
+  }
+  if ((uintptr_t)d_mid % (uintptr_t)(8 * gmres_width(S)) != 0) return SPL_ERROR_argument_missing;
+  for (TriSolver *T : parts)
+    if (T && (trisolve_rows(T) != gmres_rows(S) || trisolve_width(T) != gmres_width(S) ||
+              trisolve_device(T) != gmres_device(S)))
+      return SPL_ERROR_dimension_mismatch;
+  gmres_set_preconditioner(S, parts[0], d_mid, parts[1]);
+  return SPL_OK;
+}
+
+// M is borrowed and may serve several solvers; NULL takes the preconditioner away
+int spl_gmres_set_preconditioner_amg(void *G, void *M) {
+  Gmres *S = as_gmres(G);
+  if (!S) return SPL_ERROR_invalid_handle;
+  Amg *P = nullptr;
+  if (M) {
+    P = as_amg(M);
+    if (!P) return SPL_ERROR_invalid_handle;
+    if (amg_rows(P) != gmres_rows(S) || amg_width(P) != gmres_width(S) || amg_device(P) != gmres_device(S))
+      return SPL_ERROR_dimension_mismatch;
+  }
+  gmres_set_preconditioner_amg(S, P);
+  return SPL_OK;
+}
+
+namespace {
+// what both solve calls refuse before anything else is looked at
+int check_gmres_solve(const Gmres *S, double rtol, double atol, int64_t max_iter, int check_every, const int64_t *result,
+                      const double *history, const double *residual) {
+  if (!S) return SPL_ERROR_invalid_handle;
+  if (!result || !residual) return SPL_ERROR_argument_missing;
+  if (max_iter < 0) return SPL_ERROR_n_nonpositive;
+  if (!(rtol >= 0.0) || !(atol >= 0.0) || check_every < 0) return SPL_ERROR_argument_missing;  // a NaN is refused too
+  if (history && max_iter >= ((int64_t)1 << 31)) return SPL_ERROR_index_overflow;
+  return SPL_OK;
+}
+void empty_gmres_result(int64_t result[6], double *history, double residual[2]) {
+  for (int i = 0; i < 6; ++i) result[i] = 0;
+  residual[0] = residual[1] = 0.0;
+  if (history) history[0] = 0.0;
+}
+}  // namespace
+
+int spl_gmres_solve_dev(void *G, const double *d_b, double *d_x, int use_x0, double rtol, double atol, int64_t max_iter,
+                        int check_every, int64_t result[6], double *history, double residual[2], void *stream) {
+  Gmres *S = as_gmres(G);
+  const int refused = check_gmres_solve(S, rtol, atol, max_iter, check_every, result, history, residual);
+  if (refused != SPL_OK) return refused;
+  if (gmres_rows(S) == 0) {
+    empty_gmres_result(result, history, residual);
+    return SPL_OK;
+  }
+  if (!d_b || !d_x || d_b == d_x) return SPL_ERROR_argument_missing;
+  const uintptr_t entry = (uintptr_t)(8 * gmres_width(S));  // the kernels load and store whole entries
+  if ((uintptr_t)d_b % entry != 0 || (uintptr_t)d_x % entry != 0) return SPL_ERROR_argument_missing;
+  return guarded([&]() -> int {
+    DeviceGuard g(gmres_device(S));
+    return gmres_solve(S, d_b, d_x, use_x0 ? 1 : 0, rtol, atol, max_iter, check_every, result, history, residual,
+                       as_stream(stream));
+  });
+}
+
+// host vectors of n entries, packed complex: up, solved on the default stream with a look after every cycle, down
+int spl_gmres_solve(void *G, const double *b, double *x, int use_x0, double rtol, double atol, int64_t max_iter,
+                    int64_t result[6], double *history, double residual[2]) {
+  Gmres *S = as_gmres(G);
+  const int refused = check_gmres_solve(S, rtol, atol, max_iter, 0, result, history, residual);
+  if (refused != SPL_OK) return refused;
+  if (gmres_rows(S) == 0) {
+    empty_gmres_result(result, history, residual);
+    return SPL_OK;
+  }
+  if (!b || !x) return SPL_ERROR_argument_missing;
+  return guarded([&]() -> int {
+    DeviceGuard g(gmres_device(S));
+    hipStream_t s = nullptr;
+    const size_t count = (size_t)gmres_rows(S) * (size_t)gmres_width(S);
+    DBuf<double> d(2 * count);
+    double *d_b = d.get(), *d_x = d.get() + count;
+    SPL_HIP(hipMemcpyAsync(d_b, b, count * sizeof(double), hipMemcpyHostToDevice, s));
+    if (use_x0) SPL_HIP(hipMemcpyAsync(d_x, x, count * sizeof(double), hipMemcpyHostToDevice, s));
+    const int st = gmres_solve(S, d_b, d_x, use_x0 ? 1 : 0, rtol, atol, max_iter, 0, result, history, residual, s);
+    if (st != SPL_OK) {
+      (void)hipStreamSynchronize(s);
+      return st;
+    }
+    SPL_HIP(hipMemcpyAsync(x, d_x, count * sizeof(double), hipMemcpyDeviceToHost, s));
+    SPL_HIP(hipStreamSynchronize(s));
+    return SPL_OK;
+  });
+}
+
+int spl_gmres_info(void *G, int64_t info[8]) {
+  Gmres *S = as_gmres(G);
+  if (!S) return SPL_ERROR_invalid_handle;
+  if (!info) return SPL_ERROR_argument_missing;
+  gmres_info(S, info);
+  return SPL_OK;
+}
+
+void spl_gmres_free(void **G) {
+  if (!G || !*G) return;
+  Gmres *S = as_gmres(*G);
+  *G = nullptr;
+  if (!S) return;
+  int prev = -1;
+  const bool have_prev = hipGetDevice(&prev) == hipSuccess;
+  (void)hipSetDevice(gmres_device(S));  // may run on a finalizer thread with another current device
+  gmres_delete(S);
+  if (have_prev) (void)hipSetDevice(prev);
+}
+
 // mulM on Complex Double (the reference's SPECIALIZE instance, Sparse.hs:475): one axpy_ per column of B there; here the
 // packed-complex image of A and one multi-vector product.  B and C are row-major like spl_mulm's; the kernel wants one
 // vector after the other, so both are turned on the device (the call is bounded by its copies over PCIe).

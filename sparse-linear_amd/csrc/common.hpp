@@ -391,6 +391,27 @@ void amg_delete(Amg *M);
 // M: borrowed, of K's size, value kind and device (the caller checked), or nullptr; clears the triangular parts
 void krylov_set_preconditioner_amg(Krylov *K, Amg *M);
 
+// ---- restarted GMRES on handles and the fused multi-vector inner product (gmres.hip) ---------------------------------
+// <V[:, i], w>, i < k, of n entries of vw doubles each to d_out (k entries, device memory); column i starts at
+// d_V + i * ldv * vw.  Each value is vector_dot's, bit for bit; enqueues on s, no synchronisation
+int vector_dots(int device, int64_t n, int vw, int k, const double *d_V, int64_t ldv, const double *d_w, double *d_out,
+                hipStream_t s);
+struct Gmres;
+Gmres *as_gmres(void *g);  // nullptr unless g carries the object's magic word
+// A: whole and square, 1 <= restart <= 128 (the caller checked); borrowed.  SPL_OK
+int gmres_create(const Matrix *A, int restart, Gmres **out);
+// the parts are borrowed and of G's size, value kind and device (the caller checked); nullptr: the identity
+void gmres_set_preconditioner(Gmres *G, TriSolver *T1, const double *d_mid, TriSolver *T2);
+void gmres_set_preconditioner_amg(Gmres *G, Amg *M);
+// n > 0 and the arguments are checked by the caller; enqueues on s and synchronises it (the outcome is read back)
+int gmres_solve(Gmres *G, const double *d_b, double *d_x, int use_x0, double rtol, double atol, int64_t max_iter,
+                int check_every, int64_t result[6], double *history, double residual[2], hipStream_t s);
+void gmres_info(Gmres *G, int64_t info[8]);
+int gmres_device(const Gmres *G);
+int64_t gmres_rows(const Gmres *G);
+int gmres_width(const Gmres *G);  // doubles per entry: 1 real, 2 packed complex
+void gmres_delete(Gmres *G);
+
 // ---- multifrontal LU without interchanges (multifrontal.hip, mf_symbolic.hpp) ------------------
 namespace mf {
 struct Tree;

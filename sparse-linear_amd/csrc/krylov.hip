@@ -24,8 +24,7 @@
 #include <mutex>
 #include <utility>
 
-#include "row_groups.hpp"
-#include "tri_arith.hpp"
+#include "krylov_fold.hpp"
 
 namespace spl {
 
@@ -33,11 +32,8 @@ constexpr uint32_t kKrylovMagic = 0x53504C4Bu;  // "SPLK"
 
 namespace {
 
-constexpr int kChunk = 4096;              // entries per chunk of the fold
-constexpr int kLanes = 256;               // lanes of a chunk: the workgroup
-constexpr int kSteps = kChunk / kLanes;   // 16 entries per lane
+// the fold itself (chunks of 4096, 256 lanes, the levels) is krylov_fold.hpp, shared with gmres.hip
 constexpr int kMaxPlanes = 4;             // two inner products of two components at most in one pass
-constexpr int kDefaultGrid = 2048;        // workgroups of a chunk kernel at most (SPL_KRYLOV_GRID)
 constexpr int kDefaultCheckEvery = 16;    // iterations between two looks at the status block (check_every == 0)
 
 // The status block, in device memory (and its copy in pinned host memory).  The packed scalars are 16-byte aligned.
@@ -67,80 +63,6 @@ enum Stage {
   kStageResidualRho  // kStageResidual, then kStageCgRho
 };
 
-// ---- values ----------------------------------------------------------------------------------------------------------
-__device__ inline Val<1> add(Val<1> a, Val<1> b) { return Val<1>{a.re + b.re}; }
-__device__ inline Val<2> add(Val<2> a, Val<2> b) { return Val<2>{a.re + b.re, a.im + b.im}; }
-__device__ inline Val<1> conj_of(Val<1> a) { return a; }
-__device__ inline Val<2> conj_of(Val<2> a) { return Val<2>{a.re, -a.im}; }
-__device__ inline void accumulate(double *acc, Val<1> v) { acc[0] = acc[0] + v.re; }
-__device__ inline void accumulate(double *acc, Val<2> v) {
-  acc[0] = acc[0] + v.re;
-  acc[1] = acc[1] + v.im;
-}
-__device__ inline bool is_zero(Val<1> a) { return a.re == 0.0; }
-__device__ inline bool is_zero(Val<2> a) { return a.re == 0.0 && a.im == 0.0; }
-__device__ inline bool is_finite(Val<1> a) { return isfinite(a.re); }
-__device__ inline bool is_finite(Val<2> a) { return isfinite(a.re) && isfinite(a.im); }
-template <int VW>
-__device__ inline Val<VW> from_planes(const double *f, int dot);
-template <>
-__device__ inline Val<1> from_planes<1>(const double *f, int dot) {
-  return Val<1>{f[dot]};
-}
-template <>
-__device__ inline Val<2> from_planes<2>(const double *f, int dot) {
-  return Val<2>{f[2 * dot], f[2 * dot + 1]};
-}
-
-// ---- the fold --------------------------------------------------------------------------------------------------------
-// The 256 lane sums of NV planes to lane 0: s[t] += s[t + h], h = 128 ... 1.  Steps 128 and 64 through LDS in one
-// expression per lane of the first wavefront, (s[t] + s[t + 128]) + (s[t + 64] + s[t + 192]); steps 32 ... 1 by
-// shuffles inside that wavefront (lane t < h reads lane t + h, which the step before left final).  Every thread of the
-// workgroup must be here.  lds: NV * 256 doubles.
-template <int NV>
-__device__ inline void lane_tree(double (&acc)[NV], double *lds) {
-  const int t = threadIdx.x;
-#pragma unroll
-  for (int v = 0; v < NV; ++v) lds[v * kLanes + t] = acc[v];
-  __syncthreads();
-  if (t < 64) {
-#pragma unroll
-    for (int v = 0; v < NV; ++v) {
-      const double *s = lds + v * kLanes;
-      double a = (s[t] + s[t + 128]) + (s[t + 64] + s[t + 192]);
-#pragma unroll
-      for (int h = 32; h >= 1; h >>= 1) a = a + __shfl_down(a, h);
-      acc[v] = a;
-    }
-  }
-  __syncthreads();  // lds is written again for the workgroup's next chunk
-}
-
-// The chunks of [0, n) by the workgroups of the launch: body(i, acc) does the entry-wise work of entry i and adds its
-// NV contributions to the lane's sums; part[v * stride + c] receives plane v of chunk c.
-template <int NV, typename Body>
-__device__ inline void chunk_partials(int64_t n, double *part, int64_t stride, Body body) {
-  __shared__ double lds[NV * kLanes];
-  const int t = threadIdx.x;
-  const int64_t nchunks = (n + kChunk - 1) / kChunk;
-  for (int64_t c = blockIdx.x; c < nchunks; c += gridDim.x) {
-    double acc[NV];
-#pragma unroll
-    for (int v = 0; v < NV; ++v) acc[v] = 0.0;
-    const int64_t base = c * kChunk + t;
-#pragma unroll 4
-    for (int k = 0; k < kSteps; ++k) {
-      const int64_t i = base + (int64_t)k * kLanes;
-      if (i < n) body(i, acc);
-    }
-    lane_tree<NV>(acc, lds);
-    if (t == 0) {
-#pragma unroll
-      for (int v = 0; v < NV; ++v) part[v * stride + c] = acc[v];
-    }
-  }
-}
-
 // partials of ND inner products <a_d, b_d>; a and b may be the same array
 template <int VW, int ND>
 __global__ __launch_bounds__(kLanes) void dot_kernel(const Status *st, int64_t n, const double *a0, const double *b0,
@@ -150,15 +72,6 @@ __global__ __launch_bounds__(kLanes) void dot_kernel(const Status *st, int64_t n
     accumulate(acc, mul(conj_of(load_val<VW>(a0, i)), load_val<VW>(b0, i)));
     if (ND == 2) accumulate(acc + VW, mul(conj_of(load_val<VW>(a1, i)), load_val<VW>(b1, i)));
   });
-}
-
-// a middle level of the fold: plane blockIdx.y of `in` (count entries) to its ceil(count / 4096) partials
-__global__ __launch_bounds__(kLanes) void fold_kernel(const Status *st, int64_t count, const double *in, int64_t in_stride,
-                                                      double *out, int64_t out_stride) {
-  if (st && st->done) return;
-  const double *src = in + (int64_t)blockIdx.y * in_stride;
-  chunk_partials<1>(count, out + (int64_t)blockIdx.y * out_stride, 0,
-                    [&](int64_t i, double *acc) { acc[0] = acc[0] + src[i]; });
 }
 
 // The last level, by ONE workgroup: `count` <= 4096 partials of each of `planes` planes to one value each, and the
@@ -378,73 +291,20 @@ __global__ __launch_bounds__(kLanes) void diag_scale_kernel(const Status *st, in
   for (; i < n; i += stride) store_val(out, i, mul(load_val<VW>(d, i), load_val<VW>(in, i)));
 }
 
-// ---- host: the levels of the fold -------------------------------------------------------------------------------------
-inline int64_t chunks_of(int64_t n) { return (n + kChunk - 1) / kChunk; }
-
-// doubles of scratch `planes` planes of the fold of n entries need: the first level and one middle level
-inline size_t fold_scratch(int64_t n, int planes) {
-  const int64_t c1 = chunks_of(n), c2 = chunks_of(c1);
-  return (size_t)planes * (size_t)((c1 ? c1 : 1) + (c2 ? c2 : 1));
-}
-
-int chunk_grid_cap() {
-  const char *e = getenv("SPL_KRYLOV_GRID");
-  const long v = e ? atol(e) : 0;
-  return v >= 1 && v <= 65535 ? (int)v : kDefaultGrid;
-}
-
-inline unsigned chunk_grid(int64_t n) {
-  const int64_t c = chunks_of(n), cap = chunk_grid_cap();
-  return (unsigned)(c < 1 ? 1 : c < cap ? c : cap);
-}
-
-// What the last level reads, and the middle levels that were launched before it
-struct Partials {
-  const double *p;
-  int64_t stride;
-  int count;
-  int middle;
-};
-
-// The first level left chunks_of(n) partials per plane in `scratch` (stride chunks_of(n)); middle levels until at most
-// 4096 are left.  The scratch is two parts (fold_scratch): planes * c1 entries for the first level, planes * c2 for the
-// next, and the levels take turns between them: level k + 2 writes planes * c(k+2) <= planes * c(k) entries where level k
-// wrote, so any number of levels fits.  One middle level serves up to 4096^3 entries; no vector in memory needs two.
-Partials middle_levels(const Status *st, int64_t n, int planes, double *scratch, hipStream_t s) {
-  int64_t count = chunks_of(n);
-  const int64_t first_stride = count ? count : 1;
-  double *cur = scratch, *other = scratch + (size_t)planes * (size_t)first_stride;
-  int64_t stride = first_stride;
-  int middle = 0;
-  while (count > kChunk) {
-    ++middle;
-    const int64_t next = chunks_of(count);
-    hipLaunchKernelGGL(fold_kernel, dim3(chunk_grid(count), planes), dim3(kLanes), 0, s, st, count, cur, stride, other, next);
-    std::swap(cur, other);
-    stride = next;
-    count = next;
-  }
-  return Partials{cur, stride, (int)count, middle};
-}
-
 // Scratch of spl_vector_dot_dev: a block from the device pool PER CALL, so two calls never share partials, from whatever
 // threads and on whatever streams they come.  A call takes a block whose previous user has finished on the device (an
 // event recorded behind that user's last kernel says so), or a new one; it records its own event behind its last kernel
 // and gives the block back.  Blocks are reused across streams, a finished block that is too small is released, and
 // at most kDotBlocksKept finished blocks are kept: nothing grows with the number of streams or calls.  The list lives
 // as long as the process (nothing is released at exit, when the runtime may be gone).
-struct DotBlock {
-  DBuf<double> buf;
-  hipEvent_t done = nullptr;  // behind the last kernel that reads or writes buf
-  int device = 0;
-  bool taken = false;         // a host thread is enqueueing on it
-};
 constexpr size_t kDotBlocksKept = 8;
 std::mutex g_dot_mu;
 std::vector<DotBlock *> *dot_blocks() {
   static auto *list = new std::vector<DotBlock *>;
   return list;
 }
+
+}  // namespace
 
 DotBlock *dot_block_take(int device, size_t doubles) {
   std::lock_guard<std::mutex> hold(g_dot_mu);
@@ -497,6 +357,11 @@ void dot_block_give(DotBlock *b, hipStream_t s, bool enqueued) {
   std::lock_guard<std::mutex> hold(g_dot_mu);
   b->taken = false;
 }
+
+namespace {
+
+// the `done` flag of a status block in device memory, for the levels of the fold
+inline const int *done_flag(const Status *st) { return st ? &st->done : nullptr; }
 
 template <int VW>
 void dot_launch(int64_t n, const double *d_a, const double *d_b, double *d_out, double *scratch, hipStream_t s) {
@@ -615,7 +480,7 @@ struct Run {
   int64_t stride() const { return chunks_of(n); }
 
   void scalar(int stage, int first, int dots) {
-    const Partials P = middle_levels(st, n, dots * VW, scratch, s);
+    const Partials P = middle_levels(done_flag(st), n, dots * VW, scratch, s);
     launches += P.middle + 1;
     hipLaunchKernelGGL((scalar_kernel<VW>), dim3(1), dim3(kLanes), 0, s, st, stage, first, P.p, P.stride, P.count,
                        dots * VW, rtol, atol, max_iter, hist, (double *)nullptr);

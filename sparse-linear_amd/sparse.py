@@ -29,6 +29,8 @@ are solved on the device by ``DeviceMatrix.triangular`` / ``TriangularSolver`` (
 and ``DeviceMatrix.ilu0`` / ``ILU0`` (``ilu0`` from a host Matrix) produces the incomplete factors those solvers apply.
 ``DeviceMatrix.krylov`` / ``KrylovSolver`` (``cg`` / ``bicgstab`` from a host Matrix) solve ``A x = b`` with them:
 preconditioned CG and BiCGSTAB whose scalars stay on the device; ``vector_dot_dev`` is their fixed-order inner product.
+``DeviceMatrix.gmres`` / ``GMRESSolver`` (``gmres`` from a host Matrix) is restarted GMRES for unsymmetric and indefinite
+systems with the same preconditioners; ``vector_dots_dev`` is the k-column inner product its orthogonalisation uses.
 ``DeviceMatrix.amg`` / ``AMG`` (``amg`` from a host Matrix) build an aggregation multigrid hierarchy from the handle
 operations above, and its V-cycle is a preconditioner the solvers take (``M=<AMG>`` or ``M="amg"``).
 """
@@ -851,6 +853,11 @@ class DeviceMatrix(object):
         M (None, an ILU0, 'jacobi', 'sgs' or a (T1, mid, T2) triple).  The handle is borrowed: the solver keeps it alive"""
         return KrylovSolver(self, method, M)
 
+    def gmres(self, restart=30, M=None):
+        """a GMRESSolver for this whole square handle (spl_gmres_create): restarted GMRES(restart), 1 ... 128, for
+        unsymmetric and indefinite systems, with the preconditioner M as KrylovSolver takes it"""
+        return GMRESSolver(self, restart, M)
+
     def coloring(self, seed=0):
         """the multicolour ordering of this whole square handle (spl_matrix_color): a Coloring with colors, perm and
         offsets; ``coloring().krylov(method, M)`` solves with the preconditioner built in that ordering"""
@@ -1183,40 +1190,38 @@ def vector_dot_dev(n, a_ptr, b_ptr, out_ptr, is_complex=False, stream=0):
                                    C.c_void_p(out_ptr), C.c_void_p(stream)))
 
 
-class KrylovSolver(object):
-    """Owner of a ``void *K`` from ``spl_krylov_create``: preconditioned CG or BiCGSTAB on a whole square device handle
-    (csrc/krylov.hip), real or complex, every scalar of the iteration in device memory.  The iterates, the iteration
-    count and the residual history are those of the serial restatement in include/sparse_linear_hip.h bit for bit.
+def vector_dots_dev(n, k, V_ptr, ldv, w_ptr, out_ptr, is_complex=False, stream=0):
+    """out[i] = <V[:, i], w>, i < k, in ONE pass over w (spl_vector_dots_dev): column i of V starts ldv entries after
+    column i - 1, ldv >= n, 1 <= k <= 128; every value is vector_dot_dev's bit for bit.  Device pointers (ints), out k
+    doubles or packed pairs; enqueues on `stream`, no sync"""
+    check("spl_vector_dots_dev",
+          lib().spl_vector_dots_dev(int(n), 2 if is_complex else 1, int(k), C.c_void_p(V_ptr), int(ldv), C.c_void_p(w_ptr),
+                                    C.c_void_p(out_ptr), C.c_void_p(stream)))
 
-    ``M``: None; an ``ILU0``; ``"jacobi"`` (1 / diag(A)); ``"sgs"`` (symmetric Gauss-Seidel: tril(A), diag(A), triu(A));
-    or a triple ``(T1, mid, T2)`` of a TriangularSolver or None, a torch device vector of n entries or None, and a
-    TriangularSolver or None, applied as ``z = T2^-1 (mid * (T1^-1 r))``.  The object keeps references to A and to the
-    parts of M, so nothing it borrows is collected under it; ``parts`` is the triple in use.  An ``AMG`` object, or
-    ``"amg"`` (one built here with the defaults and freed with the solver), makes its V-cycle the preconditioner
-    instead of the triple; ``amg`` is the one in use."""
-    METHODS = {"cg": _ffi.SPL_KRYLOV_cg, "bicgstab": _ffi.SPL_KRYLOV_bicgstab}
+
+class _PreconditionedSolver(object):
+    """What KrylovSolver and GMRESSolver share: the handle, the preconditioner vocabulary (None, an ``ILU0``, an ``AMG``,
+    ``"jacobi"``, ``"sgs"``, ``"amg"`` or a ``(T1, mid, T2)`` triple), ``info`` and the vector plumbing of ``solve``.  A
+    subclass names its C calls (``_CALLS``: set_preconditioner, set_preconditioner_amg, info, free) and has
+    ``solve_dev`` and ``_solve_host``."""
     REASONS = ("converged", "max_iter", "breakdown", "non_finite")
-    INFO_KEYS = ("n", "method", "flags", "device_bytes", "solves", "iterations", "launches_per_iteration", "reserved")
     DEFAULT_MAXITER = 20000
+    _NAME = None
+    _CALLS = None
 
-    def __init__(self, A, method="cg", M=None):
-        if method not in self.METHODS:
-            raise ValueError("KrylovSolver: method %r; 'cg' or 'bicgstab' is needed" % (method,))
+    def _begin(self, A, M):
         self._k = C.c_void_p()
-        self._finalizer = weakref.finalize(self, KrylovSolver._free, self._k)
+        self._finalizer = weakref.finalize(self, type(self)._free, self._k)
         self.A = A
-        self.method = method
         self.parts = (None, None, None)
         self.amg = None   # the AMG in use: M itself, or the one "amg" made here
         self._owned = []  # what "jacobi", "sgs" and "amg" made here
         self._M = M       # an ILU0 stays alive with its solvers
-        check("spl_krylov_create", lib().spl_krylov_create(A.handle, self.METHODS[method], C.byref(self._k)))
-        self.set_preconditioner(M)
 
-    @staticmethod
-    def _free(k):
+    @classmethod
+    def _free(cls, k):
         try:
-            lib().spl_krylov_free(C.byref(k))
+            getattr(lib(), cls._CALLS["free"])(C.byref(k))
         except Exception:  # interpreter shutdown
             pass
 
@@ -1229,7 +1234,7 @@ class KrylovSolver(object):
     @property
     def handle(self):
         if not self._k.value:
-            raise _ffi.SparseLinearError("KrylovSolver", _ffi.SPL_ERROR_invalid_handle)
+            raise _ffi.SparseLinearError(self._NAME, _ffi.SPL_ERROR_invalid_handle)
         return self._k
 
     def _diagonal(self):
@@ -1245,12 +1250,13 @@ class KrylovSolver(object):
     def set_preconditioner(self, M):
         """replaces the preconditioner (the forms of the class docstring)"""
         owned = []
+        set_parts, set_amg = self._CALLS["set_preconditioner"], self._CALLS["set_preconditioner_amg"]
         if isinstance(M, AMG) or (isinstance(M, str) and M == "amg"):
             cycle = M
             if isinstance(M, str):  # built here with the defaults, and freed with the solver
                 cycle = AMG(self.A)
                 owned = [cycle]
-            check("spl_krylov_set_preconditioner_amg", lib().spl_krylov_set_preconditioner_amg(self.handle, cycle.handle))
+            check(set_amg, getattr(lib(), set_amg)(self.handle, cycle.handle))
             for part in self._owned:
                 part.free()
             self._owned, self.parts, self._M, self.amg = owned, (None, None, None), cycle, cycle
@@ -1268,8 +1274,8 @@ class KrylovSolver(object):
         elif isinstance(M, (tuple, list)) and len(M) == 3:
             parts = tuple(M)
         else:
-            raise ValueError("KrylovSolver: M %r; None, an ILU0, an AMG, 'jacobi', 'sgs', 'amg' or a (T1, mid, T2) triple "
-                             "is needed" % (M,))
+            raise ValueError("%s: M %r; None, an ILU0, an AMG, 'jacobi', 'sgs', 'amg' or a (T1, mid, T2) triple "
+                             "is needed" % (self._NAME, M))
         t1, mid, t2 = parts
         if mid is not None:
             n, cplx = self.info()["n"], self.A.is_complex
@@ -1277,22 +1283,106 @@ class KrylovSolver(object):
             want = torch.complex128 if cplx else torch.float64
             if not (isinstance(mid, torch.Tensor) and mid.is_cuda and mid.dtype == want and mid.dim() == 1
                     and int(mid.shape[0]) == n and (n <= 1 or mid.stride(0) == 1)):
-                _oops("KrylovSolver", "the middle part must be a contiguous torch device vector of %d %s entries" % (n, want))
-        check("spl_krylov_set_preconditioner",
-              lib().spl_krylov_set_preconditioner(self.handle, t1.handle if t1 is not None else None,
-                                                  C.c_void_p(mid.data_ptr()) if mid is not None else None,
-                                                  t2.handle if t2 is not None else None))
+                _oops(self._NAME, "the middle part must be a contiguous torch device vector of %d %s entries" % (n, want))
+        check(set_parts,
+              getattr(lib(), set_parts)(self.handle, t1.handle if t1 is not None else None,
+                                        C.c_void_p(mid.data_ptr()) if mid is not None else None,
+                                        t2.handle if t2 is not None else None))
         for part in self._owned:
             part.free()
         self._owned, self.parts, self._M, self.amg = owned, parts, M, None
 
     def info(self):
         out = np.zeros(8, dtype=I64)
-        check("spl_krylov_info", lib().spl_krylov_info(self.handle, _ffi.p_i64(out)))
+        check(self._CALLS["info"], getattr(lib(), self._CALLS["info"])(self.handle, _ffi.p_i64(out)))
         d = dict(zip(self.INFO_KEYS, (int(v) for v in out)))
         d.update(complex=bool(d["flags"] & 1), T1=bool(d["flags"] & 2), mid=bool(d["flags"] & 4), T2=bool(d["flags"] & 8),
                  amg=bool(d["flags"] & 16))
         return d
+
+    def _maxiter(self, maxiter):
+        if maxiter is None:
+            return min(10 * self.info()["n"], self.DEFAULT_MAXITER)
+        return int(maxiter)
+
+    def solve(self, b, x0=None, rtol=1e-8, atol=0.0, maxiter=None, check_every=0):
+        """(x, result dict) with A x = b.  b (and x0): numpy arrays, or torch tensors on the device (x is one then and
+        the solve runs on torch's current stream); float64 on a real object, complex128 on a complex one"""
+        where = self._NAME + ".solve"
+        inf = self.info()
+        n, cplx = inf["n"], inf["complex"]
+        try:
+            import torch
+            is_tensor = isinstance(b, torch.Tensor)
+        except ImportError:  # pragma: no cover
+            is_tensor = False
+        if is_tensor:
+            want = torch.complex128 if cplx else torch.float64
+            for v, what in ((b, "right-hand side"), (x0, "start")):
+                if v is None:
+                    continue
+                if not (isinstance(v, torch.Tensor) and v.is_cuda and v.dtype == want and tuple(v.shape) == (n,)):
+                    _oops(where, "the %s must be a device tensor of %d %s entries" % (what, n, want))
+            with torch.cuda.device(b.device):
+                bb = b.contiguous()
+                x = torch.empty(max(n, 1), dtype=want, device=b.device)[:n]
+                if x0 is not None:
+                    x.copy_(x0)
+                res = self.solve_dev(bb.data_ptr(), x.data_ptr(), x0 is not None, rtol, atol, maxiter, check_every,
+                                     True, torch.cuda.current_stream().cuda_stream)
+            return x, res
+        want = C128 if cplx else F64
+        a = np.ascontiguousarray(b)
+        if a.dtype != want or a.shape != (n,):
+            _oops(where, "right-hand side of dtype %s and shape %s; %d %s entries are needed"
+                  % (a.dtype, a.shape, n, np.dtype(want)))
+        x = np.zeros(n, dtype=want)
+        if x0 is not None:
+            x0 = np.asarray(x0)
+            if x0.dtype != want or x0.shape != (n,):
+                _oops(where, "a start of dtype %s and shape %s; %d %s entries are needed"
+                      % (x0.dtype, x0.shape, n, np.dtype(want)))
+            x[:] = x0
+        maxiter = self._maxiter(maxiter)
+        if check_every:  # the host-vector call has no such argument: through device tensors
+            import torch
+            with torch.cuda.device(self.A.info()["device"]):
+                db = torch.from_numpy(a).cuda()
+                dx = torch.from_numpy(x).cuda()
+                res = self.solve_dev(db.data_ptr(), dx.data_ptr(), x0 is not None, rtol, atol, maxiter, check_every,
+                                     True, torch.cuda.current_stream().cuda_stream)
+                return dx.cpu().numpy(), res
+        return x, self._solve_host(a, x, x0 is not None, rtol, atol, maxiter)
+
+
+class KrylovSolver(_PreconditionedSolver):
+    """Owner of a ``void *K`` from ``spl_krylov_create``: preconditioned CG or BiCGSTAB on a whole square device handle
+    (csrc/krylov.hip), real or complex, every scalar of the iteration in device memory.  The iterates, the iteration
+    count and the residual history are those of the serial restatement in include/sparse_linear_hip.h bit for bit.
+
+    ``M``: None; an ``ILU0``; ``"jacobi"`` (1 / diag(A)); ``"sgs"`` (symmetric Gauss-Seidel: tril(A), diag(A), triu(A));
+    or a triple ``(T1, mid, T2)`` of a TriangularSolver or None, a torch device vector of n entries or None, and a
+    TriangularSolver or None, applied as ``z = T2^-1 (mid * (T1^-1 r))``.  The object keeps references to A and to the
+    parts of M, so nothing it borrows is collected under it; ``parts`` is the triple in use.  An ``AMG`` object, or
+    ``"amg"`` (one built here with the defaults and freed with the solver), makes its V-cycle the preconditioner
+    instead of the triple; ``amg`` is the one in use."""
+    METHODS = {"cg": _ffi.SPL_KRYLOV_cg, "bicgstab": _ffi.SPL_KRYLOV_bicgstab}
+    REASONS = ("converged", "max_iter", "breakdown", "non_finite")
+    INFO_KEYS = ("n", "method", "flags", "device_bytes", "solves", "iterations", "launches_per_iteration", "reserved")
+    DEFAULT_MAXITER = 20000
+
+    _NAME = "KrylovSolver"
+    _CALLS = {"set_preconditioner": "spl_krylov_set_preconditioner",
+              "set_preconditioner_amg": "spl_krylov_set_preconditioner_amg", "info": "spl_krylov_info",
+              "free": "spl_krylov_free"}
+
+    def __init__(self, A, method="cg", M=None):
+        if method not in self.METHODS:
+            raise ValueError("KrylovSolver: method %r; 'cg' or 'bicgstab' is needed" % (method,))
+        self._begin(A, M)
+        self.method = method
+        check("spl_krylov_create", lib().spl_krylov_create(A.handle, self.METHODS[method], C.byref(self._k)))
+        self.set_preconditioner(M)
 
     @classmethod
     def _result(cls, result, history):
@@ -1302,11 +1392,6 @@ class KrylovSolver(object):
         if history is not None:
             out["history"] = history[:it + 1].copy()
         return out
-
-    def _maxiter(self, maxiter):
-        if maxiter is None:
-            return min(10 * self.info()["n"], self.DEFAULT_MAXITER)
-        return int(maxiter)
 
     def solve_dev(self, b_ptr, x_ptr, use_x0=False, rtol=1e-8, atol=0.0, maxiter=None, check_every=0, history=True,
                   stream=0):
@@ -1322,58 +1407,81 @@ class KrylovSolver(object):
                                          p_f64(hist) if history else None, C.c_void_p(stream)))
         return self._result(result, hist)
 
-    def solve(self, b, x0=None, rtol=1e-8, atol=0.0, maxiter=None, check_every=0):
-        """(x, result dict) with A x = b.  b (and x0): numpy arrays, or torch tensors on the device (x is one then and
-        the solve runs on torch's current stream); float64 on a real object, complex128 on a complex one"""
-        inf = self.info()
-        n, cplx = inf["n"], inf["complex"]
-        try:
-            import torch
-            is_tensor = isinstance(b, torch.Tensor)
-        except ImportError:  # pragma: no cover
-            is_tensor = False
-        if is_tensor:
-            want = torch.complex128 if cplx else torch.float64
-            for v, what in ((b, "right-hand side"), (x0, "start")):
-                if v is None:
-                    continue
-                if not (isinstance(v, torch.Tensor) and v.is_cuda and v.dtype == want and tuple(v.shape) == (n,)):
-                    _oops("KrylovSolver.solve", "the %s must be a device tensor of %d %s entries" % (what, n, want))
-            with torch.cuda.device(b.device):
-                bb = b.contiguous()
-                x = torch.empty(max(n, 1), dtype=want, device=b.device)[:n]
-                if x0 is not None:
-                    x.copy_(x0)
-                res = self.solve_dev(bb.data_ptr(), x.data_ptr(), x0 is not None, rtol, atol, maxiter, check_every,
-                                     True, torch.cuda.current_stream().cuda_stream)
-            return x, res
-        want = C128 if cplx else F64
-        a = np.ascontiguousarray(b)
-        if a.dtype != want or a.shape != (n,):
-            _oops("KrylovSolver.solve", "right-hand side of dtype %s and shape %s; %d %s entries are needed"
-                  % (a.dtype, a.shape, n, np.dtype(want)))
-        x = np.zeros(n, dtype=want)
-        if x0 is not None:
-            x0 = np.asarray(x0)
-            if x0.dtype != want or x0.shape != (n,):
-                _oops("KrylovSolver.solve", "a start of dtype %s and shape %s; %d %s entries are needed"
-                      % (x0.dtype, x0.shape, n, np.dtype(want)))
-            x[:] = x0
-        maxiter = self._maxiter(maxiter)
-        if check_every:  # the host-vector call has no such argument: through device tensors
-            import torch
-            with torch.cuda.device(self.A.info()["device"]):
-                db = torch.from_numpy(a).cuda()
-                dx = torch.from_numpy(x).cuda()
-                res = self.solve_dev(db.data_ptr(), dx.data_ptr(), x0 is not None, rtol, atol, maxiter, check_every,
-                                     True, torch.cuda.current_stream().cuda_stream)
-                return dx.cpu().numpy(), res
+    def _solve_host(self, a, x, use_x0, rtol, atol, maxiter):
         result = np.zeros(4, dtype=I64)
         hist = np.zeros(maxiter + 1, dtype=F64)
         check("spl_krylov_solve",
-              lib().spl_krylov_solve(self.handle, p_f64(a.view(F64)), p_f64(x.view(F64)), 1 if x0 is not None else 0,
+              lib().spl_krylov_solve(self.handle, p_f64(a.view(F64)), p_f64(x.view(F64)), 1 if use_x0 else 0,
                                      float(rtol), float(atol), maxiter, _ffi.p_i64(result), p_f64(hist)))
-        return x, self._result(result, hist)
+        return self._result(result, hist)
+
+
+class GMRESSolver(_PreconditionedSolver):
+    """Owner of a ``void *G`` from ``spl_gmres_create``: right-preconditioned restarted GMRES(restart) on a whole square
+    device handle (csrc/gmres.hip), real or complex, for unsymmetric and indefinite systems.  The orthogonalisation is
+    classical Gram-Schmidt done twice on the fused multi-vector inner product; every scalar stays in device memory, and
+    x, the counts, the history and the residuals are those of the header's sequence bit for bit.  ``M`` as KrylovSolver
+    takes it.  The result dict has ``cycles`` and ``residual`` (the true residual norm of the last cycle start)
+    and ``estimate`` (the rotations' estimate at the last close) besides KrylovSolver's keys."""
+    INFO_KEYS = ("n", "restart", "flags", "device_bytes", "solves", "iterations", "launches", "reserved")
+    RESULT_KEYS = ("iterations", "reason", "cycles", "spmvs", "preconditioner_applications", "reserved")
+    _NAME = "GMRESSolver"
+    _CALLS = {"set_preconditioner": "spl_gmres_set_preconditioner",
+              "set_preconditioner_amg": "spl_gmres_set_preconditioner_amg", "info": "spl_gmres_info",
+              "free": "spl_gmres_free"}
+
+    def __init__(self, A, restart=30, M=None):
+        restart = int(restart)
+        if not 1 <= restart <= 128:
+            raise ValueError("GMRESSolver: restart %r; 1 ... 128 is needed" % (restart,))
+        self._begin(A, M)
+        self.restart = restart
+        check("spl_gmres_create", lib().spl_gmres_create(A.handle, restart, C.byref(self._k)))
+        self.set_preconditioner(M)
+
+    @classmethod
+    def _result(cls, result, history, residual):
+        out = dict(zip(cls.RESULT_KEYS, (int(v) for v in result)))
+        del out["reserved"]
+        it, reason = out["iterations"], out["reason"]
+        out.update(reason_name=cls.REASONS[reason], converged=reason == 0, residual=float(residual[0]),
+                   estimate=float(residual[1]))
+        if history is not None:
+            out["history"] = history[:it + 1].copy()
+        return out
+
+    def solve_dev(self, b_ptr, x_ptr, use_x0=False, rtol=1e-8, atol=0.0, maxiter=None, check_every=0, history=True,
+                  stream=0):
+        """device pointers (ints) to b and x (n doubles, or packed pairs); use_x0: x holds the start.  Enqueues on
+        `stream` and returns after the solve's last synchronisation with the result dict; check_every: cycles between
+        two looks at the status block (0: every cycle)"""
+        maxiter = self._maxiter(maxiter)
+        result, residual = np.zeros(6, dtype=I64), np.zeros(2, dtype=F64)
+        hist = np.zeros(maxiter + 1, dtype=F64) if history else None
+        check("spl_gmres_solve_dev",
+              lib().spl_gmres_solve_dev(self.handle, C.c_void_p(b_ptr), C.c_void_p(x_ptr), 1 if use_x0 else 0,
+                                        float(rtol), float(atol), maxiter, int(check_every), _ffi.p_i64(result),
+                                        p_f64(hist) if history else None, p_f64(residual), C.c_void_p(stream)))
+        return self._result(result, hist, residual)
+
+    def _solve_host(self, a, x, use_x0, rtol, atol, maxiter):
+        result, residual = np.zeros(6, dtype=I64), np.zeros(2, dtype=F64)
+        hist = np.zeros(maxiter + 1, dtype=F64)
+        check("spl_gmres_solve",
+              lib().spl_gmres_solve(self.handle, p_f64(a.view(F64)), p_f64(x.view(F64)), 1 if use_x0 else 0,
+                                    float(rtol), float(atol), maxiter, _ffi.p_i64(result), p_f64(hist), p_f64(residual)))
+        return self._result(result, hist, residual)
+
+
+def gmres(mat, b, M=None, x0=None, restart=30, rtol=1e-8, atol=0.0, maxiter=None):
+    """(x, result dict) with mat x = b by right-preconditioned restarted GMRES on the device; mat: a host Matrix; M as
+    KrylovSolver takes it.  The dict is bicgstab's plus ``cycles``, ``residual`` (the true residual norm) and
+    ``estimate``"""
+    G = mat.device_handle().gmres(restart, M)
+    try:
+        return G.solve(b, x0, rtol, atol, maxiter)
+    finally:
+        G.free()
 
 
 def _krylov(method, mat, b, M, x0, rtol, atol, maxiter):
