@@ -963,6 +963,115 @@ int spl_gmres_solve(void *G, const double *b, double *x, int use_x0, double rtol
 int spl_gmres_info(void *G, int64_t info[8]);
 void spl_gmres_free(void **G);
 
+/* ---- thick-restart Lanczos on handles and the in-place basis rotation (csrc/eigsh.hip) ---------------------------------
+ * A few eigenpairs of a real symmetric or complex Hermitian handle without a factorisation: restarted Lanczos with full
+ * reorthogonalisation and thick restarts (Wu & Simon's TRLan scheme), directly on A for the ends of the spectrum, or on
+ * (A - sigma I)^-1 through a spl_krylov object for the eigenvalues nearest sigma.  The contract is the one of the
+ * sections above: values, vectors, residuals, history and counts are a serial restatement's bit for bit.
+ *
+ * spl_vector_rotate_dev: column i of the result, i = 0 ... k - 1, is x = Y[0][i] v_0; x = x + Y[l][i] v_l for
+ *   l = 1 ... m - 1 ascending, where v_l is column l of V (n entries of value_width doubles, complex as packed pairs,
+ *   column l at d_V + l * ldv * value_width doubles, ldv >= n: the layout of spl_vector_dots_dev) and Y is a REAL m x k
+ *   matrix in DEVICE memory, column major, Y[l][i] at d_Y[i * ldy + l], ldy >= m.  A real number times an entry is done
+ *   part by part; each term is one product and one sum, each rounded once.  1 <= k <= m <= 128.  d_out == NULL: the
+ *   result overwrites V[:, 0:k] IN PLACE (no second basis is allocated; columns k ... m - 1 and the rows from n on are
+ *   untouched); otherwise it goes to d_out (column i at d_out + i * ldo * value_width, ldo >= n), V is untouched and
+ *   d_out may not overlap V.  V is read once and the k columns are written once: a workgroup stages a tile of rows in
+ *   LDS, so every input of a row is read before any output of that row is written.  No floating-point atomic, no
+ *   kernel waits for another workgroup; the tile height (SPL_EIGSH_ROTATE_ROWS = 16, 32 or 64, for measurement) and
+ *   SPL_KRYLOV_GRID do not show in the bits.  Enqueued on `stream`, no synchronisation.  n == 0: SPL_OK, nothing is
+ *   written.  Errors, in this order: n < 0 SPL_ERROR_n_nonpositive; value_width not 1 or 2, m outside 1 ... 128, k
+ *   outside 1 ... m, ldv < n, ldy < m, ldo < n (with d_out), a NULL d_V or d_Y when n > 0, a pointer not aligned to an
+ *   entry (d_Y: to a double), d_out overlapping V: SPL_ERROR_argument_missing.
+ *
+ * spl_eigsh_create: a solver object for the whole square handle A with a basis of ncv columns, 2 ... 128.  Ownership,
+ *   borrowing, the lock (one solve at a time), the magic word and spl_eigsh_free's idempotence are spl_gmres_create's.
+ *   Errors, in this order: SPL_ERROR_invalid_handle (A is no matrix handle); SPL_ERROR_argument_missing (E is NULL;
+ *   otherwise *E = NULL first; then ncv outside 2 ... 128); SPL_ERROR_dimension_mismatch (not square);
+ *   SPL_ERROR_invalid_matrix (a row-block handle); SPL_ERROR_device without a GPU; SPL_ERROR_invalid_matrix (a handle for
+ *   which spl_matrix_hermitian says 0, or on which it cannot run: the test is a kernel, so it comes behind the device).
+ *   The object holds ncv + 2 vectors (the basis v_0 ... v_ncv, where slot j + 1 receives w before it is normalised, and
+ *   one product for the residuals), the partials, 7 ncv + ncv^2 doubles of tables (the coefficients of the two passes,
+ *   alpha, beta, the residuals, Y) and a status block in device memory: info[3] has the bytes.  The operator is
+ *   spl_matrix_spmv_dev as the caller configured it; SPL_ORDER_FREE voids the bit contract.
+ * spl_eigsh_set_inverse: the operator becomes OP = (A - sigma I)^-1, applied as spl_krylov_solve_dev(K, v, w, use_x0 = 0,
+ *   rtol, atol, max_iter) with the default check interval.  K is a spl_krylov object the CALLER built on A - sigma I
+ *   (spl_matrix_lin) with whatever preconditioner they set; it is borrowed.  K == NULL: back to direct mode, the other
+ *   arguments are not looked at.  Errors, in this order: SPL_ERROR_invalid_handle (E, or K, is no such object);
+ *   SPL_ERROR_dimension_mismatch (K of another size, value kind or device); SPL_ERROR_n_nonpositive (max_iter < 0);
+ *   SPL_ERROR_argument_missing (rtol or atol negative or NaN, sigma not finite).
+ *
+ * The method.  Every real operation is rounded once; a real number times an entry and an entry over a real number are
+ * done part by part; <a,b> and its fold are those of the sections above.  OP v is spl_matrix_spmv_dev on A, or the
+ * solve above; in inverse mode a solve whose reason is not 0 ends everything with reason 4 and no pairs.
+ *   start:    eta = sqrt(Re<v0,v0>);  history[0] = eta;  eta not finite: reason 3, no pairs;  eta == 0: reason 2, no
+ *             pairs;  v_0 = v0 / eta;  k = 0;  cycle = 0
+ *   step j    (j = k ... ncv - 1):  w = OP v_j
+ *             c1_i = <v_i, w>, i = 0 ... j  (one pass);  w = ((w - c1_0 v_0) - c1_1 v_1) - ...  (ascending i)
+ *             c2_i = <v_i, w>;  w = w - sum c2_i v_i the same way
+ *             alpha_j = Re(c1_j + c2_j);  beta_j = eta = sqrt(Re<w,w>);  ops = ops + 1
+ *             alpha_j or eta not finite: reason 3, no pairs
+ *             eta == 0: the cycle closes with m' = j + 1 and the solve ends behind the close
+ *             otherwise v_(j+1) = w / eta;  behind step ncv - 1 the cycle closes with m' = ncv
+ *   close:    T, real symmetric m' x m':  T_ii = theta_i and T_ik = T_ki = s_i for i < k (kept from the restart);
+ *             T_jj = alpha_j for j >= k;  T_(j,j+1) = T_(j+1,j) = beta_j for k <= j < m' - 1;  beta_last = beta_(m'-1)
+ *             T = Y diag(theta) Y^T by cyclic Jacobi on full symmetric storage, Y = I at the start:
+ *               a sweep starts only if some strict upper entry is non-zero; in a sweep p ascending, q > p ascending,
+ *               a = T_pq:  a == 0: skip;  |T_pp| + |a| == |T_pp| and |T_qq| + |a| == |T_qq|: T_pq = T_qp = 0, no rotation
+ *               otherwise tau = (T_qq - T_pp) / (2 a);  t = sgn(tau) / (|tau| + sqrt(1 + tau tau)), sgn(0) = +1;
+ *               c = 1 / sqrt(1 + t t);  s = t c;  for r != p, q:  (T_rp, T_rq) <- (c T_rp - s T_rq, s T_rp + c T_rq),
+ *               mirrored;  T_pp = T_pp - t a;  T_qq = T_qq + t a (the old diagonal);  T_pq = T_qp = 0;  for all r:
+ *               (Y_rp, Y_rq) <- (c Y_rp - s Y_rq, s Y_rp + c Y_rq)
+ *               a 61st sweep, or a theta or an entry of Y not finite at the end: reason 3, no pairs
+ *             cycle = cycle + 1;  the pairs are ordered stably by `which` (ties: lower column first), applied to the
+ *             OPERATOR's theta:  0 largest algebraic, 1 smallest algebraic, 2 largest magnitude
+ *             est_i = |beta_last Y[m'-1][i]|;  pairs = min(nev, m');  history[cycle] = max est_i, i < pairs
+ *             pair i is converged when est_i <= max(tol |theta_i|, atol)
+ *             eta was 0: reason 0 when m' >= nev, otherwise reason 2, with `pairs` pairs
+ *             else all nev converged: reason 0;  else cycle == max_restarts: reason 1, the nev Ritz pairs are returned
+ *             else restart:  k = min(m' - 1, nev + (m' - nev) / 2) (integer division);  V[:, :k] <- V Y[:, :k] in place
+ *             by spl_vector_rotate_dev's kernel;  v_k <- v_(m');  theta_i is kept, s_i = beta_last Y[m'-1][i]
+ *   finish:   X = V Y[:, :pairs] by the same kernel into d_vectors, not renormalised
+ *             values[i] = theta_i, in inverse mode sigma + 1 / theta_i (IEEE)
+ *             residuals[i] = sqrt(Re<r,r>), r = A x_i - values[i] x_i:  the product by spl_matrix_spmv_dev on A itself
+ *             in both modes, each entry of r one product part by part and one difference
+ * The test that drops a coupling is on |a| itself: on |t a| it drops couplings that still carry the last row of Y, and
+ * the estimate becomes 0 on a residual that is not.  A single-vector Lanczos finds ONE copy of a multiple eigenvalue.
+ *
+ * spl_eigsh_solve_dev: d_v0 (n entries) and d_vectors (nev columns, ldx >= n entries apart) are DEVICE arrays; values,
+ *   residuals (nev doubles each), result and history (NULL, or max_restarts + 1 doubles) are the HOST's.  d_v0 is
+ *   required: the library draws no random numbers.  In direct mode no scalar leaves the device inside a cycle: one
+ *   workgroup behind the folds writes alpha_j and beta_j into a table, the host issues every step of the cycle and each
+ *   kernel returns once the cycle is closed; the close is the host's, ONE synchronisation per cycle.  In inverse mode
+ *   the inner solve synchronises, and the status block is read behind every step.  No captured graph.
+ *   result = {reason, cycles closed, applications of OP (a failed inner solve is not counted), pairs returned, inner
+ *   iterations in total, most Jacobi sweeps of a close}; reasons: 0 converged, 1 max_restarts, 2 invariant subspace
+ *   smaller than nev (or a zero start), 3 not finite, 4 inner solve failed.  Only the first result[3] entries of values,
+ *   residuals and d_vectors are written.  Returns SPL_OK whenever it ran.  Errors, in this order:
+ *   SPL_ERROR_invalid_handle (E); SPL_ERROR_argument_missing (values, residuals or result NULL);
+ *   SPL_ERROR_n_nonpositive (max_restarts < 1); SPL_ERROR_argument_missing (not 1 <= nev < ncv <= n, `which` outside
+ *   0 ... 2, tol or atol negative or NaN); SPL_ERROR_index_overflow (a history of 2^31 entries or more);
+ *   SPL_ERROR_argument_missing (d_v0 or d_vectors NULL or not aligned to an entry, ldx < n).
+ * spl_eigsh_solve: the same with a HOST v0 and HOST vectors, on the default stream.
+ * spl_eigsh_info: [0] n, [1] ncv, [2] flags (1 complex, 2 inverse mode), [3] bytes of device memory, [4] solves,
+ *   [5] cycles of the last solve, [6] launches of the last solve (the SpMV counted as one, inner solves not counted),
+ *   [7] 0.
+ * spl_eigsh_free: idempotent, as spl_krylov_free. */
+#define SPL_EIGSH_largest_algebraic 0
+#define SPL_EIGSH_smallest_algebraic 1
+#define SPL_EIGSH_largest_magnitude 2
+int spl_vector_rotate_dev(int64_t n, int value_width, int m, int k, double *d_V, int64_t ldv, const double *d_Y, int ldy,
+                          double *d_out, int64_t ldo, void *stream);
+int spl_eigsh_create(void *A, int ncv, void **E);
+int spl_eigsh_set_inverse(void *E, void *K, double sigma, double rtol, double atol, int64_t max_iter);
+int spl_eigsh_solve_dev(void *E, int nev, int which, double tol, double atol, int64_t max_restarts, const double *d_v0,
+                        double *values, double *d_vectors, int64_t ldx, double *residuals, int64_t result[6],
+                        double *history, void *stream);
+int spl_eigsh_solve(void *E, int nev, int which, double tol, double atol, int64_t max_restarts, const double *v0,
+                    double *values, double *vectors, int64_t ldx, double *residuals, int64_t result[6], double *history);
+int spl_eigsh_info(void *E, int64_t info[8]);
+void spl_eigsh_free(void **E);
+
 /* select a kernel variant for spl_matrix_spmv_dev (tuning / ablation only): 0 = default
  * (whatever spl_matrix_optimize chose), 1-6 CSR-stream shapes, 7 sub-wavefront kernel, 8
  * column-blocked image, 9-11 gather cache policies, 15 sliced-ELL image, 16 column-sorted panel

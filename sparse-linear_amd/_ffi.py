@@ -40,6 +40,7 @@ SPL_DIAG_stored, SPL_DIAG_unit = 0, 1
 SPL_OP_n, SPL_OP_t, SPL_OP_h = 0, 1, 2
 # preconditioned CG and BiCGSTAB on handles (spl_krylov_*)
 SPL_KRYLOV_cg, SPL_KRYLOV_bicgstab = 0, 1
+SPL_EIGSH_largest_algebraic, SPL_EIGSH_smallest_algebraic, SPL_EIGSH_largest_magnitude = 0, 1, 2
 # multicolour ordering on handles (spl_matrix_color)
 SPL_COLOR_hash = 0
 
@@ -183,6 +184,13 @@ def _declare(L):
         "spl_gmres_solve_dev": [C.c_void_p, C.c_void_p, C.c_void_p, i, d, d, i64, i, c_i64_p, c_dbl_p, c_dbl_p, C.c_void_p],
         "spl_gmres_solve": [C.c_void_p, c_dbl_p, c_dbl_p, i, d, d, i64, c_i64_p, c_dbl_p, c_dbl_p],
         "spl_gmres_info": [C.c_void_p, c_i64_p],
+        "spl_vector_rotate_dev": [i64, i, i, i, C.c_void_p, i64, C.c_void_p, i, C.c_void_p, i64, C.c_void_p],
+        "spl_eigsh_create": [C.c_void_p, i, c_void_pp],
+        "spl_eigsh_set_inverse": [C.c_void_p, C.c_void_p, d, d, d, i64],
+        "spl_eigsh_solve_dev": [C.c_void_p, i, i, d, d, i64, C.c_void_p, c_dbl_p, C.c_void_p, i64, c_dbl_p, c_i64_p,
+                                c_dbl_p, C.c_void_p],
+        "spl_eigsh_solve": [C.c_void_p, i, i, d, d, i64, c_dbl_p, c_dbl_p, c_dbl_p, i64, c_dbl_p, c_i64_p, c_dbl_p],
+        "spl_eigsh_info": [C.c_void_p, c_i64_p],
         "spl_matrix_set_variant": [C.c_void_p, i],
         "spl_matrix_optimize": [C.c_void_p],
         "spl_matrix_build_blocked": [C.c_void_p, i, i, i],
@@ -221,6 +229,9 @@ def _declare(L):
     if hasattr(L, "spl_gmres_free"):
         L.spl_gmres_free.restype = None
         L.spl_gmres_free.argtypes = [c_void_pp]
+    if hasattr(L, "spl_eigsh_free"):
+        L.spl_eigsh_free.restype = None
+        L.spl_eigsh_free.argtypes = [c_void_pp]
     if hasattr(L, "spl_amg_free"):
         L.spl_amg_free.restype = None
         L.spl_amg_free.argtypes = [c_void_pp]

@@ -2102,6 +2102,143 @@ void spl_gmres_free(void **G) {
   if (have_prev) (void)hipSetDevice(prev);
 }
 
+// ---- thick-restart Lanczos on handles and the in-place basis rotation (csrc/eigsh.hip) ----------------------------------
+int spl_vector_rotate_dev(int64_t n, int value_width, int m, int k, double *d_V, int64_t ldv, const double *d_Y, int ldy,
+                          double *d_out, int64_t ldo, void *stream) {
+  if (n < 0) return SPL_ERROR_n_nonpositive;
+  if (value_width != 1 && value_width != 2) return SPL_ERROR_argument_missing;
+  if (m < 1 || m > 128 || k < 1 || k > m || ldv < n || ldy < m || (d_out && ldo < n)) return SPL_ERROR_argument_missing;
+  if (n > 0 && (!d_V || !d_Y)) return SPL_ERROR_argument_missing;
+  const uintptr_t entry = (uintptr_t)(8 * value_width);  // the kernel loads and stores whole entries
+  if ((uintptr_t)d_V % entry != 0 || (uintptr_t)d_Y % sizeof(double) != 0 || (uintptr_t)d_out % entry != 0)
+    return SPL_ERROR_argument_missing;
+  if (d_out && n > 0) {  // the result beside V, not over it
+    const uintptr_t v0 = (uintptr_t)d_V, v1 = v0 + ((uintptr_t)(m - 1) * (uintptr_t)ldv + (uintptr_t)n) * entry;
+    const uintptr_t o0 = (uintptr_t)d_out, o1 = o0 + ((uintptr_t)(k - 1) * (uintptr_t)ldo + (uintptr_t)n) * entry;
+    if (o0 < v1 && v0 < o1) return SPL_ERROR_argument_missing;
+  }
+  return guarded([&]() -> int {
+    (void)current_device();
+    return vector_rotate(n, value_width, m, k, d_V, ldv, d_Y, ldy, d_out, ldo, as_stream(stream));
+  });
+}
+
+// A is borrowed: the object keeps the pointer, its ncv + 2 vectors and its tables
+int spl_eigsh_create(void *A, int ncv, void **E) {
+  Matrix *M = as_matrix(A);
+  if (!M) return SPL_ERROR_invalid_handle;
+  if (!E) return SPL_ERROR_argument_missing;
+  *E = nullptr;
+  if (ncv < 2 || ncv > 128) return SPL_ERROR_argument_missing;
+  if (M->nrows_global != M->ncols) return SPL_ERROR_dimension_mismatch;
+  if (!whole(M)) return SPL_ERROR_invalid_matrix;
+  return guarded([&]() -> int {
+    (void)current_device();
+    DeviceGuard g(M->device);
+    if (!M->rowptr.get() || hermitian_device(M, nullptr) != 1) return SPL_ERROR_invalid_matrix;
+    Eigsh *S = nullptr;
+    const int st = eigsh_create(M, ncv, &S);
+    *E = S;
+    return st;
+  });
+}
+
+// K is borrowed; NULL: the operator is A again
+int spl_eigsh_set_inverse(void *E, void *K, double sigma, double rtol, double atol, int64_t max_iter) {
+  Eigsh *S = as_eigsh(E);
+  if (!S) return SPL_ERROR_invalid_handle;
+  Krylov *P = nullptr;
+  if (K) {
+    P = as_krylov(K);
+    if (!P) return SPL_ERROR_invalid_handle;
+    if (krylov_rows(P) != eigsh_rows(S) || krylov_width(P) != eigsh_width(S) || krylov_device(P) != eigsh_device(S))
+      return SPL_ERROR_dimension_mismatch;
+    if (max_iter < 0) return SPL_ERROR_n_nonpositive;
+    if (!(rtol >= 0.0) || !(atol >= 0.0) || !std::isfinite(sigma)) return SPL_ERROR_argument_missing;  // a NaN too
+  }
+  eigsh_set_inverse(S, P, sigma, rtol, atol, max_iter);
+  return SPL_OK;
+}
+
+namespace {
+// what both solve calls refuse before the vectors are looked at
+int check_eigsh_solve(const Eigsh *S, int nev, int which, double tol, double atol, int64_t max_restarts,
+                      const double *values, const double *residuals, const int64_t *result, const double *history) {
+  if (!S) return SPL_ERROR_invalid_handle;
+  if (!values || !residuals || !result) return SPL_ERROR_argument_missing;
+  if (max_restarts < 1) return SPL_ERROR_n_nonpositive;
+  if (nev < 1 || nev >= eigsh_ncv(S) || (int64_t)eigsh_ncv(S) > eigsh_rows(S) || which < 0 || which > 2 || !(tol >= 0.0) ||
+      !(atol >= 0.0))
+    return SPL_ERROR_argument_missing;  // a NaN is refused too
+  if (history && max_restarts >= ((int64_t)1 << 31)) return SPL_ERROR_index_overflow;
+  return SPL_OK;
+}
+}  // namespace
+
+int spl_eigsh_solve_dev(void *E, int nev, int which, double tol, double atol, int64_t max_restarts, const double *d_v0,
+                        double *values, double *d_vectors, int64_t ldx, double *residuals, int64_t result[6],
+                        double *history, void *stream) {
+  Eigsh *S = as_eigsh(E);
+  const int refused = check_eigsh_solve(S, nev, which, tol, atol, max_restarts, values, residuals, result, history);
+  if (refused != SPL_OK) return refused;
+  if (!d_v0 || !d_vectors || ldx < eigsh_rows(S)) return SPL_ERROR_argument_missing;
+  const uintptr_t entry = (uintptr_t)(8 * eigsh_width(S));  // the kernels load and store whole entries
+  if ((uintptr_t)d_v0 % entry != 0 || (uintptr_t)d_vectors % entry != 0) return SPL_ERROR_argument_missing;
+  return guarded([&]() -> int {
+    DeviceGuard g(eigsh_device(S));
+    return eigsh_solve(S, nev, which, tol, atol, max_restarts, d_v0, values, d_vectors, ldx, residuals, result, history,
+                       as_stream(stream));
+  });
+}
+
+// host v0 (n entries, packed complex) and vectors (nev columns, ldx entries apart): up, solved on the default stream, down
+int spl_eigsh_solve(void *E, int nev, int which, double tol, double atol, int64_t max_restarts, const double *v0,
+                    double *values, double *vectors, int64_t ldx, double *residuals, int64_t result[6], double *history) {
+  Eigsh *S = as_eigsh(E);
+  const int refused = check_eigsh_solve(S, nev, which, tol, atol, max_restarts, values, residuals, result, history);
+  if (refused != SPL_OK) return refused;
+  if (!v0 || !vectors || ldx < eigsh_rows(S)) return SPL_ERROR_argument_missing;
+  return guarded([&]() -> int {
+    DeviceGuard g(eigsh_device(S));
+    hipStream_t s = nullptr;
+    const size_t count = (size_t)eigsh_rows(S) * (size_t)eigsh_width(S);
+    DBuf<double> d(((size_t)nev + 1) * count);
+    double *d_v0 = d.get(), *d_vectors = d.get() + count;
+    SPL_HIP(hipMemcpyAsync(d_v0, v0, count * sizeof(double), hipMemcpyHostToDevice, s));
+    const int st = eigsh_solve(S, nev, which, tol, atol, max_restarts, d_v0, values, d_vectors, eigsh_rows(S), residuals,
+                               result, history, s);
+    if (st != SPL_OK) {
+      (void)hipStreamSynchronize(s);
+      return st;
+    }
+    for (int64_t i = 0; i < result[3]; ++i)
+      SPL_HIP(hipMemcpyAsync(vectors + (size_t)i * (size_t)ldx * (size_t)eigsh_width(S), d_vectors + (size_t)i * count,
+                             count * sizeof(double), hipMemcpyDeviceToHost, s));
+    SPL_HIP(hipStreamSynchronize(s));
+    return SPL_OK;
+  });
+}
+
+int spl_eigsh_info(void *E, int64_t info[8]) {
+  Eigsh *S = as_eigsh(E);
+  if (!S) return SPL_ERROR_invalid_handle;
+  if (!info) return SPL_ERROR_argument_missing;
+  eigsh_info(S, info);
+  return SPL_OK;
+}
+
+void spl_eigsh_free(void **E) {
+  if (!E || !*E) return;
+  Eigsh *S = as_eigsh(*E);
+  *E = nullptr;
+  if (!S) return;
+  int prev = -1;
+  const bool have_prev = hipGetDevice(&prev) == hipSuccess;
+  (void)hipSetDevice(eigsh_device(S));  // may run on a finalizer thread with another current device
+  eigsh_delete(S);
+  if (have_prev) (void)hipSetDevice(prev);
+}
+
 // mulM on Complex Double (the reference's SPECIALIZE instance, Sparse.hs:475): one axpy_ per column of B there; here the
 // packed-complex image of A and one multi-vector product.  B and C are row-major like spl_mulm's; the kernel wants one
 // vector after the other, so both are turned on the device (the call is bounded by its copies over PCIe).

@@ -412,6 +412,28 @@ int64_t gmres_rows(const Gmres *G);
 int gmres_width(const Gmres *G);  // doubles per entry: 1 real, 2 packed complex
 void gmres_delete(Gmres *G);
 
+// ---- thick-restart Lanczos on handles and the in-place basis rotation (eigsh.hip) ---------------------------------------
+// V[:, :k] <- V Y (d_out == nullptr) or d_out = V Y: V n x m entries of vw doubles, Y real m x k, all column major in
+// device memory; 1 <= k <= m <= 128 and d_out clear of V (the caller checked); enqueues on s, no synchronisation
+int vector_rotate(int64_t n, int vw, int m, int k, double *d_V, int64_t ldv, const double *d_Y, int ldy, double *d_out,
+                  int64_t ldo, hipStream_t s);
+struct Eigsh;
+Eigsh *as_eigsh(void *e);  // nullptr unless e carries the object's magic word
+// A: whole, square and Hermitian, 2 <= ncv <= 128 (the caller checked); borrowed.  SPL_OK
+int eigsh_create(const Matrix *A, int ncv, Eigsh **out);
+// K: borrowed, of E's size, value kind and device (the caller checked), or nullptr: the operator is A again
+void eigsh_set_inverse(Eigsh *E, Krylov *K, double sigma, double rtol, double atol, int64_t max_iter);
+// n > 0 and the arguments are checked by the caller; enqueues on s and synchronises it (the outcome is read back)
+int eigsh_solve(Eigsh *E, int nev, int which, double tol, double atol, int64_t max_restarts, const double *d_v0,
+                double *values, double *d_vectors, int64_t ldx, double *residuals, int64_t result[6], double *history,
+                hipStream_t s);
+void eigsh_info(Eigsh *E, int64_t info[8]);
+int eigsh_device(const Eigsh *E);
+int64_t eigsh_rows(const Eigsh *E);
+int eigsh_width(const Eigsh *E);  // doubles per entry: 1 real, 2 packed complex
+int eigsh_ncv(const Eigsh *E);
+void eigsh_delete(Eigsh *E);
+
 // ---- multifrontal LU without interchanges (multifrontal.hip, mf_symbolic.hpp) ------------------
 namespace mf {
 struct Tree;

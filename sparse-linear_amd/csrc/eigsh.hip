@@ -1,0 +1,622 @@
+// eigsh.hip — thick-restart Lanczos with full reorthogonalisation on device handles, Double and packed Complex Double
+// (real symmetric and complex Hermitian), and the in-place basis rotation its restart is built on
+// (spl_vector_rotate_dev).
+//
+// The arithmetic is the fold of krylov_fold.hpp and the sequence of include/sparse_linear_hip.h ("thick-restart
+// Lanczos").  A step is a GMRES step: the product, classical Gram-Schmidt done twice with the one-pass kernels of
+// krylov_basis.hpp, the norm.  In direct mode no scalar leaves the device inside a cycle: ONE workgroup behind the folds
+// (step_kernel) writes alpha_j and beta_j into a table and sets `skip` when the cycle ends early; the host issues every
+// step and each kernel returns on `skip`.  In inverse mode the product is a solve by a spl_krylov object, which
+// synchronises anyway, and the host reads the status block behind every step.
+//
+// The close is the host's: one synchronisation per cycle brings the two tables down, the projected matrix (an arrow head
+// from the restart and a tridiagonal tail) is diagonalised by cyclic Jacobi in plain C++ (-ffp-contract=off: a product
+// and a sum are rounded apart on the host too), and the restart V[:, :k] <- V Y is the rotate kernel IN PLACE: a row tile
+// of the basis is staged in LDS, so every input of a row is read before any output of that row is written, and no second
+// basis exists.  No kernel waits for another workgroup, there is no floating-point atomic and no captured graph.
+#include <algorithm>
+#include <cmath>
+#include <vector>
+
+#include "krylov_basis.hpp"
+
+namespace spl {
+
+constexpr uint32_t kEigshMagic = 0x53504C45u;  // "SPLE"
+
+namespace {
+
+constexpr int kRotateCols = 4;              // output columns a lane carries through one walk over the tile's columns
+constexpr int kRotateRowsLog2 = 6;          // rows of a tile: 64; SPL_EIGSH_ROTATE_ROWS = 16, 32, 64
+constexpr size_t kRotateLds = 64 * 1024;    // bytes of LDS a tile may take
+constexpr int kMaxSweeps = 60;
+
+// ---- V[:, :k] <- V Y ---------------------------------------------------------------------------------------------------
+// A workgroup takes tiles of R = 2^rows_log2 consecutive rows.  Load: lane t takes row t mod R of the columns t / R,
+// t / R + 256 / R, ...: consecutive lanes read consecutive rows of a column.  The tile lies in LDS plane by plane,
+// tile[(l * VW + p) * R + r], so the R lanes that read column l in the product read consecutive doubles (no bank
+// conflict; lanes of another column group read the same words, a broadcast).  Product: the lane keeps its row and takes
+// the output columns g, g + G, ... (G = 256 / R), kRotateCols of them per walk over l, each
+// x = Y[0][i] v_0; x = x + Y[l][i] v_l ascending, a product and a sum per term and part.  V and out may be the same
+// array: a tile's loads are all in front of the barrier, its stores behind it, and no other workgroup touches its rows.
+// WAVE (R == 64): a wavefront is one column group, so its output columns and the entries of Y it needs are the same in
+// every lane, and Y is read through the scalar cache instead of one vector load per lane and term.
+template <int VW, bool WAVE>
+__global__ __launch_bounds__(kLanes) void rotate_kernel(int64_t n, int m, int k, int rows_log2, const double *V,
+                                                        int64_t ldv, const double *__restrict__ Y, int ldy, double *out,
+                                                        int64_t ldo) {
+  extern __shared__ double tile[];
+  constexpr int kTerms = WAVE ? 2 : 4;  // terms per round of the walk: by four the scalar registers of WAVE do not fit
+  const int R = 1 << rows_log2, t = threadIdx.x, r = t & (R - 1), G = kLanes >> rows_log2;
+  const int g = WAVE ? __builtin_amdgcn_readfirstlane(t >> rows_log2) : t >> rows_log2;
+  const int64_t ntiles = (n + R - 1) >> rows_log2;
+  for (int64_t tl = blockIdx.x; tl < ntiles; tl += gridDim.x) {
+    const int64_t row = (tl << rows_log2) + r;
+    const bool live = row < n;
+    for (int l = g; l < m; l += G) {
+      const Val<VW> v = live ? load_val<VW>(V + (size_t)l * (size_t)ldv * VW, row) : Val<VW>();
+      tile[(size_t)(l * VW) * R + r] = v.re;
+      if (VW == 2) tile[(size_t)(l * VW + 1) * R + r] = imag_of(v);
+    }
+    __syncthreads();
+    for (int i0 = g; i0 < k; i0 += kRotateCols * G) {
+      const double *y[kRotateCols];
+      double acc[kRotateCols * VW];
+#pragma unroll
+      for (int c = 0; c < kRotateCols; ++c) {
+        const int col = i0 + c * G;
+        y[c] = Y + (size_t)(col < k ? col : i0) * (size_t)ldy;  // a column past k: computed again, never stored
+      }
+#pragma unroll
+      for (int p = 0; p < VW; ++p) {
+        const double a = tile[(size_t)p * R + r];
+#pragma unroll
+        for (int c = 0; c < kRotateCols; ++c) acc[c * VW + p] = y[c][0] * a;
+      }
+#pragma unroll kTerms
+      for (int l = 1; l < m; ++l) {
+#pragma unroll
+        for (int p = 0; p < VW; ++p) {
+          const double a = tile[(size_t)(l * VW + p) * R + r];
+#pragma unroll
+          for (int c = 0; c < kRotateCols; ++c) acc[c * VW + p] = acc[c * VW + p] + y[c][l] * a;
+        }
+      }
+      if (live) {
+#pragma unroll
+        for (int c = 0; c < kRotateCols; ++c) {
+          const int col = i0 + c * G;
+          if (col < k) store_val(out + (size_t)col * (size_t)ldo * VW, row, from_planes<VW>(acc + c * VW, 0));
+        }
+      }
+    }
+    __syncthreads();  // the tile is written again for the workgroup's next rows
+  }
+}
+
+// rows of a tile: the knob, halved until the tile fits; a function of m and the value width alone
+int rotate_rows_log2(int m, int vw) {
+  const char *e = getenv("SPL_EIGSH_ROTATE_ROWS");
+  const long v = e ? atol(e) : 0;
+  int lg = v == 16 ? 4 : v == 32 ? 5 : v == 64 ? 6 : kRotateRowsLog2;
+  while (lg > 4 && ((size_t)m * (size_t)vw * sizeof(double) << lg) > kRotateLds) --lg;
+  return lg;
+}
+
+// n > 0; 1 <= k <= m <= 128.  One launch on s
+void rotate_launch(int64_t n, int vw, int m, int k, const double *V, int64_t ldv, const double *Y, int ldy,
+                   double *out, int64_t ldo, hipStream_t s) {
+  const int lg = rotate_rows_log2(m, vw);
+  const size_t lds = (size_t)m * (size_t)vw * sizeof(double) << lg;
+  const int64_t tiles = (n + ((int64_t)1 << lg) - 1) >> lg, cap = chunk_grid_cap();
+  const dim3 grid((unsigned)(tiles < cap ? tiles : cap)), block(kLanes);
+  if (vw == 1 && lg == 6)
+    hipLaunchKernelGGL((rotate_kernel<1, true>), grid, block, lds, s, n, m, k, lg, V, ldv, Y, ldy, out, ldo);
+  else if (vw == 1)
+    hipLaunchKernelGGL((rotate_kernel<1, false>), grid, block, lds, s, n, m, k, lg, V, ldv, Y, ldy, out, ldo);
+  else if (lg == 6)
+    hipLaunchKernelGGL((rotate_kernel<2, true>), grid, block, lds, s, n, m, k, lg, V, ldv, Y, ldy, out, ldo);
+  else
+    hipLaunchKernelGGL((rotate_kernel<2, false>), grid, block, lds, s, n, m, k, lg, V, ldv, Y, ldy, out, ldo);
+}
+
+// ---- the status block and the tables -------------------------------------------------------------------------------------
+struct EStatus {
+  int skip;       // the cycle is closed (eta == 0) or the solve is over (pending): the kernels of a step return
+  int pending;    // reason + 1 of what ends the solve
+  int mprime;     // columns of the cycle so far: j + 1 behind step j
+  int spare;
+  long long ops;  // applications of the operator
+  double scale;   // eta: what the next basis vector is divided by
+  double eta0;    // the norm of the start
+};
+
+// in doubles from the start of the block; m = ncv
+struct ETables {
+  double *alpha, *beta;  // m each; with `res` the part the host reads at a close and at the end
+  double *res;           // m: |r_i|^2 of the pairs returned
+  double *c1, *c2;       // the coefficients of the two passes: m entries each
+  double *Y;             // m x m, column major
+};
+inline size_t etable_doubles(int m) { return (size_t)7 * (size_t)m + (size_t)m * (size_t)m; }
+inline ETables etables_at(double *base, int m) {
+  ETables T;
+  T.c1 = base;  // packed pairs are loaded whole: 16-byte aligned
+  T.c2 = T.c1 + 2 * m;
+  T.alpha = T.c2 + 2 * m;
+  T.beta = T.alpha + m;
+  T.res = T.beta + m;
+  T.Y = T.res + m;
+  return T;
+}
+
+// ---- the vector kernels ---------------------------------------------------------------------------------------------------
+// partials of Re<v,v>
+template <int VW>
+__global__ __launch_bounds__(kLanes) void norm_kernel(int64_t n, const double *__restrict__ v, double *part) {
+  chunk_partials<1>(n, part, 0, [&](int64_t i, double *acc) {
+    const Val<VW> vi = load_val<VW>(v, i);
+    acc[0] = acc[0] + mul(conj_of(vi), vi).re;
+  });
+}
+
+// out = in / *d, part by part: `count` doubles; in and out may be the same array
+__global__ __launch_bounds__(kLanes) void divide_kernel(const int *stop, int64_t count, const double *d, const double *in,
+                                                        double *out) {
+  if (*stop) return;
+  const double by = *d;
+  int64_t i = (int64_t)blockIdx.x * kLanes + threadIdx.x;
+  const int64_t stride = (int64_t)gridDim.x * kLanes;
+  for (; i < count; i += stride) out[i] = in[i] / by;
+}
+
+// r = ax - lambda x, one product part by part and one difference per entry; partials of Re<r,r>
+template <int VW>
+__global__ __launch_bounds__(kLanes) void residual_kernel(int64_t n, const double *__restrict__ ax,
+                                                          const double *__restrict__ x, double lambda, double *part) {
+  chunk_partials<1>(n, part, 0, [&](int64_t i, double *acc) {
+    const Val<VW> ri = sub(load_val<VW>(ax, i), scaled(lambda, load_val<VW>(x, i)));
+    acc[0] = acc[0] + mul(conj_of(ri), ri).re;
+  });
+}
+
+// ---- the scalar kernels: ONE workgroup each ------------------------------------------------------------------------------
+// eta = sqrt(Re<v0,v0>) from the last partials, and what it decides
+__global__ __launch_bounds__(kLanes) void start_kernel(EStatus *st, const double *part, int count) {
+  __shared__ double lds[kLanes];
+  const int t = threadIdx.x;
+  double f[1] = {0.0};
+  for (int i = t; i < count; i += kLanes) f[0] = f[0] + part[i];
+  lane_tree<1>(f, lds);
+  if (t != 0) return;
+  const double eta = sqrt(f[0]);
+  st->eta0 = eta;
+  if (!isfinite(eta)) {
+    st->pending = 3 + 1;
+    st->skip = 1;
+  } else if (eta == 0.0) {
+    st->pending = 2 + 1;
+    st->skip = 1;
+  } else {
+    st->scale = eta;
+  }
+}
+
+// Step j behind the folds: eta from the partials of <w,w>, alpha_j = Re(c1_j + c2_j), the two tables and the decisions
+template <int VW>
+__global__ __launch_bounds__(kLanes) void step_kernel(EStatus *st, int j, const double *part, int count, ETables T) {
+  if (st->skip) return;
+  __shared__ double lds[kLanes];
+  const int t = threadIdx.x;
+  double f[1] = {0.0};
+  for (int i = t; i < count; i += kLanes) f[0] = f[0] + part[i];
+  lane_tree<1>(f, lds);
+  if (t != 0) return;
+  const double eta = sqrt(f[0]);
+  const double alpha = add(load_val<VW>(T.c1, j), load_val<VW>(T.c2, j)).re;
+  T.alpha[j] = alpha;
+  T.beta[j] = eta;
+  st->ops = st->ops + 1;
+  if (!isfinite(alpha) || !isfinite(eta)) {
+    st->pending = 3 + 1;
+    st->skip = 1;
+    return;
+  }
+  st->mprime = j + 1;
+  if (eta == 0.0) {
+    st->skip = 1;
+    return;
+  }
+  st->scale = eta;
+}
+
+// ---- the close, on the host ------------------------------------------------------------------------------------------------
+// Cyclic Jacobi on the full symmetric T (m x m, T[r * m + c]) with Y = I at the start (Y[r * m + c]): T's diagonal
+// becomes the values, Y's columns the vectors.  Sweeps started, or -1 past kMaxSweeps
+int jacobi(int m, std::vector<double> &T, std::vector<double> &Y) {
+  auto at = [m](std::vector<double> &M, int r, int c) -> double & { return M[(size_t)r * m + c]; };
+  for (int r = 0; r < m; ++r)
+    for (int c = 0; c < m; ++c) at(Y, r, c) = r == c ? 1.0 : 0.0;
+  for (int sweeps = 0;; ++sweeps) {
+    bool any = false;
+    for (int p = 0; p < m && !any; ++p)
+      for (int q = p + 1; q < m; ++q)
+        if (at(T, p, q) != 0.0) { any = true; break; }
+    if (!any) return sweeps;
+    if (sweeps == kMaxSweeps) return -1;
+    for (int p = 0; p < m; ++p)
+      for (int q = p + 1; q < m; ++q) {
+        const double a = at(T, p, q);
+        if (a == 0.0) continue;
+        const double app = at(T, p, p), aqq = at(T, q, q);
+        if (fabs(app) + fabs(a) == fabs(app) && fabs(aqq) + fabs(a) == fabs(aqq)) {
+          at(T, p, q) = at(T, q, p) = 0.0;
+          continue;
+        }
+        const double tau = (aqq - app) / (2.0 * a);
+        const double den = fabs(tau) + sqrt(1.0 + tau * tau);
+        const double tt = (tau >= 0.0 ? 1.0 : -1.0) / den;
+        const double c = 1.0 / sqrt(1.0 + tt * tt), s = tt * c;
+        for (int r = 0; r < m; ++r) {
+          if (r == p || r == q) continue;
+          const double rp = at(T, r, p), rq = at(T, r, q);
+          const double np = c * rp - s * rq, nq = s * rp + c * rq;
+          at(T, r, p) = at(T, p, r) = np;
+          at(T, r, q) = at(T, q, r) = nq;
+        }
+        at(T, p, p) = app - tt * a;
+        at(T, q, q) = aqq + tt * a;
+        at(T, p, q) = at(T, q, p) = 0.0;
+        for (int r = 0; r < m; ++r) {
+          const double rp = at(Y, r, p), rq = at(Y, r, q);
+          at(Y, r, p) = c * rp - s * rq;
+          at(Y, r, q) = s * rp + c * rq;
+        }
+      }
+  }
+}
+
+}  // namespace
+
+// V[:, :k] <- V Y (d_out == nullptr) or out = V Y; enqueues on s.  Arguments checked by the caller.
+int vector_rotate(int64_t n, int vw, int m, int k, double *d_V, int64_t ldv, const double *d_Y, int ldy, double *d_out,
+                  int64_t ldo, hipStream_t s) {
+  if (n == 0) return SPL_OK;
+  rotate_launch(n, vw, m, k, d_V, ldv, d_Y, ldy, d_out ? d_out : d_V, d_out ? ldo : ldv, s);
+  const hipError_t e = hipGetLastError();
+  if (e != hipSuccess) {
+    set_last_error("vector rotate launch", e);
+    (void)hipStreamSynchronize(s);
+    return SPL_ERROR_device;
+  }
+  return SPL_OK;
+}
+
+// ---- the solver object -------------------------------------------------------------------------------------------------
+struct Eigsh {
+  uint32_t magic = kEigshMagic;
+  int device = 0;
+  int vw = 1;
+  int ncv = 0;
+  int64_t n = 0;
+  const Matrix *A = nullptr;  // borrowed
+  Krylov *K = nullptr;        // borrowed; set: the operator is (A - sigma I)^-1 by K
+  double sigma = 0.0, rtol = 0.0, atol = 0.0;
+  int64_t max_iter = 0;
+  DBuf<double> work;     // ncv + 2 vectors: the basis v_0 ... v_ncv and A x of the residuals
+  DBuf<double> scratch;  // partials of the fold
+  DBuf<double> tables;
+  DBuf<EStatus> status;
+  EStatus *pinned = nullptr;  // the status block, alpha, beta and res, and the ncv x ncv doubles that go up
+  size_t bytes = 0;
+  std::mutex lock;  // one solve at a time
+  int64_t solves = 0, last_cycles = 0, last_launches = 0;
+  double *vec(int i) const { return work.get() + (size_t)i * (size_t)n * (size_t)vw; }
+  double *host_tables() const { return reinterpret_cast<double *>(pinned + 1); }
+  double *host_y() const { return host_tables() + 3 * ncv; }
+};
+
+Eigsh *as_eigsh(void *e) {
+  Eigsh *E = static_cast<Eigsh *>(e);
+  return (E && E->magic == kEigshMagic) ? E : nullptr;
+}
+
+// A: whole, square and Hermitian, 2 <= ncv <= 128 (the caller checked)
+int eigsh_create(const Matrix *A, int ncv, Eigsh **out) {
+  std::unique_ptr<Eigsh> E(new Eigsh);
+  E->device = A->device;
+  E->vw = A->vw;
+  E->ncv = ncv;
+  E->n = A->nrows_local;
+  E->A = A;
+  const size_t vec_doubles = (size_t)E->n * (size_t)E->vw, nvec = (size_t)ncv + 2;
+  E->work.alloc(nvec * vec_doubles);
+  const size_t scratch = fold_scratch(E->n, ncv * E->vw);
+  E->scratch.alloc(scratch);
+  E->tables.alloc(etable_doubles(ncv));
+  E->status.alloc(1);
+  SPL_HIP(hipHostMalloc(reinterpret_cast<void **>(&E->pinned),
+                        sizeof(EStatus) + ((size_t)3 * ncv + (size_t)ncv * ncv) * sizeof(double), hipHostMallocDefault));
+  E->bytes = (nvec * vec_doubles + scratch + etable_doubles(ncv)) * sizeof(double) + sizeof(EStatus);
+  *out = E.release();
+  return SPL_OK;
+}
+
+void eigsh_set_inverse(Eigsh *E, Krylov *K, double sigma, double rtol, double atol, int64_t max_iter) {
+  std::lock_guard<std::mutex> hold(E->lock);
+  E->K = K;
+  E->sigma = K ? sigma : 0.0;
+  E->rtol = rtol;
+  E->atol = atol;
+  E->max_iter = max_iter;
+}
+
+namespace {
+
+// One solve's launches; everything is enqueued on s
+template <int VW>
+struct ERun {
+  Eigsh *E;
+  hipStream_t s;
+  int64_t n;
+  int m;  // ncv
+  EStatus *st;
+  double *scratch;
+  ETables T;
+  unsigned flat, chunked;
+  int64_t launches = 0, inner = 0;
+
+  ERun(Eigsh *e, hipStream_t stream)
+      : E(e), s(stream), n(e->n), m(e->ncv), st(e->status.get()), scratch(e->scratch.get()),
+        T(etables_at(e->tables.get(), e->ncv)), flat(grid_flat(e->n, 4096)), chunked(chunk_grid(e->n)) {}
+
+  double *basis(int j) const { return E->vec(j); }
+  double *product() const { return E->vec(m + 1); }
+  const int *skip() const { return &st->skip; }
+
+  const EStatus &look(bool tables) {
+    SPL_HIP(hipMemcpyAsync(E->pinned, st, sizeof(EStatus), hipMemcpyDeviceToHost, s));
+    if (tables)
+      SPL_HIP(hipMemcpyAsync(E->host_tables(), T.alpha, (size_t)3 * m * sizeof(double), hipMemcpyDeviceToHost, s));
+    SPL_HIP(hipStreamSynchronize(s));
+    return *E->pinned;
+  }
+  int launch_status(const char *where) {
+    const hipError_t e = hipGetLastError();
+    if (e == hipSuccess) return SPL_OK;
+    set_last_error(where, e);
+    (void)hipStreamSynchronize(s);
+    return SPL_ERROR_device;
+  }
+
+  void start(const double *v0) {
+    hipLaunchKernelGGL((norm_kernel<VW>), dim3(chunked), dim3(kLanes), 0, s, n, v0, scratch);
+    const Partials P = middle_levels(nullptr, n, 1, scratch, s);
+    hipLaunchKernelGGL(start_kernel, dim3(1), dim3(kLanes), 0, s, st, P.p, P.count);
+    hipLaunchKernelGGL(divide_kernel, dim3(flat), dim3(kLanes), 0, s, skip(), n * VW, (const double *)&st->scale, v0,
+                       basis(0));
+    launches += P.middle + 3;
+  }
+
+  // w = OP v_j to slot j + 1; *failed: the inner solve did not converge
+  int apply(int j, bool *failed) {
+    if (!E->K) {
+      ++launches;
+      return launch_spmv(E->A, basis(j), basis(j + 1), 0, s);
+    }
+    int64_t result[4] = {0, 0, 0, 0};
+    const int e = krylov_solve(E->K, basis(j), basis(j + 1), 0, E->rtol, E->atol, E->max_iter, 0, result, nullptr, s);
+    if (e != SPL_OK) return e;
+    inner += result[0];
+    *failed = result[1] != 0;
+    return SPL_OK;
+  }
+
+  void orthogonalise(int j) {
+    double *w = basis(j + 1);
+    launches += dots_launch<VW>(skip(), n, j + 1, basis(0), n, w, T.c1, scratch, s);
+    hipLaunchKernelGGL((update_kernel<VW, false>), dim3(chunked), dim3(kLanes), 0, s, skip(), n, j + 1,
+                       (const double *)basis(0), n, (const double *)T.c1, w, scratch);
+    launches += dots_launch<VW>(skip(), n, j + 1, basis(0), n, w, T.c2, scratch, s);
+    hipLaunchKernelGGL((update_kernel<VW, true>), dim3(chunked), dim3(kLanes), 0, s, skip(), n, j + 1,
+                       (const double *)basis(0), n, (const double *)T.c2, w, scratch);
+    const Partials P = middle_levels(skip(), n, 1, scratch, s);
+    hipLaunchKernelGGL((step_kernel<VW>), dim3(1), dim3(kLanes), 0, s, st, j, P.p, P.count, T);
+    hipLaunchKernelGGL(divide_kernel, dim3(flat), dim3(kLanes), 0, s, skip(), n * VW, (const double *)&st->scale,
+                       (const double *)w, w);
+    launches += P.middle + 4;
+  }
+
+  // Y[:, order[0 .. cols)] of the m' x m' host matrix to the device table, leading dimension m'
+  void upload(const std::vector<double> &Y, const std::vector<int> &order, int mp, int cols) {
+    double *h = E->host_y();
+    for (int c = 0; c < cols; ++c)
+      for (int r = 0; r < mp; ++r) h[(size_t)c * mp + r] = Y[(size_t)r * mp + order[c]];
+    SPL_HIP(hipMemcpyAsync(T.Y, h, (size_t)cols * mp * sizeof(double), hipMemcpyHostToDevice, s));
+  }
+
+  // X = V Y[:, :pairs], the values and the residual norms; synchronises
+  int finish(const std::vector<double> &Y, const std::vector<int> &order, const std::vector<double> &theta, int mp,
+             int pairs, double *values, double *d_vectors, int64_t ldx, double *residuals) {
+    if (pairs == 0) return SPL_OK;
+    upload(Y, order, mp, pairs);
+    rotate_launch(n, VW, mp, pairs, basis(0), n, T.Y, mp, d_vectors, ldx, s);
+    ++launches;
+    for (int i = 0; i < pairs; ++i) {
+      values[i] = E->K ? E->sigma + 1.0 / theta[i] : theta[i];
+      const double *x = d_vectors + (size_t)i * (size_t)ldx * VW;
+      const int e = launch_spmv(E->A, x, product(), 0, s);
+      if (e != SPL_OK) return e;
+      hipLaunchKernelGGL((residual_kernel<VW>), dim3(chunked), dim3(kLanes), 0, s, n, (const double *)product(), x,
+                         values[i], scratch);
+      const Partials P = middle_levels(nullptr, n, 1, scratch, s);
+      hipLaunchKernelGGL(fold_kernel, dim3(1, 1), dim3(kLanes), 0, s, (const int *)nullptr, (int64_t)P.count, P.p, P.stride,
+                         T.res + i, (int64_t)1);
+      launches += P.middle + 3;
+    }
+    const int e = launch_status("eigsh finish");
+    if (e != SPL_OK) return e;
+    look(true);
+    const double *res = E->host_tables() + 2 * m;
+    for (int i = 0; i < pairs; ++i) residuals[i] = sqrt(res[i]);
+    return SPL_OK;
+  }
+
+  int solve(int nev, int which, double tol, double atol, int64_t max_restarts, const double *d_v0, double *values,
+            double *d_vectors, int64_t ldx, double *residuals, int64_t result[6], double *history) {
+    int e;
+    SPL_HIP(hipMemsetAsync(st, 0, sizeof(EStatus), s));
+    start(d_v0);
+    if ((e = launch_status("eigsh start")) != SPL_OK) return e;
+    EStatus now = look(false);
+    if (history) history[0] = now.eta0;
+    int64_t cycles = 0, ops = 0, sweeps_most = 0;
+    auto done = [&](int reason, int pairs) {
+      result[0] = reason;
+      result[1] = cycles;
+      result[2] = ops;
+      result[3] = pairs;
+      result[4] = inner;
+      result[5] = sweeps_most;
+      return SPL_OK;
+    };
+    if (now.pending) return done(now.pending - 1, 0);
+    int k = 0;
+    std::vector<double> theta, kept;  // theta_i and s_i of the restart, i < k
+    std::vector<double> Tm, Y, est;
+    std::vector<int> order;
+    for (;;) {
+      bool failed = false;
+      for (int j = k; j < m && !failed; ++j) {
+        if ((e = apply(j, &failed)) != SPL_OK) return e;
+        if (failed) break;
+        orthogonalise(j);
+        if (E->K && look(false).skip) break;  // the product is a solve of its own: it does not read `skip`
+      }
+      if ((e = launch_status("eigsh cycle")) != SPL_OK) return e;
+      now = look(true);
+      ops = now.ops;
+      if (failed) return done(4, 0);
+      if (now.pending) return done(now.pending - 1, 0);
+      const int mp = now.mprime;
+      const bool invariant = now.skip != 0;  // eta == 0 closed the cycle
+      const double *alpha = E->host_tables(), *beta = alpha + m;
+      Tm.assign((size_t)mp * mp, 0.0);
+      Y.assign((size_t)mp * mp, 0.0);
+      for (int i = 0; i < k; ++i) {
+        Tm[(size_t)i * mp + i] = theta[i];
+        Tm[(size_t)i * mp + k] = Tm[(size_t)k * mp + i] = kept[i];
+      }
+      for (int j = k; j < mp; ++j) {
+        Tm[(size_t)j * mp + j] = alpha[j];
+        if (j < mp - 1) Tm[(size_t)j * mp + j + 1] = Tm[(size_t)(j + 1) * mp + j] = beta[j];
+      }
+      const double last = beta[mp - 1];
+      const int sweeps = jacobi(mp, Tm, Y);
+      bool finite = sweeps >= 0;
+      for (int i = 0; finite && i < mp; ++i) {
+        finite = std::isfinite(Tm[(size_t)i * mp + i]);
+        for (int r = 0; finite && r < mp; ++r) finite = std::isfinite(Y[(size_t)r * mp + i]);
+      }
+      if (!finite) return done(3, 0);
+      ++cycles;
+      if (sweeps > sweeps_most) sweeps_most = sweeps;
+      order.resize(mp);
+      for (int i = 0; i < mp; ++i) order[i] = i;
+      auto value = [&](int i) { return Tm[(size_t)i * mp + i]; };
+      std::stable_sort(order.begin(), order.end(), [&](int a, int b) {
+        if (which == 0) return value(a) > value(b);
+        if (which == 1) return value(a) < value(b);
+        return fabs(value(a)) > fabs(value(b));
+      });
+      const int pairs = nev < mp ? nev : mp;
+      est.assign(mp, 0.0);
+      double worst = 0.0;
+      bool converged = true;
+      for (int i = 0; i < mp; ++i) {
+        est[i] = fabs(last * Y[(size_t)(mp - 1) * mp + order[i]]);
+        if (i >= pairs) continue;
+        if (est[i] > worst) worst = est[i];
+        const double bound = tol * fabs(value(order[i]));
+        converged = converged && est[i] <= (bound > atol ? bound : atol);
+      }
+      if (history) history[cycles] = worst;
+      int reason = -1;
+      if (invariant) reason = mp >= nev ? 0 : 2;
+      else if (converged) reason = 0;
+      else if (cycles >= max_restarts) reason = 1;
+      if (reason >= 0) {
+        std::vector<double> sorted(pairs);
+        for (int i = 0; i < pairs; ++i) sorted[i] = value(order[i]);
+        if ((e = finish(Y, order, sorted, mp, pairs, values, d_vectors, ldx, residuals)) != SPL_OK) return e;
+        return done(reason, pairs);
+      }
+      // ---- the restart: k Ritz vectors and v_(m'), the arrow head theta_i, s_i
+      const int half = nev + (mp - nev) / 2;
+      k = half < mp - 1 ? half : mp - 1;
+      upload(Y, order, mp, k);
+      rotate_launch(n, VW, mp, k, basis(0), n, T.Y, mp, basis(0), n, s);
+      SPL_HIP(hipMemcpyAsync(basis(k), basis(mp), (size_t)n * VW * sizeof(double), hipMemcpyDeviceToDevice, s));
+      launches += 2;
+      theta.resize(k);
+      kept.resize(k);
+      for (int i = 0; i < k; ++i) {
+        theta[i] = value(order[i]);
+        kept[i] = last * Y[(size_t)(mp - 1) * mp + order[i]];
+      }
+    }
+  }
+};
+
+}  // namespace
+
+// arguments checked by the caller; n > 0.  Enqueues on s and synchronises it: the outcome is read back.
+int eigsh_solve(Eigsh *E, int nev, int which, double tol, double atol, int64_t max_restarts, const double *d_v0,
+                double *values, double *d_vectors, int64_t ldx, double *residuals, int64_t result[6], double *history,
+                hipStream_t s) {
+  std::lock_guard<std::mutex> hold(E->lock);
+  int e;
+  int64_t launches = 0;
+  if (E->vw == 1) {
+    ERun<1> run(E, s);
+    e = run.solve(nev, which, tol, atol, max_restarts, d_v0, values, d_vectors, ldx, residuals, result, history);
+    launches = run.launches;
+  } else {
+    ERun<2> run(E, s);
+    e = run.solve(nev, which, tol, atol, max_restarts, d_v0, values, d_vectors, ldx, residuals, result, history);
+    launches = run.launches;
+  }
+  if (e != SPL_OK) {
+    (void)hipStreamSynchronize(s);
+    return e;
+  }
+  E->last_cycles = result[1];
+  E->last_launches = launches;
+  ++E->solves;
+  return SPL_OK;
+}
+
+void eigsh_info(Eigsh *E, int64_t info[8]) {
+  std::lock_guard<std::mutex> hold(E->lock);
+  info[0] = E->n;
+  info[1] = E->ncv;
+  info[2] = (E->vw == 2 ? 1 : 0) | (E->K ? 2 : 0);
+  info[3] = (int64_t)E->bytes;
+  info[4] = E->solves;
+  info[5] = E->last_cycles;
+  info[6] = E->last_launches;
+  info[7] = 0;
+}
+
+int eigsh_device(const Eigsh *E) { return E->device; }
+int64_t eigsh_rows(const Eigsh *E) { return E->n; }
+int eigsh_width(const Eigsh *E) { return E->vw; }
+int eigsh_ncv(const Eigsh *E) { return E->ncv; }
+
+void eigsh_delete(Eigsh *E) {
+  E->magic = 0;
+  if (E->pinned) (void)hipHostFree(E->pinned);
+  delete E;
+}
+
+}  // namespace spl

@@ -13,17 +13,13 @@
 // The host cannot know how long a cycle is: it issues all `restart` steps and the close, and every kernel of a step
 // reads `skip` (cycle closed, or done) first and returns without touching a vector when it is set.  No kernel waits for
 // another workgroup, there is no floating-point atomic and no captured graph.
-#include "krylov_fold.hpp"
+#include "krylov_basis.hpp"
 
 namespace spl {
 
 constexpr uint32_t kGmresMagic = 0x53504C47u;  // "SPLG"
 
 namespace {
-
-// Columns of the basis per lane_tree round of dots_kernel.  Tuned: SPL_GMRES_DOTS_BATCH = 2, 4 or 8
-// chooses another width for a measurement; the bits do not depend on it.
-constexpr int kDotsBatch = 4;
 
 // The status block, in device memory (and its copy in pinned host memory)
 struct GStatus {
@@ -61,131 +57,10 @@ inline Tables tables_at(double *base, int m) {
   return T;
 }
 
-__device__ inline Val<1> scaled(double s, Val<1> a) { return Val<1>{s * a.re}; }
-__device__ inline Val<2> scaled(double s, Val<2> a) { return Val<2>{s * a.re, s * a.im}; }
-__device__ inline Val<1> over(Val<1> a, double d) { return Val<1>{a.re / d}; }
-__device__ inline Val<2> over(Val<2> a, double d) { return Val<2>{a.re / d, a.im / d}; }
 __device__ inline Val<1> negated(Val<1> a) { return Val<1>{-a.re}; }
 __device__ inline Val<2> negated(Val<2> a) { return Val<2>{-a.re, -a.im}; }
-__device__ inline double imag_of(Val<1>) { return 0.0; }
-__device__ inline double imag_of(Val<2> a) { return a.im; }
 
-// ---- k inner products in one pass ------------------------------------------------------------------------------------
-// part[(col * VW + p) * stride + c] = plane p of chunk c of <V[:, col], w>.  A workgroup takes whole chunks; it loads its
-// 16 entries per lane of w once and walks the columns B at a time: B * VW lane sums, one lane_tree round for them.  A
-// column's sums are dot_kernel's: from +0.0, the entries t, t + 256, ... in ascending order, the same product.
-template <int VW, int B>
-__global__ __launch_bounds__(kLanes) void dots_kernel(const int *stop, int64_t n, int k, const double *__restrict__ V,
-                                                      int64_t ldv, const double *__restrict__ w, double *part,
-                                                      int64_t stride) {
-  if (stop && *stop) return;
-  __shared__ double lds[B * VW * kLanes];
-  const int t = threadIdx.x;
-  const int64_t nchunks = (n + kChunk - 1) / kChunk;
-  for (int64_t c = blockIdx.x; c < nchunks; c += gridDim.x) {
-    const int64_t base = c * kChunk + t;
-    const bool full = n - c * kChunk >= kChunk;
-    Val<VW> wv[kSteps];
-#pragma unroll
-    for (int s = 0; s < kSteps; ++s) {
-      const int64_t i = base + (int64_t)s * kLanes;
-      wv[s] = (full || i < n) ? load_val<VW>(w, i) : Val<VW>();
-    }
-    for (int col0 = 0; col0 < k; col0 += B) {
-      double acc[B * VW];
-#pragma unroll
-      for (int v = 0; v < B * VW; ++v) acc[v] = 0.0;
-#pragma unroll
-      for (int b = 0; b < B; ++b) {
-        if (col0 + b < k) {
-          const double *col = V + (size_t)(col0 + b) * (size_t)ldv * VW;
-#pragma unroll
-          for (int s = 0; s < kSteps; ++s) {
-            const int64_t i = base + (int64_t)s * kLanes;
-            if (full || i < n) accumulate(acc + b * VW, mul(conj_of(load_val<VW>(col, i)), wv[s]));
-          }
-        }
-      }
-      lane_tree<B * VW>(acc, lds);
-      if (t == 0) {
-#pragma unroll
-        for (int b = 0; b < B; ++b)
-          if (col0 + b < k)
-#pragma unroll
-            for (int p = 0; p < VW; ++p) part[((int64_t)(col0 + b) * VW + p) * stride + c] = acc[b * VW + p];
-      }
-    }
-  }
-}
-
-int dots_batch() {
-  const char *e = getenv("SPL_GMRES_DOTS_BATCH");
-  const long v = e ? atol(e) : 0;
-  return v == 2 || v == 4 || v == 8 ? (int)v : kDotsBatch;
-}
-
-// the first level, the middle levels and the last one of k inner products: `out` receives k entries.  n > 0
-template <int VW>
-int dots_launch(const int *stop, int64_t n, int k, const double *V, int64_t ldv, const double *w, double *out,
-                double *scratch, hipStream_t s) {
-  const int64_t c1 = chunks_of(n);
-  const dim3 grid(chunk_grid(n)), block(kLanes);
-  switch (dots_batch()) {
-    case 2: hipLaunchKernelGGL((dots_kernel<VW, 2>), grid, block, 0, s, stop, n, k, V, ldv, w, scratch, c1); break;
-    case 8: hipLaunchKernelGGL((dots_kernel<VW, 8>), grid, block, 0, s, stop, n, k, V, ldv, w, scratch, c1); break;
-    default: hipLaunchKernelGGL((dots_kernel<VW, 4>), grid, block, 0, s, stop, n, k, V, ldv, w, scratch, c1); break;
-  }
-  const Partials P = middle_levels(stop, n, k * VW, scratch, s);
-  hipLaunchKernelGGL(fold_kernel, dim3(1, k * VW), block, 0, s, stop, (int64_t)P.count, P.p, P.stride, out, (int64_t)1);
-  return P.middle + 2;
-}
-
-// ---- the vector kernels of a step ---------------------------------------------------------------------------------------
-// w = ((w - c_0 v_0) - c_1 v_1) - ... over ncols columns, a product and a difference per term; NORM: the partials of
-// Re<w,w> of the result to part[chunk]
-template <int VW, bool NORM>
-__global__ __launch_bounds__(kLanes) void update_kernel(const GStatus *st, int64_t n, int ncols,
-                                                        const double *__restrict__ V, int64_t ldv,
-                                                        const double *__restrict__ coef, double *__restrict__ w,
-                                                        double *part) {
-  if (st->skip) return;
-  __shared__ double lds[kLanes];
-  const int t = threadIdx.x;
-  const int64_t nchunks = (n + kChunk - 1) / kChunk;
-  for (int64_t c = blockIdx.x; c < nchunks; c += gridDim.x) {
-    const int64_t base = c * kChunk + t;
-    const bool full = n - c * kChunk >= kChunk;
-    Val<VW> wv[kSteps];
-#pragma unroll
-    for (int s = 0; s < kSteps; ++s) {
-      const int64_t i = base + (int64_t)s * kLanes;
-      wv[s] = (full || i < n) ? load_val<VW>(w, i) : Val<VW>();
-    }
-    for (int col = 0; col < ncols; ++col) {
-      const Val<VW> cf = load_val<VW>(coef, col);
-      const double *v = V + (size_t)col * (size_t)ldv * VW;
-#pragma unroll
-      for (int s = 0; s < kSteps; ++s) {
-        const int64_t i = base + (int64_t)s * kLanes;
-        if (full || i < n) wv[s] = sub(wv[s], mul(cf, load_val<VW>(v, i)));
-      }
-    }
-    double acc[1] = {0.0};
-#pragma unroll
-    for (int s = 0; s < kSteps; ++s) {
-      const int64_t i = base + (int64_t)s * kLanes;
-      if (full || i < n) {
-        store_val(w, i, wv[s]);
-        if (NORM) acc[0] = acc[0] + mul(conj_of(wv[s]), wv[s]).re;
-      }
-    }
-    if (NORM) {
-      lane_tree<1>(acc, lds);
-      if (t == 0) part[c] = acc[0];
-    }
-  }
-}
-
+// ---- the vector kernels of a step (dots_kernel and update_kernel: krylov_basis.hpp) ------------------------------------
 // r = b - q (q == nullptr: r = b and x = 0); partials of <r,r> and, in the first cycle, of <b,b>
 template <int VW, bool FIRST>
 __global__ __launch_bounds__(kLanes) void residual_kernel(const GStatus *st, int64_t n, const double *__restrict__ b,
@@ -555,10 +430,10 @@ struct GRun {
     double *w = basis(j + 1);
     if ((e = spmv(z, w)) != SPL_OK) return e;
     launches += dots_launch<VW>(skip(), n, j + 1, basis(0), n, w, T.c1, scratch, s);
-    hipLaunchKernelGGL((update_kernel<VW, false>), dim3(chunked), dim3(kLanes), 0, s, (const GStatus *)st, n, j + 1,
+    hipLaunchKernelGGL((update_kernel<VW, false>), dim3(chunked), dim3(kLanes), 0, s, skip(), n, j + 1,
                        (const double *)basis(0), n, (const double *)T.c1, w, scratch);
     launches += dots_launch<VW>(skip(), n, j + 1, basis(0), n, w, T.c2, scratch, s);
-    hipLaunchKernelGGL((update_kernel<VW, true>), dim3(chunked), dim3(kLanes), 0, s, (const GStatus *)st, n, j + 1,
+    hipLaunchKernelGGL((update_kernel<VW, true>), dim3(chunked), dim3(kLanes), 0, s, skip(), n, j + 1,
                        (const double *)basis(0), n, (const double *)T.c2, w, scratch);
     const Partials P = middle_levels(skip(), n, 1, scratch, s);
     hipLaunchKernelGGL((step_kernel<VW>), dim3(1), dim3(kLanes), 0, s, st, j, m, P.p, P.count, T, max_iter, hist);

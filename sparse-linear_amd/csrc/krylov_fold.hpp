@@ -1,8 +1,9 @@
 // krylov_fold.hpp — the fixed-order fold and the value helpers shared by the Krylov solvers on device handles
-// (krylov.hip: CG, BiCGSTAB and spl_vector_dot_dev; gmres.hip: restarted GMRES and spl_vector_dots_dev).  The
+// (krylov.hip: CG, BiCGSTAB and spl_vector_dot_dev; gmres.hip: restarted GMRES and spl_vector_dots_dev; eigsh.hip:
+// thick-restart Lanczos, the last two through krylov_basis.hpp).  The
 // arithmetic contract is the one at the head of krylov.hip: chunks of 4096 entries, 256 lanes that add their 16 entries
 // in ascending order from +0.0, the halving tree, and the partials folded again by the same fold; the order is a function
-// of the length alone.  Device code and the host code that launches the levels; included by those two files only.
+// of the length alone.  Device code and the host code that launches the levels; included by those files only.
 #pragma once
 
 #include <math.h>

@@ -858,6 +858,20 @@ class DeviceMatrix(object):
         unsymmetric and indefinite systems, with the preconditioner M as KrylovSolver takes it"""
         return GMRESSolver(self, restart, M)
 
+    def eigsh(self, nev, which="LA", ncv=None, sigma=None, M=None, tol=1e-10, atol=0.0, max_restarts=1000, v0=None,
+              inner_rtol=1e-12, inner_atol=0.0, inner_maxiter=None):
+        """(values, vectors, result dict): nev eigenpairs of this whole square Hermitian handle by thick-restart Lanczos
+        (spl_eigsh_*).  which: 'LA', 'SA' or 'LM' of the operator's values; sigma: work on (A - sigma I)^-1 by CG with the
+        preconditioner M, so that 'LM' finds the eigenvalues nearest sigma; ncv: the basis, default
+        min(n, max(2 nev + 1, 20)) capped at 128; v0: the start, default numpy.random.default_rng(0).standard_normal"""
+        n = self.info()["nrows_global"]
+        E = EigenSolver(self, default_ncv(n, nev) if ncv is None else ncv, sigma, M, inner_rtol, inner_atol,
+                        inner_maxiter)
+        try:
+            return E.solve(nev, which, tol, atol, max_restarts, v0)
+        finally:
+            E.free()
+
     def coloring(self, seed=0):
         """the multicolour ordering of this whole square handle (spl_matrix_color): a Coloring with colors, perm and
         offsets; ``coloring().krylov(method, M)`` solves with the preconditioner built in that ordering"""
@@ -1482,6 +1496,188 @@ def gmres(mat, b, M=None, x0=None, restart=30, rtol=1e-8, atol=0.0, maxiter=None
         return G.solve(b, x0, rtol, atol, maxiter)
     finally:
         G.free()
+
+
+def vector_rotate_dev(n, m, k, V_ptr, ldv, Y_ptr, ldy, out_ptr=None, ldo=0, is_complex=False, stream=0):
+    """V[:, :k] <- V Y in place (out_ptr None), or out = V Y (spl_vector_rotate_dev): V has m columns of n entries, ldv
+    entries apart; Y is a REAL m x k device matrix, column major, ldy >= m; 1 <= k <= m <= 128.  Column i is
+    Y[0][i] v_0 + Y[1][i] v_1 + ... summed in ascending order.  Device pointers (ints); enqueues on `stream`, no sync"""
+    check("spl_vector_rotate_dev",
+          lib().spl_vector_rotate_dev(int(n), 2 if is_complex else 1, int(m), int(k), C.c_void_p(V_ptr), int(ldv),
+                                      C.c_void_p(Y_ptr), int(ldy), C.c_void_p(out_ptr) if out_ptr else None, int(ldo),
+                                      C.c_void_p(stream)))
+
+
+class EigenSolver(object):
+    """Owner of a ``void *E`` from ``spl_eigsh_create``: thick-restart Lanczos with full reorthogonalisation on a whole
+    square Hermitian device handle (csrc/eigsh.hip), real or complex, with a basis of ``ncv`` columns.  Directly on A it
+    finds the ends of the spectrum; with ``sigma`` it works on ``(A - sigma I)^-1``, applied by a CG ``KrylovSolver``
+    built here on ``A.lin(1, I, -sigma)`` with the preconditioner ``M`` (as KrylovSolver takes it), and ``which="LM"``
+    then finds the eigenvalues nearest sigma.  ``which`` orders the OPERATOR's values.  Values, vectors, residuals,
+    history and counts are those of the sequence in include/sparse_linear_hip.h bit for bit.  A single-vector Lanczos
+    finds one copy of a multiple eigenvalue."""
+    WHICH = {"LA": _ffi.SPL_EIGSH_largest_algebraic, "SA": _ffi.SPL_EIGSH_smallest_algebraic,
+             "LM": _ffi.SPL_EIGSH_largest_magnitude}
+    REASONS = ("converged", "max_restarts", "invariant_subspace", "non_finite", "inner_solve_failed")
+    INFO_KEYS = ("n", "ncv", "flags", "device_bytes", "solves", "cycles", "launches", "reserved")
+    RESULT_KEYS = ("reason", "cycles", "applications", "pairs", "inner_iterations", "jacobi_sweeps")
+    DEFAULT_INNER_MAXITER = 20000
+
+    def __init__(self, A, ncv=20, sigma=None, M=None, inner_rtol=1e-12, inner_atol=0.0, inner_maxiter=None):
+        ncv = int(ncv)
+        if not 2 <= ncv <= 128:
+            raise ValueError("EigenSolver: ncv %r; 2 ... 128 is needed" % (ncv,))
+        self._e = C.c_void_p()
+        self._finalizer = weakref.finalize(self, EigenSolver._free, self._e)
+        self.A, self.ncv, self.sigma = A, ncv, None
+        self.shifted = self.inner = None
+        check("spl_eigsh_create", lib().spl_eigsh_create(A.handle, ncv, C.byref(self._e)))
+        if sigma is not None:
+            self.set_inverse(sigma, M, inner_rtol, inner_atol, inner_maxiter)
+
+    @staticmethod
+    def _free(e):
+        try:
+            lib().spl_eigsh_free(C.byref(e))
+        except Exception:  # interpreter shutdown
+            pass
+
+    def free(self):
+        self._finalizer()
+        self._drop_inner()
+
+    def _drop_inner(self):
+        if self.inner is not None:
+            self.inner.free()
+        self.shifted = self.inner = None
+
+    @property
+    def handle(self):
+        if not self._e.value:
+            raise _ffi.SparseLinearError("EigenSolver", _ffi.SPL_ERROR_invalid_handle)
+        return self._e
+
+    def set_inverse(self, sigma, M=None, inner_rtol=1e-12, inner_atol=0.0, inner_maxiter=None):
+        """the operator becomes (A - sigma I)^-1 by CG on ``A.lin(1, I, -sigma)`` with the preconditioner M; sigma None:
+        back to A itself"""
+        if sigma is None:
+            check("spl_eigsh_set_inverse", lib().spl_eigsh_set_inverse(self.handle, None, 0.0, 0.0, 0.0, 0))
+            self._drop_inner()
+            self.sigma = None
+            return
+        n = self.info()["n"]
+        shifted = self.A.lin(1.0, DeviceMatrix.ident(n, complex=self.A.is_complex), -float(sigma))
+        inner = KrylovSolver(shifted, "cg", M)
+        if inner_maxiter is None:
+            inner_maxiter = min(10 * n, self.DEFAULT_INNER_MAXITER)
+        try:
+            check("spl_eigsh_set_inverse",
+                  lib().spl_eigsh_set_inverse(self.handle, inner.handle, float(sigma), float(inner_rtol),
+                                              float(inner_atol), int(inner_maxiter)))
+        except Exception:
+            inner.free()
+            raise
+        self._drop_inner()
+        self.shifted, self.inner, self.sigma = shifted, inner, float(sigma)
+
+    def info(self):
+        out = np.zeros(8, dtype=I64)
+        check("spl_eigsh_info", lib().spl_eigsh_info(self.handle, _ffi.p_i64(out)))
+        d = dict(zip(self.INFO_KEYS, (int(v) for v in out)))
+        d.update(complex=bool(d["flags"] & 1), inverse=bool(d["flags"] & 2))
+        return d
+
+    @classmethod
+    def _which(cls, which):
+        if which not in cls.WHICH:
+            raise ValueError("EigenSolver: which %r; 'LA', 'SA' or 'LM' is needed" % (which,))
+        return cls.WHICH[which]
+
+    @classmethod
+    def _result(cls, result, values, residuals, history):
+        out = dict(zip(cls.RESULT_KEYS, (int(v) for v in result)))
+        pairs = out["pairs"]
+        out.update(reason_name=cls.REASONS[out["reason"]], converged=out["reason"] == 0,
+                   residuals=residuals[:pairs].copy())
+        if history is not None:
+            out["history"] = history[:out["cycles"] + 1].copy()
+        return values[:pairs].copy(), out
+
+    def solve_dev(self, nev, v0_ptr, vectors_ptr, ldx, which="LA", tol=1e-10, atol=0.0, max_restarts=1000, history=True,
+                  stream=0):
+        """device pointers (ints) to v0 (n entries) and the vectors (nev columns, ldx entries apart).  Enqueues on
+        `stream` and returns (values, result dict) after the solve's last synchronisation; the dict has reason, cycles,
+        applications, pairs, inner_iterations, jacobi_sweeps, residuals and history"""
+        nev, max_restarts = int(nev), int(max_restarts)
+        values, residuals = np.zeros(max(nev, 1), dtype=F64), np.zeros(max(nev, 1), dtype=F64)
+        result = np.zeros(6, dtype=I64)
+        hist = np.zeros(max(max_restarts, 0) + 1, dtype=F64) if history else None
+        check("spl_eigsh_solve_dev",
+              lib().spl_eigsh_solve_dev(self.handle, nev, self._which(which), float(tol), float(atol), max_restarts,
+                                        C.c_void_p(v0_ptr), p_f64(values), C.c_void_p(vectors_ptr), int(ldx),
+                                        p_f64(residuals), _ffi.p_i64(result), p_f64(hist) if history else None,
+                                        C.c_void_p(stream)))
+        return self._result(result, values, residuals, hist)
+
+    def default_start(self):
+        """numpy.random.default_rng(0).standard_normal of n entries (complex: both parts)"""
+        inf = self.info()
+        rng = np.random.default_rng(0)
+        if inf["complex"]:
+            return (rng.standard_normal(inf["n"]) + 1j * rng.standard_normal(inf["n"])).astype(C128)
+        return rng.standard_normal(inf["n"])
+
+    def solve(self, nev, which="LA", tol=1e-10, atol=0.0, max_restarts=1000, v0=None):
+        """(values, vectors, result dict): vectors has one column per pair returned.  v0: None (default_start), a numpy
+        array, or a torch tensor on the device (the vectors are one then and the solve runs on torch's current
+        stream); float64 on a real object, complex128 on a complex one"""
+        where = "EigenSolver.solve"
+        inf = self.info()
+        n, cplx = inf["n"], inf["complex"]
+        nev, max_restarts = int(nev), int(max_restarts)
+        try:
+            import torch
+            is_tensor = isinstance(v0, torch.Tensor)
+        except ImportError:  # pragma: no cover
+            is_tensor = False
+        if is_tensor:
+            want = torch.complex128 if cplx else torch.float64
+            if not (v0.is_cuda and v0.dtype == want and tuple(v0.shape) == (n,)):
+                _oops(where, "the start must be a device tensor of %d %s entries" % (n, want))
+            with torch.cuda.device(v0.device):
+                start = v0.contiguous()
+                X = torch.zeros((max(nev, 1), max(n, 1)), dtype=want, device=v0.device)
+                values, res = self.solve_dev(nev, start.data_ptr(), X.data_ptr(), max(n, 1), which, tol, atol,
+                                             max_restarts, True, torch.cuda.current_stream().cuda_stream)
+            return values, X[:res["pairs"], :n].T, res
+        want = C128 if cplx else F64
+        start = self.default_start() if v0 is None else np.ascontiguousarray(v0)
+        if start.dtype != want or start.shape != (n,):
+            _oops(where, "a start of dtype %s and shape %s; %d %s entries are needed"
+                  % (start.dtype, start.shape, n, np.dtype(want)))
+        X = np.zeros((max(nev, 1), max(n, 1)), dtype=want)
+        values, residuals = np.zeros(max(nev, 1), dtype=F64), np.zeros(max(nev, 1), dtype=F64)
+        result = np.zeros(6, dtype=I64)
+        hist = np.zeros(max(max_restarts, 0) + 1, dtype=F64)
+        check("spl_eigsh_solve",
+              lib().spl_eigsh_solve(self.handle, nev, self._which(which), float(tol), float(atol), max_restarts,
+                                    p_f64(start.view(F64)), p_f64(values), p_f64(X.view(F64)), max(n, 1),
+                                    p_f64(residuals), _ffi.p_i64(result), p_f64(hist)))
+        values, res = self._result(result, values, residuals, hist)
+        return values, X[:res["pairs"], :n].T.copy(), res
+
+
+def default_ncv(n, nev):
+    """min(n, max(2 nev + 1, 20)), capped at 128"""
+    return min(int(n), max(2 * int(nev) + 1, 20), 128)
+
+
+def eigsh(mat, nev, which="LA", ncv=None, sigma=None, M=None, tol=1e-10, atol=0.0, max_restarts=1000, v0=None,
+          inner_rtol=1e-12, inner_atol=0.0, inner_maxiter=None):
+    """(values, vectors, result dict): nev eigenpairs of the Hermitian host Matrix `mat` by thick-restart Lanczos on the
+    device (DeviceMatrix.eigsh)"""
+    return mat.device_handle().eigsh(nev, which, ncv, sigma, M, tol, atol, max_restarts, v0, inner_rtol, inner_atol,
+                                     inner_maxiter)
 
 
 def _krylov(method, mat, b, M, x0, rtol, atol, maxiter):
