@@ -41,6 +41,142 @@ int current_device() {
   return dev;
 }
 
+bool whole(const Matrix *m) { return m->row0 == 0 && m->nrows_local == m->nrows_global; }
+
+// ---- what the entry points of the objects behind handles share -------------------------------------------------------
+inline int device_of(const Matrix *m) { return m->device; }
+template <typename T>
+int device_of(const T *object) { return head(object).device; }
+
+// spl_*_free: the object goes with its own device current, and the handle is cleared whatever it held
+template <typename T>
+void free_object(void **h, T *(*as)(void *), void (*destroy)(T *)) {
+  if (!h || !*h) return;
+  T *object = as(*h);
+  *h = nullptr;
+  if (!object) return;
+  int prev = -1;
+  const bool have_prev = hipGetDevice(&prev) == hipSuccess;
+  (void)hipSetDevice(device_of(object));  // may run on a finalizer thread with another current device
+  destroy(object);
+  if (have_prev) (void)hipSetDevice(prev);
+}
+
+// the tail of an entry point that makes an object from the handle A, on A's device: make(&object) returns the status
+template <typename T, typename Make>
+int create_object(const Matrix *A, void **out, Make &&make) {
+  return guarded([&]() -> int {
+    (void)current_device();
+    DeviceGuard g(A->device);
+    T *object = nullptr;
+    const int st = make(&object);
+    *out = object;
+    return st;
+  });
+}
+
+// spl_*_info
+template <typename T, typename P>
+int info_of(void *h, T *(*as)(void *), void (*info_fn)(P *, int64_t *), int64_t info[8]) {
+  T *object = as(h);
+  if (!object) return SPL_ERROR_invalid_handle;
+  if (!info) return SPL_ERROR_argument_missing;
+  info_fn(object, info);
+  return SPL_OK;
+}
+
+// a part serves an object of its size, value kind and device only
+inline bool same_shape(const ObjectHead &a, const ObjectHead &b) {
+  return a.n == b.n && a.vw == b.vw && a.device == b.device;
+}
+
+// The triangular parts and the diagonal of a preconditioner for the solver S: out[i] is the object behind T1 / T2, or
+// nullptr for NULL (the identity)
+int preconditioner_parts(const ObjectHead &S, void *T1, const double *d_mid, void *T2, TriSolver *out[2]) {
+  void *given[2] = {T1, T2};
+  for (int i = 0; i < 2; ++i) {
+    out[i] = nullptr;
+    if (!given[i]) continue;
+    out[i] = as_trisolver(given[i]);
+    if (!out[i]) return SPL_ERROR_invalid_handle;
+  }
+  if ((uintptr_t)d_mid % (uintptr_t)(8 * S.vw) != 0) return SPL_ERROR_argument_missing;
+  for (int i = 0; i < 2; ++i)
+    if (out[i] && !same_shape(head(out[i]), S)) return SPL_ERROR_dimension_mismatch;
+  return SPL_OK;
+}
+
+// M is borrowed and may serve several solvers; NULL takes the preconditioner away (*out = nullptr)
+int preconditioner_amg(const ObjectHead &S, void *M, Amg **out) {
+  *out = nullptr;
+  if (!M) return SPL_OK;
+  *out = as_amg(M);
+  if (!*out) return SPL_ERROR_invalid_handle;
+  return same_shape(head(*out), S) ? SPL_OK : SPL_ERROR_dimension_mismatch;
+}
+
+// what the solve calls of CG, BiCGSTAB and GMRES refuse before anything else is looked at; outputs: none of the
+// arrays the results go to is NULL
+int check_linear_solve(bool valid, bool outputs, double rtol, double atol, int64_t max_iter, int check_every,
+                       const double *history) {
+  if (!valid) return SPL_ERROR_invalid_handle;
+  if (!outputs) return SPL_ERROR_argument_missing;
+  if (max_iter < 0) return SPL_ERROR_n_nonpositive;
+  if (!(rtol >= 0.0) || !(atol >= 0.0) || check_every < 0) return SPL_ERROR_argument_missing;  // a NaN is refused too
+  if (history && max_iter >= ((int64_t)1 << 31)) return SPL_ERROR_index_overflow;
+  return SPL_OK;
+}
+// the result of a solve with n == 0
+void empty_linear_result(int nresult, int64_t *result, double *history) {
+  for (int i = 0; i < nresult; ++i) result[i] = 0;
+  if (history) history[0] = 0.0;
+}
+
+// the two device vectors of a solve or an application: given, apart, and aligned to whole entries (the kernels load
+// and store whole entries)
+int check_device_vectors(const ObjectHead &o, const double *d_b, const double *d_x) {
+  if (!d_b || !d_x || d_b == d_x) return SPL_ERROR_argument_missing;
+  const uintptr_t entry = (uintptr_t)(8 * o.vw);
+  if ((uintptr_t)d_b % entry != 0 || (uintptr_t)d_x % entry != 0) return SPL_ERROR_argument_missing;
+  return SPL_OK;
+}
+
+// The opening of spl_krylov_create, spl_gmres_create and spl_eigsh_create: A is a whole square handle, *out is
+// cleared, option_ok says that the method / restart / ncv was in range
+int square_whole_matrix(void *A, void **out, bool option_ok, Matrix **M) {
+  *M = as_matrix(A);
+  if (!*M) return SPL_ERROR_invalid_handle;
+  if (!out) return SPL_ERROR_argument_missing;
+  *out = nullptr;
+  if (!option_ok) return SPL_ERROR_argument_missing;
+  if ((*M)->nrows_global != (*M)->ncols) return SPL_ERROR_dimension_mismatch;
+  if (!whole(*M)) return SPL_ERROR_invalid_matrix;
+  return SPL_OK;
+}
+
+// The host-side entry points of the objects: a device block of `slots` vectors of `count` doubles on the object's
+// device; up0 goes up to slot 0 and up1 (when given) to slot 1; run(block, stream) on the default stream; then slot
+// `down_slot` comes down to `down` (nullptr: run enqueued its own copies) and the stream is synchronised
+template <typename Run>
+int with_host_vectors(int device, size_t count, size_t slots, const double *up0, const double *up1, size_t down_slot,
+                      double *down, Run &&run) {
+  return guarded([&]() -> int {
+    DeviceGuard g(device);
+    hipStream_t s = nullptr;
+    DBuf<double> d(slots * count);
+    SPL_HIP(hipMemcpyAsync(d.get(), up0, count * sizeof(double), hipMemcpyHostToDevice, s));
+    if (up1) SPL_HIP(hipMemcpyAsync(d.get() + count, up1, count * sizeof(double), hipMemcpyHostToDevice, s));
+    const int st = run(d.get(), s);
+    if (st != SPL_OK) {
+      (void)hipStreamSynchronize(s);
+      return st;
+    }
+    if (down) SPL_HIP(hipMemcpyAsync(down, d.get() + down_slot * count, count * sizeof(double), hipMemcpyDeviceToHost, s));
+    SPL_HIP(hipStreamSynchronize(s));
+    return SPL_OK;
+  });
+}
+
 template <typename T>
 void upload(DBuf<T> &dst, const T *src, size_t n, hipStream_t s) {
   dst.alloc(n);
@@ -611,10 +747,6 @@ int spl_matrix_hermitian(void *H, int *result) {
 }
 
 // ---- the structural constructors, handle to handle (csrc/assemble_handles.hip) ------------------------------------
-namespace {
-bool whole(const Matrix *m) { return m->row0 == 0 && m->nrows_local == m->nrows_global; }
-}  // namespace
-
 // C = A (x) B (`kronecker`, Sparse.hs:597-634).  A handle holds the ROW-major image, i.e. the CSC fields of the
 // transpose, and (A (x) B)^T = A^T (x) B^T: the reference's walk — for every entry of A's column, every entry of B's,
 // index ia * nrowsB + ib, value b * a — applied to the two row images writes the row image of A (x) B, so the handle
@@ -1066,18 +1198,7 @@ int spl_matrix_norm(void *H, int which, double *result) {
   });
 }
 
-void spl_matrix_free(void **H) {
-  if (!H || !*H) return;
-  Matrix *m = as_matrix(*H);
-  *H = nullptr;
-  if (!m) return;
-  int prev = -1;
-  const bool have_prev = hipGetDevice(&prev) == hipSuccess;
-  (void)hipSetDevice(m->device);  // may run on a finalizer thread with another current device
-  m->magic = 0;
-  delete m;
-  if (have_prev) (void)hipSetDevice(prev);
-}
+void spl_matrix_free(void **H) { free_object(H, as_matrix, delete_object<Matrix>); }
 
 int spl_matrix_info(void *H, int64_t info[8]) {
   Matrix *m = as_matrix(H);
@@ -1508,14 +1629,7 @@ int spl_trisolve_analyze(void *H, int uplo, int diag, void **T) {
     return SPL_ERROR_argument_missing;
   if (A->nrows_global != A->ncols) return SPL_ERROR_dimension_mismatch;
   if (!whole(A) || !A->rowptr.get()) return SPL_ERROR_invalid_matrix;
-  return guarded([&]() -> int {
-    (void)current_device();
-    DeviceGuard g(A->device);
-    TriSolver *S = nullptr;
-    const int st = trisolve_analyze(A, uplo, diag, &S);
-    *T = S;
-    return st;
-  });
+  return create_object<TriSolver>(A, T, [&](TriSolver **S) { return trisolve_analyze(A, uplo, diag, S); });
 }
 
 int spl_trisolve_solve_dev(void *T, int op, int k, const double *d_B, int64_t ldb, double *d_X, int64_t ldx,
@@ -1523,14 +1637,15 @@ int spl_trisolve_solve_dev(void *T, int op, int k, const double *d_B, int64_t ld
   TriSolver *S = as_trisolver(T);
   if (!S) return SPL_ERROR_invalid_handle;
   if (k < 0) return SPL_ERROR_n_nonpositive;
-  if (k == 0 || trisolve_rows(S) == 0) return SPL_OK;
+  const ObjectHead &o = head(S);
+  if (k == 0 || o.n == 0) return SPL_OK;
   if (op != SPL_OP_n && op != SPL_OP_t && op != SPL_OP_h) return SPL_ERROR_argument_missing;
   if (!d_B || !d_X) return SPL_ERROR_argument_missing;
-  const uintptr_t entry = (uintptr_t)(8 * trisolve_width(S));  // the kernels load and store whole entries
+  const uintptr_t entry = (uintptr_t)(8 * o.vw);  // the kernels load and store whole entries
   if ((uintptr_t)d_B % entry != 0 || (uintptr_t)d_X % entry != 0) return SPL_ERROR_argument_missing;
-  if (k > 1 && (ldb < trisolve_rows(S) || ldx < trisolve_rows(S))) return SPL_ERROR_dimension_mismatch;
+  if (k > 1 && (ldb < o.n || ldx < o.n)) return SPL_ERROR_dimension_mismatch;
   return guarded([&]() -> int {
-    DeviceGuard g(trisolve_device(S));
+    DeviceGuard g(o.device);
     return trisolve_solve(S, op, k, d_B, ldb, d_X, ldx, as_stream(stream));
   });
 }
@@ -1540,46 +1655,19 @@ int spl_trisolve_solve(void *T, int op, int k, const double *B, double *X) {
   TriSolver *S = as_trisolver(T);
   if (!S) return SPL_ERROR_invalid_handle;
   if (k < 0) return SPL_ERROR_n_nonpositive;
-  if (k == 0 || trisolve_rows(S) == 0) return SPL_OK;
+  const ObjectHead &o = head(S);
+  if (k == 0 || o.n == 0) return SPL_OK;
   if (op != SPL_OP_n && op != SPL_OP_t && op != SPL_OP_h) return SPL_ERROR_argument_missing;
   if (!B || !X) return SPL_ERROR_argument_missing;
-  return guarded([&]() -> int {
-    DeviceGuard g(trisolve_device(S));
-    hipStream_t s = nullptr;
-    const int64_t n = trisolve_rows(S);
-    const size_t count = (size_t)n * (size_t)k * (size_t)trisolve_width(S);
-    DBuf<double> d(count);
-    SPL_HIP(hipMemcpyAsync(d.get(), B, count * sizeof(double), hipMemcpyHostToDevice, s));
-    const int st = trisolve_solve(S, op, k, d.get(), n, d.get(), n, s);
-    if (st != SPL_OK) {
-      (void)hipStreamSynchronize(s);
-      return st;
-    }
-    SPL_HIP(hipMemcpyAsync(X, d.get(), count * sizeof(double), hipMemcpyDeviceToHost, s));
-    SPL_HIP(hipStreamSynchronize(s));
-    return SPL_OK;
+  const size_t count = (size_t)o.n * (size_t)k * (size_t)o.vw;
+  return with_host_vectors(o.device, count, 1, B, nullptr, 0, X, [&](double *d, hipStream_t s) {
+    return trisolve_solve(S, op, k, d, o.n, d, o.n, s);
   });
 }
 
-int spl_trisolve_info(void *T, int64_t info[8]) {
-  TriSolver *S = as_trisolver(T);
-  if (!S) return SPL_ERROR_invalid_handle;
-  if (!info) return SPL_ERROR_argument_missing;
-  trisolve_info(S, info);
-  return SPL_OK;
-}
+int spl_trisolve_info(void *T, int64_t info[8]) { return info_of(T, as_trisolver, trisolve_info, info); }
 
-void spl_trisolve_free(void **T) {
-  if (!T || !*T) return;
-  TriSolver *S = as_trisolver(*T);
-  *T = nullptr;
-  if (!S) return;
-  int prev = -1;
-  const bool have_prev = hipGetDevice(&prev) == hipSuccess;
-  (void)hipSetDevice(trisolve_device(S));  // may run on a finalizer thread with another current device
-  trisolve_delete(S);
-  if (have_prev) (void)hipSetDevice(prev);
-}
+void spl_trisolve_free(void **T) { free_object(T, as_trisolver, trisolve_delete); }
 
 // ---- ILU(0) on handles (csrc/ilu0.hip) ---------------------------------------------------------------------------------
 // The plan keeps its own device copy of the pattern and the level tables, no values: H is borrowed for the call.
@@ -1590,14 +1678,7 @@ int spl_ilu0_analyze(void *H, void **P) {
   *P = nullptr;
   if (A->nrows_global != A->ncols) return SPL_ERROR_dimension_mismatch;
   if (!whole(A) || !A->rowptr.get()) return SPL_ERROR_invalid_matrix;
-  return guarded([&]() -> int {
-    (void)current_device();
-    DeviceGuard g(A->device);
-    IluPlan *S = nullptr;
-    const int st = ilu0_analyze(A, &S);
-    *P = S;
-    return st;
-  });
+  return create_object<IluPlan>(A, P, [&](IluPlan **S) { return ilu0_analyze(A, S); });
 }
 
 // F: a new ordinary handle with H's pattern and the L\U values; H any whole handle with the analysed pattern
@@ -1607,7 +1688,7 @@ int spl_ilu0_factor(void *P, void *H, void **F) {
   if (!S || !A) return SPL_ERROR_invalid_handle;
   if (!F) return SPL_ERROR_argument_missing;
   *F = nullptr;
-  if (!whole(A) || !A->rowptr.get() || A->device != ilu0_device(S)) return SPL_ERROR_invalid_matrix;
+  if (!whole(A) || !A->rowptr.get() || A->device != head(S).device) return SPL_ERROR_invalid_matrix;
   return guarded([&]() -> int {
     DeviceGuard g(A->device);
     hipStream_t s = nullptr;
@@ -1619,25 +1700,9 @@ int spl_ilu0_factor(void *P, void *H, void **F) {
   });
 }
 
-int spl_ilu0_info(void *P, int64_t info[8]) {
-  IluPlan *S = as_ilu_plan(P);
-  if (!S) return SPL_ERROR_invalid_handle;
-  if (!info) return SPL_ERROR_argument_missing;
-  ilu0_info(S, info);
-  return SPL_OK;
-}
+int spl_ilu0_info(void *P, int64_t info[8]) { return info_of(P, as_ilu_plan, ilu0_info, info); }
 
-void spl_ilu0_free(void **P) {
-  if (!P || !*P) return;
-  IluPlan *S = as_ilu_plan(*P);
-  *P = nullptr;
-  if (!S) return;
-  int prev = -1;
-  const bool have_prev = hipGetDevice(&prev) == hipSuccess;
-  (void)hipSetDevice(ilu0_device(S));  // may run on a finalizer thread with another current device
-  ilu0_delete(S);
-  if (have_prev) (void)hipSetDevice(prev);
-}
+void spl_ilu0_free(void **P) { free_object(P, as_ilu_plan, ilu0_delete); }
 
 // analyze + factor + free: the one-shot form
 int spl_matrix_ilu0(void *H, void **F) {
@@ -1667,73 +1732,35 @@ int spl_vector_dot_dev(int64_t n, int value_width, const double *d_a, const doub
 
 // A is borrowed: the object keeps the pointer and its own work vectors
 int spl_krylov_create(void *A, int method, void **K) {
-  Matrix *M = as_matrix(A);
-  if (!M) return SPL_ERROR_invalid_handle;
-  if (!K) return SPL_ERROR_argument_missing;
-  *K = nullptr;
-  if (method != SPL_KRYLOV_cg && method != SPL_KRYLOV_bicgstab) return SPL_ERROR_argument_missing;
-  if (M->nrows_global != M->ncols) return SPL_ERROR_dimension_mismatch;
-  if (!whole(M)) return SPL_ERROR_invalid_matrix;
-  return guarded([&]() -> int {
-    (void)current_device();
-    DeviceGuard g(M->device);
-    Krylov *S = nullptr;
-    const int st = krylov_create(M, method, &S);
-    *K = S;
-    return st;
-  });
+  Matrix *M = nullptr;
+  const int refused = square_whole_matrix(A, K, method == SPL_KRYLOV_cg || method == SPL_KRYLOV_bicgstab, &M);
+  if (refused != SPL_OK) return refused;
+  return create_object<Krylov>(M, K, [&](Krylov **S) { return krylov_create(M, method, S); });
 }
 
 int spl_krylov_set_preconditioner(void *K, void *T1, const double *d_mid, void *T2) {
   Krylov *S = as_krylov(K);
   if (!S) return SPL_ERROR_invalid_handle;
-  TriSolver *parts[2] = {nullptr, nullptr};
-  void *given[2] = {T1, T2};
-  for (int i = 0; i < 2; ++i) {
-    if (!given[i]) continue;
-    parts[i] = as_trisolver(given[i]);
-    if (!parts[i]) return SPL_ERROR_invalid_handle;
-  }
-  if ((uintptr_t)d_mid % (uintptr_t)(8 * krylov_width(S)) != 0) return SPL_ERROR_argument_missing;
-  for (TriSolver *T : parts)
-    if (T && (trisolve_rows(T) != krylov_rows(S) || trisolve_width(T) != krylov_width(S) ||
-              trisolve_device(T) != krylov_device(S)))
-      return SPL_ERROR_dimension_mismatch;
+  TriSolver *parts[2];
+  const int refused = preconditioner_parts(head(S), T1, d_mid, T2, parts);
+  if (refused != SPL_OK) return refused;
   krylov_set_preconditioner(S, parts[0], d_mid, parts[1]);
   return SPL_OK;
 }
 
-namespace {
-// what both solve calls refuse before anything else is looked at
-int check_krylov_solve(const Krylov *S, double rtol, double atol, int64_t max_iter, int check_every,
-                       const int64_t *result, const double *history) {
-  if (!S) return SPL_ERROR_invalid_handle;
-  if (!result) return SPL_ERROR_argument_missing;
-  if (max_iter < 0) return SPL_ERROR_n_nonpositive;
-  if (!(rtol >= 0.0) || !(atol >= 0.0) || check_every < 0) return SPL_ERROR_argument_missing;  // a NaN is refused too
-  if (history && max_iter >= ((int64_t)1 << 31)) return SPL_ERROR_index_overflow;
-  return SPL_OK;
-}
-void empty_krylov_result(int64_t result[4], double *history) {
-  result[0] = result[1] = result[2] = result[3] = 0;
-  if (history) history[0] = 0.0;
-}
-}  // namespace
-
 int spl_krylov_solve_dev(void *K, const double *d_b, double *d_x, int use_x0, double rtol, double atol, int64_t max_iter,
                          int check_every, int64_t result[4], double *history, void *stream) {
   Krylov *S = as_krylov(K);
-  const int refused = check_krylov_solve(S, rtol, atol, max_iter, check_every, result, history);
+  int refused = check_linear_solve(S != nullptr, result != nullptr, rtol, atol, max_iter, check_every, history);
   if (refused != SPL_OK) return refused;
-  if (krylov_rows(S) == 0) {
-    empty_krylov_result(result, history);
+  const ObjectHead &o = head(S);
+  if (o.n == 0) {
+    empty_linear_result(4, result, history);
     return SPL_OK;
   }
-  if (!d_b || !d_x || d_b == d_x) return SPL_ERROR_argument_missing;
-  const uintptr_t entry = (uintptr_t)(8 * krylov_width(S));  // the kernels load and store whole entries
-  if ((uintptr_t)d_b % entry != 0 || (uintptr_t)d_x % entry != 0) return SPL_ERROR_argument_missing;
+  if ((refused = check_device_vectors(o, d_b, d_x)) != SPL_OK) return refused;
   return guarded([&]() -> int {
-    DeviceGuard g(krylov_device(S));
+    DeviceGuard g(o.device);
     return krylov_solve(S, d_b, d_x, use_x0 ? 1 : 0, rtol, atol, max_iter, check_every, result, history, as_stream(stream));
   });
 }
@@ -1742,51 +1769,23 @@ int spl_krylov_solve_dev(void *K, const double *d_b, double *d_x, int use_x0, do
 int spl_krylov_solve(void *K, const double *b, double *x, int use_x0, double rtol, double atol, int64_t max_iter,
                      int64_t result[4], double *history) {
   Krylov *S = as_krylov(K);
-  const int refused = check_krylov_solve(S, rtol, atol, max_iter, 0, result, history);
+  const int refused = check_linear_solve(S != nullptr, result != nullptr, rtol, atol, max_iter, 0, history);
   if (refused != SPL_OK) return refused;
-  if (krylov_rows(S) == 0) {
-    empty_krylov_result(result, history);
+  const ObjectHead &o = head(S);
+  if (o.n == 0) {
+    empty_linear_result(4, result, history);
     return SPL_OK;
   }
   if (!b || !x) return SPL_ERROR_argument_missing;
-  return guarded([&]() -> int {
-    DeviceGuard g(krylov_device(S));
-    hipStream_t s = nullptr;
-    const size_t count = (size_t)krylov_rows(S) * (size_t)krylov_width(S);
-    DBuf<double> d(2 * count);
-    double *d_b = d.get(), *d_x = d.get() + count;
-    SPL_HIP(hipMemcpyAsync(d_b, b, count * sizeof(double), hipMemcpyHostToDevice, s));
-    if (use_x0) SPL_HIP(hipMemcpyAsync(d_x, x, count * sizeof(double), hipMemcpyHostToDevice, s));
-    const int st = krylov_solve(S, d_b, d_x, use_x0 ? 1 : 0, rtol, atol, max_iter, 0, result, history, s);
-    if (st != SPL_OK) {
-      (void)hipStreamSynchronize(s);
-      return st;
-    }
-    SPL_HIP(hipMemcpyAsync(x, d_x, count * sizeof(double), hipMemcpyDeviceToHost, s));
-    SPL_HIP(hipStreamSynchronize(s));
-    return SPL_OK;
+  const size_t count = (size_t)o.n * (size_t)o.vw;
+  return with_host_vectors(o.device, count, 2, b, use_x0 ? x : nullptr, 1, x, [&](double *d, hipStream_t s) {
+    return krylov_solve(S, d, d + count, use_x0 ? 1 : 0, rtol, atol, max_iter, 0, result, history, s);
   });
 }
 
-int spl_krylov_info(void *K, int64_t info[8]) {
-  Krylov *S = as_krylov(K);
-  if (!S) return SPL_ERROR_invalid_handle;
-  if (!info) return SPL_ERROR_argument_missing;
-  krylov_info(S, info);
-  return SPL_OK;
-}
+int spl_krylov_info(void *K, int64_t info[8]) { return info_of(K, as_krylov, krylov_info, info); }
 
-void spl_krylov_free(void **K) {
-  if (!K || !*K) return;
-  Krylov *S = as_krylov(*K);
-  *K = nullptr;
-  if (!S) return;
-  int prev = -1;
-  const bool have_prev = hipGetDevice(&prev) == hipSuccess;
-  (void)hipSetDevice(krylov_device(S));  // may run on a finalizer thread with another current device
-  krylov_delete(S);
-  if (have_prev) (void)hipSetDevice(prev);
-}
+void spl_krylov_free(void **K) { free_object(K, as_krylov, krylov_delete); }
 
 // ---- multicolour ordering on handles (csrc/coloring.hip) --------------------------------------------------------------
 // H is borrowed for the call; d_colors and d_perm are the caller's device arrays, *offsets a malloc()'d host array
@@ -1854,23 +1853,10 @@ int spl_amg_create(void *A, const int64_t opt[8], void **M) {
     return SPL_ERROR_argument_missing;
   if (H->nrows_global != H->ncols) return SPL_ERROR_dimension_mismatch;
   if (!whole(H) || H->nnz >= (int64_t)0x7fffffff || (H->nrows_local > 0 && !H->rowptr.get())) return SPL_ERROR_invalid_matrix;
-  return guarded([&]() -> int {
-    (void)current_device();
-    DeviceGuard g(H->device);
-    Amg *S = nullptr;
-    const int st = amg_create(H, o, &S);
-    *M = S;
-    return st;
-  });
+  return create_object<Amg>(H, M, [&](Amg **S) { return amg_create(H, o, S); });
 }
 
-int spl_amg_info(void *M, int64_t info[8]) {
-  Amg *S = as_amg(M);
-  if (!S) return SPL_ERROR_invalid_handle;
-  if (!info) return SPL_ERROR_argument_missing;
-  amg_info(S, info);
-  return SPL_OK;
-}
+int spl_amg_info(void *M, int64_t info[8]) { return info_of(M, as_amg, amg_info, info); }
 
 // the handles and the weights are lent: they live as long as M does and are not the caller's to free
 int spl_amg_level(void *M, int level, void **HA, void **HP, void **HR, const double **d_w, int64_t dims[2]) {
@@ -1886,12 +1872,12 @@ int spl_amg_level(void *M, int level, void **HA, void **HP, void **HR, const dou
 int spl_amg_apply_dev(void *M, const double *d_b, double *d_x, void *stream) {
   Amg *S = as_amg(M);
   if (!S) return SPL_ERROR_invalid_handle;
-  if (amg_rows(S) == 0) return SPL_OK;
-  if (!d_b || !d_x || d_b == d_x) return SPL_ERROR_argument_missing;
-  const uintptr_t entry = (uintptr_t)(8 * amg_width(S));  // the kernels load and store whole entries
-  if ((uintptr_t)d_b % entry != 0 || (uintptr_t)d_x % entry != 0) return SPL_ERROR_argument_missing;
+  const ObjectHead &o = head(S);
+  if (o.n == 0) return SPL_OK;
+  const int refused = check_device_vectors(o, d_b, d_x);
+  if (refused != SPL_OK) return refused;
   return guarded([&]() -> int {
-    DeviceGuard g(amg_device(S));
+    DeviceGuard g(o.device);
     return amg_apply(S, d_b, d_x, as_stream(stream), nullptr);
   });
 }
@@ -1900,49 +1886,24 @@ int spl_amg_apply_dev(void *M, const double *d_b, double *d_x, void *stream) {
 int spl_amg_apply(void *M, const double *b, double *x) {
   Amg *S = as_amg(M);
   if (!S) return SPL_ERROR_invalid_handle;
-  if (amg_rows(S) == 0) return SPL_OK;
+  const ObjectHead &o = head(S);
+  if (o.n == 0) return SPL_OK;
   if (!b || !x) return SPL_ERROR_argument_missing;
-  return guarded([&]() -> int {
-    DeviceGuard g(amg_device(S));
-    hipStream_t s = nullptr;
-    const size_t count = (size_t)amg_rows(S) * (size_t)amg_width(S);
-    DBuf<double> d(2 * count);
-    double *d_b = d.get(), *d_x = d.get() + count;
-    SPL_HIP(hipMemcpyAsync(d_b, b, count * sizeof(double), hipMemcpyHostToDevice, s));
-    const int st = amg_apply(S, d_b, d_x, s, nullptr);
-    if (st != SPL_OK) {
-      (void)hipStreamSynchronize(s);
-      return st;
-    }
-    SPL_HIP(hipMemcpyAsync(x, d_x, count * sizeof(double), hipMemcpyDeviceToHost, s));
-    SPL_HIP(hipStreamSynchronize(s));
-    return SPL_OK;
+  const size_t count = (size_t)o.n * (size_t)o.vw;
+  return with_host_vectors(o.device, count, 2, b, nullptr, 1, x, [&](double *d, hipStream_t s) {
+    return amg_apply(S, d, d + count, s, nullptr);
   });
 }
 
-void spl_amg_free(void **M) {
-  if (!M || !*M) return;
-  Amg *S = as_amg(*M);
-  *M = nullptr;
-  if (!S) return;
-  int prev = -1;
-  const bool have_prev = hipGetDevice(&prev) == hipSuccess;
-  (void)hipSetDevice(amg_device(S));  // may run on a finalizer thread with another current device
-  amg_delete(S);
-  if (have_prev) (void)hipSetDevice(prev);
-}
+void spl_amg_free(void **M) { free_object(M, as_amg, amg_delete); }
 
 // M is borrowed and may serve several solvers; NULL takes the preconditioner away
 int spl_krylov_set_preconditioner_amg(void *K, void *M) {
   Krylov *S = as_krylov(K);
   if (!S) return SPL_ERROR_invalid_handle;
   Amg *P = nullptr;
-  if (M) {
-    P = as_amg(M);
-    if (!P) return SPL_ERROR_invalid_handle;
-    if (amg_rows(P) != krylov_rows(S) || amg_width(P) != krylov_width(S) || amg_device(P) != krylov_device(S))
-      return SPL_ERROR_dimension_mismatch;
-  }
+  const int refused = preconditioner_amg(head(S), M, &P);
+  if (refused != SPL_OK) return refused;
   krylov_set_preconditioner_amg(S, P);
   return SPL_OK;
 }
@@ -1964,38 +1925,18 @@ int spl_vector_dots_dev(int64_t n, int value_width, int k, const double *d_V, in
 
 // A is borrowed: the object keeps the pointer, its restart + 3 vectors and its tables
 int spl_gmres_create(void *A, int restart, void **G) {
-  Matrix *M = as_matrix(A);
-  if (!M) return SPL_ERROR_invalid_handle;
-  if (!G) return SPL_ERROR_argument_missing;
-  *G = nullptr;
-  if (restart < 1 || restart > 128) return SPL_ERROR_argument_missing;
-  if (M->nrows_global != M->ncols) return SPL_ERROR_dimension_mismatch;
-  if (!whole(M)) return SPL_ERROR_invalid_matrix;
-  return guarded([&]() -> int {
-    (void)current_device();
-    DeviceGuard g(M->device);
-    Gmres *S = nullptr;
-    const int st = gmres_create(M, restart, &S);
-    *G = S;
-    return st;
-  });
+  Matrix *M = nullptr;
+  const int refused = square_whole_matrix(A, G, restart >= 1 && restart <= 128, &M);
+  if (refused != SPL_OK) return refused;
+  return create_object<Gmres>(M, G, [&](Gmres **S) { return gmres_create(M, restart, S); });
 }
 
 int spl_gmres_set_preconditioner(void *G, void *T1, const double *d_mid, void *T2) {
   Gmres *S = as_gmres(G);
   if (!S) return SPL_ERROR_invalid_handle;
-  TriSolver *parts[2] = {nullptr, nullptr};
-  void *given[2] = {T1, T2};
-  for (int i = 0; i < 2; ++i) {
-    if (!given[i]) continue;
-    parts[i] = as_trisolver(given[i]);
-    if (!parts[i]) return SPL_ERROR_invalid_handle;
-  }
-  if ((uintptr_t)d_mid % (uintptr_t)(8 * gmres_width(S)) != 0) return SPL_ERROR_argument_missing;
-  for (TriSolver *T : parts)
-    if (T && (trisolve_rows(T) != gmres_rows(S) || trisolve_width(T) != gmres_width(S) ||
-              trisolve_device(T) != gmres_device(S)))
-      return SPL_ERROR_dimension_mismatch;
+  TriSolver *parts[2];
+  const int refused = preconditioner_parts(head(S), T1, d_mid, T2, parts);
+  if (refused != SPL_OK) return refused;
   gmres_set_preconditioner(S, parts[0], d_mid, parts[1]);
   return SPL_OK;
 }
@@ -2005,48 +1946,26 @@ int spl_gmres_set_preconditioner_amg(void *G, void *M) {
   Gmres *S = as_gmres(G);
   if (!S) return SPL_ERROR_invalid_handle;
   Amg *P = nullptr;
-  if (M) {
-    P = as_amg(M);
-    if (!P) return SPL_ERROR_invalid_handle;
-    if (amg_rows(P) != gmres_rows(S) || amg_width(P) != gmres_width(S) || amg_device(P) != gmres_device(S))
-      return SPL_ERROR_dimension_mismatch;
-  }
+  const int refused = preconditioner_amg(head(S), M, &P);
+  if (refused != SPL_OK) return refused;
   gmres_set_preconditioner_amg(S, P);
   return SPL_OK;
 }
 
-namespace {
-// what both solve calls refuse before anything else is looked at
-int check_gmres_solve(const Gmres *S, double rtol, double atol, int64_t max_iter, int check_every, const int64_t *result,
-                      const double *history, const double *residual) {
-  if (!S) return SPL_ERROR_invalid_handle;
-  if (!result || !residual) return SPL_ERROR_argument_missing;
-  if (max_iter < 0) return SPL_ERROR_n_nonpositive;
-  if (!(rtol >= 0.0) || !(atol >= 0.0) || check_every < 0) return SPL_ERROR_argument_missing;  // a NaN is refused too
-  if (history && max_iter >= ((int64_t)1 << 31)) return SPL_ERROR_index_overflow;
-  return SPL_OK;
-}
-void empty_gmres_result(int64_t result[6], double *history, double residual[2]) {
-  for (int i = 0; i < 6; ++i) result[i] = 0;
-  residual[0] = residual[1] = 0.0;
-  if (history) history[0] = 0.0;
-}
-}  // namespace
-
 int spl_gmres_solve_dev(void *G, const double *d_b, double *d_x, int use_x0, double rtol, double atol, int64_t max_iter,
                         int check_every, int64_t result[6], double *history, double residual[2], void *stream) {
   Gmres *S = as_gmres(G);
-  const int refused = check_gmres_solve(S, rtol, atol, max_iter, check_every, result, history, residual);
+  int refused = check_linear_solve(S != nullptr, result && residual, rtol, atol, max_iter, check_every, history);
   if (refused != SPL_OK) return refused;
-  if (gmres_rows(S) == 0) {
-    empty_gmres_result(result, history, residual);
+  const ObjectHead &o = head(S);
+  if (o.n == 0) {
+    empty_linear_result(6, result, history);
+    residual[0] = residual[1] = 0.0;
     return SPL_OK;
   }
-  if (!d_b || !d_x || d_b == d_x) return SPL_ERROR_argument_missing;
-  const uintptr_t entry = (uintptr_t)(8 * gmres_width(S));  // the kernels load and store whole entries
-  if ((uintptr_t)d_b % entry != 0 || (uintptr_t)d_x % entry != 0) return SPL_ERROR_argument_missing;
+  if ((refused = check_device_vectors(o, d_b, d_x)) != SPL_OK) return refused;
   return guarded([&]() -> int {
-    DeviceGuard g(gmres_device(S));
+    DeviceGuard g(o.device);
     return gmres_solve(S, d_b, d_x, use_x0 ? 1 : 0, rtol, atol, max_iter, check_every, result, history, residual,
                        as_stream(stream));
   });
@@ -2056,51 +1975,24 @@ int spl_gmres_solve_dev(void *G, const double *d_b, double *d_x, int use_x0, dou
 int spl_gmres_solve(void *G, const double *b, double *x, int use_x0, double rtol, double atol, int64_t max_iter,
                     int64_t result[6], double *history, double residual[2]) {
   Gmres *S = as_gmres(G);
-  const int refused = check_gmres_solve(S, rtol, atol, max_iter, 0, result, history, residual);
+  const int refused = check_linear_solve(S != nullptr, result && residual, rtol, atol, max_iter, 0, history);
   if (refused != SPL_OK) return refused;
-  if (gmres_rows(S) == 0) {
-    empty_gmres_result(result, history, residual);
+  const ObjectHead &o = head(S);
+  if (o.n == 0) {
+    empty_linear_result(6, result, history);
+    residual[0] = residual[1] = 0.0;
     return SPL_OK;
   }
   if (!b || !x) return SPL_ERROR_argument_missing;
-  return guarded([&]() -> int {
-    DeviceGuard g(gmres_device(S));
-    hipStream_t s = nullptr;
-    const size_t count = (size_t)gmres_rows(S) * (size_t)gmres_width(S);
-    DBuf<double> d(2 * count);
-    double *d_b = d.get(), *d_x = d.get() + count;
-    SPL_HIP(hipMemcpyAsync(d_b, b, count * sizeof(double), hipMemcpyHostToDevice, s));
-    if (use_x0) SPL_HIP(hipMemcpyAsync(d_x, x, count * sizeof(double), hipMemcpyHostToDevice, s));
-    const int st = gmres_solve(S, d_b, d_x, use_x0 ? 1 : 0, rtol, atol, max_iter, 0, result, history, residual, s);
-    if (st != SPL_OK) {
-      (void)hipStreamSynchronize(s);
-      return st;
-    }
-    SPL_HIP(hipMemcpyAsync(x, d_x, count * sizeof(double), hipMemcpyDeviceToHost, s));
-    SPL_HIP(hipStreamSynchronize(s));
-    return SPL_OK;
+  const size_t count = (size_t)o.n * (size_t)o.vw;
+  return with_host_vectors(o.device, count, 2, b, use_x0 ? x : nullptr, 1, x, [&](double *d, hipStream_t s) {
+    return gmres_solve(S, d, d + count, use_x0 ? 1 : 0, rtol, atol, max_iter, 0, result, history, residual, s);
   });
 }
 
-int spl_gmres_info(void *G, int64_t info[8]) {
-  Gmres *S = as_gmres(G);
-  if (!S) return SPL_ERROR_invalid_handle;
-  if (!info) return SPL_ERROR_argument_missing;
-  gmres_info(S, info);
-  return SPL_OK;
-}
+int spl_gmres_info(void *G, int64_t info[8]) { return info_of(G, as_gmres, gmres_info, info); }
 
-void spl_gmres_free(void **G) {
-  if (!G || !*G) return;
-  Gmres *S = as_gmres(*G);
-  *G = nullptr;
-  if (!S) return;
-  int prev = -1;
-  const bool have_prev = hipGetDevice(&prev) == hipSuccess;
-  (void)hipSetDevice(gmres_device(S));  // may run on a finalizer thread with another current device
-  gmres_delete(S);
-  if (have_prev) (void)hipSetDevice(prev);
-}
+void spl_gmres_free(void **G) { free_object(G, as_gmres, gmres_delete); }
 
 // ---- thick-restart Lanczos on handles and the in-place basis rotation (csrc/eigsh.hip) ----------------------------------
 int spl_vector_rotate_dev(int64_t n, int value_width, int m, int k, double *d_V, int64_t ldv, const double *d_Y, int ldy,
@@ -2125,21 +2017,12 @@ int spl_vector_rotate_dev(int64_t n, int value_width, int m, int k, double *d_V,
 
 // A is borrowed: the object keeps the pointer, its ncv + 2 vectors and its tables
 int spl_eigsh_create(void *A, int ncv, void **E) {
-  Matrix *M = as_matrix(A);
-  if (!M) return SPL_ERROR_invalid_handle;
-  if (!E) return SPL_ERROR_argument_missing;
-  *E = nullptr;
-  if (ncv < 2 || ncv > 128) return SPL_ERROR_argument_missing;
-  if (M->nrows_global != M->ncols) return SPL_ERROR_dimension_mismatch;
-  if (!whole(M)) return SPL_ERROR_invalid_matrix;
-  return guarded([&]() -> int {
-    (void)current_device();
-    DeviceGuard g(M->device);
+  Matrix *M = nullptr;
+  const int refused = square_whole_matrix(A, E, ncv >= 2 && ncv <= 128, &M);
+  if (refused != SPL_OK) return refused;
+  return create_object<Eigsh>(M, E, [&](Eigsh **S) -> int {
     if (!M->rowptr.get() || hermitian_device(M, nullptr) != 1) return SPL_ERROR_invalid_matrix;
-    Eigsh *S = nullptr;
-    const int st = eigsh_create(M, ncv, &S);
-    *E = S;
-    return st;
+    return eigsh_create(M, ncv, S);
   });
 }
 
@@ -2151,8 +2034,7 @@ int spl_eigsh_set_inverse(void *E, void *K, double sigma, double rtol, double at
   if (K) {
     P = as_krylov(K);
     if (!P) return SPL_ERROR_invalid_handle;
-    if (krylov_rows(P) != eigsh_rows(S) || krylov_width(P) != eigsh_width(S) || krylov_device(P) != eigsh_device(S))
-      return SPL_ERROR_dimension_mismatch;
+    if (!same_shape(head(P), head(S))) return SPL_ERROR_dimension_mismatch;
     if (max_iter < 0) return SPL_ERROR_n_nonpositive;
     if (!(rtol >= 0.0) || !(atol >= 0.0) || !std::isfinite(sigma)) return SPL_ERROR_argument_missing;  // a NaN too
   }
@@ -2167,7 +2049,7 @@ int check_eigsh_solve(const Eigsh *S, int nev, int which, double tol, double ato
   if (!S) return SPL_ERROR_invalid_handle;
   if (!values || !residuals || !result) return SPL_ERROR_argument_missing;
   if (max_restarts < 1) return SPL_ERROR_n_nonpositive;
-  if (nev < 1 || nev >= eigsh_ncv(S) || (int64_t)eigsh_ncv(S) > eigsh_rows(S) || which < 0 || which > 2 || !(tol >= 0.0) ||
+  if (nev < 1 || nev >= eigsh_ncv(S) || (int64_t)eigsh_ncv(S) > head(S).n || which < 0 || which > 2 || !(tol >= 0.0) ||
       !(atol >= 0.0))
     return SPL_ERROR_argument_missing;  // a NaN is refused too
   if (history && max_restarts >= ((int64_t)1 << 31)) return SPL_ERROR_index_overflow;
@@ -2181,11 +2063,12 @@ int spl_eigsh_solve_dev(void *E, int nev, int which, double tol, double atol, in
   Eigsh *S = as_eigsh(E);
   const int refused = check_eigsh_solve(S, nev, which, tol, atol, max_restarts, values, residuals, result, history);
   if (refused != SPL_OK) return refused;
-  if (!d_v0 || !d_vectors || ldx < eigsh_rows(S)) return SPL_ERROR_argument_missing;
-  const uintptr_t entry = (uintptr_t)(8 * eigsh_width(S));  // the kernels load and store whole entries
+  const ObjectHead &o = head(S);
+  if (!d_v0 || !d_vectors || ldx < o.n) return SPL_ERROR_argument_missing;
+  const uintptr_t entry = (uintptr_t)(8 * o.vw);  // the kernels load and store whole entries
   if ((uintptr_t)d_v0 % entry != 0 || (uintptr_t)d_vectors % entry != 0) return SPL_ERROR_argument_missing;
   return guarded([&]() -> int {
-    DeviceGuard g(eigsh_device(S));
+    DeviceGuard g(o.device);
     return eigsh_solve(S, nev, which, tol, atol, max_restarts, d_v0, values, d_vectors, ldx, residuals, result, history,
                        as_stream(stream));
   });
@@ -2197,47 +2080,24 @@ int spl_eigsh_solve(void *E, int nev, int which, double tol, double atol, int64_
   Eigsh *S = as_eigsh(E);
   const int refused = check_eigsh_solve(S, nev, which, tol, atol, max_restarts, values, residuals, result, history);
   if (refused != SPL_OK) return refused;
-  if (!v0 || !vectors || ldx < eigsh_rows(S)) return SPL_ERROR_argument_missing;
-  return guarded([&]() -> int {
-    DeviceGuard g(eigsh_device(S));
-    hipStream_t s = nullptr;
-    const size_t count = (size_t)eigsh_rows(S) * (size_t)eigsh_width(S);
-    DBuf<double> d(((size_t)nev + 1) * count);
-    double *d_v0 = d.get(), *d_vectors = d.get() + count;
-    SPL_HIP(hipMemcpyAsync(d_v0, v0, count * sizeof(double), hipMemcpyHostToDevice, s));
-    const int st = eigsh_solve(S, nev, which, tol, atol, max_restarts, d_v0, values, d_vectors, eigsh_rows(S), residuals,
-                               result, history, s);
-    if (st != SPL_OK) {
-      (void)hipStreamSynchronize(s);
-      return st;
-    }
-    for (int64_t i = 0; i < result[3]; ++i)
-      SPL_HIP(hipMemcpyAsync(vectors + (size_t)i * (size_t)ldx * (size_t)eigsh_width(S), d_vectors + (size_t)i * count,
+  const ObjectHead &o = head(S);
+  if (!v0 || !vectors || ldx < o.n) return SPL_ERROR_argument_missing;
+  const size_t count = (size_t)o.n * (size_t)o.vw;
+  return with_host_vectors(o.device, count, (size_t)nev + 1, v0, nullptr, 0, nullptr, [&](double *d, hipStream_t s) {
+    double *d_vectors = d + count;
+    const int st = eigsh_solve(S, nev, which, tol, atol, max_restarts, d, values, d_vectors, o.n, residuals, result,
+                               history, s);
+    if (st != SPL_OK) return st;
+    for (int64_t i = 0; i < result[3]; ++i)  // the columns found, ldx entries apart
+      SPL_HIP(hipMemcpyAsync(vectors + (size_t)i * (size_t)ldx * (size_t)o.vw, d_vectors + (size_t)i * count,
                              count * sizeof(double), hipMemcpyDeviceToHost, s));
-    SPL_HIP(hipStreamSynchronize(s));
     return SPL_OK;
   });
 }
 
-int spl_eigsh_info(void *E, int64_t info[8]) {
-  Eigsh *S = as_eigsh(E);
-  if (!S) return SPL_ERROR_invalid_handle;
-  if (!info) return SPL_ERROR_argument_missing;
-  eigsh_info(S, info);
-  return SPL_OK;
-}
+int spl_eigsh_info(void *E, int64_t info[8]) { return info_of(E, as_eigsh, eigsh_info, info); }
 
-void spl_eigsh_free(void **E) {
-  if (!E || !*E) return;
-  Eigsh *S = as_eigsh(*E);
-  *E = nullptr;
-  if (!S) return;
-  int prev = -1;
-  const bool have_prev = hipGetDevice(&prev) == hipSuccess;
-  (void)hipSetDevice(eigsh_device(S));  // may run on a finalizer thread with another current device
-  eigsh_delete(S);
-  if (have_prev) (void)hipSetDevice(prev);
-}
+void spl_eigsh_free(void **E) { free_object(E, as_eigsh, eigsh_delete); }
 
 // mulM on Complex Double (the reference's SPECIALIZE instance, Sparse.hs:475): one axpy_ per column of B there; here the
 // packed-complex image of A and one multi-vector product.  B and C are row-major like spl_mulm's; the kernel wants one

@@ -32,8 +32,6 @@
 
 namespace spl {
 
-constexpr uint32_t kAmgMagic = 0x53504C47u;  // "SPLG"
-
 namespace {
 
 constexpr int kAmgGridDefault = 2048;       // workgroups of an aggregation launch at most (SPL_AMG_GRID)
@@ -483,10 +481,8 @@ void must(int st) {
 
 }  // namespace
 
-struct Amg {
-  uint32_t magic = kAmgMagic;
-  int device = 0, vw = 1;
-  int64_t n = 0;
+struct Amg : ObjectHead {
+  Amg() : ObjectHead(kAmgMagic) {}
   uint64_t seed = 0;
   int nu = 1, coarse_sweeps = 4, max_levels = 16, plain = 0;
   int64_t coarse_size = 256;
@@ -509,11 +505,6 @@ struct Amg {
     if (applied) (void)hipEventDestroy(applied);
   }
 };
-
-Amg *as_amg(void *m) {
-  Amg *M = static_cast<Amg *>(m);
-  return (M && M->magic == kAmgMagic) ? M : nullptr;
-}
 
 namespace {
 
@@ -795,14 +786,9 @@ int amg_apply(Amg *M, const double *d_b, double *d_x, hipStream_t s, int64_t *la
   return e;
 }
 
-int amg_device(const Amg *M) { return M->device; }
-int64_t amg_rows(const Amg *M) { return M->n; }
-int amg_width(const Amg *M) { return M->vw; }
-
 void amg_delete(Amg *M) {
   if (M->applied) (void)hipEventSynchronize(M->applied);
-  M->magic = 0;
-  delete M;
+  delete_object(M);
 }
 
 }  // namespace spl

@@ -105,6 +105,37 @@ struct DeviceGuard {
 
 constexpr uint32_t kMatrixMagic = 0x53504C4Du;  // "SPLM"
 
+// What every other object behind a handle begins with (it is the object's first base): the C boundary (abi.hip) tells
+// the objects apart by the magic word and compares devices, sizes and value kinds without seeing their types.
+struct ObjectHead {
+  uint32_t magic;
+  int device = 0;
+  int vw = 1;     // doubles per entry: 1 real, 2 packed complex
+  int64_t n = 0;  // rows
+  explicit ObjectHead(uint32_t word) : magic(word) {}
+};
+constexpr uint32_t kTriMagic = 0x53504C54u;     // "SPLT"
+constexpr uint32_t kIluMagic = 0x53504C49u;     // "SPLI"
+constexpr uint32_t kKrylovMagic = 0x53504C4Bu;  // "SPLK"
+constexpr uint32_t kAmgMagic = 0x53504C47u;     // "SPLG"
+constexpr uint32_t kGmresMagic = 0x53504C47u;   // "SPLG": the word of the AMG object, so the two are not told apart
+constexpr uint32_t kEigshMagic = 0x53504C45u;   // "SPLE"
+// the object behind h, or nullptr unless h carries the magic word
+template <typename T, uint32_t Magic>
+T *as_object(void *h) {
+  const ObjectHead *o = static_cast<const ObjectHead *>(h);
+  return (o && o->magic == Magic) ? static_cast<T *>(h) : nullptr;
+}
+// the head of an object whose type the caller does not see (the head lies at the object's address)
+template <typename T>
+const ObjectHead &head(const T *object) { return *reinterpret_cast<const ObjectHead *>(object); }
+// the end of an object: the handle stops being one before the memory goes
+template <typename T>
+void delete_object(T *object) {
+  object->magic = 0;
+  delete object;
+}
+
 // column-blocked image of a row block (spmv_blocked.hip)
 struct BlockedImage {
   int R = 0, w = 0;               // panel = R rows (R << w must fit 31 bits), column block = 2^w columns
@@ -297,20 +328,17 @@ double norm_handle(const Matrix *A, int which, hipStream_t s);  // synchronises 
 
 // ---- sparse triangular solves on handles (trisolve.hip, tri_levels.hpp) ----------------------------------------
 struct TriSolver;
-TriSolver *as_trisolver(void *t);  // nullptr unless t carries the object's magic word
+inline TriSolver *as_trisolver(void *t) { return as_object<TriSolver, kTriMagic>(t); }
 // A: whole, square, 32-bit row pointers (the caller checked).  SPL_OK or SPL_WARNING_singular_matrix; synchronises
 int trisolve_analyze(const Matrix *A, int uplo, int diag, TriSolver **out);
 // enqueues on s; the first solve with a transposed op builds that image under the object's lock and synchronises
 int trisolve_solve(TriSolver *T, int op, int k, const double *d_B, int64_t ldb, double *d_X, int64_t ldx, hipStream_t s);
 void trisolve_info(const TriSolver *T, int64_t info[8]);
-int trisolve_device(const TriSolver *T);
-int trisolve_rows(const TriSolver *T);
-int trisolve_width(const TriSolver *T);  // doubles per entry: 1 real, 2 packed complex
 void trisolve_delete(TriSolver *T);
 
 // ---- ILU(0) on handles (ilu0.hip, tri_levels.hpp): the producer of what the triangular solves apply -------------
 struct IluPlan;
-IluPlan *as_ilu_plan(void *p);  // nullptr unless p carries the object's magic word
+inline IluPlan *as_ilu_plan(void *p) { return as_object<IluPlan, kIluMagic>(p); }
 // A: whole, square, 32-bit row pointers (the caller checked).  SPL_OK; synchronises
 int ilu0_analyze(const Matrix *A, IluPlan **out);
 // A: whole, 32-bit row pointers, on the plan's device (the caller checked); C: dimensions and value kind set by the
@@ -318,14 +346,13 @@ int ilu0_analyze(const Matrix *A, IluPlan **out);
 // the L\U values (rowptr64 / colidx / val / nnz): SPL_OK or SPL_WARNING_singular_matrix.  Synchronises s
 int ilu0_factor(IluPlan *P, const Matrix *A, Matrix *C, hipStream_t s);
 void ilu0_info(const IluPlan *P, int64_t info[8]);
-int ilu0_device(const IluPlan *P);
 void ilu0_delete(IluPlan *P);
 
 // ---- the fixed-order inner product, preconditioned CG and BiCGSTAB on handles (krylov.hip) ----------------------
 // <a,b> of n entries of vw doubles each to d_out (vw doubles, device memory); enqueues on s, no synchronisation
 int vector_dot(int device, int64_t n, int vw, const double *d_a, const double *d_b, double *d_out, hipStream_t s);
 struct Krylov;
-Krylov *as_krylov(void *k);  // nullptr unless k carries the object's magic word
+inline Krylov *as_krylov(void *k) { return as_object<Krylov, kKrylovMagic>(k); }
 // A: whole and square (the caller checked); borrowed.  SPL_OK
 int krylov_create(const Matrix *A, int method, Krylov **out);
 // the parts are borrowed and of K's size and value kind (the caller checked); nullptr: the part is the identity
@@ -334,9 +361,6 @@ void krylov_set_preconditioner(Krylov *K, TriSolver *T1, const double *d_mid, Tr
 int krylov_solve(Krylov *K, const double *d_b, double *d_x, int use_x0, double rtol, double atol, int64_t max_iter,
                  int check_every, int64_t result[4], double *history, hipStream_t s);
 void krylov_info(Krylov *K, int64_t info[8]);
-int krylov_device(const Krylov *K);
-int64_t krylov_rows(const Krylov *K);
-int krylov_width(const Krylov *K);  // doubles per entry: 1 real, 2 packed complex
 void krylov_delete(Krylov *K);
 
 // ---- multicolour ordering on handles (coloring.hip) -----------------------------------------------------------------
@@ -376,7 +400,7 @@ void color_graph_max_degree(const ColorGraph &graph, int n, int G, int64_t grid_
 // stream; synchronises.  SPL_OK
 int aggregate_handle(const Matrix *A, uint64_t seed, int *d_agg, int *d_roots, int64_t info[8]);
 struct Amg;
-Amg *as_amg(void *m);  // nullptr unless m carries the object's magic word
+inline Amg *as_amg(void *m) { return as_object<Amg, kAmgMagic>(m); }
 // A: whole and square (the caller checked), borrowed; opt: the eight options with the defaults filled in and checked
 int amg_create(Matrix *A, const int64_t opt[8], Amg **out);
 void amg_info(Amg *M, int64_t info[8]);
@@ -384,9 +408,6 @@ void amg_info(Amg *M, int64_t info[8]);
 void amg_level(Amg *M, int level, void **HA, void **HP, void **HR, const double **d_w, int64_t dims[2]);
 // x = cycle(0, b); d_b != d_x (the caller checked); enqueues on s.  *launches (may be nullptr): kernels enqueued
 int amg_apply(Amg *M, const double *d_b, double *d_x, hipStream_t s, int64_t *launches);
-int amg_device(const Amg *M);
-int64_t amg_rows(const Amg *M);
-int amg_width(const Amg *M);  // doubles per entry: 1 real, 2 packed complex
 void amg_delete(Amg *M);
 // M: borrowed, of K's size, value kind and device (the caller checked), or nullptr; clears the triangular parts
 void krylov_set_preconditioner_amg(Krylov *K, Amg *M);
@@ -397,7 +418,7 @@ void krylov_set_preconditioner_amg(Krylov *K, Amg *M);
 int vector_dots(int device, int64_t n, int vw, int k, const double *d_V, int64_t ldv, const double *d_w, double *d_out,
                 hipStream_t s);
 struct Gmres;
-Gmres *as_gmres(void *g);  // nullptr unless g carries the object's magic word
+inline Gmres *as_gmres(void *g) { return as_object<Gmres, kGmresMagic>(g); }
 // A: whole and square, 1 <= restart <= 128 (the caller checked); borrowed.  SPL_OK
 int gmres_create(const Matrix *A, int restart, Gmres **out);
 // the parts are borrowed and of G's size, value kind and device (the caller checked); nullptr: the identity
@@ -407,9 +428,6 @@ void gmres_set_preconditioner_amg(Gmres *G, Amg *M);
 int gmres_solve(Gmres *G, const double *d_b, double *d_x, int use_x0, double rtol, double atol, int64_t max_iter,
                 int check_every, int64_t result[6], double *history, double residual[2], hipStream_t s);
 void gmres_info(Gmres *G, int64_t info[8]);
-int gmres_device(const Gmres *G);
-int64_t gmres_rows(const Gmres *G);
-int gmres_width(const Gmres *G);  // doubles per entry: 1 real, 2 packed complex
 void gmres_delete(Gmres *G);
 
 // ---- thick-restart Lanczos on handles and the in-place basis rotation (eigsh.hip) ---------------------------------------
@@ -418,7 +436,7 @@ void gmres_delete(Gmres *G);
 int vector_rotate(int64_t n, int vw, int m, int k, double *d_V, int64_t ldv, const double *d_Y, int ldy, double *d_out,
                   int64_t ldo, hipStream_t s);
 struct Eigsh;
-Eigsh *as_eigsh(void *e);  // nullptr unless e carries the object's magic word
+inline Eigsh *as_eigsh(void *e) { return as_object<Eigsh, kEigshMagic>(e); }
 // A: whole, square and Hermitian, 2 <= ncv <= 128 (the caller checked); borrowed.  SPL_OK
 int eigsh_create(const Matrix *A, int ncv, Eigsh **out);
 // K: borrowed, of E's size, value kind and device (the caller checked), or nullptr: the operator is A again
@@ -428,9 +446,6 @@ int eigsh_solve(Eigsh *E, int nev, int which, double tol, double atol, int64_t m
                 double *values, double *d_vectors, int64_t ldx, double *residuals, int64_t result[6], double *history,
                 hipStream_t s);
 void eigsh_info(Eigsh *E, int64_t info[8]);
-int eigsh_device(const Eigsh *E);
-int64_t eigsh_rows(const Eigsh *E);
-int eigsh_width(const Eigsh *E);  // doubles per entry: 1 real, 2 packed complex
 int eigsh_ncv(const Eigsh *E);
 void eigsh_delete(Eigsh *E);
 

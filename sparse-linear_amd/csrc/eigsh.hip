@@ -19,10 +19,9 @@
 #include <vector>
 
 #include "krylov_basis.hpp"
+#include "solver_core.hpp"
 
 namespace spl {
-
-constexpr uint32_t kEigshMagic = 0x53504C45u;  // "SPLE"
 
 namespace {
 
@@ -292,53 +291,27 @@ int vector_rotate(int64_t n, int vw, int m, int k, double *d_V, int64_t ldv, con
   return SPL_OK;
 }
 
-// ---- the solver object -------------------------------------------------------------------------------------------------
-struct Eigsh {
-  uint32_t magic = kEigshMagic;
-  int device = 0;
-  int vw = 1;
-  int ncv = 0;
-  int64_t n = 0;
-  const Matrix *A = nullptr;  // borrowed
-  Krylov *K = nullptr;        // borrowed; set: the operator is (A - sigma I)^-1 by K
+// ---- the solver object (the shared part: solver_core.hpp) ---------------------------------------------------------------
+struct Eigsh : SolverCore {  // work: ncv + 2 vectors, the basis v_0 ... v_ncv and A x of the residuals
+  int ncv;
+  Krylov *K = nullptr;  // borrowed; set: the operator is (A - sigma I)^-1 by K
   double sigma = 0.0, rtol = 0.0, atol = 0.0;
   int64_t max_iter = 0;
-  DBuf<double> work;     // ncv + 2 vectors: the basis v_0 ... v_ncv and A x of the residuals
-  DBuf<double> scratch;  // partials of the fold
   DBuf<double> tables;
-  DBuf<EStatus> status;
-  EStatus *pinned = nullptr;  // the status block, alpha, beta and res, and the ncv x ncv doubles that go up
-  size_t bytes = 0;
-  std::mutex lock;  // one solve at a time
-  int64_t solves = 0, last_cycles = 0, last_launches = 0;
-  double *vec(int i) const { return work.get() + (size_t)i * (size_t)n * (size_t)vw; }
-  double *host_tables() const { return reinterpret_cast<double *>(pinned + 1); }
+  StatusBlock<EStatus> status;  // behind the pinned copy: alpha, beta and res, and the ncv x ncv doubles that go up
+  int64_t last_cycles = 0;
+  Eigsh(const Matrix *A, int m)
+      : SolverCore(kEigshMagic, A, (size_t)m + 2, fold_scratch(A->nrows_local, m * A->vw)), ncv(m),
+        tables(etable_doubles(m)), status(((size_t)3 * m + (size_t)m * m) * sizeof(double)) {
+    bytes += etable_doubles(m) * sizeof(double) + sizeof(EStatus);
+  }
+  double *host_tables() const { return reinterpret_cast<double *>(status.pinned + 1); }
   double *host_y() const { return host_tables() + 3 * ncv; }
 };
 
-Eigsh *as_eigsh(void *e) {
-  Eigsh *E = static_cast<Eigsh *>(e);
-  return (E && E->magic == kEigshMagic) ? E : nullptr;
-}
-
 // A: whole, square and Hermitian, 2 <= ncv <= 128 (the caller checked)
 int eigsh_create(const Matrix *A, int ncv, Eigsh **out) {
-  std::unique_ptr<Eigsh> E(new Eigsh);
-  E->device = A->device;
-  E->vw = A->vw;
-  E->ncv = ncv;
-  E->n = A->nrows_local;
-  E->A = A;
-  const size_t vec_doubles = (size_t)E->n * (size_t)E->vw, nvec = (size_t)ncv + 2;
-  E->work.alloc(nvec * vec_doubles);
-  const size_t scratch = fold_scratch(E->n, ncv * E->vw);
-  E->scratch.alloc(scratch);
-  E->tables.alloc(etable_doubles(ncv));
-  E->status.alloc(1);
-  SPL_HIP(hipHostMalloc(reinterpret_cast<void **>(&E->pinned),
-                        sizeof(EStatus) + ((size_t)3 * ncv + (size_t)ncv * ncv) * sizeof(double), hipHostMallocDefault));
-  E->bytes = (nvec * vec_doubles + scratch + etable_doubles(ncv)) * sizeof(double) + sizeof(EStatus);
-  *out = E.release();
+  *out = new Eigsh(A, ncv);
   return SPL_OK;
 }
 
@@ -355,38 +328,26 @@ namespace {
 
 // One solve's launches; everything is enqueued on s
 template <int VW>
-struct ERun {
+struct ERun : RunCore {
   Eigsh *E;
-  hipStream_t s;
-  int64_t n;
   int m;  // ncv
   EStatus *st;
-  double *scratch;
   ETables T;
-  unsigned flat, chunked;
-  int64_t launches = 0, inner = 0;
+  int64_t inner = 0;
 
   ERun(Eigsh *e, hipStream_t stream)
-      : E(e), s(stream), n(e->n), m(e->ncv), st(e->status.get()), scratch(e->scratch.get()),
-        T(etables_at(e->tables.get(), e->ncv)), flat(grid_flat(e->n, 4096)), chunked(chunk_grid(e->n)) {}
+      : RunCore(*e, stream), E(e), m(e->ncv), st(e->status.device.get()), T(etables_at(e->tables.get(), e->ncv)) {}
 
   double *basis(int j) const { return E->vec(j); }
   double *product() const { return E->vec(m + 1); }
   const int *skip() const { return &st->skip; }
 
+  // tables: alpha, beta and res come down beside the status block
   const EStatus &look(bool tables) {
-    SPL_HIP(hipMemcpyAsync(E->pinned, st, sizeof(EStatus), hipMemcpyDeviceToHost, s));
-    if (tables)
-      SPL_HIP(hipMemcpyAsync(E->host_tables(), T.alpha, (size_t)3 * m * sizeof(double), hipMemcpyDeviceToHost, s));
-    SPL_HIP(hipStreamSynchronize(s));
-    return *E->pinned;
-  }
-  int launch_status(const char *where) {
-    const hipError_t e = hipGetLastError();
-    if (e == hipSuccess) return SPL_OK;
-    set_last_error(where, e);
-    (void)hipStreamSynchronize(s);
-    return SPL_ERROR_device;
+    return RunCore::look(E->status, [&] {
+      if (tables)
+        SPL_HIP(hipMemcpyAsync(E->host_tables(), T.alpha, (size_t)3 * m * sizeof(double), hipMemcpyDeviceToHost, s));
+    });
   }
 
   void start(const double *v0) {
@@ -414,17 +375,11 @@ struct ERun {
 
   void orthogonalise(int j) {
     double *w = basis(j + 1);
-    launches += dots_launch<VW>(skip(), n, j + 1, basis(0), n, w, T.c1, scratch, s);
-    hipLaunchKernelGGL((update_kernel<VW, false>), dim3(chunked), dim3(kLanes), 0, s, skip(), n, j + 1,
-                       (const double *)basis(0), n, (const double *)T.c1, w, scratch);
-    launches += dots_launch<VW>(skip(), n, j + 1, basis(0), n, w, T.c2, scratch, s);
-    hipLaunchKernelGGL((update_kernel<VW, true>), dim3(chunked), dim3(kLanes), 0, s, skip(), n, j + 1,
-                       (const double *)basis(0), n, (const double *)T.c2, w, scratch);
-    const Partials P = middle_levels(skip(), n, 1, scratch, s);
+    const Partials P = orthogonalise_twice<VW>(skip(), n, j + 1, basis(0), w, T.c1, T.c2, scratch, chunked, s, &launches);
     hipLaunchKernelGGL((step_kernel<VW>), dim3(1), dim3(kLanes), 0, s, st, j, P.p, P.count, T);
     hipLaunchKernelGGL(divide_kernel, dim3(flat), dim3(kLanes), 0, s, skip(), n * VW, (const double *)&st->scale,
                        (const double *)w, w);
-    launches += P.middle + 4;
+    launches += 2;
   }
 
   // Y[:, order[0 .. cols)] of the m' x m' host matrix to the device table, leading dimension m'
@@ -608,15 +563,8 @@ void eigsh_info(Eigsh *E, int64_t info[8]) {
   info[7] = 0;
 }
 
-int eigsh_device(const Eigsh *E) { return E->device; }
-int64_t eigsh_rows(const Eigsh *E) { return E->n; }
-int eigsh_width(const Eigsh *E) { return E->vw; }
 int eigsh_ncv(const Eigsh *E) { return E->ncv; }
 
-void eigsh_delete(Eigsh *E) {
-  E->magic = 0;
-  if (E->pinned) (void)hipHostFree(E->pinned);
-  delete E;
-}
+void eigsh_delete(Eigsh *E) { delete_object(E); }
 
 }  // namespace spl

@@ -14,10 +14,9 @@
 // reads `skip` (cycle closed, or done) first and returns without touching a vector when it is set.  No kernel waits for
 // another workgroup, there is no floating-point atomic and no captured graph.
 #include "krylov_basis.hpp"
+#include "solver_core.hpp"
 
 namespace spl {
-
-constexpr uint32_t kGmresMagic = 0x53504C47u;  // "SPLG"
 
 namespace {
 
@@ -85,16 +84,6 @@ __global__ __launch_bounds__(kLanes) void divide_kernel(const GStatus *st, int64
   int64_t i = (int64_t)blockIdx.x * kLanes + threadIdx.x;
   const int64_t stride = (int64_t)gridDim.x * kLanes;
   for (; i < count; i += stride) v[i] = v[i] / by;
-}
-
-// out = d (.) in, entry by entry; stop: `skip` inside a cycle, `done` at a close
-template <int VW>
-__global__ __launch_bounds__(kLanes) void diag_kernel(const int *stop, int64_t n, const double *d, const double *in,
-                                                      double *out) {
-  if (*stop) return;
-  int64_t i = (int64_t)blockIdx.x * kLanes + threadIdx.x;
-  const int64_t stride = (int64_t)gridDim.x * kLanes;
-  for (; i < n; i += stride) store_val(out, i, mul(load_val<VW>(d, i), load_val<VW>(in, i)));
 }
 
 // The close: u = y_0 v_0, u = u + y_l v_l in ascending l < k; x != nullptr: x = x + u, otherwise u is stored
@@ -264,138 +253,57 @@ int vector_dots(int device, int64_t n, int vw, int k, const double *d_V, int64_t
   return SPL_OK;
 }
 
-// ---- the solver object -------------------------------------------------------------------------------------------------
-struct Gmres {
-  uint32_t magic = kGmresMagic;
-  int device = 0;
-  int vw = 1;
-  int restart = 0;
-  int64_t n = 0;
-  const Matrix *A = nullptr;                 // borrowed
-  TriSolver *T1 = nullptr, *T2 = nullptr;    // borrowed
-  const double *d_mid = nullptr;             // borrowed
-  Amg *amg = nullptr;                        // borrowed; set: the three parts above are not
-  DBuf<double> work;     // restart + 3 vectors: the basis v_0 ... v_restart, u, M^-1 u
-  DBuf<double> scratch;  // partials of the fold
+// ---- the solver object (the shared part: solver_core.hpp) ---------------------------------------------------------------
+struct Gmres : SolverCore {  // work: restart + 3 vectors, the basis v_0 ... v_restart, u, M^-1 u
+  int restart;
+  Preconditioner pre;
   DBuf<double> tables;
-  DBuf<double> hist;     // history[it], grown with the iterations issued
-  DBuf<GStatus> status;
-  GStatus *pinned = nullptr;
-  size_t bytes = 0;
-  std::mutex lock;       // one solve at a time
-  int64_t solves = 0, last_iterations = 0, last_launches = 0;
-  double *vec(int i) const { return work.get() + (size_t)i * (size_t)n * (size_t)vw; }
-  bool preconditioned() const { return T1 || T2 || d_mid || amg; }
+  DBuf<double> hist;  // history[it], grown with the iterations issued (room_for)
+  StatusBlock<GStatus> status;
+  int64_t last_iterations = 0;
+  Gmres(const Matrix *A, int m)
+      : SolverCore(kGmresMagic, A, (size_t)m + 3, fold_scratch(A->nrows_local, (m > 1 ? m : 2) * A->vw)), restart(m),
+        tables(table_doubles(m)) {
+    bytes += table_doubles(m) * sizeof(double) + sizeof(GStatus);
+  }
 };
-
-Gmres *as_gmres(void *g) {
-  Gmres *G = static_cast<Gmres *>(g);
-  return (G && G->magic == kGmresMagic) ? G : nullptr;
-}
 
 // A: whole and square, 1 <= restart <= 128 (the caller checked)
 int gmres_create(const Matrix *A, int restart, Gmres **out) {
-  std::unique_ptr<Gmres> G(new Gmres);
-  G->device = A->device;
-  G->vw = A->vw;
-  G->restart = restart;
-  G->n = A->nrows_local;
-  G->A = A;
-  const size_t vec_doubles = (size_t)G->n * (size_t)G->vw, nvec = (size_t)restart + 3;
-  G->work.alloc(nvec * vec_doubles);
-  const size_t scratch = fold_scratch(G->n, (restart > 1 ? restart : 2) * G->vw);
-  G->scratch.alloc(scratch);
-  G->tables.alloc(table_doubles(restart));
-  G->status.alloc(1);
-  SPL_HIP(hipHostMalloc(reinterpret_cast<void **>(&G->pinned), sizeof(GStatus), hipHostMallocDefault));
-  G->bytes = (nvec * vec_doubles + scratch + table_doubles(restart)) * sizeof(double) + sizeof(GStatus);
-  *out = G.release();
+  *out = new Gmres(A, restart);
   return SPL_OK;
 }
 
 void gmres_set_preconditioner(Gmres *G, TriSolver *T1, const double *d_mid, TriSolver *T2) {
   std::lock_guard<std::mutex> hold(G->lock);
-  G->T1 = T1;
-  G->d_mid = d_mid;
-  G->T2 = T2;
-  G->amg = nullptr;
+  G->pre.set_parts(T1, d_mid, T2);
 }
 
 void gmres_set_preconditioner_amg(Gmres *G, Amg *M) {
   std::lock_guard<std::mutex> hold(G->lock);
-  G->T1 = G->T2 = nullptr;
-  G->d_mid = nullptr;
-  G->amg = M;
+  G->pre.set_amg(M);
 }
 
 namespace {
 
 // One solve's launches; everything is enqueued on s
 template <int VW>
-struct GRun {
+struct GRun : LinearRun {
   Gmres *G;
-  hipStream_t s;
-  double rtol, atol;
-  long long max_iter;
-  bool hist_wanted;
-  double *hist = nullptr;
-  int64_t n;
   int m;
   GStatus *st;
-  double *scratch;
   Tables T;
-  unsigned flat, chunked;
-  int64_t spmvs = 0, applications = 0, launches = 0;
 
   GRun(Gmres *g, hipStream_t stream, double rt, double at, long long mi, bool history)
-      : G(g), s(stream), rtol(rt), atol(at), max_iter(mi), hist_wanted(history), n(g->n), m(g->restart),
-        st(g->status.get()), scratch(g->scratch.get()), T(tables_at(g->tables.get(), g->restart)),
-        flat(grid_flat(g->n, 4096)), chunked(chunk_grid(g->n)) {}
+      : LinearRun(*g, g->pre, g->hist, stream, rt, at, mi, history), G(g), m(g->restart), st(g->status.device.get()),
+        T(tables_at(g->tables.get(), g->restart)) {}
 
   double *basis(int j) const { return G->vec(j); }
   double *u() const { return G->vec(m + 1); }
   double *mu() const { return G->vec(m + 2); }
   const int *skip() const { return &st->skip; }
   const int *done() const { return &st->done; }
-
-  int spmv(const double *x, double *y) {
-    ++spmvs;
-    ++launches;
-    return launch_spmv(G->A, x, y, 0, s);
-  }
-  // out = T2^-1 (d_mid (.) (T1^-1 in)), or the AMG cycle of `in`; called only when a part is set.  The solves and the
-  // cycle do not read the status block: they write `out` and their own vectors only, which nothing reads once the flag
-  // `stop` of the kernels around them is set
-  int apply(const double *in, double *out, const int *stop) {
-    ++applications;
-    if (G->amg) {
-      int64_t enqueued = 0;
-      const int e = amg_apply(G->amg, in, out, s, &enqueued);
-      launches += enqueued;
-      return e;
-    }
-    const double *cur = in;
-    int64_t info[8];
-    if (G->T1) {
-      const int e = trisolve_solve(G->T1, SPL_OP_n, 1, cur, n, out, n, s);
-      if (e != SPL_OK) return e;
-      trisolve_info(G->T1, info);
-      launches += info[3];
-      cur = out;
-    }
-    if (G->d_mid) {
-      hipLaunchKernelGGL((diag_kernel<VW>), dim3(flat), dim3(kLanes), 0, s, stop, n, G->d_mid, cur, out);
-      ++launches;
-      cur = out;
-    }
-    if (G->T2) {
-      const int e = trisolve_solve(G->T2, SPL_OP_n, 1, cur, n, out, n, s);
-      if (e != SPL_OK) return e;
-      trisolve_info(G->T2, info);
-      launches += info[3];
-    }
-    return SPL_OK;
-  }
+  const GStatus &look() { return LinearRun::look(G->status); }
 
   // r = b - A x to v_0, its norm, the checks, v_0 = r / beta
   int cycle_start(const double *b, double *x, bool first, int use_x0) {
@@ -413,7 +321,7 @@ struct GRun {
                          basis(0), scratch, chunks_of(n));
     const Partials P = middle_levels(done(), n, (first ? 2 : 1) * VW, scratch, s);
     hipLaunchKernelGGL((start_kernel<VW>), dim3(1), dim3(kLanes), 0, s, st, first ? 1 : 0, P.p, P.stride, P.count, rtol,
-                       atol, max_iter, hist, T.g);
+                       atol, max_iter, hist.get(), T.g);
     hipLaunchKernelGGL(divide_kernel, dim3(flat), dim3(kLanes), 0, s, (const GStatus *)st, n * VW,
                        (const double *)&st->scale, basis(0));
     launches += P.middle + 3;
@@ -423,30 +331,24 @@ struct GRun {
   int step(int j) {
     const double *z = basis(j);
     int e;
-    if (G->preconditioned()) {
-      if ((e = apply(basis(j), mu(), skip())) != SPL_OK) return e;
+    if (pre.set()) {
+      if ((e = apply<VW>(basis(j), mu(), skip())) != SPL_OK) return e;
       z = mu();
     }
     double *w = basis(j + 1);
     if ((e = spmv(z, w)) != SPL_OK) return e;
-    launches += dots_launch<VW>(skip(), n, j + 1, basis(0), n, w, T.c1, scratch, s);
-    hipLaunchKernelGGL((update_kernel<VW, false>), dim3(chunked), dim3(kLanes), 0, s, skip(), n, j + 1,
-                       (const double *)basis(0), n, (const double *)T.c1, w, scratch);
-    launches += dots_launch<VW>(skip(), n, j + 1, basis(0), n, w, T.c2, scratch, s);
-    hipLaunchKernelGGL((update_kernel<VW, true>), dim3(chunked), dim3(kLanes), 0, s, skip(), n, j + 1,
-                       (const double *)basis(0), n, (const double *)T.c2, w, scratch);
-    const Partials P = middle_levels(skip(), n, 1, scratch, s);
-    hipLaunchKernelGGL((step_kernel<VW>), dim3(1), dim3(kLanes), 0, s, st, j, m, P.p, P.count, T, max_iter, hist);
+    const Partials P = orthogonalise_twice<VW>(skip(), n, j + 1, basis(0), w, T.c1, T.c2, scratch, chunked, s, &launches);
+    hipLaunchKernelGGL((step_kernel<VW>), dim3(1), dim3(kLanes), 0, s, st, j, m, P.p, P.count, T, max_iter, hist.get());
     hipLaunchKernelGGL(divide_kernel, dim3(flat), dim3(kLanes), 0, s, (const GStatus *)st, n * VW,
                        (const double *)&st->scale, w);
-    launches += P.middle + 4;
+    launches += 2;
     return SPL_OK;
   }
 
   int close(double *x) {
     hipLaunchKernelGGL((solve_kernel<VW>), dim3(1), dim3(64), 0, s, (const GStatus *)st, m, T);
     ++launches;
-    if (!G->preconditioned()) {
+    if (!pre.set()) {
       hipLaunchKernelGGL((combine_kernel<VW>), dim3(flat), dim3(kLanes), 0, s, (const GStatus *)st, n,
                          (const double *)basis(0), n, (const double *)T.y, (double *)nullptr, x);
       ++launches;
@@ -454,49 +356,18 @@ struct GRun {
     }
     hipLaunchKernelGGL((combine_kernel<VW>), dim3(flat), dim3(kLanes), 0, s, (const GStatus *)st, n,
                        (const double *)basis(0), n, (const double *)T.y, u(), (double *)nullptr);
-    const int e = apply(u(), mu(), done());
+    const int e = apply<VW>(u(), mu(), done());
     if (e != SPL_OK) return e;
     hipLaunchKernelGGL((add_kernel<VW>), dim3(flat), dim3(kLanes), 0, s, (const GStatus *)st, n, (const double *)mu(), x);
     launches += 2;
     return SPL_OK;
   }
 
-  // Room for `entries` values of the device history, of which `written` may be written already.  Called before the
-  // first launch and right after a look, when s is idle: the history grows with the iterations that were issued
-  void room_for(long long entries, long long written) {
-    if (!hist_wanted) return;
-    if (entries > max_iter + 1) entries = max_iter + 1;
-    if ((long long)G->hist.n < entries) {
-      long long want = 2 * (long long)G->hist.n > entries ? 2 * (long long)G->hist.n : entries;
-      if (want < 64) want = 64;
-      if (want > max_iter + 1) want = max_iter + 1;
-      DBuf<double> bigger((size_t)want);
-      if (written > 0) {
-        SPL_HIP(hipMemcpyAsync(bigger.get(), G->hist.get(), (size_t)written * sizeof(double), hipMemcpyDeviceToDevice, s));
-        SPL_HIP(hipStreamSynchronize(s));  // the old block goes back to the pool on the next line
-      }
-      G->hist = std::move(bigger);
-    }
-    hist = G->hist.get();
-  }
-  const GStatus &look() {
-    SPL_HIP(hipMemcpyAsync(G->pinned, st, sizeof(GStatus), hipMemcpyDeviceToHost, s));
-    SPL_HIP(hipStreamSynchronize(s));
-    return *G->pinned;
-  }
-  int launch_status(const char *where) {
-    const hipError_t e = hipGetLastError();
-    if (e == hipSuccess) return SPL_OK;
-    set_last_error(where, e);
-    (void)hipStreamSynchronize(s);
-    return SPL_ERROR_device;
-  }
-
   int solve(const double *b, double *x, int use_x0, int check_every, GStatus *last) {
     const long long every = check_every > 0 ? check_every : 1;
     int e;
     SPL_HIP(hipMemsetAsync(st, 0, sizeof(GStatus), s));
-    room_for(every * m + 1, 0);
+    room_for(hist, every * m + 1, 0, max_iter);
     if ((e = cycle_start(b, x, true, use_x0)) != SPL_OK) return e;
     if ((e = launch_status("gmres start")) != SPL_OK) return e;
     // One look before the first cycle: a start that is already good enough (or not finite) costs no cycle issued for
@@ -513,7 +384,7 @@ struct GRun {
       if (issued % every == 0) {
         const GStatus &now = look();
         if (now.done) break;
-        room_for(now.it + every * m + 1, now.it + 1);
+        room_for(hist, now.it + every * m + 1, now.it + 1, max_iter);
       }
     }
     *last = look();
@@ -541,7 +412,7 @@ int solve_width(Gmres *G, const double *d_b, double *d_x, int use_x0, double rto
   residual[0] = last.res0;
   residual[1] = last.res1;
   if (history) {
-    SPL_HIP(hipMemcpyAsync(history, run.hist, ((size_t)last.it + 1) * sizeof(double), hipMemcpyDeviceToHost, s));
+    SPL_HIP(hipMemcpyAsync(history, run.hist.get(), ((size_t)last.it + 1) * sizeof(double), hipMemcpyDeviceToHost, s));
     SPL_HIP(hipStreamSynchronize(s));
   }
   G->last_iterations = last.it;
@@ -565,7 +436,7 @@ void gmres_info(Gmres *G, int64_t info[8]) {
   std::lock_guard<std::mutex> hold(G->lock);
   info[0] = G->n;
   info[1] = G->restart;
-  info[2] = (G->vw == 2 ? 1 : 0) | (G->T1 ? 2 : 0) | (G->d_mid ? 4 : 0) | (G->T2 ? 8 : 0) | (G->amg ? 16 : 0);
+  info[2] = (G->vw == 2 ? 1 : 0) | G->pre.flags();
   info[3] = (int64_t)G->bytes;
   info[4] = G->solves;
   info[5] = G->last_iterations;
@@ -573,14 +444,6 @@ void gmres_info(Gmres *G, int64_t info[8]) {
   info[7] = 0;
 }
 
-int gmres_device(const Gmres *G) { return G->device; }
-int64_t gmres_rows(const Gmres *G) { return G->n; }
-int gmres_width(const Gmres *G) { return G->vw; }
-
-void gmres_delete(Gmres *G) {
-  G->magic = 0;
-  if (G->pinned) (void)hipHostFree(G->pinned);
-  delete G;
-}
+void gmres_delete(Gmres *G) { delete_object(G); }
 
 }  // namespace spl

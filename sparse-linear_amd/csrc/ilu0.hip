@@ -30,8 +30,6 @@
 
 namespace spl {
 
-constexpr uint32_t kIluMagic = 0x53504C49u;  // "SPLI"
-
 namespace {
 
 // The analysed pattern in device memory; rows in their original places, reached through the level order
@@ -135,10 +133,8 @@ void upload_ints(DBuf<T> &dst, const std::vector<T> &src, hipStream_t s, size_t 
 
 }  // namespace
 
-struct IluPlan {
-  uint32_t magic = kIluMagic;
-  int device = 0;
-  int n = 0;
+struct IluPlan : ObjectHead {  // no values: vw stays 1
+  IluPlan() : ObjectHead(kIluMagic) {}
   int64_t nnz = 0, missing = 0, longest = 0;
   int nlevels = 0;
   std::vector<tri::Segment> segments;  // host: the launch plan
@@ -148,11 +144,6 @@ struct IluPlan {
   IluView view() const { return IluView{rows.get(), ptr.get(), col.get(), diag.get(), upper.get(), level_ptr.get()}; }
 };
 
-IluPlan *as_ilu_plan(void *p) {
-  IluPlan *P = static_cast<IluPlan *>(p);
-  return (P && P->magic == kIluMagic) ? P : nullptr;
-}
-
 // A is whole, square, with 32-bit row pointers: checked by the caller.  Synchronises.
 int ilu0_analyze(const Matrix *A, IluPlan **out) {
   hipStream_t s = nullptr;
@@ -160,7 +151,7 @@ int ilu0_analyze(const Matrix *A, IluPlan **out) {
   P->device = A->device;
   P->n = (int)A->nrows_local;
   P->nnz = A->nnz;
-  const int n = P->n;
+  const int n = (int)P->n;
   // the pattern, once
   std::vector<int> rowptr((size_t)n + 1, 0), colidx((size_t)A->nnz);
   if (n > 0) SPL_HIP(hipMemcpyAsync(rowptr.data(), A->rowptr.get(), ((size_t)n + 1) * sizeof(int), hipMemcpyDeviceToHost, s));
@@ -277,11 +268,6 @@ void ilu0_info(const IluPlan *P, int64_t info[8]) {
   info[7] = P->factorisations.load(std::memory_order_relaxed);
 }
 
-int ilu0_device(const IluPlan *P) { return P->device; }
-
-void ilu0_delete(IluPlan *P) {
-  P->magic = 0;
-  delete P;
-}
+void ilu0_delete(IluPlan *P) { delete_object(P); }
 
 }  // namespace spl

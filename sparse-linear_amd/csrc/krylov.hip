@@ -24,11 +24,9 @@
 #include <mutex>
 #include <utility>
 
-#include "krylov_fold.hpp"
+#include "solver_core.hpp"
 
 namespace spl {
-
-constexpr uint32_t kKrylovMagic = 0x53504C4Bu;  // "SPLK"
 
 namespace {
 
@@ -281,16 +279,6 @@ __global__ __launch_bounds__(kLanes) void bicg_full_kernel(const Status *st, int
   });
 }
 
-// out = d (.) in, entry by entry; in may be out
-template <int VW>
-__global__ __launch_bounds__(kLanes) void diag_scale_kernel(const Status *st, int64_t n, const double *d, const double *in,
-                                                            double *out) {
-  if (st->done) return;
-  int64_t i = (int64_t)blockIdx.x * kLanes + threadIdx.x;
-  const int64_t stride = (int64_t)gridDim.x * kLanes;
-  for (; i < n; i += stride) store_val(out, i, mul(load_val<VW>(d, i), load_val<VW>(in, i)));
-}
-
 // Scratch of spl_vector_dot_dev: a block from the device pool PER CALL, so two calls never share partials, from whatever
 // threads and on whatever streams they come.  A call takes a block whose previous user has finished on the device (an
 // event recorded behind that user's last kernel says so), or a new one; it records its own event behind its last kernel
@@ -392,98 +380,55 @@ int vector_dot(int device, int64_t n, int vw, const double *d_a, const double *d
   return SPL_OK;
 }
 
-// ---- the solver object -------------------------------------------------------------------------------------------------
-struct Krylov {
-  uint32_t magic = kKrylovMagic;
-  int device = 0;
-  int method = SPL_KRYLOV_cg;
-  int vw = 1;
-  int64_t n = 0;
-  const Matrix *A = nullptr;                 // borrowed
-  TriSolver *T1 = nullptr, *T2 = nullptr;    // borrowed
-  const double *d_mid = nullptr;             // borrowed
-  Amg *amg = nullptr;                        // borrowed; set: the three parts above are not
-  int nvec = 0;
-  DBuf<double> work;     // nvec vectors
-  DBuf<double> scratch;  // partials of the fold
-  DBuf<double> hist;     // |r|^2 of every iteration, grown with the iterations issued (Run::room_for)
-  DBuf<Status> status;
-  Status *pinned = nullptr;
-  size_t bytes = 0;
-  std::mutex lock;       // one solve at a time
-  int64_t solves = 0, last_iterations = 0, last_launches = 0;
-  double *vec(int i) const { return work.get() + (size_t)i * (size_t)n * (size_t)vw; }
-  bool preconditioned() const { return T1 || T2 || d_mid || amg; }
+// ---- the solver object (the shared part: solver_core.hpp) ---------------------------------------------------------------
+struct Krylov : SolverCore {
+  int method;
+  Preconditioner pre;
+  DBuf<double> hist;  // |r|^2 of every iteration, grown with the iterations issued (room_for)
+  StatusBlock<Status> status;
+  int64_t last_iterations = 0;
+  Krylov(const Matrix *A, int m)
+      : SolverCore(kKrylovMagic, A, m == SPL_KRYLOV_cg ? 4 : 8, fold_scratch(A->nrows_local, kMaxPlanes)), method(m) {
+    bytes += sizeof(Status);
+  }
 };
-
-Krylov *as_krylov(void *k) {
-  Krylov *K = static_cast<Krylov *>(k);
-  return (K && K->magic == kKrylovMagic) ? K : nullptr;
-}
 
 // A: whole and square (the caller checked)
 int krylov_create(const Matrix *A, int method, Krylov **out) {
-  std::unique_ptr<Krylov> K(new Krylov);
-  K->device = A->device;
-  K->method = method;
-  K->vw = A->vw;
-  K->n = A->nrows_local;
-  K->A = A;
-  K->nvec = method == SPL_KRYLOV_cg ? 4 : 8;
-  const size_t vec_doubles = (size_t)K->n * (size_t)K->vw;
-  K->work.alloc((size_t)K->nvec * vec_doubles);
-  const size_t scratch = fold_scratch(K->n, kMaxPlanes);
-  K->scratch.alloc(scratch);
-  K->status.alloc(1);
-  SPL_HIP(hipHostMalloc(reinterpret_cast<void **>(&K->pinned), sizeof(Status), hipHostMallocDefault));
-  K->bytes = ((size_t)K->nvec * vec_doubles + scratch) * sizeof(double) + sizeof(Status);
-  *out = K.release();
+  *out = new Krylov(A, method);
   return SPL_OK;
 }
 
 void krylov_set_preconditioner(Krylov *K, TriSolver *T1, const double *d_mid, TriSolver *T2) {
   std::lock_guard<std::mutex> hold(K->lock);
-  K->T1 = T1;
-  K->d_mid = d_mid;
-  K->T2 = T2;
-  K->amg = nullptr;
+  K->pre.set_parts(T1, d_mid, T2);
 }
 
 void krylov_set_preconditioner_amg(Krylov *K, Amg *M) {
   std::lock_guard<std::mutex> hold(K->lock);
-  K->T1 = K->T2 = nullptr;
-  K->d_mid = nullptr;
-  K->amg = M;
+  K->pre.set_amg(M);
 }
 
 namespace {
 
 // One solve's launches; everything is enqueued on s
 template <int VW>
-struct Run {
+struct Run : LinearRun {
   Krylov *K;
-  hipStream_t s;
-  double rtol, atol;
-  long long max_iter;
-  bool hist_wanted;
-  double *hist = nullptr;
-  int64_t n;
   Status *st;
-  double *scratch;
-  unsigned flat, chunked;
-  int64_t spmvs = 0, applications = 0, launches = 0;
 
   Run(Krylov *k, hipStream_t stream, double rt, double at, long long mi, bool history)
-      : K(k), s(stream), rtol(rt), atol(at), max_iter(mi), hist_wanted(history), n(k->n), st(k->status.get()),
-        scratch(k->scratch.get()), flat(grid_flat(k->n, 4096)), chunked(chunk_grid(k->n)) {}
+      : LinearRun(*k, k->pre, k->hist, stream, rt, at, mi, history), K(k), st(k->status.device.get()) {}
 
   int64_t stride() const { return chunks_of(n); }
+  // the preconditioner's diagonal returns on `done`, as every vector kernel of this file does
+  int apply(const double *in, double *out) { return LinearRun::apply<VW>(in, out, done_flag(st)); }
 
   void scalar(int stage, int first, int dots) {
     const Partials P = middle_levels(done_flag(st), n, dots * VW, scratch, s);
     launches += P.middle + 1;
     hipLaunchKernelGGL((scalar_kernel<VW>), dim3(1), dim3(kLanes), 0, s, st, stage, first, P.p, P.stride, P.count,
-                       dots * VW, rtol, atol, max_iter, hist, (double *)nullptr);
+                       dots * VW, rtol, atol, max_iter, hist.get(), (double *)nullptr);
   }
   void dot(int stage, int first, const double *a, const double *b) {
     hipLaunchKernelGGL((dot_kernel<VW, 1>), dim3(chunked), dim3(kLanes), 0, s, (const Status *)st, n, a, b, a, b, scratch,
@@ -497,43 +442,6 @@ struct Run {
     ++launches;
     scalar(stage, 0, 2);
   }
-  int spmv(const double *x, double *y) {
-    ++spmvs;
-    ++launches;
-    return launch_spmv(K->A, x, y, 0, s);
-  }
-  // out = T2^-1 (d_mid (.) (T1^-1 in)), or the AMG cycle of `in`; called only when a part is set.  The cycle's
-  // kernels do not read `done`: they write `out` and the AMG object's own vectors only, which nothing reads once it is set
-  int apply(const double *in, double *out) {
-    ++applications;
-    if (K->amg) {
-      int64_t enqueued = 0;
-      const int e = amg_apply(K->amg, in, out, s, &enqueued);
-      launches += enqueued;
-      return e;
-    }
-    const double *cur = in;
-    int64_t info[8];
-    if (K->T1) {
-      const int e = trisolve_solve(K->T1, SPL_OP_n, 1, cur, n, out, n, s);
-      if (e != SPL_OK) return e;
-      trisolve_info(K->T1, info);
-      launches += info[3];
-      cur = out;
-    }
-    if (K->d_mid) {
-      hipLaunchKernelGGL((diag_scale_kernel<VW>), dim3(flat), dim3(kLanes), 0, s, (const Status *)st, n, K->d_mid, cur, out);
-      ++launches;
-      cur = out;
-    }
-    if (K->T2) {
-      const int e = trisolve_solve(K->T2, SPL_OP_n, 1, cur, n, out, n, s);
-      if (e != SPL_OK) return e;
-      trisolve_info(K->T2, info);
-      launches += info[3];
-    }
-    return SPL_OK;
-  }
   // r = b - A x (use_x0) or r = b, x = 0; the threshold and the checks of iteration 0.  q: room for A x
   int start(const double *b, double *x, int use_x0, double *q, double *r, double *rhat, int stage = kStageInit) {
     SPL_HIP(hipMemsetAsync(st, 0, sizeof(Status), s));
@@ -546,37 +454,8 @@ struct Run {
     scalar(stage, 0, 2);
     return SPL_OK;
   }
-  // Room for `entries` values of the device history, of which `written` may be written already.  Called before the
-  // first launch and right after a look, when s is idle: the history grows with the iterations that were issued, in
-  // steps of a check interval at least and by doubling, never with max_iter
-  void room_for(long long entries, long long written) {
-    if (!hist_wanted) return;
-    if ((long long)K->hist.n < entries) {
-      long long want = 2 * (long long)K->hist.n > entries ? 2 * (long long)K->hist.n : entries;
-      if (want < 64) want = 64;
-      if (want > max_iter + 1) want = max_iter + 1;
-      DBuf<double> bigger((size_t)want);
-      if (written > 0) {
-        SPL_HIP(hipMemcpyAsync(bigger.get(), K->hist.get(), (size_t)written * sizeof(double), hipMemcpyDeviceToDevice, s));
-        SPL_HIP(hipStreamSynchronize(s));  // the old block goes back to the pool on the next line
-      }
-      K->hist = std::move(bigger);
-    }
-    hist = K->hist.get();
-  }
   long long batch_end(long long issued, int every) const { return issued + every < max_iter ? issued + every : max_iter; }
-  const Status &look() {
-    SPL_HIP(hipMemcpyAsync(K->pinned, st, sizeof(Status), hipMemcpyDeviceToHost, s));
-    SPL_HIP(hipStreamSynchronize(s));
-    return *K->pinned;
-  }
-  int launch_status(const char *where) {
-    const hipError_t e = hipGetLastError();
-    if (e == hipSuccess) return SPL_OK;
-    set_last_error(where, e);
-    (void)hipStreamSynchronize(s);
-    return SPL_ERROR_device;
-  }
+  const Status &look() { return LinearRun::look(K->status); }
 
   int cg_iteration(double *x, double *r, double *z, double *p, double *q) {
     int e = spmv(p, q);
@@ -585,7 +464,7 @@ struct Run {
     hipLaunchKernelGGL((cg_update_kernel<VW>), dim3(chunked), dim3(kLanes), 0, s, (const Status *)st, n, p, q, x, r, scratch,
                        stride());
     ++launches;
-    if (K->preconditioned()) {
+    if (pre.set()) {
       scalar(kStageResidual, 0, 1);
       if ((e = apply(r, z)) != SPL_OK) return e;
       dot(kStageCgRho, 0, r, z);
@@ -603,14 +482,14 @@ struct Run {
     hipLaunchKernelGGL((bicg_direction_kernel<VW>), dim3(flat), dim3(kLanes), 0, s, (const Status *)st, n, first, r, v, p);
     ++launches;
     int e;
-    if (K->preconditioned() && (e = apply(p, y)) != SPL_OK) return e;
+    if (pre.set() && (e = apply(p, y)) != SPL_OK) return e;
     if ((e = spmv(y, v)) != SPL_OK) return e;
     dot(kStageBiAlpha, 0, rhat, v);
     hipLaunchKernelGGL((bicg_half_kernel<VW>), dim3(chunked), dim3(kLanes), 0, s, (const Status *)st, n, r, v, y, sv, x,
                        scratch, stride());
     ++launches;
     scalar(kStageBiHalf, 0, 1);
-    if (K->preconditioned() && (e = apply(sv, z)) != SPL_OK) return e;
+    if (pre.set() && (e = apply(sv, z)) != SPL_OK) return e;
     if ((e = spmv(z, t)) != SPL_OK) return e;
     dot2(kStageBiOmega, t, sv, t, t);
     hipLaunchKernelGGL((bicg_full_kernel<VW>), dim3(chunked), dim3(kLanes), 0, s, (const Status *)st, n, sv, z, t, x, r,
@@ -622,10 +501,10 @@ struct Run {
 
   int solve(const double *b, double *x, int use_x0, int check_every, Status *last) {
     const int every = check_every > 0 ? check_every : kDefaultCheckEvery;
-    const bool pre = K->preconditioned();
+    const bool pre = this->pre.set();
     int e;
     int64_t per_iteration = 0;
-    room_for(batch_end(0, every) + 1, 0);
+    room_for(hist, batch_end(0, every) + 1, 0, max_iter);
     if (K->method == SPL_KRYLOV_cg) {
       double *r = K->vec(0), *z = pre ? K->vec(1) : r, *p = K->vec(2), *q = K->vec(3);
       if ((e = start(b, x, use_x0, q, r, nullptr, pre ? kStageInit : kStageInitRho)) != SPL_OK) return e;
@@ -636,7 +515,7 @@ struct Run {
       hipLaunchKernelGGL((cg_direction_kernel<VW>), dim3(flat), dim3(kLanes), 0, s, (const Status *)st, n, 1, z, p);
       if ((e = launch_status("krylov cg start")) != SPL_OK) return e;
       for (long long issued = 0; issued < max_iter;) {
-        if (issued % every == 0) room_for(batch_end(issued, every) + 1, issued + 1);
+        if (issued % every == 0) room_for(hist, batch_end(issued, every) + 1, issued + 1, max_iter);
         const int64_t before = launches;
         if ((e = cg_iteration(x, r, z, p, q)) != SPL_OK) return e;
         per_iteration = launches - before;
@@ -649,7 +528,7 @@ struct Run {
       if ((e = start(b, x, use_x0, v, r, rhat)) != SPL_OK) return e;
       if ((e = launch_status("krylov bicgstab start")) != SPL_OK) return e;
       for (long long issued = 0; issued < max_iter;) {
-        if (issued % every == 0) room_for(batch_end(issued, every) + 1, issued + 1);
+        if (issued % every == 0) room_for(hist, batch_end(issued, every) + 1, issued + 1, max_iter);
         const int64_t before = launches;
         if ((e = bicgstab_iteration(issued == 0, x, r, rhat, p, v, y, sv, z, t)) != SPL_OK) return e;
         per_iteration = launches - before;
@@ -679,7 +558,7 @@ int solve_width(Krylov *K, const double *d_b, double *d_x, int use_x0, double rt
   result[2] = run.spmvs;
   result[3] = run.applications;
   if (history) {
-    SPL_HIP(hipMemcpyAsync(history, run.hist, ((size_t)last.it + 1) * sizeof(double), hipMemcpyDeviceToHost, s));
+    SPL_HIP(hipMemcpyAsync(history, run.hist.get(), ((size_t)last.it + 1) * sizeof(double), hipMemcpyDeviceToHost, s));
     SPL_HIP(hipStreamSynchronize(s));
     for (long long i = 0; i <= last.it; ++i) history[i] = sqrt(history[i]);  // |r|^2 came down: the norm is its root
   }
@@ -702,7 +581,7 @@ void krylov_info(Krylov *K, int64_t info[8]) {
   std::lock_guard<std::mutex> hold(K->lock);
   info[0] = K->n;
   info[1] = K->method;
-  info[2] = (K->vw == 2 ? 1 : 0) | (K->T1 ? 2 : 0) | (K->d_mid ? 4 : 0) | (K->T2 ? 8 : 0) | (K->amg ? 16 : 0);
+  info[2] = (K->vw == 2 ? 1 : 0) | K->pre.flags();
   info[3] = (int64_t)K->bytes;
   info[4] = K->solves;
   info[5] = K->last_iterations;
@@ -710,14 +589,6 @@ void krylov_info(Krylov *K, int64_t info[8]) {
   info[7] = 0;
 }
 
-int krylov_device(const Krylov *K) { return K->device; }
-int64_t krylov_rows(const Krylov *K) { return K->n; }
-int krylov_width(const Krylov *K) { return K->vw; }
-
-void krylov_delete(Krylov *K) {
-  K->magic = 0;
-  if (K->pinned) (void)hipHostFree(K->pinned);
-  delete K;
-}
+void krylov_delete(Krylov *K) { delete_object(K); }
 
 }  // namespace spl

@@ -137,5 +137,23 @@ __global__ __launch_bounds__(kLanes) void update_kernel(const int *stop, int64_t
   }
 }
 
+// ---- the launches of a step --------------------------------------------------------------------------------------------
+// Classical Gram-Schmidt done twice of w against the first k columns of V (leading dimension n): the coefficients of
+// the passes to c1 and c2 (k entries each), the partials of <w,w> of the result folded until the last level is left.
+// *launches grows by the kernels.  n > 0
+template <int VW>
+Partials orthogonalise_twice(const int *stop, int64_t n, int k, const double *V, double *w, double *c1, double *c2,
+                             double *scratch, unsigned chunked, hipStream_t s, int64_t *launches) {
+  *launches += dots_launch<VW>(stop, n, k, V, n, w, c1, scratch, s);
+  hipLaunchKernelGGL((update_kernel<VW, false>), dim3(chunked), dim3(kLanes), 0, s, stop, n, k, V, n, (const double *)c1, w,
+                     scratch);
+  *launches += dots_launch<VW>(stop, n, k, V, n, w, c2, scratch, s);
+  hipLaunchKernelGGL((update_kernel<VW, true>), dim3(chunked), dim3(kLanes), 0, s, stop, n, k, V, n, (const double *)c2, w,
+                     scratch);
+  const Partials P = middle_levels(stop, n, 1, scratch, s);
+  *launches += P.middle + 2;
+  return P;
+}
+
 }  // namespace
 }  // namespace spl

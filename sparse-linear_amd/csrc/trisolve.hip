@@ -29,8 +29,6 @@
 
 namespace spl {
 
-constexpr uint32_t kTriMagic = 0x53504C54u;  // "SPLT"
-
 namespace {
 
 constexpr int kTriGroupCols = 8;  // right-hand sides one pass of the launch chain takes (kSolveGroup of the LU solves)
@@ -209,23 +207,15 @@ void build_image(TriImage &img, int n, int vw, bool lower, bool unit, const tri:
 
 }  // namespace
 
-struct TriSolver {
-  uint32_t magic = kTriMagic;
-  int device = 0;
-  int n = 0, vw = 1;
+struct TriSolver : ObjectHead {
   bool upper = false, unit = false;
   tri::Knobs knobs;
   int64_t stored = 0, longest = 0, zero_diag = 0;
   TriImage img[3];                 // SPL_OP_n, _t, _h; real: _h is _t's
   std::atomic<bool> built[3];
   std::mutex lock;                 // the lazy build of the transposed images
-  TriSolver() { for (auto &b : built) b.store(false); }
+  TriSolver() : ObjectHead(kTriMagic) { for (auto &b : built) b.store(false); }
 };
-
-TriSolver *as_trisolver(void *t) {
-  TriSolver *T = static_cast<TriSolver *>(t);
-  return (T && T->magic == kTriMagic) ? T : nullptr;
-}
 
 // A is whole, square, with 32-bit row pointers: checked by the caller.  Returns SPL_OK or SPL_WARNING_singular_matrix.
 int trisolve_analyze(const Matrix *A, int uplo, int diag, TriSolver **out) {
@@ -237,7 +227,7 @@ int trisolve_analyze(const Matrix *A, int uplo, int diag, TriSolver **out) {
   T->upper = uplo == SPL_TRI_upper;
   T->unit = diag == SPL_DIAG_unit;
   T->knobs = tri::read_knobs();
-  const int n = T->n;
+  const int n = (int)T->n;
   // the pattern, once
   std::vector<int> rowptr((size_t)n + 1, 0), colidx((size_t)A->nnz);
   if (n > 0) SPL_HIP(hipMemcpyAsync(rowptr.data(), A->rowptr.get(), ((size_t)n + 1) * sizeof(int), hipMemcpyDeviceToHost, s));
@@ -277,7 +267,7 @@ namespace {
 void build_transposed(TriSolver *T, int slot, bool conj) {
   hipStream_t s = nullptr;
   const TriImage &N = T->img[0];
-  const int n = T->n;
+  const int n = (int)T->n;
   std::vector<int> pptr((size_t)n + 1, 0);
   if (n > 0) SPL_HIP(hipMemcpyAsync(pptr.data(), N.ptr.get(), ((size_t)n + 1) * sizeof(int), hipMemcpyDeviceToHost, s));
   SPL_HIP(hipStreamSynchronize(s));
@@ -354,13 +344,6 @@ void trisolve_info(const TriSolver *T, int64_t info[8]) {
   info[7] = (T->vw == 2 ? 1 : 0) | (T->upper ? 2 : 0) | (T->unit ? 4 : 0) | (transposed ? 8 : 0);
 }
 
-int trisolve_device(const TriSolver *T) { return T->device; }
-int trisolve_rows(const TriSolver *T) { return T->n; }
-int trisolve_width(const TriSolver *T) { return T->vw; }
-
-void trisolve_delete(TriSolver *T) {
-  T->magic = 0;
-  delete T;
-}
+void trisolve_delete(TriSolver *T) { delete_object(T); }
 
 }  // namespace spl
