@@ -963,6 +963,31 @@ int spl_gmres_solve(void *G, const double *b, double *x, int use_x0, double rtol
 int spl_gmres_info(void *G, int64_t info[8]);
 void spl_gmres_free(void **G);
 
+/* ---- a block of inner products in one pass (csrc/gram.hip) --------------------------------------------------------------
+ * spl_vector_gram_dev: G[i][j] = <V[:, i], W[:, j]>, i = 0 ... k - 1, j = 0 ... l - 1, of n entries of value_width
+ *   doubles each, all in DEVICE memory (complex: packed pairs, conjugate on the left).  V and W are column blocks in the
+ *   layout of spl_vector_dots_dev: column i of V at d_V + i * ldv * value_width doubles, ldv >= n, column j of W at
+ *   d_W + j * ldw * value_width, ldw >= n; they may be the same block.  G is column major, entry (i, j) at
+ *   d_G + (j * ldg + i) * value_width doubles, ldg >= k.  upper == 1 writes only the entries with i <= j and leaves the
+ *   rest of G untouched (the Hermitian use, V == W: the caller mirrors with conjugates); the gaps of a padded ldg are
+ *   never written.  Every entry is BIT FOR BIT what spl_vector_dot_dev(n, value_width, V[:, i], W[:, j], ...) writes:
+ *   the same chunks of 4096, lane t of 256 adding its 16 products in ascending order from +0.0, the halving tree and
+ *   the fold of partials, every product rounded on its own; no floating-point atomic, and no kernel waits for another
+ *   workgroup.  What makes it one pass: a workgroup takes a chunk and a tile of columns of W, each lane keeps its 16
+ *   entries of those columns in registers and the columns of V stream past them, so V is read once per tile and not
+ *   once per column of W.  The tile (SPL_GRAM_TILE = 1, 2 or 4 columns of W, for measurement; default 4 real, 2
+ *   complex), SPL_KRYLOV_GRID and the placement of workgroups do not show in the bits.  The partials are a pool block
+ *   per call; a call whose partials would exceed 64 MiB is cut into blocks of columns inside the entry point, so the
+ *   scratch is at most max(64 MiB, n / 16 bytes) plus one middle level.  (SPL_GRAM_SCRATCH = bytes is a TEST HOOK and
+ *   no tuning knob: it replaces the 64 MiB by any positive number, down to 1, so that the tests reach the cut at a few
+ *   thousand rows; it does not show in the bits either.)  Enqueued on `stream`, no synchronisation.
+ *   1 <= k, l <= 128; n == 0 writes +0.0 to every entry it would write.  Errors, in this order: n < 0
+ *   SPL_ERROR_n_nonpositive; value_width not 1 or 2; k or l outside 1 ... 128, upper not 0 or 1, ldv < n, ldw < n,
+ *   ldg < k; a NULL pointer (d_V and d_W only when n > 0); a pointer not aligned to an entry; G overlapping V or W
+ *   (n > 0): SPL_ERROR_argument_missing. */
+int spl_vector_gram_dev(int64_t n, int value_width, int k, int l, const double *d_V, int64_t ldv, const double *d_W,
+                        int64_t ldw, double *d_G, int64_t ldg, int upper, void *stream);
+
 /* ---- thick-restart Lanczos on handles and the in-place basis rotation (csrc/eigsh.hip) ---------------------------------
  * A few eigenpairs of a real symmetric or complex Hermitian handle without a factorisation: restarted Lanczos with full
  * reorthogonalisation and thick restarts (Wu & Simon's TRLan scheme), directly on A for the ends of the spectrum, or on
@@ -1056,12 +1081,23 @@ void spl_gmres_free(void **G);
  * spl_eigsh_info: [0] n, [1] ncv, [2] flags (1 complex, 2 inverse mode), [3] bytes of device memory, [4] solves,
  *   [5] cycles of the last solve, [6] launches of the last solve (the SpMV counted as one, inner solves not counted),
  *   [7] 0.
- * spl_eigsh_free: idempotent, as spl_krylov_free. */
+ * spl_eigsh_free: idempotent, as spl_krylov_free.
+ *
+ * spl_vector_rotate_z_dev: spl_vector_rotate_dev with a COMPLEX Y, for a block method's projected matrix on a complex
+ *   Hermitian handle.  value_width must be 2.  Y is m x k packed pairs in DEVICE memory, column major, Y[l][i] at
+ *   d_Y + 2 * (i * ldy + l) doubles, ldy >= m.  Column i of the result is x = Y[0][i] v_0; x = x + Y[l][i] v_l for
+ *   l = 1 ... m - 1 ascending, where the product of Y[l][i] = a + b i and an entry c + d i is Data.Complex's,
+ *   (a c - b d, a d + b c): four products, one difference and one sum, each rounded once; then one sum per part.
+ *   Everything else is spl_vector_rotate_dev's: the in-place guarantee with d_out == NULL, the tile in LDS, the knobs
+ *   that do not show, n == 0, and the errors in the same order, with "value_width not 2" where "not 1 or 2" comes there.
+ *   spl_vector_rotate_dev itself is unchanged. */
 #define SPL_EIGSH_largest_algebraic 0
 #define SPL_EIGSH_smallest_algebraic 1
 #define SPL_EIGSH_largest_magnitude 2
 int spl_vector_rotate_dev(int64_t n, int value_width, int m, int k, double *d_V, int64_t ldv, const double *d_Y, int ldy,
                           double *d_out, int64_t ldo, void *stream);
+int spl_vector_rotate_z_dev(int64_t n, int value_width, int m, int k, double *d_V, int64_t ldv, const double *d_Y, int ldy,
+                            double *d_out, int64_t ldo, void *stream);
 int spl_eigsh_create(void *A, int ncv, void **E);
 int spl_eigsh_set_inverse(void *E, void *K, double sigma, double rtol, double atol, int64_t max_iter);
 int spl_eigsh_solve_dev(void *E, int nev, int which, double tol, double atol, int64_t max_restarts, const double *d_v0,
@@ -1071,6 +1107,110 @@ int spl_eigsh_solve(void *E, int nev, int which, double tol, double atol, int64_
                     double *values, double *vectors, int64_t ldx, double *residuals, int64_t result[6], double *history);
 int spl_eigsh_info(void *E, int64_t info[8]);
 void spl_eigsh_free(void **E);
+
+/* ---- LOBPCG on handles (csrc/lobpcg.hip, csrc/ritz_jacobi.hpp) -----------------------------------------------------------
+ * A few extreme eigenpairs of a real symmetric or complex Hermitian handle by a BLOCK method with the preconditioner
+ * inside the iteration (Knyazev's LOBPCG on an orthonormal basis): it finds every copy of a multiple eigenvalue that its
+ * block has room for, and on the small end of an elliptic operator it applies one preconditioner cycle per column and
+ * iteration instead of an inner solve.  The contract is the one of the sections above: values, vectors, residuals,
+ * history and every count are a serial restatement's bit for bit, whatever SPL_KRYLOV_GRID, SPL_GMRES_DOTS_BATCH,
+ * SPL_EIGSH_ROTATE_ROWS and SPL_GRAM_TILE are; SPL_ORDER_FREE on the operator voids it.  No captured graph, no
+ * floating-point atomic, no kernel waits for another workgroup.
+ *
+ * spl_lobpcg_create: a solver object for the whole square handle A with a block of `block` columns, 1 ... 42 (so that
+ *   the basis of 3 block columns stays within the 128 of spl_vector_gram_dev and spl_vector_rotate_dev).  Ownership,
+ *   borrowing, the lock (one solve at a time) and spl_lobpcg_free's idempotence are spl_eigsh_create's, and so are the
+ *   errors and their order, with "block outside 1 ... 42" where "ncv outside 2 ... 128" comes there.  The object holds
+ *   7 block + 1 vectors (S = [X | P | W], A S, R for the preconditioner, one product for the residuals at the end), the
+ *   partials, 30 block^2 + 19 block doubles and 3 block ints of tables (T, the rotation, the coefficients of the two
+ *   passes, norms, residuals, flags) and a status block in device memory: info[3] has the bytes.  The products are
+ *   spl_matrix_spmv_many_dev's (the CSR image, reference order), the one of the residuals at the end
+ *   spl_matrix_spmv_dev's.
+ * spl_lobpcg_set_preconditioner, spl_lobpcg_set_preconditioner_amg: as the spl_krylov_ calls; w = M^-1 r is applied
+ *   column by column.
+ *
+ * The method.  b = block; S has the columns s_0 ... s_(3b-1): X = s_0 .. s_(b-1), P the next b, W the last b; A S is kept
+ * beside it.  Every real operation is rounded once; a real number times an entry and an entry over a real number are done
+ * part by part; <a,b> and its fold are those of the sections above; the product of two complex numbers is Data.Complex's.
+ *   settle(c): column c against the c columns before it.  eta0 = sqrt(Re<s_c,s_c>);  c > 0:  c1_i = <s_i, s_c>, i < c
+ *             (one pass);  s_c = ((s_c - c1_0 s_0) - c1_1 s_1) - ... ascending;  c2_i = <s_i, s_c>;  s_c = s_c - sum c2_i
+ *             s_i the same way;  eta2 = sqrt(Re<s_c,s_c>)  (c == 0: eta2 is eta0 computed again)
+ *             eta0 or eta2 not finite: flag_c = 2;  else eta2 == 0 or eta2 <= 2^-40 eta0: flag_c = 1 (dropped);  else
+ *             flag_c = 0.  flag_c != 0: s_c = 0 (every entry +0.0);  else s_c = s_c / eta2.  The decision is taken on the
+ *             device; a zero column gives +0.0 coefficients and terms, so the launches do not depend on what dropped.
+ *             2^-40: what is left of a column after the first pass is below 2^-40 of it exactly when the second pass can
+ *             no longer restore orthogonality to rounding level from it.
+ *   close(m, k): G_ij = <s_i, (A s)_j> for i <= j < m by spl_vector_gram_dev's kernel (upper).
+ *             A flag_j == 2 with j < m, or any flag other than 0 on a column of X (j < b): reason 3.
+ *             kept = the j < m with flag_j == 0, ascending, m' of them.
+ *             T (m' x m'):  T_aa = Re G_(kept a, kept a);  T_ac = G_(kept a, kept c) and T_ca its conjugate for a < c;
+ *             an entry of T not finite: reason 3.
+ *             T = Y diag(theta) Y^H by cyclic Jacobi with Y = I at the start: real handles by the rule of the Lanczos
+ *             section; complex handles by the same rule with the coupling turned real first:
+ *               a sweep starts only if some strict upper entry has a non-zero part; p ascending, q > p ascending,
+ *               a = T_pq:  both parts 0: skip;  g = sqrt(Re a Re a + Im a Im a);  |T_pp| + g == |T_pp| and
+ *               |T_qq| + g == |T_qq|:  T_pq = T_qp = 0, no rotation;  otherwise u = (Re a / g, Im a / g);
+ *               tau = (T_qq - T_pp) / (2 g);  t, c, s from tau as in the real rule;  for r != p, q:  z = T_rq conj(u)
+ *               = (Re T_rq Re u + Im T_rq Im u,  Im T_rq Re u - Re T_rq Im u);  (T_rp, T_rq) <- (c T_rp - s z,
+ *               s T_rp + c z) part by part, T_pr and T_qr their conjugates;  T_pp = T_pp - t g;  T_qq = T_qq + t g (the old
+ *               diagonal);  T_pq = T_qp = 0;  for all r:  z = Y_rq conj(u) likewise;  (Y_rp, Y_rq) <- (c Y_rp - s z,
+ *               s Y_rp + c z).  A 61st sweep, or a theta or a part of Y not finite at the end: reason 3.
+ *             The pairs are ordered stably by `which` (ties: lower column first).  Z (m x k):  column i < b has
+ *             Y[a][order i] in row kept_a and +0.0 in the rows of flagged columns;  column b + i (when k = 2 b) is column
+ *             i with the rows 0 ... b-1 set to +0.0.  S[:, :k] <- S[:, :m] Z and (A S)[:, :k] <- (A S)[:, :m] Z in place
+ *             by spl_vector_rotate_dev's kernel (complex handles: spl_vector_rotate_z_dev's);  theta_i = theta_(order i),
+ *             i < b.  Then X' is settled again, settle(0) ... settle(b-1), and A X' with it:  (A s)_c = ((A s)_c - c1_0
+ *             (A s)_0) - ... and the same with c2, ascending, then (A s)_c / eta2, or zeros where s_c got them: A X' stays
+ *             the product of X'.  (The rotation alone leaves X' orthonormal to ITS rounding, and the loss adds up: 1.2e-13
+ *             after 56 iterations on a 12 x 12 grid, which biases theta by as much.)  A flag on a column of X is found at
+ *             the next close: reason 3.
+ *   start:    X = X0;  P = 0 (flagged as dropped, not counted);  settle(0) ... settle(b-1);  a flag 2: reason 3, no pairs;
+ *             a flag 1: reason 2, no pairs (the start block is rank deficient).  A X by one product of b columns;
+ *             close(b, b).
+ *   iteration it = 0, 1, ...:
+ *             r_i = (A x)_i - theta_i x_i, i < b, each entry one product part by part and one difference;
+ *             rho_i = sqrt(Re<r_i,r_i>);  a rho_i not finite: reason 3, no pairs.  history[it] = max rho_i, i < nev.
+ *             Column i < nev is converged when rho_i <= max(tol |theta_i|, atol);  all nev converged: reason 0;  else
+ *             it == max_iter: reason 1;  both end at `finish`.
+ *             w_i = M^-1 r_i, or r_i without a preconditioner, into column 2 b + i.
+ *             settle(b) ... settle(3 b - 1): P and then W against everything before them.  A [P | W] by ONE product of
+ *             2 b columns (a zero column gives a zero column).  close(3 b, 2 b): [X' | P'] and [A X' | .].  Flags 1 are
+ *             counted as drops, those of P in iteration 0 excepted.  iterations = it + 1.
+ *   finish:   d_vectors = the first nev columns of X as the last close left them;
+ *             values[i] = theta_i;  residuals[i] = sqrt(Re<r,r>), r = A x_i - theta_i x_i with a fresh
+ *             spl_matrix_spmv_dev product.
+ * Limits: converged columns are not locked (they stay in the block and are iterated on); A x = lambda B x, interior
+ * eigenvalues, row-block handles and several devices are not served.
+ *
+ * spl_lobpcg_solve_dev: d_X0 (block columns, ldx0 >= n entries apart) and d_vectors (nev columns, ldx >= n apart) are
+ *   DEVICE arrays; values, residuals (nev doubles each), result and history (NULL, or max_iter + 1 doubles) are the
+ *   HOST's.  d_X0 is required and is not changed: the library draws no random numbers.  `which` is
+ *   SPL_EIGSH_smallest_algebraic or SPL_EIGSH_largest_algebraic.  The host synchronises twice per iteration (the
+ *   residual norms; T and the flags), once at the start and once at the end.  result = {reason, iterations, columns
+ *   multiplied by A, pairs returned, preconditioner applications, most Jacobi sweeps of a close, columns dropped in
+ *   total, synchronisations}; reasons: 0 converged, 1 max_iter, 2 start block rank deficient, 3 not finite.  Reasons 0
+ *   and 1 return nev pairs, 2 and 3 none, and only the first result[3] entries of values, residuals and d_vectors are
+ *   written.  Returns SPL_OK whenever it ran.  Errors, in this order: SPL_ERROR_invalid_handle (L);
+ *   SPL_ERROR_argument_missing (values, residuals or result NULL); SPL_ERROR_n_nonpositive (max_iter < 0);
+ *   SPL_ERROR_argument_missing (not 1 <= nev <= block <= n, `which` largest magnitude or unknown, tol or atol negative
+ *   or NaN); SPL_ERROR_index_overflow (a history of 2^31 entries or more); SPL_ERROR_argument_missing (d_X0 or d_vectors
+ *   NULL, ldx0 < n, ldx < n, a pointer not aligned to an entry).
+ * spl_lobpcg_solve: the same with a HOST X0 and HOST vectors, on the default stream.
+ * spl_lobpcg_info: [0] n, [1] block, [2] flags (1 complex, and 2 / 4 / 8 / 16 as spl_krylov_info's), [3] bytes of device
+ *   memory, [4] solves, [5] iterations of the last solve, [6] launches of the last solve (a product counted as
+ *   one, a Gram matrix as the kernels it enqueues, whatever its cut), [7] 0.
+ * spl_lobpcg_free: idempotent, as spl_krylov_free. */
+int spl_lobpcg_create(void *A, int block, void **L);
+int spl_lobpcg_set_preconditioner(void *L, void *T1, const double *d_mid, void *T2);
+int spl_lobpcg_set_preconditioner_amg(void *L, void *M);
+int spl_lobpcg_solve_dev(void *L, int nev, int which, double tol, double atol, int64_t max_iter, const double *d_X0,
+                         int64_t ldx0, double *values, double *d_vectors, int64_t ldx, double *residuals,
+                         int64_t result[8], double *history, void *stream);
+int spl_lobpcg_solve(void *L, int nev, int which, double tol, double atol, int64_t max_iter, const double *X0,
+                     int64_t ldx0, double *values, double *vectors, int64_t ldx, double *residuals, int64_t result[8],
+                     double *history);
+int spl_lobpcg_info(void *L, int64_t info[8]);
+void spl_lobpcg_free(void **L);
 
 /* select a kernel variant for spl_matrix_spmv_dev (tuning / ablation only): 0 = default
  * (whatever spl_matrix_optimize chose), 1-6 CSR-stream shapes, 7 sub-wavefront kernel, 8

@@ -185,12 +185,21 @@ def _declare(L):
         "spl_gmres_solve": [C.c_void_p, c_dbl_p, c_dbl_p, i, d, d, i64, c_i64_p, c_dbl_p, c_dbl_p],
         "spl_gmres_info": [C.c_void_p, c_i64_p],
         "spl_vector_rotate_dev": [i64, i, i, i, C.c_void_p, i64, C.c_void_p, i, C.c_void_p, i64, C.c_void_p],
+        "spl_vector_rotate_z_dev": [i64, i, i, i, C.c_void_p, i64, C.c_void_p, i, C.c_void_p, i64, C.c_void_p],
+        "spl_vector_gram_dev": [i64, i, i, i, C.c_void_p, i64, C.c_void_p, i64, C.c_void_p, i64, i, C.c_void_p],
         "spl_eigsh_create": [C.c_void_p, i, c_void_pp],
         "spl_eigsh_set_inverse": [C.c_void_p, C.c_void_p, d, d, d, i64],
         "spl_eigsh_solve_dev": [C.c_void_p, i, i, d, d, i64, C.c_void_p, c_dbl_p, C.c_void_p, i64, c_dbl_p, c_i64_p,
                                 c_dbl_p, C.c_void_p],
         "spl_eigsh_solve": [C.c_void_p, i, i, d, d, i64, c_dbl_p, c_dbl_p, c_dbl_p, i64, c_dbl_p, c_i64_p, c_dbl_p],
         "spl_eigsh_info": [C.c_void_p, c_i64_p],
+        "spl_lobpcg_create": [C.c_void_p, i, c_void_pp],
+        "spl_lobpcg_set_preconditioner": [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p],
+        "spl_lobpcg_set_preconditioner_amg": [C.c_void_p, C.c_void_p],
+        "spl_lobpcg_solve_dev": [C.c_void_p, i, i, d, d, i64, C.c_void_p, i64, c_dbl_p, C.c_void_p, i64, c_dbl_p, c_i64_p,
+                                 c_dbl_p, C.c_void_p],
+        "spl_lobpcg_solve": [C.c_void_p, i, i, d, d, i64, c_dbl_p, i64, c_dbl_p, c_dbl_p, i64, c_dbl_p, c_i64_p, c_dbl_p],
+        "spl_lobpcg_info": [C.c_void_p, c_i64_p],
         "spl_matrix_set_variant": [C.c_void_p, i],
         "spl_matrix_optimize": [C.c_void_p],
         "spl_matrix_build_blocked": [C.c_void_p, i, i, i],
@@ -232,6 +241,9 @@ def _declare(L):
     if hasattr(L, "spl_eigsh_free"):
         L.spl_eigsh_free.restype = None
         L.spl_eigsh_free.argtypes = [c_void_pp]
+    if hasattr(L, "spl_lobpcg_free"):
+        L.spl_lobpcg_free.restype = None
+        L.spl_lobpcg_free.argtypes = [c_void_pp]
     if hasattr(L, "spl_amg_free"):
         L.spl_amg_free.restype = None
         L.spl_amg_free.argtypes = [c_void_pp]

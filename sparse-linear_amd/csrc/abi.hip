@@ -1923,6 +1923,28 @@ int spl_vector_dots_dev(int64_t n, int value_width, int k, const double *d_V, in
   });
 }
 
+// ---- a block of inner products in one pass (csrc/gram.hip) ---------------------------------------------------------------
+int spl_vector_gram_dev(int64_t n, int value_width, int k, int l, const double *d_V, int64_t ldv, const double *d_W,
+                        int64_t ldw, double *d_G, int64_t ldg, int upper, void *stream) {
+  if (n < 0) return SPL_ERROR_n_nonpositive;
+  if (value_width != 1 && value_width != 2) return SPL_ERROR_argument_missing;
+  if (k < 1 || k > 128 || l < 1 || l > 128 || (upper != 0 && upper != 1) || ldv < n || ldw < n || ldg < k)
+    return SPL_ERROR_argument_missing;
+  if (!d_G || (n > 0 && (!d_V || !d_W))) return SPL_ERROR_argument_missing;
+  const uintptr_t entry = (uintptr_t)(8 * value_width);  // the kernels load and store whole entries
+  if ((uintptr_t)d_V % entry != 0 || (uintptr_t)d_W % entry != 0 || (uintptr_t)d_G % entry != 0)
+    return SPL_ERROR_argument_missing;
+  if (n > 0) {  // G beside the blocks, not inside them
+    const uintptr_t g0 = (uintptr_t)d_G, g1 = g0 + ((uintptr_t)(l - 1) * (uintptr_t)ldg + (uintptr_t)k) * entry;
+    const uintptr_t v0 = (uintptr_t)d_V, v1 = v0 + ((uintptr_t)(k - 1) * (uintptr_t)ldv + (uintptr_t)n) * entry;
+    const uintptr_t w0 = (uintptr_t)d_W, w1 = w0 + ((uintptr_t)(l - 1) * (uintptr_t)ldw + (uintptr_t)n) * entry;
+    if ((g0 < v1 && v0 < g1) || (g0 < w1 && w0 < g1)) return SPL_ERROR_argument_missing;
+  }
+  return guarded([&]() -> int {
+    return vector_gram(current_device(), n, value_width, k, l, d_V, ldv, d_W, ldw, d_G, ldg, upper, as_stream(stream));
+  });
+}
+
 // A is borrowed: the object keeps the pointer, its restart + 3 vectors and its tables
 int spl_gmres_create(void *A, int restart, void **G) {
   Matrix *M = nullptr;
@@ -2015,6 +2037,27 @@ int spl_vector_rotate_dev(int64_t n, int value_width, int m, int k, double *d_V,
   });
 }
 
+// the same with a complex Y (packed pairs) on complex vectors
+int spl_vector_rotate_z_dev(int64_t n, int value_width, int m, int k, double *d_V, int64_t ldv, const double *d_Y, int ldy,
+                            double *d_out, int64_t ldo, void *stream) {
+  if (n < 0) return SPL_ERROR_n_nonpositive;
+  if (value_width != 2) return SPL_ERROR_argument_missing;  // a complex Y makes a complex result
+  if (m < 1 || m > 128 || k < 1 || k > m || ldv < n || ldy < m || (d_out && ldo < n)) return SPL_ERROR_argument_missing;
+  if (n > 0 && (!d_V || !d_Y)) return SPL_ERROR_argument_missing;
+  const uintptr_t entry = 16;  // the kernel loads and stores whole entries; Y is read double by double
+  if ((uintptr_t)d_V % entry != 0 || (uintptr_t)d_Y % sizeof(double) != 0 || (uintptr_t)d_out % entry != 0)
+    return SPL_ERROR_argument_missing;
+  if (d_out && n > 0) {  // the result beside V, not over it
+    const uintptr_t v0 = (uintptr_t)d_V, v1 = v0 + ((uintptr_t)(m - 1) * (uintptr_t)ldv + (uintptr_t)n) * entry;
+    const uintptr_t o0 = (uintptr_t)d_out, o1 = o0 + ((uintptr_t)(k - 1) * (uintptr_t)ldo + (uintptr_t)n) * entry;
+    if (o0 < v1 && v0 < o1) return SPL_ERROR_argument_missing;
+  }
+  return guarded([&]() -> int {
+    (void)current_device();
+    return vector_rotate(n, 2, m, k, d_V, ldv, d_Y, ldy, d_out, ldo, as_stream(stream), true);
+  });
+}
+
 // A is borrowed: the object keeps the pointer, its ncv + 2 vectors and its tables
 int spl_eigsh_create(void *A, int ncv, void **E) {
   Matrix *M = nullptr;
@@ -2098,6 +2141,106 @@ int spl_eigsh_solve(void *E, int nev, int which, double tol, double atol, int64_
 int spl_eigsh_info(void *E, int64_t info[8]) { return info_of(E, as_eigsh, eigsh_info, info); }
 
 void spl_eigsh_free(void **E) { free_object(E, as_eigsh, eigsh_delete); }
+
+// ---- LOBPCG on handles (csrc/lobpcg.hip) -----------------------------------------------------------------------------------
+// A is borrowed: the object keeps the pointer, its 7 block + 1 vectors and its tables
+int spl_lobpcg_create(void *A, int block, void **L) {
+  Matrix *M = nullptr;
+  const int refused = square_whole_matrix(A, L, block >= 1 && block <= 42, &M);
+  if (refused != SPL_OK) return refused;
+  return create_object<Lobpcg>(M, L, [&](Lobpcg **S) -> int {
+    if (!M->rowptr.get() || hermitian_device(M, nullptr) != 1) return SPL_ERROR_invalid_matrix;
+    return lobpcg_create(M, block, S);
+  });
+}
+
+int spl_lobpcg_set_preconditioner(void *L, void *T1, const double *d_mid, void *T2) {
+  Lobpcg *S = as_lobpcg(L);
+  if (!S) return SPL_ERROR_invalid_handle;
+  TriSolver *parts[2];
+  const int refused = preconditioner_parts(head(S), T1, d_mid, T2, parts);
+  if (refused != SPL_OK) return refused;
+  lobpcg_set_preconditioner(S, parts[0], d_mid, parts[1]);
+  return SPL_OK;
+}
+
+// M is borrowed and may serve several solvers; NULL takes the preconditioner away
+int spl_lobpcg_set_preconditioner_amg(void *L, void *M) {
+  Lobpcg *S = as_lobpcg(L);
+  if (!S) return SPL_ERROR_invalid_handle;
+  Amg *P = nullptr;
+  const int refused = preconditioner_amg(head(S), M, &P);
+  if (refused != SPL_OK) return refused;
+  lobpcg_set_preconditioner_amg(S, P);
+  return SPL_OK;
+}
+
+namespace {
+// what both solve calls refuse before the vectors are looked at
+int check_lobpcg_solve(const Lobpcg *S, int nev, int which, double tol, double atol, int64_t max_iter,
+                       const double *values, const double *residuals, const int64_t *result, const double *history) {
+  if (!S) return SPL_ERROR_invalid_handle;
+  if (!values || !residuals || !result) return SPL_ERROR_argument_missing;
+  if (max_iter < 0) return SPL_ERROR_n_nonpositive;
+  if (nev < 1 || nev > lobpcg_block(S) || (int64_t)lobpcg_block(S) > head(S).n ||
+      (which != SPL_EIGSH_largest_algebraic && which != SPL_EIGSH_smallest_algebraic) || !(tol >= 0.0) || !(atol >= 0.0))
+    return SPL_ERROR_argument_missing;  // a NaN is refused too
+  if (history && max_iter >= ((int64_t)1 << 31)) return SPL_ERROR_index_overflow;
+  return SPL_OK;
+}
+}  // namespace
+
+int spl_lobpcg_solve_dev(void *L, int nev, int which, double tol, double atol, int64_t max_iter, const double *d_X0,
+                         int64_t ldx0, double *values, double *d_vectors, int64_t ldx, double *residuals,
+                         int64_t result[8], double *history, void *stream) {
+  Lobpcg *S = as_lobpcg(L);
+  const int refused = check_lobpcg_solve(S, nev, which, tol, atol, max_iter, values, residuals, result, history);
+  if (refused != SPL_OK) return refused;
+  const ObjectHead &o = head(S);
+  if (!d_X0 || !d_vectors || ldx0 < o.n || ldx < o.n) return SPL_ERROR_argument_missing;
+  const uintptr_t entry = (uintptr_t)(8 * o.vw);  // the kernels load and store whole entries
+  if ((uintptr_t)d_X0 % entry != 0 || (uintptr_t)d_vectors % entry != 0) return SPL_ERROR_argument_missing;
+  return guarded([&]() -> int {
+    DeviceGuard g(o.device);
+    return lobpcg_solve(S, nev, which, tol, atol, max_iter, d_X0, ldx0, values, d_vectors, ldx, residuals, result,
+                        history, as_stream(stream));
+  });
+}
+
+// host X0 (block columns, ldx0 entries apart, packed complex) and vectors (nev columns, ldx entries apart): up, solved on
+// the default stream, down
+int spl_lobpcg_solve(void *L, int nev, int which, double tol, double atol, int64_t max_iter, const double *X0,
+                     int64_t ldx0, double *values, double *vectors, int64_t ldx, double *residuals, int64_t result[8],
+                     double *history) {
+  Lobpcg *S = as_lobpcg(L);
+  const int refused = check_lobpcg_solve(S, nev, which, tol, atol, max_iter, values, residuals, result, history);
+  if (refused != SPL_OK) return refused;
+  const ObjectHead &o = head(S);
+  if (!X0 || !vectors || ldx0 < o.n || ldx < o.n) return SPL_ERROR_argument_missing;
+  const size_t count = (size_t)o.n * (size_t)o.vw;
+  const int block = lobpcg_block(S);
+  return guarded([&]() -> int {
+    DeviceGuard g(o.device);
+    hipStream_t s = nullptr;
+    DBuf<double> d(((size_t)block + (size_t)nev) * count);
+    for (int j = 0; j < block; ++j)
+      SPL_HIP(hipMemcpyAsync(d.get() + (size_t)j * count, X0 + (size_t)j * (size_t)ldx0 * (size_t)o.vw,
+                             count * sizeof(double), hipMemcpyHostToDevice, s));
+    double *d_vectors = d.get() + (size_t)block * count;
+    const int st = lobpcg_solve(S, nev, which, tol, atol, max_iter, d.get(), o.n, values, d_vectors, o.n, residuals,
+                                result, history, s);
+    if (st != SPL_OK) return st;
+    for (int64_t i = 0; i < result[3]; ++i)  // the columns found, ldx entries apart
+      SPL_HIP(hipMemcpyAsync(vectors + (size_t)i * (size_t)ldx * (size_t)o.vw, d_vectors + (size_t)i * count,
+                             count * sizeof(double), hipMemcpyDeviceToHost, s));
+    SPL_HIP(hipStreamSynchronize(s));
+    return SPL_OK;
+  });
+}
+
+int spl_lobpcg_info(void *L, int64_t info[8]) { return info_of(L, as_lobpcg, lobpcg_info, info); }
+
+void spl_lobpcg_free(void **L) { free_object(L, as_lobpcg, lobpcg_delete); }
 
 // mulM on Complex Double (the reference's SPECIALIZE instance, Sparse.hs:475): one axpy_ per column of B there; here the
 // packed-complex image of A and one multi-vector product.  B and C are row-major like spl_mulm's; the kernel wants one

@@ -120,6 +120,7 @@ constexpr uint32_t kKrylovMagic = 0x53504C4Bu;  // "SPLK"
 constexpr uint32_t kAmgMagic = 0x53504C47u;     // "SPLG"
 constexpr uint32_t kGmresMagic = 0x53504C47u;   // "SPLG": the word of the AMG object, so the two are not told apart
 constexpr uint32_t kEigshMagic = 0x53504C45u;   // "SPLE"
+constexpr uint32_t kLobpcgMagic = 0x53504C42u;  // "SPLB": the block eigensolver
 // the object behind h, or nullptr unless h carries the magic word
 template <typename T, uint32_t Magic>
 T *as_object(void *h) {
@@ -412,6 +413,13 @@ void amg_delete(Amg *M);
 // M: borrowed, of K's size, value kind and device (the caller checked), or nullptr; clears the triangular parts
 void krylov_set_preconditioner_amg(Krylov *K, Amg *M);
 
+// ---- a block of inner products in one pass (gram.hip) --------------------------------------------------------------------
+// G[i][j] = <V[:, i], W[:, j]>, i < k, j < l, of n entries of vw doubles each to d_G (column major, entry (i, j) at
+// d_G + (j * ldg + i) * vw; upper: only i <= j is written).  Each value is vector_dot's, bit for bit; enqueues on s;
+// *launches (may be nullptr) grows by the kernels enqueued, whatever the cut into blocks of columns is
+int vector_gram(int device, int64_t n, int vw, int k, int l, const double *d_V, int64_t ldv, const double *d_W,
+                int64_t ldw, double *d_G, int64_t ldg, int upper, hipStream_t s, int64_t *launches = nullptr);
+
 // ---- restarted GMRES on handles and the fused multi-vector inner product (gmres.hip) ---------------------------------
 // <V[:, i], w>, i < k, of n entries of vw doubles each to d_out (k entries, device memory); column i starts at
 // d_V + i * ldv * vw.  Each value is vector_dot's, bit for bit; enqueues on s, no synchronisation
@@ -433,8 +441,9 @@ void gmres_delete(Gmres *G);
 // ---- thick-restart Lanczos on handles and the in-place basis rotation (eigsh.hip) ---------------------------------------
 // V[:, :k] <- V Y (d_out == nullptr) or d_out = V Y: V n x m entries of vw doubles, Y real m x k, all column major in
 // device memory; 1 <= k <= m <= 128 and d_out clear of V (the caller checked); enqueues on s, no synchronisation
+// y_complex (vw == 2 only): Y holds packed pairs and a term is Data.Complex's product (spl_vector_rotate_z_dev)
 int vector_rotate(int64_t n, int vw, int m, int k, double *d_V, int64_t ldv, const double *d_Y, int ldy, double *d_out,
-                  int64_t ldo, hipStream_t s);
+                  int64_t ldo, hipStream_t s, bool y_complex = false);
 struct Eigsh;
 inline Eigsh *as_eigsh(void *e) { return as_object<Eigsh, kEigshMagic>(e); }
 // A: whole, square and Hermitian, 2 <= ncv <= 128 (the caller checked); borrowed.  SPL_OK
@@ -448,6 +457,22 @@ int eigsh_solve(Eigsh *E, int nev, int which, double tol, double atol, int64_t m
 void eigsh_info(Eigsh *E, int64_t info[8]);
 int eigsh_ncv(const Eigsh *E);
 void eigsh_delete(Eigsh *E);
+
+// ---- LOBPCG on handles (lobpcg.hip) ---------------------------------------------------------------------------------------
+struct Lobpcg;
+inline Lobpcg *as_lobpcg(void *l) { return as_object<Lobpcg, kLobpcgMagic>(l); }
+// A: whole, square and Hermitian, 1 <= block <= 42 (the caller checked); borrowed.  SPL_OK
+int lobpcg_create(const Matrix *A, int block, Lobpcg **out);
+// the parts are borrowed and of L's size, value kind and device (the caller checked); nullptr: the identity
+void lobpcg_set_preconditioner(Lobpcg *L, TriSolver *T1, const double *d_mid, TriSolver *T2);
+void lobpcg_set_preconditioner_amg(Lobpcg *L, Amg *M);
+// n > 0 and the arguments are checked by the caller; enqueues on s and synchronises it (the outcome is read back)
+int lobpcg_solve(Lobpcg *L, int nev, int which, double tol, double atol, int64_t max_iter, const double *d_X0,
+                 int64_t ldx0, double *values, double *d_vectors, int64_t ldx, double *residuals, int64_t result[8],
+                 double *history, hipStream_t s);
+void lobpcg_info(Lobpcg *L, int64_t info[8]);
+int lobpcg_block(const Lobpcg *L);
+void lobpcg_delete(Lobpcg *L);
 
 // ---- multifrontal LU without interchanges (multifrontal.hip, mf_symbolic.hpp) ------------------
 namespace mf {

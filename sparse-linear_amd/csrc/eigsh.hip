@@ -40,7 +40,9 @@ constexpr int kMaxSweeps = 60;
 // array: a tile's loads are all in front of the barrier, its stores behind it, and no other workgroup touches its rows.
 // WAVE (R == 64): a wavefront is one column group, so its output columns and the entries of Y it needs are the same in
 // every lane, and Y is read through the scalar cache instead of one vector load per lane and term.
-template <int VW, bool WAVE>
+// YZ (spl_vector_rotate_z_dev, VW == 2): Y holds packed pairs and a term is x = x + Y[l][i] v_l with Data.Complex's
+// product, (ac - bd, ad + bc) for Y = a + bi and v = c + di, each operation rounded once.
+template <int VW, bool WAVE, bool YZ = false>
 __global__ __launch_bounds__(kLanes) void rotate_kernel(int64_t n, int m, int k, int rows_log2, const double *V,
                                                         int64_t ldv, const double *__restrict__ Y, int ldy, double *out,
                                                         int64_t ldo) {
@@ -64,21 +66,41 @@ __global__ __launch_bounds__(kLanes) void rotate_kernel(int64_t n, int m, int k,
 #pragma unroll
       for (int c = 0; c < kRotateCols; ++c) {
         const int col = i0 + c * G;
-        y[c] = Y + (size_t)(col < k ? col : i0) * (size_t)ldy;  // a column past k: computed again, never stored
+        y[c] = Y + (size_t)(col < k ? col : i0) * (size_t)ldy * (YZ ? 2 : 1);  // past k: computed again, never stored
       }
+      if constexpr (YZ) {
+        const double a = tile[r], b = tile[(size_t)R + r];
 #pragma unroll
-      for (int p = 0; p < VW; ++p) {
-        const double a = tile[(size_t)p * R + r];
-#pragma unroll
-        for (int c = 0; c < kRotateCols; ++c) acc[c * VW + p] = y[c][0] * a;
-      }
+        for (int c = 0; c < kRotateCols; ++c) {
+          const Val<2> x = mul(Val<2>{y[c][0], y[c][1]}, Val<2>{a, b});
+          acc[c * 2] = x.re;
+          acc[c * 2 + 1] = x.im;
+        }
 #pragma unroll kTerms
-      for (int l = 1; l < m; ++l) {
+        for (int l = 1; l < m; ++l) {
+          const double a = tile[(size_t)(l * 2) * R + r], b = tile[(size_t)(l * 2 + 1) * R + r];
+#pragma unroll
+          for (int c = 0; c < kRotateCols; ++c) {
+            const Val<2> x = mul(Val<2>{y[c][2 * l], y[c][2 * l + 1]}, Val<2>{a, b});
+            acc[c * 2] = acc[c * 2] + x.re;
+            acc[c * 2 + 1] = acc[c * 2 + 1] + x.im;
+          }
+        }
+      } else {
 #pragma unroll
         for (int p = 0; p < VW; ++p) {
-          const double a = tile[(size_t)(l * VW + p) * R + r];
+          const double a = tile[(size_t)p * R + r];
 #pragma unroll
-          for (int c = 0; c < kRotateCols; ++c) acc[c * VW + p] = acc[c * VW + p] + y[c][l] * a;
+          for (int c = 0; c < kRotateCols; ++c) acc[c * VW + p] = y[c][0] * a;
+        }
+#pragma unroll kTerms
+        for (int l = 1; l < m; ++l) {
+#pragma unroll
+          for (int p = 0; p < VW; ++p) {
+            const double a = tile[(size_t)(l * VW + p) * R + r];
+#pragma unroll
+            for (int c = 0; c < kRotateCols; ++c) acc[c * VW + p] = acc[c * VW + p] + y[c][l] * a;
+          }
         }
       }
       if (live) {
@@ -102,14 +124,18 @@ int rotate_rows_log2(int m, int vw) {
   return lg;
 }
 
-// n > 0; 1 <= k <= m <= 128.  One launch on s
+// n > 0; 1 <= k <= m <= 128.  One launch on s.  y_complex: Y holds packed pairs (vw == 2 only)
 void rotate_launch(int64_t n, int vw, int m, int k, const double *V, int64_t ldv, const double *Y, int ldy,
-                   double *out, int64_t ldo, hipStream_t s) {
+                   double *out, int64_t ldo, hipStream_t s, bool y_complex = false) {
   const int lg = rotate_rows_log2(m, vw);
   const size_t lds = (size_t)m * (size_t)vw * sizeof(double) << lg;
   const int64_t tiles = (n + ((int64_t)1 << lg) - 1) >> lg, cap = chunk_grid_cap();
   const dim3 grid((unsigned)(tiles < cap ? tiles : cap)), block(kLanes);
-  if (vw == 1 && lg == 6)
+  if (y_complex && lg == 6)
+    hipLaunchKernelGGL((rotate_kernel<2, true, true>), grid, block, lds, s, n, m, k, lg, V, ldv, Y, ldy, out, ldo);
+  else if (y_complex)
+    hipLaunchKernelGGL((rotate_kernel<2, false, true>), grid, block, lds, s, n, m, k, lg, V, ldv, Y, ldy, out, ldo);
+  else if (vw == 1 && lg == 6)
     hipLaunchKernelGGL((rotate_kernel<1, true>), grid, block, lds, s, n, m, k, lg, V, ldv, Y, ldy, out, ldo);
   else if (vw == 1)
     hipLaunchKernelGGL((rotate_kernel<1, false>), grid, block, lds, s, n, m, k, lg, V, ldv, Y, ldy, out, ldo);
@@ -279,9 +305,9 @@ int jacobi(int m, std::vector<double> &T, std::vector<double> &Y) {
 
 // V[:, :k] <- V Y (d_out == nullptr) or out = V Y; enqueues on s.  Arguments checked by the caller.
 int vector_rotate(int64_t n, int vw, int m, int k, double *d_V, int64_t ldv, const double *d_Y, int ldy, double *d_out,
-                  int64_t ldo, hipStream_t s) {
+                  int64_t ldo, hipStream_t s, bool y_complex) {
   if (n == 0) return SPL_OK;
-  rotate_launch(n, vw, m, k, d_V, ldv, d_Y, ldy, d_out ? d_out : d_V, d_out ? ldo : ldv, s);
+  rotate_launch(n, vw, m, k, d_V, ldv, d_Y, ldy, d_out ? d_out : d_V, d_out ? ldo : ldv, s, y_complex);
   const hipError_t e = hipGetLastError();
   if (e != hipSuccess) {
     set_last_error("vector rotate launch", e);

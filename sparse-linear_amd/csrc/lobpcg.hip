@@ -1,0 +1,444 @@
+// lobpcg.hip — LOBPCG on device handles: a block eigensolver with the preconditioner inside the iteration, Double and
+// packed Complex Double (real symmetric and complex Hermitian).
+//
+// The method is written out in include/sparse_linear_hip.h ("LOBPCG on handles"); this file issues it.  The basis
+// S = [X | P | W] (3 block columns) is kept ORTHONORMAL by classical Gram-Schmidt done twice on the one-pass kernels of
+// krylov_basis.hpp, so the Ritz problem is a standard Hermitian one: T = S^H (A S) by spl_vector_gram_dev's kernel
+// (gram.hip), diagonalised on the host by the cyclic Jacobi of ritz_jacobi.hpp, and [X' | P'] = S [C | C without its X
+// rows] by the in-place rotation of eigsh.hip, real or complex.  Rank deficiency is decided on the device without a
+// synchronisation per column: a column whose norm after the two passes is 0, not finite, or at most 2^-40 of its norm
+// before is written as zeros and flagged; a zero column contributes +0.0 terms only, so the launch sequence of an
+// iteration is the same whatever drops, and the host removes the flagged rows and columns from T.  Two synchronisations
+// per iteration: the residual norms; T and the flags.  No captured graph, no floating-point atomic, no kernel waits for
+// another workgroup.
+#include <algorithm>
+#include <cmath>
+#include <vector>
+
+#include "krylov_basis.hpp"
+#include "ritz_jacobi.hpp"
+#include "solver_core.hpp"
+
+namespace spl {
+
+namespace {
+
+constexpr double kDropRatio = 0x1p-40;  // eta2 <= kDropRatio * eta0: the column was in the span of those before it
+
+struct LStatus {
+  int zero;  // never set: the flag the shared kernels of a step read
+  int spare[3];
+};
+
+// in doubles from the start of the block; b = block, m = 3 b.  G and Z first: packed pairs are stored whole
+struct LTables {
+  double *G;         // m x m entries: S^H (A S), column major
+  double *Z;         // m x 2 b entries: the rotation
+  double *c1, *c2;   // the coefficients of the two passes: m entries each
+  double *eta0;      // m: Re<w,w> of a column before its passes
+  double *scale;     // m: its norm after them
+  double *res;       // b: Re<r,r>
+};
+inline size_t ltable_doubles(int b) { return (size_t)30 * b * b + (size_t)19 * b; }
+inline LTables ltables_at(double *base, int b) {
+  LTables T;
+  T.G = base;
+  T.Z = T.G + (size_t)18 * b * b;
+  T.c1 = T.Z + (size_t)12 * b * b;
+  T.c2 = T.c1 + 6 * b;
+  T.eta0 = T.c2 + 6 * b;
+  T.scale = T.eta0 + 3 * b;
+  T.res = T.scale + 3 * b;
+  return T;
+}
+
+// partials of Re<v,v>
+template <int VW>
+__global__ __launch_bounds__(kLanes) void lnorm_kernel(int64_t n, const double *__restrict__ v, double *part) {
+  chunk_partials<1>(n, part, 0, [&](int64_t i, double *acc) {
+    const Val<VW> vi = load_val<VW>(v, i);
+    acc[0] = acc[0] + mul(conj_of(vi), vi).re;
+  });
+}
+
+// r = ax - theta x, one product part by part and one difference per entry, stored when r is given; partials of Re<r,r>
+template <int VW>
+__global__ __launch_bounds__(kLanes) void lresidual_kernel(int64_t n, const double *__restrict__ ax,
+                                                           const double *__restrict__ x, double theta,
+                                                           double *__restrict__ r, double *part) {
+  chunk_partials<1>(n, part, 0, [&](int64_t i, double *acc) {
+    const Val<VW> ri = sub(load_val<VW>(ax, i), scaled(theta, load_val<VW>(x, i)));
+    if (r) store_val(r, i, ri);
+    acc[0] = acc[0] + mul(conj_of(ri), ri).re;
+  });
+}
+
+// ONE workgroup behind the passes of a column: eta2 from the last partials of Re<w,w>, eta0 from the table, the flag
+// (0 kept, 1 dropped, 2 not finite) and what a kept column is divided by
+__global__ __launch_bounds__(kLanes) void decide_kernel(const double *part, int count, const double *eta0sq,
+                                                        double *scale, int *flag) {
+  __shared__ double lds[kLanes];
+  const int t = threadIdx.x;
+  double f[1] = {0.0};
+  for (int i = t; i < count; i += kLanes) f[0] = f[0] + part[i];
+  lane_tree<1>(f, lds);
+  if (t != 0) return;
+  const double e2 = sqrt(f[0]), e0 = sqrt(*eta0sq);
+  *scale = e2;
+  if (!isfinite(e0) || !isfinite(e2)) *flag = 2;
+  else if (e2 == 0.0 || e2 <= kDropRatio * e0) *flag = 1;
+  else *flag = 0;
+}
+
+// w = w / scale part by part, or zeros when the column is flagged
+template <int VW>
+__global__ __launch_bounds__(kLanes) void settle_kernel(int64_t n, const int *flag, const double *scale, double *w) {
+  const bool drop = *flag != 0;
+  const double by = *scale;
+  int64_t i = (int64_t)blockIdx.x * kLanes + threadIdx.x;
+  const int64_t stride = (int64_t)gridDim.x * kLanes;
+  for (; i < n; i += stride) store_val(w, i, drop ? Val<VW>() : over(load_val<VW>(w, i), by));
+}
+
+}  // namespace
+
+// ---- the solver object (the shared part: solver_core.hpp) ---------------------------------------------------------------
+struct Lobpcg : SolverCore {  // work: 7 block + 1 vectors: S (3 block), A S (3 block), R (block), one product
+  int block;
+  Preconditioner pre;
+  DBuf<double> tables;
+  DBuf<int> flags;               // 3 block
+  StatusBlock<LStatus> status;   // behind the pinned copy: G, Z, res and the flags of the host
+  int64_t last_iterations = 0;
+  Lobpcg(const Matrix *A, int b)
+      : SolverCore(kLobpcgMagic, A, (size_t)7 * b + 1, fold_scratch(A->nrows_local, 3 * b * A->vw)), block(b),
+        tables(ltable_doubles(b)), flags((size_t)3 * b),
+        status(((size_t)30 * b * b + (size_t)b) * sizeof(double) + (size_t)3 * b * sizeof(int)) {
+    bytes += ltable_doubles(b) * sizeof(double) + (size_t)3 * b * sizeof(int) + sizeof(LStatus);
+  }
+  double *host_g() const { return reinterpret_cast<double *>(status.pinned + 1); }
+  double *host_z() const { return host_g() + (size_t)18 * block * block; }
+  double *host_res() const { return host_z() + (size_t)12 * block * block; }
+  int *host_flags() const { return reinterpret_cast<int *>(host_res() + block); }
+};
+
+// A: whole, square and Hermitian, 1 <= block <= 42 (the caller checked)
+int lobpcg_create(const Matrix *A, int block, Lobpcg **out) {
+  *out = new Lobpcg(A, block);
+  return SPL_OK;
+}
+
+void lobpcg_set_preconditioner(Lobpcg *L, TriSolver *T1, const double *d_mid, TriSolver *T2) {
+  std::lock_guard<std::mutex> hold(L->lock);
+  L->pre.set_parts(T1, d_mid, T2);
+}
+
+void lobpcg_set_preconditioner_amg(Lobpcg *L, Amg *M) {
+  std::lock_guard<std::mutex> hold(L->lock);
+  L->pre.set_amg(M);
+}
+
+int lobpcg_block(const Lobpcg *L) { return L->block; }
+
+namespace {
+
+// One solve's launches; everything is enqueued on s
+template <int VW>
+struct LRun : RunCore {
+  Lobpcg *L;
+  int b;
+  LTables T;
+  int *flags;
+  const int *never;  // the flag that is never set
+  int64_t spmv_columns = 0, applications = 0, sweeps_most = 0, dropped = 0, syncs = 0;
+  std::vector<double> theta;  // of the block's columns
+
+  LRun(Lobpcg *l, hipStream_t stream)
+      : RunCore(*l, stream), L(l), b(l->block), T(ltables_at(l->tables.get(), l->block)), flags(l->flags.get()),
+        never(&l->status.device.get()->zero), theta((size_t)l->block, 0.0) {}
+
+  double *basis(int j) const { return L->vec(j); }               // S
+  double *image(int j) const { return L->vec(3 * b + j); }       // A S
+  double *residual(int j) const { return L->vec(6 * b + j); }    // R, when a preconditioner reads it
+  double *product() const { return L->vec(7 * b); }
+
+  void sync() {
+    SPL_HIP(hipStreamSynchronize(s));
+    ++syncs;
+  }
+
+  // Re<v,v> of n entries folded to *out
+  void norm_to(const double *v, double *out) {
+    hipLaunchKernelGGL((lnorm_kernel<VW>), dim3(chunked), dim3(kLanes), 0, s, n, v, scratch);
+    const Partials P = middle_levels(nullptr, n, 1, scratch, s);
+    hipLaunchKernelGGL(fold_kernel, dim3(1, 1), dim3(kLanes), 0, s, (const int *)nullptr, (int64_t)P.count, P.p, P.stride, out,
+                       (int64_t)1);
+    launches += P.middle + 2;
+  }
+
+  // column c of S against the c columns before it: the norm before, the two passes, the decision, the division
+  void settle_column(int c) {
+    double *w = basis(c);
+    norm_to(w, T.eta0 + c);
+    Partials P;
+    if (c > 0) {
+      P = orthogonalise_twice<VW>(never, n, c, basis(0), w, T.c1, T.c2, scratch, chunked, s, &launches);
+    } else {
+      hipLaunchKernelGGL((lnorm_kernel<VW>), dim3(chunked), dim3(kLanes), 0, s, n, (const double *)w, scratch);
+      P = middle_levels(nullptr, n, 1, scratch, s);
+      launches += P.middle + 1;
+    }
+    hipLaunchKernelGGL(decide_kernel, dim3(1), dim3(kLanes), 0, s, P.p, P.count, (const double *)(T.eta0 + c), T.scale + c,
+                       flags + c);
+    hipLaunchKernelGGL((settle_kernel<VW>), dim3(flat), dim3(kLanes), 0, s, n, (const int *)(flags + c),
+                       (const double *)(T.scale + c), w);
+    launches += 2;
+  }
+
+  // X' behind a rotation is orthonormal to the rounding of the rotation only, and that loss adds up over the iterations
+  // (1.2e-13 after 56 of them on the 12 x 12 grid, which biases theta by as much, relatively).  So X is settled again,
+  // and A X receives the same coefficients, the same division and the same zeros: it stays the product of X
+  void settle_block() {
+    for (int j = 0; j < b; ++j) {
+      settle_column(j);
+      if (j > 0) {
+        hipLaunchKernelGGL((update_kernel<VW, false>), dim3(chunked), dim3(kLanes), 0, s, never, n, j,
+                           (const double *)image(0), n, (const double *)T.c1, image(j), scratch);
+        hipLaunchKernelGGL((update_kernel<VW, false>), dim3(chunked), dim3(kLanes), 0, s, never, n, j,
+                           (const double *)image(0), n, (const double *)T.c2, image(j), scratch);
+        launches += 2;
+      }
+      hipLaunchKernelGGL((settle_kernel<VW>), dim3(flat), dim3(kLanes), 0, s, n, (const int *)(flags + j),
+                         (const double *)(T.scale + j), image(j));
+      ++launches;
+    }
+  }
+
+  // r_i = A x_i - theta_i x_i to `out(i)` (nullptr: not stored) and Re<r_i,r_i> to res[i], i < count; ax(i): A x_i
+  template <typename Ax, typename Out>
+  void residuals_of(int count, Ax ax, Out out) {
+    for (int i = 0; i < count; ++i) {
+      hipLaunchKernelGGL((lresidual_kernel<VW>), dim3(chunked), dim3(kLanes), 0, s, n, (const double *)ax(i),
+                         (const double *)basis(i), theta[i], out(i), scratch);
+      const Partials P = middle_levels(nullptr, n, 1, scratch, s);
+      hipLaunchKernelGGL(fold_kernel, dim3(1, 1), dim3(kLanes), 0, s, (const int *)nullptr, (int64_t)P.count, P.p, P.stride,
+                         T.res + i, (int64_t)1);
+      launches += P.middle + 2;
+    }
+  }
+
+  // The close on the first mc columns of S: T = S^H (A S), the flags, Jacobi, the order, and the rotation that leaves
+  // kout columns (b: X' alone; 2 b: [X' | P']).  count_from: the first column whose drop is counted.  *reason >= 0
+  // ends the solve; -1: go on.  Synchronises once
+  int close(int mc, int kout, int which, int count_from, int *reason) {
+    *reason = -1;
+    int e = vector_gram(L->device, n, VW, mc, mc, basis(0), n, image(0), n, T.G, mc, 1, s, &launches);
+    if (e != SPL_OK) return e;
+    double *G = L->host_g();
+    int *flag = L->host_flags();
+    SPL_HIP(hipMemcpyAsync(G, T.G, (size_t)mc * mc * VW * sizeof(double), hipMemcpyDeviceToHost, s));
+    SPL_HIP(hipMemcpyAsync(flag, flags, (size_t)3 * b * sizeof(int), hipMemcpyDeviceToHost, s));
+    sync();
+    std::vector<int> kept;
+    for (int j = 0; j < mc; ++j) {
+      if (flag[j] == 2 || (j < b && flag[j] != 0)) return not_finite(reason);  // a column of X never drops
+      if (flag[j] == 0) kept.push_back(j);
+      else if (j >= count_from) ++dropped;
+    }
+    const int mp = (int)kept.size();
+    std::vector<double> Tm((size_t)mp * mp * VW), Y((size_t)mp * mp * VW);
+    for (int a = 0; a < mp; ++a)
+      for (int c = a; c < mp; ++c) {
+        const double *g = G + ((size_t)kept[c] * mc + kept[a]) * VW;  // the upper triangle: i <= j
+        if (!std::isfinite(g[0]) || (VW == 2 && a != c && !std::isfinite(g[1]))) return not_finite(reason);
+        if (VW == 1) {
+          Tm[(size_t)a * mp + c] = Tm[(size_t)c * mp + a] = g[0];
+        } else {
+          Tm[2 * ((size_t)a * mp + c)] = Tm[2 * ((size_t)c * mp + a)] = g[0];
+          const double gi = a == c ? 0.0 : g[1];
+          Tm[2 * ((size_t)a * mp + c) + 1] = gi;
+          Tm[2 * ((size_t)c * mp + a) + 1] = a == c ? 0.0 : -gi;
+        }
+      }
+    const int sweeps = VW == 1 ? ritz_jacobi_real(mp, Tm.data(), Y.data()) : ritz_jacobi_hermitian(mp, Tm.data(), Y.data());
+    if (sweeps < 0) return not_finite(reason);
+    auto value = [&](int i) { return Tm[((size_t)i * mp + i) * VW]; };
+    for (int i = 0; i < mp; ++i)
+      if (!std::isfinite(value(i))) return not_finite(reason);
+    for (size_t q = 0; q < Y.size(); ++q)
+      if (!std::isfinite(Y[q])) return not_finite(reason);
+    if (sweeps > sweeps_most) sweeps_most = sweeps;
+    std::vector<int> order(mp);
+    for (int i = 0; i < mp; ++i) order[i] = i;
+    std::stable_sort(order.begin(), order.end(), [&](int x, int y) {
+      return which == SPL_EIGSH_largest_algebraic ? value(x) > value(y) : value(x) < value(y);
+    });
+    // Z: mc x kout, column major; rows of flagged columns and, in the second block, the rows of X are +0.0
+    double *Z = L->host_z();
+    for (size_t q = 0; q < (size_t)mc * kout * VW; ++q) Z[q] = 0.0;
+    for (int i = 0; i < kout; ++i) {
+      const int col = order[i < b ? i : i - b];
+      for (int a = 0; a < mp; ++a) {
+        if (i >= b && kept[a] < b) continue;
+        for (int p = 0; p < VW; ++p) Z[((size_t)i * mc + kept[a]) * VW + p] = Y[((size_t)a * mp + col) * VW + p];
+      }
+    }
+    SPL_HIP(hipMemcpyAsync(T.Z, Z, (size_t)mc * kout * VW * sizeof(double), hipMemcpyHostToDevice, s));
+    if ((e = vector_rotate(n, VW, mc, kout, basis(0), n, T.Z, mc, nullptr, 0, s, VW == 2)) != SPL_OK) return e;
+    if ((e = vector_rotate(n, VW, mc, kout, image(0), n, T.Z, mc, nullptr, 0, s, VW == 2)) != SPL_OK) return e;
+    launches += 2;
+    for (int i = 0; i < b; ++i) theta[i] = value(order[i]);
+    settle_block();
+    return SPL_OK;
+  }
+  static int not_finite(int *reason) {
+    *reason = 3;
+    return SPL_OK;
+  }
+
+  int solve(int nev, int which, double tol, double atol, int64_t max_iter, const double *d_X0, int64_t ldx0,
+            double *values, double *d_vectors, int64_t ldx, double *residuals, int64_t result[8], double *history) {
+    int e;
+    int64_t iterations = 0;
+    const size_t column = (size_t)n * VW * sizeof(double);
+    auto done = [&](int reason, int pairs) {
+      result[0] = reason;
+      result[1] = iterations;
+      result[2] = spmv_columns;
+      result[3] = pairs;
+      result[4] = applications;
+      result[5] = sweeps_most;
+      result[6] = dropped;
+      result[7] = syncs;
+      return SPL_OK;
+    };
+    // X and the pairs' true residuals; synchronises
+    auto finish = [&](int reason) {
+      for (int i = 0; i < nev; ++i) {
+        SPL_HIP(hipMemcpyAsync(d_vectors + (size_t)i * (size_t)ldx * VW, basis(i), column, hipMemcpyDeviceToDevice, s));
+        values[i] = theta[i];
+        const int st = launch_spmv(L->A, basis(i), product(), 0, s);
+        if (st != SPL_OK) return st;
+        ++spmv_columns;
+        ++launches;
+        hipLaunchKernelGGL((lresidual_kernel<VW>), dim3(chunked), dim3(kLanes), 0, s, n, (const double *)product(),
+                           (const double *)basis(i), theta[i], (double *)nullptr, scratch);
+        const Partials P = middle_levels(nullptr, n, 1, scratch, s);
+        hipLaunchKernelGGL(fold_kernel, dim3(1, 1), dim3(kLanes), 0, s, (const int *)nullptr, (int64_t)P.count, P.p,
+                           P.stride, T.res + i, (int64_t)1);
+        launches += P.middle + 2;
+      }
+      const int st = launch_status("lobpcg finish");
+      if (st != SPL_OK) return st;
+      SPL_HIP(hipMemcpyAsync(L->host_res(), T.res, (size_t)nev * sizeof(double), hipMemcpyDeviceToHost, s));
+      sync();
+      for (int i = 0; i < nev; ++i) residuals[i] = sqrt(L->host_res()[i]);
+      return done(reason, nev);
+    };
+
+    // ---- start: X = orthonormalised X0, P = 0, Rayleigh-Ritz on X alone
+    SPL_HIP(hipMemsetAsync(L->status.device.get(), 0, sizeof(LStatus), s));
+    SPL_HIP(hipMemsetAsync(flags, 0, (size_t)3 * b * sizeof(int), s));
+    for (int j = 0; j < b; ++j)
+      SPL_HIP(hipMemcpyAsync(basis(j), d_X0 + (size_t)j * (size_t)ldx0 * VW, column, hipMemcpyDeviceToDevice, s));
+    SPL_HIP(hipMemsetAsync(basis(b), 0, column * (size_t)b, s));
+    for (int j = 0; j < b; ++j) settle_column(j);
+    if ((e = launch_status("lobpcg start")) != SPL_OK) return e;
+    SPL_HIP(hipMemcpyAsync(L->host_flags(), flags, (size_t)3 * b * sizeof(int), hipMemcpyDeviceToHost, s));
+    sync();
+    bool deficient = false;
+    for (int j = 0; j < b; ++j) {
+      if (L->host_flags()[j] == 2) return done(3, 0);
+      deficient = deficient || L->host_flags()[j] == 1;
+    }
+    if (deficient) return done(2, 0);
+    if ((e = launch_spmv_many(L->A, b, basis(0), n, image(0), n, 0, s)) != SPL_OK) return e;
+    spmv_columns += b;
+    ++launches;
+    int code = -1;
+    if ((e = close(b, b, which, b, &code)) != SPL_OK) return e;
+    if (code >= 0) return done(code, 0);
+
+    for (int64_t it = 0;; ++it) {
+      iterations = it;
+      const bool pre = L->pre.set();
+      residuals_of(b, [&](int i) { return image(i); }, [&](int i) { return pre ? residual(i) : basis(2 * b + i); });
+      if ((e = launch_status("lobpcg residuals")) != SPL_OK) return e;
+      SPL_HIP(hipMemcpyAsync(L->host_res(), T.res, (size_t)b * sizeof(double), hipMemcpyDeviceToHost, s));
+      sync();
+      double worst = 0.0;
+      bool converged = true, finite = true;
+      for (int i = 0; i < b; ++i) {
+        const double rn = sqrt(L->host_res()[i]);
+        finite = finite && std::isfinite(rn);
+        if (i >= nev) continue;
+        if (rn > worst) worst = rn;
+        const double bound = tol * fabs(theta[i]);
+        converged = converged && rn <= (bound > atol ? bound : atol);
+      }
+      if (!finite) return done(3, 0);
+      if (history) history[it] = worst;
+      if (converged) return finish(0);
+      if (it >= max_iter) return finish(1);
+      if (pre) {
+        for (int i = 0; i < b; ++i) {
+          if ((e = L->pre.template apply<VW>(never, n, residual(i), basis(2 * b + i), flat, s, &launches)) != SPL_OK) return e;
+          ++applications;
+        }
+      }
+      for (int j = b; j < 3 * b; ++j) settle_column(j);  // P, then W
+      if ((e = launch_spmv_many(L->A, 2 * b, basis(b), n, image(b), n, 0, s)) != SPL_OK) return e;
+      spmv_columns += 2 * b;
+      ++launches;
+      if ((e = launch_status("lobpcg iteration")) != SPL_OK) return e;
+      // iteration 0 has no P: its zero columns are not drops
+      if ((e = close(3 * b, 2 * b, which, it == 0 ? 2 * b : b, &code)) != SPL_OK) return e;
+      iterations = it + 1;
+      if (code >= 0) return done(code, 0);
+    }
+  }
+};
+
+}  // namespace
+
+// arguments checked by the caller; n > 0.  Enqueues on s and synchronises it: the outcome is read back.
+int lobpcg_solve(Lobpcg *L, int nev, int which, double tol, double atol, int64_t max_iter, const double *d_X0,
+                 int64_t ldx0, double *values, double *d_vectors, int64_t ldx, double *residuals, int64_t result[8],
+                 double *history, hipStream_t s) {
+  std::lock_guard<std::mutex> hold(L->lock);
+  int e;
+  int64_t launches = 0;
+  if (L->vw == 1) {
+    LRun<1> run(L, s);
+    e = run.solve(nev, which, tol, atol, max_iter, d_X0, ldx0, values, d_vectors, ldx, residuals, result, history);
+    launches = run.launches;
+  } else {
+    LRun<2> run(L, s);
+    e = run.solve(nev, which, tol, atol, max_iter, d_X0, ldx0, values, d_vectors, ldx, residuals, result, history);
+    launches = run.launches;
+  }
+  if (e != SPL_OK) {
+    (void)hipStreamSynchronize(s);
+    return e;
+  }
+  L->last_iterations = result[1];
+  L->last_launches = launches;
+  ++L->solves;
+  return SPL_OK;
+}
+
+void lobpcg_info(Lobpcg *L, int64_t info[8]) {
+  std::lock_guard<std::mutex> hold(L->lock);
+  info[0] = L->n;
+  info[1] = L->block;
+  info[2] = (L->vw == 2 ? 1 : 0) | L->pre.flags();
+  info[3] = (int64_t)L->bytes;
+  info[4] = L->solves;
+  info[5] = L->last_iterations;
+  info[6] = L->last_launches;
+  info[7] = 0;
+}
+
+void lobpcg_delete(Lobpcg *L) { delete_object(L); }
+
+}  // namespace spl

@@ -1,7 +1,7 @@
 // solver_core.hpp — what the iterative objects on device handles share on the host: the object (SolverCore: krylov.hip,
-// gmres.hip, eigsh.hip), the status block in device and pinned memory, and what one solve's launches have in common
-// (RunCore; LinearRun for the two that solve A x = b with a preconditioner and a history).  What differs between the
-// solvers (status structs, tables, stages, iteration bodies) is in their files.  Included by those three files only.
+// gmres.hip, eigsh.hip, lobpcg.hip), the status block in device and pinned memory, and what one solve's launches have in
+// common (RunCore; LinearRun for the two that solve A x = b with a preconditioner and a history).  What differs between
+// the solvers (status structs, tables, stages, iteration bodies) is in their files.  Included by those four files only.
 #pragma once
 
 #include "history_room.hpp"

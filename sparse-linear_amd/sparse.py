@@ -30,7 +30,8 @@ and ``DeviceMatrix.ilu0`` / ``ILU0`` (``ilu0`` from a host Matrix) produces the 
 ``DeviceMatrix.krylov`` / ``KrylovSolver`` (``cg`` / ``bicgstab`` from a host Matrix) solve ``A x = b`` with them:
 preconditioned CG and BiCGSTAB whose scalars stay on the device; ``vector_dot_dev`` is their fixed-order inner product.
 ``DeviceMatrix.gmres`` / ``GMRESSolver`` (``gmres`` from a host Matrix) is restarted GMRES for unsymmetric and indefinite
-systems with the same preconditioners; ``vector_dots_dev`` is the k-column inner product its orthogonalisation uses.
+systems with the same preconditioners; ``vector_dots_dev`` is the k-column inner product its orthogonalisation uses,
+and ``vector_gram_dev`` the k x l block of inner products of two column blocks in one pass.
 ``DeviceMatrix.amg`` / ``AMG`` (``amg`` from a host Matrix) build an aggregation multigrid hierarchy from the handle
 operations above, and its V-cycle is a preconditioner the solvers take (``M=<AMG>`` or ``M="amg"``).
 """
@@ -872,6 +873,18 @@ class DeviceMatrix(object):
         finally:
             E.free()
 
+    def lobpcg(self, X0, nev=None, largest=False, M=None, tol=1e-8, atol=0.0, maxiter=200):
+        """(values, vectors, result dict): the nev smallest (largest=True: largest) eigenpairs of this whole square
+        Hermitian handle by LOBPCG (spl_lobpcg_*) from the start block X0 (n x block, 1 <= block <= 42; nev defaults to
+        the block), with the preconditioner M (as KrylovSolver takes it) applied inside the iteration.  A block method:
+        multiple eigenvalues come with their copies"""
+        block = int(X0.shape[1]) if getattr(X0, "ndim", 0) == 2 else 0
+        L = LOBPCGSolver(self, block, M)
+        try:
+            return L.solve(X0, nev, largest, tol, atol, maxiter)
+        finally:
+            L.free()
+
     def coloring(self, seed=0):
         """the multicolour ordering of this whole square handle (spl_matrix_color): a Coloring with colors, perm and
         offsets; ``coloring().krylov(method, M)`` solves with the preconditioner built in that ordering"""
@@ -1213,6 +1226,17 @@ def vector_dots_dev(n, k, V_ptr, ldv, w_ptr, out_ptr, is_complex=False, stream=0
                                     C.c_void_p(out_ptr), C.c_void_p(stream)))
 
 
+def vector_gram_dev(n, k, l, V_ptr, ldv, W_ptr, ldw, G_ptr, ldg, upper=False, is_complex=False, stream=0):
+    """G[i][j] = <V[:, i], W[:, j]>, i < k, j < l, in ONE pass (spl_vector_gram_dev): V and W are column blocks in
+    vector_dots_dev's layout (ldv, ldw >= n), G is column major with ldg >= k; 1 <= k, l <= 128.  ``upper`` writes only
+    i <= j and leaves the rest of G alone.  Every entry is vector_dot_dev's bit for bit.  Device pointers (ints);
+    enqueues on `stream`, no sync"""
+    check("spl_vector_gram_dev",
+          lib().spl_vector_gram_dev(int(n), 2 if is_complex else 1, int(k), int(l), C.c_void_p(V_ptr), int(ldv),
+                                    C.c_void_p(W_ptr), int(ldw), C.c_void_p(G_ptr), int(ldg), 1 if upper else 0,
+                                    C.c_void_p(stream)))
+
+
 class _PreconditionedSolver(object):
     """What KrylovSolver and GMRESSolver share: the handle, the preconditioner vocabulary (None, an ``ILU0``, an ``AMG``,
     ``"jacobi"``, ``"sgs"``, ``"amg"`` or a ``(T1, mid, T2)`` triple), ``info`` and the vector plumbing of ``solve``.  A
@@ -1498,10 +1522,20 @@ def gmres(mat, b, M=None, x0=None, restart=30, rtol=1e-8, atol=0.0, maxiter=None
         G.free()
 
 
-def vector_rotate_dev(n, m, k, V_ptr, ldv, Y_ptr, ldy, out_ptr=None, ldo=0, is_complex=False, stream=0):
+def vector_rotate_dev(n, m, k, V_ptr, ldv, Y_ptr, ldy, out_ptr=None, ldo=0, is_complex=False, stream=0,
+                      Y_is_complex=False):
     """V[:, :k] <- V Y in place (out_ptr None), or out = V Y (spl_vector_rotate_dev): V has m columns of n entries, ldv
     entries apart; Y is a REAL m x k device matrix, column major, ldy >= m; 1 <= k <= m <= 128.  Column i is
-    Y[0][i] v_0 + Y[1][i] v_1 + ... summed in ascending order.  Device pointers (ints); enqueues on `stream`, no sync"""
+    Y[0][i] v_0 + Y[1][i] v_1 + ... summed in ascending order.  ``Y_is_complex``: Y holds packed pairs and V is complex
+    (spl_vector_rotate_z_dev).  Device pointers (ints); enqueues on `stream`, no sync"""
+    if Y_is_complex:
+        if not is_complex:
+            raise ValueError("vector_rotate_dev: a complex Y needs complex vectors (is_complex=True)")
+        check("spl_vector_rotate_z_dev",
+              lib().spl_vector_rotate_z_dev(int(n), 2, int(m), int(k), C.c_void_p(V_ptr), int(ldv), C.c_void_p(Y_ptr),
+                                            int(ldy), C.c_void_p(out_ptr) if out_ptr else None, int(ldo),
+                                            C.c_void_p(stream)))
+        return
     check("spl_vector_rotate_dev",
           lib().spl_vector_rotate_dev(int(n), 2 if is_complex else 1, int(m), int(k), C.c_void_p(V_ptr), int(ldv),
                                       C.c_void_p(Y_ptr), int(ldy), C.c_void_p(out_ptr) if out_ptr else None, int(ldo),
@@ -1678,6 +1712,107 @@ def eigsh(mat, nev, which="LA", ncv=None, sigma=None, M=None, tol=1e-10, atol=0.
     device (DeviceMatrix.eigsh)"""
     return mat.device_handle().eigsh(nev, which, ncv, sigma, M, tol, atol, max_restarts, v0, inner_rtol, inner_atol,
                                      inner_maxiter)
+
+
+class LOBPCGSolver(_PreconditionedSolver):
+    """Owner of a ``void *L`` from ``spl_lobpcg_create``: LOBPCG on a whole square Hermitian device handle
+    (csrc/lobpcg.hip), real or complex, with a block of ``block`` columns (1 ... 42) and the preconditioner ``M`` (as
+    KrylovSolver takes it) applied inside the iteration, one application per column and iteration.  A block method: it
+    returns every copy of a multiple eigenvalue its block has room for.  Values, vectors, residuals, history and counts
+    are those of the sequence in include/sparse_linear_hip.h bit for bit.  Converged columns are not locked."""
+    REASONS = ("converged", "max_iter", "start_rank_deficient", "non_finite")
+    INFO_KEYS = ("n", "block", "flags", "device_bytes", "solves", "iterations", "launches", "reserved")
+    RESULT_KEYS = ("reason", "iterations", "spmv_columns", "pairs", "preconditioner_applications", "jacobi_sweeps",
+                   "columns_dropped", "synchronisations")
+    _NAME = "LOBPCGSolver"
+    _CALLS = {"set_preconditioner": "spl_lobpcg_set_preconditioner",
+              "set_preconditioner_amg": "spl_lobpcg_set_preconditioner_amg", "info": "spl_lobpcg_info",
+              "free": "spl_lobpcg_free"}
+
+    def __init__(self, A, block, M=None):
+        block = int(block)
+        if not 1 <= block <= 42:
+            raise ValueError("LOBPCGSolver: block %r; 1 ... 42 is needed" % (block,))
+        self._begin(A, M)
+        self.block = block
+        check("spl_lobpcg_create", lib().spl_lobpcg_create(A.handle, block, C.byref(self._k)))
+        self.set_preconditioner(M)
+
+    @classmethod
+    def _result(cls, result, values, residuals, history):
+        out = dict(zip(cls.RESULT_KEYS, (int(v) for v in result)))
+        pairs = out["pairs"]
+        out.update(reason_name=cls.REASONS[out["reason"]], converged=out["reason"] == 0,
+                   residuals=residuals[:pairs].copy())
+        if history is not None:
+            out["history"] = history[:min(out["iterations"], len(history) - 1) + 1].copy()
+        return values[:pairs].copy(), out
+
+    @staticmethod
+    def _which(largest):
+        return _ffi.SPL_EIGSH_largest_algebraic if largest else _ffi.SPL_EIGSH_smallest_algebraic
+
+    def solve_dev(self, nev, X0_ptr, ldx0, vectors_ptr, ldx, largest=False, tol=1e-8, atol=0.0, maxiter=200, history=True,
+                  stream=0):
+        """device pointers (ints) to X0 (block columns, ldx0 entries apart; not changed) and the vectors (nev columns,
+        ldx entries apart).  Enqueues on `stream` and returns (values, result dict) after the solve's last
+        synchronisation"""
+        nev, maxiter = int(nev), int(maxiter)
+        values, residuals = np.zeros(max(nev, 1), dtype=F64), np.zeros(max(nev, 1), dtype=F64)
+        result = np.zeros(8, dtype=I64)
+        hist = np.zeros(max(maxiter, 0) + 1, dtype=F64) if history else None
+        check("spl_lobpcg_solve_dev",
+              lib().spl_lobpcg_solve_dev(self.handle, nev, self._which(largest), float(tol), float(atol), maxiter,
+                                         C.c_void_p(X0_ptr), int(ldx0), p_f64(values), C.c_void_p(vectors_ptr), int(ldx),
+                                         p_f64(residuals), _ffi.p_i64(result), p_f64(hist) if history else None,
+                                         C.c_void_p(stream)))
+        return self._result(result, values, residuals, hist)
+
+    def solve(self, X0, nev=None, largest=False, tol=1e-8, atol=0.0, maxiter=200):
+        """(values, vectors, result dict): X0 is the start block, n x block, a numpy array or a torch tensor on the device
+        (the vectors are one then and the solve runs on torch's current stream); float64 on a real object, complex128
+        on a complex one.  nev: the pairs wanted, default the whole block"""
+        where = "LOBPCGSolver.solve"
+        inf = self.info()
+        n, cplx, block = inf["n"], inf["complex"], inf["block"]
+        nev, maxiter = block if nev is None else int(nev), int(maxiter)
+        try:
+            import torch
+            is_tensor = isinstance(X0, torch.Tensor)
+        except ImportError:  # pragma: no cover
+            is_tensor = False
+        if is_tensor:
+            want = torch.complex128 if cplx else torch.float64
+            if not (X0.is_cuda and X0.dtype == want and tuple(X0.shape) == (n, block)):
+                _oops(where, "the start must be a device tensor of %d x %d %s entries" % (n, block, want))
+            with torch.cuda.device(X0.device):
+                start = X0.T.contiguous()  # one column after the other
+                X = torch.zeros((max(nev, 1), max(n, 1)), dtype=want, device=X0.device)
+                values, res = self.solve_dev(nev, start.data_ptr(), max(n, 1), X.data_ptr(), max(n, 1), largest, tol, atol,
+                                             maxiter, True, torch.cuda.current_stream().cuda_stream)
+            return values, X[:res["pairs"], :n].T, res
+        want = C128 if cplx else F64
+        start = np.asarray(X0)
+        if start.dtype != want or start.shape != (n, block):
+            _oops(where, "a start of dtype %s and shape %s; %d x %d %s entries are needed"
+                  % (start.dtype, start.shape, n, block, np.dtype(want)))
+        start = np.ascontiguousarray(start.T)
+        X = np.zeros((max(nev, 1), max(n, 1)), dtype=want)
+        values, residuals = np.zeros(max(nev, 1), dtype=F64), np.zeros(max(nev, 1), dtype=F64)
+        result = np.zeros(8, dtype=I64)
+        hist = np.zeros(max(maxiter, 0) + 1, dtype=F64)
+        check("spl_lobpcg_solve",
+              lib().spl_lobpcg_solve(self.handle, nev, self._which(largest), float(tol), float(atol), maxiter,
+                                     p_f64(start.view(F64)), max(n, 1), p_f64(values), p_f64(X.view(F64)), max(n, 1),
+                                     p_f64(residuals), _ffi.p_i64(result), p_f64(hist)))
+        values, res = self._result(result, values, residuals, hist)
+        return values, X[:res["pairs"], :n].T.copy(), res
+
+
+def lobpcg(mat, X0, nev=None, largest=False, M=None, tol=1e-8, atol=0.0, maxiter=200):
+    """(values, vectors, result dict): the nev smallest (or largest) eigenpairs of the Hermitian host Matrix `mat` by
+    LOBPCG on the device from the start block X0 (DeviceMatrix.lobpcg)"""
+    return mat.device_handle().lobpcg(X0, nev, largest, M, tol, atol, maxiter)
 
 
 def _krylov(method, mat, b, M, x0, rtol, atol, maxiter):
