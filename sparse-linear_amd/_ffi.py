@@ -5,6 +5,7 @@ The shared library is the product: if it is missing, every operation raises
 """
 import ctypes as C
 import os
+import weakref
 
 import numpy as np
 
@@ -262,6 +263,34 @@ def check(where, status):
         detail = lib().spl_last_error().decode() if status == SPL_ERROR_device else ""
         raise SparseLinearError(where, status, detail)
     return status
+
+
+class Handle(object):
+    """Owner of a ``void *`` object of the library, freed through ``void **`` by the call named ``free_name``
+    (UMFPACK style: Umfpack.hs:63-65), by ``free()`` or by the collector, whichever comes first.  ``handle`` is what the
+    library's calls take; once freed it raises ``SPL_ERROR_invalid_handle`` in the owner's name (``_NAME``, or the
+    class name)."""
+    _NAME = None
+
+    def __init__(self, free_name, value=None):
+        self._h = C.c_void_p(value)
+        self._finalizer = weakref.finalize(self, Handle._free, self._h, free_name)
+
+    @staticmethod
+    def _free(h, free_name):
+        try:
+            getattr(lib(), free_name)(C.byref(h))
+        except Exception:  # interpreter shutdown
+            pass
+
+    def free(self):
+        self._finalizer()
+
+    @property
+    def handle(self):
+        if not self._h.value:
+            raise SparseLinearError(self._NAME or type(self).__name__, SPL_ERROR_invalid_handle)
+        return self._h
 
 
 def device_count():

@@ -90,29 +90,40 @@ inline bool same_shape(const ObjectHead &a, const ObjectHead &b) {
   return a.n == b.n && a.vw == b.vw && a.device == b.device;
 }
 
-// The triangular parts and the diagonal of a preconditioner for the solver S: out[i] is the object behind T1 / T2, or
-// nullptr for NULL (the identity)
-int preconditioner_parts(const ObjectHead &S, void *T1, const double *d_mid, void *T2, TriSolver *out[2]) {
+// spl_*_set_preconditioner: the triangular parts and the diagonal of a preconditioner for the solver behind h; the
+// object behind T1 / T2, or nullptr for NULL (the identity), goes to set()
+template <typename T>
+int set_preconditioner_of(void *h, T *(*as)(void *), void (*set)(T *, TriSolver *, const double *, TriSolver *), void *T1,
+                          const double *d_mid, void *T2) {
+  T *S = as(h);
+  if (!S) return SPL_ERROR_invalid_handle;
   void *given[2] = {T1, T2};
+  TriSolver *parts[2] = {nullptr, nullptr};
   for (int i = 0; i < 2; ++i) {
-    out[i] = nullptr;
     if (!given[i]) continue;
-    out[i] = as_trisolver(given[i]);
-    if (!out[i]) return SPL_ERROR_invalid_handle;
+    parts[i] = as_trisolver(given[i]);
+    if (!parts[i]) return SPL_ERROR_invalid_handle;
   }
-  if ((uintptr_t)d_mid % (uintptr_t)(8 * S.vw) != 0) return SPL_ERROR_argument_missing;
+  if ((uintptr_t)d_mid % (uintptr_t)(8 * head(S).vw) != 0) return SPL_ERROR_argument_missing;
   for (int i = 0; i < 2; ++i)
-    if (out[i] && !same_shape(head(out[i]), S)) return SPL_ERROR_dimension_mismatch;
+    if (parts[i] && !same_shape(head(parts[i]), head(S))) return SPL_ERROR_dimension_mismatch;
+  set(S, parts[0], d_mid, parts[1]);
   return SPL_OK;
 }
 
-// M is borrowed and may serve several solvers; NULL takes the preconditioner away (*out = nullptr)
-int preconditioner_amg(const ObjectHead &S, void *M, Amg **out) {
-  *out = nullptr;
-  if (!M) return SPL_OK;
-  *out = as_amg(M);
-  if (!*out) return SPL_ERROR_invalid_handle;
-  return same_shape(head(*out), S) ? SPL_OK : SPL_ERROR_dimension_mismatch;
+// spl_*_set_preconditioner_amg: M is borrowed and may serve several solvers; NULL takes the preconditioner away
+template <typename T>
+int set_preconditioner_amg_of(void *h, T *(*as)(void *), void (*set)(T *, Amg *), void *M) {
+  T *S = as(h);
+  if (!S) return SPL_ERROR_invalid_handle;
+  Amg *P = nullptr;
+  if (M) {
+    P = as_amg(M);
+    if (!P) return SPL_ERROR_invalid_handle;
+    if (!same_shape(head(P), head(S))) return SPL_ERROR_dimension_mismatch;
+  }
+  set(S, P);
+  return SPL_OK;
 }
 
 // what the solve calls of CG, BiCGSTAB and GMRES refuse before anything else is looked at; outputs: none of the
@@ -174,6 +185,65 @@ int with_host_vectors(int device, size_t count, size_t slots, const double *up0,
     if (down) SPL_HIP(hipMemcpyAsync(down, d.get() + down_slot * count, count * sizeof(double), hipMemcpyDeviceToHost, s));
     SPL_HIP(hipStreamSynchronize(s));
     return SPL_OK;
+  });
+}
+
+// The same for the two eigensolvers: the k columns of `up`, ld entries apart, go up to the first k slots;
+// run(block, vectors, stream) with `vectors` the nev slots behind them; then the result[3] columns found come down to
+// `down`, ldx entries apart
+template <typename Run>
+int with_host_columns(const ObjectHead &o, int k, const double *up, int64_t ld, int nev, double *down, int64_t ldx,
+                      const int64_t *result, Run &&run) {
+  const size_t count = (size_t)o.n * (size_t)o.vw;
+  return with_host_vectors(o.device, count, (size_t)k + (size_t)nev, up, nullptr, 0, nullptr, [&](double *d, hipStream_t s) {
+    for (int j = 1; j < k; ++j)
+      SPL_HIP(hipMemcpyAsync(d + (size_t)j * count, up + (size_t)j * (size_t)ld * (size_t)o.vw, count * sizeof(double),
+                             hipMemcpyHostToDevice, s));
+    double *d_vectors = d + (size_t)k * count;
+    const int st = run(d, d_vectors, s);
+    if (st != SPL_OK) return st;
+    for (int64_t i = 0; i < result[3]; ++i)
+      SPL_HIP(hipMemcpyAsync(down + (size_t)i * (size_t)ldx * (size_t)o.vw, d_vectors + (size_t)i * count,
+                             count * sizeof(double), hipMemcpyDeviceToHost, s));
+    return SPL_OK;
+  });
+}
+
+// What the solve calls of Lanczos and LOBPCG refuse before the vectors are looked at.  columns: ncv or the block; the
+// solve returns up to that less `spare` pairs, in one of the orders 0 ... which_most (SPL_EIGSH_*), and needs at least
+// `least_rounds` restarts or iterations
+template <typename T>
+int check_eigen_solve(const T *S, int (*columns)(const T *), int spare, int which_most, int64_t least_rounds, int nev,
+                      int which, double tol, double atol, int64_t rounds, const double *values, const double *residuals,
+                      const int64_t *result, const double *history) {
+  if (!S) return SPL_ERROR_invalid_handle;
+  if (!values || !residuals || !result) return SPL_ERROR_argument_missing;
+  if (rounds < least_rounds) return SPL_ERROR_n_nonpositive;
+  if (nev < 1 || nev > columns(S) - spare || (int64_t)columns(S) > head(S).n || which < 0 || which > which_most ||
+      !(tol >= 0.0) || !(atol >= 0.0))
+    return SPL_ERROR_argument_missing;  // a NaN is refused too
+  if (history && rounds >= ((int64_t)1 << 31)) return SPL_ERROR_index_overflow;
+  return SPL_OK;
+}
+
+// spl_vector_rotate_dev and, with y_complex, spl_vector_rotate_z_dev: a complex Y makes a complex result
+int rotate_checked(int64_t n, int value_width, int m, int k, double *d_V, int64_t ldv, const double *d_Y, int ldy,
+                   double *d_out, int64_t ldo, void *stream, bool y_complex) {
+  if (n < 0) return SPL_ERROR_n_nonpositive;
+  if (value_width != 2 && (y_complex || value_width != 1)) return SPL_ERROR_argument_missing;
+  if (m < 1 || m > 128 || k < 1 || k > m || ldv < n || ldy < m || (d_out && ldo < n)) return SPL_ERROR_argument_missing;
+  if (n > 0 && (!d_V || !d_Y)) return SPL_ERROR_argument_missing;
+  const uintptr_t entry = (uintptr_t)(8 * value_width);  // the kernel loads and stores whole entries; Y double by double
+  if ((uintptr_t)d_V % entry != 0 || (uintptr_t)d_Y % sizeof(double) != 0 || (uintptr_t)d_out % entry != 0)
+    return SPL_ERROR_argument_missing;
+  if (d_out && n > 0) {  // the result beside V, not over it
+    const uintptr_t v0 = (uintptr_t)d_V, v1 = v0 + ((uintptr_t)(m - 1) * (uintptr_t)ldv + (uintptr_t)n) * entry;
+    const uintptr_t o0 = (uintptr_t)d_out, o1 = o0 + ((uintptr_t)(k - 1) * (uintptr_t)ldo + (uintptr_t)n) * entry;
+    if (o0 < v1 && v0 < o1) return SPL_ERROR_argument_missing;
+  }
+  return guarded([&]() -> int {
+    (void)current_device();
+    return vector_rotate(n, value_width, m, k, d_V, ldv, d_Y, ldy, d_out, ldo, as_stream(stream), y_complex);
   });
 }
 
@@ -1739,13 +1809,7 @@ int spl_krylov_create(void *A, int method, void **K) {
 }
 
 int spl_krylov_set_preconditioner(void *K, void *T1, const double *d_mid, void *T2) {
-  Krylov *S = as_krylov(K);
-  if (!S) return SPL_ERROR_invalid_handle;
-  TriSolver *parts[2];
-  const int refused = preconditioner_parts(head(S), T1, d_mid, T2, parts);
-  if (refused != SPL_OK) return refused;
-  krylov_set_preconditioner(S, parts[0], d_mid, parts[1]);
-  return SPL_OK;
+  return set_preconditioner_of(K, as_krylov, krylov_set_preconditioner, T1, d_mid, T2);
 }
 
 int spl_krylov_solve_dev(void *K, const double *d_b, double *d_x, int use_x0, double rtol, double atol, int64_t max_iter,
@@ -1899,13 +1963,7 @@ void spl_amg_free(void **M) { free_object(M, as_amg, amg_delete); }
 
 // M is borrowed and may serve several solvers; NULL takes the preconditioner away
 int spl_krylov_set_preconditioner_amg(void *K, void *M) {
-  Krylov *S = as_krylov(K);
-  if (!S) return SPL_ERROR_invalid_handle;
-  Amg *P = nullptr;
-  const int refused = preconditioner_amg(head(S), M, &P);
-  if (refused != SPL_OK) return refused;
-  krylov_set_preconditioner_amg(S, P);
-  return SPL_OK;
+  return set_preconditioner_amg_of(K, as_krylov, krylov_set_preconditioner_amg, M);
 }
 
 // ---- restarted GMRES on handles and the fused multi-vector inner product (csrc/gmres.hip) -------------------------------
@@ -1954,24 +2012,12 @@ int spl_gmres_create(void *A, int restart, void **G) {
 }
 
 int spl_gmres_set_preconditioner(void *G, void *T1, const double *d_mid, void *T2) {
-  Gmres *S = as_gmres(G);
-  if (!S) return SPL_ERROR_invalid_handle;
-  TriSolver *parts[2];
-  const int refused = preconditioner_parts(head(S), T1, d_mid, T2, parts);
-  if (refused != SPL_OK) return refused;
-  gmres_set_preconditioner(S, parts[0], d_mid, parts[1]);
-  return SPL_OK;
+  return set_preconditioner_of(G, as_gmres, gmres_set_preconditioner, T1, d_mid, T2);
 }
 
 // M is borrowed and may serve several solvers; NULL takes the preconditioner away
 int spl_gmres_set_preconditioner_amg(void *G, void *M) {
-  Gmres *S = as_gmres(G);
-  if (!S) return SPL_ERROR_invalid_handle;
-  Amg *P = nullptr;
-  const int refused = preconditioner_amg(head(S), M, &P);
-  if (refused != SPL_OK) return refused;
-  gmres_set_preconditioner_amg(S, P);
-  return SPL_OK;
+  return set_preconditioner_amg_of(G, as_gmres, gmres_set_preconditioner_amg, M);
 }
 
 int spl_gmres_solve_dev(void *G, const double *d_b, double *d_x, int use_x0, double rtol, double atol, int64_t max_iter,
@@ -2019,43 +2065,13 @@ void spl_gmres_free(void **G) { free_object(G, as_gmres, gmres_delete); }
 // ---- thick-restart Lanczos on handles and the in-place basis rotation (csrc/eigsh.hip) ----------------------------------
 int spl_vector_rotate_dev(int64_t n, int value_width, int m, int k, double *d_V, int64_t ldv, const double *d_Y, int ldy,
                           double *d_out, int64_t ldo, void *stream) {
-  if (n < 0) return SPL_ERROR_n_nonpositive;
-  if (value_width != 1 && value_width != 2) return SPL_ERROR_argument_missing;
-  if (m < 1 || m > 128 || k < 1 || k > m || ldv < n || ldy < m || (d_out && ldo < n)) return SPL_ERROR_argument_missing;
-  if (n > 0 && (!d_V || !d_Y)) return SPL_ERROR_argument_missing;
-  const uintptr_t entry = (uintptr_t)(8 * value_width);  // the kernel loads and stores whole entries
-  if ((uintptr_t)d_V % entry != 0 || (uintptr_t)d_Y % sizeof(double) != 0 || (uintptr_t)d_out % entry != 0)
-    return SPL_ERROR_argument_missing;
-  if (d_out && n > 0) {  // the result beside V, not over it
-    const uintptr_t v0 = (uintptr_t)d_V, v1 = v0 + ((uintptr_t)(m - 1) * (uintptr_t)ldv + (uintptr_t)n) * entry;
-    const uintptr_t o0 = (uintptr_t)d_out, o1 = o0 + ((uintptr_t)(k - 1) * (uintptr_t)ldo + (uintptr_t)n) * entry;
-    if (o0 < v1 && v0 < o1) return SPL_ERROR_argument_missing;
-  }
-  return guarded([&]() -> int {
-    (void)current_device();
-    return vector_rotate(n, value_width, m, k, d_V, ldv, d_Y, ldy, d_out, ldo, as_stream(stream));
-  });
+  return rotate_checked(n, value_width, m, k, d_V, ldv, d_Y, ldy, d_out, ldo, stream, false);
 }
 
 // the same with a complex Y (packed pairs) on complex vectors
 int spl_vector_rotate_z_dev(int64_t n, int value_width, int m, int k, double *d_V, int64_t ldv, const double *d_Y, int ldy,
                             double *d_out, int64_t ldo, void *stream) {
-  if (n < 0) return SPL_ERROR_n_nonpositive;
-  if (value_width != 2) return SPL_ERROR_argument_missing;  // a complex Y makes a complex result
-  if (m < 1 || m > 128 || k < 1 || k > m || ldv < n || ldy < m || (d_out && ldo < n)) return SPL_ERROR_argument_missing;
-  if (n > 0 && (!d_V || !d_Y)) return SPL_ERROR_argument_missing;
-  const uintptr_t entry = 16;  // the kernel loads and stores whole entries; Y is read double by double
-  if ((uintptr_t)d_V % entry != 0 || (uintptr_t)d_Y % sizeof(double) != 0 || (uintptr_t)d_out % entry != 0)
-    return SPL_ERROR_argument_missing;
-  if (d_out && n > 0) {  // the result beside V, not over it
-    const uintptr_t v0 = (uintptr_t)d_V, v1 = v0 + ((uintptr_t)(m - 1) * (uintptr_t)ldv + (uintptr_t)n) * entry;
-    const uintptr_t o0 = (uintptr_t)d_out, o1 = o0 + ((uintptr_t)(k - 1) * (uintptr_t)ldo + (uintptr_t)n) * entry;
-    if (o0 < v1 && v0 < o1) return SPL_ERROR_argument_missing;
-  }
-  return guarded([&]() -> int {
-    (void)current_device();
-    return vector_rotate(n, 2, m, k, d_V, ldv, d_Y, ldy, d_out, ldo, as_stream(stream), true);
-  });
+  return rotate_checked(n, value_width, m, k, d_V, ldv, d_Y, ldy, d_out, ldo, stream, true);
 }
 
 // A is borrowed: the object keeps the pointer, its ncv + 2 vectors and its tables
@@ -2085,26 +2101,12 @@ int spl_eigsh_set_inverse(void *E, void *K, double sigma, double rtol, double at
   return SPL_OK;
 }
 
-namespace {
-// what both solve calls refuse before the vectors are looked at
-int check_eigsh_solve(const Eigsh *S, int nev, int which, double tol, double atol, int64_t max_restarts,
-                      const double *values, const double *residuals, const int64_t *result, const double *history) {
-  if (!S) return SPL_ERROR_invalid_handle;
-  if (!values || !residuals || !result) return SPL_ERROR_argument_missing;
-  if (max_restarts < 1) return SPL_ERROR_n_nonpositive;
-  if (nev < 1 || nev >= eigsh_ncv(S) || (int64_t)eigsh_ncv(S) > head(S).n || which < 0 || which > 2 || !(tol >= 0.0) ||
-      !(atol >= 0.0))
-    return SPL_ERROR_argument_missing;  // a NaN is refused too
-  if (history && max_restarts >= ((int64_t)1 << 31)) return SPL_ERROR_index_overflow;
-  return SPL_OK;
-}
-}  // namespace
-
 int spl_eigsh_solve_dev(void *E, int nev, int which, double tol, double atol, int64_t max_restarts, const double *d_v0,
                         double *values, double *d_vectors, int64_t ldx, double *residuals, int64_t result[6],
                         double *history, void *stream) {
   Eigsh *S = as_eigsh(E);
-  const int refused = check_eigsh_solve(S, nev, which, tol, atol, max_restarts, values, residuals, result, history);
+  const int refused = check_eigen_solve(S, eigsh_ncv, 1, SPL_EIGSH_largest_magnitude, 1, nev, which, tol, atol,
+                                        max_restarts, values, residuals, result, history);
   if (refused != SPL_OK) return refused;
   const ObjectHead &o = head(S);
   if (!d_v0 || !d_vectors || ldx < o.n) return SPL_ERROR_argument_missing;
@@ -2121,20 +2123,13 @@ int spl_eigsh_solve_dev(void *E, int nev, int which, double tol, double atol, in
 int spl_eigsh_solve(void *E, int nev, int which, double tol, double atol, int64_t max_restarts, const double *v0,
                     double *values, double *vectors, int64_t ldx, double *residuals, int64_t result[6], double *history) {
   Eigsh *S = as_eigsh(E);
-  const int refused = check_eigsh_solve(S, nev, which, tol, atol, max_restarts, values, residuals, result, history);
+  const int refused = check_eigen_solve(S, eigsh_ncv, 1, SPL_EIGSH_largest_magnitude, 1, nev, which, tol, atol,
+                                        max_restarts, values, residuals, result, history);
   if (refused != SPL_OK) return refused;
   const ObjectHead &o = head(S);
   if (!v0 || !vectors || ldx < o.n) return SPL_ERROR_argument_missing;
-  const size_t count = (size_t)o.n * (size_t)o.vw;
-  return with_host_vectors(o.device, count, (size_t)nev + 1, v0, nullptr, 0, nullptr, [&](double *d, hipStream_t s) {
-    double *d_vectors = d + count;
-    const int st = eigsh_solve(S, nev, which, tol, atol, max_restarts, d, values, d_vectors, o.n, residuals, result,
-                               history, s);
-    if (st != SPL_OK) return st;
-    for (int64_t i = 0; i < result[3]; ++i)  // the columns found, ldx entries apart
-      SPL_HIP(hipMemcpyAsync(vectors + (size_t)i * (size_t)ldx * (size_t)o.vw, d_vectors + (size_t)i * count,
-                             count * sizeof(double), hipMemcpyDeviceToHost, s));
-    return SPL_OK;
+  return with_host_columns(o, 1, v0, o.n, nev, vectors, ldx, result, [&](double *d, double *d_vectors, hipStream_t s) {
+    return eigsh_solve(S, nev, which, tol, atol, max_restarts, d, values, d_vectors, o.n, residuals, result, history, s);
   });
 }
 
@@ -2155,46 +2150,20 @@ int spl_lobpcg_create(void *A, int block, void **L) {
 }
 
 int spl_lobpcg_set_preconditioner(void *L, void *T1, const double *d_mid, void *T2) {
-  Lobpcg *S = as_lobpcg(L);
-  if (!S) return SPL_ERROR_invalid_handle;
-  TriSolver *parts[2];
-  const int refused = preconditioner_parts(head(S), T1, d_mid, T2, parts);
-  if (refused != SPL_OK) return refused;
-  lobpcg_set_preconditioner(S, parts[0], d_mid, parts[1]);
-  return SPL_OK;
+  return set_preconditioner_of(L, as_lobpcg, lobpcg_set_preconditioner, T1, d_mid, T2);
 }
 
 // M is borrowed and may serve several solvers; NULL takes the preconditioner away
 int spl_lobpcg_set_preconditioner_amg(void *L, void *M) {
-  Lobpcg *S = as_lobpcg(L);
-  if (!S) return SPL_ERROR_invalid_handle;
-  Amg *P = nullptr;
-  const int refused = preconditioner_amg(head(S), M, &P);
-  if (refused != SPL_OK) return refused;
-  lobpcg_set_preconditioner_amg(S, P);
-  return SPL_OK;
+  return set_preconditioner_amg_of(L, as_lobpcg, lobpcg_set_preconditioner_amg, M);
 }
-
-namespace {
-// what both solve calls refuse before the vectors are looked at
-int check_lobpcg_solve(const Lobpcg *S, int nev, int which, double tol, double atol, int64_t max_iter,
-                       const double *values, const double *residuals, const int64_t *result, const double *history) {
-  if (!S) return SPL_ERROR_invalid_handle;
-  if (!values || !residuals || !result) return SPL_ERROR_argument_missing;
-  if (max_iter < 0) return SPL_ERROR_n_nonpositive;
-  if (nev < 1 || nev > lobpcg_block(S) || (int64_t)lobpcg_block(S) > head(S).n ||
-      (which != SPL_EIGSH_largest_algebraic && which != SPL_EIGSH_smallest_algebraic) || !(tol >= 0.0) || !(atol >= 0.0))
-    return SPL_ERROR_argument_missing;  // a NaN is refused too
-  if (history && max_iter >= ((int64_t)1 << 31)) return SPL_ERROR_index_overflow;
-  return SPL_OK;
-}
-}  // namespace
 
 int spl_lobpcg_solve_dev(void *L, int nev, int which, double tol, double atol, int64_t max_iter, const double *d_X0,
                          int64_t ldx0, double *values, double *d_vectors, int64_t ldx, double *residuals,
                          int64_t result[8], double *history, void *stream) {
   Lobpcg *S = as_lobpcg(L);
-  const int refused = check_lobpcg_solve(S, nev, which, tol, atol, max_iter, values, residuals, result, history);
+  const int refused = check_eigen_solve(S, lobpcg_block, 0, SPL_EIGSH_smallest_algebraic, 0, nev, which, tol, atol,
+                                        max_iter, values, residuals, result, history);
   if (refused != SPL_OK) return refused;
   const ObjectHead &o = head(S);
   if (!d_X0 || !d_vectors || ldx0 < o.n || ldx < o.n) return SPL_ERROR_argument_missing;
@@ -2213,29 +2182,16 @@ int spl_lobpcg_solve(void *L, int nev, int which, double tol, double atol, int64
                      int64_t ldx0, double *values, double *vectors, int64_t ldx, double *residuals, int64_t result[8],
                      double *history) {
   Lobpcg *S = as_lobpcg(L);
-  const int refused = check_lobpcg_solve(S, nev, which, tol, atol, max_iter, values, residuals, result, history);
+  const int refused = check_eigen_solve(S, lobpcg_block, 0, SPL_EIGSH_smallest_algebraic, 0, nev, which, tol, atol,
+                                        max_iter, values, residuals, result, history);
   if (refused != SPL_OK) return refused;
   const ObjectHead &o = head(S);
   if (!X0 || !vectors || ldx0 < o.n || ldx < o.n) return SPL_ERROR_argument_missing;
-  const size_t count = (size_t)o.n * (size_t)o.vw;
-  const int block = lobpcg_block(S);
-  return guarded([&]() -> int {
-    DeviceGuard g(o.device);
-    hipStream_t s = nullptr;
-    DBuf<double> d(((size_t)block + (size_t)nev) * count);
-    for (int j = 0; j < block; ++j)
-      SPL_HIP(hipMemcpyAsync(d.get() + (size_t)j * count, X0 + (size_t)j * (size_t)ldx0 * (size_t)o.vw,
-                             count * sizeof(double), hipMemcpyHostToDevice, s));
-    double *d_vectors = d.get() + (size_t)block * count;
-    const int st = lobpcg_solve(S, nev, which, tol, atol, max_iter, d.get(), o.n, values, d_vectors, o.n, residuals,
-                                result, history, s);
-    if (st != SPL_OK) return st;
-    for (int64_t i = 0; i < result[3]; ++i)  // the columns found, ldx entries apart
-      SPL_HIP(hipMemcpyAsync(vectors + (size_t)i * (size_t)ldx * (size_t)o.vw, d_vectors + (size_t)i * count,
-                             count * sizeof(double), hipMemcpyDeviceToHost, s));
-    SPL_HIP(hipStreamSynchronize(s));
-    return SPL_OK;
-  });
+  return with_host_columns(o, lobpcg_block(S), X0, ldx0, nev, vectors, ldx, result,
+                           [&](double *d, double *d_vectors, hipStream_t s) {
+                             return lobpcg_solve(S, nev, which, tol, atol, max_iter, d, o.n, values, d_vectors, o.n,
+                                                 residuals, result, history, s);
+                           });
 }
 
 int spl_lobpcg_info(void *L, int64_t info[8]) { return info_of(L, as_lobpcg, lobpcg_info, info); }

@@ -10,15 +10,17 @@
 // synchronises anyway, and the host reads the status block behind every step.
 //
 // The close is the host's: one synchronisation per cycle brings the two tables down, the projected matrix (an arrow head
-// from the restart and a tridiagonal tail) is diagonalised by cyclic Jacobi in plain C++ (-ffp-contract=off: a product
-// and a sum are rounded apart on the host too), and the restart V[:, :k] <- V Y is the rotate kernel IN PLACE: a row tile
-// of the basis is staged in LDS, so every input of a row is read before any output of that row is written, and no second
-// basis exists.  No kernel waits for another workgroup, there is no floating-point atomic and no captured graph.
+// from the restart and a tridiagonal tail) goes through the Ritz step of ritz_jacobi.hpp (cyclic Jacobi and the order, in
+// plain C++; -ffp-contract=off: a product and a sum are rounded apart on the host too), and the restart
+// V[:, :k] <- V Y is the rotate kernel IN PLACE: a row tile of the basis is staged in LDS, so every input of a row is
+// read before any output of that row is written, and no second basis exists.  No kernel waits for another workgroup,
+// there is no floating-point atomic and no captured graph.
 #include <algorithm>
 #include <cmath>
 #include <vector>
 
 #include "krylov_basis.hpp"
+#include "ritz_jacobi.hpp"
 #include "solver_core.hpp"
 
 namespace spl {
@@ -28,7 +30,6 @@ namespace {
 constexpr int kRotateCols = 4;              // output columns a lane carries through one walk over the tile's columns
 constexpr int kRotateRowsLog2 = 6;          // rows of a tile: 64; SPL_EIGSH_ROTATE_ROWS = 16, 32, 64
 constexpr size_t kRotateLds = 64 * 1024;    // bytes of LDS a tile may take
-constexpr int kMaxSweeps = 60;
 
 // ---- V[:, :k] <- V Y ---------------------------------------------------------------------------------------------------
 // A workgroup takes tiles of R = 2^rows_log2 consecutive rows.  Load: lane t takes row t mod R of the columns t / R,
@@ -175,16 +176,7 @@ inline ETables etables_at(double *base, int m) {
   return T;
 }
 
-// ---- the vector kernels ---------------------------------------------------------------------------------------------------
-// partials of Re<v,v>
-template <int VW>
-__global__ __launch_bounds__(kLanes) void norm_kernel(int64_t n, const double *__restrict__ v, double *part) {
-  chunk_partials<1>(n, part, 0, [&](int64_t i, double *acc) {
-    const Val<VW> vi = load_val<VW>(v, i);
-    acc[0] = acc[0] + mul(conj_of(vi), vi).re;
-  });
-}
-
+// ---- the vector kernels (norm_kernel and residual_kernel: krylov_basis.hpp) -------------------------------------------
 // out = in / *d, part by part: `count` doubles; in and out may be the same array
 __global__ __launch_bounds__(kLanes) void divide_kernel(const int *stop, int64_t count, const double *d, const double *in,
                                                         double *out) {
@@ -195,26 +187,12 @@ __global__ __launch_bounds__(kLanes) void divide_kernel(const int *stop, int64_t
   for (; i < count; i += stride) out[i] = in[i] / by;
 }
 
-// r = ax - lambda x, one product part by part and one difference per entry; partials of Re<r,r>
-template <int VW>
-__global__ __launch_bounds__(kLanes) void residual_kernel(int64_t n, const double *__restrict__ ax,
-                                                          const double *__restrict__ x, double lambda, double *part) {
-  chunk_partials<1>(n, part, 0, [&](int64_t i, double *acc) {
-    const Val<VW> ri = sub(load_val<VW>(ax, i), scaled(lambda, load_val<VW>(x, i)));
-    acc[0] = acc[0] + mul(conj_of(ri), ri).re;
-  });
-}
-
 // ---- the scalar kernels: ONE workgroup each ------------------------------------------------------------------------------
 // eta = sqrt(Re<v0,v0>) from the last partials, and what it decides
 __global__ __launch_bounds__(kLanes) void start_kernel(EStatus *st, const double *part, int count) {
-  __shared__ double lds[kLanes];
-  const int t = threadIdx.x;
-  double f[1] = {0.0};
-  for (int i = t; i < count; i += kLanes) f[0] = f[0] + part[i];
-  lane_tree<1>(f, lds);
-  if (t != 0) return;
-  const double eta = sqrt(f[0]);
+  const double sum = sum_partials(part, count);
+  if (threadIdx.x != 0) return;
+  const double eta = sqrt(sum);
   st->eta0 = eta;
   if (!isfinite(eta)) {
     st->pending = 3 + 1;
@@ -231,13 +209,9 @@ __global__ __launch_bounds__(kLanes) void start_kernel(EStatus *st, const double
 template <int VW>
 __global__ __launch_bounds__(kLanes) void step_kernel(EStatus *st, int j, const double *part, int count, ETables T) {
   if (st->skip) return;
-  __shared__ double lds[kLanes];
-  const int t = threadIdx.x;
-  double f[1] = {0.0};
-  for (int i = t; i < count; i += kLanes) f[0] = f[0] + part[i];
-  lane_tree<1>(f, lds);
-  if (t != 0) return;
-  const double eta = sqrt(f[0]);
+  const double sum = sum_partials(part, count);
+  if (threadIdx.x != 0) return;
+  const double eta = sqrt(sum);
   const double alpha = add(load_val<VW>(T.c1, j), load_val<VW>(T.c2, j)).re;
   T.alpha[j] = alpha;
   T.beta[j] = eta;
@@ -253,52 +227,6 @@ __global__ __launch_bounds__(kLanes) void step_kernel(EStatus *st, int j, const 
     return;
   }
   st->scale = eta;
-}
-
-// ---- the close, on the host ------------------------------------------------------------------------------------------------
-// Cyclic Jacobi on the full symmetric T (m x m, T[r * m + c]) with Y = I at the start (Y[r * m + c]): T's diagonal
-// becomes the values, Y's columns the vectors.  Sweeps started, or -1 past kMaxSweeps
-int jacobi(int m, std::vector<double> &T, std::vector<double> &Y) {
-  auto at = [m](std::vector<double> &M, int r, int c) -> double & { return M[(size_t)r * m + c]; };
-  for (int r = 0; r < m; ++r)
-    for (int c = 0; c < m; ++c) at(Y, r, c) = r == c ? 1.0 : 0.0;
-  for (int sweeps = 0;; ++sweeps) {
-    bool any = false;
-    for (int p = 0; p < m && !any; ++p)
-      for (int q = p + 1; q < m; ++q)
-        if (at(T, p, q) != 0.0) { any = true; break; }
-    if (!any) return sweeps;
-    if (sweeps == kMaxSweeps) return -1;
-    for (int p = 0; p < m; ++p)
-      for (int q = p + 1; q < m; ++q) {
-        const double a = at(T, p, q);
-        if (a == 0.0) continue;
-        const double app = at(T, p, p), aqq = at(T, q, q);
-        if (fabs(app) + fabs(a) == fabs(app) && fabs(aqq) + fabs(a) == fabs(aqq)) {
-          at(T, p, q) = at(T, q, p) = 0.0;
-          continue;
-        }
-        const double tau = (aqq - app) / (2.0 * a);
-        const double den = fabs(tau) + sqrt(1.0 + tau * tau);
-        const double tt = (tau >= 0.0 ? 1.0 : -1.0) / den;
-        const double c = 1.0 / sqrt(1.0 + tt * tt), s = tt * c;
-        for (int r = 0; r < m; ++r) {
-          if (r == p || r == q) continue;
-          const double rp = at(T, r, p), rq = at(T, r, q);
-          const double np = c * rp - s * rq, nq = s * rp + c * rq;
-          at(T, r, p) = at(T, p, r) = np;
-          at(T, r, q) = at(T, q, r) = nq;
-        }
-        at(T, p, p) = app - tt * a;
-        at(T, q, q) = aqq + tt * a;
-        at(T, p, q) = at(T, q, p) = 0.0;
-        for (int r = 0; r < m; ++r) {
-          const double rp = at(Y, r, p), rq = at(Y, r, q);
-          at(Y, r, p) = c * rp - s * rq;
-          at(Y, r, q) = s * rp + c * rq;
-        }
-      }
-  }
 }
 
 }  // namespace
@@ -325,7 +253,6 @@ struct Eigsh : SolverCore {  // work: ncv + 2 vectors, the basis v_0 ... v_ncv a
   int64_t max_iter = 0;
   DBuf<double> tables;
   StatusBlock<EStatus> status;  // behind the pinned copy: alpha, beta and res, and the ncv x ncv doubles that go up
-  int64_t last_cycles = 0;
   Eigsh(const Matrix *A, int m)
       : SolverCore(kEigshMagic, A, (size_t)m + 2, fold_scratch(A->nrows_local, m * A->vw)), ncv(m),
         tables(etable_doubles(m)), status(((size_t)3 * m + (size_t)m * m) * sizeof(double)) {
@@ -378,11 +305,11 @@ struct ERun : RunCore {
 
   void start(const double *v0) {
     hipLaunchKernelGGL((norm_kernel<VW>), dim3(chunked), dim3(kLanes), 0, s, n, v0, scratch);
-    const Partials P = middle_levels(nullptr, n, 1, scratch, s);
+    const Partials P = last_level();
     hipLaunchKernelGGL(start_kernel, dim3(1), dim3(kLanes), 0, s, st, P.p, P.count);
     hipLaunchKernelGGL(divide_kernel, dim3(flat), dim3(kLanes), 0, s, skip(), n * VW, (const double *)&st->scale, v0,
                        basis(0));
-    launches += P.middle + 3;
+    launches += 3;
   }
 
   // w = OP v_j to slot j + 1; *failed: the inner solve did not converge
@@ -429,11 +356,9 @@ struct ERun : RunCore {
       const int e = launch_spmv(E->A, x, product(), 0, s);
       if (e != SPL_OK) return e;
       hipLaunchKernelGGL((residual_kernel<VW>), dim3(chunked), dim3(kLanes), 0, s, n, (const double *)product(), x,
-                         values[i], scratch);
-      const Partials P = middle_levels(nullptr, n, 1, scratch, s);
-      hipLaunchKernelGGL(fold_kernel, dim3(1, 1), dim3(kLanes), 0, s, (const int *)nullptr, (int64_t)P.count, P.p, P.stride,
-                         T.res + i, (int64_t)1);
-      launches += P.middle + 3;
+                         values[i], (double *)nullptr, scratch);
+      launches += 2;
+      fold_to(T.res + i);
     }
     const int e = launch_status("eigsh finish");
     if (e != SPL_OK) return e;
@@ -493,23 +418,12 @@ struct ERun : RunCore {
         if (j < mp - 1) Tm[(size_t)j * mp + j + 1] = Tm[(size_t)(j + 1) * mp + j] = beta[j];
       }
       const double last = beta[mp - 1];
-      const int sweeps = jacobi(mp, Tm, Y);
-      bool finite = sweeps >= 0;
-      for (int i = 0; finite && i < mp; ++i) {
-        finite = std::isfinite(Tm[(size_t)i * mp + i]);
-        for (int r = 0; finite && r < mp; ++r) finite = std::isfinite(Y[(size_t)r * mp + i]);
-      }
-      if (!finite) return done(3, 0);
+      order.resize(mp);
+      const int sweeps = ritz_step(mp, 1, which, Tm.data(), Y.data(), order.data());
+      if (sweeps < 0) return done(3, 0);
       ++cycles;
       if (sweeps > sweeps_most) sweeps_most = sweeps;
-      order.resize(mp);
-      for (int i = 0; i < mp; ++i) order[i] = i;
       auto value = [&](int i) { return Tm[(size_t)i * mp + i]; };
-      std::stable_sort(order.begin(), order.end(), [&](int a, int b) {
-        if (which == 0) return value(a) > value(b);
-        if (which == 1) return value(a) < value(b);
-        return fabs(value(a)) > fabs(value(b));
-      });
       const int pairs = nev < mp ? nev : mp;
       est.assign(mp, 0.0);
       double worst = 0.0;
@@ -556,37 +470,17 @@ int eigsh_solve(Eigsh *E, int nev, int which, double tol, double atol, int64_t m
                 double *values, double *d_vectors, int64_t ldx, double *residuals, int64_t result[6], double *history,
                 hipStream_t s) {
   std::lock_guard<std::mutex> hold(E->lock);
-  int e;
-  int64_t launches = 0;
-  if (E->vw == 1) {
-    ERun<1> run(E, s);
-    e = run.solve(nev, which, tol, atol, max_restarts, d_v0, values, d_vectors, ldx, residuals, result, history);
-    launches = run.launches;
-  } else {
-    ERun<2> run(E, s);
-    e = run.solve(nev, which, tol, atol, max_restarts, d_v0, values, d_vectors, ldx, residuals, result, history);
-    launches = run.launches;
-  }
-  if (e != SPL_OK) {
-    (void)hipStreamSynchronize(s);
+  return E->solve_and_record(s, result + 1, [&](auto width, int64_t *launches) {
+    ERun<decltype(width)::value> run(E, s);
+    const int e = run.solve(nev, which, tol, atol, max_restarts, d_v0, values, d_vectors, ldx, residuals, result, history);
+    *launches = run.launches;
     return e;
-  }
-  E->last_cycles = result[1];
-  E->last_launches = launches;
-  ++E->solves;
-  return SPL_OK;
+  });
 }
 
 void eigsh_info(Eigsh *E, int64_t info[8]) {
   std::lock_guard<std::mutex> hold(E->lock);
-  info[0] = E->n;
-  info[1] = E->ncv;
-  info[2] = (E->vw == 2 ? 1 : 0) | (E->K ? 2 : 0);
-  info[3] = (int64_t)E->bytes;
-  info[4] = E->solves;
-  info[5] = E->last_cycles;
-  info[6] = E->last_launches;
-  info[7] = 0;
+  E->fill_info(info, E->ncv, E->K ? 2 : 0);
 }
 
 int eigsh_ncv(const Eigsh *E) { return E->ncv; }

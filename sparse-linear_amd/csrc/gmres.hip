@@ -260,7 +260,6 @@ struct Gmres : SolverCore {  // work: restart + 3 vectors, the basis v_0 ... v_r
   DBuf<double> tables;
   DBuf<double> hist;  // history[it], grown with the iterations issued (room_for)
   StatusBlock<GStatus> status;
-  int64_t last_iterations = 0;
   Gmres(const Matrix *A, int m)
       : SolverCore(kGmresMagic, A, (size_t)m + 3, fold_scratch(A->nrows_local, (m > 1 ? m : 2) * A->vw)), restart(m),
         tables(table_doubles(m)) {
@@ -415,7 +414,7 @@ int solve_width(Gmres *G, const double *d_b, double *d_x, int use_x0, double rto
     SPL_HIP(hipMemcpyAsync(history, run.hist.get(), ((size_t)last.it + 1) * sizeof(double), hipMemcpyDeviceToHost, s));
     SPL_HIP(hipStreamSynchronize(s));
   }
-  G->last_iterations = last.it;
+  G->last_rounds = last.it;
   G->last_launches = run.launches;
   ++G->solves;
   return SPL_OK;
@@ -434,14 +433,7 @@ int gmres_solve(Gmres *G, const double *d_b, double *d_x, int use_x0, double rto
 
 void gmres_info(Gmres *G, int64_t info[8]) {
   std::lock_guard<std::mutex> hold(G->lock);
-  info[0] = G->n;
-  info[1] = G->restart;
-  info[2] = (G->vw == 2 ? 1 : 0) | G->pre.flags();
-  info[3] = (int64_t)G->bytes;
-  info[4] = G->solves;
-  info[5] = G->last_iterations;
-  info[6] = G->last_launches;
-  info[7] = 0;
+  G->fill_info(info, G->restart, G->pre.flags());
 }
 
 void gmres_delete(Gmres *G) { delete_object(G); }

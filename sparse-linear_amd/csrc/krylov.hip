@@ -386,7 +386,6 @@ struct Krylov : SolverCore {
   Preconditioner pre;
   DBuf<double> hist;  // |r|^2 of every iteration, grown with the iterations issued (room_for)
   StatusBlock<Status> status;
-  int64_t last_iterations = 0;
   Krylov(const Matrix *A, int m)
       : SolverCore(kKrylovMagic, A, m == SPL_KRYLOV_cg ? 4 : 8, fold_scratch(A->nrows_local, kMaxPlanes)), method(m) {
     bytes += sizeof(Status);
@@ -562,7 +561,7 @@ int solve_width(Krylov *K, const double *d_b, double *d_x, int use_x0, double rt
     SPL_HIP(hipStreamSynchronize(s));
     for (long long i = 0; i <= last.it; ++i) history[i] = sqrt(history[i]);  // |r|^2 came down: the norm is its root
   }
-  K->last_iterations = last.it;
+  K->last_rounds = last.it;
   ++K->solves;
   return SPL_OK;
 }
@@ -579,14 +578,7 @@ int krylov_solve(Krylov *K, const double *d_b, double *d_x, int use_x0, double r
 
 void krylov_info(Krylov *K, int64_t info[8]) {
   std::lock_guard<std::mutex> hold(K->lock);
-  info[0] = K->n;
-  info[1] = K->method;
-  info[2] = (K->vw == 2 ? 1 : 0) | K->pre.flags();
-  info[3] = (int64_t)K->bytes;
-  info[4] = K->solves;
-  info[5] = K->last_iterations;
-  info[6] = K->last_launches;
-  info[7] = 0;
+  K->fill_info(info, K->method, K->pre.flags());
 }
 
 void krylov_delete(Krylov *K) { delete_object(K); }

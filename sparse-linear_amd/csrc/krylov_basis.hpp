@@ -1,8 +1,10 @@
 // krylov_basis.hpp — the two basis kernels of a Gram-Schmidt step, shared by gmres.hip (restarted GMRES and
-// spl_vector_dots_dev) and eigsh.hip (thick-restart Lanczos): k inner products against a basis in ONE pass
-// (dots_kernel / dots_launch) and the update w = ((w - c_0 v_0) - c_1 v_1) - ... in one pass (update_kernel).  The
-// arithmetic is the fold of krylov_fold.hpp: every value is what k separate inner products and k separate updates would
-// give, bit for bit.  Device code and the host code that launches it; included by those two files only.
+// spl_vector_dots_dev), eigsh.hip (thick-restart Lanczos) and lobpcg.hip (LOBPCG): k inner products against a basis in
+// ONE pass (dots_kernel / dots_launch) and the update w = ((w - c_0 v_0) - c_1 v_1) - ... in one pass (update_kernel);
+// and the two first levels the eigensolvers fold to a scalar, a norm and a pair's residual (norm_kernel,
+// residual_kernel).  The arithmetic is the fold of krylov_fold.hpp: every value is what k separate inner products and
+// k separate updates would give, bit for bit.  Device code and the host code that launches it; included by those
+// three files only.
 #pragma once
 
 #include "krylov_fold.hpp"
@@ -135,6 +137,28 @@ __global__ __launch_bounds__(kLanes) void update_kernel(const int *stop, int64_t
       if (t == 0) part[c] = acc[0];
     }
   }
+}
+
+// ---- the first levels of the eigensolvers' scalars ---------------------------------------------------------------------
+// partials of Re<v,v>
+template <int VW>
+__global__ __launch_bounds__(kLanes) void norm_kernel(int64_t n, const double *__restrict__ v, double *part) {
+  chunk_partials<1>(n, part, 0, [&](int64_t i, double *acc) {
+    const Val<VW> vi = load_val<VW>(v, i);
+    acc[0] = acc[0] + mul(conj_of(vi), vi).re;
+  });
+}
+
+// r = ax - lambda x, one product part by part and one difference per entry, stored when r is given; partials of Re<r,r>
+template <int VW>
+__global__ __launch_bounds__(kLanes) void residual_kernel(int64_t n, const double *__restrict__ ax,
+                                                          const double *__restrict__ x, double lambda,
+                                                          double *__restrict__ r, double *part) {
+  chunk_partials<1>(n, part, 0, [&](int64_t i, double *acc) {
+    const Val<VW> ri = sub(load_val<VW>(ax, i), scaled(lambda, load_val<VW>(x, i)));
+    if (r) store_val(r, i, ri);
+    acc[0] = acc[0] + mul(conj_of(ri), ri).re;
+  });
 }
 
 // ---- the launches of a step --------------------------------------------------------------------------------------------

@@ -1,9 +1,9 @@
 // krylov_fold.hpp — the fixed-order fold and the value helpers shared by the Krylov solvers on device handles
 // (krylov.hip: CG, BiCGSTAB and spl_vector_dot_dev; gmres.hip: restarted GMRES and spl_vector_dots_dev; eigsh.hip:
-// thick-restart Lanczos, the last two through krylov_basis.hpp).  The
-// arithmetic contract is the one at the head of krylov.hip: chunks of 4096 entries, 256 lanes that add their 16 entries
-// in ascending order from +0.0, the halving tree, and the partials folded again by the same fold; the order is a function
-// of the length alone.  Device code and the host code that launches the levels; included by those files only.
+// thick-restart Lanczos; lobpcg.hip: LOBPCG; the last three through krylov_basis.hpp).  The arithmetic contract is the
+// one at the head of krylov.hip: chunks of 4096 entries, 256 lanes that add their 16 entries in ascending order from
+// +0.0, the halving tree, and the partials folded again by the same fold; the order is a function of the length alone.
+// Device code and the host code that launches the levels; included by those files only.
 #pragma once
 
 #include <math.h>
@@ -81,6 +81,17 @@ __device__ inline void lane_tree(double (&acc)[NV], double *lds) {
     }
   }
   __syncthreads();  // lds is written again for the workgroup's next chunk
+}
+
+// How a ONE-workgroup kernel behind the fold opens: the sum of the `count` partials of the last level, lane t taking
+// t, t + 256, ... in ascending order from +0.0, then the tree.  Every thread of the workgroup must be here (the tree
+// has barriers); lane 0 has the sum and goes on alone.
+__device__ inline double sum_partials(const double *part, int count) {
+  __shared__ double lds[kLanes];
+  double f[1] = {0.0};
+  for (int i = threadIdx.x; i < count; i += kLanes) f[0] = f[0] + part[i];
+  lane_tree<1>(f, lds);
+  return f[0];
 }
 
 // The chunks of [0, n) by the workgroups of the launch: body(i, acc) does the entry-wise work of entry i and adds its

@@ -4,13 +4,13 @@
 // The method is written out in include/sparse_linear_hip.h ("LOBPCG on handles"); this file issues it.  The basis
 // S = [X | P | W] (3 block columns) is kept ORTHONORMAL by classical Gram-Schmidt done twice on the one-pass kernels of
 // krylov_basis.hpp, so the Ritz problem is a standard Hermitian one: T = S^H (A S) by spl_vector_gram_dev's kernel
-// (gram.hip), diagonalised on the host by the cyclic Jacobi of ritz_jacobi.hpp, and [X' | P'] = S [C | C without its X
-// rows] by the in-place rotation of eigsh.hip, real or complex.  Rank deficiency is decided on the device without a
-// synchronisation per column: a column whose norm after the two passes is 0, not finite, or at most 2^-40 of its norm
-// before is written as zeros and flagged; a zero column contributes +0.0 terms only, so the launch sequence of an
-// iteration is the same whatever drops, and the host removes the flagged rows and columns from T.  Two synchronisations
-// per iteration: the residual norms; T and the flags.  No captured graph, no floating-point atomic, no kernel waits for
-// another workgroup.
+// (gram.hip), diagonalised and ordered on the host by the Ritz step of ritz_jacobi.hpp, and
+// [X' | P'] = S [C | C without its X rows] by the in-place rotation of eigsh.hip, real or complex.  Rank deficiency is
+// decided on the device without a synchronisation per column: a column whose norm after the two passes is 0, not
+// finite, or at most 2^-40 of its norm before is written as zeros and flagged; a zero column contributes +0.0 terms
+// only, so the launch sequence of an iteration is the same whatever drops, and the host removes the flagged rows and
+// columns from T.  Two synchronisations per iteration: the residual norms; T and the flags.  No captured graph, no
+// floating-point atomic, no kernel waits for another workgroup.
 #include <algorithm>
 #include <cmath>
 #include <vector>
@@ -52,38 +52,13 @@ inline LTables ltables_at(double *base, int b) {
   return T;
 }
 
-// partials of Re<v,v>
-template <int VW>
-__global__ __launch_bounds__(kLanes) void lnorm_kernel(int64_t n, const double *__restrict__ v, double *part) {
-  chunk_partials<1>(n, part, 0, [&](int64_t i, double *acc) {
-    const Val<VW> vi = load_val<VW>(v, i);
-    acc[0] = acc[0] + mul(conj_of(vi), vi).re;
-  });
-}
-
-// r = ax - theta x, one product part by part and one difference per entry, stored when r is given; partials of Re<r,r>
-template <int VW>
-__global__ __launch_bounds__(kLanes) void lresidual_kernel(int64_t n, const double *__restrict__ ax,
-                                                           const double *__restrict__ x, double theta,
-                                                           double *__restrict__ r, double *part) {
-  chunk_partials<1>(n, part, 0, [&](int64_t i, double *acc) {
-    const Val<VW> ri = sub(load_val<VW>(ax, i), scaled(theta, load_val<VW>(x, i)));
-    if (r) store_val(r, i, ri);
-    acc[0] = acc[0] + mul(conj_of(ri), ri).re;
-  });
-}
-
 // ONE workgroup behind the passes of a column: eta2 from the last partials of Re<w,w>, eta0 from the table, the flag
 // (0 kept, 1 dropped, 2 not finite) and what a kept column is divided by
 __global__ __launch_bounds__(kLanes) void decide_kernel(const double *part, int count, const double *eta0sq,
                                                         double *scale, int *flag) {
-  __shared__ double lds[kLanes];
-  const int t = threadIdx.x;
-  double f[1] = {0.0};
-  for (int i = t; i < count; i += kLanes) f[0] = f[0] + part[i];
-  lane_tree<1>(f, lds);
-  if (t != 0) return;
-  const double e2 = sqrt(f[0]), e0 = sqrt(*eta0sq);
+  const double sum = sum_partials(part, count);
+  if (threadIdx.x != 0) return;
+  const double e2 = sqrt(sum), e0 = sqrt(*eta0sq);
   *scale = e2;
   if (!isfinite(e0) || !isfinite(e2)) *flag = 2;
   else if (e2 == 0.0 || e2 <= kDropRatio * e0) *flag = 1;
@@ -109,7 +84,6 @@ struct Lobpcg : SolverCore {  // work: 7 block + 1 vectors: S (3 block), A S (3 
   DBuf<double> tables;
   DBuf<int> flags;               // 3 block
   StatusBlock<LStatus> status;   // behind the pinned copy: G, Z, res and the flags of the host
-  int64_t last_iterations = 0;
   Lobpcg(const Matrix *A, int b)
       : SolverCore(kLobpcgMagic, A, (size_t)7 * b + 1, fold_scratch(A->nrows_local, 3 * b * A->vw)), block(b),
         tables(ltable_doubles(b)), flags((size_t)3 * b),
@@ -169,11 +143,9 @@ struct LRun : RunCore {
 
   // Re<v,v> of n entries folded to *out
   void norm_to(const double *v, double *out) {
-    hipLaunchKernelGGL((lnorm_kernel<VW>), dim3(chunked), dim3(kLanes), 0, s, n, v, scratch);
-    const Partials P = middle_levels(nullptr, n, 1, scratch, s);
-    hipLaunchKernelGGL(fold_kernel, dim3(1, 1), dim3(kLanes), 0, s, (const int *)nullptr, (int64_t)P.count, P.p, P.stride, out,
-                       (int64_t)1);
-    launches += P.middle + 2;
+    hipLaunchKernelGGL((norm_kernel<VW>), dim3(chunked), dim3(kLanes), 0, s, n, v, scratch);
+    ++launches;
+    fold_to(out);
   }
 
   // column c of S against the c columns before it: the norm before, the two passes, the decision, the division
@@ -184,9 +156,9 @@ struct LRun : RunCore {
     if (c > 0) {
       P = orthogonalise_twice<VW>(never, n, c, basis(0), w, T.c1, T.c2, scratch, chunked, s, &launches);
     } else {
-      hipLaunchKernelGGL((lnorm_kernel<VW>), dim3(chunked), dim3(kLanes), 0, s, n, (const double *)w, scratch);
-      P = middle_levels(nullptr, n, 1, scratch, s);
-      launches += P.middle + 1;
+      hipLaunchKernelGGL((norm_kernel<VW>), dim3(chunked), dim3(kLanes), 0, s, n, (const double *)w, scratch);
+      ++launches;
+      P = last_level();
     }
     hipLaunchKernelGGL(decide_kernel, dim3(1), dim3(kLanes), 0, s, P.p, P.count, (const double *)(T.eta0 + c), T.scale + c,
                        flags + c);
@@ -214,17 +186,12 @@ struct LRun : RunCore {
     }
   }
 
-  // r_i = A x_i - theta_i x_i to `out(i)` (nullptr: not stored) and Re<r_i,r_i> to res[i], i < count; ax(i): A x_i
-  template <typename Ax, typename Out>
-  void residuals_of(int count, Ax ax, Out out) {
-    for (int i = 0; i < count; ++i) {
-      hipLaunchKernelGGL((lresidual_kernel<VW>), dim3(chunked), dim3(kLanes), 0, s, n, (const double *)ax(i),
-                         (const double *)basis(i), theta[i], out(i), scratch);
-      const Partials P = middle_levels(nullptr, n, 1, scratch, s);
-      hipLaunchKernelGGL(fold_kernel, dim3(1, 1), dim3(kLanes), 0, s, (const int *)nullptr, (int64_t)P.count, P.p, P.stride,
-                         T.res + i, (int64_t)1);
-      launches += P.middle + 2;
-    }
+  // r_i = ax - theta_i x_i to `out` (nullptr: not stored) and Re<r_i,r_i> to res[i]; ax: A x_i
+  void residual_of(int i, const double *ax, double *out) {
+    hipLaunchKernelGGL((residual_kernel<VW>), dim3(chunked), dim3(kLanes), 0, s, n, ax, (const double *)basis(i), theta[i],
+                       out, scratch);
+    ++launches;
+    fold_to(T.res + i);
   }
 
   // The close on the first mc columns of S: T = S^H (A S), the flags, Jacobi, the order, and the rotation that leaves
@@ -260,19 +227,11 @@ struct LRun : RunCore {
           Tm[2 * ((size_t)c * mp + a) + 1] = a == c ? 0.0 : -gi;
         }
       }
-    const int sweeps = VW == 1 ? ritz_jacobi_real(mp, Tm.data(), Y.data()) : ritz_jacobi_hermitian(mp, Tm.data(), Y.data());
-    if (sweeps < 0) return not_finite(reason);
-    auto value = [&](int i) { return Tm[((size_t)i * mp + i) * VW]; };
-    for (int i = 0; i < mp; ++i)
-      if (!std::isfinite(value(i))) return not_finite(reason);
-    for (size_t q = 0; q < Y.size(); ++q)
-      if (!std::isfinite(Y[q])) return not_finite(reason);
-    if (sweeps > sweeps_most) sweeps_most = sweeps;
     std::vector<int> order(mp);
-    for (int i = 0; i < mp; ++i) order[i] = i;
-    std::stable_sort(order.begin(), order.end(), [&](int x, int y) {
-      return which == SPL_EIGSH_largest_algebraic ? value(x) > value(y) : value(x) < value(y);
-    });
+    const int sweeps = ritz_step(mp, VW, which, Tm.data(), Y.data(), order.data());
+    if (sweeps < 0) return not_finite(reason);
+    if (sweeps > sweeps_most) sweeps_most = sweeps;
+    auto value = [&](int i) { return Tm[((size_t)i * mp + i) * VW]; };
     // Z: mc x kout, column major; rows of flagged columns and, in the second block, the rows of X are +0.0
     double *Z = L->host_z();
     for (size_t q = 0; q < (size_t)mc * kout * VW; ++q) Z[q] = 0.0;
@@ -321,12 +280,7 @@ struct LRun : RunCore {
         if (st != SPL_OK) return st;
         ++spmv_columns;
         ++launches;
-        hipLaunchKernelGGL((lresidual_kernel<VW>), dim3(chunked), dim3(kLanes), 0, s, n, (const double *)product(),
-                           (const double *)basis(i), theta[i], (double *)nullptr, scratch);
-        const Partials P = middle_levels(nullptr, n, 1, scratch, s);
-        hipLaunchKernelGGL(fold_kernel, dim3(1, 1), dim3(kLanes), 0, s, (const int *)nullptr, (int64_t)P.count, P.p,
-                           P.stride, T.res + i, (int64_t)1);
-        launches += P.middle + 2;
+        residual_of(i, product(), nullptr);
       }
       const int st = launch_status("lobpcg finish");
       if (st != SPL_OK) return st;
@@ -362,7 +316,7 @@ struct LRun : RunCore {
     for (int64_t it = 0;; ++it) {
       iterations = it;
       const bool pre = L->pre.set();
-      residuals_of(b, [&](int i) { return image(i); }, [&](int i) { return pre ? residual(i) : basis(2 * b + i); });
+      for (int i = 0; i < b; ++i) residual_of(i, image(i), pre ? residual(i) : basis(2 * b + i));
       if ((e = launch_status("lobpcg residuals")) != SPL_OK) return e;
       SPL_HIP(hipMemcpyAsync(L->host_res(), T.res, (size_t)b * sizeof(double), hipMemcpyDeviceToHost, s));
       sync();
@@ -406,37 +360,17 @@ int lobpcg_solve(Lobpcg *L, int nev, int which, double tol, double atol, int64_t
                  int64_t ldx0, double *values, double *d_vectors, int64_t ldx, double *residuals, int64_t result[8],
                  double *history, hipStream_t s) {
   std::lock_guard<std::mutex> hold(L->lock);
-  int e;
-  int64_t launches = 0;
-  if (L->vw == 1) {
-    LRun<1> run(L, s);
-    e = run.solve(nev, which, tol, atol, max_iter, d_X0, ldx0, values, d_vectors, ldx, residuals, result, history);
-    launches = run.launches;
-  } else {
-    LRun<2> run(L, s);
-    e = run.solve(nev, which, tol, atol, max_iter, d_X0, ldx0, values, d_vectors, ldx, residuals, result, history);
-    launches = run.launches;
-  }
-  if (e != SPL_OK) {
-    (void)hipStreamSynchronize(s);
+  return L->solve_and_record(s, result + 1, [&](auto width, int64_t *launches) {
+    LRun<decltype(width)::value> run(L, s);
+    const int e = run.solve(nev, which, tol, atol, max_iter, d_X0, ldx0, values, d_vectors, ldx, residuals, result, history);
+    *launches = run.launches;
     return e;
-  }
-  L->last_iterations = result[1];
-  L->last_launches = launches;
-  ++L->solves;
-  return SPL_OK;
+  });
 }
 
 void lobpcg_info(Lobpcg *L, int64_t info[8]) {
   std::lock_guard<std::mutex> hold(L->lock);
-  info[0] = L->n;
-  info[1] = L->block;
-  info[2] = (L->vw == 2 ? 1 : 0) | L->pre.flags();
-  info[3] = (int64_t)L->bytes;
-  info[4] = L->solves;
-  info[5] = L->last_iterations;
-  info[6] = L->last_launches;
-  info[7] = 0;
+  L->fill_info(info, L->block, L->pre.flags());
 }
 
 void lobpcg_delete(Lobpcg *L) { delete_object(L); }

@@ -1,9 +1,11 @@
-// ritz_jacobi.hpp — cyclic Jacobi for the projected matrix of a block eigensolver (lobpcg.hip), real symmetric and
-// complex Hermitian, in plain C++ on the host: no device code, no library type.  The rules are written out in
-// include/sparse_linear_hip.h (the real one in the Lanczos section, the complex one in the LOBPCG section); a product
-// and a sum are rounded apart (-ffp-contract=off).  tests/native/ritz_jacobi_check.cpp runs both under the sanitizers.
+// ritz_jacobi.hpp — the Ritz step of the two eigensolvers (eigsh.hip: thick-restart Lanczos; lobpcg.hip: LOBPCG): cyclic
+// Jacobi on the projected matrix, real symmetric and complex Hermitian, and the order of the values, in plain C++ on the
+// host: no device code, no library type.  The rules are written out in include/sparse_linear_hip.h (the real one in
+// the Lanczos section, the complex one in the LOBPCG section); a product and a sum are rounded apart
+// (-ffp-contract=off).  tests/native/ritz_jacobi_check.cpp runs all of it under the sanitizers.
 #pragma once
 
+#include <algorithm>
 #include <cmath>
 #include <cstddef>
 
@@ -121,6 +123,27 @@ inline int ritz_jacobi_hermitian(int m, double *T, double *Y) {
         }
       }
   }
+}
+
+// What a close does with its projected matrix: the rule (width 1: ritz_jacobi_real; 2: ritz_jacobi_hermitian, T and Y
+// in that rule's layout), then `order`: the m indices stable-sorted by the values T_ii after `which`, one of the
+// SPL_EIGSH_* orders (0 largest first, 1 smallest first, 2 largest magnitude first).  Sweeps started; -1 when the rule
+// does not converge or a value or an entry of Y is not finite (order is not written then)
+inline int ritz_step(int m, int width, int which, double *T, double *Y, int *order) {
+  const int sweeps = width == 1 ? ritz_jacobi_real(m, T, Y) : ritz_jacobi_hermitian(m, T, Y);
+  if (sweeps < 0) return -1;
+  auto value = [&](int i) { return T[((size_t)i * m + i) * width]; };
+  for (int i = 0; i < m; ++i)
+    if (!std::isfinite(value(i))) return -1;
+  for (size_t q = 0; q < (size_t)m * m * width; ++q)
+    if (!std::isfinite(Y[q])) return -1;
+  for (int i = 0; i < m; ++i) order[i] = i;
+  std::stable_sort(order, order + m, [&](int a, int b) {
+    if (which == 0) return value(a) > value(b);
+    if (which == 1) return value(a) < value(b);
+    return std::fabs(value(a)) > std::fabs(value(b));
+  });
+  return sweeps;
 }
 
 }  // namespace spl

@@ -1,7 +1,8 @@
 // solver_core.hpp — what the iterative objects on device handles share on the host: the object (SolverCore: krylov.hip,
 // gmres.hip, eigsh.hip, lobpcg.hip), the status block in device and pinned memory, and what one solve's launches have in
-// common (RunCore; LinearRun for the two that solve A x = b with a preconditioner and a history).  What differs between
-// the solvers (status structs, tables, stages, iteration bodies) is in their files.  Included by those four files only.
+// common (RunCore, with the one reduction of a first level's partials to a scalar; LinearRun for the three that solve
+// A x = b with a preconditioner and a history: CG, BiCGSTAB, GMRES).  What differs between the solvers (status structs,
+// tables, stages, iteration bodies) is in their files.  Included by those four files only.
 #pragma once
 
 #include "history_room.hpp"
@@ -18,6 +19,7 @@ struct SolverCore : ObjectHead {
   size_t bytes;          // of device memory; the owner adds its tables and its status block
   std::mutex lock;       // one solve at a time
   int64_t solves = 0, last_launches = 0;
+  int64_t last_rounds = 0;  // of the last solve: iterations (CG, BiCGSTAB, GMRES, LOBPCG) or cycles (Lanczos)
   // A: whole and square (the caller checked)
   SolverCore(uint32_t magic, const Matrix *a, size_t nvec, size_t scratch_doubles) : ObjectHead(magic), A(a) {
     device = a->device;
@@ -28,6 +30,38 @@ struct SolverCore : ObjectHead {
     bytes = (nvec * (size_t)n * (size_t)vw + scratch_doubles) * sizeof(double);
   }
   double *vec(int i) const { return work.get() + (size_t)i * (size_t)n * (size_t)vw; }
+
+  // The tail of a *_solve, under the lock: run(Width<VW>(), &launches) at the object's value width returns the status
+  // and the kernels it launched; an error synchronises s and records nothing.  *rounds is read after the run
+  template <int VW>
+  struct Width {
+    static constexpr int value = VW;
+  };
+  template <typename Run>
+  int solve_and_record(hipStream_t s, const int64_t *rounds, Run &&run) {
+    int64_t launches = 0;
+    const int e = vw == 1 ? run(Width<1>(), &launches) : run(Width<2>(), &launches);
+    if (e != SPL_OK) {
+      (void)hipStreamSynchronize(s);
+      return e;
+    }
+    last_rounds = *rounds;
+    last_launches = launches;
+    ++solves;
+    return SPL_OK;
+  }
+  // The six slots every *_info fills alike, under the lock; `option` (the method, the restart, ncv, the block) and the
+  // flag bits above bit 0 are the solver's
+  void fill_info(int64_t info[8], int64_t option, int flags) const {
+    info[0] = n;
+    info[1] = option;
+    info[2] = (vw == 2 ? 1 : 0) | flags;
+    info[3] = (int64_t)bytes;
+    info[4] = solves;
+    info[5] = last_rounds;
+    info[6] = last_launches;
+    info[7] = 0;
+  }
 };
 
 // A solver's status block in device memory and its copy in pinned host memory, with `host_extra` bytes behind the copy
@@ -74,6 +108,20 @@ struct RunCore {
   template <typename StatusT>
   const StatusT &look(const StatusBlock<StatusT> &b) {
     return look(b, [] {});
+  }
+  // A first level left its partials of ONE plane in scratch: the middle levels, for a one-workgroup kernel to read the
+  // last level (sum_partials) ...
+  Partials last_level() {
+    const Partials P = middle_levels(nullptr, n, 1, scratch, s);
+    launches += P.middle;
+    return P;
+  }
+  // ... or the whole fold to the double *out
+  void fold_to(double *out) {
+    const Partials P = last_level();
+    hipLaunchKernelGGL(fold_kernel, dim3(1, 1), dim3(kLanes), 0, s, (const int *)nullptr, (int64_t)P.count, P.p, P.stride,
+                       out, (int64_t)1);
+    ++launches;
   }
 };
 

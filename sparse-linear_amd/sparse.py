@@ -36,7 +36,6 @@ and ``vector_gram_dev`` the k x l block of inner products of two column blocks i
 operations above, and its V-cycle is a preconditioner the solvers take (``M=<AMG>`` or ``M="amg"``).
 """
 import ctypes as C
-import weakref
 
 import numpy as np
 
@@ -55,6 +54,33 @@ class SparseError(ValueError):
 
 def _oops(fn, msg):
     raise SparseError("%s: %s" % (fn, msg))
+
+
+def _vector_arg(where, v, shape, cplx, what, the=None, tensor=None):
+    """The vector or block argument v of `where`: a torch tensor on the device or what numpy reads (tensor True / False:
+    which of the two it has to be; None: as v is), of the shape `shape`, (n,) or (n, k), complex128 when cplx and
+    float64 otherwise.  what / the: its name in the refusal of an array ("a start") and of a tensor ("start"; None: the
+    only argument).  Returns (v or the array, the dtype wanted, is a tensor)"""
+    size = " x ".join("%d" % d for d in shape)
+    if tensor is None:
+        try:
+            import torch
+            tensor = isinstance(v, torch.Tensor)
+        except ImportError:  # pragma: no cover
+            tensor = False
+    if tensor:
+        import torch
+        want = torch.complex128 if cplx else torch.float64
+        if not (isinstance(v, torch.Tensor) and v.is_cuda and v.dtype == want and tuple(v.shape) == tuple(shape)):
+            needed = "a device tensor of %s %s entries" % (size, want)
+            _oops(where, "the %s must be %s" % (the, needed) if the else needed + " is needed")
+        return v, want, True
+    want = C128 if cplx else F64
+    a = np.atleast_1d(np.asarray(v))  # a scalar is a vector of one entry
+    if a.dtype != want or a.shape != tuple(shape):
+        _oops(where, "%s of dtype %s and shape %s; %s %s entries are needed"
+              % (what, a.dtype, a.shape, size, np.dtype(want)))
+    return a, want, False
 
 
 def _frozen(a):
@@ -189,7 +215,7 @@ class Matrix(object):
         return self._handle
 
 
-class DeviceMatrix(object):
+class DeviceMatrix(_ffi.Handle):
     """Owner of a ``void *H`` from ``spl_matrix_create*`` (UMFPACK-style handle:
     callee-allocated, freed through ``void **``; Umfpack.hs:63-65)."""
     ORDER_REFERENCE = 0
@@ -202,24 +228,7 @@ class DeviceMatrix(object):
     PANEL_FORM_ROUNDS = 11
 
     def __init__(self, handle):
-        self._h = C.c_void_p(handle)
-        self._finalizer = weakref.finalize(self, DeviceMatrix._free, self._h)
-
-    @staticmethod
-    def _free(h):
-        try:
-            lib().spl_matrix_free(C.byref(h))
-        except Exception:  # interpreter shutdown
-            pass
-
-    def free(self):
-        self._finalizer()
-
-    @property
-    def handle(self):
-        if not self._h.value:
-            raise _ffi.SparseLinearError("DeviceMatrix", _ffi.SPL_ERROR_invalid_handle)
-        return self._h
+        _ffi.Handle.__init__(self, "spl_matrix_free", handle)
 
     @classmethod
     def from_csc(cls, mat, part=0, nparts=1):
@@ -1003,7 +1012,7 @@ class DeviceMatrix(object):
                                         1 if accumulate else 0, C.c_void_p(stream)))
 
 
-class TriangularSolver(object):
+class TriangularSolver(_ffi.Handle):
     """Owner of a ``void *T`` from ``spl_trisolve_analyze``: the level-scheduled solves T x = b, T^T x = b, T^H x = b
     on the device (csrc/trisolve.hip).  Every result is the serial substitution loop bit for bit, whatever the schedule
     and the number of right-hand sides.  ``singular``: the analysis found a missing or zero d_i (the solves then give
@@ -1012,25 +1021,8 @@ class TriangularSolver(object):
     TRANS = {"N": _ffi.SPL_OP_n, "T": _ffi.SPL_OP_t, "H": _ffi.SPL_OP_h}
 
     def __init__(self, handle, status=0):
-        self._t = C.c_void_p(handle)
+        _ffi.Handle.__init__(self, "spl_trisolve_free", handle)
         self.singular = status == _ffi.SPL_WARNING_singular_matrix
-        self._finalizer = weakref.finalize(self, TriangularSolver._free, self._t)
-
-    @staticmethod
-    def _free(t):
-        try:
-            lib().spl_trisolve_free(C.byref(t))
-        except Exception:  # interpreter shutdown
-            pass
-
-    def free(self):
-        self._finalizer()
-
-    @property
-    def handle(self):
-        if not self._t.value:
-            raise _ffi.SparseLinearError("TriangularSolver", _ffi.SPL_ERROR_invalid_handle)
-        return self._t
 
     @classmethod
     def _op(cls, trans):
@@ -1119,7 +1111,7 @@ def solveTriangular(mat, b, lower=True, unit=False, trans="N"):
         T.free()
 
 
-class ILU0(object):
+class ILU0(_ffi.Handle):
     """The incomplete LU factorisation without fill of a whole square device handle (csrc/ilu0.hip): the serial IKJ
     loop bit for bit, whatever the schedule.  ``factors`` is a DeviceMatrix with A's pattern that holds L (unit lower,
     its ones not stored) and U; ``lower`` / ``upper`` are the TriangularSolvers built from it (unit / stored diagonal);
@@ -1128,25 +1120,13 @@ class ILU0(object):
     INFO_KEYS = ("n", "nnz", "levels", "launches", "missing_diagonals", "longest_row", "device_bytes", "factorisations")
 
     def __init__(self, A):
-        self._p = C.c_void_p()
+        _ffi.Handle.__init__(self, "spl_ilu0_free")
         self.factors = self.lower = self.upper = None
         self.singular = False
-        self._finalizer = weakref.finalize(self, ILU0._free, self._p)
-        check("spl_ilu0_analyze", lib().spl_ilu0_analyze(A.handle, C.byref(self._p)))
+        check("spl_ilu0_analyze", lib().spl_ilu0_analyze(A.handle, C.byref(self._h)))
         self.refactor(A)
 
-    @staticmethod
-    def _free(p):
-        try:
-            lib().spl_ilu0_free(C.byref(p))
-        except Exception:  # interpreter shutdown
-            pass
-
-    @property
-    def plan(self):
-        if not self._p.value:
-            raise _ffi.SparseLinearError("ILU0", _ffi.SPL_ERROR_invalid_handle)
-        return self._p
+    plan = _ffi.Handle.handle  # the handle is the plan of spl_ilu0_analyze
 
     def _drop_factors(self):
         for part in (self.lower, self.upper, self.factors):
@@ -1156,7 +1136,7 @@ class ILU0(object):
 
     def free(self):
         self._drop_factors()
-        self._finalizer()
+        _ffi.Handle.free(self)
 
     def info(self):
         out = np.zeros(8, dtype=I64)
@@ -1237,7 +1217,7 @@ def vector_gram_dev(n, k, l, V_ptr, ldv, W_ptr, ldw, G_ptr, ldg, upper=False, is
                                     C.c_void_p(stream)))
 
 
-class _PreconditionedSolver(object):
+class _PreconditionedSolver(_ffi.Handle):
     """What KrylovSolver and GMRESSolver share: the handle, the preconditioner vocabulary (None, an ``ILU0``, an ``AMG``,
     ``"jacobi"``, ``"sgs"``, ``"amg"`` or a ``(T1, mid, T2)`` triple), ``info`` and the vector plumbing of ``solve``.  A
     subclass names its C calls (``_CALLS``: set_preconditioner, set_preconditioner_amg, info, free) and has
@@ -1248,32 +1228,18 @@ class _PreconditionedSolver(object):
     _CALLS = None
 
     def _begin(self, A, M):
-        self._k = C.c_void_p()
-        self._finalizer = weakref.finalize(self, type(self)._free, self._k)
+        _ffi.Handle.__init__(self, self._CALLS["free"])
         self.A = A
         self.parts = (None, None, None)
         self.amg = None   # the AMG in use: M itself, or the one "amg" made here
         self._owned = []  # what "jacobi", "sgs" and "amg" made here
         self._M = M       # an ILU0 stays alive with its solvers
 
-    @classmethod
-    def _free(cls, k):
-        try:
-            getattr(lib(), cls._CALLS["free"])(C.byref(k))
-        except Exception:  # interpreter shutdown
-            pass
-
     def free(self):
-        self._finalizer()
+        _ffi.Handle.free(self)
         for part in self._owned:
             part.free()
         self._owned = []
-
-    @property
-    def handle(self):
-        if not self._k.value:
-            raise _ffi.SparseLinearError(self._NAME, _ffi.SPL_ERROR_invalid_handle)
-        return self._k
 
     def _diagonal(self):
         import torch
@@ -1349,18 +1315,11 @@ class _PreconditionedSolver(object):
         where = self._NAME + ".solve"
         inf = self.info()
         n, cplx = inf["n"], inf["complex"]
-        try:
-            import torch
-            is_tensor = isinstance(b, torch.Tensor)
-        except ImportError:  # pragma: no cover
-            is_tensor = False
+        a, want, is_tensor = _vector_arg(where, b, (n,), cplx, "right-hand side", "right-hand side")
+        if x0 is not None:
+            x0 = _vector_arg(where, x0, (n,), cplx, "a start", "start", is_tensor)[0]
         if is_tensor:
-            want = torch.complex128 if cplx else torch.float64
-            for v, what in ((b, "right-hand side"), (x0, "start")):
-                if v is None:
-                    continue
-                if not (isinstance(v, torch.Tensor) and v.is_cuda and v.dtype == want and tuple(v.shape) == (n,)):
-                    _oops(where, "the %s must be a device tensor of %d %s entries" % (what, n, want))
+            import torch
             with torch.cuda.device(b.device):
                 bb = b.contiguous()
                 x = torch.empty(max(n, 1), dtype=want, device=b.device)[:n]
@@ -1369,17 +1328,9 @@ class _PreconditionedSolver(object):
                 res = self.solve_dev(bb.data_ptr(), x.data_ptr(), x0 is not None, rtol, atol, maxiter, check_every,
                                      True, torch.cuda.current_stream().cuda_stream)
             return x, res
-        want = C128 if cplx else F64
-        a = np.ascontiguousarray(b)
-        if a.dtype != want or a.shape != (n,):
-            _oops(where, "right-hand side of dtype %s and shape %s; %d %s entries are needed"
-                  % (a.dtype, a.shape, n, np.dtype(want)))
+        a = np.ascontiguousarray(a)
         x = np.zeros(n, dtype=want)
         if x0 is not None:
-            x0 = np.asarray(x0)
-            if x0.dtype != want or x0.shape != (n,):
-                _oops(where, "a start of dtype %s and shape %s; %d %s entries are needed"
-                      % (x0.dtype, x0.shape, n, np.dtype(want)))
             x[:] = x0
         maxiter = self._maxiter(maxiter)
         if check_every:  # the host-vector call has no such argument: through device tensors
@@ -1419,7 +1370,7 @@ class KrylovSolver(_PreconditionedSolver):
             raise ValueError("KrylovSolver: method %r; 'cg' or 'bicgstab' is needed" % (method,))
         self._begin(A, M)
         self.method = method
-        check("spl_krylov_create", lib().spl_krylov_create(A.handle, self.METHODS[method], C.byref(self._k)))
+        check("spl_krylov_create", lib().spl_krylov_create(A.handle, self.METHODS[method], C.byref(self._h)))
         self.set_preconditioner(M)
 
     @classmethod
@@ -1474,7 +1425,7 @@ class GMRESSolver(_PreconditionedSolver):
             raise ValueError("GMRESSolver: restart %r; 1 ... 128 is needed" % (restart,))
         self._begin(A, M)
         self.restart = restart
-        check("spl_gmres_create", lib().spl_gmres_create(A.handle, restart, C.byref(self._k)))
+        check("spl_gmres_create", lib().spl_gmres_create(A.handle, restart, C.byref(self._h)))
         self.set_preconditioner(M)
 
     @classmethod
@@ -1542,7 +1493,46 @@ def vector_rotate_dev(n, m, k, V_ptr, ldv, Y_ptr, ldy, out_ptr=None, ldo=0, is_c
                                       C.c_void_p(stream)))
 
 
-class EigenSolver(object):
+class _EigenPairs(object):
+    """What EigenSolver and LOBPCGSolver share: the host buffers of a solve, the result dict, and the end of ``solve``
+    that makes room for the vectors and cuts them to the pairs found.  A subclass has ``RESULT_KEYS``, ``REASONS`` and
+    ``_history_entries(out, history)``, the entries of the history its solve wrote."""
+
+    @classmethod
+    def _buffers(cls, nev, rounds, history=True):
+        """values, residuals, result and the history of a solve of at most `rounds` restarts or iterations"""
+        return (np.zeros(max(nev, 1), dtype=F64), np.zeros(max(nev, 1), dtype=F64),
+                np.zeros(len(cls.RESULT_KEYS), dtype=I64), np.zeros(max(rounds, 0) + 1, dtype=F64) if history else None)
+
+    @classmethod
+    def _result(cls, result, values, residuals, history):
+        out = dict(zip(cls.RESULT_KEYS, (int(v) for v in result)))
+        pairs = out["pairs"]
+        out.update(reason_name=cls.REASONS[out["reason"]], converged=out["reason"] == 0,
+                   residuals=residuals[:pairs].copy())
+        if history is not None:
+            out["history"] = history[:cls._history_entries(out, history)].copy()
+        return values[:pairs].copy(), out
+
+    @staticmethod
+    def _solve_pairs(nev, n, start, want, is_tensor, on_device, on_host):
+        """(values, vectors, result dict) from the start, one column after the other: a device tensor, solved by
+        ``on_device(start_ptr, vectors_ptr, stream)`` on torch's current stream, or a numpy array, solved by
+        ``on_host(start, vectors)``; both return (values, result dict)"""
+        if is_tensor:
+            import torch
+            with torch.cuda.device(start.device):
+                start = start.contiguous()
+                X = torch.zeros((max(nev, 1), max(n, 1)), dtype=want, device=start.device)
+                values, res = on_device(start.data_ptr(), X.data_ptr(), torch.cuda.current_stream().cuda_stream)
+            return values, X[:res["pairs"], :n].T, res
+        start = np.ascontiguousarray(start)
+        X = np.zeros((max(nev, 1), max(n, 1)), dtype=want)
+        values, res = on_host(p_f64(start.view(F64)), p_f64(X.view(F64)))
+        return values, X[:res["pairs"], :n].T.copy(), res
+
+
+class EigenSolver(_ffi.Handle, _EigenPairs):
     """Owner of a ``void *E`` from ``spl_eigsh_create``: thick-restart Lanczos with full reorthogonalisation on a whole
     square Hermitian device handle (csrc/eigsh.hip), real or complex, with a basis of ``ncv`` columns.  Directly on A it
     finds the ends of the spectrum; with ``sigma`` it works on ``(A - sigma I)^-1``, applied by a CG ``KrylovSolver``
@@ -1561,35 +1551,21 @@ class EigenSolver(object):
         ncv = int(ncv)
         if not 2 <= ncv <= 128:
             raise ValueError("EigenSolver: ncv %r; 2 ... 128 is needed" % (ncv,))
-        self._e = C.c_void_p()
-        self._finalizer = weakref.finalize(self, EigenSolver._free, self._e)
+        _ffi.Handle.__init__(self, "spl_eigsh_free")
         self.A, self.ncv, self.sigma = A, ncv, None
         self.shifted = self.inner = None
-        check("spl_eigsh_create", lib().spl_eigsh_create(A.handle, ncv, C.byref(self._e)))
+        check("spl_eigsh_create", lib().spl_eigsh_create(A.handle, ncv, C.byref(self._h)))
         if sigma is not None:
             self.set_inverse(sigma, M, inner_rtol, inner_atol, inner_maxiter)
 
-    @staticmethod
-    def _free(e):
-        try:
-            lib().spl_eigsh_free(C.byref(e))
-        except Exception:  # interpreter shutdown
-            pass
-
     def free(self):
-        self._finalizer()
+        _ffi.Handle.free(self)
         self._drop_inner()
 
     def _drop_inner(self):
         if self.inner is not None:
             self.inner.free()
         self.shifted = self.inner = None
-
-    @property
-    def handle(self):
-        if not self._e.value:
-            raise _ffi.SparseLinearError("EigenSolver", _ffi.SPL_ERROR_invalid_handle)
-        return self._e
 
     def set_inverse(self, sigma, M=None, inner_rtol=1e-12, inner_atol=0.0, inner_maxiter=None):
         """the operator becomes (A - sigma I)^-1 by CG on ``A.lin(1, I, -sigma)`` with the preconditioner M; sigma None:
@@ -1627,15 +1603,9 @@ class EigenSolver(object):
             raise ValueError("EigenSolver: which %r; 'LA', 'SA' or 'LM' is needed" % (which,))
         return cls.WHICH[which]
 
-    @classmethod
-    def _result(cls, result, values, residuals, history):
-        out = dict(zip(cls.RESULT_KEYS, (int(v) for v in result)))
-        pairs = out["pairs"]
-        out.update(reason_name=cls.REASONS[out["reason"]], converged=out["reason"] == 0,
-                   residuals=residuals[:pairs].copy())
-        if history is not None:
-            out["history"] = history[:out["cycles"] + 1].copy()
-        return values[:pairs].copy(), out
+    @staticmethod
+    def _history_entries(out, history):
+        return out["cycles"] + 1
 
     def solve_dev(self, nev, v0_ptr, vectors_ptr, ldx, which="LA", tol=1e-10, atol=0.0, max_restarts=1000, history=True,
                   stream=0):
@@ -1643,9 +1613,7 @@ class EigenSolver(object):
         `stream` and returns (values, result dict) after the solve's last synchronisation; the dict has reason, cycles,
         applications, pairs, inner_iterations, jacobi_sweeps, residuals and history"""
         nev, max_restarts = int(nev), int(max_restarts)
-        values, residuals = np.zeros(max(nev, 1), dtype=F64), np.zeros(max(nev, 1), dtype=F64)
-        result = np.zeros(6, dtype=I64)
-        hist = np.zeros(max(max_restarts, 0) + 1, dtype=F64) if history else None
+        values, residuals, result, hist = self._buffers(nev, max_restarts, history)
         check("spl_eigsh_solve_dev",
               lib().spl_eigsh_solve_dev(self.handle, nev, self._which(which), float(tol), float(atol), max_restarts,
                                         C.c_void_p(v0_ptr), p_f64(values), C.c_void_p(vectors_ptr), int(ldx),
@@ -1669,36 +1637,21 @@ class EigenSolver(object):
         inf = self.info()
         n, cplx = inf["n"], inf["complex"]
         nev, max_restarts = int(nev), int(max_restarts)
-        try:
-            import torch
-            is_tensor = isinstance(v0, torch.Tensor)
-        except ImportError:  # pragma: no cover
-            is_tensor = False
-        if is_tensor:
-            want = torch.complex128 if cplx else torch.float64
-            if not (v0.is_cuda and v0.dtype == want and tuple(v0.shape) == (n,)):
-                _oops(where, "the start must be a device tensor of %d %s entries" % (n, want))
-            with torch.cuda.device(v0.device):
-                start = v0.contiguous()
-                X = torch.zeros((max(nev, 1), max(n, 1)), dtype=want, device=v0.device)
-                values, res = self.solve_dev(nev, start.data_ptr(), X.data_ptr(), max(n, 1), which, tol, atol,
-                                             max_restarts, True, torch.cuda.current_stream().cuda_stream)
-            return values, X[:res["pairs"], :n].T, res
-        want = C128 if cplx else F64
-        start = self.default_start() if v0 is None else np.ascontiguousarray(v0)
-        if start.dtype != want or start.shape != (n,):
-            _oops(where, "a start of dtype %s and shape %s; %d %s entries are needed"
-                  % (start.dtype, start.shape, n, np.dtype(want)))
-        X = np.zeros((max(nev, 1), max(n, 1)), dtype=want)
-        values, residuals = np.zeros(max(nev, 1), dtype=F64), np.zeros(max(nev, 1), dtype=F64)
-        result = np.zeros(6, dtype=I64)
-        hist = np.zeros(max(max_restarts, 0) + 1, dtype=F64)
-        check("spl_eigsh_solve",
-              lib().spl_eigsh_solve(self.handle, nev, self._which(which), float(tol), float(atol), max_restarts,
-                                    p_f64(start.view(F64)), p_f64(values), p_f64(X.view(F64)), max(n, 1),
-                                    p_f64(residuals), _ffi.p_i64(result), p_f64(hist)))
-        values, res = self._result(result, values, residuals, hist)
-        return values, X[:res["pairs"], :n].T.copy(), res
+        start, want, is_tensor = _vector_arg(where, self.default_start() if v0 is None else v0, (n,), cplx, "a start",
+                                             "start")
+
+        def on_host(start_p, vectors_p):
+            values, residuals, result, hist = self._buffers(nev, max_restarts)
+            check("spl_eigsh_solve",
+                  lib().spl_eigsh_solve(self.handle, nev, self._which(which), float(tol), float(atol), max_restarts, start_p,
+                                        p_f64(values), vectors_p, max(n, 1), p_f64(residuals), _ffi.p_i64(result),
+                                        p_f64(hist)))
+            return self._result(result, values, residuals, hist)
+
+        return self._solve_pairs(nev, n, start, want, is_tensor,
+                                 lambda v0_ptr, vectors_ptr, stream: self.solve_dev(
+                                     nev, v0_ptr, vectors_ptr, max(n, 1), which, tol, atol, max_restarts, True, stream),
+                                 on_host)
 
 
 def default_ncv(n, nev):
@@ -1714,7 +1667,7 @@ def eigsh(mat, nev, which="LA", ncv=None, sigma=None, M=None, tol=1e-10, atol=0.
                                      inner_maxiter)
 
 
-class LOBPCGSolver(_PreconditionedSolver):
+class LOBPCGSolver(_PreconditionedSolver, _EigenPairs):
     """Owner of a ``void *L`` from ``spl_lobpcg_create``: LOBPCG on a whole square Hermitian device handle
     (csrc/lobpcg.hip), real or complex, with a block of ``block`` columns (1 ... 42) and the preconditioner ``M`` (as
     KrylovSolver takes it) applied inside the iteration, one application per column and iteration.  A block method: it
@@ -1735,18 +1688,12 @@ class LOBPCGSolver(_PreconditionedSolver):
             raise ValueError("LOBPCGSolver: block %r; 1 ... 42 is needed" % (block,))
         self._begin(A, M)
         self.block = block
-        check("spl_lobpcg_create", lib().spl_lobpcg_create(A.handle, block, C.byref(self._k)))
+        check("spl_lobpcg_create", lib().spl_lobpcg_create(A.handle, block, C.byref(self._h)))
         self.set_preconditioner(M)
 
-    @classmethod
-    def _result(cls, result, values, residuals, history):
-        out = dict(zip(cls.RESULT_KEYS, (int(v) for v in result)))
-        pairs = out["pairs"]
-        out.update(reason_name=cls.REASONS[out["reason"]], converged=out["reason"] == 0,
-                   residuals=residuals[:pairs].copy())
-        if history is not None:
-            out["history"] = history[:min(out["iterations"], len(history) - 1) + 1].copy()
-        return values[:pairs].copy(), out
+    @staticmethod
+    def _history_entries(out, history):
+        return min(out["iterations"], len(history) - 1) + 1
 
     @staticmethod
     def _which(largest):
@@ -1758,9 +1705,7 @@ class LOBPCGSolver(_PreconditionedSolver):
         ldx entries apart).  Enqueues on `stream` and returns (values, result dict) after the solve's last
         synchronisation"""
         nev, maxiter = int(nev), int(maxiter)
-        values, residuals = np.zeros(max(nev, 1), dtype=F64), np.zeros(max(nev, 1), dtype=F64)
-        result = np.zeros(8, dtype=I64)
-        hist = np.zeros(max(maxiter, 0) + 1, dtype=F64) if history else None
+        values, residuals, result, hist = self._buffers(nev, maxiter, history)
         check("spl_lobpcg_solve_dev",
               lib().spl_lobpcg_solve_dev(self.handle, nev, self._which(largest), float(tol), float(atol), maxiter,
                                          C.c_void_p(X0_ptr), int(ldx0), p_f64(values), C.c_void_p(vectors_ptr), int(ldx),
@@ -1776,37 +1721,20 @@ class LOBPCGSolver(_PreconditionedSolver):
         inf = self.info()
         n, cplx, block = inf["n"], inf["complex"], inf["block"]
         nev, maxiter = block if nev is None else int(nev), int(maxiter)
-        try:
-            import torch
-            is_tensor = isinstance(X0, torch.Tensor)
-        except ImportError:  # pragma: no cover
-            is_tensor = False
-        if is_tensor:
-            want = torch.complex128 if cplx else torch.float64
-            if not (X0.is_cuda and X0.dtype == want and tuple(X0.shape) == (n, block)):
-                _oops(where, "the start must be a device tensor of %d x %d %s entries" % (n, block, want))
-            with torch.cuda.device(X0.device):
-                start = X0.T.contiguous()  # one column after the other
-                X = torch.zeros((max(nev, 1), max(n, 1)), dtype=want, device=X0.device)
-                values, res = self.solve_dev(nev, start.data_ptr(), max(n, 1), X.data_ptr(), max(n, 1), largest, tol, atol,
-                                             maxiter, True, torch.cuda.current_stream().cuda_stream)
-            return values, X[:res["pairs"], :n].T, res
-        want = C128 if cplx else F64
-        start = np.asarray(X0)
-        if start.dtype != want or start.shape != (n, block):
-            _oops(where, "a start of dtype %s and shape %s; %d x %d %s entries are needed"
-                  % (start.dtype, start.shape, n, block, np.dtype(want)))
-        start = np.ascontiguousarray(start.T)
-        X = np.zeros((max(nev, 1), max(n, 1)), dtype=want)
-        values, residuals = np.zeros(max(nev, 1), dtype=F64), np.zeros(max(nev, 1), dtype=F64)
-        result = np.zeros(8, dtype=I64)
-        hist = np.zeros(max(maxiter, 0) + 1, dtype=F64)
-        check("spl_lobpcg_solve",
-              lib().spl_lobpcg_solve(self.handle, nev, self._which(largest), float(tol), float(atol), maxiter,
-                                     p_f64(start.view(F64)), max(n, 1), p_f64(values), p_f64(X.view(F64)), max(n, 1),
-                                     p_f64(residuals), _ffi.p_i64(result), p_f64(hist)))
-        values, res = self._result(result, values, residuals, hist)
-        return values, X[:res["pairs"], :n].T.copy(), res
+        start, want, is_tensor = _vector_arg(where, X0, (n, block), cplx, "a start", "start")
+
+        def on_host(start_p, vectors_p):
+            values, residuals, result, hist = self._buffers(nev, maxiter)
+            check("spl_lobpcg_solve",
+                  lib().spl_lobpcg_solve(self.handle, nev, self._which(largest), float(tol), float(atol), maxiter, start_p,
+                                         max(n, 1), p_f64(values), vectors_p, max(n, 1), p_f64(residuals),
+                                         _ffi.p_i64(result), p_f64(hist)))
+            return self._result(result, values, residuals, hist)
+
+        return self._solve_pairs(nev, n, start.T, want, is_tensor,  # .T: one column after the other
+                                 lambda X0_ptr, vectors_ptr, stream: self.solve_dev(
+                                     nev, X0_ptr, max(n, 1), vectors_ptr, max(n, 1), largest, tol, atol, maxiter, True, stream),
+                                 on_host)
 
 
 def lobpcg(mat, X0, nev=None, largest=False, M=None, tol=1e-8, atol=0.0, maxiter=200):
@@ -1841,7 +1769,7 @@ class _DeviceArray(object):
         self.__cuda_array_interface__ = {"shape": (int(n),), "typestr": typestr, "data": (int(ptr), False), "version": 2}
 
 
-class AMG(object):
+class AMG(_ffi.Handle):
     """Owner of a ``void *M`` from ``spl_amg_create``: the aggregation AMG hierarchy of a whole square device handle and
     its V-cycle (csrc/amg.hip), real or complex.  Every level is the composition of the public handle operations that
     include/sparse_linear_hip.h lists, and ``apply`` is that header's cycle bit for bit.  ``KrylovSolver(A, method, M=amg)``
@@ -1855,8 +1783,7 @@ class AMG(object):
         unknown = sorted(set(options) - set(self.OPTIONS))
         if unknown:
             raise TypeError("AMG: unknown option %s; the options are %s" % (", ".join(unknown), ", ".join(self.OPTIONS)))
-        self._m = C.c_void_p()
-        self._finalizer = weakref.finalize(self, AMG._free, self._m)
+        _ffi.Handle.__init__(self, "spl_amg_free")
         self.A = A
         opt = np.zeros(8, dtype=I64)
         opt[0] = int(options.get("seed", 0))
@@ -1865,23 +1792,7 @@ class AMG(object):
         opt[3] = int(options.get("max_levels", 0))
         opt[4] = int(options.get("coarse_sweeps", 0))
         opt[5] = 1 if options.get("plain", False) else 0
-        check("spl_amg_create", lib().spl_amg_create(A.handle, _ffi.p_i64(opt), C.byref(self._m)))
-
-    @staticmethod
-    def _free(m):
-        try:
-            lib().spl_amg_free(C.byref(m))
-        except Exception:  # interpreter shutdown
-            pass
-
-    def free(self):
-        self._finalizer()
-
-    @property
-    def handle(self):
-        if not self._m.value:
-            raise _ffi.SparseLinearError("AMG", _ffi.SPL_ERROR_invalid_handle)
-        return self._m
+        check("spl_amg_create", lib().spl_amg_create(A.handle, _ffi.p_i64(opt), C.byref(self._h)))
 
     def info(self):
         out = np.zeros(8, dtype=I64)
@@ -1924,20 +1835,15 @@ class AMG(object):
         """the cycle of b: a numpy array for a numpy array, a device tensor (on torch's current stream) for one"""
         inf = self.info()
         n, cplx = inf["n"], inf["complex"]
-        import torch
-        if isinstance(b, torch.Tensor):
-            want = torch.complex128 if cplx else torch.float64
-            if not (b.is_cuda and b.dtype == want and tuple(b.shape) == (n,)):
-                _oops("AMG.apply", "a device tensor of %d %s entries is needed" % (n, want))
+        a, want, is_tensor = _vector_arg("AMG.apply", b, (n,), cplx, "a vector")
+        if is_tensor:
+            import torch
             with torch.cuda.device(b.device):
                 bb = b.contiguous()
                 x = torch.empty(max(n, 1), dtype=want, device=b.device)[:n]
                 self.apply_dev(bb.data_ptr(), x.data_ptr(), torch.cuda.current_stream().cuda_stream)
             return x
-        want = C128 if cplx else F64
-        a = np.ascontiguousarray(b)
-        if a.dtype != want or a.shape != (n,):
-            _oops("AMG.apply", "a vector of dtype %s and shape %s; %d %s entries are needed" % (a.dtype, a.shape, n, np.dtype(want)))
+        a = np.ascontiguousarray(a)
         x = np.zeros(n, dtype=want)
         check("spl_amg_apply", lib().spl_amg_apply(self.handle, p_f64(a.view(F64)), p_f64(x.view(F64))))
         return x

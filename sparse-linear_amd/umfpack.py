@@ -7,7 +7,6 @@ imports (Umfpack/Internal.hs:137-148).  Handles are owned like the reference's F
 the free function is the finalizer and receives a ``void**``.
 """
 import ctypes as C
-import weakref
 
 import numpy as np
 
@@ -100,20 +99,12 @@ def _report(where, status):
     return status
 
 
-class _Handle(object):
+class _Handle(_ffi.Handle):
     def __init__(self, value, free_name):
-        self._h = C.c_void_p(value)
-        self._finalizer = weakref.finalize(self, _Handle._free, self._h, free_name)
-
-    @staticmethod
-    def _free(h, free_name):
-        try:
-            getattr(lib(), free_name)(C.byref(h))
-        except Exception:
-            pass
+        _ffi.Handle.__init__(self, free_name, value)
 
     @property
-    def value(self):
+    def value(self):  # not checked: a NULL object comes back as the call's own status
         return self._h
 
 

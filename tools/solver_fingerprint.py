@@ -6,11 +6,13 @@ the library bit for bit (a refactor of the host side must not move one).
   BiCGSTAB         convection-diffusion 12 x 12 (not symmetric): no preconditioner, ILU(0)
   GMRES(5), (30)   the same: no preconditioner, ILU(0), amg
   eigsh            2-D Poisson 12 x 12: 'LA', 'SA', and shift-invert about sigma (with and without jacobi inside)
+  lobpcg           the same matrix: block 4, 3 pairs, smallest and largest: no preconditioner, jacobi, amg
 
 Every case real and complex (the Poisson matrix with Hermitian imaginary off-diagonals, the other with complex
 convection), right-hand sides and starts from a fixed seed.  A linear case hashes x, the history and the integer
 results, the reason among them (GMRES: its two residuals too); an eigsh case the values, the vectors, the residuals,
-the history and the integer results.
+the history and the integer results; its "+launches" twin and every lobpcg case also info()["launches"] after the
+solve.  The "dev" cases go through solve_dev with torch tensors.
 
 python tools/solver_fingerprint.py [--lib path/to/libsparse_linear_hip.so] [--out file.json]
 Prints one JSON object {case: sha256}; two builds agree when the two objects are equal."""
@@ -110,16 +112,43 @@ def main():
                 linear("gmres(%d) %s" % (restart, name), uns.gmres(restart, preconditioner(uns, name)))
         linear("gmres(5) None x0", uns.gmres(5, None), x0)
 
-        def eigen(label, **kw):
-            values, vectors, res = spd.eigsh(3, ncv=12, tol=1e-10, max_restarts=200, **kw)
-            ints = [res[k] for k in ("reason", "cycles", "applications", "pairs", "inner_iterations", "jacobi_sweeps")]
-            out["%s %s" % (label, kind)] = digest(np, values, vectors, res["residuals"], res["history"],
-                                                  np.array(ints, dtype=I64))
+        def eigen_digest(res, values, vectors, *more):
+            ints = [res[k] for k in res if isinstance(res[k], int) and not isinstance(res[k], bool)] + list(more)
+            return digest(np, values, vectors, res["residuals"], res["history"], np.array(ints, dtype=I64))
 
-        eigen("eigsh LA", which="LA")
-        eigen("eigsh SA", which="SA")
-        eigen("eigsh sigma=0.05 LM", which="LM", sigma=0.05)  # below the spectrum: the inner CG stays positive definite
-        eigen("eigsh sigma=0.05 LM jacobi", which="LM", sigma=0.05, M="jacobi")
+        def eigen(label, which, sigma=None, M=None):
+            E = pkg.EigenSolver(spd, 12, sigma, M)
+            values, vectors, res = E.solve(3, which, 1e-10, 0.0, 200)
+            out["%s %s" % (label, kind)] = eigen_digest(res, values, vectors)
+            out["%s +launches %s" % (label, kind)] = eigen_digest(res, values, vectors, E.info()["launches"])
+            E.free()
+
+        eigen("eigsh LA", "LA")
+        eigen("eigsh SA", "SA")
+        eigen("eigsh sigma=0.05 LM", "LM", 0.05)  # below the spectrum: the inner CG stays positive definite
+        eigen("eigsh sigma=0.05 LM jacobi", "LM", 0.05, "jacobi")
+
+        X0 = rng.standard_normal((n, 4)) + (1j * rng.standard_normal((n, 4)) if cplx else 0.0)
+        for name in (None, "jacobi", "amg"):
+            for largest in (False, True):
+                L = pkg.LOBPCGSolver(spd, 4, preconditioner(spd, name))
+                values, vectors, res = L.solve(X0, 3, largest, 1e-8, 0.0, 200)
+                out["lobpcg %s %s %s" % (name, "largest" if largest else "smallest", kind)] = eigen_digest(
+                    res, values, vectors, L.info()["launches"])
+                L.free()
+
+        # the same two solvers through solve_dev, on torch tensors and torch's current stream
+        stream = torch.cuda.current_stream().cuda_stream
+        dX0 = torch.from_numpy(np.ascontiguousarray(X0.T)).cuda()
+        dX = torch.zeros((3, n), dtype=dX0.dtype, device="cuda")
+        E = pkg.EigenSolver(spd, 12)
+        values, res = E.solve_dev(3, dX0.data_ptr(), dX.data_ptr(), n, "SA", 1e-10, 0.0, 200, True, stream)
+        out["eigsh SA dev %s" % kind] = eigen_digest(res, values, dX.cpu().numpy(), E.info()["launches"])
+        E.free()
+        L = pkg.LOBPCGSolver(spd, 4, "jacobi")
+        values, res = L.solve_dev(3, dX0.data_ptr(), n, dX.data_ptr(), n, False, 1e-8, 0.0, 200, True, stream)
+        out["lobpcg jacobi smallest dev %s" % kind] = eigen_digest(res, values, dX.cpu().numpy(), L.info()["launches"])
+        L.free()
     text = json.dumps(out, indent=1, sort_keys=True)
     print(text)
     if args.out:
