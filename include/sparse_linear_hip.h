@@ -1179,8 +1179,48 @@ void spl_eigsh_free(void **E);
  *   finish:   d_vectors = the first nev columns of X as the last close left them;
  *             values[i] = theta_i;  residuals[i] = sqrt(Re<r,r>), r = A x_i - theta_i x_i with a fresh
  *             spl_matrix_spmv_dev product.
- * Limits: converged columns are not locked (they stay in the block and are iterated on); A x = lambda B x, interior
- * eigenvalues, row-block handles and several devices are not served.
+ * Limits: converged columns are not locked (they stay in the block and are iterated on); interior eigenvalues,
+ * row-block handles and several devices are not served.
+ *
+ * The generalized problem A x = lambda B x.  spl_lobpcg_set_mass gives the object a Hermitian positive definite handle B
+ *   (a FEM mass matrix); B is borrowed, as A is.  No solve with B is needed: the method above runs in the inner product
+ *   <u,v>_B = <u, B v>, with B S kept beside S and A S, so the Ritz problem stays a standard one.  The object then holds
+ *   10 block + 2 vectors (B S: 3 block; a second product for the residuals at the end); info[2] has bit 32, info[3] the
+ *   bytes, info[7] the columns multiplied by B in the last solve (result[2] stays A's).  B == NULL returns the object
+ *   to the standard method, releases that memory, and info[3] has its old value again.  Positive definiteness is the
+ *   caller's promise and is not tested.  Errors, in this order: SPL_ERROR_invalid_handle (L is no such object, or B is
+ *   no matrix handle); SPL_ERROR_dimension_mismatch (B is not n x n, of the other value kind, or on another device);
+ *   SPL_ERROR_invalid_matrix (B is a row block, or spl_matrix_hermitian says 0).
+ *   The method with B: everything not named here is the text above unchanged.
+ *   settle(c): q0 = Re<s_c, (B s)_c>;  c > 0:  c1_i = <(B s)_i, s_c>, i < c (one pass, B S as the basis);  s_c and (B s)_c
+ *             are updated TOGETHER with c1, ascending, a product and a difference per term (spl_vector_update_pair_dev's
+ *             kernel);  c2_i likewise, and the paired update with c2, which delivers q2 = Re<s_c, (B s)_c>  (c == 0: q2
+ *             is q0 computed again).  q0 or q2 not finite: flag_c = 2;  else q0 < 0 or q2 < 0: flag_c = 1;  else
+ *             eta0 = sqrt(q0), eta2 = sqrt(q2), eta2 == 0 or eta2 <= 2^-40 eta0: flag_c = 1;  else flag_c = 0.
+ *             flag_c != 0: s_c and (B s)_c become +0.0;  else both are divided by eta2.
+ *   settle of X' after a close: (A s)_c receives the same coefficients, the division and the zeros, as above.
+ *   close(m, k): G = S^H (A S), upper, unchanged; the rotation is applied in place to S, A S and B S.
+ *   start:    X = X0;  B X by one product of b columns (spl_matrix_spmv_many_dev on B);  settle(0) ... settle(b-1), the
+ *             flags as above;  A X by one product;  close(b, b).
+ *   iteration: r_i = (A x)_i - theta_i (B x)_i, one product part by part and one difference per entry;  rho_i =
+ *             sqrt(Re<r_i,r_i>), the Euclidean norm; the convergence rule is unchanged.  w_i = M^-1 r_i into column
+ *             2 b + i;  B W by one product of b columns into (B S)[:, 2b:3b] (P's image is the rotation's);
+ *             settle(b) ... settle(3 b - 1);  A [P | W] by one product of 2 b columns;  close(3 b, 2 b).
+ *   finish:   values[i] = theta_i;  residuals[i] = |A x_i - theta_i B x_i|_2 from fresh spl_matrix_spmv_dev products
+ *             on A and on B.  The vectors are B-orthonormal.
+ *   With B an identity handle every quantity equals the standard method's bit for bit, but for the sign of a zero that
+ *   an identity product may turn positive.  Two synchronisations per iteration, as above; the launch sequence does not
+ *   depend on what dropped.  Lanczos (spl_eigsh_*) takes no mass matrix; a B that is not definite is not served.
+ *
+ * spl_vector_update_pair_dev: w = ((w - c_0 v_0) - c_1 v_1) - ... and bw = ((bw - c_0 (Bv)_0) - c_1 (Bv)_1) - ... over
+ *   the k columns of V and BV (laid out as in spl_vector_dots_dev, ldv, ldbv >= n), ascending, with the same k
+ *   coefficients d_coef (device memory) for both, in ONE launch: each term is one product (Data.Complex's on packed
+ *   pairs) and one difference.  With d_q given, *d_q = Re<w, bw> of the results, the real part of what
+ *   spl_vector_dot_dev(n, value_width, w, bw, ...) writes bit for bit; SPL_KRYLOV_GRID does not show in the bits.
+ *   1 <= k <= 128; n == 0 returns SPL_OK and +0.0 goes to d_q.  Enqueues on `stream`, no synchronisation.  Errors, in
+ *   this order: SPL_ERROR_n_nonpositive (n < 0); SPL_ERROR_argument_missing (value_width not 1 or 2, k out of range,
+ *   ldv < n or ldbv < n; a NULL pointer other than d_q, the vector pointers only when n > 0; a pointer not aligned to an
+ *   entry; w or bw overlapping each other, V or BV).
  *
  * spl_lobpcg_solve_dev: d_X0 (block columns, ldx0 >= n entries apart) and d_vectors (nev columns, ldx >= n apart) are
  *   DEVICE arrays; values, residuals (nev doubles each), result and history (NULL, or max_iter + 1 doubles) are the
@@ -1198,7 +1238,7 @@ void spl_eigsh_free(void **E);
  * spl_lobpcg_solve: the same with a HOST X0 and HOST vectors, on the default stream.
  * spl_lobpcg_info: [0] n, [1] block, [2] flags (1 complex, and 2 / 4 / 8 / 16 as spl_krylov_info's), [3] bytes of device
  *   memory, [4] solves, [5] iterations of the last solve, [6] launches of the last solve (a product counted as
- *   one, a Gram matrix as the kernels it enqueues, whatever its cut), [7] 0.
+ *   one, a Gram matrix as the kernels it enqueues, whatever its cut), [7] 0 (with a mass matrix: see below).
  * spl_lobpcg_free: idempotent, as spl_krylov_free. */
 int spl_lobpcg_create(void *A, int block, void **L);
 int spl_lobpcg_set_preconditioner(void *L, void *T1, const double *d_mid, void *T2);
@@ -1211,6 +1251,9 @@ int spl_lobpcg_solve(void *L, int nev, int which, double tol, double atol, int64
                      double *history);
 int spl_lobpcg_info(void *L, int64_t info[8]);
 void spl_lobpcg_free(void **L);
+int spl_lobpcg_set_mass(void *L, void *B);
+int spl_vector_update_pair_dev(int64_t n, int value_width, int k, const double *d_V, int64_t ldv, const double *d_BV,
+                               int64_t ldbv, const double *d_coef, double *d_w, double *d_bw, double *d_q, void *stream);
 
 /* select a kernel variant for spl_matrix_spmv_dev (tuning / ablation only): 0 = default
  * (whatever spl_matrix_optimize chose), 1-6 CSR-stream shapes, 7 sub-wavefront kernel, 8

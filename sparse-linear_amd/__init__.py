@@ -20,7 +20,7 @@ from .sparse import DeviceMatrix, Matrix, SparseError  # noqa: F401
 from .sparse import GMRESSolver, gmres, vector_dots_dev  # noqa: F401
 from .sparse import EigenSolver, eigsh, vector_rotate_dev  # noqa: F401
 from .sparse import vector_gram_dev  # noqa: F401
-from .sparse import LOBPCGSolver, lobpcg  # noqa: F401
+from .sparse import LOBPCGSolver, lobpcg, vector_update_pair_dev  # noqa: F401
 from .foreign import fromForeign, withConstMatrix  # noqa: F401
 from . import dist  # noqa: F401
 from . import umfpack  # noqa: F401

@@ -201,6 +201,9 @@ def _declare(L):
                                  c_dbl_p, C.c_void_p],
         "spl_lobpcg_solve": [C.c_void_p, i, i, d, d, i64, c_dbl_p, i64, c_dbl_p, c_dbl_p, i64, c_dbl_p, c_i64_p, c_dbl_p],
         "spl_lobpcg_info": [C.c_void_p, c_i64_p],
+        "spl_lobpcg_set_mass": [C.c_void_p, C.c_void_p],
+        "spl_vector_update_pair_dev": [i64, i, i, C.c_void_p, i64, C.c_void_p, i64, C.c_void_p, C.c_void_p, C.c_void_p,
+                                       C.c_void_p, C.c_void_p],
         "spl_matrix_set_variant": [C.c_void_p, i],
         "spl_matrix_optimize": [C.c_void_p],
         "spl_matrix_build_blocked": [C.c_void_p, i, i, i],

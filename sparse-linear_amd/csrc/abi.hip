@@ -2158,6 +2158,52 @@ int spl_lobpcg_set_preconditioner_amg(void *L, void *M) {
   return set_preconditioner_amg_of(L, as_lobpcg, lobpcg_set_preconditioner_amg, M);
 }
 
+// B is borrowed, as A is; NULL: the standard problem again
+int spl_lobpcg_set_mass(void *L, void *B) {
+  Lobpcg *S = as_lobpcg(L);
+  if (!S) return SPL_ERROR_invalid_handle;
+  Matrix *M = nullptr;
+  if (B) {
+    M = as_matrix(B);
+    if (!M) return SPL_ERROR_invalid_handle;
+    const ObjectHead &o = head(S);
+    if (M->nrows_global != o.n || M->ncols != o.n || M->vw != o.vw || M->device != o.device)
+      return SPL_ERROR_dimension_mismatch;
+    if (!whole(M) || !M->rowptr.get()) return SPL_ERROR_invalid_matrix;
+  }
+  return guarded([&]() -> int {
+    DeviceGuard g(head(S).device);
+    if (M && hermitian_device(M, nullptr) != 1) return SPL_ERROR_invalid_matrix;
+    lobpcg_set_mass(S, M);
+    return SPL_OK;
+  });
+}
+
+// ---- the paired update of a column and its image under B (csrc/basis_pair.hpp) ------------------------------------------
+int spl_vector_update_pair_dev(int64_t n, int value_width, int k, const double *d_V, int64_t ldv, const double *d_BV,
+                               int64_t ldbv, const double *d_coef, double *d_w, double *d_bw, double *d_q, void *stream) {
+  if (n < 0) return SPL_ERROR_n_nonpositive;
+  if (value_width != 1 && value_width != 2) return SPL_ERROR_argument_missing;
+  if (k < 1 || k > 128 || ldv < n || ldbv < n) return SPL_ERROR_argument_missing;
+  if (!d_coef || (n > 0 && (!d_V || !d_BV || !d_w || !d_bw))) return SPL_ERROR_argument_missing;
+  const uintptr_t entry = (uintptr_t)(8 * value_width);  // the kernel loads and stores whole entries
+  if ((uintptr_t)d_V % entry != 0 || (uintptr_t)d_BV % entry != 0 || (uintptr_t)d_coef % entry != 0 ||
+      (uintptr_t)d_w % entry != 0 || (uintptr_t)d_bw % entry != 0 || (uintptr_t)d_q % sizeof(double) != 0)
+    return SPL_ERROR_argument_missing;
+  if (n > 0) {  // w and bw beside each other and beside the blocks, not inside them
+    const uintptr_t w0 = (uintptr_t)d_w, w1 = w0 + (uintptr_t)n * entry, b0 = (uintptr_t)d_bw, b1 = b0 + (uintptr_t)n * entry;
+    const uintptr_t v0 = (uintptr_t)d_V, v1 = v0 + ((uintptr_t)(k - 1) * (uintptr_t)ldv + (uintptr_t)n) * entry;
+    const uintptr_t u0 = (uintptr_t)d_BV, u1 = u0 + ((uintptr_t)(k - 1) * (uintptr_t)ldbv + (uintptr_t)n) * entry;
+    if ((w0 < b1 && b0 < w1) || (w0 < v1 && v0 < w1) || (w0 < u1 && u0 < w1) || (b0 < v1 && v0 < b1) ||
+        (b0 < u1 && u0 < b1))
+      return SPL_ERROR_argument_missing;
+  }
+  return guarded([&]() -> int {
+    return vector_update_pair(current_device(), n, value_width, k, d_V, ldv, d_BV, ldbv, d_coef, d_w, d_bw, d_q,
+                              as_stream(stream));
+  });
+}
+
 int spl_lobpcg_solve_dev(void *L, int nev, int which, double tol, double atol, int64_t max_iter, const double *d_X0,
                          int64_t ldx0, double *values, double *d_vectors, int64_t ldx, double *residuals,
                          int64_t result[8], double *history, void *stream) {

@@ -471,6 +471,13 @@ int lobpcg_solve(Lobpcg *L, int nev, int which, double tol, double atol, int64_t
                  int64_t ldx0, double *values, double *d_vectors, int64_t ldx, double *residuals, int64_t result[8],
                  double *history, hipStream_t s);
 void lobpcg_info(Lobpcg *L, int64_t info[8]);
+// B: borrowed; whole, square, Hermitian and of L's size, value kind and device (the caller checked), or nullptr: the
+// standard problem again, and the vectors of B S are released
+void lobpcg_set_mass(Lobpcg *L, const Matrix *B);
+// w = ((w - c_0 v_0) - ...) and bw = ((bw - c_0 (Bv)_0) - ...) over k columns in one pass, and Re<w, bw> of the results
+// to d_q (may be nullptr), the real part of vector_dot's value bit for bit; enqueues on s, no synchronisation
+int vector_update_pair(int device, int64_t n, int vw, int k, const double *d_V, int64_t ldv, const double *d_BV,
+                       int64_t ldbv, const double *d_coef, double *d_w, double *d_bw, double *d_q, hipStream_t s);
 int lobpcg_block(const Lobpcg *L);
 void lobpcg_delete(Lobpcg *L);
 

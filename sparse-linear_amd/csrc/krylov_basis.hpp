@@ -4,7 +4,7 @@
 // and the two first levels the eigensolvers fold to a scalar, a norm and a pair's residual (norm_kernel,
 // residual_kernel).  The arithmetic is the fold of krylov_fold.hpp: every value is what k separate inner products and
 // k separate updates would give, bit for bit.  Device code and the host code that launches it; included by those
-// three files only.
+// three files only (lobpcg.hip also through basis_pair.hpp, the same step in the inner product of a mass matrix).
 #pragma once
 
 #include "krylov_fold.hpp"

@@ -11,10 +11,16 @@
 // only, so the launch sequence of an iteration is the same whatever drops, and the host removes the flagged rows and
 // columns from T.  Two synchronisations per iteration: the residual norms; T and the flags.  No captured graph, no
 // floating-point atomic, no kernel waits for another workgroup.
+//
+// With a mass matrix (spl_lobpcg_set_mass) the same method runs in the inner product <u,v>_B = <u, B v> for
+// A x = lambda B x: B S is kept beside S and A S, a column is settled together with its image under B by the paired
+// update of basis_pair.hpp, the residual is that of the pencil and the rotation is applied to B S too.  Every such step
+// is behind `if (B)`: without a mass matrix the kernels, their order and the tables are what they were.
 #include <algorithm>
 #include <cmath>
 #include <vector>
 
+#include "basis_pair.hpp"
 #include "krylov_basis.hpp"
 #include "ritz_jacobi.hpp"
 #include "solver_core.hpp"
@@ -65,6 +71,21 @@ __global__ __launch_bounds__(kLanes) void decide_kernel(const double *part, int 
   else *flag = 0;
 }
 
+// The same behind the passes of a column in the inner product of a mass matrix: q2 = Re<s, B s> from the last partials,
+// q0 from the table.  A negative q says that B is not positive definite on the column: dropped
+__global__ __launch_bounds__(kLanes) void decide_pair_kernel(const double *part, int count, const double *q0p,
+                                                             double *scale, int *flag) {
+  const double q2 = sum_partials(part, count);
+  if (threadIdx.x != 0) return;
+  const double q0 = *q0p;
+  const double e2 = sqrt(q2), e0 = sqrt(q0);
+  *scale = e2;
+  if (!isfinite(q0) || !isfinite(q2)) *flag = 2;
+  else if (q0 < 0.0 || q2 < 0.0) *flag = 1;
+  else if (e2 == 0.0 || e2 <= kDropRatio * e0) *flag = 1;
+  else *flag = 0;
+}
+
 // w = w / scale part by part, or zeros when the column is flagged
 template <int VW>
 __global__ __launch_bounds__(kLanes) void settle_kernel(int64_t n, const int *flag, const double *scale, double *w) {
@@ -78,9 +99,13 @@ __global__ __launch_bounds__(kLanes) void settle_kernel(int64_t n, const int *fl
 }  // namespace
 
 // ---- the solver object (the shared part: solver_core.hpp) ---------------------------------------------------------------
+// with a mass matrix 3 block + 1 more (`mass`): 10 block + 2 in all
 struct Lobpcg : SolverCore {  // work: 7 block + 1 vectors: S (3 block), A S (3 block), R (block), one product
   int block;
   Preconditioner pre;
+  const Matrix *B = nullptr;     // the mass matrix of A x = lambda B x, borrowed; nullptr: the standard problem
+  DBuf<double> mass;             // with B: 3 block + 1 vectors, B S and a second product
+  int64_t last_mass_columns = 0;  // columns multiplied by B in the last solve
   DBuf<double> tables;
   DBuf<int> flags;               // 3 block
   StatusBlock<LStatus> status;   // behind the pinned copy: G, Z, res and the flags of the host
@@ -94,6 +119,7 @@ struct Lobpcg : SolverCore {  // work: 7 block + 1 vectors: S (3 block), A S (3 
   double *host_z() const { return host_g() + (size_t)18 * block * block; }
   double *host_res() const { return host_z() + (size_t)12 * block * block; }
   int *host_flags() const { return reinterpret_cast<int *>(host_res() + block); }
+  size_t mass_doubles() const { return ((size_t)3 * block + 1) * (size_t)n * (size_t)vw; }
 };
 
 // A: whole, square and Hermitian, 1 <= block <= 42 (the caller checked)
@@ -112,6 +138,20 @@ void lobpcg_set_preconditioner_amg(Lobpcg *L, Amg *M) {
   L->pre.set_amg(M);
 }
 
+// B: whole, square, Hermitian and of L's size, value kind and device (the caller checked), or nullptr
+void lobpcg_set_mass(Lobpcg *L, const Matrix *B) {
+  std::lock_guard<std::mutex> hold(L->lock);
+  if (B && !L->B) {
+    L->mass.alloc(L->mass_doubles());
+    L->bytes += L->mass_doubles() * sizeof(double);
+  } else if (!B && L->B) {
+    L->mass.release();
+    L->bytes -= L->mass_doubles() * sizeof(double);
+  }
+  L->B = B;
+  L->last_mass_columns = 0;
+}
+
 int lobpcg_block(const Lobpcg *L) { return L->block; }
 
 namespace {
@@ -124,17 +164,20 @@ struct LRun : RunCore {
   LTables T;
   int *flags;
   const int *never;  // the flag that is never set
-  int64_t spmv_columns = 0, applications = 0, sweeps_most = 0, dropped = 0, syncs = 0;
+  const Matrix *B;   // the mass matrix, or nullptr
+  int64_t spmv_columns = 0, mass_columns = 0, applications = 0, sweeps_most = 0, dropped = 0, syncs = 0;
   std::vector<double> theta;  // of the block's columns
 
   LRun(Lobpcg *l, hipStream_t stream)
       : RunCore(*l, stream), L(l), b(l->block), T(ltables_at(l->tables.get(), l->block)), flags(l->flags.get()),
-        never(&l->status.device.get()->zero), theta((size_t)l->block, 0.0) {}
+        never(&l->status.device.get()->zero), B(l->B), theta((size_t)l->block, 0.0) {}
 
   double *basis(int j) const { return L->vec(j); }               // S
   double *image(int j) const { return L->vec(3 * b + j); }       // A S
   double *residual(int j) const { return L->vec(6 * b + j); }    // R, when a preconditioner reads it
   double *product() const { return L->vec(7 * b); }
+  double *mass_image(int j) const { return L->mass.get() + (size_t)j * (size_t)n * VW; }  // B S
+  double *mass_product() const { return mass_image(3 * b); }
 
   void sync() {
     SPL_HIP(hipStreamSynchronize(s));
@@ -150,6 +193,7 @@ struct LRun : RunCore {
 
   // column c of S against the c columns before it: the norm before, the two passes, the decision, the division
   void settle_column(int c) {
+    if (B) return settle_column_mass(c);
     double *w = basis(c);
     norm_to(w, T.eta0 + c);
     Partials P;
@@ -165,6 +209,38 @@ struct LRun : RunCore {
     hipLaunchKernelGGL((settle_kernel<VW>), dim3(flat), dim3(kLanes), 0, s, n, (const int *)(flags + c),
                        (const double *)(T.scale + c), w);
     launches += 2;
+  }
+
+  // Re<a,b> of n entries: its first level in scratch
+  void pair_norm(const double *a, const double *bv) {
+    hipLaunchKernelGGL((pair_norm_kernel<VW>), dim3(chunked), dim3(kLanes), 0, s, n, a, bv, scratch);
+    ++launches;
+  }
+
+  // settle_column in the inner product of B: s_c and (B s)_c against the columns before them, the coefficients from
+  // B S, both updated in one pass that also leaves Re<s_c, (B s)_c>
+  void settle_column_mass(int c) {
+    double *w = basis(c), *bw = mass_image(c);
+    pair_norm(w, bw);
+    fold_to(T.eta0 + c);
+    Partials P;
+    if (c > 0) {
+      launches += dots_launch<VW>(never, n, c, mass_image(0), n, w, T.c1, scratch, s);
+      update_pair_launch<VW>(never, n, c, basis(0), n, mass_image(0), n, T.c1, w, bw, false, scratch, chunked, s);
+      launches += dots_launch<VW>(never, n, c, mass_image(0), n, w, T.c2, scratch, s);
+      update_pair_launch<VW>(never, n, c, basis(0), n, mass_image(0), n, T.c2, w, bw, true, scratch, chunked, s);
+      launches += 2;
+    } else {
+      pair_norm(w, bw);
+    }
+    P = last_level();
+    hipLaunchKernelGGL(decide_pair_kernel, dim3(1), dim3(kLanes), 0, s, P.p, P.count, (const double *)(T.eta0 + c),
+                       T.scale + c, flags + c);
+    hipLaunchKernelGGL((settle_kernel<VW>), dim3(flat), dim3(kLanes), 0, s, n, (const int *)(flags + c),
+                       (const double *)(T.scale + c), w);
+    hipLaunchKernelGGL((settle_kernel<VW>), dim3(flat), dim3(kLanes), 0, s, n, (const int *)(flags + c),
+                       (const double *)(T.scale + c), bw);
+    launches += 3;
   }
 
   // X' behind a rotation is orthonormal to the rounding of the rotation only, and that loss adds up over the iterations
@@ -186,10 +262,14 @@ struct LRun : RunCore {
     }
   }
 
-  // r_i = ax - theta_i x_i to `out` (nullptr: not stored) and Re<r_i,r_i> to res[i]; ax: A x_i
-  void residual_of(int i, const double *ax, double *out) {
-    hipLaunchKernelGGL((residual_kernel<VW>), dim3(chunked), dim3(kLanes), 0, s, n, ax, (const double *)basis(i), theta[i],
-                       out, scratch);
+  // r_i = ax - theta_i x_i (with a mass matrix: ax - theta_i bx) to `out` (nullptr: not stored) and Re<r_i,r_i> to
+  // res[i]; ax: A x_i, bx: B x_i
+  void residual_of(int i, const double *ax, const double *bx, double *out) {
+    if (B)
+      hipLaunchKernelGGL((pencil_residual_kernel<VW>), dim3(chunked), dim3(kLanes), 0, s, n, ax, bx, theta[i], out, scratch);
+    else
+      hipLaunchKernelGGL((residual_kernel<VW>), dim3(chunked), dim3(kLanes), 0, s, n, ax, (const double *)basis(i), theta[i],
+                         out, scratch);
     ++launches;
     fold_to(T.res + i);
   }
@@ -246,6 +326,10 @@ struct LRun : RunCore {
     if ((e = vector_rotate(n, VW, mc, kout, basis(0), n, T.Z, mc, nullptr, 0, s, VW == 2)) != SPL_OK) return e;
     if ((e = vector_rotate(n, VW, mc, kout, image(0), n, T.Z, mc, nullptr, 0, s, VW == 2)) != SPL_OK) return e;
     launches += 2;
+    if (B) {
+      if ((e = vector_rotate(n, VW, mc, kout, mass_image(0), n, T.Z, mc, nullptr, 0, s, VW == 2)) != SPL_OK) return e;
+      ++launches;
+    }
     for (int i = 0; i < b; ++i) theta[i] = value(order[i]);
     settle_block();
     return SPL_OK;
@@ -280,7 +364,13 @@ struct LRun : RunCore {
         if (st != SPL_OK) return st;
         ++spmv_columns;
         ++launches;
-        residual_of(i, product(), nullptr);
+        if (B) {
+          const int sb = launch_spmv(B, basis(i), mass_product(), 0, s);
+          if (sb != SPL_OK) return sb;
+          ++mass_columns;
+          ++launches;
+        }
+        residual_of(i, product(), B ? mass_product() : nullptr, nullptr);
       }
       const int st = launch_status("lobpcg finish");
       if (st != SPL_OK) return st;
@@ -296,6 +386,12 @@ struct LRun : RunCore {
     for (int j = 0; j < b; ++j)
       SPL_HIP(hipMemcpyAsync(basis(j), d_X0 + (size_t)j * (size_t)ldx0 * VW, column, hipMemcpyDeviceToDevice, s));
     SPL_HIP(hipMemsetAsync(basis(b), 0, column * (size_t)b, s));
+    if (B) {  // B X by one product; the image of P = 0 is zero
+      SPL_HIP(hipMemsetAsync(mass_image(b), 0, column * (size_t)b, s));
+      if ((e = launch_spmv_many(B, b, basis(0), n, mass_image(0), n, 0, s)) != SPL_OK) return e;
+      mass_columns += b;
+      ++launches;
+    }
     for (int j = 0; j < b; ++j) settle_column(j);
     if ((e = launch_status("lobpcg start")) != SPL_OK) return e;
     SPL_HIP(hipMemcpyAsync(L->host_flags(), flags, (size_t)3 * b * sizeof(int), hipMemcpyDeviceToHost, s));
@@ -316,7 +412,8 @@ struct LRun : RunCore {
     for (int64_t it = 0;; ++it) {
       iterations = it;
       const bool pre = L->pre.set();
-      for (int i = 0; i < b; ++i) residual_of(i, image(i), pre ? residual(i) : basis(2 * b + i));
+      for (int i = 0; i < b; ++i)
+        residual_of(i, image(i), B ? mass_image(i) : nullptr, pre ? residual(i) : basis(2 * b + i));
       if ((e = launch_status("lobpcg residuals")) != SPL_OK) return e;
       SPL_HIP(hipMemcpyAsync(L->host_res(), T.res, (size_t)b * sizeof(double), hipMemcpyDeviceToHost, s));
       sync();
@@ -339,6 +436,11 @@ struct LRun : RunCore {
           if ((e = L->pre.template apply<VW>(never, n, residual(i), basis(2 * b + i), flat, s, &launches)) != SPL_OK) return e;
           ++applications;
         }
+      }
+      if (B) {  // B W by one product; P's image is the rotation's
+        if ((e = launch_spmv_many(B, b, basis(2 * b), n, mass_image(2 * b), n, 0, s)) != SPL_OK) return e;
+        mass_columns += b;
+        ++launches;
       }
       for (int j = b; j < 3 * b; ++j) settle_column(j);  // P, then W
       if ((e = launch_spmv_many(L->A, 2 * b, basis(b), n, image(b), n, 0, s)) != SPL_OK) return e;
@@ -364,15 +466,47 @@ int lobpcg_solve(Lobpcg *L, int nev, int which, double tol, double atol, int64_t
     LRun<decltype(width)::value> run(L, s);
     const int e = run.solve(nev, which, tol, atol, max_iter, d_X0, ldx0, values, d_vectors, ldx, residuals, result, history);
     *launches = run.launches;
+    if (e == SPL_OK) L->last_mass_columns = run.mass_columns;
     return e;
   });
 }
 
 void lobpcg_info(Lobpcg *L, int64_t info[8]) {
   std::lock_guard<std::mutex> hold(L->lock);
-  L->fill_info(info, L->block, L->pre.flags());
+  L->fill_info(info, L->block, L->pre.flags() | (L->B ? 32 : 0));
+  info[7] = L->last_mass_columns;
 }
 
 void lobpcg_delete(Lobpcg *L) { delete_object(L); }
+
+// ---- spl_vector_update_pair_dev ---------------------------------------------------------------------------------------------
+// w and bw against the k columns of V and BV by the coefficients d_coef, and Re<w, bw> of the results to d_q when it is
+// given; enqueues on s.  Arguments checked by the caller.
+int vector_update_pair(int device, int64_t n, int vw, int k, const double *d_V, int64_t ldv, const double *d_BV,
+                       int64_t ldbv, const double *d_coef, double *d_w, double *d_bw, double *d_q, hipStream_t s) {
+  if (n == 0) {
+    if (d_q) SPL_HIP(hipMemsetAsync(d_q, 0, sizeof(double), s));  // +0.0
+    return SPL_OK;
+  }
+  DotBlock *block = d_q ? dot_block_take(device, fold_scratch(n, 1)) : nullptr;
+  double *scratch = block ? block->buf.get() : nullptr;
+  const unsigned chunked = chunk_grid(n);
+  if (vw == 1) update_pair_launch<1>(nullptr, n, k, d_V, ldv, d_BV, ldbv, d_coef, d_w, d_bw, d_q != nullptr, scratch, chunked, s);
+  else update_pair_launch<2>(nullptr, n, k, d_V, ldv, d_BV, ldbv, d_coef, d_w, d_bw, d_q != nullptr, scratch, chunked, s);
+  if (d_q) {
+    const Partials P = middle_levels(nullptr, n, 1, scratch, s);
+    hipLaunchKernelGGL(fold_kernel, dim3(1, 1), dim3(kLanes), 0, s, (const int *)nullptr, (int64_t)P.count, P.p, P.stride,
+                       d_q, (int64_t)1);
+  }
+  const hipError_t e = hipGetLastError();
+  if (e != hipSuccess) {
+    set_last_error("vector update pair launch", e);
+    (void)hipStreamSynchronize(s);
+    if (block) dot_block_give(block, s, false);
+    return SPL_ERROR_device;
+  }
+  if (block) dot_block_give(block, s, true);
+  return SPL_OK;
+}
 
 }  // namespace spl

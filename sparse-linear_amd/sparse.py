@@ -32,6 +32,9 @@ preconditioned CG and BiCGSTAB whose scalars stay on the device; ``vector_dot_de
 ``DeviceMatrix.gmres`` / ``GMRESSolver`` (``gmres`` from a host Matrix) is restarted GMRES for unsymmetric and indefinite
 systems with the same preconditioners; ``vector_dots_dev`` is the k-column inner product its orthogonalisation uses,
 and ``vector_gram_dev`` the k x l block of inner products of two column blocks in one pass.
+``DeviceMatrix.lobpcg`` / ``LOBPCGSolver`` (``lobpcg`` from a host Matrix) is the block eigensolver; with ``B=`` (or
+``LOBPCGSolver.set_mass``) it solves ``A x = lambda B x`` for a Hermitian positive definite mass matrix, and
+``vector_update_pair_dev`` is the paired update of a column and its image under ``B`` that its orthogonalisation uses.
 ``DeviceMatrix.amg`` / ``AMG`` (``amg`` from a host Matrix) build an aggregation multigrid hierarchy from the handle
 operations above, and its V-cycle is a preconditioner the solvers take (``M=<AMG>`` or ``M="amg"``).
 """
@@ -882,13 +885,14 @@ class DeviceMatrix(_ffi.Handle):
         finally:
             E.free()
 
-    def lobpcg(self, X0, nev=None, largest=False, M=None, tol=1e-8, atol=0.0, maxiter=200):
+    def lobpcg(self, X0, nev=None, largest=False, M=None, tol=1e-8, atol=0.0, maxiter=200, B=None):
         """(values, vectors, result dict): the nev smallest (largest=True: largest) eigenpairs of this whole square
         Hermitian handle by LOBPCG (spl_lobpcg_*) from the start block X0 (n x block, 1 <= block <= 42; nev defaults to
         the block), with the preconditioner M (as KrylovSolver takes it) applied inside the iteration.  A block method:
-        multiple eigenvalues come with their copies"""
+        multiple eigenvalues come with their copies.  B: a Hermitian positive definite DeviceMatrix, for
+        A x = lambda B x with B-orthonormal vectors"""
         block = int(X0.shape[1]) if getattr(X0, "ndim", 0) == 2 else 0
-        L = LOBPCGSolver(self, block, M)
+        L = LOBPCGSolver(self, block, M, B)
         try:
             return L.solve(X0, nev, largest, tol, atol, maxiter)
         finally:
@@ -1682,14 +1686,31 @@ class LOBPCGSolver(_PreconditionedSolver, _EigenPairs):
               "set_preconditioner_amg": "spl_lobpcg_set_preconditioner_amg", "info": "spl_lobpcg_info",
               "free": "spl_lobpcg_free"}
 
-    def __init__(self, A, block, M=None):
+    def __init__(self, A, block, M=None, B=None):
         block = int(block)
         if not 1 <= block <= 42:
             raise ValueError("LOBPCGSolver: block %r; 1 ... 42 is needed" % (block,))
         self._begin(A, M)
         self.block = block
+        self.B = None
         check("spl_lobpcg_create", lib().spl_lobpcg_create(A.handle, block, C.byref(self._h)))
         self.set_preconditioner(M)
+        if B is not None:
+            self.set_mass(B)
+
+    def set_mass(self, B):
+        """the generalized problem A x = lambda B x with the Hermitian positive definite DeviceMatrix B (a mass matrix),
+        which this object keeps alive; None: the standard problem again, and the memory of B S is released.  The vectors
+        of a solve are B-orthonormal and the residuals are those of the pencil"""
+        if B is not None and not isinstance(B, DeviceMatrix):
+            raise ValueError("LOBPCGSolver.set_mass: B %r; a DeviceMatrix or None is needed" % (B,))
+        check("spl_lobpcg_set_mass", lib().spl_lobpcg_set_mass(self.handle, B.handle if B is not None else None))
+        self.B = B
+
+    def info(self):
+        d = _PreconditionedSolver.info(self)
+        d.update(generalized=bool(d["flags"] & 32), mass_columns=d["reserved"])
+        return d
 
     @staticmethod
     def _history_entries(out, history):
@@ -1737,10 +1758,23 @@ class LOBPCGSolver(_PreconditionedSolver, _EigenPairs):
                                  on_host)
 
 
-def lobpcg(mat, X0, nev=None, largest=False, M=None, tol=1e-8, atol=0.0, maxiter=200):
+def lobpcg(mat, X0, nev=None, largest=False, M=None, tol=1e-8, atol=0.0, maxiter=200, B=None):
     """(values, vectors, result dict): the nev smallest (or largest) eigenpairs of the Hermitian host Matrix `mat` by
-    LOBPCG on the device from the start block X0 (DeviceMatrix.lobpcg)"""
-    return mat.device_handle().lobpcg(X0, nev, largest, M, tol, atol, maxiter)
+    LOBPCG on the device from the start block X0 (DeviceMatrix.lobpcg); B: a Hermitian positive definite host Matrix
+    for mat x = lambda B x"""
+    return mat.device_handle().lobpcg(X0, nev, largest, M, tol, atol, maxiter,
+                                      B.device_handle() if B is not None else None)
+
+
+def vector_update_pair_dev(n, k, V_ptr, ldv, BV_ptr, ldbv, coef_ptr, w_ptr, bw_ptr, q_ptr=None, is_complex=False, stream=0):
+    """w = ((w - c_0 v_0) - c_1 v_1) - ... and bw = ((bw - c_0 (Bv)_0) - ...) over the k columns of V and BV with the same
+    k coefficients, in ONE launch (spl_vector_update_pair_dev): the columns are laid out as vector_dots_dev's (ldv, ldbv
+    >= n), 1 <= k <= 128.  With q_ptr, one double receives Re<w, bw> of the results, the real part of vector_dot_dev's
+    value bit for bit.  Device pointers (ints); enqueues on `stream`, no sync"""
+    check("spl_vector_update_pair_dev",
+          lib().spl_vector_update_pair_dev(int(n), 2 if is_complex else 1, int(k), C.c_void_p(V_ptr), int(ldv),
+                                           C.c_void_p(BV_ptr), int(ldbv), C.c_void_p(coef_ptr), C.c_void_p(w_ptr),
+                                           C.c_void_p(bw_ptr), C.c_void_p(q_ptr) if q_ptr else None, C.c_void_p(stream)))
 
 
 def _krylov(method, mat, b, M, x0, rtol, atol, maxiter):

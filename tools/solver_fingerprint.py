@@ -6,7 +6,8 @@ the library bit for bit (a refactor of the host side must not move one).
   BiCGSTAB         convection-diffusion 12 x 12 (not symmetric): no preconditioner, ILU(0)
   GMRES(5), (30)   the same: no preconditioner, ILU(0), amg
   eigsh            2-D Poisson 12 x 12: 'LA', 'SA', and shift-invert about sigma (with and without jacobi inside)
-  lobpcg           the same matrix: block 4, 3 pairs, smallest and largest: no preconditioner, jacobi, amg
+  lobpcg           the same matrix: block 4, 3 pairs, smallest and largest: no preconditioner, jacobi, amg; and the
+                   smallest pairs with the 9-point mass matrix (a build without spl_lobpcg_set_mass has no such case)
 
 Every case real and complex (the Poisson matrix with Hermitian imaginary off-diagonals, the other with complex
 convection), right-hand sides and starts from a fixed seed.  A linear case hashes x, the history and the integer
@@ -136,6 +137,17 @@ def main():
                 out["lobpcg %s %s %s" % (name, "largest" if largest else "smallest", kind)] = eigen_digest(
                     res, values, vectors, L.info()["launches"])
                 L.free()
+
+        # the generalized problem: the 9-point mass matrix kron(T, T), T = tridiag(1, 4, 1), beside the same operator
+        if hasattr(pkg._ffi.lib(), "spl_lobpcg_set_mass"):  # --lib may name an older build
+            T = sp.diags([np.ones(M - 1), 4.0 * np.ones(M), np.ones(M - 1)], [-1, 0, 1])
+            mass = sp.csc_matrix(sp.kron(T, T)).astype(np.complex128 if cplx else np.float64)
+            mass.sort_indices()
+            L = pkg.LOBPCGSolver(spd, 4, None, handle_of(pkg, np, mass))
+            values, vectors, res = L.solve(X0, 3, False, 1e-8, 0.0, 200)
+            out["lobpcg None smallest mass %s" % kind] = eigen_digest(res, values, vectors, L.info()["launches"],
+                                                                      L.info()["mass_columns"])
+            L.free()
 
         # the same two solvers through solve_dev, on torch tensors and torch's current stream
         stream = torch.cuda.current_stream().cuda_stream
