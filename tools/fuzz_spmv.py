@@ -3,8 +3,14 @@
 columns, a few very long rows, skewed column distributions, rectangular shapes, duplicated-looking neighbours,
 sizes around the panel / block boundaries.  Every kernel family is forced in turn on the same handle (CSR-stream,
 sub-wavefront, column-blocked image, sliced ELL where its shape test admits the matrix, column-sorted panels in
-every storage form with random shapes) and compared with the oracle: bit for bit in the reference-order kernels,
-to 1e-10 (and exactly on integer data) in the order-free panels; y <- A x + y as well as y = A x.
+every storage form with random shapes, the rounds form among them) and compared with the oracle: bit for bit in the
+reference-order kernels, exactly on integer data and within the rounding bound of the row in the order-free panels;
+y <- A x + y as well as y = A x.
+
+The rounding bound is per row: any summation order of the separately rounded products of a row of n entries is within
+gamma_n sum |a| |x| of the exact sum (gamma_n = n u / (1 - n u), u = 2^-53; n + 1 terms and + |y0| when accumulating),
+so device and oracle differ by at most twice that.  The row's own length and scale: a bound scaled by the nnz of the
+whole matrix would let a row drop a small entry.
 python tools/fuzz_spmv.py [seed] [cases]"""
 import os
 import sys
@@ -13,6 +19,8 @@ import numpy as np
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
+
+U = 2.0 ** -53
 
 
 def structure(rng, kind, nr, nc):
@@ -68,13 +76,18 @@ def main():
         xh = rng.integers(-5, 6, nc).astype(float) if ints else rng.normal(size=nc)
         y0 = rng.integers(-5, 6, nr).astype(float) if ints else rng.normal(size=nr)
         ref, refa = O.mulV(A, xh), O.axpy(A, xh, y0)
-        scale = O.mulV((A[0], A[1], A[2], A[3], np.abs(A[4])), np.abs(xh)) + np.abs(y0)
+        sabs = O.mulV((A[0], A[1], A[2], A[3], np.abs(A[4])), np.abs(xh))   # sum |a| |x| per row
         x = torch.from_numpy(xh).cuda()
         H = pkg.DeviceMatrix.from_csc(M)
         # CSR-stream: rows longer than one 512-entry LDS chunk are summed by a wavefront tree (documented exception
         # to the reference order): exact comparison only when no row is that long
         lens = np.diff(O.transpose(A)[2])
         short = bool(lens.max(initial=0) <= 512)
+        # 2 gamma_n scale per row, y = A x and y <- A x + y0; / (1 - gamma_n): sabs itself is a rounded sum
+        bounds = []
+        for n, scale in ((lens, sabs), (lens + 1, sabs + np.abs(y0))):
+            g = n * U / (1.0 - n * U)
+            bounds.append(2.0 * g * scale / (1.0 - g))
         plans = [("stream", lambda: H.set_variant(1)), ("stream4", lambda: H.set_variant(4)),
                  ("default", lambda: (H.set_variant(0), H.optimize()))]
 
@@ -95,6 +108,14 @@ def main():
                 H.build_panel(P, w if P else 0, 0, form)
                 H.set_variant(16)
             plans.append(("panel%d" % form, panel))
+
+        def rounds(case=case):
+            g = np.random.default_rng([seed, case])   # its own generator: the shared one draws what it drew before
+            P = int(g.choice([0, 64, 777, 4096, 20479]))
+            w = int(g.choice([0, 4, 9, 13, 17]))
+            H.build_panel(P, w if P else 0, int(g.choice([0, 3, 4, 5, 6])), D.PANEL_FORM_ROUNDS)
+            H.set_variant(16)
+        plans.append(("rounds", rounds))
         for name, plan in plans:
             try:
                 plan()
@@ -109,7 +130,7 @@ def main():
                 torch.cuda.synchronize()
                 launches += 1
                 got, want = y.cpu().numpy(), (refa if acc else ref)
-                ok = np.array_equal(got, want) if exact else bool(np.all(np.abs(got - want) <= 1e-13 * np.maximum(scale, 1e-300) * max(1, len(rows))))
+                ok = np.array_equal(got, want) if exact else bool(np.all(np.abs(got - want) <= bounds[acc]))
                 if not ok:
                     bad += 1
                     print("case %d %s acc=%d: nr=%d nc=%d nnz=%d kind=%d ints=%d: max diff %.3e" %
